@@ -6,15 +6,19 @@ SwiGLU 1536; window 600, patch 25 -> N=6144 tokens; 2-block perceiver with 32 qu
 batch 32 x T=600 x 256 electrodes, bf16 compute / fp32 masters.  One step = forward + backward + (DP gradient
 all-reduce) + clip_grad_value_ + AdamW over one synthetic batch already resident in HBM.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs if --dump-outputs is given and prints the line.
+--full adds the side measurements after the timed steps: the roofline of the attention kernels and the kernel-family timers (HIP
+events inside the timed steps), the live bf16-vs-reference parity check, the other BASELINE configurations and the CPU baseline.
 
 N > 1: either launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...` (RANK / LOCAL_RANK /
 WORLD_SIZE in the environment), or plain `python bench.py --gpus N`, in which case this process starts that launcher itself as a
 CHILD process before anything touches the GPU, relays rank 0's JSON line and exits with the child's code.  One rank per GPU, RCCL.
 
-Prints ONE JSON line on rank 0.  `value` = total frames/s of the whole job (frames = B*T input time-steps).
-`roofline` is for the dominant kernel family (measured live with HIP events on the launch stream);
-`cpu_baseline` times the CPU oracle (oracle/, a port of the reference's PyTorch path) on this box's host cores.
+Prints ONE JSON line on rank 0.  `value` = total frames/s of the whole job (frames = B*T input time-steps), `ms_per_step` = the
+time of one timed step.  With --full: `roofline` is for the dominant kernel family (measured live with HIP events on the launch
+stream); `cpu_baseline` times the CPU oracle (oracle/, a port of the reference's PyTorch path) on this box's host cores.
 """
 from __future__ import annotations
 
@@ -377,6 +381,32 @@ def other_configs(dev, steps=10, warmup=3):
     return out
 
 
+DUMP_BYTES = 60 << 20            # parameter share of the --dump-outputs budget (64 MB in all)
+DUMP_SEED = 2024
+
+
+def dump_outputs(out_dir, model, loss):
+    """What a caller of the timed path holds after its last step: the loss train_step returned (loss.npy) and the updated fp32
+    master parameters (param.<name>.npy).  A parameter larger than the per-parameter cap is written as a fixed seeded sample of its
+    flattened elements (sorted indices); the cap is the largest power-of-two fraction of the biggest parameter that keeps all
+    parameters within DUMP_BYTES.  Same arguments -> same inputs, same sample: two builds compare file for file."""
+    import numpy as np
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    params = list(model.named_parameters())
+    sizes = [p.numel() for _, p in params]
+    cap = max(sizes)
+    while sum(min(n, cap) for n in sizes) * 4 > DUMP_BYTES:
+        cap //= 2
+    np.save(out_dir / "loss.npy", np.asarray(loss.detach().float().cpu().numpy(), dtype=np.float32))
+    for name, p in params:
+        flat = p.detach().float().flatten()
+        if flat.numel() > cap:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(flat.numel(), cap, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        np.save(out_dir / f"param.{name}.npy", flat.cpu().numpy().astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -385,6 +415,9 @@ def main():
     ap.add_argument("--batch", type=int, default=32, help="per-GPU batch")
     ap.add_argument("--dtype", default="bf16")
     ap.add_argument("--head", default="l1", choices=["l1", "ce"], help="l1: the headline workload; ce: cfg2's CE-head variant (25 tokens, V = 50257)")
+    ap.add_argument("--full", action="store_true", help="also the side measurements: kernel-family timers + roofline, live parity, "
+                    "the other BASELINE configurations, the CPU baseline (the --no-* switches below leave single ones out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps write the last step's loss and updated parameters as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-timers", action="store_true")
     ap.add_argument("--no-other-configs", action="store_true", help="skip the live timing of BASELINE configs[4] (SimpleMAE, B = 32 / 256) and configs[0] (Franky)")
@@ -392,6 +425,8 @@ def main():
     ap.add_argument("--all-timers", action="store_true", help="HIP-event timing of every kernel family (default: the roofline kernel family only)")
     ap.add_argument("--dry-run", action="store_true", help="launcher + rendezvous only, gloo on the CPU (no GPU work)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(self_launch(args))
@@ -445,7 +480,7 @@ def main():
         tu.train_step(model, pool[step % 2], opt, step, tcfg, sched)
         step += 1
     sync()
-    if not args.no_timers:
+    if args.full and not args.no_timers:
         K.TIMERS = {}
         K.TIMER_PREFIX = None if args.all_timers else "attn_"    # ~2000 event pairs per step cost ~1.2 ms; the roofline needs attention only
     t0 = time.perf_counter()
@@ -460,40 +495,13 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax)
     assert torch.isfinite(loss).item(), "loss diverged"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, loss)
     dp = dp_report(opt.sync, opt.arena, dev, args.steps) if world > 1 else None
 
     if rank == 0:
         frames = B * T * world * args.steps
         value = frames / dt
-        fpf = FLOP_PER_FRAME_CE if args.head == "ce" else FLOP_PER_FRAME
-        fams = {}
-        for name, evs in (timers or {}).items():
-            ms = [a.elapsed_time(b) for a, b in evs]
-            fams[name] = (sum(ms), len(ms))
-        roof = None
-        enc = {n: v for n, v in fams.items() if n.startswith("attn_") and ":%dx6x6144x6144x64" % B in n}
-        detail = {}
-        for n, (tot, cnt) in sorted(fams.items(), key=lambda kv: -kv[1][0])[:8]:
-            detail[n] = {"ms_total_per_step": round(tot / args.steps, 3), "launches_per_step": cnt // args.steps}
-        if enc:
-            name, (tot, cnt) = max(enc.items(), key=lambda kv: kv[1][0])
-            bwd = name.startswith("attn_bwd")
-            fl = attn_flops(B, 6, 6144, 6144, 64, 256, bwd)
-            avg_s = tot / cnt / 1e3
-            traffic, traffic_src = None, None
-            try:   # HBM bytes per call from the newest committed rocprofv3 PMC passes (FETCH_SIZE x2 corrected + WRITE_SIZE)
-                tpath = _latest_profile("pmc_traffic.json")
-                pm = json.load(open(tpath))
-                traffic = pm["fk_attn_bwd_bytes_per_call"] if bwd else None
-                traffic_src = f"profiles/{tpath.name}, builder-run rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes (not measured in this run)"
-            except Exception:
-                pass
-            roof = {"kernel": "fk_attn_bwd (attn_bwd_dq [+ delta] and attn_bwd_dkdv launches of one call)" if bwd else "fk_attn_fwd",
-                    "bound": "mfma", "achieved": round(fl / avg_s / 1e12, 2), "peak": MFMA_PEAK_BF16 / 1e12,
-                    "unit": "TFLOP/s", "frac": round(fl / avg_s / MFMA_PEAK_BF16, 4), "traffic": traffic,
-                    "traffic_source": traffic_src,
-                    "traffic_note": "HBM bytes per call; algorithmic bytes 1.21e9 with every tensor counted once; the two deterministic kernels (dQ, dK/dV) each have to read Q, K, V, dO, so their compulsory traffic is 1.82e9",
-                    "flops_per_launch": fl, "avg_launch_ms": round(avg_s * 1e3, 3)}
         out = {
             "metric": "neural frames/sec (train fwd+bwd+AdamW, whole job)", "value": round(value, 1), "unit": "frames/s",
             "n_gpus": world, "world": world, "rccl": (".".join(map(str, torch.cuda.nccl.version())) if world > 1 else None),
@@ -503,39 +511,75 @@ def main():
                                    + ("L1 head" if args.head == "l1" else "CE head (25 tokens, V=50257, fused head loss)") + "; "
                                    "fwd+bwd+clip+AdamW", "per_gpu_batch": B, "global_batch": B * world, "frames_T": T,
                        "electrodes": Cn, "parallelism": f"dp{world}", "weights": "random-init (seed 42)"},
-            "roofline": roof,
+            "dp": dp, "nccl_max_nchannels": os.environ.get("NCCL_MAX_NCHANNELS") if world > 1 else None,
+            "loss": round(float(loss), 5),
+        }
+        if args.full:
+            out.update(full_report(args, B, world, value, timers))
+            # the side legs never cost the headline line: a failure is reported in its block
+            if world == 1 and args.dtype == "bf16" and not args.no_parity:      # N = 1 only, like cpu_baseline: the other ranks of a DP run do not wait for it
+                try:
+                    out["parity"] = parity_live(dev)
+                except Exception as e:
+                    out["parity"] = {"error": f"{type(e).__name__}: {str(e)[:300]}"}
+            if world == 1 and not args.no_other_configs:
+                del model, opt, pool
+                torch.cuda.empty_cache()
+                try:
+                    out["other_configs"] = other_configs(dev)
+                except Exception as e:
+                    out["other_configs"] = {"error": f"{type(e).__name__}: {str(e)[:300]}"}
+                import frankenstein_amd as fa
+                fa.set_compute_dtype(args.dtype)
+            if world == 1 and not args.no_cpu_baseline:
+                try:
+                    out["cpu_baseline"] = cpu_baseline()
+                except Exception as e:
+                    out["cpu_baseline"] = {"error": f"{type(e).__name__}: {str(e)[:300]}"}
+        print(json.dumps(out), flush=True)
+    if world > 1:
+        dist.destroy_process_group()
+
+
+def full_report(args, B, world, value, timers):
+    """--full: the roofline of the dominant attention launch (HIP events inside the timed steps), the whole step against the MFMA
+    peak, the costliest kernel families"""
+    fpf = FLOP_PER_FRAME_CE if args.head == "ce" else FLOP_PER_FRAME
+    fams = {}
+    for name, evs in (timers or {}).items():
+        ms = [a.elapsed_time(b) for a, b in evs]
+        fams[name] = (sum(ms), len(ms))
+    roof = None
+    enc = {n: v for n, v in fams.items() if n.startswith("attn_") and ":%dx6x6144x6144x64" % B in n}
+    detail = {}
+    for n, (tot, cnt) in sorted(fams.items(), key=lambda kv: -kv[1][0])[:8]:
+        detail[n] = {"ms_total_per_step": round(tot / args.steps, 3), "launches_per_step": cnt // args.steps}
+    if enc:
+        name, (tot, cnt) = max(enc.items(), key=lambda kv: kv[1][0])
+        bwd = name.startswith("attn_bwd")
+        fl = attn_flops(B, 6, 6144, 6144, 64, 256, bwd)
+        avg_s = tot / cnt / 1e3
+        traffic, traffic_src = None, None
+        try:   # HBM bytes per call from the newest committed rocprofv3 PMC passes (FETCH_SIZE x2 corrected + WRITE_SIZE)
+            tpath = _latest_profile("pmc_traffic.json")
+            pm = json.load(open(tpath))
+            traffic = pm["fk_attn_bwd_bytes_per_call"] if bwd else None
+            traffic_src = f"profiles/{tpath.name}, builder-run rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes (not measured in this run)"
+        except Exception:
+            pass
+        roof = {"kernel": "fk_attn_bwd (attn_bwd_dq [+ delta] and attn_bwd_dkdv launches of one call)" if bwd else "fk_attn_fwd",
+                "bound": "mfma", "achieved": round(fl / avg_s / 1e12, 2), "peak": MFMA_PEAK_BF16 / 1e12,
+                "unit": "TFLOP/s", "frac": round(fl / avg_s / MFMA_PEAK_BF16, 4), "traffic": traffic,
+                "traffic_source": traffic_src,
+                "traffic_note": "HBM bytes per call; algorithmic bytes 1.21e9 with every tensor counted once; the two deterministic kernels (dQ, dK/dV) each have to read Q, K, V, dO, so their compulsory traffic is 1.82e9",
+                "flops_per_launch": fl, "avg_launch_ms": round(avg_s * 1e3, 3)}
+    return {"roofline": roof,
             "step_roofline": {"bound": "mfma", "achieved": round(value / world * fpf / 1e12, 2),
                               "mfma_util_pmc": mfma_util_pmc(),
                               "peak": MFMA_PEAK_BF16 / 1e12, "unit": "TFLOP/s",
                               "frac": round(value / world * fpf / MFMA_PEAK_BF16, 4),
                               "note": f"whole step per GPU: frames/s x {fpf / 1e9:.4f} GFLOP/frame (SURVEY §8d)"},
-            "dp": dp, "nccl_max_nchannels": os.environ.get("NCCL_MAX_NCHANNELS") if world > 1 else None,
-            "kernel_families": detail,
-            "loss": round(float(loss), 5),
-        }
-        # the side legs never cost the headline line: a failure is reported in its block
-        if world == 1 and args.dtype == "bf16" and not args.no_parity:      # N = 1 only, like cpu_baseline: the other ranks of a DP run do not wait for it
-            try:
-                out["parity"] = parity_live(dev)
-            except Exception as e:
-                out["parity"] = {"error": f"{type(e).__name__}: {str(e)[:300]}"}
-        if world == 1 and not args.no_other_configs:
-            del model, opt, pool
-            torch.cuda.empty_cache()
-            try:
-                out["other_configs"] = other_configs(dev)
-            except Exception as e:
-                out["other_configs"] = {"error": f"{type(e).__name__}: {str(e)[:300]}"}
-            import frankenstein_amd as fa
-            fa.set_compute_dtype(args.dtype)
-        if world == 1 and not args.no_cpu_baseline:
-            try:
-                out["cpu_baseline"] = cpu_baseline()
-            except Exception as e:
-                out["cpu_baseline"] = {"error": f"{type(e).__name__}: {str(e)[:300]}"}
-        print(json.dumps(out), flush=True)
-    if world > 1:
-        dist.destroy_process_group()
+            "kernel_families": detail}
 
 
 if __name__ == "__main__":

@@ -329,6 +329,18 @@ def test_bench_self_launch_dry_run_world2():
         assert r.returncode == 2 and "GPU(s) visible" in r.stderr and "AssertionError" not in r.stderr
 
 
+def test_bench_options():
+    """--full and --dump-outputs exist; --steps sets the number of timed steps, so a run without any is refused before setup."""
+    import subprocess
+    import sys
+    from pathlib import Path
+    root = Path(__file__).resolve().parents[1]
+    r = subprocess.run([sys.executable, str(root / "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout
+    r = subprocess.run([sys.executable, str(root / "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "--steps must be >= 1" in r.stderr
+
+
 STREAMS = {"dkdv": "attn_dkdv_asm.inc", "dq": "attn_dq_asm.inc", "fwd": "attn_fwd_asm.inc", "dq16": "attn_dq16_asm.inc", "dkdvw": "attn_dkdvw_asm.inc",
            "mlpb": "mlp_bwd_asm.inc"}
 

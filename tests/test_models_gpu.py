@@ -527,7 +527,8 @@ def test_cfg2_b1_bf16_vs_reference(golden):
     """The BENCHMARKED precision at the benchmarked shape (6 layers, d = 384, N = 6144 tokens, B = 1) against the reference's own
     fp32 CPU run: loss within 1e-2 relative, prediction and encoder rows within stated absolute bounds, and every parameter's
     gradient pointing the reference's way (cosine >= 0.99 on the fixture's samples).  The measured numbers go to
-    gpurun_out/parity_cfg2_bf16.json; bench.py measures the same quantities itself in every run (`parity` block, bench.parity_live)."""
+    parity_cfg2_bf16.json in the run's output folder if there is one; `bench.py --full` measures the same quantities itself (`parity`
+    block, bench.parity_live)."""
     import json
     import os
     from frankenstein_amd.models import brainformer as bf
@@ -1105,6 +1106,39 @@ def test_cfg2_full_size_properties():
         assert rel < 2e-2, rel                                    # bf16 activations: split batches round differently
     finally:
         fa.set_compute_dtype("fp32")
+
+
+def test_bench_plain_run_and_dumped_outputs(tmp_path):
+    """A plain `bench.py` run (child processes, small batch) prints the headline line only — no side legs — and --dump-outputs writes
+    the last timed step's loss and updated parameters as float32 .npy files within 64 MB; the same arguments give the same bits."""
+    import json
+    import subprocess
+    import sys
+    from pathlib import Path
+    root = Path(__file__).resolve().parents[1]
+    outs = []
+    for run in range(2):
+        d = tmp_path / f"run{run}"
+        r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "4",
+                            "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        out = json.loads(lines[0])
+        assert out["steps"] == 2 and out["warmup"] == 1 and out["dtype"] == "bf16" and out["higher_is_better"] is True
+        assert out["unit"] == "frames/s" and out["ms_per_step"] > 0
+        assert abs(out["value"] - 4 * 600 / (out["ms_per_step"] / 1e3)) / out["value"] < 1e-2
+        assert not {"roofline", "step_roofline", "kernel_families", "parity", "other_configs", "cpu_baseline"} & set(out)
+        files = sorted(d.glob("*.npy"))
+        assert (d / "loss.npy") in files and len(files) > 100
+        assert sum(f.stat().st_size for f in files) <= 64 << 20
+        arrs = {f.name: np.load(f) for f in files}
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrs.values())
+        assert abs(float(arrs["loss.npy"]) - out["loss"]) < 1e-4
+        outs.append(arrs)
+    assert outs[0].keys() == outs[1].keys()
+    for k in outs[0]:
+        np.testing.assert_array_equal(outs[0][k], outs[1][k], err_msg=k)
 
 
 def test_bf16_odd_shapes_train_steps():

@@ -5,8 +5,8 @@ P=${1:-r04_i}
 O=gpurun_out
 mkdir -p $O
 timeout -k 10 900 python -m pytest tests -m gpu -q > $O/${P}_gpu_tests.log 2>&1; tail -2 $O/${P}_gpu_tests.log
-python bench.py > $O/${P}_bench.log 2>&1; tail -1 $O/${P}_bench.log | cut -c1-330
-python bench.py --head ce --no-cpu-baseline --no-other-configs > $O/${P}_bench_ce.log 2>&1; tail -1 $O/${P}_bench_ce.log | cut -c1-200
+python bench.py --full > $O/${P}_bench.log 2>&1; tail -1 $O/${P}_bench.log | cut -c1-330
+python bench.py --full --head ce --no-cpu-baseline --no-other-configs > $O/${P}_bench_ce.log 2>&1; tail -1 $O/${P}_bench_ce.log | cut -c1-200
 bash tools/profile_step.sh ${P} "round 4" > $O/${P}_profile.out 2>&1; tail -1 $O/${P}_profile.out | cut -c1-200
 bash tools/pmc_step.sh ${P} > $O/${P}_pmc_step.out 2>&1; tail -3 $O/${P}_pmc_step.out
 { echo "== in-tree library"; python tools/gemm_bench.py 5 2>&1 | grep -E "^nt|^tn|sum"; } > $O/${P}_gemm_bench.txt 2>&1; tail -1 $O/${P}_gemm_bench.txt
