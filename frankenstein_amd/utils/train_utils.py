@@ -9,7 +9,8 @@ MI355X-first implementation: all trainable parameters live in ONE flat fp32 aren
 moments), so clip + AdamW + zero_grad is a single HBM-bound kernel launch (fk_adamw_step) and the data-parallel
 gradient exchange is a handful of large contiguous RCCL all-reduces issued from autograd hooks while the
 backward is still running (one process per GPU, torch.distributed 'nccl' = RCCL over xGMI).  No accelerate /
-wandb dependency (accelerate's DDP wrapping, utils/train_utils.py:97-101,122, is what GradSync replaces).
+wandb dependency (accelerate's DDP wrapping, utils/train_utils.py:97-101,122, is what GradSync replaces, and its loader
+sharding what ShardedLoader does).
 """
 from __future__ import annotations
 
@@ -446,13 +447,15 @@ class GraphedTrainStep:
     """The hot loop's forward + backward captured ONCE as a hipGraph and replayed per batch; the update (whose learning
     rate changes every step) runs eagerly after each replay.  For the small configurations (gpt2-nano, SimpleMAE B=32)
     a step is ~300 launches of a few microseconds each and the Python/ctypes launch path, not the GPU, sets the step
-    time; replaying a graph removes it.  Requirements: static batch shape, one process (the gradient exchange is
-    hook-driven and not captured), grad_accum == 1, a forward without host-side randomness.  With the weight-gradient side
-    stream on (FusedAdamW(overlap_wgrad=True)) the dW GEMMs become a parallel branch of the graph.  Same numbers as ``train_step``: the captured kernels are the ones the eager step launches."""
+    time; replaying a graph removes it.  Requirements: static batch shape, grad_accum == 1, a forward without host-side
+    randomness.  With the weight-gradient side stream on (FusedAdamW(overlap_wgrad=True)) the dW GEMMs become a parallel
+    branch of the graph.  Same numbers as ``train_step``: the captured kernels are the ones the eager step launches.
+    Data parallel: no collective is captured — warm-up and capture run with the exchange switched off — and the gradient
+    hooks do not fire on replay, so after each replay GradSync.finish() all-reduces the whole arena (every bucket, SUM, the
+    1/world in the AdamW kernel) before the eager update.  That exchange is exposed (it does not overlap the backward as in
+    ``train_step``); with two ranks each bucket is a + b either way, so the result is the eager step's bit for bit."""
 
     def __init__(self, model, batch, optimizer: FusedAdamW, cfg: TrainConfig, scheduler=None, warmup: int = 2):
-        if _dist_info()[1] != 1:
-            raise RuntimeError("GraphedTrainStep is single-process: the bucketed gradient exchange is not captured")
         if cfg.grad_accum != 1:
             raise RuntimeError("GraphedTrainStep needs grad_accum == 1")
         self.model, self.optimizer, self.cfg = model, optimizer, cfg
@@ -493,6 +496,7 @@ class GraphedTrainStep:
             g['lr'] = lr
         self.graph.replay()
         self.optimizer.mark_touched(self._touched)
+        self.optimizer.sync.enabled = True             # no bucket went out during the replay: finish() exchanges all of them
         self.optimizer.step()
         return self.loss
 
@@ -502,6 +506,28 @@ def _dist_info():
     if dist.is_available() and dist.is_initialized():
         return dist.get_rank(), dist.get_world_size()
     return 0, 1
+
+
+def init_distributed():
+    """The process group of a data-parallel run -> (rank, world, created).  A default group that already exists is used as is
+    (created False).  Otherwise, with WORLD_SIZE > 1 in the environment (torchrun, accelerate.notebook_launcher(...,
+    num_processes=N)): the rank binds its GPU (LOCAL_RANK) before any other GPU call and creates the default group (created True:
+    the caller destroys it), RCCL's defaults being those of bench.dp_env (NCCL_MAX_NCHANNELS=8, HSA_ENABLE_IPC_MODE_LEGACY=0 unless
+    set).  Backend: $FK_DIST_BACKEND, else "nccl" (= RCCL); FK_DIST_BACKEND=gloo lets two ranks share one
+    GPU, which RCCL refuses.  WORLD_SIZE unset or 1: (0, 1, False) without creating a group or touching the GPU."""
+    import torch.distributed as dist
+    if dist.is_available() and dist.is_initialized():
+        return dist.get_rank(), dist.get_world_size(), False
+    if int(os.environ.get("WORLD_SIZE") or 1) <= 1:
+        return 0, 1, False
+    # set before set_device: the HSA runtime reads its variables when it starts, which set_device makes it do
+    os.environ.setdefault("NCCL_MAX_NCHANNELS", "8")
+    os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
+    device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", 0)))
+    torch.cuda.set_device(device)
+    backend = os.environ.get("FK_DIST_BACKEND", "nccl")
+    dist.init_process_group(backend, device_id=device if backend == "nccl" else None)
+    return dist.get_rank(), dist.get_world_size(), True
 
 
 def shard_batch(batch, rank: int, world: int):
@@ -515,6 +541,128 @@ def shard_batch(batch, rank: int, world: int):
     return tuple(t[rank * k:(rank + 1) * k] if torch.is_tensor(t) else t for t in batch)
 
 
+def _n_samples(batch) -> int:
+    for x in batch:
+        if torch.is_tensor(x) and x.dim() > 0:
+            return x.shape[0]
+    for x in batch:
+        if isinstance(x, (list, tuple)):
+            return len(x)
+    raise ValueError("a batch needs a tensor or a list with one entry per sample")
+
+
+def _per_sample(x, n: int) -> bool:
+    """tensors and lists whose leading length is the batch's sample count are split; anything else (None, constants) is shared"""
+    return (torch.is_tensor(x) and x.dim() > 0 and x.shape[0] == n) or (isinstance(x, (list, tuple)) and len(x) == n)
+
+
+def _append_samples(x, first, idx: List[int], n: int):
+    """field x of an n-sample batch followed by samples `idx` of the same field of the epoch's first batch"""
+    if not _per_sample(x, n):
+        return x
+    if torch.is_tensor(x):
+        return torch.cat([x, first[torch.tensor(idx, device=first.device)].to(x.device)])
+    out = list(x) + [first[i] for i in idx]
+    return tuple(out) if isinstance(x, tuple) else out
+
+
+def _batch_crc(batch) -> int:
+    import zlib
+    crc = 0
+    for x in batch:
+        if torch.is_tensor(x):
+            crc = zlib.crc32(x.detach().cpu().contiguous().reshape(-1).view(torch.uint8).numpy(), crc)
+        elif isinstance(x, (list, tuple)):
+            crc = zlib.crc32(repr(list(x)).encode(), crc)
+    return crc
+
+
+def _check_same_batch(batch) -> None:
+    """every rank holds the same global batch, else raise (one all-reduce of a CRC-32 of its bytes)"""
+    import torch.distributed as dist
+    c = _batch_crc(batch)
+    dev = torch.device("cuda", torch.cuda.current_device()) if dist.get_backend() == "nccl" else torch.device("cpu")
+    t = torch.tensor([c, -c], dtype=torch.int64, device=dev)
+    dist.all_reduce(t, op=dist.ReduceOp.MAX)
+    hi, lo = int(t[0]), -int(t[1])
+    if hi != lo:
+        raise RuntimeError(f"rank {dist.get_rank()}: the ranks' loaders yield different global batches (CRC-32 {c:#010x}, group "
+                           f"min {lo:#010x} max {hi:#010x}); every rank must draw the same shuffled order (same seed, same draws from "
+                           f"the CPU generator before each epoch)")
+
+
+class ShardedLoader:
+    """accelerate's ``prepare(loader)`` with ``split_batches=True, even_batches=True`` (utils/train_utils.py:100,122), done on the
+    host.  The wrapped loader yields GLOBAL batches, the same ones in the same order on every rank (same seed, same draws from the
+    CPU generator: the order a one-process run sees); rank r takes the r-th contiguous slice of each and copies only that slice to
+    `device` (non_blocking: asynchronous when the loader pins memory).  A batch smaller than the global batch (an epoch's last) is
+    first completed with the epoch's first samples, cycled if the epoch has fewer (accelerate's BatchSamplerShard).  The global
+    batch is the loader's (or its batch sampler's) `batch_size`, else the size of each epoch's first batch.  With a process group,
+    a checksum of each epoch's first global batch is compared across the ranks, and a mismatch raises instead of training on
+    misaligned shards.  World 1: the loader's batches as they come, moved to `device`.  rank / world default to the process
+    group's."""
+
+    def __init__(self, loader, rank: Optional[int] = None, world: Optional[int] = None, device=None):
+        import torch.distributed as dist
+        r, w = _dist_info()
+        self.loader, self.device = loader, device
+        self.rank = r if rank is None else int(rank)
+        self.world = w if world is None else int(world)
+        assert 0 <= self.rank < self.world, (self.rank, self.world)
+        self.check = self.world > 1 and dist.is_available() and dist.is_initialized()
+        bs = getattr(loader, "batch_size", None)
+        if bs is None:                                   # a DataLoader built from a batch_sampler
+            bs = getattr(getattr(loader, "batch_sampler", None), "batch_size", None)
+        self.batch_size = bs if isinstance(bs, int) else None
+        if self.world > 1 and self.batch_size is not None and self.batch_size % self.world:
+            raise ValueError(f"split_batches: the global batch ({self.batch_size}) must be a multiple of the world size ({self.world})")
+
+    def __len__(self):
+        return len(self.loader)
+
+    def _to_device(self, batch):
+        if self.device is None:
+            return batch
+        return tuple(x.to(self.device, non_blocking=True) if torch.is_tensor(x) else x for x in batch)
+
+    def __iter__(self):
+        if self.world == 1:
+            for batch in self.loader:
+                yield self._to_device(tuple(batch))
+            return
+        first, B = None, self.batch_size
+        for batch in self.loader:
+            batch = tuple(batch)
+            n = _n_samples(batch)
+            if first is None:
+                first, B = batch, B or n
+                if B % self.world:
+                    raise ValueError(f"split_batches: the global batch ({B}) must be a multiple of the world size ({self.world})")
+                if self.check:
+                    _check_same_batch(batch)
+            if n > B:
+                raise ValueError(f"a batch of {n} samples from a loader whose global batch is {B}")
+            if n < B:
+                idx = [i % _n_samples(first) for i in range(B - n)]
+                batch = tuple(_append_samples(x, f, idx, n) for x, f in zip(batch, first))
+            k = B // self.world
+            lo = self.rank * k
+            yield self._to_device(tuple(x[lo:lo + k] if _per_sample(x, B) else x for x in batch))
+
+
+def mean_val_loss(losses) -> float:
+    """The validation loss of run_train_model from the per-batch losses of this rank's shards: each batch's loss averaged across
+    the ranks (all-reduce), then the batches' mean — for a mean-reduced loss on equal shards the one-process value, so the best
+    checkpoint does not depend on the world size."""
+    v = torch.stack([x.detach().float().reshape(()) for x in losses])
+    world = _dist_info()[1]
+    if world > 1:
+        import torch.distributed as dist
+        dist.all_reduce(v, op=dist.ReduceOp.SUM)
+        v = v / world
+    return float(v.mean())
+
+
 def save_model(model, path) -> None:
     """safetensors checkpoint with the reference's key names (utils/train_utils.py:172).  Parameters are views into the
     flat arena, which safetensors refuses to serialise as-is (shared storage), so tensors are cloned first."""
@@ -524,29 +672,44 @@ def save_model(model, path) -> None:
 
 
 def run_train_model(model, datasets, config, project_name='transformer', save_folder=Path('logs'), logger=None):
-    """Same contract as the reference: trains until max_steps, evaluates every eval_interval on the main process and
-    saves the best model as safetensors.  Launch one process per GPU (torchrun) for data parallelism."""
+    """Same contract as the reference (utils/train_utils.py:93-185): trains until max_steps, evaluates every eval_interval and
+    saves the best model as safetensors.  Data parallel when launched one process per GPU (torchrun, or
+    accelerate.notebook_launcher(run_train_model, args, num_processes=N)): init_distributed() creates the process group and it is
+    destroyed on return (a group the caller made is used and left alone); the loaders' global batches are split on the host
+    (ShardedLoader: accelerate's split_batches=True, even_batches=True); every rank evaluates its shard of each validation batch
+    and the losses are averaged across the ranks (mean_val_loss), so the validation loss and the best checkpoint do not depend on
+    the world size; rank 0 alone prints, logs and writes the checkpoint, and the ranks meet at a barrier after each evaluation."""
+    import torch.distributed as dist
+    rank, world, created = init_distributed()
+    try:
+        return _train_loop(model, datasets, config, save_folder, logger, rank, world)
+    finally:
+        if created:
+            dist.destroy_process_group()
+
+
+def _train_loop(model, datasets, config, save_folder, logger, rank: int, world: int):
     import safetensors.torch
+    import torch.distributed as dist
     torch.manual_seed(42)
-    rank, world = _dist_info()
     device = torch.device('cuda', int(os.environ.get('LOCAL_RANK', 0)))
     torch.cuda.set_device(device)
     E.set_compute_dtype('bf16' if config.mixed_precision else 'fp32')
     save_folder = Path(save_folder) / config.exp_name
-    save_folder.mkdir(parents=True, exist_ok=True)
+    if rank == 0:
+        save_folder.mkdir(parents=True, exist_ok=True)
     train_dataset, val_dataset = datasets
     train_loader, val_loader = prepare_data_loaders(train_dataset, val_dataset, config)
+    train_loader, val_loader = ShardedLoader(train_loader, rank, world, device), ShardedLoader(val_loader, rank, world, device)
     model.to(device).float()
     optimizer = FusedAdamW(model, lr=config.learning_rate, weight_decay=config.weight_decay, grad_clip=config.grad_clip)
     scheduler = init_lr_scheduler(config)
-    to_dev = lambda b: tuple(t.to(device, non_blocking=True) if torch.is_tensor(t) else t for t in b)
     overall_step, best_val = 0, float('inf')
     accum = GradAccumulation(config.grad_accum)
     done = False
     while not done:
         n_batches = len(train_loader)
         for i_batch, batch in enumerate(train_loader):
-            batch = shard_batch(to_dev(batch), rank, world)
             loss = train_step(model, batch, optimizer, overall_step, config, scheduler,
                               sync=accum.sync(end_of_loader=i_batch == n_batches - 1))
             overall_step += 1
@@ -554,26 +717,27 @@ def run_train_model(model, datasets, config, project_name='transformer', save_fo
                 print('*', end='')
                 if logger is not None:
                     logger({'train/loss': float(loss), 'lr': optimizer.param_groups[0]['lr']}, overall_step)
-            if overall_step % config.eval_interval == 0 and rank == 0:
+            if overall_step % config.eval_interval == 0:
                 model.eval()
-                vals = []
                 with torch.no_grad():
-                    for vb in val_loader:
-                        inputs, labels, date_info = to_dev(vb)
-                        vals.append(model(inputs, labels, date_info)[0].float())
-                mean_val = float(torch.stack(vals).mean())
-                print(f"overall_steps {overall_step}: {float(loss)}")
-                print(f"val loss: {mean_val}")
-                if logger is not None:
-                    logger({'val/loss': mean_val}, overall_step)
-                if mean_val < best_val:
+                    mean_val = mean_val_loss([model(inputs, labels, date_info)[0] for inputs, labels, date_info in val_loader])
+                if rank == 0:
+                    print(f"overall_steps {overall_step}: {float(loss)}")
+                    print(f"val loss: {mean_val}")
+                    if logger is not None:
+                        logger({'val/loss': mean_val}, overall_step)
+                if mean_val < best_val:                 # the same value on every rank (all-reduced)
                     best_val = mean_val
-                    path = save_folder / f"step_{overall_step}_loss_{mean_val:.4f}.safetensors"
-                    save_model(model, path)
-                    print('saved model: ', path.name)
+                    if rank == 0:
+                        path = save_folder / f"step_{overall_step}_loss_{mean_val:.4f}.safetensors"
+                        save_model(model, path)
+                        print('saved model: ', path.name)
+                if world > 1:
+                    dist.barrier()                      # no rank runs ahead of rank 0's checkpoint
                 model.train()
             if overall_step > config.max_steps:
-                print('Complete training')
+                if rank == 0:
+                    print('Complete training')
                 done = True
                 break
     return model
