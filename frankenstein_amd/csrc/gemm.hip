@@ -1587,6 +1587,12 @@ static int launch_nt(const char* name, const void* A, int64_t lda, const void* B
   FK_CHECK_ARG(M > 0 && N > 0 && K > 0, "%s: empty problem M=%lld N=%lld K=%lld", name, (long long)M, (long long)N, (long long)K);
   FK_CHECK_ARG(M < (1LL << 31) && N < (1LL << 31) && K < (1LL << 31), "%s: dims must fit int32", name);
   FK_CHECK_ARG(K % vec == 0 && lda % vec == 0 && ldb % vec == 0, "%s: K/lda/ldb must be multiples of %d", name, vec);
+  // every buffer's leading dimension covers its row (a single row never uses its stride): C has 2N columns in mode 2 (the dh13 buffer),
+  // the aux buffer N / 2 in mode 1 (G) and 2N in mode 2 (H13)
+  const int64_t ccols = mode == 2 ? 2 * N : N, auxcols = mode == 1 ? N / 2 : (mode == 2 ? 2 * N : 0);
+  FK_CHECK_ARG((M == 1 || (lda >= K && ldc >= ccols && ldaux >= auxcols && (!residual || res_rows == 1 || ldr >= N))) && (N == 1 || ldb >= K),
+               "%s: leading dimensions must cover their rows (lda=%lld ldb=%lld K=%lld, ldc=%lld for %lld columns, aux %lld for %lld)", name,
+               (long long)lda, (long long)ldb, (long long)K, (long long)ldc, (long long)ccols, (long long)ldaux, (long long)auxcols);
   FK_CHECK_ARG(A && B && C, "%s: null pointer", name);
   FK_CHECK_ARG(((uintptr_t)A & 15) == 0 && ((uintptr_t)B & 15) == 0, "%s: A/B must be 16-byte aligned", name);
   const int ovec = 8;   // epilogue handles 8 columns per lane

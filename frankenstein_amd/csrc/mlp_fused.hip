@@ -902,8 +902,10 @@ static bool mu_grid_fills(int64_t M) {
 bool fk_qkv_rope_fused_ok(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, const void* bias, int64_t T, int64_t D, int64_t rot_cols,
                           int64_t q_cols, int dtype) {
   static const bool off = getenv("FK_QKV_FUSED") != nullptr && getenv("FK_QKV_FUSED")[0] == '0';
-  return !off && dtype == FK_BF16 && K == MF_D && D == 64 && N % 64 == 0 && rot_cols % 64 == 0 && q_cols % 64 == 0 && rot_cols <= N && !bias && mu_grid_fills(M) &&
-         M < (1LL << 31) && T > 0 && M % T == 0 && lda % 8 == 0 && ldb % 8 == 0 && ldc % 8 == 0 && 64 * ldb * 2 < (1LL << 32);
+  // anything launch_nt would refuse (an empty problem, a leading dimension shorter than its row) is left to it: this kernel has no checks of its own
+  return !off && dtype == FK_BF16 && K == MF_D && D == 64 && N > 0 && N < (1LL << 31) && N % 64 == 0 && rot_cols % 64 == 0 && q_cols % 64 == 0 && rot_cols <= N && !bias &&
+         mu_grid_fills(M) && M < (1LL << 31) && T > 0 && M % T == 0 && lda % 8 == 0 && ldb % 8 == 0 && ldc % 8 == 0 && lda >= K && ldb >= K && ldc >= N &&
+         64 * ldb * 2 < (1LL << 32);
 }
 int fk_qkv_rope_fused_launch(const void* A, int64_t lda, const void* W, int64_t ldb, void* C, int64_t ldc, int64_t M, int64_t N, const float* table,
                              int64_t table_bs, int64_t T, int64_t pos_off, int64_t rot_cols, int64_t q_cols, int64_t q_off, void* stream) {
@@ -919,8 +921,8 @@ int fk_qkv_rope_fused_launch(const void* A, int64_t lda, const void* W, int64_t 
 // the token-on-the-lane form of fk_gemm_nt_swiglu for the shapes it is built for (called from gemm.hip's entry point)
 bool fk_mlp_up_fused_ok(int64_t M, int64_t H, int64_t K, int64_t lda, int64_t ldb, int64_t ldh, int64_t ldg, int dtype) {
   static const bool off = getenv("FK_MLP_UP_FUSED") != nullptr && getenv("FK_MLP_UP_FUSED")[0] == '0';
-  return !off && dtype == FK_BF16 && K == MF_D && H % 32 == 0 && mu_grid_fills(M) && M < (1LL << 31) && lda % 8 == 0 && ldb % 8 == 0 && ldh % 8 == 0 && ldg % 8 == 0 &&
-         64 * ldb * 2 < (1LL << 32);
+  return !off && dtype == FK_BF16 && K == MF_D && H > 0 && H < (1LL << 30) && H % 32 == 0 && mu_grid_fills(M) && M < (1LL << 31) && lda % 8 == 0 && ldb % 8 == 0 &&
+         ldh % 8 == 0 && ldg % 8 == 0 && lda >= K && ldb >= K && ldh >= 2 * H && ldg >= H && 64 * ldb * 2 < (1LL << 32);      // the rest: launch_nt's refusals
 }
 int fk_mlp_up_fused_launch(const void* A, int64_t lda, const void* W13, int64_t ldb, void* H13, int64_t ldh, void* G, int64_t ldg, int64_t M, int64_t H,
                            void* stream) {

@@ -47,7 +47,9 @@ const char* fk_last_error(void);
  * fk_gemm_nt: C[M,N] = A[M,K] * B[N,K]^T (+ bias[N]) (+ residual[m % res_rows, n]); row-major, ld* in elements.
  *   A,B,bias,residual have `dtype`; C has `out_dtype` (= dtype, or FK_F32).  res_rows = 0 means one residual
  *   row per output row; res_rows = R broadcasts an [R, N] table over rows (the space embedding of
- *   models/brainformer.py:343).  K, lda, ldb multiples of 16 bytes.                                          */
+ *   models/brainformer.py:343).  K, lda, ldb multiples of 16 bytes.  Every leading dimension covers its row
+ *   (lda, ldb >= K, ldc >= N, ldr >= N; the same for the H13 / G / dH13 buffers of the fused calls below): a
+ *   shorter one is refused, whichever kernel the shape would have taken.                                     */
 int fk_gemm_nt(const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc, int64_t M, int64_t N,
                int64_t K, const void* bias, const void* residual, int64_t ldr, int64_t res_rows, int dtype,
                int out_dtype, void* stream);

@@ -68,6 +68,22 @@ def test_argument_validation_needs_no_gpu(built):
     assert rc == -1 and b"out_cols" in lib.fk_last_error()
 
 
+def test_fast_paths_refuse_what_launch_nt_refuses(built):
+    """fk_gemm_nt_rope / fk_gemm_nt_swiglu at a shape that would take the token-on-the-lane kernels (bf16, K = 384, 49 152 rows): an empty
+    problem or a leading dimension shorter than its row is refused on the host like on every other path (tests/test_envelope_gpu.py holds
+    the same calls to "not a byte written" on the GPU)."""
+    from frankenstein_amd import _lib
+    lib = _lib.lib()
+    M, d, N, H = 49152, 384, 1152, 1536
+    rope = lambda n, ldc: lib.fk_gemm_nt_rope(16, d, 16, d, 16, ldc, M, n, d, None, 16, 0, 64, 0, 64, min(768, n), 0, 0, _lib.FK_BF16, None)
+    assert rope(0, N) == -1 and b"empty problem" in lib.fk_last_error()
+    assert rope(N, N - 8) == -1 and b"leading dimensions" in lib.fk_last_error()
+    up = lambda ldh, ldg: lib.fk_gemm_nt_swiglu(16, d, 16, d, 16, ldh, 16, ldg, M, H, d, _lib.FK_BF16, None)
+    assert up(2 * H - 8, H) == -1 and b"leading dimensions" in lib.fk_last_error()
+    assert up(2 * H, H - 8) == -1 and b"leading dimensions" in lib.fk_last_error()
+    assert lib.fk_gemm_nt(16, d - 8, 16, d, 16, N, M, N, d, None, None, 0, 0, _lib.FK_BF16, _lib.FK_BF16, None) == -1 and b"leading dimensions" in lib.fk_last_error()
+
+
 def test_integration_snippet_matches_the_binding():
     """The ctypes example a maintainer would copy from INTEGRATION.md: its argtypes equal _lib.SIGNATURES["fk_attn_fwd"] and the call
     passes exactly that many arguments (the round-1 version of the snippet had drifted from the header)."""
