@@ -47,6 +47,15 @@ int fk_set_error(int code, const char* fmt, ...);
 
 static inline int64_t fk_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// Launch of a kernel that takes one argument struct and more dynamic LDS than the 64 KiB every kernel may have: the kernel's limit is
+// raised on the first launch of each instantiation (once per process and kernel), then it is launched.
+template <auto Kernel, typename Args>
+static inline void fk_launch_lds(dim3 grid, dim3 block, size_t lds, hipStream_t s, const Args& a) {
+  static const bool once = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
+  (void)once;
+  hipLaunchKernelGGL(Kernel, grid, block, lds, s, a);
+}
+
 // ------------------------------------------------------------------------------------------------
 // scalar conversions
 // ------------------------------------------------------------------------------------------------

@@ -16,6 +16,8 @@
 //       16-lane group); the 64-B granule g of row r is stored at granule g ^ (r&3) so the 4 rows of a
 //       block hit different banks.  fp32 fragments use ds_read_b32 (conflict free unswizzled).
 // blockIdx is remapped XCD-aware (xcd_remap) so tiles that share an A row panel share an L2.
+#include <type_traits>
+
 #include "fk_common.h"
 
 namespace {
@@ -410,11 +412,39 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_nt_kernel(NtArgs p) {
   nt_epilogue<T, TO>(p, acc, smem + wave * 16384, m0 + (wave >> 1) * 64, n0 + (wave & 1) * 64, lane, true);
 }
 
+// ------------------------------------------------------------------------------------------------ persistent LDS-DMA kernels
+// Persistent blocks (the grid is a few blocks per CU, not one per tile: at 128x128 the workgroup dispatch rate, not
+// the math, bounded the short-K GEMMs).  Blocks b, b+8, ... share an XCD (round-robin dispatch); XCD x owns the
+// contiguous tile range [x*T/8, (x+1)*T/8) and its blocks walk it round-robin, so concurrently running blocks of an XCD
+// work on neighbouring tiles (same A row panel in that XCD's L2).  Pure speed: any placement is correct.
+// This block's tiles are beg + jb, beg + jb + nbx, ... below end.
+struct TileRange { int jb, nbx, beg, end; };
+FK_DEV TileRange tile_range(int ntiles) {
+  const int nb = gridDim.x, xcd = blockIdx.x & 7, jb = blockIdx.x >> 3, nbx = (nb + 7 - xcd) >> 3;
+  const int q8 = ntiles >> 3, r8 = ntiles & 7;
+  const int t_beg = xcd * q8 + min(xcd, r8), t_end = t_beg + q8 + (xcd < r8 ? 1 : 0);
+  return {jb, nbx, t_beg, t_end};
+}
+
+// image of a k-stage: row r holds RB bytes; its 16-byte chunk c sits at chunk c ^ swz(r) (conflict-free ds_read_b128 down a column)
+template <int RB> FK_DEV int ring_swz(int row) { return RB == 128 ? ((row >> 1) & 7) : ((row >> 2) & 3); }
+template <int RB> FK_DEV int ring_off(int row, int chunk) { return row * RB + ((chunk ^ ring_swz<RB>(row)) << 4); }
+
+// Per-lane source of LDS-DMA request `piece` of an operand tile: one request (1 KiB, global_load_lds_dwordx4) fills the 1024 / RB image
+// rows from piece * 1024 / RB on, a lane its 16-byte chunk of one of them.  The LDS destination of an LDS-DMA is lane-linear, so the
+// XOR swizzle of the image is applied to the SOURCE address (chunk c' of row r is fetched from logical chunk c' ^ swz(r)); reads use
+// nt_off / ring_off unchanged.  The tile starts at row r0 of `base` (leading dimension ld); rows from `lim` on are clamped to the last
+// one (their products are never stored) unless the caller guarantees whole tiles (CLAMP = false).
+template <int RB = ROW_BYTES, bool CLAMP = true>
+FK_DEV const bf16_t* dma_src(const void* base, int r0, int lim, int64_t ld, int piece, int lane) {
+  constexpr int RPI = 1024 / RB, LPR = RB / 16;               // rows, lanes per row of a request
+  const int row = piece * RPI + lane / LPR;
+  return (const bf16_t*)base + (int64_t)(CLAMP ? min(r0 + row, lim - 1) : r0 + row) * ld + ((lane % LPR) ^ ring_swz<RB>(row)) * 8;
+}
+
 // bf16 fast path: operand tiles go global -> LDS directly (global_load_lds_dwordx4, 1 KiB = 8 image rows per wave
 // instruction), no staging registers and no ds_write pass (the ds_write_b128 traffic was what bound the register-staged
-// loop).  The LDS destination of an LDS-DMA is lane-linear, so the XOR swizzle of the image is applied to the per-lane
-// SOURCE address (chunk c' of row r is fetched from logical chunk c' ^ ((r>>1)&7)); reads use nt_off unchanged.
-// Rows beyond M / N are clamped (their products are never stored); needs K % 64 == 0.
+// loop); see dma_src for the swizzle.  Needs K % 64 == 0.
 typedef __attribute__((address_space(3))) void lds_void_t;
 typedef __attribute__((address_space(1))) const void glb_void_t;
 
@@ -426,14 +456,8 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_nt_glds_kernel(NtArgs p) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1, li = lane & 31, lh = lane >> 5;
   const int ntn = (p.N + BN - 1) / BN;
-  const int ntiles = ((p.M + BM - 1) / BM) * ntn;
-  // Persistent blocks (the grid is a few blocks per CU, not one per tile: at 128x128 the workgroup dispatch rate, not
-  // the math, bounded the short-K GEMMs).  Blocks b, b+8, ... share an XCD (round-robin dispatch); XCD x owns the
-  // contiguous tile range [x*T/8, (x+1)*T/8) and its blocks walk it round-robin, so concurrently running blocks of an XCD
-  // work on neighbouring tiles (same A row panel in that XCD's L2).  Pure speed: any placement is correct.
-  const int nb = gridDim.x, xcd = blockIdx.x & 7, jb = blockIdx.x >> 3, nbx = (nb + 7 - xcd) >> 3;
-  const int q8 = ntiles >> 3, r8 = ntiles & 7;
-  const int t_beg = xcd * q8 + min(xcd, r8), t_end = t_beg + q8 + (xcd < r8 ? 1 : 0);
+  const TileRange tr = tile_range(((p.M + BM - 1) / BM) * ntn);
+  const int nbx = tr.nbx, t_end = tr.end;
 
   const T* srcA[4];
   const T* srcB[4];
@@ -441,10 +465,8 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_nt_glds_kernel(NtArgs p) {
     const int m0 = (tile / ntn) * BM, n0 = (tile % ntn) * BN;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const int row = (wave * 4 + j) * 8 + (lane >> 3);
-      const int ch = (lane & 7) ^ ((row >> 1) & 7);
-      srcA[j] = (const T*)p.A + (int64_t)min(m0 + row, p.M - 1) * p.lda + ch * 8;
-      srcB[j] = (const T*)p.B + (int64_t)min(n0 + row, p.N - 1) * p.ldb + ch * 8;
+      srcA[j] = dma_src(p.A, m0, p.M, p.lda, wave * 4 + j, lane);
+      srcB[j] = dma_src(p.B, n0, p.N, p.ldb, wave * 4 + j, lane);
     }
   };
   auto stage = [&](int buf, int k0) {
@@ -456,7 +478,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_nt_glds_kernel(NtArgs p) {
     }
   };
   const int nk = p.K / 64;
-  int tile = t_beg + jb;
+  int tile = tr.beg + tr.jb;
   if (tile < t_end) { set_src(tile); stage(0, 0); }
   for (; tile < t_end; tile += nbx) {
     const int m0 = (tile / ntn) * BM, n0 = (tile % ntn) * BN;
@@ -518,10 +540,8 @@ __global__ __launch_bounds__(NTHREADS, 1) void gemm_nt_glds4_kernel(NtArgs p) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1, li = lane & 31, lh = lane >> 5;
   const int ntn = (p.N + BN - 1) / BN;
-  const int ntiles = ((p.M + BM - 1) / BM) * ntn;
-  const int nb = gridDim.x, xcd = blockIdx.x & 7, jb = blockIdx.x >> 3, nbx = (nb + 7 - xcd) >> 3;
-  const int q8 = ntiles >> 3, r8 = ntiles & 7;
-  const int t_beg = xcd * q8 + min(xcd, r8), t_end = t_beg + q8 + (xcd < r8 ? 1 : 0);
+  const TileRange tr = tile_range(((p.M + BM - 1) / BM) * ntn);
+  const int nbx = tr.nbx, t_end = tr.end;
 
   const T* srcA[4];
   const T* srcB[4];
@@ -529,10 +549,8 @@ __global__ __launch_bounds__(NTHREADS, 1) void gemm_nt_glds4_kernel(NtArgs p) {
     const int m0 = (tile / ntn) * BM, n0 = (tile % ntn) * BN;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const int row = (wave * 4 + j) * 8 + (lane >> 3);
-      const int ch = (lane & 7) ^ ((row >> 1) & 7);
-      srcA[j] = (const T*)p.A + (int64_t)min(m0 + row, p.M - 1) * p.lda + ch * 8;
-      srcB[j] = (const T*)p.B + (int64_t)min(n0 + row, p.N - 1) * p.ldb + ch * 8;
+      srcA[j] = dma_src(p.A, m0, p.M, p.lda, wave * 4 + j, lane);
+      srcB[j] = dma_src(p.B, n0, p.N, p.ldb, wave * 4 + j, lane);
     }
   };
   auto stage = [&](int buf, int k0) __attribute__((always_inline)) {
@@ -549,7 +567,7 @@ __global__ __launch_bounds__(NTHREADS, 1) void gemm_nt_glds4_kernel(NtArgs p) {
     if (nk > 1) stage(1, 64);
     if (nk > 2) stage(2, 128);
   };
-  int tile = t_beg + jb;
+  int tile = tr.beg + tr.jb;
   if (tile < t_end) { set_src(tile); head(); }
   for (; tile < t_end; tile += nbx) {
     const int m0 = (tile / ntn) * BM, n0 = (tile % ntn) * BN;
@@ -604,10 +622,8 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_big_kernel(NtArgs p) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave / WCOLS, wn = wave % WCOLS, li = lane & 31, lh = lane >> 5;
   const int ntn = (p.N + BN_ - 1) / BN_;
-  const int ntiles = ((p.M + BM_ - 1) / BM_) * ntn;
-  const int nb = gridDim.x, xcd = blockIdx.x & 7, jb = blockIdx.x >> 3, nbx = (nb + 7 - xcd) >> 3;
-  const int q8 = ntiles >> 3, r8 = ntiles & 7;
-  const int t_beg = xcd * q8 + min(xcd, r8), t_end = t_beg + q8 + (xcd < r8 ? 1 : 0);
+  const TileRange tr = tile_range(((p.M + BM_ - 1) / BM_) * ntn);
+  const int nbx = tr.nbx, t_end = tr.end;
 
   static_assert(STAGE >= 8 * 8192, "the epilogue stages 8 waves x 8 KiB through the second stage buffer");
   const T* srcA[A_PER_WAVE];
@@ -615,15 +631,9 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_big_kernel(NtArgs p) {
   auto set_src = [&](int tile) {
     const int m0 = (tile / ntn) * BM_, n0 = (tile % ntn) * BN_;
 #pragma unroll
-    for (int j = 0; j < A_PER_WAVE; ++j) {
-      const int row = (wave * A_PER_WAVE + j) * 8 + (lane >> 3);
-      srcA[j] = (const T*)p.A + (int64_t)min(m0 + row, p.M - 1) * p.lda + ((lane & 7) ^ ((row >> 1) & 7)) * 8;
-    }
+    for (int j = 0; j < A_PER_WAVE; ++j) srcA[j] = dma_src(p.A, m0, p.M, p.lda, wave * A_PER_WAVE + j, lane);
 #pragma unroll
-    for (int j = 0; j < B_PER_WAVE; ++j) {
-      const int row = (wave * B_PER_WAVE + j) * 8 + (lane >> 3);
-      srcB[j] = (const T*)p.B + (int64_t)min(n0 + row, p.N - 1) * p.ldb + ((lane & 7) ^ ((row >> 1) & 7)) * 8;
-    }
+    for (int j = 0; j < B_PER_WAVE; ++j) srcB[j] = dma_src(p.B, n0, p.N, p.ldb, wave * B_PER_WAVE + j, lane);
   };
   auto stage = [&](int buf, int k0) {
     char* as = smem + buf * STAGE;
@@ -635,7 +645,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_big_kernel(NtArgs p) {
       __builtin_amdgcn_global_load_lds((glb_void_t*)(srcB[j] + k0), (lds_void_t*)(as + A_BYTES + (wave * B_PER_WAVE + j) * 1024), 16, 0, 0);
   };
   const int nk = p.K / 64;
-  int tile = t_beg + jb;
+  int tile = tr.beg + tr.jb;
   if (tile < t_end) { set_src(tile); stage(0, 0); }
   for (; tile < t_end; tile += nbx) {
     const int m0 = (tile / ntn) * BM_, n0 = (tile % ntn) * BN_;
@@ -695,26 +705,21 @@ template <int BN_, int RB, int NS> struct Ring {
   static constexpr int APW = BM_ * RB / 8192, BPW = BN_ * RB / 8192, PER = APW + BPW;
   static_assert(LDS <= 160 * 1024, "ring does not fit the LDS of a CU");
 };
-// image of a k-stage: row r holds RB bytes; its 16-byte chunk c sits at chunk c ^ swz(r) (conflict-free ds_read_b128 down a column)
-template <int RB> FK_DEV int ring_swz(int row) { return RB == 128 ? ((row >> 1) & 7) : ((row >> 2) & 3); }
-template <int RB> FK_DEV int ring_off(int row, int chunk) { return row * RB + ((chunk ^ ring_swz<RB>(row)) << 4); }
 
 template <typename TO, int BN_, int RB, int NS, int EPI>
 __global__ __launch_bounds__(512, 2) void gemm_nt_ring_kernel(NtArgs p) {
   using T = bf16_t;
   using R = Ring<BN_, RB, NS>;
   constexpr int BM_ = R::BM_, STAGE = R::STAGE, A_BYTES = R::A_BYTES, APW = R::APW, BPW = R::BPW, PER = R::PER;
-  constexpr int BKE = RB / 2, SSTEPS = RB / 32, RPI = 1024 / RB, LPR = RB / 16;   // k elements / k16 steps per stage; rows, lanes per row of a DMA
+  constexpr int BKE = RB / 2, SSTEPS = RB / 32;   // k elements / k16 steps per stage
   constexpr int WCOLS = BN_ / 64, WROWS = 8 / WCOLS, WM = BM_ / WROWS, MT = WM / 32;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave / WCOLS, wn = wave % WCOLS, li = lane & 31, lh = lane >> 5;
   const int ntn = (p.N + BN_ - 1) / BN_;
-  const int ntiles = ((p.M + BM_ - 1) / BM_) * ntn;
-  const int nb = gridDim.x, xcd = blockIdx.x & 7, jb = blockIdx.x >> 3, nbx = (nb + 7 - xcd) >> 3;
-  const int q8 = ntiles >> 3, r8 = ntiles & 7;
-  const int t_beg = xcd * q8 + min(xcd, r8), t_end = t_beg + q8 + (xcd < r8 ? 1 : 0);
+  const TileRange tr = tile_range(((p.M + BM_ - 1) / BM_) * ntn);
+  const int nbx = tr.nbx, t_end = tr.end;
   const int nk = p.K / BKE;
 
   const T* srcA[APW];
@@ -722,18 +727,12 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_ring_kernel(NtArgs p) {
   auto set_src = [&](int tile) {
     const int m0 = (tile / ntn) * BM_, n0 = (tile % ntn) * BN_;
 #pragma unroll
-    for (int j = 0; j < APW; ++j) {
-      const int row = (wave * APW + j) * RPI + lane / LPR;
-      srcA[j] = (const T*)p.A + (int64_t)min(m0 + row, p.M - 1) * p.lda + ((lane % LPR) ^ ring_swz<RB>(row)) * 8;
-    }
+    for (int j = 0; j < APW; ++j) srcA[j] = dma_src<RB>(p.A, m0, p.M, p.lda, wave * APW + j, lane);
 #pragma unroll
-    for (int j = 0; j < BPW; ++j) {
-      const int row = (wave * BPW + j) * RPI + lane / LPR;
-      srcB[j] = (const T*)p.B + (int64_t)min(n0 + row, p.N - 1) * p.ldb + ((lane % LPR) ^ ring_swz<RB>(row)) * 8;
-    }
+    for (int j = 0; j < BPW; ++j) srcB[j] = dma_src<RB>(p.B, n0, p.N, p.ldb, wave * BPW + j, lane);
   };
   // issue cursor of the stage stream: (itile, ikt) is the next stage to fetch
-  int itile = t_beg + jb, ikt = 0;
+  int itile = tr.beg + tr.jb, ikt = 0;
   if (itile < t_end) set_src(itile);
   // The PER requests of a stage are issued in SSTEPS parts, one behind the MFMAs of every k16-step of the stage being computed (part
   // < 0: all at once).  Issued together right after the barrier, the 48 requests of the eight waves queue up at the CU's one address unit
@@ -761,7 +760,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_ring_kernel(NtArgs p) {
 #pragma unroll
   for (int s = 0; s < NS - 1; ++s) issue(s, -1);
   int slot = 0;                                     // ring slot of the stage being computed
-  for (int tile = t_beg + jb; tile < t_end; tile += nbx) {
+  for (int tile = tr.beg + tr.jb; tile < t_end; tile += nbx) {
     const int m0 = (tile / ntn) * BM_, n0 = (tile % ntn) * BN_;
     const bool last_tile = tile + nbx >= t_end;
     f32x16 acc[MT][2];
@@ -836,11 +835,23 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_ring_kernel(NtArgs p) {
   }
 }
 
-// 256 x 256 tile with full-line (128-B) requests: three slots do not fit (3 x 64 KiB), so the operands get rings of different depth,
-// A (activations, streamed from HBM) three 32-KiB slots and B (weights, L2-resident) two.  Per step the wave issues B(g+1) and then
-// A(g+2); the wait before stage g is vmcnt(APW): everything but the 4 newest instructions, i.e. all of A(g) and B(g), has landed
-// and A(g+1) stays in flight across the barrier, so the memory pipe never drains.  The epilogue stages through the A and B slots
-// just computed (4 waves each).  LDS = 96 + 64 KiB.
+// Dual-ring kernels: 256-row tiles with full-line (128-B) requests.  Three whole stages do not fit the LDS (3 x 64 KiB), so the operands
+// get rings of different depth: A (activations, streamed from HBM) three 32-KiB slots, B (weights, L2-resident) two.  Two issue cursors
+// walk the same stage stream, A two stages ahead of the compute and B one.  Per step the wave issues B(g+1) and then A(g+2), B in the
+// gaps behind the first two k16-steps and A behind the last two - the order the counted wait relies on - instead of all of them right
+// after the barrier (measured -1.5...-2 % on the 256 x 128 kernel, +-0 here).  The wait before stage g is vmcnt(APW): everything but the
+// 4 newest instructions, i.e. all of A(g) and B(g), has landed and A(g+1) stays in flight across the barrier, so the memory pipe never
+// drains.  The epilogue stages through the A and B slots just computed, 8 KiB per wave.  The protocol is written twice, once per geometry
+// (a shared body behind the two kernel names changed what hipcc made of both main loops, so they share tile_range and dma_src only):
+//                          gemm_nt_ring2_kernel                       gemm_nt_ring192_kernel
+//   route                  N % 256 == 0, or N % 128 == 0 from 1024    N = 384 / 768, plain / bias / residual epilogue only
+//   tile                   256 x 256                                  256 x 192 (N = 384: two column tiles, not three of 128)
+//   B slot, requests/wave  32 KiB, 4, issued as 2 + 2                 24 KiB, 3, issued as 1 + 2
+//   waves, tiles per wave  2 x 4, acc[4][2] (128 x 64)                8 x 1, acc[6] (32 x 192: three 64-column sweeps)
+//   B rows                 clamped to N - 1                           N % 192 == 0 by the route: no clamp in the hot loop
+//   staging                4 waves in the A slot, 4 in the B slot     4 + 3, the eighth in a spare 8 KiB above the rings
+//   residual at EPI == 0   read in the sweep                          fetched before the staging writes (nt_epilogue PRE_RES)
+//   LDS                    R2_LDS = 96 + 64 KiB                       R192_LDS = 96 + 48 + 8 KiB
 constexpr int R2_A = 256 * ROW_BYTES, R2_LDS = 5 * R2_A;
 static_assert(R2_LDS <= 160 * 1024, "LDS of a CU");
 
@@ -855,10 +866,8 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_ring2_kernel(NtArgs p) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 2, wn = wave & 3, li = lane & 31, lh = lane >> 5;
   const int ntn = (p.N + BN_ - 1) / BN_;
-  const int ntiles = ((p.M + BM_ - 1) / BM_) * ntn;
-  const int nb = gridDim.x, xcd = blockIdx.x & 7, jb = blockIdx.x >> 3, nbx = (nb + 7 - xcd) >> 3;
-  const int q8 = ntiles >> 3, r8 = ntiles & 7;
-  const int t_beg = xcd * q8 + min(xcd, r8), t_end = t_beg + q8 + (xcd < r8 ? 1 : 0);
+  const TileRange tr = tile_range(((p.M + BM_ - 1) / BM_) * ntn);
+  const int nbx = tr.nbx, t_end = tr.end;
   const int nk = p.K / 64;
 
   const T* srcA[APW];
@@ -866,25 +875,17 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_ring2_kernel(NtArgs p) {
   auto set_a = [&](int tile) {
     const int m0 = (tile / ntn) * BM_;
 #pragma unroll
-    for (int j = 0; j < APW; ++j) {
-      const int row = (wave * APW + j) * 8 + (lane >> 3);
-      srcA[j] = (const T*)p.A + (int64_t)min(m0 + row, p.M - 1) * p.lda + ((lane & 7) ^ ((row >> 1) & 7)) * 8;
-    }
+    for (int j = 0; j < APW; ++j) srcA[j] = dma_src(p.A, m0, p.M, p.lda, wave * APW + j, lane);
   };
   auto set_b = [&](int tile) {
     const int n0 = (tile % ntn) * BN_;
 #pragma unroll
-    for (int j = 0; j < BPW; ++j) {
-      const int row = (wave * BPW + j) * 8 + (lane >> 3);
-      srcB[j] = (const T*)p.B + (int64_t)min(n0 + row, p.N - 1) * p.ldb + ((lane & 7) ^ ((row >> 1) & 7)) * 8;
-    }
+    for (int j = 0; j < BPW; ++j) srcB[j] = dma_src(p.B, n0, p.N, p.ldb, wave * BPW + j, lane);
   };
   // two issue cursors over the same stage stream: A runs two stages ahead of the compute, B one
-  int atile = t_beg + jb, akt = 0, btile = atile, bkt = 0;
+  int atile = tr.beg + tr.jb, akt = 0, btile = atile, bkt = 0;
   if (atile < t_end) { set_a(atile); set_b(btile); }
-  // half = 0 / 1: the first / second two requests of the stage, -1: all four (the steps of the loop issue B in the gaps behind the first
-  // two k16-steps and A behind the last two — the order the counted wait relies on — instead of all eight right after the barrier;
-  // measured -1.5...-2 % on the 256 x 128 kernel, +-0 here)
+  // half = 0 / 1: the first / second two requests of the stage, -1: all four
   auto issue_a = [&](int slot, int half) __attribute__((always_inline)) {
     if (atile >= t_end) return;
     char* as = aslot(slot);
@@ -907,7 +908,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_ring2_kernel(NtArgs p) {
   issue_b(0, -1);
   issue_a(1, -1);
   int sa = 0, sb = 0;                               // slots of the stage being computed
-  for (int tile = t_beg + jb; tile < t_end; tile += nbx) {
+  for (int tile = tr.beg + tr.jb; tile < t_end; tile += nbx) {
     const int m0 = (tile / ntn) * BM_, n0 = (tile % ntn) * BN_;
     const bool last_tile = tile + nbx >= t_end;
     f32x16 acc[MT][2];
@@ -959,11 +960,9 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_ring2_kernel(NtArgs p) {
   }
 }
 
-// 256 x 192 tile for N = 384 (two column tiles instead of three 128-wide ones).  These launches are bound by the bytes that go through
-// LDS-DMA (57 GB/s per CU out of L2, 24 out of HBM): a 256 x 128 tile moves 384 rows per k-stage for 256 x 128 outputs and the
-// three column tiles fetch the same A rows three times; 256 x 192 moves 448 rows for 256 x 192 outputs and fetches A twice: 22 % fewer
-// bytes for the same product.  Rings as in the 256 x 256 kernel (A: three 32-KiB slots, two stages ahead; B: two 24-KiB slots, one ahead;
-// counted wait vmcnt(4)); every wave owns 32 rows and all 192 columns (6 accumulator tiles), so the epilogue is three 64-column sweeps.
+// 256 x 192 geometry of the table above.  The N = 384 launches are bound by the bytes that go through LDS-DMA (57 GB/s per CU
+// out of L2, 24 out of HBM): a 256 x 128 tile moves 384 rows per k-stage for 256 x 128 outputs and the three column tiles fetch the same A
+// rows three times; 256 x 192 moves 448 rows for 256 x 192 outputs and fetches A twice: 22 % fewer bytes for the same product.
 constexpr int R192_A = 256 * ROW_BYTES, R192_B = 192 * ROW_BYTES, R192_LDS = 3 * R192_A + 2 * R192_B + 8192;
 static_assert(R192_LDS <= 160 * 1024, "LDS of a CU");
 
@@ -978,10 +977,8 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_ring192_kernel(NtArgs p) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int li = lane & 31, lh = lane >> 5;
   const int ntn = p.N / BN_;
-  const int ntiles = ((p.M + BM_ - 1) / BM_) * ntn;
-  const int nb = gridDim.x, xcd = blockIdx.x & 7, jb = blockIdx.x >> 3, nbx = (nb + 7 - xcd) >> 3;
-  const int q8 = ntiles >> 3, r8 = ntiles & 7;
-  const int t_beg = xcd * q8 + min(xcd, r8), t_end = t_beg + q8 + (xcd < r8 ? 1 : 0);
+  const TileRange tr = tile_range(((p.M + BM_ - 1) / BM_) * ntn);
+  const int nbx = tr.nbx, t_end = tr.end;
   const int nk = p.K / 64;
 
   const T* srcA[APW];
@@ -989,20 +986,14 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_ring192_kernel(NtArgs p) {
   auto set_a = [&](int tile) {
     const int m0 = (tile / ntn) * BM_;
 #pragma unroll
-    for (int j = 0; j < APW; ++j) {
-      const int row = (wave * APW + j) * 8 + (lane >> 3);
-      srcA[j] = (const T*)p.A + (int64_t)min(m0 + row, p.M - 1) * p.lda + ((lane & 7) ^ ((row >> 1) & 7)) * 8;
-    }
+    for (int j = 0; j < APW; ++j) srcA[j] = dma_src(p.A, m0, p.M, p.lda, wave * APW + j, lane);
   };
   auto set_b = [&](int tile) {
     const int n0 = (tile % ntn) * BN_;
 #pragma unroll
-    for (int j = 0; j < BPW; ++j) {
-      const int row = (wave * BPW + j) * 8 + (lane >> 3);
-      srcB[j] = (const T*)p.B + (int64_t)(n0 + row) * p.ldb + ((lane & 7) ^ ((row >> 1) & 7)) * 8;
-    }
+    for (int j = 0; j < BPW; ++j) srcB[j] = dma_src<ROW_BYTES, false>(p.B, n0, p.N, p.ldb, wave * BPW + j, lane);   // N % 192 == 0: no clamp
   };
-  int atile = t_beg + jb, akt = 0, btile = atile, bkt = 0;
+  int atile = tr.beg + tr.jb, akt = 0, btile = atile, bkt = 0;
   if (atile < t_end) { set_a(atile); set_b(btile); }
   // part 0 / 1 of a stage's requests (-1: all): B first, A after it - the order the counted wait relies on
   auto issue_a = [&](int slot, int part) __attribute__((always_inline)) {
@@ -1027,7 +1018,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_ring192_kernel(NtArgs p) {
   issue_b(0, -1);
   issue_a(1, -1);
   int sa = 0, sb = 0;
-  for (int tile = t_beg + jb; tile < t_end; tile += nbx) {
+  for (int tile = tr.beg + tr.jb; tile < t_end; tile += nbx) {
     const int m0 = (tile / ntn) * BM_, n0 = (tile % ntn) * BN_;
     const bool last_tile = tile + nbx >= t_end;
     f32x16 acc[NT6];
@@ -1087,48 +1078,40 @@ static unsigned persistent_grid(int64_t nt) {
   return (unsigned)(nt < cap ? nt : cap);
 }
 
-template <typename TO>
-static void launch_ring192(const NtArgs& p, int64_t M, int64_t N, hipStream_t s) {
-  const int64_t nt = fk_cdiv(M, 256) * (N / 192);
-  static bool once = (hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_ring192_kernel<TO, 0>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, R192_LDS) == hipSuccess);
-  (void)once;
-  hipLaunchKernelGGL((gemm_nt_ring192_kernel<TO, 0>), dim3(persistent_grid(nt)), dim3(512), R192_LDS, s, p);
+// The kernels fk_gemm_nt and its fused forms choose between (launch_nt); all but the last need bf16 operands with K % 64 == 0.
+enum NtRoute { NT_RING2, NT_RING192, NT_RING128, NT_BIG, NT_GLDS4, NT_GLDS, NT_STAGED };
+
+// The ring kernels are instantiated per fused epilogue (nt_epilogue's EPI): f(std::integral_constant<int, EPI>) for this call's
+template <typename F> static void with_epi(const NtArgs& p, F f) {
+  if (p.mode == 1) f(std::integral_constant<int, 1>{});
+  else if (p.mode == 2) f(std::integral_constant<int, 2>{});
+  else if (p.rope_table) f(std::integral_constant<int, 3>{});
+  else f(std::integral_constant<int, 0>{});
 }
 
-template <typename TO, int EPI>
-static void launch_ring2_epi(const NtArgs& p, int64_t M, int64_t N, hipStream_t s) {
-  const int64_t nt = fk_cdiv(M, 256) * fk_cdiv(N, 256);
-  static bool once = (hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_ring2_kernel<TO, EPI>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, R2_LDS) == hipSuccess);
-  (void)once;
-  hipLaunchKernelGGL((gemm_nt_ring2_kernel<TO, EPI>), dim3(persistent_grid(nt)), dim3(512), R2_LDS, s, p);
-}
-template <typename TO>
-static void launch_ring2(const NtArgs& p, int64_t M, int64_t N, hipStream_t s) {
-  static const bool generic = getenv("FK_NT_RING2_GENERIC") != nullptr;    // tuning knob: one epilogue body for every mode
-  if (generic) launch_ring2_epi<TO, -1>(p, M, N, s);
-  else if (p.mode == 1) launch_ring2_epi<TO, 1>(p, M, N, s);
-  else if (p.mode == 2) launch_ring2_epi<TO, 2>(p, M, N, s);
-  else if (p.rope_table) launch_ring2_epi<TO, 3>(p, M, N, s);
-  else launch_ring2_epi<TO, 0>(p, M, N, s);
-}
-
-template <typename TO, int BN_, int RB, int NS, int EPI>
-static void launch_ring_epi(const NtArgs& p, int64_t M, int64_t N, hipStream_t s) {
-  using R = Ring<BN_, RB, NS>;
-  const int64_t nt = fk_cdiv(M, R::BM_) * (N / BN_);
-  static bool once = (hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_ring_kernel<TO, BN_, RB, NS, EPI>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, R::LDS) == hipSuccess);
-  (void)once;
-  hipLaunchKernelGGL((gemm_nt_ring_kernel<TO, BN_, RB, NS, EPI>), dim3(persistent_grid(nt)), dim3(512), R::LDS, s, p);
-}
-template <typename TO, int BN_, int RB, int NS>
-static void launch_ring(const NtArgs& p, int64_t M, int64_t N, hipStream_t s) {   // one instantiation per fused epilogue mode
-  if (p.mode == 1) launch_ring_epi<TO, BN_, RB, NS, 1>(p, M, N, s);
-  else if (p.mode == 2) launch_ring_epi<TO, BN_, RB, NS, 2>(p, M, N, s);
-  else if (p.rope_table) launch_ring_epi<TO, BN_, RB, NS, 3>(p, M, N, s);
-  else launch_ring_epi<TO, BN_, RB, NS, 0>(p, M, N, s);
+// launch of the bf16-operand kernel of `route` that writes TO
+template <typename TO> static void launch_nt_route(NtRoute route, const NtArgs& p, int64_t M, int64_t N, hipStream_t s) {
+  const int64_t nwg = fk_cdiv(M, BM) * fk_cdiv(N, BN);
+  const dim3 grid((unsigned)nwg), block(NTHREADS), block8(512);
+  auto tiles256 = [&](int bn) { return dim3(persistent_grid(fk_cdiv(M, 256) * fk_cdiv(N, bn))); };   // persistent grid over 256 x bn tiles
+  switch (route) {
+    case NT_RING2: {
+      static const bool generic = getenv("FK_NT_RING2_GENERIC") != nullptr;    // tuning knob: one epilogue body for every mode
+      if (generic) fk_launch_lds<gemm_nt_ring2_kernel<TO, -1>>(tiles256(256), block8, R2_LDS, s, p);
+      else with_epi(p, [&](auto epi) { fk_launch_lds<gemm_nt_ring2_kernel<TO, decltype(epi)::value>>(tiles256(256), block8, R2_LDS, s, p); });
+      break;
+    }
+    case NT_RING192: fk_launch_lds<gemm_nt_ring192_kernel<TO, 0>>(tiles256(192), block8, R192_LDS, s, p); break;
+    case NT_RING128:
+      with_epi(p, [&](auto epi) { fk_launch_lds<gemm_nt_ring_kernel<TO, 128, 128, 3, decltype(epi)::value>>(tiles256(128), block8, Ring<128, 128, 3>::LDS, s, p); });
+      break;
+    case NT_BIG: fk_launch_lds<gemm_nt_big_kernel<TO, 256>>(tiles256(256), block8, 2 * (256 + 256) * ROW_BYTES, s, p); break;
+    case NT_GLDS4: fk_launch_lds<gemm_nt_glds4_kernel<TO>>(grid, block, G4_LDS, s, p); break;
+    case NT_GLDS:                                          // persistent: 2 blocks per CU (64 KiB LDS each)
+      hipLaunchKernelGGL((gemm_nt_glds_kernel<TO>), dim3((unsigned)(nwg < 512 ? nwg : 512)), block, 4 * TILE_BYTES, s, p);
+      break;
+    case NT_STAGED: hipLaunchKernelGGL((gemm_nt_kernel<bf16_t, TO>), grid, block, 4 * TILE_BYTES, s, p); break;
+  }
 }
 
 // ------------------------------------------------------------------------------------------------ TN
@@ -1607,8 +1590,6 @@ static int launch_nt(const char* name, const void* A, int64_t lda, const void* B
   NtArgs p{A, B, C, bias, residual, lda, ldb, ldc, ldr, res_rows, (int)M, (int)N, (int)K, vec_epi ? 1 : 0, mode, aux, ldaux,
            rope.table, rope.bs, rope.T, rope.off, rope.D, rope.cols, rope.qcols, rope.qoff};
   const int64_t nwg = fk_cdiv(M, BM) * fk_cdiv(N, BN);
-  dim3 grid((unsigned)nwg), block(NTHREADS);
-  const size_t sh = 4 * TILE_BYTES;
   hipStream_t s = (hipStream_t)stream;
   const bool glds = dtype == FK_BF16 && (K % 64 == 0);
   static const bool no_ring = getenv("FK_NT_NO_RING") != nullptr;       // tuning knob: the double-buffered kernels instead
@@ -1618,54 +1599,22 @@ static int launch_nt(const char* name, const void* A, int64_t lda, const void* B
   const char* ring_min_env = getenv("FK_NT_RING_MIN_TILES");
   const int ring_min = ring_min_env ? atoi(ring_min_env) : 128;
   const bool wide = glds && M >= 4096 && vec_epi && !no_ring && fk_cdiv(M, 256) * fk_cdiv(N, 256) >= ring_min;
-  if (wide && (N % 256 == 0 || (N % 128 == 0 && N >= 1024))) {   // 256 x 256 tiles, split A/B rings (N = 1152: the last column tile is
-                                                                  // half empty, still 4 % faster than 256 x 128 tiles)
-    if (out_dtype == FK_BF16) launch_ring2<bf16_t>(p, M, N, s); else launch_ring2<float>(p, M, N, s);
-    FK_CHECK_LAUNCH(name);
-    return FK_OK;
-  }
-  static const bool no_192 = getenv("FK_NT_NO_192") != nullptr;        // tuning knob: 256 x 128 tiles for N = 384 / 768 too
-  if (wide && N % 192 == 0 && N % 256 != 0 && N <= 768 && mode == 0 && !rope.table && !no_192) {   // N = 384: two 192-column tiles
-    if (out_dtype == FK_BF16) launch_ring192<bf16_t>(p, M, N, s); else launch_ring192<float>(p, M, N, s);
-    FK_CHECK_LAUNCH(name);
-    return FK_OK;
-  }
-  if (wide && N % 128 == 0) {                  // N = 128 / 384 / 640 / 896: 256 x 128 ring
-    if (out_dtype == FK_BF16) launch_ring<bf16_t, 128, 128, 3>(p, M, N, s); else launch_ring<float, 128, 128, 3>(p, M, N, s);
-    FK_CHECK_LAUNCH(name);
-    return FK_OK;
-  }
-  if (glds && M >= 4096 && N % 256 == 0 && vec_epi) {
-        // large projections: 256 x 256 tiles, 1 block per CU (the 256x128
-                                                                // variant measured slower than 128x128 at N = 384)
-    const int64_t nt = fk_cdiv(M, 256) * (N / 256);
-    dim3 bgrid(persistent_grid(nt)), bblock(512);
-    const size_t bsh = 2 * (size_t)(256 + 256) * ROW_BYTES;
-    if (out_dtype == FK_BF16) { static bool once = (hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_big_kernel<bf16_t, 256>), hipFuncAttributeMaxDynamicSharedMemorySize, 131072) == hipSuccess); (void)once;
-      hipLaunchKernelGGL((gemm_nt_big_kernel<bf16_t, 256>), bgrid, bblock, bsh, s, p); }
-    else { static bool once = (hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_big_kernel<float, 256>), hipFuncAttributeMaxDynamicSharedMemorySize, 131072) == hipSuccess); (void)once;
-      hipLaunchKernelGGL((gemm_nt_big_kernel<float, 256>), bgrid, bblock, bsh, s, p); }
-    FK_CHECK_LAUNCH(name);
-    return FK_OK;
-  }
-  static const bool no_g4 = getenv("FK_NT_NO_GLDS4") != nullptr;       // tuning knob
-  if (glds && nwg <= 256 && !no_g4) {                      // at most one tile per CU: the short-latency ring
-    if (out_dtype == FK_BF16) {
-      static bool once = (hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_glds4_kernel<bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, G4_LDS) == hipSuccess); (void)once;
-      hipLaunchKernelGGL((gemm_nt_glds4_kernel<bf16_t>), grid, block, G4_LDS, s, p);
-    } else {
-      static bool once = (hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_glds4_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, G4_LDS) == hipSuccess); (void)once;
-      hipLaunchKernelGGL((gemm_nt_glds4_kernel<float>), grid, block, G4_LDS, s, p);
-    }
-    FK_CHECK_LAUNCH(name);
-    return FK_OK;
-  }
-  dim3 pgrid((unsigned)(nwg < 512 ? nwg : 512));           // persistent: 2 blocks per CU (64 KiB LDS each)
-  if (glds && out_dtype == FK_BF16) hipLaunchKernelGGL((gemm_nt_glds_kernel<bf16_t>), pgrid, block, sh, s, p);
-  else if (glds) hipLaunchKernelGGL((gemm_nt_glds_kernel<float>), pgrid, block, sh, s, p);
-  else if (dtype == FK_BF16 && out_dtype == FK_BF16) hipLaunchKernelGGL((gemm_nt_kernel<bf16_t, bf16_t>), grid, block, sh, s, p);
-  else if (dtype == FK_BF16) hipLaunchKernelGGL((gemm_nt_kernel<bf16_t, float>), grid, block, sh, s, p);
-  else hipLaunchKernelGGL((gemm_nt_kernel<float, float>), grid, block, sh, s, p);
+  const NtRoute route = [&] {
+    // 256 x 256 tiles, split A/B rings (N = 1152: the last column tile is half empty, still 4 % faster than 256 x 128 tiles)
+    if (wide && (N % 256 == 0 || (N % 128 == 0 && N >= 1024))) return NT_RING2;
+    static const bool no_192 = getenv("FK_NT_NO_192") != nullptr;        // tuning knob: 256 x 128 tiles for N = 384 / 768 too
+    if (wide && N % 192 == 0 && N % 256 != 0 && N <= 768 && mode == 0 && !rope.table && !no_192) return NT_RING192;   // N = 384: two 192-column tiles
+    if (wide && N % 128 == 0) return NT_RING128;           // N = 128 / 384 / 640 / 896: 256 x 128 ring
+    // large projections: 256 x 256 tiles, 1 block per CU (the 256x128 variant measured slower than 128x128 at N = 384)
+    if (glds && M >= 4096 && N % 256 == 0 && vec_epi) return NT_BIG;
+    static const bool no_g4 = getenv("FK_NT_NO_GLDS4") != nullptr;       // tuning knob
+    if (glds && nwg <= 256 && !no_g4) return NT_GLDS4;     // at most one tile per CU: the short-latency ring
+    return glds ? NT_GLDS : NT_STAGED;
+  }();
+  if (dtype == FK_F32)                                     // fp32 operands: the register-staged kernel only (route == NT_STAGED)
+    hipLaunchKernelGGL((gemm_nt_kernel<float, float>), dim3((unsigned)nwg), dim3(NTHREADS), 4 * TILE_BYTES, s, p);
+  else if (out_dtype == FK_BF16) launch_nt_route<bf16_t>(route, p, M, N, s);
+  else launch_nt_route<float>(route, p, M, N, s);
   FK_CHECK_LAUNCH(name);
   return FK_OK;
 }
@@ -1733,13 +1682,9 @@ int fk_gemm_tn(const void* A, int64_t lda, const void* B, int64_t ldb, float* C,
     dim3 bgrid((unsigned)((N1 / TG_A) * (N2 / tb) * ns));
     if (tb == 192) {
       constexpr int LDS192 = TG_NS * (TG_A_BYTES + TG_K * 512);
-      static bool once = (hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_big_kernel<192>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS192) == hipSuccess);
-      (void)once;
-      hipLaunchKernelGGL(gemm_tn_big_kernel<192>, bgrid, dim3(512), LDS192, s, p);
+      fk_launch_lds<gemm_tn_big_kernel<192>>(bgrid, dim3(512), LDS192, s, p);
     } else {
-      static bool once = (hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_big_kernel<128>), hipFuncAttributeMaxDynamicSharedMemorySize, TG_NS * TG_STAGE) == hipSuccess);
-      (void)once;
-      hipLaunchKernelGGL(gemm_tn_big_kernel<128>, bgrid, dim3(512), TG_NS * TG_STAGE, s, p);
+      fk_launch_lds<gemm_tn_big_kernel<128>>(bgrid, dim3(512), TG_NS * TG_STAGE, s, p);
     }
   } else if (dtype == FK_BF16) hipLaunchKernelGGL((gemm_tn_kernel<bf16_t>), grid, block, 4 * TILE_BYTES, s, p);
   else hipLaunchKernelGGL((gemm_tn_kernel<float>), grid, block, 4 * TILE_BYTES, s, p);

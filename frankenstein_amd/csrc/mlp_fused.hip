@@ -911,9 +911,7 @@ int fk_qkv_rope_fused_launch(const void* A, int64_t lda, const void* W, int64_t 
                              int64_t table_bs, int64_t T, int64_t pos_off, int64_t rot_cols, int64_t q_cols, int64_t q_off, void* stream) {
   QkvArgs a{(const bf16_t*)A, (const bf16_t*)W, (bf16_t*)C, table, lda, ldb, ldc, table_bs, q_off, (int)M, (int)N, (int)T, (int)pos_off,
             (int)(rot_cols / 64), (int)(q_cols / 64)};
-  static bool once = (hipFuncSetAttribute(reinterpret_cast<const void*>(qkv_rope_fused_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, QK_LDS) == hipSuccess);
-  (void)once;
-  hipLaunchKernelGGL(qkv_rope_fused_kernel, dim3((unsigned)fk_cdiv(M, MU_TOK)), dim3(MU_NW * 64), QK_LDS, (hipStream_t)stream, a);
+  fk_launch_lds<qkv_rope_fused_kernel>(dim3((unsigned)fk_cdiv(M, MU_TOK)), dim3(MU_NW * 64), QK_LDS, (hipStream_t)stream, a);
   FK_CHECK_LAUNCH("fk_gemm_nt_rope (token-on-the-lane kernel)");
   return FK_OK;
 }
@@ -927,9 +925,7 @@ bool fk_mlp_up_fused_ok(int64_t M, int64_t H, int64_t K, int64_t lda, int64_t ld
 int fk_mlp_up_fused_launch(const void* A, int64_t lda, const void* W13, int64_t ldb, void* H13, int64_t ldh, void* G, int64_t ldg, int64_t M, int64_t H,
                            void* stream) {
   MlpUpArgs a{(const bf16_t*)A, (const bf16_t*)W13, (bf16_t*)H13, (bf16_t*)G, lda, ldb, ldh, ldg, (int)M, (int)H};
-  static bool once = (hipFuncSetAttribute(reinterpret_cast<const void*>(mlp_up_fused_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, MU_LDS) == hipSuccess);
-  (void)once;
-  hipLaunchKernelGGL(mlp_up_fused_kernel, dim3((unsigned)fk_cdiv(M, MU_TOK)), dim3(MU_NW * 64), MU_LDS, (hipStream_t)stream, a);
+  fk_launch_lds<mlp_up_fused_kernel>(dim3((unsigned)fk_cdiv(M, MU_TOK)), dim3(MU_NW * 64), MU_LDS, (hipStream_t)stream, a);
   FK_CHECK_LAUNCH("fk_gemm_nt_swiglu (token-on-the-lane kernel)");
   return FK_OK;
 }
@@ -960,14 +956,11 @@ extern "C" int fk_mlp_bwd_fused(const void* dY, int64_t lddy, const void* W2T, i
   MlpBwdArgs a{(const bf16_t*)dY, (const bf16_t*)W2T, (const bf16_t*)H13, (const bf16_t*)W13T, (bf16_t*)dH13, (bf16_t*)dX,
                lddy, ldw2t, ldh, ldw13t, lddh, lddx, (int)M, (int)H};
   static const bool asm_off = getenv("FK_MLP_BWD_ASM") != nullptr && getenv("FK_MLP_BWD_ASM")[0] == '0';
-  static bool once = (hipFuncSetAttribute(reinterpret_cast<const void*>(mlp_bwd_fused_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, MF_LDS) == hipSuccess) &&
-                     (hipFuncSetAttribute(reinterpret_cast<const void*>(mlp_bwd_fused_asm_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, MF_LDS) == hipSuccess);
-  (void)once;
   // whole 128-token tiles, and the dh13 rows addressable with 32-bit byte offsets from a per-chunk scalar base: the generated-stream kernel
   if (!asm_off && M % MF_TOK == 0 && M * lddh * 2 < (1LL << 32))
-    hipLaunchKernelGGL(mlp_bwd_fused_asm_kernel, dim3((unsigned)(M / MF_TOK)), dim3(MF_NW * 64), MF_LDS, (hipStream_t)stream, a);
+    fk_launch_lds<mlp_bwd_fused_asm_kernel>(dim3((unsigned)(M / MF_TOK)), dim3(MF_NW * 64), MF_LDS, (hipStream_t)stream, a);
   else
-    hipLaunchKernelGGL(mlp_bwd_fused_kernel, dim3((unsigned)fk_cdiv(M, MF_TOK)), dim3(MF_NW * 64), MF_LDS, (hipStream_t)stream, a);
+    fk_launch_lds<mlp_bwd_fused_kernel>(dim3((unsigned)fk_cdiv(M, MF_TOK)), dim3(MF_NW * 64), MF_LDS, (hipStream_t)stream, a);
   FK_CHECK_LAUNCH("fk_mlp_bwd_fused");
   return FK_OK;
 }
