@@ -17,6 +17,7 @@ FK_F32, FK_BF16 = 0, 1
 MASK_NONE, MASK_CAUSAL, MASK_BLOCK_CAUSAL, MASK_PREFIX, MASK_KEYPAD, MASK_DENSE = 0, 1, 2, 3, 4, 5
 NORM_LAYER, NORM_RMS = 0, 1
 ATTN_Q_PRESCALED = 1
+GEMV_GELU = 1
 
 _p, _i64, _int, _f32, _f64, _sz, _u32 = C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_double, C.c_size_t, C.c_uint32
 
@@ -25,6 +26,7 @@ SIGNATURES = {
     "fk_version": (_int, []),
     "fk_last_error": (C.c_char_p, []),
     "fk_gemm_nt": (_int, [_p, _i64, _p, _i64, _p, _i64, _i64, _i64, _i64, _p, _p, _i64, _i64, _int, _int, _p]),
+    "fk_gemv_nt": (_int, [_p, _i64, _p, _i64, _p, _i64, _i64, _i64, _i64, _p, _p, _i64, _p, _p, _f32, _int, _int, _int, _p]),
     "fk_gemm_nt_rope": (_int, [_p, _i64, _p, _i64, _p, _i64, _i64, _i64, _i64, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _int, _p]),
     "fk_gemm_nt_swiglu": (_int, [_p, _i64, _p, _i64, _p, _i64, _p, _i64, _i64, _i64, _i64, _int, _p]),
     "fk_gemm_nt_dswiglu": (_int, [_p, _i64, _p, _i64, _p, _i64, _p, _i64, _i64, _i64, _i64, _int, _p]),

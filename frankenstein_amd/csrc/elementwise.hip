@@ -137,7 +137,7 @@ __global__ void gelu_fwd_kernel(const T* x, T* y, int64_t nvec) {
     float a[N], o[N];
     V16<T>::ld(x + i * N, a);
 #pragma unroll
-    for (int j = 0; j < N; ++j) o[j] = 0.5f * a[j] * (1.0f + erff(a[j] * 0.70710678118654752f));
+    for (int j = 0; j < N; ++j) o[j] = fk_gelu(a[j]);
     V16<T>::st(y + i * N, o);
   }
 }

@@ -136,6 +136,9 @@ FK_DEV bf16x4 lds_read_tr4(const bf16_t* p) {
   return __builtin_bit_cast(bf16x4, r);
 }
 
+// nn.GELU() (exact erf, models/gpt2_model.py:83,89): the one expression fk_gelu_fwd and the fk_gemv_nt epilogue share
+FK_DEV float fk_gelu(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752f)); }
+
 // ------------------------------------------------------------------------------------------------
 // wave helpers
 // ------------------------------------------------------------------------------------------------

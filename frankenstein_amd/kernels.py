@@ -93,6 +93,41 @@ def gemm_nt(a: Tensor, w: Tensor, bias: Optional[Tensor] = None, residual: Optio
     return out
 
 
+def gemv_nt(a: Tensor, w: Tensor, bias: Optional[Tensor] = None, residual: Optional[Tensor] = None,
+            ln: Optional[Tuple[Tensor, Optional[Tensor], float]] = None, act: Optional[str] = None,
+            out_dtype: Optional[torch.dtype] = None, n: Optional[int] = None, out: Optional[Tensor] = None) -> Tensor:
+    """Weight-streaming skinny product for 1 <= M <= 16 rows (the single-token decode step):
+    out[M,N] = act(LN(a)[M,K] @ w[:N,K]^T + bias) + residual.  ln = (gamma, beta or None, eps), act = None | "gelu";
+    n < w.shape[0] uses the first n rows of a padded weight shadow (the vocabulary head)."""
+    assert a.dim() == 2 and w.dim() == 2 and a.shape[1] == w.shape[1], (a.shape, w.shape)
+    assert a.dtype == w.dtype and a.stride(1) == 1 and w.stride(1) == 1
+    assert act in (None, "gelu"), act
+    M, K = a.shape
+    N = w.shape[0] if n is None else n
+    assert 0 < N <= w.shape[0], (N, w.shape)
+    odt = out_dtype or a.dtype
+    if out is None:
+        out = torch.empty((M, N), dtype=odt, device=a.device)
+    assert out.shape == (M, N) and out.stride(1) == 1 and out.dtype == odt
+    if bias is not None:
+        assert bias.dtype == a.dtype and bias.numel() == N and bias.is_contiguous()
+    ldr = 0
+    if residual is not None:
+        assert residual.dtype == a.dtype and residual.dim() == 2 and residual.stride(1) == 1 and residual.shape == (M, N)
+        ldr = residual.stride(0)
+    gamma = beta = None
+    eps = 0.0
+    if ln is not None:
+        gamma, beta, eps = ln
+        assert gamma.dtype == torch.float32 and gamma.numel() == K and gamma.is_contiguous()
+        assert beta is None or (beta.dtype == torch.float32 and beta.numel() == K and beta.is_contiguous())
+    with _timed(f"gemv_nt:{M}x{N}x{K}"):
+        call("fk_gemv_nt", a.data_ptr(), a.stride(0), w.data_ptr(), w.stride(0), out.data_ptr(), out.stride(0), M, N, K,
+             _ptr(bias), _ptr(residual), ldr, _ptr(gamma), _ptr(beta), float(eps), _lib.GEMV_GELU if act == "gelu" else 0,
+             fk_dtype(a), fk_dtype(odt), _stream())
+    return out
+
+
 def gemm_nt_rope(a: Tensor, w: Tensor, bias: Optional[Tensor], table: Tensor, T: int, pos_off: int, D: int,
                  rot_cols: int, q_cols: int = 0, q_table: Optional[Tensor] = None) -> Tensor:
     """out[M,N] = a @ w^T (+ bias) with RoPE applied to the first rot_cols columns (heads of width D); rows are B x T tokens.

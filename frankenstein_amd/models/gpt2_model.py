@@ -98,20 +98,16 @@ class Block(nn.Module):
         at, ml = self.attn, self.mlp
         H, D = at.n_head, d // at.n_head
         x2 = x.reshape(B * t, d)
-        h, _, _ = K.norm_fwd(x2, self.ln_1.weight.detach(), None if self.ln_1.bias is None else self.ln_1.bias.detach(), self.ln_1.eps)
-        qkv = K.gemm_nt(h, E.shadow([at.c_attn.weight]), None if at.c_attn.bias is None else E.shadow([at.c_attn.bias]))
+        qkv = _step_linear(x2, at.c_attn, ln=self.ln_1)
         q3 = qkv.view(B, t, 3 * d)
         for b in range(B):                                   # append k|v rows of the new tokens
             K.copy2d(q3[b, :, d:], kv[b, pos:pos + t])
         k = kv[:, :pos + t, :d].unflatten(-1, (H, D))
         v = kv[:, :pos + t, d:].unflatten(-1, (H, D))
         o, _ = K.attn_fwd(q3[..., :d].unflatten(-1, (H, D)), k, v, Mask(MASK_CAUSAL, q_off=pos))
-        x2 = K.gemm_nt(o.view(B * t, d), E.shadow([at.c_proj.weight]), None if at.c_proj.bias is None else E.shadow([at.c_proj.bias]),
-                       residual=x2)
-        h, _, _ = K.norm_fwd(x2, self.ln_2.weight.detach(), None if self.ln_2.bias is None else self.ln_2.bias.detach(), self.ln_2.eps)
-        a = K.gemm_nt(h, E.shadow([ml.c_fc.weight]), None if ml.c_fc.bias is None else E.shadow([ml.c_fc.bias]))
-        x2 = K.gemm_nt(K.gelu_fwd(a), E.shadow([ml.c_proj.weight]), None if ml.c_proj.bias is None else E.shadow([ml.c_proj.bias]),
-                       residual=x2)
+        x2 = _step_linear(o.view(B * t, d), at.c_proj, residual=x2)
+        a = _step_linear(x2, ml.c_fc, ln=self.ln_2, gelu=True)
+        x2 = _step_linear(a, ml.c_proj, residual=x2)
         return x2.view(B, t, d)
 
 
@@ -119,17 +115,41 @@ def _bias(lin):
     return None if lin.bias is None else E.shadow([lin.bias])
 
 
+GEMV_MAX_ROWS = 16      # the envelope of K.gemv_nt (fk_gemv_nt: 1 <= M <= 16)
+
+
+def _step_linear(x, lin, ln=None, gelu=False, residual=None, step_rows=None, head_vocab=None):
+    """One linear layer of a cached inference step, x [rows, K]: act(LN(x) W^T + bias) + residual.
+    A step of at most GEMV_MAX_ROWS rows (step_rows = B * t, by default the rows of x) is a decode step: the layer is ONE
+    weight-streaming launch (K.gemv_nt) with the LayerNorm in front, the bias, the GELU and the residual folded in.  Anything
+    larger (the prefill) runs the training kernels: norm, MFMA GEMM, GELU.  The host-position step (forward_cached,
+    _cached_logits) and the device-position step (forward_decode, _decode_logits_dev) both come through here, so they take
+    the same route.  head_vocab = V: the vocabulary head, fp32 logits [rows, V] from the 16-byte-padded shadow of the weight."""
+    rows = x.shape[0] if step_rows is None else step_rows
+    if head_vocab is None:
+        w, n, odt = E.shadow([lin.weight]), None, None
+    else:
+        w, n, odt = E.shadow([lin.weight], pad_n=(head_vocab + 7) // 8 * 8), head_vocab, torch.float32   # 16-byte rows for the vector GEMM epilogue
+    lnp = None if ln is None else (ln.weight.detach(), None if ln.bias is None else ln.bias.detach(), ln.eps)
+    if rows <= GEMV_MAX_ROWS:
+        return K.gemv_nt(x, w, _bias(lin), residual=residual, ln=lnp, act="gelu" if gelu else None, out_dtype=odt, n=n)
+    if lnp is not None:
+        x, _, _ = K.norm_fwd(x, *lnp)
+    y = K.gemm_nt(x, w, _bias(lin), residual=residual, out_dtype=odt)
+    if gelu:
+        y = K.gelu_fwd(y)
+    return y if head_vocab is None else y[:, :head_vocab]
+
+
 def _block_forward_decode(self, x, kv, pos):
     """One new token per sample with the position in a device int32 (graph-capturable): x [B, d], kv [B, Tmax, 2d]."""
     at, ml = self.attn, self.mlp
-    h, _, _ = K.norm_fwd(x, self.ln_1.weight.detach(), None if self.ln_1.bias is None else self.ln_1.bias.detach(), self.ln_1.eps)
-    qkv = K.gemm_nt(h, E.shadow([at.c_attn.weight]), _bias(at.c_attn))
+    qkv = _step_linear(x, at.c_attn, ln=self.ln_1)
     K.kv_append_(qkv, kv, pos)
     o = K.attn_decode(qkv, kv, pos, at.n_head)
-    x = K.gemm_nt(o, E.shadow([at.c_proj.weight]), _bias(at.c_proj), residual=x)
-    h, _, _ = K.norm_fwd(x, self.ln_2.weight.detach(), None if self.ln_2.bias is None else self.ln_2.bias.detach(), self.ln_2.eps)
-    a = K.gemm_nt(h, E.shadow([ml.c_fc.weight]), _bias(ml.c_fc))
-    return K.gemm_nt(K.gelu_fwd(a), E.shadow([ml.c_proj.weight]), _bias(ml.c_proj), residual=x)
+    x = _step_linear(o, at.c_proj, residual=x)
+    a = _step_linear(x, ml.c_fc, ln=self.ln_2, gelu=True)
+    return _step_linear(a, ml.c_proj, residual=x)
 
 
 Block.forward_decode = _block_forward_decode
@@ -302,10 +322,7 @@ class GPT(nn.Module):
             x = block.forward_cached(x, cache[li], pos)
         ln = self.transformer.ln_f
         last = x[:, -1, :].contiguous()
-        h, _, _ = K.norm_fwd(last, ln.weight.detach(), None if ln.bias is None else ln.bias.detach(), ln.eps)
-        V = self.config.vocab_size
-        npad = (V + 7) // 8 * 8                               # 16-byte rows for the vector GEMM epilogue
-        logits = K.gemm_nt(h, E.shadow([self.lm_head.weight], pad_n=npad), out_dtype=torch.float32)[:, :V]
+        logits = _step_linear(last, self.lm_head, ln=ln, step_rows=x.shape[0] * t, head_vocab=self.config.vocab_size)
         return logits, pos + t
 
     @torch.no_grad()
@@ -314,10 +331,7 @@ class GPT(nn.Module):
         x = K.gpt_embed_step(cur, self.transformer.wte.weight.detach(), self.transformer.wpe.weight.detach(), pos, E.compute_dtype())
         for li, block in enumerate(self.transformer.h):
             x = block.forward_decode(x, cache[li], pos)
-        ln = self.transformer.ln_f
-        h, _, _ = K.norm_fwd(x, ln.weight.detach(), None if ln.bias is None else ln.bias.detach(), ln.eps)
-        V = self.config.vocab_size
-        return K.gemm_nt(h, E.shadow([self.lm_head.weight], pad_n=(V + 7) // 8 * 8), out_dtype=torch.float32)[:, :V]
+        return _step_linear(x, self.lm_head, ln=self.transformer.ln_f, head_vocab=self.config.vocab_size)
 
     @staticmethod
     def _sample(logits, temperature, top_k, state=None):

@@ -39,6 +39,7 @@ enum { FK_MASK_NONE = 0, FK_MASK_CAUSAL = 1, FK_MASK_BLOCK_CAUSAL = 2, FK_MASK_P
 enum { FK_ATTN_Q_PRESCALED = 1 };
 enum { FK_NORM_LAYER = 0, FK_NORM_RMS = 1 };
 enum { FK_ACT_SWIGLU = 0, FK_ACT_GELU = 1 };
+enum { FK_GEMV_GELU = 1 };   /* fk_gemv_nt flags */
 
 int fk_version(void);
 const char* fk_last_error(void);
@@ -53,6 +54,20 @@ const char* fk_last_error(void);
 int fk_gemm_nt(const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc, int64_t M, int64_t N,
                int64_t K, const void* bias, const void* residual, int64_t ldr, int64_t res_rows, int dtype,
                int out_dtype, void* stream);
+/* fk_gemv_nt: the same product for the single-token decode step, 1 <= M <= 16 rows (models/gpt2_model.py:35,37,56,75,82-90,133 at one
+ *   new token per sample), as a stream of the weight matrix instead of MFMA tiles, with the step's neighbours folded in:
+ *     C[m, n] = act( sum_k LN(A[m, :])[k] * W[n, k] + bias[n] ) + residual[m, n].
+ *   W is row-major [N, K] (ldw; the layout of the weight shadows, rows past N are never read); A, W, bias [N], residual [M, N] (ldr)
+ *   have `dtype`, C has `out_dtype` (= dtype, or FK_F32).  bias / residual: NULL = absent.  ln_gamma != NULL: LayerNorm over K in
+ *   front of the product (F.layer_norm, models/gpt2_model.py:27): gamma / beta fp32 [K], beta may be NULL, statistics and the
+ *   normalised row kept in fp32.  flags & FK_GEMV_GELU: act = exact-erf GELU (the function of fk_gelu_fwd), else identity.
+ *   Envelope: 1 <= M <= 16 (anything larger is refused, not forwarded), any N >= 1 (no multiple required), K a multiple of 16 bytes
+ *   (8 bf16 / 4 fp32), every leading dimension covers its row, A and W rows 16-byte aligned, sizes within int32.
+ *   fp32 accumulation; deterministic (no split over workgroups, no atomics, no workspace), and batch invariant: row m of the result
+ *   does not depend on M, so a sample decodes to the same bits alone or in a batch.                                              */
+int fk_gemv_nt(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc, int64_t M, int64_t N, int64_t K,
+               const void* bias, const void* residual, int64_t ldr, const float* ln_gamma, const float* ln_beta, float ln_eps,
+               int flags, int dtype, int out_dtype, void* stream);
 /* fk_gemm_nt_rope: fk_gemm_nt (+ bias) with apply_rope (models/brainformer.py:70-91) fused into the epilogue: the first
  * rot_cols output columns (q and k of a packed q|k|v projection, heads of width D) of row m are rotated by
  * table[m / T][pos_off + m % T][(n % D) / 2] = (cos, sin)  (table_bs = 0: one cache shared by all samples).
