@@ -427,7 +427,7 @@ int fk_norm_bwd(const void* dy, const void* x, const float* gamma, const float* 
   FK_CHECK_ARG(kind == FK_NORM_LAYER || kind == FK_NORM_RMS, "fk_norm_bwd: bad kind %d", kind);
   const int vec = dtype == FK_BF16 ? 8 : 4;
   FK_CHECK_ARG(rows > 0 && dim > 0 && dim % vec == 0, "fk_norm_bwd: dim %lld must be a multiple of %d", (long long)dim, vec);
-  FK_CHECK_ARG(dy && x && gamma && rstd && dx, "fk_norm_bwd: null pointer");
+  FK_CHECK_ARG(dy && x && gamma && rstd && dx && (kind == FK_NORM_RMS || mean), "fk_norm_bwd: null pointer");
   hipStream_t s = (hipStream_t)stream;
   const int per16 = 16 * vec, per64 = 64 * vec;
   const bool fits = (dtype == FK_BF16 ? dim <= 4 * per64 : dim <= 4 * per64) && (size_t)8 * dim * sizeof(float) <= 65536 &&

@@ -163,7 +163,8 @@ int fk_dropout(const void* x, const void* res, void* y, int64_t n, float p, cons
  *      mean/rstd fp32 [rows] saved for backward (mean unused for RMS).                                        */
 int fk_norm_fwd(const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd,
                 int64_t rows, int64_t dim, float eps, int kind, int dtype, void* stream);
-/* dx = (dres ? dres : 0) + norm_bwd(dy); dgamma/dbeta (fp32, +=  when accumulate) via workspace partials.     */
+/* dx = (dres ? dres : 0) + norm_bwd(dy); dgamma/dbeta (fp32, +=  when accumulate) via workspace partials;
+ *      mean may be NULL for FK_NORM_RMS only (a NULL mean with FK_NORM_LAYER is refused).                      */
 size_t fk_norm_bwd_workspace_bytes(int64_t rows, int64_t dim);
 int fk_norm_bwd(const void* dy, const void* x, const float* gamma, const float* mean, const float* rstd,
                 const void* dres, void* dx, float* dgamma, float* dbeta, int64_t rows, int64_t dim, int kind,

@@ -63,6 +63,9 @@ def test_argument_validation_needs_no_gpu(built):
     assert rc == -1 and b"FK_ATTN_Q_PRESCALED" in lib.fk_last_error()
     rc = lib.fk_patchify(16, 16, 1, 10, 4, 3, 8, 0, None)
     assert rc == -1
+    # fk_norm_bwd: LayerNorm's backward reads mean[row], so a NULL mean is refused before any launch (RMSNorm never reads it)
+    rc = lib.fk_norm_bwd(16, 16, 16, None, 16, None, 16, 16, 16, 8, 64, _lib.NORM_LAYER, 0, _lib.FK_F32, 16, 1 << 20, None)
+    assert rc == -1 and b"fk_norm_bwd: null pointer" in lib.fk_last_error()
     # fk_sample_topk: an output buffer without its width is refused (the device-side step counter is not trusted to stay inside it)
     rc = lib.fk_sample_topk(16, 8, 1, 8, 1.0, 0, 16, 16, None, 16, 16, 4, 0, 16, None)
     assert rc == -1 and b"out_cols" in lib.fk_last_error()
