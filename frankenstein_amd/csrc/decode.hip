@@ -4,6 +4,8 @@
 //   fk_kv_append       kv[b, *pos, :] = qkv[b, d : 3d]   (key | value rows of the new token into the per-layer cache)
 //   fk_attn_decode     o[b, h, :] = softmax_j( q[b,h,:] . k[b,j,h,:] * scale ) v[b,j,h,:],  j = 0 .. *pos   (causal, one query)
 // All three read the position from a device int32 (bumped by the host graph between steps).  HBM / latency-bound, no MFMA.
+//   fk_sample_topk     the sampling tail of GPT.generate as one launch
+//   fk_attn_decode_beam / fk_beam_topk / fk_beam_select    the step of the beam search on shared caches (ancestry table), further down
 #include "fk_common.h"
 
 namespace {
@@ -120,6 +122,51 @@ template <typename F> FK_DEV float block_reduce(float v, float* red, F op, float
   return r;
 }
 
+// k-th largest of the V values row[i] * inv_temp (1 <= k <= V) as its sortable key, by a 4-pass radix select, 8 bits per pass from the
+// top; every thread of the block calls it and gets the same key.  hist: 256 words of LDS, sel_prefix / sel_remaining: one word each.
+// Behind it *sel_remaining says how many of the values EQUAL to the k-th belong to the k largest (k minus the count of strictly larger
+// ones) and hist[key & 255] how many such values the row holds.
+FK_DEV unsigned radix_select_kth(const float* row, int V, float inv_temp, int k, unsigned* hist, unsigned* sel_prefix, unsigned* sel_remaining) {
+  const int tid = threadIdx.x;
+  if (tid == 0) { *sel_prefix = 0u; *sel_remaining = (unsigned)k; }
+  for (int pass = 0; pass < 4; ++pass) {
+    const int shift = 24 - 8 * pass;
+    if (tid < 256) hist[tid] = 0u;
+    __syncthreads();
+    const unsigned prefix = *sel_prefix, mask_hi = pass == 0 ? 0u : (0xFFFFFFFFu << (shift + 8));
+    for (int i = tid; i < V; i += SAMPLE_THREADS) {
+      const unsigned key = f32_sortable(row[i] * inv_temp);
+      if ((key & mask_hi) == prefix) atomicAdd(&hist[(key >> shift) & 255u], 1u);
+    }
+    __syncthreads();
+    if (tid < 64) {                                     // walk the 256 bins from the top until the k-th largest falls into one: lane l
+      const unsigned rem0 = *sel_remaining;             // of the first wave owns the bins 255 - 4l .. 252 - 4l, a scan finds the lane
+      unsigned h[4], mine = 0u;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) { h[q] = hist[255 - 4 * tid - q]; mine += h[q]; }
+      unsigned incl = mine;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const unsigned up = __shfl_up(incl, o, 64);
+        if (tid >= o) incl += up;
+      }
+      const unsigned before = incl - mine;              // keys in the bins above this lane's
+      if (before < rem0 && (rem0 <= incl || tid == 63)) {   // one lane; bin 0 takes whatever is left, as a walk that stops at bin 1 would
+        unsigned rem = rem0 - before;
+        int q = 0;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          if (q == c && h[c] < rem) { rem -= h[c]; q = c + 1; }
+        }
+        *sel_prefix = prefix | ((unsigned)(255 - 4 * tid - q) << shift);
+        *sel_remaining = rem;
+      }
+    }
+    __syncthreads();
+  }
+  return *sel_prefix;
+}
+
 __global__ __launch_bounds__(SAMPLE_THREADS) void sample_topk_kernel(const float* logits, int64_t ld, int V, float inv_temp, int top_k,
                                                                      const unsigned long long* seed, int64_t* step, int32_t* pos_inc,
                                                                      int64_t* cur, int64_t* out, int64_t out_ld, int64_t out_cols, unsigned* ticket) {
@@ -134,32 +181,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_topk_kernel(const float
 
   // ---- k-th largest key (top_k <= 0 or >= V: keep everything)
   unsigned kth = 0u;
-  if (top_k > 0 && top_k < V) {
-    if (tid == 0) { sel_prefix = 0u; sel_remaining = (unsigned)top_k; }
-    for (int pass = 0; pass < 4; ++pass) {
-      const int shift = 24 - 8 * pass;
-      if (tid < 256) hist[tid] = 0u;
-      __syncthreads();
-      const unsigned prefix = sel_prefix, mask_hi = pass == 0 ? 0u : (0xFFFFFFFFu << (shift + 8));
-      for (int i = tid; i < V; i += SAMPLE_THREADS) {
-        const unsigned key = f32_sortable(row[i] * inv_temp);
-        if ((key & mask_hi) == prefix) atomicAdd(&hist[(key >> shift) & 255u], 1u);
-      }
-      __syncthreads();
-      if (tid == 0) {                                     // walk the 256 bins from the top until the k-th largest falls into one
-        unsigned rem = sel_remaining;
-        int bin = 255;
-        for (; bin > 0; --bin) {
-          if (hist[bin] >= rem) break;
-          rem -= hist[bin];
-        }
-        sel_prefix = prefix | ((unsigned)bin << shift);
-        sel_remaining = rem;
-      }
-      __syncthreads();
-    }
-    kth = sel_prefix;
-  }
+  if (top_k > 0 && top_k < V) kth = radix_select_kth(row, V, inv_temp, top_k, hist, &sel_prefix, &sel_remaining);
   // ---- softmax over the kept logits: maximum, then the sum of exp; per-thread partial sums of CONTIGUOUS index chunks for the draw
   float mx = -INFINITY;
   for (int i = tid; i < V; i += SAMPLE_THREADS) {
@@ -220,6 +242,232 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_topk_kernel(const float
   }
 }
 
+// ---- beam search on the caches (models/gpt2_model.py:355-416).  The W beams share ONE set of caches [W, Tmax, 2d]: slot b holds the rows
+// that beam position b wrote, and the ancestry table anc[b, j] names the slot in which beam b's row j lives, so reordering the beams
+// rewrites W x (pos + 1) int32 and never moves a key or a value.
+
+// block = (h, b), 256 threads.  A key row of D elements is spread over LPK = D / (16 bytes of T) neighbouring lanes, one 16-byte load
+// each, so a wave reads 64 / LPK whole rows per trip as contiguous 16-byte pieces; the score is summed across the LPK lanes, every
+// lane keeps the running (max, sum) of its key group and its own 16-byte slice of the output, and the groups are merged across the
+// wave (lanes with the same slice) and then across the four waves.
+template <typename T, int D>
+__global__ __launch_bounds__(256) void attn_decode_beam_kernel(const T* q, int64_t q_bs, const T* kv, int64_t kv_bs, int64_t kv_rs, const int32_t* anc,
+                                                               int64_t anc_ld, T* out, int64_t o_bs, const int32_t* pos, int W, int H, float scale) {
+  constexpr int VN = Vec16<T>::N, LPK = D / VN, GROUPS = 256 / LPK;
+  typedef T vec_t __attribute__((ext_vector_type(VN)));
+  __shared__ float red[4][D + 2];
+  const int h = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, wave = tid >> 6;
+  const int sub = tid % LPK, grp = tid / LPK;
+  const int p = pos[0], nk = p + 1;
+  const int d_model = H * D;
+  float qf[VN], o[VN];
+#pragma unroll
+  for (int i = 0; i < VN; ++i) {
+    qf[i] = to_f32<T>(q[(int64_t)b * q_bs + h * D + sub * VN + i]) * scale;
+    o[i] = 0.0f;
+  }
+  float m = -INFINITY, l = 0.0f;
+  const int32_t* arow = anc + (int64_t)b * anc_ld;
+  for (int j = grp; j < nk; j += GROUPS) {
+    int slot = b;                                         // the newest row is the beam's own (fk_kv_append has just written it)
+    if (j < p) {
+      slot = arow[j];
+      slot = slot < 0 ? 0 : (slot >= W ? W - 1 : slot);   // a corrupt table reads a wrong row, never outside the cache
+    }
+    const T* kr = kv + (int64_t)slot * kv_bs + (int64_t)j * kv_rs + h * D + sub * VN;
+    const vec_t kvec = *reinterpret_cast<const vec_t*>(kr);
+    const vec_t vvec = *reinterpret_cast<const vec_t*>(kr + d_model);
+    float s = 0.0f;
+#pragma unroll
+    for (int i = 0; i < VN; ++i) s += qf[i] * to_f32<T>(kvec[i]);
+#pragma unroll
+    for (int off = LPK >> 1; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+    const float mn = fmaxf(m, s), a = __expf(m - mn), pj = __expf(s - mn);
+    l = l * a + pj;
+#pragma unroll
+    for (int i = 0; i < VN; ++i) o[i] = o[i] * a + pj * to_f32<T>(vvec[i]);
+    m = mn;
+  }
+  // wave merge over the key groups (lanes that hold the same slice of D)
+  float wm = m;
+#pragma unroll
+  for (int off = 32; off >= LPK; off >>= 1) wm = fmaxf(wm, __shfl_xor(wm, off, 64));
+  const float w = (m == -INFINITY) ? 0.0f : __expf(m - wm);
+  l *= w;
+#pragma unroll
+  for (int off = 32; off >= LPK; off >>= 1) l += __shfl_xor(l, off, 64);
+#pragma unroll
+  for (int i = 0; i < VN; ++i) {
+    float v = o[i] * w;
+#pragma unroll
+    for (int off = 32; off >= LPK; off >>= 1) v += __shfl_xor(v, off, 64);
+    o[i] = v;
+  }
+  if ((tid & 63) < LPK) {
+    if (sub == 0) { red[wave][D] = wm; red[wave][D + 1] = l; }
+#pragma unroll
+    for (int i = 0; i < VN; ++i) red[wave][sub * VN + i] = o[i];
+  }
+  __syncthreads();
+  if (tid < D) {
+    const float M4 = fmaxf(fmaxf(red[0][D], red[1][D]), fmaxf(red[2][D], red[3][D]));
+    float L = 0.0f, acc = 0.0f;
+#pragma unroll
+    for (int wv = 0; wv < 4; ++wv) {
+      const float ww = (red[wv][D] == -INFINITY) ? 0.0f : __expf(red[wv][D] - M4);
+      L += red[wv][D + 1] * ww;
+      acc += red[wv][tid] * ww;
+    }
+    out[(int64_t)b * o_bs + h * D + tid] = from_f32<T>(acc / L);
+  }
+}
+
+// One block per row: lp = x - logsumexp(x), x = logits * (1 / temperature); the k largest lp, descending, equal values by ascending id.
+// The k-th largest comes from the radix select above; everything strictly above it is collected in any order (LDS append) and what
+// is still missing is taken from the values EQUAL to it by ascending id; a rank sort over (value, id) then fixes the output order, so
+// nothing depends on the order in which the atomics landed.
+constexpr int BEAM_MAX_K = 64, BEAM_MAX_W = 16;
+
+__global__ __launch_bounds__(SAMPLE_THREADS) void beam_topk_kernel(const float* logits, int64_t ld, int V, float inv_temp, int k, float* top_lp,
+                                                                   int64_t* top_id) {
+  __shared__ unsigned hist[256];
+  __shared__ float red[SAMPLE_THREADS / 64];
+  __shared__ unsigned scan[SAMPLE_THREADS];
+  __shared__ unsigned sel_prefix, sel_remaining, n_above;
+  __shared__ unsigned ckey[BEAM_MAX_K];
+  __shared__ int cid[BEAM_MAX_K];
+  const int tid = threadIdx.x, r = blockIdx.x;
+  const float* row = logits + (int64_t)r * ld;
+  if (tid < BEAM_MAX_K) { ckey[tid] = 0u; cid[tid] = 0; }
+  const unsigned kth = radix_select_kth(row, V, inv_temp, k, hist, &sel_prefix, &sel_remaining);
+  const unsigned n_eq_take = sel_remaining, n_eq = hist[kth & 255u];        // ties with the k-th value: wanted, present
+  const int n_gt = k - (int)n_eq_take;
+  if (tid == 0) n_above = 0u;
+  // ---- log-sum-exp over the whole row
+  float mx = -INFINITY;
+  for (int i = tid; i < V; i += SAMPLE_THREADS) mx = fmaxf(mx, row[i] * inv_temp);
+  mx = block_reduce(mx, red, [](float a, float c) { return fmaxf(a, c); }, -INFINITY);
+  float part = 0.0f;
+  const bool take_all_eq = n_eq == n_eq_take;              // no tie straddles rank k: everything >= the k-th value is in
+  for (int i = tid; i < V; i += SAMPLE_THREADS) {
+    const float x = row[i] * inv_temp;
+    part += expf(x - mx);
+    const unsigned key = f32_sortable(x);
+    if (key > kth || (take_all_eq && key == kth)) {
+      const unsigned at = atomicAdd(&n_above, 1u);
+      if (at < (unsigned)BEAM_MAX_K) { ckey[at] = key; cid[at] = i; }
+    }
+  }
+  const float lse = mx + logf(block_reduce(part, red, [](float a, float c) { return a + c; }, 0.0f));
+  if (!take_all_eq) {                                      // block-uniform.  The first n_eq_take ids among the ties: contiguous chunks + a scan of their counts
+    const int chunk = (V + SAMPLE_THREADS - 1) / SAMPLE_THREADS, i0 = (int)min((int64_t)V, (int64_t)tid * chunk), i1 = (int)min((int64_t)V, (int64_t)i0 + chunk);
+    unsigned mine = 0u;
+    for (int i = i0; i < i1; ++i) mine += f32_sortable(row[i] * inv_temp) == kth ? 1u : 0u;
+    scan[tid] = mine;
+    __syncthreads();
+    for (int o = 1; o < SAMPLE_THREADS; o <<= 1) {
+      const unsigned add = tid >= o ? scan[tid - o] : 0u;
+      __syncthreads();
+      scan[tid] += add;
+      __syncthreads();
+    }
+    unsigned rank = scan[tid] - mine;                      // ties in front of this chunk
+    for (int i = i0; i < i1 && rank < n_eq_take; ++i) {
+      if (f32_sortable(row[i] * inv_temp) == kth) {
+        const unsigned at = (unsigned)n_gt + rank;
+        if (at < (unsigned)BEAM_MAX_K) { ckey[at] = kth; cid[at] = i; }
+        ++rank;
+      }
+    }
+  }
+  __syncthreads();
+  if (tid < k) {
+    const unsigned mk = ckey[tid];
+    const int mi = cid[tid];
+    int rank = 0;
+    for (int c = 0; c < k; ++c) rank += (ckey[c] > mk || (ckey[c] == mk && cid[c] < mi)) ? 1 : 0;
+    top_lp[(int64_t)r * k + rank] = row[mi] * inv_temp - lse;
+    top_id[(int64_t)r * k + rank] = mi;
+  }
+}
+
+// One block: the draw, the selection and the bookkeeping of one beam-search step (models/gpt2_model.py:384-408).
+constexpr int BEAM_SELECT_THREADS = 256;
+
+__global__ __launch_bounds__(BEAM_SELECT_THREADS) void beam_select_kernel(const float* top_lp, const int64_t* top_id, int64_t row_stride, int W, int k,
+                                                                          float* scores, const unsigned long long* seed, int64_t* step,
+                                                                          const int32_t* pos, int32_t* pos_inc, int64_t* cur, int32_t* parent_log,
+                                                                          int64_t* tok_log, int64_t log_rows, int32_t* anc, int64_t anc_ld) {
+  __shared__ float gum[BEAM_MAX_W * BEAM_MAX_K];
+  __shared__ float sc[BEAM_MAX_W], cand[BEAM_MAX_W * BEAM_MAX_W];
+  __shared__ int pick[BEAM_MAX_W * BEAM_MAX_W], surv[BEAM_MAX_W], parent[BEAM_MAX_W];
+  const int tid = threadIdx.x;
+  const int64_t my_step = step[0];
+  const int p = pos[0];
+  const unsigned long long sd = seed[0];
+  if (tid < W) { sc[tid] = scores[tid]; surv[tid] = 0; }
+  if (tid < W * W) pick[tid] = 0;
+  // ---- Gumbel keys: the W largest of lp + G draw W entries without replacement with probability ~ exp(lp)
+  // two trips side by side would be packed into v_pk_*_f32 with op_sel half-swaps, which this library keeps out of its code
+#pragma clang loop vectorize(disable) interleave(disable) unroll(disable)
+  for (int e = tid; e < W * k; e += BEAM_SELECT_THREADS) {
+    const int i = e / k, j = e - i * k;
+    unsigned c[4] = {(unsigned)my_step, (unsigned)((unsigned long long)my_step >> 32), (unsigned)i, 0xBEA30000u | (unsigned)j};
+    philox4x32_10((unsigned)sd, (unsigned)(sd >> 32), c);
+    const float u = ((float)(c[0] >> 8) + 0.5f) * (1.0f / 16777216.0f);
+    gum[e] = top_lp[i * row_stride + j] - logf(-logf(u));
+  }
+  __syncthreads();
+  for (int e = tid; e < W * k; e += BEAM_SELECT_THREADS) {            // draw rank of entry j inside beam i (ties: the lower j first)
+    const int i = e / k, j = e - i * k;
+    const float g = gum[e];
+    int rank = 0;
+    for (int c = 0; c < k; ++c) rank += (gum[i * k + c] > g || (gum[i * k + c] == g && c < j)) ? 1 : 0;
+    if (rank < W) pick[i * W + rank] = j;
+  }
+  __syncthreads();
+  // ---- the W best of the W * W candidates: score descending, then parent, then draw rank (= candidate number ascending)
+  const int nc = W * W;
+  if (tid < nc) cand[tid] = sc[tid / W] + top_lp[(tid / W) * row_stride + pick[tid]];
+  __syncthreads();
+  if (tid < nc) {
+    const float s = cand[tid];
+    int rank = 0;
+    for (int c = 0; c < nc; ++c) rank += (cand[c] > s || (cand[c] == s && c < tid)) ? 1 : 0;
+    if (rank < W) surv[rank] = tid;
+  }
+  __syncthreads();
+  if (tid < W) {
+    const int c = surv[tid], pr = c / W;
+    const int64_t tok = top_id[pr * row_stride + pick[c]];
+    parent[tid] = pr;
+    scores[tid] = cand[c];
+    cur[tid] = tok;
+    if (my_step >= 0 && my_step < log_rows) {
+      parent_log[my_step * W + tid] = pr;
+      tok_log[my_step * W + tid] = tok;
+    }
+  }
+  __syncthreads();
+  // ---- ancestry: the new beam b continues beam parent[b]; one thread owns a column and reads all of it before it writes
+  for (int64_t j = tid; j <= p && j < anc_ld; j += BEAM_SELECT_THREADS) {
+    int old[BEAM_MAX_W];
+#pragma unroll
+    for (int x = 0; x < BEAM_MAX_W; ++x) old[x] = (x < W && j < p) ? anc[x * anc_ld + j] : x;
+    for (int b = 0; b < W; ++b) {
+      const int pr = parent[b];
+      int v = old[0];
+#pragma unroll
+      for (int x = 1; x < BEAM_MAX_W; ++x) v = pr == x ? old[x] : v;
+      anc[b * anc_ld + j] = v;
+    }
+  }
+  if (tid == 0) {                                          // every read of the counters is behind a barrier above
+    step[0] = my_step + 1;
+    if (pos_inc) pos_inc[0] += 1;
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -267,6 +515,49 @@ int fk_sample_topk(const float* logits, int64_t ld, int64_t B, int64_t V, float 
   hipLaunchKernelGGL(sample_topk_kernel, dim3((unsigned)B), dim3(SAMPLE_THREADS), 0, (hipStream_t)stream, logits, ld, (int)V, 1.0f / temperature,
                      (int)(top_k > 0 && top_k < V ? top_k : 0), (const unsigned long long*)seed, step, pos_inc, cur, out, out_ld, out_cols, ticket);
   FK_CHECK_LAUNCH("fk_sample_topk");
+  return FK_OK;
+}
+
+int fk_attn_decode_beam(const void* q, int64_t q_bs, const void* kv, int64_t kv_bs, int64_t kv_rs, const int32_t* anc, int64_t anc_ld, void* out,
+                        int64_t o_bs, const int32_t* pos, int64_t W, int64_t H, int64_t D, float scale, int dtype, void* stream) {
+  FK_CHECK_ARG((dtype == FK_F32 || dtype == FK_BF16) && q && kv && anc && out && pos && W > 0 && W < 65536 && H > 0 && H < 65536 && anc_ld > 0,
+               "fk_attn_decode_beam: bad arguments");
+  FK_CHECK_ARG(D == 16 || D == 32 || D == 64 || D == 128, "fk_attn_decode_beam: head_dim %lld not in {16, 32, 64, 128}", (long long)D);
+  const int64_t vn = dtype == FK_BF16 ? 8 : 4;
+  FK_CHECK_ARG(((uintptr_t)kv & 15) == 0 && kv_bs % vn == 0 && kv_rs % vn == 0 && kv_rs >= 2 * H * D,
+               "fk_attn_decode_beam: cache rows must be 16-byte aligned and hold key|value (kv_bs=%lld, kv_rs=%lld)", (long long)kv_bs, (long long)kv_rs);
+  hipStream_t s = (hipStream_t)stream;
+  dim3 grid((unsigned)H, (unsigned)W), block(256);
+#define FK_ADB(TT, DD) hipLaunchKernelGGL((attn_decode_beam_kernel<TT, DD>), grid, block, 0, s, (const TT*)q, q_bs, (const TT*)kv, kv_bs, kv_rs, anc, anc_ld, (TT*)out, o_bs, pos, (int)W, (int)H, scale)
+  if (dtype == FK_BF16) { if (D == 16) FK_ADB(bf16_t, 16); else if (D == 32) FK_ADB(bf16_t, 32); else if (D == 64) FK_ADB(bf16_t, 64); else FK_ADB(bf16_t, 128); }
+  else { if (D == 16) FK_ADB(float, 16); else if (D == 32) FK_ADB(float, 32); else if (D == 64) FK_ADB(float, 64); else FK_ADB(float, 128); }
+#undef FK_ADB
+  FK_CHECK_LAUNCH("fk_attn_decode_beam");
+  return FK_OK;
+}
+
+int fk_beam_topk(const float* logits, int64_t ld, int64_t R, int64_t V, float temperature, int64_t k, float* top_lp, int64_t* top_id, void* stream) {
+  FK_CHECK_ARG(logits && top_lp && top_id, "fk_beam_topk: null pointer");
+  FK_CHECK_ARG(R > 0 && R < 65536 && V > 0 && V < (1LL << 31) && ld >= V && temperature > 0.0f,
+               "fk_beam_topk: bad arguments (R=%lld V=%lld ld=%lld temperature=%g)", (long long)R, (long long)V, (long long)ld, (double)temperature);
+  FK_CHECK_ARG(k >= 1 && k <= BEAM_MAX_K && k <= V, "fk_beam_topk: k=%lld outside 1 .. min(%d, V=%lld)", (long long)k, BEAM_MAX_K, (long long)V);
+  hipLaunchKernelGGL(beam_topk_kernel, dim3((unsigned)R), dim3(SAMPLE_THREADS), 0, (hipStream_t)stream, logits, ld, (int)V, 1.0f / temperature, (int)k,
+                     top_lp, top_id);
+  FK_CHECK_LAUNCH("fk_beam_topk");
+  return FK_OK;
+}
+
+int fk_beam_select(const float* top_lp, const int64_t* top_id, int64_t row_stride, int64_t W, int64_t k, float* scores, const uint64_t* seed,
+                   int64_t* step, const int32_t* pos, int32_t* pos_inc, int64_t* cur, int32_t* parent_log, int64_t* tok_log, int64_t log_rows,
+                   int32_t* anc, int64_t anc_ld, void* stream) {
+  FK_CHECK_ARG(top_lp && top_id && scores && seed && step && pos && cur && anc, "fk_beam_select: null pointer");
+  FK_CHECK_ARG(W >= 1 && W <= BEAM_MAX_W && k >= W && k <= BEAM_MAX_K, "fk_beam_select: need 1 <= W <= %d and W <= k <= %d (W=%lld k=%lld)", BEAM_MAX_W,
+               BEAM_MAX_K, (long long)W, (long long)k);
+  FK_CHECK_ARG((row_stride == 0 || row_stride >= k) && anc_ld > 0 && log_rows >= 0 && (log_rows == 0 || (parent_log && tok_log)),
+               "fk_beam_select: bad arguments (row_stride=%lld anc_ld=%lld log_rows=%lld)", (long long)row_stride, (long long)anc_ld, (long long)log_rows);
+  hipLaunchKernelGGL(beam_select_kernel, dim3(1), dim3(BEAM_SELECT_THREADS), 0, (hipStream_t)stream, top_lp, top_id, row_stride, (int)W, (int)k, scores,
+                     (const unsigned long long*)seed, step, pos, pos_inc, cur, parent_log, tok_log, log_rows, anc, anc_ld);
+  FK_CHECK_LAUNCH("fk_beam_select");
   return FK_OK;
 }
 

@@ -611,6 +611,74 @@ def attn_decode(qkv: Tensor, kv: Tensor, pos: Tensor, n_head: int) -> Tensor:
     return out
 
 
+# ------------------------------------------------------------------------------------------- beam search on the caches
+BEAM_MAX_WIDTH, BEAM_MAX_TOPK = 16, 64          # the envelope of fk_beam_select / fk_beam_topk
+
+
+class BeamState:
+    """Device-side state of a cached beam search of width W: Philox seed, step counter (= row of the logs the next step writes),
+    cumulative scores [W], the per-step logs parent_log / tok_log [steps, W] the host backtracks through, and the ancestry table
+    anc [W, tmax] (anc[b, j] = the cache slot that holds beam b's key/value row j)."""
+
+    def __init__(self, device, width: int, steps: int, tmax: int, seed: Optional[int] = None):
+        if seed is None:                                   # follows torch.manual_seed like torch.multinomial would
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        self.width = width
+        self.seed = torch.tensor([seed], dtype=torch.int64, device=device)
+        self.step = torch.zeros(1, dtype=torch.int64, device=device)
+        self.scores = torch.zeros(width, dtype=torch.float32, device=device)
+        self.parent_log = torch.empty((max(steps, 1), width), dtype=torch.int32, device=device)
+        self.tok_log = torch.empty((max(steps, 1), width), dtype=torch.int64, device=device)
+        self.anc = torch.empty((width, tmax), dtype=torch.int32, device=device)
+
+
+def attn_decode_beam(qkv: Tensor, kv: Tensor, anc: Tensor, pos: Tensor, n_head: int) -> Tensor:
+    """one causal query per beam against the rows 0..pos[0] of ITS history: row j < pos[0] is read from the cache slot anc[b, j], the
+    row pos[0] from slot b.  qkv [W, 3d] (q = qkv[:, :d]), kv [W, Tmax, 2d], anc int32 [W, >= pos] -> o [W, d]."""
+    W, d3 = qkv.shape
+    d = d3 // 3
+    D = d // n_head
+    assert kv.dtype == qkv.dtype and kv.shape[0] == W and kv.shape[2] == 2 * d and kv.stride(2) == 1 and qkv.stride(1) == 1
+    assert anc.dtype == torch.int32 and anc.dim() == 2 and anc.shape[0] == W and anc.stride(1) == 1
+    assert pos.dtype == torch.int32 and pos.numel() == 1
+    out = torch.empty((W, d), dtype=qkv.dtype, device=qkv.device)
+    call("fk_attn_decode_beam", qkv.data_ptr(), qkv.stride(0), kv.data_ptr(), kv.stride(0), kv.stride(1), anc.data_ptr(), anc.stride(0),
+         out.data_ptr(), d, pos.data_ptr(), W, n_head, D, 1.0 / math.sqrt(D), fk_dtype(qkv), _stream())
+    return out
+
+
+def beam_topk(logits: Tensor, temperature: float, k: int, top_lp: Optional[Tensor] = None, top_id: Optional[Tensor] = None):
+    """log_softmax(logits / temperature) and its k largest entries per row, descending, equal values by ascending id — one launch.
+    logits fp32 [R, V] (row stride >= V) -> top_lp fp32 [R, k], top_id int64 [R, k]."""
+    assert logits.dim() == 2 and logits.dtype == torch.float32 and logits.stride(1) == 1
+    R, V = logits.shape
+    if top_lp is None:
+        top_lp = torch.empty((R, k), dtype=torch.float32, device=logits.device)
+    if top_id is None:
+        top_id = torch.empty((R, k), dtype=torch.int64, device=logits.device)
+    assert top_lp.dtype == torch.float32 and top_id.dtype == torch.int64 and top_lp.is_contiguous() and top_id.is_contiguous()
+    assert tuple(top_lp.shape) == (R, k) and tuple(top_id.shape) == (R, k)
+    call("fk_beam_topk", logits.data_ptr(), logits.stride(0), R, V, float(temperature), int(k), top_lp.data_ptr(), top_id.data_ptr(), _stream())
+    return top_lp, top_id
+
+
+def beam_select(top_lp: Tensor, top_id: Tensor, state: BeamState, cur: Tensor, pos: Tensor, pos_inc: Optional[Tensor] = None,
+                broadcast: bool = False) -> Tensor:
+    """One beam-search step on the device (draw without replacement, keep the W best of W * W, logs, ancestry; see fk_beam_select in
+    include/franken_hip.h).  top_lp / top_id [R, k] from beam_topk, R = W, or any R >= 1 with broadcast=True (every beam reads row 0:
+    the first step, where all beams are one sequence).  Writes cur [W] int64 (returned) and state; pos int32 [1] is the row the step
+    has just appended (negative: leave the ancestry alone); pos_inc (may be pos) is advanced by one."""
+    W, k = state.width, top_lp.shape[1]
+    assert top_lp.dtype == torch.float32 and top_id.dtype == torch.int64 and top_lp.is_contiguous() and top_id.is_contiguous()
+    assert top_lp.shape == top_id.shape and (broadcast or top_lp.shape[0] == W)
+    assert cur.dtype == torch.int64 and cur.is_contiguous() and cur.numel() == W
+    assert pos.dtype == torch.int32 and pos.numel() == 1 and (pos_inc is None or (pos_inc.dtype == torch.int32 and pos_inc.numel() == 1))
+    call("fk_beam_select", top_lp.data_ptr(), top_id.data_ptr(), 0 if broadcast else k, W, k, state.scores.data_ptr(), state.seed.data_ptr(),
+         state.step.data_ptr(), pos.data_ptr(), _ptr(pos_inc), cur.data_ptr(), state.parent_log.data_ptr(), state.tok_log.data_ptr(),
+         state.parent_log.shape[0], state.anc.data_ptr(), state.anc.stride(0), _stream())
+    return cur
+
+
 # ------------------------------------------------------------------------------------------- conv (VQ-VAE tokenizer)
 def im2col1d(x: Tensor, ksize: int, stride: int = 1, dil: int = 1) -> Tensor:
     """x [B, T, C] -> cols [B * Tout, ksize * C] with the causal left padding dil * (ksize - 1); Tout = (T - 1) // stride + 1."""

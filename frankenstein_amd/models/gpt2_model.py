@@ -141,12 +141,13 @@ def _step_linear(x, lin, ln=None, gelu=False, residual=None, step_rows=None, hea
     return y if head_vocab is None else y[:, :head_vocab]
 
 
-def _block_forward_decode(self, x, kv, pos):
-    """One new token per sample with the position in a device int32 (graph-capturable): x [B, d], kv [B, Tmax, 2d]."""
+def _block_forward_decode(self, x, kv, pos, anc=None):
+    """One new token per sample with the position in a device int32 (graph-capturable): x [B, d], kv [B, Tmax, 2d].
+    anc (int32 [B, Tmax]): the samples are beams that share the caches, row j of beam b is read from slot anc[b, j] (K.attn_decode_beam)."""
     at, ml = self.attn, self.mlp
     qkv = _step_linear(x, at.c_attn, ln=self.ln_1)
     K.kv_append_(qkv, kv, pos)
-    o = K.attn_decode(qkv, kv, pos, at.n_head)
+    o = K.attn_decode(qkv, kv, pos, at.n_head) if anc is None else K.attn_decode_beam(qkv, kv, anc, pos, at.n_head)
     x = _step_linear(o, at.c_proj, residual=x)
     a = _step_linear(x, ml.c_fc, ln=self.ln_2, gelu=True)
     return _step_linear(a, ml.c_proj, residual=x)
@@ -326,11 +327,12 @@ class GPT(nn.Module):
         return logits, pos + t
 
     @torch.no_grad()
-    def _decode_logits_dev(self, cur, cache, pos):
-        """last-position logits [B, V] for the tokens `cur` [B] at device position pos (int32[1]); appends to the caches."""
+    def _decode_logits_dev(self, cur, cache, pos, anc=None):
+        """last-position logits [B, V] for the tokens `cur` [B] at device position pos (int32[1]); appends to the caches.
+        anc: the beam ancestry table of a cached beam search (Block.forward_decode)."""
         x = K.gpt_embed_step(cur, self.transformer.wte.weight.detach(), self.transformer.wpe.weight.detach(), pos, E.compute_dtype())
         for li, block in enumerate(self.transformer.h):
-            x = block.forward_decode(x, cache[li], pos)
+            x = block.forward_decode(x, cache[li], pos, anc)
         return _step_linear(x, self.lm_head, ln=self.transformer.ln_f, head_vocab=self.config.vocab_size)
 
     @staticmethod
@@ -412,14 +414,22 @@ class GPT(nn.Module):
         return torch.cat((idx, out), dim=1)[0]
 
     @torch.no_grad()
-    def generate_beam_search(self, idx, max_new_tokens, prefix, temperature=1.0, topk=20, beam_width=5):
+    def generate_beam_search(self, idx, max_new_tokens, prefix, temperature=1.0, topk=20, beam_width=5, use_cache=False, use_graph=None):
         """Stochastic beam search of the reference (models/gpt2_model.py:355-416): every step each of the `beam_width` beams draws
         `beam_width` continuations WITHOUT replacement from its `topk` most likely tokens, the `beam_width` best-scoring
         (cumulative log-probability) of the beam_width^2 candidates survive; returns the best beam's ids.  Batch size 1.
-        Host-side bookkeeping around the kernel forward (one batched forward of all beams per step)."""
+        Default: host-side bookkeeping around the kernel forward (one batched forward of all beams per step, torch.multinomial draws).
+        use_cache=True: the prefix and the prompt run once, every step is one cached decode step of all beams with the draw, the
+        selection and the bookkeeping on the device (_beam_search_cached; its draws are a Philox stream seeded from torch's generator,
+        not torch.multinomial's).  Outside its envelope (sequence longer than block_size, beam_width > 16, topk > 64 or > vocabulary)
+        the call takes the re-forward loop."""
         if topk is None:
             topk = 2 * beam_width
         self.eval()
+        total = (0 if prefix is None else prefix.shape[1]) + idx.shape[1] + max_new_tokens
+        if (use_cache and idx.is_cuda and idx.shape[0] == 1 and max_new_tokens > 0 and total <= self.config.block_size
+                and 1 <= beam_width <= K.BEAM_MAX_WIDTH and beam_width <= topk <= min(K.BEAM_MAX_TOPK, self.config.vocab_size)):
+            return self._beam_search_cached(idx, max_new_tokens, prefix, temperature, topk, beam_width, use_graph)
         beams = idx.repeat(beam_width, 1)
         scores = torch.zeros(beam_width, device=idx.device)
         prefix = prefix.expand(beam_width, -1, -1)
@@ -437,21 +447,100 @@ class GPT(nn.Module):
         return beams[scores.argmax()]
 
     @torch.no_grad()
-    def beam_search(self, idx, max_new_tokens, prefix, temperature=1.0, topk=20, beam_width=3):
+    def _beam_search_cached(self, idx, max_new_tokens, prefix, temperature, topk, W, use_graph):
+        """generate_beam_search on per-layer caches [W, total, 2d] that are never reordered: slot b holds the rows beam position b
+        wrote, the int32 ancestry table names the slot of every row of every beam, and K.beam_select rewrites that table when it
+        picks the survivors.  A step is embed -> blocks (K.attn_decode_beam) -> head -> K.beam_topk -> K.beam_select: nothing in
+        it waits for the host, so with use_graph (default: from 64 new tokens, as in generate) it is captured once and replayed.
+        Sets last_beams (W id lists, prompt included) and last_beam_scores."""
+        dev, d = idx.device, self.config.n_embd
+        t_ctx = 0 if prefix is None else prefix.shape[1]
+        p0 = t_ctx + idx.shape[1]
+        total = p0 + max_new_tokens
+        if use_graph is None:
+            use_graph = max_new_tokens >= 64
+        cache = [torch.empty((W, total, 2 * d), dtype=E.compute_dtype(), device=dev) for _ in self.transformer.h]
+        logits0, _ = self._cached_logits(idx, [c[:1] for c in cache], 0, None if prefix is None else _prep(prefix))   # slot 0 <- prefix + prompt
+        state = K.BeamState(dev, W, max_new_tokens, total)
+        state.anc[:, :p0] = 0
+        cur = torch.empty(W, dtype=torch.int64, device=dev)
+        top_lp = torch.empty((W, topk), dtype=torch.float32, device=dev)
+        top_id = torch.empty((W, topk), dtype=torch.int64, device=dev)
+        lg0 = logits0.float()
+        # first step: all beams are the one prefilled sequence, they draw from the same row; no row has been appended, the table stays
+        K.beam_topk(lg0 if lg0.stride(-1) == 1 else lg0.contiguous(), temperature, topk, top_lp[:1], top_id[:1])
+        K.beam_select(top_lp[:1], top_id[:1], state, cur, torch.tensor([-1], dtype=torch.int32, device=dev), broadcast=True)
+        pos = torch.tensor([p0], dtype=torch.int32, device=dev)
+
+        def step():
+            K.beam_topk(self._decode_logits_dev(cur, cache, pos, state.anc), temperature, topk, top_lp, top_id)
+            K.beam_select(top_lp, top_id, state, cur, pos, pos_inc=pos)
+
+        if use_graph and max_new_tokens > 1:
+            n_eager = min(2, max_new_tokens - 1)            # warm-up (allocator, lazy shadows) before the capture
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                for _ in range(n_eager):
+                    step()
+                remaining = max_new_tokens - 1 - n_eager
+                if remaining > 0:
+                    graph = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(graph, stream=side):      # records the step, does not run it
+                        step()
+                    for _ in range(remaining):
+                        graph.replay()
+            torch.cuda.current_stream().wait_stream(side)
+        else:
+            for _ in range(max_new_tokens - 1):
+                step()
+        parents, toks, scores = state.parent_log.cpu().tolist(), state.tok_log.cpu().tolist(), state.scores.cpu()
+        prompt = idx[0].cpu().tolist()
+        beams = []
+        for b in range(W):                                  # walk every final beam back through its parents
+            seq = []
+            for t in range(max_new_tokens - 1, -1, -1):
+                seq.append(toks[t][b])
+                b = parents[t][b]
+            beams.append(prompt + seq[::-1])
+        self.last_beams = beams
+        self.last_beam_scores = scores.tolist()
+        return torch.tensor(beams[int(scores.argmax())], dtype=idx.dtype, device=dev)
+
+    @torch.no_grad()
+    def beam_search(self, idx, max_new_tokens, prefix, temperature=1.0, topk=20, beam_width=3, use_cache=False):
         """Deterministic beam search of the reference (models/gpt2_model.py:419-454), including its quirk: the running context
         `idx` is shared by all beams and grows by every beam's last token in turn (it is not forked per beam), so the scores are
-        those of that merged sequence.  Returns the token list of the best entry [idx[0, 0], t1, t2, ...].  Batch size 1."""
+        those of that merged sequence.  Returns the token list of the best entry [idx[0, 0], t1, t2, ...].  Batch size 1.
+        use_cache=True: that one growing sequence is prefilled once and every beam entry costs one cached decode step at batch 1
+        and one K.beam_topk instead of a forward of the whole context (same tokens, same scores)."""
         self.eval()
-        _, logits = self(idx, prefix=prefix)
-        lp, ix = torch.topk(torch.log_softmax(logits[:, -1, :].float(), dim=-1), beam_width)
+        t_ctx = 0 if prefix is None else prefix.shape[1]
+        total = t_ctx + idx.shape[1] + max(0, max_new_tokens - 1) * beam_width
+        cached = (use_cache and idx.is_cuda and idx.shape[0] == 1 and total <= self.config.block_size
+                  and 1 <= beam_width <= min(K.BEAM_MAX_TOPK, self.config.vocab_size))
+        if cached:
+            dev = idx.device
+            cache = [torch.empty((1, total, 2 * self.config.n_embd), dtype=E.compute_dtype(), device=dev) for _ in self.transformer.h]
+            logits, p0 = self._cached_logits(idx, cache, 0, None if prefix is None else _prep(prefix))
+            pos = torch.tensor([p0], dtype=torch.int32, device=dev)
+            lg = logits.float()
+            lp, ix = K.beam_topk(lg if lg.stride(-1) == 1 else lg.contiguous(), 1.0, beam_width)
+        else:
+            _, logits = self(idx, prefix=prefix)
+            lp, ix = torch.topk(torch.log_softmax(logits[:, -1, :].float(), dim=-1), beam_width)
         first = idx[0, 0].item()
         beam = [(ix[0, i], lp[0, i], [first, ix[0, i].item()]) for i in range(beam_width)]
         for _ in range(max_new_tokens - 1):
             cands = []
             for last, score, toks in beam:
-                idx = torch.cat((idx, last.reshape(1, 1)), dim=-1)
-                _, logits = self(idx, prefix=prefix)
-                lp, ix = torch.topk(torch.log_softmax(logits[:, -1, :].float(), dim=-1), beam_width)
+                if cached:
+                    lp, ix = K.beam_topk(self._decode_logits_dev(last.reshape(1).clone(), cache, pos), 1.0, beam_width)
+                    pos += 1
+                else:
+                    idx = torch.cat((idx, last.reshape(1, 1)), dim=-1)
+                    _, logits = self(idx, prefix=prefix)
+                    lp, ix = torch.topk(torch.log_softmax(logits[:, -1, :].float(), dim=-1), beam_width)
                 for i in range(beam_width):
                     cands.append((ix[0, i], score + lp[0, i], toks + [ix[0, i].item()]))
             beam = sorted(cands, key=lambda c: float(c[1]), reverse=True)[:beam_width]

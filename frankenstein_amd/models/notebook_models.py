@@ -77,3 +77,13 @@ class Franky(nn.Module):
         prefix = self.brain_model(xin)
         ids = torch.full((1, 1), eot, dtype=torch.long, device=self.device)
         return self.llm_model.generate(ids, max_new_tokens, prefix=prefix, temperature=temperature, top_k=top_k)
+
+    @torch.no_grad()
+    def generate_beam(self, x, max_new_tokens=25, temperature=1.0, topk=20, beam_width=5, eot=50256):
+        """x: numpy [T, C].  Brain features -> prefix -> the stochastic beam search of the decoder on its key/value caches
+        (GPT.generate_beam_search, use_cache=True).  Returns the best beam's ids, `eot` first."""
+        xin = torch.from_numpy(x[None]).to(self.device).float()
+        prefix = self.brain_model(xin)
+        ids = torch.full((1, 1), eot, dtype=torch.long, device=self.device)
+        return self.llm_model.generate_beam_search(ids, max_new_tokens, prefix, temperature=temperature, topk=topk, beam_width=beam_width,
+                                                   use_cache=True)

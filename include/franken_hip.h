@@ -237,6 +237,30 @@ int fk_sample_topk(const float* logits, int64_t ld, int64_t B, int64_t V, float 
                    int64_t* step, int32_t* pos_inc, int64_t* cur, int64_t* out, int64_t out_ld, int64_t out_cols, uint32_t* ticket,
                    void* stream);
 
+/* ---- beam search on the key/value caches (models/gpt2_model.py:355-454).  The W beams share one set of caches [W, Tmax, 2d]: slot b
+ * holds the rows beam position b wrote, and the int32 ancestry table anc[b*anc_ld + j] names the slot that holds beam b's row j, so
+ * reordering the beams rewrites the table and never copies a cache.
+ * fk_attn_decode_beam: fk_attn_decode with one query per beam (q + b*q_bs + h*D) whose key row j < *pos is at
+ *   kv + slot*kv_bs + j*kv_rs + h*D with slot = anc[b*anc_ld + j] clamped into [0, W) (value at + H*D); the row j == *pos is in slot b,
+ *   where fk_kv_append has just written it.  D in {16, 32, 64, 128}; kv 16-byte aligned, kv_bs and kv_rs multiples of 16 bytes.
+ * fk_beam_topk: per row r < R of fp32 logits (row stride ld >= V): x = logits / temperature, lp = x - logsumexp(x); the k largest lp in
+ *   descending order to top_lp[r*k ..] and their ids to top_id[r*k ..]; equal values by ascending id, and of the values tied with the
+ *   k-th the lowest ids are kept.  Deterministic.  1 <= k <= min(64, V), V < 2^31, temperature > 0.
+ * fk_beam_select: one step of the stochastic beam search, one block.  Beam i reads row i*row_stride of top_lp / top_id (row_stride = 0:
+ *   every beam reads row 0, the first step) and draws W of its k entries without replacement with probability ~ exp(top_lp) by the
+ *   Gumbel-top-W rule: key = top_lp[i][j] - logf(-logf(u)), u = ((c0 >> 8) + 0.5) / 2^24 in fp32, c0 = word 0 of Philox4x32-10 keyed by
+ *   *seed on the counter (step_lo, step_hi, i, 0xBEA30000 | j); the W largest keys win, larger key = earlier draw rank (ties: lower j).
+ *   Of the W*W candidates (score = scores[i] + top_lp[i][j]) the W best survive, ordered by score descending, then parent, then draw
+ *   rank.  Writes scores[W], cur[W] (the tokens), parent_log[*step*W ..] / tok_log[*step*W ..] while *step < log_rows, and the ancestry:
+ *   for every column j <= *pos (j < anc_ld): anc[b][j] = old[parent[b]][j] with old[x][*pos] = x (*pos < 0: no column).  Then
+ *   *step += 1 and, if pos_inc != NULL (it may be pos), *pos_inc += 1.  1 <= W <= 16, W <= k <= 64.                                */
+int fk_attn_decode_beam(const void* q, int64_t q_bs, const void* kv, int64_t kv_bs, int64_t kv_rs, const int32_t* anc, int64_t anc_ld, void* out,
+                        int64_t o_bs, const int32_t* pos, int64_t W, int64_t H, int64_t D, float scale, int dtype, void* stream);
+int fk_beam_topk(const float* logits, int64_t ld, int64_t R, int64_t V, float temperature, int64_t k, float* top_lp, int64_t* top_id, void* stream);
+int fk_beam_select(const float* top_lp, const int64_t* top_id, int64_t row_stride, int64_t W, int64_t k, float* scores, const uint64_t* seed,
+                   int64_t* step, const int32_t* pos, int32_t* pos_inc, int64_t* cur, int32_t* parent_log, int64_t* tok_log, int64_t log_rows,
+                   int32_t* anc, int64_t anc_ld, void* stream);
+
 /* ---- VQ-VAE tokenizer convolutions (models/vq_brain.py), channels-last [B, T, C], causal left padding dil*(K-1):
  * fk_im2col1d: cols[b, t, k, :] = x[b, t*stride + k*dil - pad, :] (zeros outside), Tout = (T-1)/stride + 1, so that
  *   CausalConv1d (:22-28) = fk_gemm_nt(cols, W') with W'[o, k*Cin + c] = W[o, c, k], and CausalConvTranspose1d(kernel 2s,

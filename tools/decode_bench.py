@@ -2,6 +2,7 @@
 
     python tools/decode_bench.py --model gpt2 --batch 1        # GPT-2 124M, the reference's decoder (franky_baseline_gpt2.ipynb)
     python tools/decode_bench.py --model nano --all-modes       # cfg1's gpt2-nano: re-forward vs kv-cache vs kv-cache + hipGraph
+    python tools/decode_bench.py --model gpt2 --beam 5 --topk 20 --new-tokens 25     # generate_beam_search: cached (+ hipGraph) vs re-forward
 
 Random weights, a 32-token brain prefix, one start token, top_k = 1.  A generate() call also pays the prefill and, in graph mode, the
 capture, so the per-token figure is the MARGINAL cost: (time of N new tokens - time of N/4 new tokens) / (3N/4), medians over the
@@ -45,6 +46,43 @@ def timed(g, start, prefix, n_new, kw, repeats):
     return statistics.median(ts), min(ts), max(ts)
 
 
+def beam_bench(g, a, prefix, start):
+    """generate_beam_search of width --beam: cached + hipGraph, cached eager and the re-forward loop (use_cache=False) in one process, the
+    repeats of the modes interleaved so that a drift of the machine hits all of them; beside them generate() at batch = beam width in
+    graph mode, the same decode step without the two beam launches.  Per-step figures are marginal like the per-token ones: (time of N
+    new tokens - time of N/4) / (3N/4); for the re-forward loop, whose steps grow with the sequence, that is the mean step between
+    N/4 and N."""
+    W, n, n4 = a.beam, a.new_tokens, max(1, a.new_tokens // 4)
+    beam = lambda kw: (lambda k: g.generate_beam_search(start, k, prefix, topk=a.topk, beam_width=W, **kw))
+    startW, prefixW = start.repeat(W, 1), prefix.repeat(W, 1, 1)
+    modes = {"beam kv-cache + hipGraph": beam(dict(use_cache=True, use_graph=True)),
+             "beam kv-cache (eager)": beam(dict(use_cache=True, use_graph=False)),
+             "beam re-forward": beam(dict(use_cache=False)),
+             f"generate batch {W} + hipGraph": lambda k: g.generate(startW, k, prefix=prefixW, top_k=a.topk, use_cache=True, use_graph=True)}
+    times = {name: {n4: [], n: []} for name in modes}
+    for name, fn in modes.items():                          # warm up both lengths of every mode
+        for k in (n4, n):
+            fn(k)
+    for _ in range(a.repeats):
+        for k in (n4, n):
+            for name, fn in modes.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn(k)
+                torch.cuda.synchronize()
+                times[name][k].append(time.perf_counter() - t0)
+    steps = {}
+    for name in modes:
+        t4, t = statistics.median(times[name][n4]), statistics.median(times[name][n])
+        steps[name] = (t - t4) / (n - n4) if n > n4 else t / n
+        print(f"{name:30s}: {steps[name] * 1e6:9.1f} us/step (marginal)   | whole call {t * 1e3:8.2f} ms [{min(times[name][n]) * 1e3:.2f} .. "
+              f"{max(times[name][n]) * 1e3:.2f}], {n4} tokens {t4 * 1e3:8.2f} ms")
+    ref = steps["beam re-forward"]
+    print(f"re-forward / cached + hipGraph = {ref / steps['beam kv-cache + hipGraph']:.2f}x per step, re-forward / cached eager = "
+          f"{ref / steps['beam kv-cache (eager)']:.2f}x; whole call {statistics.median(times['beam re-forward'][n]) / statistics.median(times['beam kv-cache + hipGraph'][n]):.2f}x "
+          f"and {statistics.median(times['beam re-forward'][n]) / statistics.median(times['beam kv-cache (eager)'][n]):.2f}x")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", choices=sorted(MODELS), default="nano")
@@ -53,6 +91,8 @@ def main():
     ap.add_argument("--dtype", choices=["bf16", "fp32"], default="bf16")
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--all-modes", action="store_true", help="also time the full re-forward and the eager kv-cache loop (default: hipGraph only)")
+    ap.add_argument("--beam", type=int, default=0, help="beam width: time generate_beam_search (cached + hipGraph, cached eager, re-forward) instead of generate")
+    ap.add_argument("--topk", type=int, default=20, help="top-k of the beam search's draws (with --beam)")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "decode_bench needs the GPU"
 
@@ -67,6 +107,10 @@ def main():
     floor = wbytes / HBM_PEAK
     print(f"model {a.model} ({sum(p.numel() for p in g.parameters()) / 1e6:.1f} M parameters), {a.dtype}, batch {B}, {n} new tokens, "
           f"{a.repeats} repeats; weights per step {wbytes / 1e6:.1f} MB -> ceiling {floor * 1e6:.1f} us/step = {B / floor:.0f} tokens/s")
+    if a.beam:
+        assert B == 1, "the beam search is batch 1"
+        print(f"beam width {a.beam}, topk {a.topk}")
+        return beam_bench(g, a, prefix, start)
     for name, kw in MODES.items():
         if not a.all_modes and name != "kv-cache + hipGraph":
             continue
