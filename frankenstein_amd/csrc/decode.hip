@@ -6,6 +6,8 @@
 // All three read the position from a device int32 (bumped by the host graph between steps).  HBM / latency-bound, no MFMA.
 //   fk_sample_topk     the sampling tail of GPT.generate as one launch
 //   fk_attn_decode_beam / fk_beam_topk / fk_beam_select    the step of the beam search on shared caches (ancestry table), further down
+//   fk_attn_decode_beam_grouped / fk_beam_select_grouped   the same step for S sentences x W beams at once: rows g * W + b, a table of
+//                       LOCAL slots, fk_kv_append folded into the attention launch, one select block per sentence + a ticket
 #include "fk_common.h"
 
 namespace {
@@ -250,15 +252,29 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_topk_kernel(const float
 // each, so a wave reads 64 / LPK whole rows per trip as contiguous 16-byte pieces; the score is summed across the LPK lanes, every
 // lane keeps the running (max, sum) of its key group and its own 16-byte slice of the output, and the groups are merged across the
 // wave (lanes with the same slice) and then across the four waves.
-template <typename T, int D>
-__global__ __launch_bounds__(256) void attn_decode_beam_kernel(const T* q, int64_t q_bs, const T* kv, int64_t kv_bs, int64_t kv_rs, const int32_t* anc,
-                                                               int64_t anc_ld, T* out, int64_t o_bs, const int32_t* pos, int W, int H, float scale) {
+//
+// GROUPED: the rows are S sentences x W beams, row b = g * W + beam, and the table holds LOCAL slots: row j < pos of row b lives in slot
+// g * W + clamp(anc[b, j], 0, W - 1), so a corrupt entry stays inside its own sentence.  tmax (rows of a cache slot, > 0) bounds the
+// position: *pos >= tmax (or >= anc_ld) counts as the last row, never a read or a write outside the cache.  append != 0 folds fk_kv_append
+// into the launch: q is then the whole [q | k | v] row, and the LPK lanes that own key *pos load head h's slices of k and v from it,
+// store them to kv[b, *pos] and use them from their registers, so no lane reads what another lane or another block wrote.
+template <typename T, int D, bool GROUPED>
+__global__ __launch_bounds__(256) void attn_decode_beam_kernel(const T* q, int64_t q_bs, T* kv, int64_t kv_bs, int64_t kv_rs, int tmax, const int32_t* anc,
+                                                               int64_t anc_ld, T* out, int64_t o_bs, const int32_t* pos, int W, int H, float scale,
+                                                               int append) {
   constexpr int VN = Vec16<T>::N, LPK = D / VN, GROUPS = 256 / LPK;
   typedef T vec_t __attribute__((ext_vector_type(VN)));
   __shared__ float red[4][D + 2];
   const int h = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, wave = tid >> 6;
   const int sub = tid % LPK, grp = tid / LPK;
-  const int p = pos[0], nk = p + 1;
+  int p = pos[0];
+  int base = 0;                                           // first slot of this row's sentence
+  if constexpr (GROUPED) {
+    base = (b / W) * W;
+    const int last = (int)(anc_ld < (int64_t)tmax ? anc_ld : (int64_t)tmax) - 1;
+    p = p > last ? last : p;
+  }
+  const int nk = p + 1;
   const int d_model = H * D;
   float qf[VN], o[VN];
 #pragma unroll
@@ -269,14 +285,23 @@ __global__ __launch_bounds__(256) void attn_decode_beam_kernel(const T* q, int64
   float m = -INFINITY, l = 0.0f;
   const int32_t* arow = anc + (int64_t)b * anc_ld;
   for (int j = grp; j < nk; j += GROUPS) {
-    int slot = b;                                         // the newest row is the beam's own (fk_kv_append has just written it)
+    int slot = b - base;                                  // the newest row is the beam's own (fk_kv_append has just written it, or this launch does)
     if (j < p) {
       slot = arow[j];
       slot = slot < 0 ? 0 : (slot >= W ? W - 1 : slot);   // a corrupt table reads a wrong row, never outside the cache
     }
-    const T* kr = kv + (int64_t)slot * kv_bs + (int64_t)j * kv_rs + h * D + sub * VN;
-    const vec_t kvec = *reinterpret_cast<const vec_t*>(kr);
-    const vec_t vvec = *reinterpret_cast<const vec_t*>(kr + d_model);
+    T* kr = kv + (int64_t)(base + slot) * kv_bs + (int64_t)j * kv_rs + h * D + sub * VN;
+    vec_t kvec, vvec;
+    if (GROUPED && append && j == p) {                    // slot == b - base here: the row is this block's own
+      const T* nr = q + (int64_t)b * q_bs + d_model + h * D + sub * VN;
+      kvec = *reinterpret_cast<const vec_t*>(nr);
+      vvec = *reinterpret_cast<const vec_t*>(nr + d_model);
+      *reinterpret_cast<vec_t*>(kr) = kvec;
+      *reinterpret_cast<vec_t*>(kr + d_model) = vvec;
+    } else {
+      kvec = *reinterpret_cast<const vec_t*>(kr);
+      vvec = *reinterpret_cast<const vec_t*>(kr + d_model);
+    }
     float s = 0.0f;
 #pragma unroll
     for (int i = 0; i < VN; ++i) s += qf[i] * to_f32<T>(kvec[i]);
@@ -394,16 +419,35 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void beam_topk_kernel(const float* 
 // One block: the draw, the selection and the bookkeeping of one beam-search step (models/gpt2_model.py:384-408).
 constexpr int BEAM_SELECT_THREADS = 256;
 
-__global__ __launch_bounds__(BEAM_SELECT_THREADS) void beam_select_kernel(const float* top_lp, const int64_t* top_id, int64_t row_stride, int W, int k,
-                                                                          float* scores, const unsigned long long* seed, int64_t* step,
+//
+// GROUPED: one block per sentence g = blockIdx.x of gridDim.x, each running the same step on ITS W beams: top_lp / top_id rows at
+// g * group_stride + i * row_stride, scores / cur / the table rows g * W .., the logs [steps, S, W], the Philox key seed[g].  The table
+// entries are local slots in [0, W), so the ancestry update is the one-sentence update on the rows of the sentence.  All blocks read the
+// one step counter and the one position on entry; the last block to finish (ticket) advances them, as in sample_topk_kernel.
+template <bool GROUPED>
+__global__ __launch_bounds__(BEAM_SELECT_THREADS) void beam_select_kernel(const float* top_lp, const int64_t* top_id, int64_t row_stride, int64_t group_stride,
+                                                                          int W, int k, float* scores, const unsigned long long* seed, int64_t* step,
                                                                           const int32_t* pos, int32_t* pos_inc, int64_t* cur, int32_t* parent_log,
-                                                                          int64_t* tok_log, int64_t log_rows, int32_t* anc, int64_t anc_ld) {
+                                                                          int64_t* tok_log, int64_t log_rows, int32_t* anc, int64_t anc_ld,
+                                                                          unsigned* ticket) {
   __shared__ float gum[BEAM_MAX_W * BEAM_MAX_K];
   __shared__ float sc[BEAM_MAX_W], cand[BEAM_MAX_W * BEAM_MAX_W];
   __shared__ int pick[BEAM_MAX_W * BEAM_MAX_W], surv[BEAM_MAX_W], parent[BEAM_MAX_W];
   const int tid = threadIdx.x;
-  const int64_t my_step = step[0];
+  const int64_t my_step = step[0];                       // read before anybody can advance it (the advance happens after the last block)
   const int p = pos[0];
+  int64_t log_ld = W;                                    // one row of the logs
+  if constexpr (GROUPED) {
+    const int g = blockIdx.x;
+    top_lp += g * group_stride;
+    top_id += g * group_stride;
+    scores += g * W;
+    cur += g * W;
+    seed += g;
+    anc += (int64_t)g * W * anc_ld;
+    log_ld = (int64_t)gridDim.x * W;
+    if (parent_log) { parent_log += g * W; tok_log += g * W; }
+  }
   const unsigned long long sd = seed[0];
   if (tid < W) { sc[tid] = scores[tid]; surv[tid] = 0; }
   if (tid < W * W) pick[tid] = 0;
@@ -444,8 +488,8 @@ __global__ __launch_bounds__(BEAM_SELECT_THREADS) void beam_select_kernel(const 
     scores[tid] = cand[c];
     cur[tid] = tok;
     if (my_step >= 0 && my_step < log_rows) {
-      parent_log[my_step * W + tid] = pr;
-      tok_log[my_step * W + tid] = tok;
+      parent_log[my_step * log_ld + tid] = pr;
+      tok_log[my_step * log_ld + tid] = tok;
     }
   }
   __syncthreads();
@@ -462,7 +506,17 @@ __global__ __launch_bounds__(BEAM_SELECT_THREADS) void beam_select_kernel(const 
       anc[b * anc_ld + j] = v;
     }
   }
-  if (tid == 0) {                                          // every read of the counters is behind a barrier above
+  if constexpr (GROUPED) {
+    __syncthreads();                                       // the whole block has written its rows of the table
+    if (tid == 0) {
+      __threadfence();
+      if (atomicAdd(ticket, 1u) == gridDim.x - 1) {        // every block has read step[0] and pos[0] and has written its sentence
+        ticket[0] = 0u;
+        step[0] = my_step + 1;
+        if (pos_inc) pos_inc[0] += 1;
+      }
+    }
+  } else if (tid == 0) {                                   // every read of the counters is behind a barrier above
     step[0] = my_step + 1;
     if (pos_inc) pos_inc[0] += 1;
   }
@@ -528,7 +582,7 @@ int fk_attn_decode_beam(const void* q, int64_t q_bs, const void* kv, int64_t kv_
                "fk_attn_decode_beam: cache rows must be 16-byte aligned and hold key|value (kv_bs=%lld, kv_rs=%lld)", (long long)kv_bs, (long long)kv_rs);
   hipStream_t s = (hipStream_t)stream;
   dim3 grid((unsigned)H, (unsigned)W), block(256);
-#define FK_ADB(TT, DD) hipLaunchKernelGGL((attn_decode_beam_kernel<TT, DD>), grid, block, 0, s, (const TT*)q, q_bs, (const TT*)kv, kv_bs, kv_rs, anc, anc_ld, (TT*)out, o_bs, pos, (int)W, (int)H, scale)
+#define FK_ADB(TT, DD) hipLaunchKernelGGL((attn_decode_beam_kernel<TT, DD, false>), grid, block, 0, s, (const TT*)q, q_bs, (TT*)kv, kv_bs, kv_rs, 0, anc, anc_ld, (TT*)out, o_bs, pos, (int)W, (int)H, scale, 0)
   if (dtype == FK_BF16) { if (D == 16) FK_ADB(bf16_t, 16); else if (D == 32) FK_ADB(bf16_t, 32); else if (D == 64) FK_ADB(bf16_t, 64); else FK_ADB(bf16_t, 128); }
   else { if (D == 16) FK_ADB(float, 16); else if (D == 32) FK_ADB(float, 32); else if (D == 64) FK_ADB(float, 64); else FK_ADB(float, 128); }
 #undef FK_ADB
@@ -555,9 +609,49 @@ int fk_beam_select(const float* top_lp, const int64_t* top_id, int64_t row_strid
                BEAM_MAX_K, (long long)W, (long long)k);
   FK_CHECK_ARG((row_stride == 0 || row_stride >= k) && anc_ld > 0 && log_rows >= 0 && (log_rows == 0 || (parent_log && tok_log)),
                "fk_beam_select: bad arguments (row_stride=%lld anc_ld=%lld log_rows=%lld)", (long long)row_stride, (long long)anc_ld, (long long)log_rows);
-  hipLaunchKernelGGL(beam_select_kernel, dim3(1), dim3(BEAM_SELECT_THREADS), 0, (hipStream_t)stream, top_lp, top_id, row_stride, (int)W, (int)k, scores,
-                     (const unsigned long long*)seed, step, pos, pos_inc, cur, parent_log, tok_log, log_rows, anc, anc_ld);
+  hipLaunchKernelGGL(beam_select_kernel<false>, dim3(1), dim3(BEAM_SELECT_THREADS), 0, (hipStream_t)stream, top_lp, top_id, row_stride, (int64_t)0, (int)W,
+                     (int)k, scores, (const unsigned long long*)seed, step, pos, pos_inc, cur, parent_log, tok_log, log_rows, anc, anc_ld, (unsigned*)nullptr);
   FK_CHECK_LAUNCH("fk_beam_select");
+  return FK_OK;
+}
+
+int fk_attn_decode_beam_grouped(const void* qkv, int64_t q_bs, void* kv, int64_t kv_bs, int64_t kv_rs, int64_t tmax, const int32_t* anc, int64_t anc_ld,
+                                void* out, int64_t o_bs, const int32_t* pos, int64_t S, int64_t W, int64_t H, int64_t D, float scale, int append, int dtype,
+                                void* stream) {
+  FK_CHECK_ARG((dtype == FK_F32 || dtype == FK_BF16) && qkv && kv && anc && out && pos && W > 0 && W < 65536 && H > 0 && H < 65536 && anc_ld > 0,
+               "fk_attn_decode_beam_grouped: bad arguments");
+  FK_CHECK_ARG(S >= 1 && S < 65536 && S * W < 65536, "fk_attn_decode_beam_grouped: need S >= 1 and S * W < 65536 rows (S=%lld W=%lld)", (long long)S, (long long)W);
+  FK_CHECK_ARG(tmax > 0 && tmax < (1LL << 31), "fk_attn_decode_beam_grouped: tmax=%lld", (long long)tmax);
+  FK_CHECK_ARG(D == 16 || D == 32 || D == 64 || D == 128, "fk_attn_decode_beam_grouped: head_dim %lld not in {16, 32, 64, 128}", (long long)D);
+  const int64_t vn = dtype == FK_BF16 ? 8 : 4;
+  FK_CHECK_ARG(((uintptr_t)kv & 15) == 0 && kv_bs % vn == 0 && kv_rs % vn == 0 && kv_rs >= 2 * H * D,
+               "fk_attn_decode_beam_grouped: cache rows must be 16-byte aligned and hold key|value (kv_bs=%lld, kv_rs=%lld)", (long long)kv_bs, (long long)kv_rs);
+  FK_CHECK_ARG(!append || (((uintptr_t)qkv & 15) == 0 && q_bs % vn == 0 && q_bs >= 3 * H * D),
+               "fk_attn_decode_beam_grouped: append reads [q | k | v] rows as 16-byte vectors (q_bs=%lld)", (long long)q_bs);
+  hipStream_t s = (hipStream_t)stream;
+  dim3 grid((unsigned)H, (unsigned)(S * W)), block(256);
+#define FK_ADB(TT, DD) hipLaunchKernelGGL((attn_decode_beam_kernel<TT, DD, true>), grid, block, 0, s, (const TT*)qkv, q_bs, (TT*)kv, kv_bs, kv_rs, (int)tmax, anc, anc_ld, (TT*)out, o_bs, pos, (int)W, (int)H, scale, append)
+  if (dtype == FK_BF16) { if (D == 16) FK_ADB(bf16_t, 16); else if (D == 32) FK_ADB(bf16_t, 32); else if (D == 64) FK_ADB(bf16_t, 64); else FK_ADB(bf16_t, 128); }
+  else { if (D == 16) FK_ADB(float, 16); else if (D == 32) FK_ADB(float, 32); else if (D == 64) FK_ADB(float, 64); else FK_ADB(float, 128); }
+#undef FK_ADB
+  FK_CHECK_LAUNCH("fk_attn_decode_beam_grouped");
+  return FK_OK;
+}
+
+int fk_beam_select_grouped(const float* top_lp, const int64_t* top_id, int64_t row_stride, int64_t group_stride, int64_t S, int64_t W, int64_t k,
+                           float* scores, const uint64_t* seed, int64_t* step, const int32_t* pos, int32_t* pos_inc, int64_t* cur, int32_t* parent_log,
+                           int64_t* tok_log, int64_t log_rows, int32_t* anc, int64_t anc_ld, uint32_t* ticket, void* stream) {
+  FK_CHECK_ARG(top_lp && top_id && scores && seed && step && pos && cur && anc && ticket, "fk_beam_select_grouped: null pointer");
+  FK_CHECK_ARG(W >= 1 && W <= BEAM_MAX_W && k >= W && k <= BEAM_MAX_K, "fk_beam_select_grouped: need 1 <= W <= %d and W <= k <= %d (W=%lld k=%lld)",
+               BEAM_MAX_W, BEAM_MAX_K, (long long)W, (long long)k);
+  FK_CHECK_ARG(S >= 1 && S * W < 65536, "fk_beam_select_grouped: need S >= 1 and S * W < 65536 rows (S=%lld W=%lld)", (long long)S, (long long)W);
+  FK_CHECK_ARG((row_stride == 0 || row_stride >= k) && group_stride >= (W - 1) * row_stride + k,
+               "fk_beam_select_grouped: rows overlap (row_stride=%lld group_stride=%lld k=%lld)", (long long)row_stride, (long long)group_stride, (long long)k);
+  FK_CHECK_ARG(anc_ld > 0 && log_rows >= 0 && (log_rows == 0 || (parent_log && tok_log)), "fk_beam_select_grouped: bad arguments (anc_ld=%lld log_rows=%lld)",
+               (long long)anc_ld, (long long)log_rows);
+  hipLaunchKernelGGL(beam_select_kernel<true>, dim3((unsigned)S), dim3(BEAM_SELECT_THREADS), 0, (hipStream_t)stream, top_lp, top_id, row_stride, group_stride,
+                     (int)W, (int)k, scores, (const unsigned long long*)seed, step, pos, pos_inc, cur, parent_log, tok_log, log_rows, anc, anc_ld, ticket);
+  FK_CHECK_LAUNCH("fk_beam_select_grouped");
   return FK_OK;
 }
 

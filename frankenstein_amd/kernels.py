@@ -616,20 +616,26 @@ BEAM_MAX_WIDTH, BEAM_MAX_TOPK = 16, 64          # the envelope of fk_beam_select
 
 
 class BeamState:
-    """Device-side state of a cached beam search of width W: Philox seed, step counter (= row of the logs the next step writes),
-    cumulative scores [W], the per-step logs parent_log / tok_log [steps, W] the host backtracks through, and the ancestry table
-    anc [W, tmax] (anc[b, j] = the cache slot that holds beam b's key/value row j)."""
+    """Device-side state of a cached beam search of `groups` sentences x `width` beams (row g * width + b): one Philox seed per sentence,
+    step counter (= row of the logs the next step writes), cumulative scores [groups * width], the per-step logs parent_log / tok_log
+    [steps, groups * width] the host backtracks through (parents are beam numbers inside the sentence), the ancestry table anc
+    [groups * width, tmax] (anc[r, j] = the cache slot, counted from the sentence's first, that holds row r's key/value row j) and the
+    ticket word of beam_select_grouped.  seed: an int (groups = 1) or a sequence of `groups` ints."""
 
-    def __init__(self, device, width: int, steps: int, tmax: int, seed: Optional[int] = None):
+    def __init__(self, device, width: int, steps: int, tmax: int, seed=None, groups: int = 1):
         if seed is None:                                   # follows torch.manual_seed like torch.multinomial would
-            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-        self.width = width
-        self.seed = torch.tensor([seed], dtype=torch.int64, device=device)
+            seed = torch.randint(0, 2 ** 62, (groups,)).tolist()
+        seed = [int(x) for x in seed] if hasattr(seed, "__iter__") else [int(seed)]
+        assert len(seed) == groups, f"{groups} sentences need {groups} seeds, got {len(seed)}"
+        seed = [x - (1 << 64) if x >= (1 << 63) else x for x in seed]          # 64 raw bits in an int64 tensor
+        self.width, self.groups = width, groups
+        self.seed = torch.tensor(seed, dtype=torch.int64, device=device)
         self.step = torch.zeros(1, dtype=torch.int64, device=device)
-        self.scores = torch.zeros(width, dtype=torch.float32, device=device)
-        self.parent_log = torch.empty((max(steps, 1), width), dtype=torch.int32, device=device)
-        self.tok_log = torch.empty((max(steps, 1), width), dtype=torch.int64, device=device)
-        self.anc = torch.empty((width, tmax), dtype=torch.int32, device=device)
+        self.scores = torch.zeros(groups * width, dtype=torch.float32, device=device)
+        self.parent_log = torch.empty((max(steps, 1), groups * width), dtype=torch.int32, device=device)
+        self.tok_log = torch.empty((max(steps, 1), groups * width), dtype=torch.int64, device=device)
+        self.anc = torch.empty((groups * width, tmax), dtype=torch.int32, device=device)
+        self.ticket = torch.zeros(1, dtype=torch.int32, device=device)
 
 
 def attn_decode_beam(qkv: Tensor, kv: Tensor, anc: Tensor, pos: Tensor, n_head: int) -> Tensor:
@@ -676,6 +682,41 @@ def beam_select(top_lp: Tensor, top_id: Tensor, state: BeamState, cur: Tensor, p
     call("fk_beam_select", top_lp.data_ptr(), top_id.data_ptr(), 0 if broadcast else k, W, k, state.scores.data_ptr(), state.seed.data_ptr(),
          state.step.data_ptr(), pos.data_ptr(), _ptr(pos_inc), cur.data_ptr(), state.parent_log.data_ptr(), state.tok_log.data_ptr(),
          state.parent_log.shape[0], state.anc.data_ptr(), state.anc.stride(0), _stream())
+    return cur
+
+
+def attn_decode_beam_grouped(qkv: Tensor, kv: Tensor, anc: Tensor, pos: Tensor, n_head: int, groups: int, append: bool = False) -> Tensor:
+    """attn_decode_beam for `groups` sentences x W beams: qkv [groups * W, 3d], kv [groups * W, Tmax, 2d], anc int32 [groups * W, >= pos]
+    of slots counted from the sentence's first (clamped into [0, W)) -> o [groups * W, d].  append=True also writes qkv[:, d:] to
+    kv[:, pos[0]] (kv_append_ folded into this launch) and uses it as the newest row."""
+    R, d3 = qkv.shape
+    d = d3 // 3
+    D = d // n_head
+    assert groups >= 1 and R % groups == 0
+    assert kv.dtype == qkv.dtype and kv.shape[0] == R and kv.shape[2] == 2 * d and kv.stride(2) == 1 and qkv.stride(1) == 1
+    assert anc.dtype == torch.int32 and anc.dim() == 2 and anc.shape[0] == R and anc.stride(1) == 1
+    assert pos.dtype == torch.int32 and pos.numel() == 1
+    out = torch.empty((R, d), dtype=qkv.dtype, device=qkv.device)
+    call("fk_attn_decode_beam_grouped", qkv.data_ptr(), qkv.stride(0), kv.data_ptr(), kv.stride(0), kv.stride(1), kv.shape[1], anc.data_ptr(),
+         anc.stride(0), out.data_ptr(), d, pos.data_ptr(), groups, R // groups, n_head, D, 1.0 / math.sqrt(D), int(bool(append)), fk_dtype(qkv),
+         _stream())
+    return out
+
+
+def beam_select_grouped(top_lp: Tensor, top_id: Tensor, state: BeamState, cur: Tensor, pos: Tensor, pos_inc: Optional[Tensor] = None,
+                        broadcast: bool = False) -> Tensor:
+    """beam_select for state.groups sentences in one launch, one block each (fk_beam_select_grouped).  top_lp / top_id [groups * W, k]
+    from beam_topk, or [groups, k] with broadcast=True (every beam of a sentence reads that sentence's row: the first step).  Writes cur
+    [groups * W] int64 (returned) and state; the one step counter and pos_inc advance once, by the last block to finish."""
+    S, W, k = state.groups, state.width, top_lp.shape[1]
+    assert top_lp.dtype == torch.float32 and top_id.dtype == torch.int64 and top_lp.is_contiguous() and top_id.is_contiguous()
+    assert top_lp.shape == top_id.shape and top_lp.shape[0] == (S if broadcast else S * W)
+    assert cur.dtype == torch.int64 and cur.is_contiguous() and cur.numel() == S * W
+    assert pos.dtype == torch.int32 and pos.numel() == 1 and (pos_inc is None or (pos_inc.dtype == torch.int32 and pos_inc.numel() == 1))
+    call("fk_beam_select_grouped", top_lp.data_ptr(), top_id.data_ptr(), 0 if broadcast else k, k if broadcast else W * k, S, W, k,
+         state.scores.data_ptr(), state.seed.data_ptr(), state.step.data_ptr(), pos.data_ptr(), _ptr(pos_inc), cur.data_ptr(),
+         state.parent_log.data_ptr(), state.tok_log.data_ptr(), state.parent_log.shape[0], state.anc.data_ptr(), state.anc.stride(0),
+         state.ticket.data_ptr(), _stream())
     return cur
 
 

@@ -141,13 +141,18 @@ def _step_linear(x, lin, ln=None, gelu=False, residual=None, step_rows=None, hea
     return y if head_vocab is None else y[:, :head_vocab]
 
 
-def _block_forward_decode(self, x, kv, pos, anc=None):
+def _block_forward_decode(self, x, kv, pos, anc=None, groups=None):
     """One new token per sample with the position in a device int32 (graph-capturable): x [B, d], kv [B, Tmax, 2d].
-    anc (int32 [B, Tmax]): the samples are beams that share the caches, row j of beam b is read from slot anc[b, j] (K.attn_decode_beam)."""
+    anc (int32 [B, Tmax]): the samples are beams that share the caches, row j of beam b is read from slot anc[b, j] (K.attn_decode_beam).
+    groups = S: the B rows are S sentences x B / S beams and anc holds slots counted inside the sentence; the append of the new key|value
+    row is part of the attention launch (K.attn_decode_beam_grouped)."""
     at, ml = self.attn, self.mlp
     qkv = _step_linear(x, at.c_attn, ln=self.ln_1)
-    K.kv_append_(qkv, kv, pos)
-    o = K.attn_decode(qkv, kv, pos, at.n_head) if anc is None else K.attn_decode_beam(qkv, kv, anc, pos, at.n_head)
+    if groups is not None:
+        o = K.attn_decode_beam_grouped(qkv, kv, anc, pos, at.n_head, groups, append=True)
+    else:
+        K.kv_append_(qkv, kv, pos)
+        o = K.attn_decode(qkv, kv, pos, at.n_head) if anc is None else K.attn_decode_beam(qkv, kv, anc, pos, at.n_head)
     x = _step_linear(o, at.c_proj, residual=x)
     a = _step_linear(x, ml.c_fc, ln=self.ln_2, gelu=True)
     return _step_linear(a, ml.c_proj, residual=x)
@@ -327,12 +332,12 @@ class GPT(nn.Module):
         return logits, pos + t
 
     @torch.no_grad()
-    def _decode_logits_dev(self, cur, cache, pos, anc=None):
+    def _decode_logits_dev(self, cur, cache, pos, anc=None, groups=None):
         """last-position logits [B, V] for the tokens `cur` [B] at device position pos (int32[1]); appends to the caches.
-        anc: the beam ancestry table of a cached beam search (Block.forward_decode)."""
+        anc: the beam ancestry table of a cached beam search, groups: its number of sentences (Block.forward_decode)."""
         x = K.gpt_embed_step(cur, self.transformer.wte.weight.detach(), self.transformer.wpe.weight.detach(), pos, E.compute_dtype())
         for li, block in enumerate(self.transformer.h):
-            x = block.forward_decode(x, cache[li], pos, anc)
+            x = block.forward_decode(x, cache[li], pos, anc, groups)
         return _step_linear(x, self.lm_head, ln=self.transformer.ln_f, head_vocab=self.config.vocab_size)
 
     @staticmethod
@@ -414,22 +419,31 @@ class GPT(nn.Module):
         return torch.cat((idx, out), dim=1)[0]
 
     @torch.no_grad()
-    def generate_beam_search(self, idx, max_new_tokens, prefix, temperature=1.0, topk=20, beam_width=5, use_cache=False, use_graph=None):
+    def generate_beam_search(self, idx, max_new_tokens, prefix, temperature=1.0, topk=20, beam_width=5, use_cache=False, use_graph=None, seeds=None):
         """Stochastic beam search of the reference (models/gpt2_model.py:355-416): every step each of the `beam_width` beams draws
         `beam_width` continuations WITHOUT replacement from its `topk` most likely tokens, the `beam_width` best-scoring
-        (cumulative log-probability) of the beam_width^2 candidates survive; returns the best beam's ids.  Batch size 1.
+        (cumulative log-probability) of the beam_width^2 candidates survive; returns the best beam's ids.
+        idx [1, t0] is the reference's call and returns the 1-D ids; idx [S, t0] with prefix [S, t_ctx, d] searches S sentences (prompts of
+        equal length), each with its own beams, and returns [S, t0 + max_new_tokens].
         Default: host-side bookkeeping around the kernel forward (one batched forward of all beams per step, torch.multinomial draws).
         use_cache=True: the prefix and the prompt run once, every step is one cached decode step of all beams with the draw, the
         selection and the bookkeeping on the device (_beam_search_cached; its draws are a Philox stream seeded from torch's generator,
-        not torch.multinomial's).  Outside its envelope (sequence longer than block_size, beam_width > 16, topk > 64 or > vocabulary)
-        the call takes the re-forward loop."""
+        not torch.multinomial's); S > 1 sentences share that step (_beam_search_cached_batched: S * beam_width rows, one Philox key per
+        sentence, `seeds` = S ints fixes them).  Outside its envelope (sequence longer than block_size, beam_width > 16, topk > 64 or
+        > vocabulary, host tensors) the call takes the re-forward loop, sentence by sentence."""
         if topk is None:
             topk = 2 * beam_width
         self.eval()
+        S = idx.shape[0]
         total = (0 if prefix is None else prefix.shape[1]) + idx.shape[1] + max_new_tokens
-        if (use_cache and idx.is_cuda and idx.shape[0] == 1 and max_new_tokens > 0 and total <= self.config.block_size
+        if (use_cache and idx.is_cuda and max_new_tokens > 0 and total <= self.config.block_size
                 and 1 <= beam_width <= K.BEAM_MAX_WIDTH and beam_width <= topk <= min(K.BEAM_MAX_TOPK, self.config.vocab_size)):
-            return self._beam_search_cached(idx, max_new_tokens, prefix, temperature, topk, beam_width, use_graph)
+            if S == 1:
+                return self._beam_search_cached(idx, max_new_tokens, prefix, temperature, topk, beam_width, use_graph, seeds)
+            return self._beam_search_cached_batched(idx, max_new_tokens, prefix, temperature, topk, beam_width, use_graph, seeds)
+        if S > 1:
+            return torch.stack([self.generate_beam_search(idx[g:g + 1], max_new_tokens, None if prefix is None else prefix[g:g + 1], temperature,
+                                                          topk, beam_width) for g in range(S)])
         beams = idx.repeat(beam_width, 1)
         scores = torch.zeros(beam_width, device=idx.device)
         prefix = prefix.expand(beam_width, -1, -1)
@@ -447,7 +461,7 @@ class GPT(nn.Module):
         return beams[scores.argmax()]
 
     @torch.no_grad()
-    def _beam_search_cached(self, idx, max_new_tokens, prefix, temperature, topk, W, use_graph):
+    def _beam_search_cached(self, idx, max_new_tokens, prefix, temperature, topk, W, use_graph, seeds=None):
         """generate_beam_search on per-layer caches [W, total, 2d] that are never reordered: slot b holds the rows beam position b
         wrote, the int32 ancestry table names the slot of every row of every beam, and K.beam_select rewrites that table when it
         picks the survivors.  A step is embed -> blocks (K.attn_decode_beam) -> head -> K.beam_topk -> K.beam_select: nothing in
@@ -461,7 +475,7 @@ class GPT(nn.Module):
             use_graph = max_new_tokens >= 64
         cache = [torch.empty((W, total, 2 * d), dtype=E.compute_dtype(), device=dev) for _ in self.transformer.h]
         logits0, _ = self._cached_logits(idx, [c[:1] for c in cache], 0, None if prefix is None else _prep(prefix))   # slot 0 <- prefix + prompt
-        state = K.BeamState(dev, W, max_new_tokens, total)
+        state = K.BeamState(dev, W, max_new_tokens, total, seed=seeds)
         state.anc[:, :p0] = 0
         cur = torch.empty(W, dtype=torch.int64, device=dev)
         top_lp = torch.empty((W, topk), dtype=torch.float32, device=dev)
@@ -506,6 +520,74 @@ class GPT(nn.Module):
         self.last_beams = beams
         self.last_beam_scores = scores.tolist()
         return torch.tensor(beams[int(scores.argmax())], dtype=idx.dtype, device=dev)
+
+    @torch.no_grad()
+    def _beam_search_cached_batched(self, idx, max_new_tokens, prefix, temperature, topk, W, use_graph, seeds=None):
+        """_beam_search_cached for S sentences at once: S * W rows, row g * W + b is beam b of sentence g.  The caches [S * W, total, 2d] are
+        never reordered; the table holds slots counted inside the sentence, so the sentences cannot read each other's rows.  The prefix and
+        the prompts are prefilled in one pass into the slots g * W (the strided view cache[::W]); the first step draws every sentence's beams
+        from its one row; then a step is embed -> blocks (K.attn_decode_beam_grouped, which also appends the new key|value row) -> head ->
+        K.beam_topk -> K.beam_select_grouped (one block per sentence; one position and one step counter for all).  Up to 16 rows the
+        linear layers stream the weights once (K.gemv_nt), beyond that they are MFMA GEMMs (_step_linear).
+        Sets last_beams (S lists of W id lists, prompt included) and last_beam_scores (S lists); returns the best beam of every sentence."""
+        dev, d = idx.device, self.config.n_embd
+        S, t0 = idx.shape
+        t_ctx = 0 if prefix is None else prefix.shape[1]
+        p0 = t_ctx + t0
+        total = p0 + max_new_tokens
+        if use_graph is None:
+            use_graph = max_new_tokens >= 64
+        cache = [torch.empty((S * W, total, 2 * d), dtype=E.compute_dtype(), device=dev) for _ in self.transformer.h]
+        logits0, _ = self._cached_logits(idx, [c[::W] for c in cache], 0, None if prefix is None else _prep(prefix))   # slot g * W <- sentence g
+        state = K.BeamState(dev, W, max_new_tokens, total, seed=seeds, groups=S)
+        state.anc[:, :p0] = 0
+        cur = torch.empty(S * W, dtype=torch.int64, device=dev)
+        top_lp = torch.empty((S * W, topk), dtype=torch.float32, device=dev)
+        top_id = torch.empty((S * W, topk), dtype=torch.int64, device=dev)
+        lg0 = logits0.float()
+        # first step: the beams of a sentence are its one prefilled sequence and draw from the same row; no row has been appended, the table stays
+        K.beam_topk(lg0 if lg0.stride(-1) == 1 else lg0.contiguous(), temperature, topk, top_lp[:S], top_id[:S])
+        K.beam_select_grouped(top_lp[:S], top_id[:S], state, cur, torch.tensor([-1], dtype=torch.int32, device=dev), broadcast=True)
+        pos = torch.tensor([p0], dtype=torch.int32, device=dev)
+
+        def step():
+            K.beam_topk(self._decode_logits_dev(cur, cache, pos, state.anc, groups=S), temperature, topk, top_lp, top_id)
+            K.beam_select_grouped(top_lp, top_id, state, cur, pos, pos_inc=pos)
+
+        if use_graph and max_new_tokens > 1:
+            n_eager = min(2, max_new_tokens - 1)            # warm-up (allocator, lazy shadows) before the capture
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                for _ in range(n_eager):
+                    step()
+                remaining = max_new_tokens - 1 - n_eager
+                if remaining > 0:
+                    graph = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(graph, stream=side):      # records the step, does not run it
+                        step()
+                    for _ in range(remaining):
+                        graph.replay()
+            torch.cuda.current_stream().wait_stream(side)
+        else:
+            for _ in range(max_new_tokens - 1):
+                step()
+        parents, toks, scores = state.parent_log.cpu().tolist(), state.tok_log.cpu().tolist(), state.scores.cpu().view(S, W)
+        prompts = idx.cpu().tolist()
+        all_beams, best = [], []
+        for g in range(S):
+            beams = []
+            for b in range(W):                              # walk every final beam back through its parents (beam numbers inside the sentence)
+                seq = []
+                for t in range(max_new_tokens - 1, -1, -1):
+                    seq.append(toks[t][g * W + b])
+                    b = parents[t][g * W + b]
+                beams.append(prompts[g] + seq[::-1])
+            all_beams.append(beams)
+            best.append(beams[int(scores[g].argmax())])
+        self.last_beams = all_beams
+        self.last_beam_scores = scores.tolist()
+        return torch.tensor(best, dtype=idx.dtype, device=dev)
 
     @torch.no_grad()
     def beam_search(self, idx, max_new_tokens, prefix, temperature=1.0, topk=20, beam_width=3, use_cache=False):

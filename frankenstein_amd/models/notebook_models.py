@@ -17,6 +17,9 @@ from .brainformer import BrainFormer as _FileBrainFormer
 from .brainformer import Config
 
 
+BEAM_BATCH_ROWS = 16    # rows (sentences x beams) of a batched beam search by default: the most the weight-streaming decode step takes
+
+
 class BrainEncoder(_FileBrainFormer):
     """forward(x) -> logits/features [B, n_output_tokens, output_dim] (no loss)."""
     config = Config
@@ -79,11 +82,26 @@ class Franky(nn.Module):
         return self.llm_model.generate(ids, max_new_tokens, prefix=prefix, temperature=temperature, top_k=top_k)
 
     @torch.no_grad()
-    def generate_beam(self, x, max_new_tokens=25, temperature=1.0, topk=20, beam_width=5, eot=50256):
+    def generate_beam(self, x, max_new_tokens=25, temperature=1.0, topk=20, beam_width=5, eot=50256, batch_sentences=None):
         """x: numpy [T, C].  Brain features -> prefix -> the stochastic beam search of the decoder on its key/value caches
-        (GPT.generate_beam_search, use_cache=True).  Returns the best beam's ids, `eot` first."""
-        xin = torch.from_numpy(x[None]).to(self.device).float()
-        prefix = self.brain_model(xin)
-        ids = torch.full((1, 1), eot, dtype=torch.long, device=self.device)
-        return self.llm_model.generate_beam_search(ids, max_new_tokens, prefix, temperature=temperature, topk=topk, beam_width=beam_width,
-                                                   use_cache=True)
+        (GPT.generate_beam_search, use_cache=True).  Returns the best beam's ids, `eot` first.
+        x: numpy [S, T, C] decodes S trials and returns ids [S, 1 + max_new_tokens]: the encoder and the search run in chunks of
+        `batch_sentences` trials that share every decode step (default: BEAM_BATCH_ROWS // beam_width, the rows that stay on the
+        weight-streaming route of the decode step)."""
+        if x.ndim == 2:
+            xin = torch.from_numpy(x[None]).to(self.device).float()
+            prefix = self.brain_model(xin)
+            ids = torch.full((1, 1), eot, dtype=torch.long, device=self.device)
+            return self.llm_model.generate_beam_search(ids, max_new_tokens, prefix, temperature=temperature, topk=topk, beam_width=beam_width,
+                                                       use_cache=True)
+        if batch_sentences is None:
+            batch_sentences = max(1, BEAM_BATCH_ROWS // beam_width)
+        outs = []
+        for s0 in range(0, x.shape[0], batch_sentences):
+            xin = torch.from_numpy(x[s0:s0 + batch_sentences]).to(self.device).float()
+            prefix = self.brain_model(xin)
+            ids = torch.full((xin.shape[0], 1), eot, dtype=torch.long, device=self.device)
+            out = self.llm_model.generate_beam_search(ids, max_new_tokens, prefix, temperature=temperature, topk=topk, beam_width=beam_width,
+                                                      use_cache=True)
+            outs.append(out.view(xin.shape[0], -1))
+        return torch.cat(outs)

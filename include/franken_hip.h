@@ -261,6 +261,26 @@ int fk_beam_select(const float* top_lp, const int64_t* top_id, int64_t row_strid
                    int64_t* step, const int32_t* pos, int32_t* pos_inc, int64_t* cur, int32_t* parent_log, int64_t* tok_log, int64_t log_rows,
                    int32_t* anc, int64_t anc_ld, void* stream);
 
+/* ---- the same step for a batch of S sentences with W beams each.  Row r = g*W + b is beam b of sentence g; the caches are [S*W, tmax, 2d]
+ * and never reordered; the table is int32 [S*W, tmax] of LOCAL slots in [0, W): row j < *pos of row r lives in cache slot
+ * g*W + anc[r*anc_ld + j], its row *pos in slot r.  One *pos and one *step serve all sentences (prompts of equal length).
+ * fk_attn_decode_beam_grouped: fk_attn_decode_beam on grid (H, S*W) with slot = g*W + clamp(anc[r][j], 0, W-1), so a corrupt table stays
+ *   inside its own sentence; *pos >= min(tmax, anc_ld) counts as the last row.  append != 0 folds fk_kv_append into the launch: qkv is the
+ *   [q | k | v] row (3*H*D elements, 16-byte aligned, q_bs a multiple of 16 bytes), block (h, r) writes head h's D keys and D values of
+ *   qkv[r] to kv[r, *pos] and uses them as key *pos; append == 0 reads row *pos from the cache.  S >= 1, S*W < 65536, tmax > 0.
+ * fk_beam_select_grouped: fk_beam_select with one block per sentence g: beam i of sentence g reads row g*group_stride + i*row_stride of
+ *   top_lp / top_id (row_stride = 0: the sentence's one row, the first step; group_stride >= (W-1)*row_stride + k), scores / cur at g*W,
+ *   the logs are [log_rows, S, W], the table rows g*W .. g*W+W-1 (local entries, so the update is fk_beam_select's), the Philox key is
+ *   seed[g] on the unchanged counter (step_lo, step_hi, i, 0xBEA30000 | j): sentence g draws what a one-sentence call with seed[g] draws.
+ *   Every block reads *step and *pos on entry; the last one to finish sets *step += 1, *pos_inc += 1 and *ticket = 0 (`ticket`: a
+ *   zero-initialised uint32 word owned by the caller).  Per sentence 1 <= W <= 16, W <= k <= 64.                                     */
+int fk_attn_decode_beam_grouped(const void* qkv, int64_t q_bs, void* kv, int64_t kv_bs, int64_t kv_rs, int64_t tmax, const int32_t* anc, int64_t anc_ld,
+                                void* out, int64_t o_bs, const int32_t* pos, int64_t S, int64_t W, int64_t H, int64_t D, float scale, int append, int dtype,
+                                void* stream);
+int fk_beam_select_grouped(const float* top_lp, const int64_t* top_id, int64_t row_stride, int64_t group_stride, int64_t S, int64_t W, int64_t k,
+                           float* scores, const uint64_t* seed, int64_t* step, const int32_t* pos, int32_t* pos_inc, int64_t* cur, int32_t* parent_log,
+                           int64_t* tok_log, int64_t log_rows, int32_t* anc, int64_t anc_ld, uint32_t* ticket, void* stream);
+
 /* ---- VQ-VAE tokenizer convolutions (models/vq_brain.py), channels-last [B, T, C], causal left padding dil*(K-1):
  * fk_im2col1d: cols[b, t, k, :] = x[b, t*stride + k*dil - pad, :] (zeros outside), Tout = (T-1)/stride + 1, so that
  *   CausalConv1d (:22-28) = fk_gemm_nt(cols, W') with W'[o, k*Cin + c] = W[o, c, k], and CausalConvTranspose1d(kernel 2s,

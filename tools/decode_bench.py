@@ -3,6 +3,7 @@
     python tools/decode_bench.py --model gpt2 --batch 1        # GPT-2 124M, the reference's decoder (franky_baseline_gpt2.ipynb)
     python tools/decode_bench.py --model nano --all-modes       # cfg1's gpt2-nano: re-forward vs kv-cache vs kv-cache + hipGraph
     python tools/decode_bench.py --model gpt2 --beam 5 --topk 20 --new-tokens 25     # generate_beam_search: cached (+ hipGraph) vs re-forward
+    python tools/decode_bench.py --model gpt2 --beam 5 --sentences 1,2,3,4,8,16 --new-tokens 25    # S sentences in one search vs S searches
 
 Random weights, a 32-token brain prefix, one start token, top_k = 1.  A generate() call also pays the prefill and, in graph mode, the
 capture, so the per-token figure is the MARGINAL cost: (time of N new tokens - time of N/4 new tokens) / (3N/4), medians over the
@@ -83,6 +84,47 @@ def beam_bench(g, a, prefix, start):
           f"and {statistics.median(times['beam re-forward'][n]) / statistics.median(times['beam kv-cache (eager)'][n]):.2f}x")
 
 
+def sentences_bench(g, a, d_model):
+    """--beam W --sentences S[,S..]: the cached beam search of S sentences in ONE call (S * W rows per step) beside S sequential
+    one-sentence calls, each as a hipGraph and eager, in one process with the repeats of the four modes interleaved.  sentences/s is the
+    whole call (prefill and capture included); us/step is marginal, (time of N new tokens - time of N/4) / (3N/4), and for the sequential
+    loop it is the step of ONE of its sentences, S of which make a step of the loop."""
+    W, n, n4 = a.beam, a.new_tokens, max(1, a.new_tokens // 4)
+    print(f"{'S':>3s} {'rows':>4s}  {'mode':32s} {'us/step':>9s} {'call ms':>9s} {'[min .. max]':>19s} {'sentences/s':>11s}")
+    for S in a.sentences:
+        prefix = torch.randn(S, 32, d_model, device="cuda")
+        start = torch.full((S, 1), 50256, dtype=torch.long, device="cuda")
+
+        def batched(kw):
+            return lambda k: g.generate_beam_search(start, k, prefix, topk=a.topk, beam_width=W, use_cache=True, **kw)
+
+        def sequential(kw):
+            def run(k):
+                for i in range(S):
+                    g.generate_beam_search(start[i:i + 1], k, prefix[i:i + 1], topk=a.topk, beam_width=W, use_cache=True, **kw)
+            return run
+
+        modes = {"batched + hipGraph": batched(dict(use_graph=True)), "batched eager": batched(dict(use_graph=False)),
+                 "sequential + hipGraph": sequential(dict(use_graph=True)), "sequential eager": sequential(dict(use_graph=False))}
+        times = {name: {n4: [], n: []} for name in modes}
+        for name, fn in modes.items():                      # warm up both lengths of every mode
+            for k in (n4, n):
+                fn(k)
+        for _ in range(a.repeats):
+            for k in (n4, n):
+                for name, fn in modes.items():
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    fn(k)
+                    torch.cuda.synchronize()
+                    times[name][k].append(time.perf_counter() - t0)
+        for name in modes:
+            t4, t = statistics.median(times[name][n4]), statistics.median(times[name][n])
+            step = ((t - t4) / (n - n4) if n > n4 else t / n) / (S if name.startswith("sequential") else 1)
+            print(f"{S:3d} {S * W:4d}  {name:32s} {step * 1e6:9.1f} {t * 1e3:9.2f} {f'[{min(times[name][n]) * 1e3:.2f} .. {max(times[name][n]) * 1e3:.2f}]':>19s} "
+                  f"{S / t:11.1f}", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", choices=sorted(MODELS), default="nano")
@@ -93,6 +135,8 @@ def main():
     ap.add_argument("--all-modes", action="store_true", help="also time the full re-forward and the eager kv-cache loop (default: hipGraph only)")
     ap.add_argument("--beam", type=int, default=0, help="beam width: time generate_beam_search (cached + hipGraph, cached eager, re-forward) instead of generate")
     ap.add_argument("--topk", type=int, default=20, help="top-k of the beam search's draws (with --beam)")
+    ap.add_argument("--sentences", type=lambda v: [int(x) for x in v.split(",")], default=None,
+                    help="with --beam: sentences per batched search, one or a comma-separated list; each beside as many one-sentence searches")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "decode_bench needs the GPU"
 
@@ -107,8 +151,12 @@ def main():
     floor = wbytes / HBM_PEAK
     print(f"model {a.model} ({sum(p.numel() for p in g.parameters()) / 1e6:.1f} M parameters), {a.dtype}, batch {B}, {n} new tokens, "
           f"{a.repeats} repeats; weights per step {wbytes / 1e6:.1f} MB -> ceiling {floor * 1e6:.1f} us/step = {B / floor:.0f} tokens/s")
+    if a.beam and a.sentences:
+        print(f"beam width {a.beam}, topk {a.topk}, sentences {a.sentences}")
+        return sentences_bench(g, a, m["n_embd"])
     if a.beam:
-        assert B == 1, "the beam search is batch 1"
+        if B != 1:
+            ap.error("--beam with --batch: give the number of sentences as --sentences")
         print(f"beam width {a.beam}, topk {a.topk}")
         return beam_bench(g, a, prefix, start)
     for name, kw in MODES.items():
