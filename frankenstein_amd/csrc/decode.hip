@@ -8,6 +8,8 @@
 //   fk_attn_decode_beam / fk_beam_topk / fk_beam_select    the step of the beam search on shared caches (ancestry table), further down
 //   fk_attn_decode_beam_grouped / fk_beam_select_grouped   the same step for S sentences x W beams at once: rows g * W + b, a table of
 //                       LOCAL slots, fk_kv_append folded into the attention launch, one select block per sentence + a ticket
+//   fk_beam_select_eos / fk_beam_backtrack / fk_sample_topk_eos   end-of-text: finished beams and rows, length-normalised ranking, a live
+//                       count for the host's early exit, and the walk through the logs on the device
 #include "fk_common.h"
 
 namespace {
@@ -169,9 +171,41 @@ FK_DEV unsigned radix_select_kth(const float* row, int V, float inv_temp, int k,
   return *sel_prefix;
 }
 
+// End-of-text state of the EOS variants below (all device pointers; unused and empty in the plain instantiations): fin[r] 0/1 (a finished
+// beam, a done row), len[r] the generated tokens so far with the end-of-text token counted once, inv_lenpow[L] = 1 / L^alpha for
+// L < n_lenpow (the kernels only multiply by it), live_acc the word the blocks add their unfinished rows to, live[0] what the last block
+// found there.
+struct EosArgs {
+  int eos;
+  int32_t* fin;
+  int32_t* len;
+  const float* inv_lenpow;
+  int n_lenpow;
+  unsigned* live_acc;
+  int32_t* live;
+};
+
+// The end of a launch of gridDim.x blocks that share one step counter: every block adds its unfinished rows to live_acc and takes a
+// ticket; the last one fetches and clears the sum and advances the counters.  Only atomics carry a value between the blocks.
+FK_DEV void eos_ticket_tail(const EosArgs& ea, unsigned n_live, unsigned* ticket, int64_t* step, int64_t my_step, int32_t* pos_inc) {
+  atomicAdd(ea.live_acc, n_live);
+  __threadfence();
+  if (atomicAdd(ticket, 1u) == gridDim.x - 1) {
+    __threadfence();
+    ea.live[0] = (int32_t)atomicExch(ea.live_acc, 0u);
+    ticket[0] = 0u;
+    step[0] = my_step + 1;
+    if (pos_inc) pos_inc[0] += 1;
+  }
+}
+
+// EOS: a row with fin[b] != 0 draws nothing and emits ea.eos; a row that draws ea.eos becomes done; len[b] counts the tokens of a row up to
+// and including its end-of-text token.  The draw of every other row is the plain kernel's (Philox keyed by step and row).
+template <bool EOS>
 __global__ __launch_bounds__(SAMPLE_THREADS) void sample_topk_kernel(const float* logits, int64_t ld, int V, float inv_temp, int top_k,
                                                                      const unsigned long long* seed, int64_t* step, int32_t* pos_inc,
-                                                                     int64_t* cur, int64_t* out, int64_t out_ld, int64_t out_cols, unsigned* ticket) {
+                                                                     int64_t* cur, int64_t* out, int64_t out_ld, int64_t out_cols, unsigned* ticket,
+                                                                     EosArgs ea) {
   __shared__ unsigned hist[256];
   __shared__ float red[SAMPLE_THREADS / 64];
   __shared__ float scan[SAMPLE_THREADS];
@@ -180,6 +214,16 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_topk_kernel(const float
   const int tid = threadIdx.x, b = blockIdx.x;
   const float* row = logits + (int64_t)b * ld;
   const int64_t my_step = step[0];                       // read before anybody can advance it (the advance happens after the last block)
+  if constexpr (EOS) {
+    if (ea.eos >= 0 && ea.fin[b] != 0) {                 // block-uniform: no barrier is skipped by part of a block; without an id no row is done
+      if (tid == 0) {
+        cur[b] = ea.eos;
+        if (out && my_step >= 0 && my_step < out_cols) out[(int64_t)b * out_ld + my_step] = ea.eos;
+        eos_ticket_tail(ea, 0u, ticket, step, my_step, pos_inc);
+      }
+      return;
+    }
+  }
 
   // ---- k-th largest key (top_k <= 0 or >= V: keep everything)
   unsigned kth = 0u;
@@ -234,12 +278,20 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_topk_kernel(const float
         if (f32_sortable(row[i] * inv_temp) >= kth) { w = i; break; }
     }
     cur[b] = w;
-    if (out && my_step < out_cols) out[(int64_t)b * out_ld + my_step] = w;       // a step counter past the buffer is not a write past it
-    __threadfence();
-    if (atomicAdd(ticket, 1u) == gridDim.x - 1) {         // every block has read step[0] and written its token
-      ticket[0] = 0u;
-      step[0] = my_step + 1;
-      if (pos_inc) pos_inc[0] += 1;
+    if constexpr (EOS) {
+      if (out && my_step >= 0 && my_step < out_cols) out[(int64_t)b * out_ld + my_step] = w;
+      const bool ended = ea.eos >= 0 && w == ea.eos;
+      ea.len[b] = (int32_t)((unsigned)ea.len[b] + 1u);
+      if (ended) ea.fin[b] = 1;
+      eos_ticket_tail(ea, ended ? 0u : 1u, ticket, step, my_step, pos_inc);
+    } else {
+      if (out && my_step < out_cols) out[(int64_t)b * out_ld + my_step] = w;       // a step counter past the buffer is not a write past it
+      __threadfence();
+      if (atomicAdd(ticket, 1u) == gridDim.x - 1) {         // every block has read step[0] and written its token
+        ticket[0] = 0u;
+        step[0] = my_step + 1;
+        if (pos_inc) pos_inc[0] += 1;
+      }
     }
   }
 }
@@ -424,15 +476,21 @@ constexpr int BEAM_SELECT_THREADS = 256;
 // g * group_stride + i * row_stride, scores / cur / the table rows g * W .., the logs [steps, S, W], the Philox key seed[g].  The table
 // entries are local slots in [0, W), so the ancestry update is the one-sentence update on the rows of the sentence.  All blocks read the
 // one step counter and the one position on entry; the last block to finish (ticket) advances them, as in sample_topk_kernel.
-template <bool GROUPED>
+//
+// EOS (with GROUPED): the end-of-text rules of fk_beam_select_eos.  A finished beam proposes ONE candidate, itself (token ea.eos, its score
+// unchanged, its length unchanged); the candidates are ranked by norm = raw * inv_lenpow[clamp(L, 0, n_lenpow - 1)], one fp32 multiply
+// behind the one fp32 add of raw, so a table of ones ranks by raw bit for bit; scores[] keeps the raw sums.
+template <bool GROUPED, bool EOS>
 __global__ __launch_bounds__(BEAM_SELECT_THREADS) void beam_select_kernel(const float* top_lp, const int64_t* top_id, int64_t row_stride, int64_t group_stride,
                                                                           int W, int k, float* scores, const unsigned long long* seed, int64_t* step,
                                                                           const int32_t* pos, int32_t* pos_inc, int64_t* cur, int32_t* parent_log,
                                                                           int64_t* tok_log, int64_t log_rows, int32_t* anc, int64_t anc_ld,
-                                                                          unsigned* ticket) {
+                                                                          unsigned* ticket, EosArgs ea) {
   __shared__ float gum[BEAM_MAX_W * BEAM_MAX_K];
   __shared__ float sc[BEAM_MAX_W], cand[BEAM_MAX_W * BEAM_MAX_W];
   __shared__ int pick[BEAM_MAX_W * BEAM_MAX_W], surv[BEAM_MAX_W], parent[BEAM_MAX_W];
+  __shared__ float cnorm[BEAM_MAX_W * BEAM_MAX_W];       // EOS only, like the three below
+  __shared__ int sfin[BEAM_MAX_W], slen[BEAM_MAX_W], alive[BEAM_MAX_W];
   const int tid = threadIdx.x;
   const int64_t my_step = step[0];                       // read before anybody can advance it (the advance happens after the last block)
   const int p = pos[0];
@@ -447,9 +505,13 @@ __global__ __launch_bounds__(BEAM_SELECT_THREADS) void beam_select_kernel(const 
     anc += (int64_t)g * W * anc_ld;
     log_ld = (int64_t)gridDim.x * W;
     if (parent_log) { parent_log += g * W; tok_log += g * W; }
+    if constexpr (EOS) { ea.fin += g * W; ea.len += g * W; }
   }
   const unsigned long long sd = seed[0];
   if (tid < W) { sc[tid] = scores[tid]; surv[tid] = 0; }
+  if constexpr (EOS) {
+    if (tid < W) { sfin[tid] = (ea.eos >= 0 && ea.fin[tid] != 0) ? 1 : 0; slen[tid] = ea.len[tid]; }   // without an id no beam is finished
+  }
   if (tid < W * W) pick[tid] = 0;
   // ---- Gumbel keys: the W largest of lp + G draw W entries without replacement with probability ~ exp(lp)
   // two trips side by side would be packed into v_pk_*_f32 with op_sel half-swaps, which this library keeps out of its code
@@ -472,18 +534,48 @@ __global__ __launch_bounds__(BEAM_SELECT_THREADS) void beam_select_kernel(const 
   __syncthreads();
   // ---- the W best of the W * W candidates: score descending, then parent, then draw rank (= candidate number ascending)
   const int nc = W * W;
-  if (tid < nc) cand[tid] = sc[tid / W] + top_lp[(tid / W) * row_stride + pick[tid]];
-  __syncthreads();
-  if (tid < nc) {
-    const float s = cand[tid];
-    int rank = 0;
-    for (int c = 0; c < nc; ++c) rank += (cand[c] > s || (cand[c] == s && c < tid)) ? 1 : 0;
-    if (rank < W) surv[rank] = tid;
+  if constexpr (EOS) {
+    if (tid < nc) {
+      const int i = tid / W;
+      const bool done = sfin[i] != 0;
+      const float raw = done ? sc[i] : sc[i] + top_lp[i * row_stride + pick[tid]];
+      const int L = done ? slen[i] : (int)((unsigned)slen[i] + 1u);
+      const int at = L < 0 ? 0 : (L > ea.n_lenpow - 1 ? ea.n_lenpow - 1 : L);      // a length past the table ranks with its last entry
+      cand[tid] = raw;
+      cnorm[tid] = raw * ea.inv_lenpow[at];
+    }
+    __syncthreads();
+    if (tid < nc && !(sfin[tid / W] != 0 && tid % W > 0)) {  // a finished beam has its candidate 0 only; at least W candidates are valid
+      const float s = cnorm[tid];
+      int rank = 0;
+      for (int c = 0; c < nc; ++c) {
+        const bool valid = !(sfin[c / W] != 0 && c % W > 0);
+        rank += (valid && (cnorm[c] > s || (cnorm[c] == s && c < tid))) ? 1 : 0;
+      }
+      if (rank < W) surv[rank] = tid;
+    }
+  } else {
+    if (tid < nc) cand[tid] = sc[tid / W] + top_lp[(tid / W) * row_stride + pick[tid]];
+    __syncthreads();
+    if (tid < nc) {
+      const float s = cand[tid];
+      int rank = 0;
+      for (int c = 0; c < nc; ++c) rank += (cand[c] > s || (cand[c] == s && c < tid)) ? 1 : 0;
+      if (rank < W) surv[rank] = tid;
+    }
   }
   __syncthreads();
   if (tid < W) {
     const int c = surv[tid], pr = c / W;
-    const int64_t tok = top_id[pr * row_stride + pick[c]];
+    int64_t tok = top_id[pr * row_stride + pick[c]];
+    if constexpr (EOS) {
+      const bool done = sfin[pr] != 0;
+      if (done) tok = ea.eos;
+      const int ended = (done || (ea.eos >= 0 && tok == ea.eos)) ? 1 : 0;
+      ea.len[tid] = done ? slen[pr] : (int)((unsigned)slen[pr] + 1u);
+      ea.fin[tid] = ended;
+      alive[tid] = 1 - ended;
+    }
     parent[tid] = pr;
     scores[tid] = cand[c];
     cur[tid] = tok;
@@ -509,17 +601,63 @@ __global__ __launch_bounds__(BEAM_SELECT_THREADS) void beam_select_kernel(const 
   if constexpr (GROUPED) {
     __syncthreads();                                       // the whole block has written its rows of the table
     if (tid == 0) {
-      __threadfence();
-      if (atomicAdd(ticket, 1u) == gridDim.x - 1) {        // every block has read step[0] and pos[0] and has written its sentence
-        ticket[0] = 0u;
-        step[0] = my_step + 1;
-        if (pos_inc) pos_inc[0] += 1;
+      if constexpr (EOS) {
+        unsigned n_live = 0u;
+        for (int b = 0; b < W; ++b) n_live += (unsigned)alive[b];
+        eos_ticket_tail(ea, n_live, ticket, step, my_step, pos_inc);
+      } else {
+        __threadfence();
+        if (atomicAdd(ticket, 1u) == gridDim.x - 1) {        // every block has read step[0] and pos[0] and has written its sentence
+          ticket[0] = 0u;
+          step[0] = my_step + 1;
+          if (pos_inc) pos_inc[0] += 1;
+        }
       }
     }
   } else if (tid == 0) {                                   // every read of the counters is behind a barrier above
     step[0] = my_step + 1;
     if (pos_inc) pos_inc[0] += 1;
   }
+}
+
+// The walk of the host through the logs, on the device: block g = one sentence, thread b < W = one final beam.  n = min(*step, log_rows)
+// steps are on record; beam b's token of step t is tok_log[t, g, x_t] with x_{n-1} = b and x_{t-1} = clamp(parent_log[t, g, x_t], 0, W-1).
+// The beams are ranked by scores * inv_lenpow[clamp(len)] descending, then by beam number, and beam b's row goes to out_ids[g, rank]:
+// columns t0 .. t0+n-1 its tokens, the columns behind them `pad`; nothing left of t0 (the caller's prompt) and nothing right of out_cols.
+constexpr int BACKTRACK_THREADS = 64;
+
+__global__ __launch_bounds__(BACKTRACK_THREADS) void beam_backtrack_kernel(const int32_t* parent_log, const int64_t* tok_log, int64_t log_rows, int W,
+                                                                           const int64_t* step, const float* scores, const int32_t* len,
+                                                                           const float* inv_lenpow, int n_lenpow, int64_t* out_ids, int64_t out_ld,
+                                                                           int64_t out_cols, int64_t t0, int64_t pad, float* out_scores, int32_t* out_len) {
+  __shared__ float norm[BEAM_MAX_W];
+  const int g = blockIdx.x, b = threadIdx.x;
+  const int64_t log_ld = (int64_t)gridDim.x * W;
+  int64_t n = step[0];
+  n = n < 0 ? 0 : (n > log_rows ? log_rows : n);          // a counter past the logs is not a read past them
+  float raw = 0.0f;
+  int L = 0;
+  if (b < W) {
+    raw = scores[g * W + b];
+    L = len[g * W + b];
+    const int at = L < 0 ? 0 : (L > n_lenpow - 1 ? n_lenpow - 1 : L);
+    norm[b] = raw * inv_lenpow[at];
+  }
+  __syncthreads();
+  if (b >= W) return;
+  int rank = 0;
+  for (int c = 0; c < W; ++c) rank += (norm[c] > norm[b] || (norm[c] == norm[b] && c < b)) ? 1 : 0;
+  int64_t* row = out_ids + ((int64_t)g * W + rank) * out_ld;
+  int x = b;
+  for (int64_t t = n - 1; t >= 0; --t) {
+    const int64_t at = t * log_ld + (int64_t)g * W + x;
+    if (t0 + t < out_cols) row[t0 + t] = tok_log[at];
+    const int pr = parent_log[at];
+    x = pr < 0 ? 0 : (pr >= W ? W - 1 : pr);
+  }
+  for (int64_t c = t0 + n; c < out_cols; ++c) row[c] = pad;
+  out_scores[g * W + rank] = raw;
+  out_len[g * W + rank] = L;
 }
 
 }  // namespace
@@ -566,8 +704,8 @@ int fk_sample_topk(const float* logits, int64_t ld, int64_t B, int64_t V, float 
                (long long)out_cols, (long long)out_ld);
   FK_CHECK_ARG(logits && seed && step && cur && ticket && B > 0 && B < 65536 && V > 0 && V < (1LL << 31) && ld >= V && temperature > 0.0f,
                "fk_sample_topk: bad arguments (B=%lld V=%lld temperature=%g)", (long long)B, (long long)V, (double)temperature);
-  hipLaunchKernelGGL(sample_topk_kernel, dim3((unsigned)B), dim3(SAMPLE_THREADS), 0, (hipStream_t)stream, logits, ld, (int)V, 1.0f / temperature,
-                     (int)(top_k > 0 && top_k < V ? top_k : 0), (const unsigned long long*)seed, step, pos_inc, cur, out, out_ld, out_cols, ticket);
+  hipLaunchKernelGGL(sample_topk_kernel<false>, dim3((unsigned)B), dim3(SAMPLE_THREADS), 0, (hipStream_t)stream, logits, ld, (int)V, 1.0f / temperature,
+                     (int)(top_k > 0 && top_k < V ? top_k : 0), (const unsigned long long*)seed, step, pos_inc, cur, out, out_ld, out_cols, ticket, EosArgs{});
   FK_CHECK_LAUNCH("fk_sample_topk");
   return FK_OK;
 }
@@ -609,8 +747,8 @@ int fk_beam_select(const float* top_lp, const int64_t* top_id, int64_t row_strid
                BEAM_MAX_K, (long long)W, (long long)k);
   FK_CHECK_ARG((row_stride == 0 || row_stride >= k) && anc_ld > 0 && log_rows >= 0 && (log_rows == 0 || (parent_log && tok_log)),
                "fk_beam_select: bad arguments (row_stride=%lld anc_ld=%lld log_rows=%lld)", (long long)row_stride, (long long)anc_ld, (long long)log_rows);
-  hipLaunchKernelGGL(beam_select_kernel<false>, dim3(1), dim3(BEAM_SELECT_THREADS), 0, (hipStream_t)stream, top_lp, top_id, row_stride, (int64_t)0, (int)W,
-                     (int)k, scores, (const unsigned long long*)seed, step, pos, pos_inc, cur, parent_log, tok_log, log_rows, anc, anc_ld, (unsigned*)nullptr);
+  hipLaunchKernelGGL((beam_select_kernel<false, false>), dim3(1), dim3(BEAM_SELECT_THREADS), 0, (hipStream_t)stream, top_lp, top_id, row_stride, (int64_t)0, (int)W,
+                     (int)k, scores, (const unsigned long long*)seed, step, pos, pos_inc, cur, parent_log, tok_log, log_rows, anc, anc_ld, (unsigned*)nullptr, EosArgs{});
   FK_CHECK_LAUNCH("fk_beam_select");
   return FK_OK;
 }
@@ -649,9 +787,64 @@ int fk_beam_select_grouped(const float* top_lp, const int64_t* top_id, int64_t r
                "fk_beam_select_grouped: rows overlap (row_stride=%lld group_stride=%lld k=%lld)", (long long)row_stride, (long long)group_stride, (long long)k);
   FK_CHECK_ARG(anc_ld > 0 && log_rows >= 0 && (log_rows == 0 || (parent_log && tok_log)), "fk_beam_select_grouped: bad arguments (anc_ld=%lld log_rows=%lld)",
                (long long)anc_ld, (long long)log_rows);
-  hipLaunchKernelGGL(beam_select_kernel<true>, dim3((unsigned)S), dim3(BEAM_SELECT_THREADS), 0, (hipStream_t)stream, top_lp, top_id, row_stride, group_stride,
-                     (int)W, (int)k, scores, (const unsigned long long*)seed, step, pos, pos_inc, cur, parent_log, tok_log, log_rows, anc, anc_ld, ticket);
+  hipLaunchKernelGGL((beam_select_kernel<true, false>), dim3((unsigned)S), dim3(BEAM_SELECT_THREADS), 0, (hipStream_t)stream, top_lp, top_id, row_stride, group_stride,
+                     (int)W, (int)k, scores, (const unsigned long long*)seed, step, pos, pos_inc, cur, parent_log, tok_log, log_rows, anc, anc_ld, ticket, EosArgs{});
   FK_CHECK_LAUNCH("fk_beam_select_grouped");
+  return FK_OK;
+}
+
+int fk_beam_select_eos(const float* top_lp, const int64_t* top_id, int64_t row_stride, int64_t group_stride, int64_t S, int64_t W, int64_t k,
+                       float* scores, const uint64_t* seed, int64_t* step, const int32_t* pos, int32_t* pos_inc, int64_t* cur, int32_t* parent_log,
+                       int64_t* tok_log, int64_t log_rows, int32_t* anc, int64_t anc_ld, uint32_t* ticket, int64_t eos, int32_t* fin, int32_t* len,
+                       const float* inv_lenpow, int64_t n_lenpow, uint32_t* live_acc, int32_t* live, void* stream) {
+  FK_CHECK_ARG(top_lp && top_id && scores && seed && step && pos && cur && anc && ticket && fin && len && inv_lenpow && live_acc && live,
+               "fk_beam_select_eos: null pointer");
+  FK_CHECK_ARG(W >= 1 && W <= BEAM_MAX_W && k >= W && k <= BEAM_MAX_K, "fk_beam_select_eos: need 1 <= W <= %d and W <= k <= %d (W=%lld k=%lld)",
+               BEAM_MAX_W, BEAM_MAX_K, (long long)W, (long long)k);
+  FK_CHECK_ARG(S >= 1 && S * W < 65536, "fk_beam_select_eos: need S >= 1 and S * W < 65536 rows (S=%lld W=%lld)", (long long)S, (long long)W);
+  FK_CHECK_ARG((row_stride == 0 || row_stride >= k) && group_stride >= (W - 1) * row_stride + k,
+               "fk_beam_select_eos: rows overlap (row_stride=%lld group_stride=%lld k=%lld)", (long long)row_stride, (long long)group_stride, (long long)k);
+  FK_CHECK_ARG(anc_ld > 0 && log_rows >= 0 && (log_rows == 0 || (parent_log && tok_log)), "fk_beam_select_eos: bad arguments (anc_ld=%lld log_rows=%lld)",
+               (long long)anc_ld, (long long)log_rows);
+  FK_CHECK_ARG(n_lenpow >= 1 && n_lenpow < (1LL << 31) && eos < (1LL << 31), "fk_beam_select_eos: need 1 <= n_lenpow < 2^31 and eos < 2^31 (n_lenpow=%lld eos=%lld)",
+               (long long)n_lenpow, (long long)eos);
+  const EosArgs ea{eos < 0 ? -1 : (int)eos, fin, len, inv_lenpow, (int)n_lenpow, live_acc, live};
+  hipLaunchKernelGGL((beam_select_kernel<true, true>), dim3((unsigned)S), dim3(BEAM_SELECT_THREADS), 0, (hipStream_t)stream, top_lp, top_id, row_stride,
+                     group_stride, (int)W, (int)k, scores, (const unsigned long long*)seed, step, pos, pos_inc, cur, parent_log, tok_log, log_rows, anc,
+                     anc_ld, ticket, ea);
+  FK_CHECK_LAUNCH("fk_beam_select_eos");
+  return FK_OK;
+}
+
+int fk_beam_backtrack(const int32_t* parent_log, const int64_t* tok_log, int64_t log_rows, int64_t S, int64_t W, const int64_t* step, const float* scores,
+                      const int32_t* len, const float* inv_lenpow, int64_t n_lenpow, int64_t* out_ids, int64_t out_ld, int64_t out_cols, int64_t t0,
+                      int64_t pad, float* out_scores, int32_t* out_len, void* stream) {
+  FK_CHECK_ARG(parent_log && tok_log && step && scores && len && inv_lenpow && out_ids && out_scores && out_len, "fk_beam_backtrack: null pointer");
+  FK_CHECK_ARG(W >= 1 && W <= BEAM_MAX_W && S >= 1 && S * W < 65536, "fk_beam_backtrack: need 1 <= W <= %d, S >= 1 and S * W < 65536 rows (S=%lld W=%lld)",
+               BEAM_MAX_W, (long long)S, (long long)W);
+  FK_CHECK_ARG(n_lenpow >= 1 && n_lenpow < (1LL << 31) && log_rows >= 1, "fk_beam_backtrack: need n_lenpow >= 1 and log_rows >= 1 (n_lenpow=%lld log_rows=%lld)",
+               (long long)n_lenpow, (long long)log_rows);
+  FK_CHECK_ARG(t0 >= 0 && out_cols >= t0 && out_cols > 0 && out_ld >= out_cols,
+               "fk_beam_backtrack: rows of out_cols=%lld ids (stride out_ld=%lld) must hold the prompt t0=%lld and must not overlap", (long long)out_cols,
+               (long long)out_ld, (long long)t0);
+  hipLaunchKernelGGL(beam_backtrack_kernel, dim3((unsigned)S), dim3(BACKTRACK_THREADS), 0, (hipStream_t)stream, parent_log, tok_log, log_rows, (int)W, step,
+                     scores, len, inv_lenpow, (int)n_lenpow, out_ids, out_ld, out_cols, t0, pad, out_scores, out_len);
+  FK_CHECK_LAUNCH("fk_beam_backtrack");
+  return FK_OK;
+}
+
+int fk_sample_topk_eos(const float* logits, int64_t ld, int64_t B, int64_t V, float temperature, int64_t top_k, const uint64_t* seed, int64_t* step,
+                       int32_t* pos_inc, int64_t* cur, int64_t* out, int64_t out_ld, int64_t out_cols, uint32_t* ticket, int64_t eos, int32_t* done,
+                       int32_t* len, uint32_t* live_acc, int32_t* live, void* stream) {
+  FK_CHECK_ARG(out == nullptr || (out_cols > 0 && out_cols <= out_ld), "fk_sample_topk_eos: out given without its width (out_cols=%lld, out_ld=%lld)",
+               (long long)out_cols, (long long)out_ld);
+  FK_CHECK_ARG(logits && seed && step && cur && ticket && done && len && live_acc && live, "fk_sample_topk_eos: null pointer");
+  FK_CHECK_ARG(B > 0 && B < 65536 && V > 0 && V < (1LL << 31) && ld >= V && temperature > 0.0f && eos < (1LL << 31),
+               "fk_sample_topk_eos: bad arguments (B=%lld V=%lld temperature=%g eos=%lld)", (long long)B, (long long)V, (double)temperature, (long long)eos);
+  const EosArgs ea{eos < 0 ? -1 : (int)eos, done, len, nullptr, 0, live_acc, live};
+  hipLaunchKernelGGL(sample_topk_kernel<true>, dim3((unsigned)B), dim3(SAMPLE_THREADS), 0, (hipStream_t)stream, logits, ld, (int)V, 1.0f / temperature,
+                     (int)(top_k > 0 && top_k < V ? top_k : 0), (const unsigned long long*)seed, step, pos_inc, cur, out, out_ld, out_cols, ticket, ea);
+  FK_CHECK_LAUNCH("fk_sample_topk_eos");
   return FK_OK;
 }
 

@@ -600,6 +600,41 @@ def sample_topk(logits: Tensor, temperature: float, top_k: Optional[int], state:
     return cur
 
 
+class SampleEosState:
+    """End-of-text state of sample_topk_eos for B rows: done [B] int32 0/1, len [B] int32 (generated tokens, the end-of-text token counted
+    once), the accumulator word live_acc and live [1] int32 = the rows not done after the last step."""
+
+    def __init__(self, device, rows: int, eos: Optional[int]):
+        self.eos = -1 if eos is None else int(eos)
+        self.done = torch.zeros(rows, dtype=torch.int32, device=device)
+        self.len = torch.zeros(rows, dtype=torch.int32, device=device)
+        self.live_acc = torch.zeros(1, dtype=torch.int32, device=device)
+        self.live = torch.full((1,), rows, dtype=torch.int32, device=device)
+
+
+def sample_topk_eos(logits: Tensor, temperature: float, top_k: Optional[int], state: SampleState, eos_state: SampleEosState,
+                    cur: Optional[Tensor] = None, out: Optional[Tensor] = None, pos_inc: Optional[Tensor] = None) -> Tensor:
+    """sample_topk with an end-of-text id (fk_sample_topk_eos): a done row emits eos_state.eos and draws nothing, every other row draws
+    what sample_topk draws with the same seed and step, its length grows by one, and a row that draws the id becomes done;
+    eos_state.live[0] = the rows still not done."""
+    assert logits.dim() == 2 and logits.dtype == torch.float32 and logits.stride(1) == 1
+    B, V = logits.shape
+    if cur is None:
+        cur = torch.empty(B, dtype=torch.int64, device=logits.device)
+    assert cur.dtype == torch.int64 and cur.is_contiguous() and cur.numel() == B
+    assert eos_state.done.numel() == B and eos_state.len.numel() == B
+    out_ld = out_cols = 0
+    if out is not None:
+        assert out.dtype == torch.int64 and out.dim() == 2 and out.shape[0] == B and out.stride(1) == 1
+        out_ld, out_cols = out.stride(0), out.shape[1]
+    if pos_inc is not None:
+        assert pos_inc.dtype == torch.int32 and pos_inc.numel() == 1
+    call("fk_sample_topk_eos", logits.data_ptr(), logits.stride(0), B, V, float(temperature), int(top_k or 0), state.seed.data_ptr(),
+         state.step.data_ptr(), _ptr(pos_inc), cur.data_ptr(), _ptr(out), out_ld, out_cols, state.ticket.data_ptr(), eos_state.eos,
+         eos_state.done.data_ptr(), eos_state.len.data_ptr(), eos_state.live_acc.data_ptr(), eos_state.live.data_ptr(), _stream())
+    return cur
+
+
 def attn_decode(qkv: Tensor, kv: Tensor, pos: Tensor, n_head: int) -> Tensor:
     """one causal query per sample against the cache rows 0..pos[0]: q = qkv[:, :d] -> o [B, d]."""
     B, d3 = qkv.shape
@@ -615,14 +650,25 @@ def attn_decode(qkv: Tensor, kv: Tensor, pos: Tensor, n_head: int) -> Tensor:
 BEAM_MAX_WIDTH, BEAM_MAX_TOPK = 16, 64          # the envelope of fk_beam_select / fk_beam_topk
 
 
+def inv_lenpow_table(n: int, alpha: float) -> Tensor:
+    """fp32 [n] on the host: entry L = 1 / L^alpha computed in float64 and rounded once, entry 0 = 1 (the length penalty the beam kernels
+    multiply by; alpha = 0 gives ones)."""
+    L = torch.arange(max(int(n), 1), dtype=torch.float64)
+    L[0] = 1.0
+    return (1.0 / L.pow(float(alpha))).to(torch.float32)
+
+
 class BeamState:
     """Device-side state of a cached beam search of `groups` sentences x `width` beams (row g * width + b): one Philox seed per sentence,
     step counter (= row of the logs the next step writes), cumulative scores [groups * width], the per-step logs parent_log / tok_log
     [steps, groups * width] the host backtracks through (parents are beam numbers inside the sentence), the ancestry table anc
     [groups * width, tmax] (anc[r, j] = the cache slot, counted from the sentence's first, that holds row r's key/value row j) and the
-    ticket word of beam_select_grouped.  seed: an int (groups = 1) or a sequence of `groups` ints."""
+    ticket word of beam_select_grouped.  seed: an int (groups = 1) or a sequence of `groups` ints.
+    With eos (an end-of-text id) or a length_penalty alpha != 0 it also holds the state of beam_select_eos / beam_backtrack: fin and len
+    [groups * width] int32, inv_lenpow fp32 [steps + 2] (inv_lenpow_table), live_acc and live [1]; otherwise none of these exist."""
 
-    def __init__(self, device, width: int, steps: int, tmax: int, seed=None, groups: int = 1):
+    def __init__(self, device, width: int, steps: int, tmax: int, seed=None, groups: int = 1, eos: Optional[int] = None,
+                 length_penalty: float = 0.0):
         if seed is None:                                   # follows torch.manual_seed like torch.multinomial would
             seed = torch.randint(0, 2 ** 62, (groups,)).tolist()
         seed = [int(x) for x in seed] if hasattr(seed, "__iter__") else [int(seed)]
@@ -636,6 +682,13 @@ class BeamState:
         self.tok_log = torch.empty((max(steps, 1), groups * width), dtype=torch.int64, device=device)
         self.anc = torch.empty((groups * width, tmax), dtype=torch.int32, device=device)
         self.ticket = torch.zeros(1, dtype=torch.int32, device=device)
+        if eos is not None or length_penalty != 0.0:
+            self.eos, self.length_penalty = eos, float(length_penalty)
+            self.fin = torch.zeros(groups * width, dtype=torch.int32, device=device)
+            self.len = torch.zeros(groups * width, dtype=torch.int32, device=device)
+            self.inv_lenpow = inv_lenpow_table(max(steps, 1) + 2, length_penalty).to(device)
+            self.live_acc = torch.zeros(1, dtype=torch.int32, device=device)
+            self.live = torch.full((1,), groups * width, dtype=torch.int32, device=device)
 
 
 def attn_decode_beam(qkv: Tensor, kv: Tensor, anc: Tensor, pos: Tensor, n_head: int) -> Tensor:
@@ -718,6 +771,40 @@ def beam_select_grouped(top_lp: Tensor, top_id: Tensor, state: BeamState, cur: T
          state.parent_log.data_ptr(), state.tok_log.data_ptr(), state.parent_log.shape[0], state.anc.data_ptr(), state.anc.stride(0),
          state.ticket.data_ptr(), _stream())
     return cur
+
+
+def beam_select_eos(top_lp: Tensor, top_id: Tensor, state: BeamState, cur: Tensor, pos: Tensor, pos_inc: Optional[Tensor] = None,
+                    broadcast: bool = False) -> Tensor:
+    """beam_select_grouped with the end-of-text rules (fk_beam_select_eos; state built with eos= / length_penalty=): a finished beam proposes
+    itself once, with its score and its length, the survivors are the W best by score * inv_lenpow[length], state.fin / state.len follow
+    them and state.live[0] = the unfinished beams of all sentences after the step.  state.groups = 1 is the one-sentence search."""
+    S, W, k = state.groups, state.width, top_lp.shape[1]
+    assert top_lp.dtype == torch.float32 and top_id.dtype == torch.int64 and top_lp.is_contiguous() and top_id.is_contiguous()
+    assert top_lp.shape == top_id.shape and top_lp.shape[0] == (S if broadcast else S * W)
+    assert cur.dtype == torch.int64 and cur.is_contiguous() and cur.numel() == S * W
+    assert pos.dtype == torch.int32 and pos.numel() == 1 and (pos_inc is None or (pos_inc.dtype == torch.int32 and pos_inc.numel() == 1))
+    call("fk_beam_select_eos", top_lp.data_ptr(), top_id.data_ptr(), 0 if broadcast else k, k if broadcast else W * k, S, W, k,
+         state.scores.data_ptr(), state.seed.data_ptr(), state.step.data_ptr(), pos.data_ptr(), _ptr(pos_inc), cur.data_ptr(),
+         state.parent_log.data_ptr(), state.tok_log.data_ptr(), state.parent_log.shape[0], state.anc.data_ptr(), state.anc.stride(0),
+         state.ticket.data_ptr(), -1 if state.eos is None else int(state.eos), state.fin.data_ptr(), state.len.data_ptr(),
+         state.inv_lenpow.data_ptr(), state.inv_lenpow.numel(), state.live_acc.data_ptr(), state.live.data_ptr(), _stream())
+    return cur
+
+
+def beam_backtrack(state: BeamState, out_ids: Tensor, t0: int, pad: int):
+    """The walk through state's logs on the device (fk_beam_backtrack).  out_ids int64 [groups, width, cols] (last stride 1, rows dense
+    or padded) whose columns < t0 the caller has filled with the prompt: beam `rank` of a sentence (0 = the best by score *
+    inv_lenpow[len]) gets its tokens in the columns t0 .. t0 + n - 1, n = min(state.step, rows of the logs), and `pad` behind them.
+    -> (out_scores fp32 [groups, width] raw, out_len int32 [groups, width]), ordered like out_ids."""
+    S, W = state.groups, state.width
+    assert out_ids.dtype == torch.int64 and out_ids.dim() == 3 and tuple(out_ids.shape[:2]) == (S, W) and out_ids.stride(2) == 1
+    assert out_ids.stride(0) == W * out_ids.stride(1)
+    out_scores = torch.empty((S, W), dtype=torch.float32, device=out_ids.device)
+    out_len = torch.empty((S, W), dtype=torch.int32, device=out_ids.device)
+    call("fk_beam_backtrack", state.parent_log.data_ptr(), state.tok_log.data_ptr(), state.parent_log.shape[0], S, W, state.step.data_ptr(),
+         state.scores.data_ptr(), state.len.data_ptr(), state.inv_lenpow.data_ptr(), state.inv_lenpow.numel(), out_ids.data_ptr(),
+         out_ids.stride(1), out_ids.shape[2], int(t0), int(pad), out_scores.data_ptr(), out_len.data_ptr(), _stream())
+    return out_scores, out_len
 
 
 # ------------------------------------------------------------------------------------------- conv (VQ-VAE tokenizer)

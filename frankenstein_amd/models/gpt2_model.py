@@ -161,6 +161,27 @@ def _block_forward_decode(self, x, kv, pos, anc=None, groups=None):
 Block.forward_decode = _block_forward_decode
 
 
+def _beam_step_host(top_lp, top_ix, picks, scores, lens, fin, eos, inv_lenpow):
+    """One selection step of the stochastic beam search with the end-of-text rules of fk_beam_select_eos, on host tensors (the
+    re-forward path; the draws `picks` [W, W] are the caller's).  A live beam i proposes its W picks, raw = scores[i] + top_lp[i, pick]
+    (one fp32 add), L = lens[i] + 1; a finished beam proposes itself once (candidate r = 0: token eos, raw = scores[i], L = lens[i]).
+    The W best candidates by raw * inv_lenpow[clamp(L)] (one fp32 multiply) survive, ties by candidate number i * W + r.
+    top_lp fp32 / top_ix int64 [W, k], scores fp32 [W], lens int [W], fin bool [W], eos an id or -1, inv_lenpow fp32 [n]
+    -> parent int64 [W], token int64 [W], scores fp32 [W] (raw), lens [W], fin bool [W]."""
+    W = scores.numel()
+    done = fin.bool()[:, None]
+    raw = torch.where(done, scores.float()[:, None], scores.float()[:, None] + top_lp.float().gather(1, picks))
+    tok = torch.where(done, torch.full_like(picks, eos), top_ix.gather(1, picks))
+    L = torch.where(done, lens.long()[:, None], lens.long()[:, None] + 1).expand(W, W)
+    norm = (raw * inv_lenpow.float()[L.clamp(0, inv_lenpow.numel() - 1)]).reshape(-1)
+    valid = (~done | (torch.arange(W, device=scores.device)[None, :] == 0)).reshape(-1).nonzero().squeeze(1)
+    order = valid[torch.sort(norm[valid], descending=True, stable=True).indices[:W]]
+    parent = order // W
+    new_tok = tok.reshape(-1)[order]
+    new_fin = fin.bool()[parent] | ((new_tok == eos) & (eos >= 0))
+    return parent, new_tok, raw.reshape(-1)[order], L.reshape(-1)[order].to(lens.dtype), new_fin
+
+
 @dataclass
 class GPTConfig:
     block_size: int = 1024
@@ -356,18 +377,25 @@ class GPT(nn.Module):
         return torch.multinomial(torch.softmax(logits, dim=-1), num_samples=1)
 
     @torch.no_grad()
-    def generate(self, idx, max_new_tokens, prefix=None, temperature=1.0, top_k=None, use_cache=True, use_graph=None):
+    def generate(self, idx, max_new_tokens, prefix=None, temperature=1.0, top_k=None, use_cache=True, use_graph=None, eos_token_id=None,
+                 check_every=8):
         """Sampling loop of the reference (models/gpt2_model.py:328-353: temperature, top-k crop, softmax, multinomial; returns
         the first sample's ids).  With use_cache (default) the prefix + prompt are run once and every new token is one
         incremental step against per-layer key/value caches; with use_graph (default: on from 64 new tokens, where the one-off
         capture has paid for itself)
         that step — embedding, blocks, head AND the sampling — reads its position from the device and is captured once as a
         hipGraph that is replayed per token (the step is launch-bound: ~25 small kernels).  When the sequence would outgrow
-        block_size the reference's crop-and-re-forward path is used instead."""
+        block_size the reference's crop-and-re-forward path is used instead.
+        eos_token_id: a row that draws this id is done: it emits the id from then on and draws nothing (its tokens up to and including
+        the id are the ones the call without it draws from the same seed); the loop asks the device every `check_every` steps whether any
+        row is still live and stops early if none is.  Returns row 0 at full length, padded with the id, and sets last_tokens
+        [B, t0 + max_new_tokens], last_lengths [B] (generated tokens, the id counted once) and last_steps (steps run)."""
         B, t0 = idx.shape
         t_ctx = 0 if prefix is None else prefix.shape[1]
         total = t_ctx + t0 + max_new_tokens
         cached = use_cache and total <= self.config.block_size and max_new_tokens > 0
+        if eos_token_id is not None:
+            return self._generate_eos(idx, max_new_tokens, prefix, temperature, top_k, cached, use_graph, int(eos_token_id), int(check_every))
         state = K.SampleState(idx.device) if idx.is_cuda else None      # one Philox stream per call, seeded from torch's generator
         if use_graph is None:
             use_graph = max_new_tokens >= 64
@@ -418,8 +446,92 @@ class GPT(nn.Module):
         torch.cuda.current_stream().wait_stream(side)
         return torch.cat((idx, out), dim=1)[0]
 
+    @staticmethod
+    def _run_polled(step, max_new_tokens, use_graph, live, check_every):
+        """Steps 2 .. max_new_tokens of a decode loop whose first step the caller has run: eager, or (use_graph) two eager warm-up steps,
+        one capture and replays.  After every `check_every`-th step `live` (int32 [1] on the device, written by the step) is read with
+        one 4-byte copy and the loop ends when it is 0.  -> the number of steps run, the first included.
+        The warm-up / capture / replay sequence is the one of _generate_graph and the cached beam searches (kept apart so that the calls
+        without an end-of-text id run their code unchanged): a change to it there belongs here too."""
+        n = 1
+
+        def stopped():                                      # asked before a step: every check_every-th step is followed by one read
+            return n % check_every == 0 and int(live.item()) == 0
+
+        if not (use_graph and max_new_tokens > 1):
+            while n < max_new_tokens and not stopped():
+                step()
+                n += 1
+            return n
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            warm = 1 + min(2, max_new_tokens - 1)           # warm-up (allocator, lazy shadows) before the capture
+            stop = False
+            while n < warm and not stop:
+                stop = stopped()
+                if not stop:
+                    step()
+                    n += 1
+            if not stop and n < max_new_tokens:
+                graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graph, stream=side):      # records the step, does not run it
+                    step()
+                while n < max_new_tokens and not stopped():
+                    graph.replay()
+                    n += 1
+        torch.cuda.current_stream().wait_stream(side)
+        return n
+
     @torch.no_grad()
-    def generate_beam_search(self, idx, max_new_tokens, prefix, temperature=1.0, topk=20, beam_width=5, use_cache=False, use_graph=None, seeds=None):
+    def _generate_eos(self, idx, max_new_tokens, prefix, temperature, top_k, cached, use_graph, eos, check_every):
+        """generate with an end-of-text id.  On the caches the step is generate's graph step with K.sample_topk_eos as its tail (done rows,
+        lengths and the live count live on the device); the re-forward loop applies the same rule with torch.where on the host."""
+        assert 0 <= eos < self.config.vocab_size, f"eos_token_id {eos} outside the vocabulary"
+        assert check_every >= 1
+        B, t0 = idx.shape
+        dev = idx.device
+        if use_graph is None:
+            use_graph = max_new_tokens >= 64
+        if cached and idx.is_cuda:
+            d = self.config.n_embd
+            t_ctx = 0 if prefix is None else prefix.shape[1]
+            cache = [torch.empty((B, t_ctx + t0 + max_new_tokens, 2 * d), dtype=E.compute_dtype(), device=dev) for _ in self.transformer.h]
+            logits0, pos0 = self._cached_logits(idx, cache, 0, None if prefix is None else _prep(prefix))
+            out = torch.full((B, max_new_tokens), eos, dtype=torch.int64, device=dev)
+            cur = torch.empty(B, dtype=torch.int64, device=dev)
+            state, es = K.SampleState(dev), K.SampleEosState(dev, B, eos)
+            lg0 = logits0.float()
+            K.sample_topk_eos(lg0 if lg0.stride(-1) == 1 else lg0.contiguous(), temperature, top_k, state, es, cur=cur, out=out)
+            pos = torch.tensor([pos0], dtype=torch.int32, device=dev)
+
+            def step():
+                K.sample_topk_eos(self._decode_logits_dev(cur, cache, pos), temperature, top_k, state, es, cur=cur, out=out, pos_inc=pos)
+
+            self.last_steps = self._run_polled(step, max_new_tokens, use_graph, es.live, check_every)
+            self.last_tokens, self.last_lengths = torch.cat((idx, out), dim=1), es.len.to(torch.int64)
+            return self.last_tokens[0]
+        state = K.SampleState(dev) if idx.is_cuda else None
+        done = torch.zeros(B, dtype=torch.bool, device=dev)
+        lens = torch.zeros(B, dtype=torch.int64, device=dev)
+        n = 0
+        while n < max_new_tokens:
+            if n > 0 and n % check_every == 0 and bool(done.all()):
+                break
+            idx_cond = idx if idx.size(1) <= self.config.block_size else idx[:, -self.config.block_size:]
+            _, lg = self(idx_cond, prefix=prefix)
+            tok = torch.where(done, torch.full_like(lens, eos), self._sample(lg[:, -1, :], temperature, top_k, state).view(-1))
+            lens += (~done).long()
+            done = done | (tok == eos)
+            idx = torch.cat((idx, tok[:, None]), dim=1)
+            n += 1
+        pad = torch.full((B, max_new_tokens - n), eos, dtype=idx.dtype, device=dev)
+        self.last_steps, self.last_tokens, self.last_lengths = n, torch.cat((idx, pad), dim=1), lens
+        return self.last_tokens[0]
+
+    @torch.no_grad()
+    def generate_beam_search(self, idx, max_new_tokens, prefix, temperature=1.0, topk=20, beam_width=5, use_cache=False, use_graph=None, seeds=None,
+                             eos_token_id=None, length_penalty=0.0, check_every=8):
         """Stochastic beam search of the reference (models/gpt2_model.py:355-416): every step each of the `beam_width` beams draws
         `beam_width` continuations WITHOUT replacement from its `topk` most likely tokens, the `beam_width` best-scoring
         (cumulative log-probability) of the beam_width^2 candidates survive; returns the best beam's ids.
@@ -430,14 +542,28 @@ class GPT(nn.Module):
         selection and the bookkeeping on the device (_beam_search_cached; its draws are a Philox stream seeded from torch's generator,
         not torch.multinomial's); S > 1 sentences share that step (_beam_search_cached_batched: S * beam_width rows, one Philox key per
         sentence, `seeds` = S ints fixes them).  Outside its envelope (sequence longer than block_size, beam_width > 16, topk > 64 or
-        > vocabulary, host tensors) the call takes the re-forward loop, sentence by sentence."""
+        > vocabulary, host tensors) the call takes the re-forward loop, sentence by sentence.
+        eos_token_id / length_penalty (alpha): a beam that has emitted the id is finished: it stays a candidate with its score and its
+        length and draws nothing more; candidates and final beams are ranked by score / length^alpha (length = generated tokens, the id
+        counted once); the search stops once every beam of every sentence is finished, which the host asks the device every `check_every`
+        steps.  The result is padded with the id to t0 + max_new_tokens; last_beams / last_beam_scores (raw sums) are ordered best
+        first, last_beam_lengths and last_steps are set as well.  Both arguments at their defaults: the search above, unchanged."""
         if topk is None:
             topk = 2 * beam_width
         self.eval()
         S = idx.shape[0]
         total = (0 if prefix is None else prefix.shape[1]) + idx.shape[1] + max_new_tokens
-        if (use_cache and idx.is_cuda and max_new_tokens > 0 and total <= self.config.block_size
-                and 1 <= beam_width <= K.BEAM_MAX_WIDTH and beam_width <= topk <= min(K.BEAM_MAX_TOPK, self.config.vocab_size)):
+        in_envelope = (use_cache and idx.is_cuda and max_new_tokens > 0 and total <= self.config.block_size
+                       and 1 <= beam_width <= K.BEAM_MAX_WIDTH and beam_width <= topk <= min(K.BEAM_MAX_TOPK, self.config.vocab_size))
+        if eos_token_id is not None or length_penalty != 0.0:
+            eos = None if eos_token_id is None else int(eos_token_id)
+            assert eos is None or 0 <= eos < self.config.vocab_size, f"eos_token_id {eos} outside the vocabulary"
+            assert check_every >= 1
+            if in_envelope:
+                return self._beam_search_cached_eos(idx, max_new_tokens, prefix, temperature, topk, beam_width, use_graph, seeds, eos,
+                                                    float(length_penalty), int(check_every))
+            return self._beam_search_host_eos(idx, max_new_tokens, prefix, temperature, topk, beam_width, eos, float(length_penalty), int(check_every))
+        if in_envelope:
             if S == 1:
                 return self._beam_search_cached(idx, max_new_tokens, prefix, temperature, topk, beam_width, use_graph, seeds)
             return self._beam_search_cached_batched(idx, max_new_tokens, prefix, temperature, topk, beam_width, use_graph, seeds)
@@ -588,6 +714,86 @@ class GPT(nn.Module):
         self.last_beams = all_beams
         self.last_beam_scores = scores.tolist()
         return torch.tensor(best, dtype=idx.dtype, device=dev)
+
+    @torch.no_grad()
+    def _beam_search_cached_eos(self, idx, max_new_tokens, prefix, temperature, topk, W, use_graph, seeds, eos, alpha, check_every):
+        """_beam_search_cached / _beam_search_cached_batched with end-of-text: the same step with K.beam_select_eos as its tail (one block per
+        sentence, S = 1 included), replayed in chunks of `check_every` between reads of the live count, and K.beam_backtrack instead of the
+        host's walk through the logs: the ids come back ranked, [S, W, t0 + max_new_tokens], padded behind the steps that ran."""
+        dev, d = idx.device, self.config.n_embd
+        S, t0 = idx.shape
+        t_ctx = 0 if prefix is None else prefix.shape[1]
+        p0 = t_ctx + t0
+        total = p0 + max_new_tokens
+        if use_graph is None:
+            use_graph = max_new_tokens >= 64
+        cache = [torch.empty((S * W, total, 2 * d), dtype=E.compute_dtype(), device=dev) for _ in self.transformer.h]
+        logits0, _ = self._cached_logits(idx, [c[:1] if S == 1 else c[::W] for c in cache], 0, None if prefix is None else _prep(prefix))
+        state = K.BeamState(dev, W, max_new_tokens, total, seed=seeds, groups=S, eos=eos, length_penalty=alpha)
+        state.anc[:, :p0] = 0
+        cur = torch.empty(S * W, dtype=torch.int64, device=dev)
+        top_lp = torch.empty((S * W, topk), dtype=torch.float32, device=dev)
+        top_id = torch.empty((S * W, topk), dtype=torch.int64, device=dev)
+        lg0 = logits0.float()
+        K.beam_topk(lg0 if lg0.stride(-1) == 1 else lg0.contiguous(), temperature, topk, top_lp[:S], top_id[:S])
+        K.beam_select_eos(top_lp[:S], top_id[:S], state, cur, torch.tensor([-1], dtype=torch.int32, device=dev), broadcast=True)
+        pos = torch.tensor([p0], dtype=torch.int32, device=dev)
+        groups = None if S == 1 else S                      # one sentence: the one-sentence attention, as in _beam_search_cached
+
+        def step():
+            K.beam_topk(self._decode_logits_dev(cur, cache, pos, state.anc, groups=groups), temperature, topk, top_lp, top_id)
+            K.beam_select_eos(top_lp, top_id, state, cur, pos, pos_inc=pos)
+
+        self.last_steps = self._run_polled(step, max_new_tokens, use_graph, state.live, check_every)
+        ids = torch.empty((S, W, t0 + max_new_tokens), dtype=torch.int64, device=dev)
+        ids[:, :, :t0] = idx[:, None, :]
+        scores, lens = K.beam_backtrack(state, ids, t0, 0 if eos is None else eos)
+        beams, scores, lens = ids.cpu().tolist(), scores.cpu().tolist(), lens.cpu().tolist()
+        if S == 1:
+            self.last_beams, self.last_beam_scores, self.last_beam_lengths = beams[0], scores[0], lens[0]
+            return ids[0, 0].to(idx.dtype)
+        self.last_beams, self.last_beam_scores, self.last_beam_lengths = beams, scores, lens
+        return ids[:, 0].to(idx.dtype)
+
+    @torch.no_grad()
+    def _beam_search_host_eos(self, idx, max_new_tokens, prefix, temperature, topk, W, eos, alpha, check_every):
+        """The re-forward loop of generate_beam_search with the end-of-text rules (_beam_step_host), sentence by sentence; draws by
+        torch.multinomial.  Sets last_beams, last_beam_scores, last_beam_lengths (best first) and last_steps like the cached search."""
+        S, t0 = idx.shape
+        dev = idx.device
+        pad_id = 0 if eos is None else eos
+        table = K.inv_lenpow_table(max(max_new_tokens, 1) + 2, alpha).to(dev)
+        all_beams, all_scores, all_lens, steps = [], [], [], 0
+        for g in range(S):
+            beams = idx[g:g + 1].repeat(W, 1)
+            scores = torch.zeros(W, device=dev)
+            lens = torch.zeros(W, dtype=torch.int64, device=dev)
+            fin = torch.zeros(W, dtype=torch.bool, device=dev)
+            pf = None if prefix is None else prefix[g:g + 1].expand(W, -1, -1).contiguous()
+            n = 0
+            while n < max_new_tokens:
+                if n > 0 and n % check_every == 0 and bool(fin.all()):
+                    break
+                cond = beams if beams.size(1) <= self.config.block_size else beams[:, -self.config.block_size:]
+                _, logits = self(cond, prefix=pf)
+                logp = torch.log_softmax(logits[:, -1, :].float() / temperature, dim=-1)
+                top_lp, top_ix = logp.topk(topk, dim=-1)
+                picks = torch.multinomial(top_lp.exp(), W, replacement=False)
+                parent, tok, scores, lens, fin = _beam_step_host(top_lp, top_ix, picks, scores, lens, fin, -1 if eos is None else eos, table)
+                beams = torch.cat((beams[parent], tok[:, None]), dim=1)
+                n += 1
+            steps = max(steps, n)
+            beams = torch.cat((beams, torch.full((W, max_new_tokens - n), pad_id, dtype=beams.dtype, device=dev)), dim=1)
+            order = torch.sort(scores * table[lens.clamp(0, table.numel() - 1)], descending=True, stable=True).indices
+            all_beams.append(beams[order])
+            all_scores.append(scores[order].tolist())
+            all_lens.append(lens[order].tolist())
+        self.last_steps = steps
+        if S == 1:
+            self.last_beams, self.last_beam_scores, self.last_beam_lengths = all_beams[0].tolist(), all_scores[0], all_lens[0]
+            return all_beams[0][0]
+        self.last_beams, self.last_beam_scores, self.last_beam_lengths = [b.tolist() for b in all_beams], all_scores, all_lens
+        return torch.stack([b[0] for b in all_beams])
 
     @torch.no_grad()
     def beam_search(self, idx, max_new_tokens, prefix, temperature=1.0, topk=20, beam_width=3, use_cache=False):

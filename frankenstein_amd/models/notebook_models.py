@@ -74,34 +74,59 @@ class Franky(nn.Module):
         return self.llm_model.forward(idx=new_idx, prefix=features, targets=targets)
 
     @torch.no_grad()
-    def generate(self, x, max_new_tokens=25, temperature=1.0, top_k=10, eot=50256):
-        """x: numpy [T, C].  Returns generated token ids (the notebook's version is unfinished; this one runs)."""
+    def generate(self, x, max_new_tokens=25, temperature=1.0, top_k=10, eot=50256, stop=False):
+        """x: numpy [T, C].  Returns generated token ids (the notebook's version is unfinished; this one runs).
+        stop=True ends a sentence at its first generated `eot` (what the notebook's cell tried with its undefined stop_tokens): the ids come
+        back trimmed behind that token; x: numpy [S, T, C] then decodes S trials, returns [S, 1 + max_new_tokens] padded with `eot` and sets
+        last_lengths [S] (generated tokens, `eot` included)."""
+        if stop:
+            xin = torch.from_numpy(x if x.ndim == 3 else x[None]).to(self.device).float()
+            prefix = self.brain_model(xin)
+            ids = torch.full((xin.shape[0], 1), eot, dtype=torch.long, device=self.device)
+            self.llm_model.generate(ids, max_new_tokens, prefix=prefix, temperature=temperature, top_k=top_k, eos_token_id=eot)
+            self.last_lengths = self.llm_model.last_lengths.cpu()           # int64 on the host, as generate_beam leaves it
+            if x.ndim == 3:
+                return self.llm_model.last_tokens
+            return self.llm_model.last_tokens[0, :1 + int(self.last_lengths[0])]
         xin = torch.from_numpy(x[None]).to(self.device).float()
         prefix = self.brain_model(xin)
         ids = torch.full((1, 1), eot, dtype=torch.long, device=self.device)
         return self.llm_model.generate(ids, max_new_tokens, prefix=prefix, temperature=temperature, top_k=top_k)
 
     @torch.no_grad()
-    def generate_beam(self, x, max_new_tokens=25, temperature=1.0, topk=20, beam_width=5, eot=50256, batch_sentences=None):
+    def generate_beam(self, x, max_new_tokens=25, temperature=1.0, topk=20, beam_width=5, eot=50256, batch_sentences=None, stop=False,
+                      length_penalty=0.0):
         """x: numpy [T, C].  Brain features -> prefix -> the stochastic beam search of the decoder on its key/value caches
         (GPT.generate_beam_search, use_cache=True).  Returns the best beam's ids, `eot` first.
         x: numpy [S, T, C] decodes S trials and returns ids [S, 1 + max_new_tokens]: the encoder and the search run in chunks of
         `batch_sentences` trials that share every decode step (default: BEAM_BATCH_ROWS // beam_width, the rows that stay on the
-        weight-streaming route of the decode step)."""
+        weight-streaming route of the decode step).
+        stop=True makes `eot` the end-of-text id of the search (finished beams, ranking by score / length^length_penalty, early exit):
+        [T, C] returns the best beam trimmed behind its first generated `eot`, [S, T, C] the padded [S, 1 + max_new_tokens] and sets
+        last_lengths [S]."""
+        eos_kw = dict(eos_token_id=eot if stop else None, length_penalty=length_penalty) if (stop or length_penalty != 0.0) else {}
         if x.ndim == 2:
             xin = torch.from_numpy(x[None]).to(self.device).float()
             prefix = self.brain_model(xin)
             ids = torch.full((1, 1), eot, dtype=torch.long, device=self.device)
-            return self.llm_model.generate_beam_search(ids, max_new_tokens, prefix, temperature=temperature, topk=topk, beam_width=beam_width,
-                                                       use_cache=True)
+            out = self.llm_model.generate_beam_search(ids, max_new_tokens, prefix, temperature=temperature, topk=topk, beam_width=beam_width,
+                                                      use_cache=True, **eos_kw)
+            if eos_kw:
+                self.last_lengths = torch.tensor([self.llm_model.last_beam_lengths[0]])
+            return out[:1 + int(self.last_lengths[0])] if stop else out
         if batch_sentences is None:
             batch_sentences = max(1, BEAM_BATCH_ROWS // beam_width)
-        outs = []
+        outs, lengths = [], []
         for s0 in range(0, x.shape[0], batch_sentences):
             xin = torch.from_numpy(x[s0:s0 + batch_sentences]).to(self.device).float()
             prefix = self.brain_model(xin)
             ids = torch.full((xin.shape[0], 1), eot, dtype=torch.long, device=self.device)
             out = self.llm_model.generate_beam_search(ids, max_new_tokens, prefix, temperature=temperature, topk=topk, beam_width=beam_width,
-                                                      use_cache=True)
+                                                      use_cache=True, **eos_kw)
             outs.append(out.view(xin.shape[0], -1))
+            if eos_kw:
+                lens = self.llm_model.last_beam_lengths
+                lengths += [lens[0]] if xin.shape[0] == 1 else [l[0] for l in lens]
+        if eos_kw:
+            self.last_lengths = torch.tensor(lengths)
         return torch.cat(outs)

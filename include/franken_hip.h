@@ -281,6 +281,40 @@ int fk_beam_select_grouped(const float* top_lp, const int64_t* top_id, int64_t r
                            float* scores, const uint64_t* seed, int64_t* step, const int32_t* pos, int32_t* pos_inc, int64_t* cur, int32_t* parent_log,
                            int64_t* tok_log, int64_t log_rows, int32_t* anc, int64_t anc_ld, uint32_t* ticket, void* stream);
 
+/* ---- end-of-text aware decoding.  `eos` is one token id (eos < 0: none; fin / done are then read as 0: nothing is finished and no id
+ * below 0 is ever emitted).  Per row r: fin[r] int32 0/1 (the hypothesis has emitted eos),
+ * len[r] int32 = its generated tokens so far, eos counted once.  inv_lenpow: fp32 [n_lenpow], entry L = 1 / L^alpha rounded from float64,
+ * entry 0 = 1; the kernels only multiply by it, so norm = (score + lp) * inv_lenpow[L] is one fp32 add and one fp32 multiply, and a table
+ * of ones (alpha = 0) ranks by the raw score bit for bit.  A length outside the table uses clamp(L, 0, n_lenpow-1).
+ * fk_beam_select_eos: fk_beam_select_grouped (S >= 1 blocks, same Philox counters and keys, same draws) with these rules per sentence:
+ *   a live beam i proposes its W drawn entries, raw = scores[i] + top_lp[i][pick], L = len[i] + 1; a finished beam proposes ONE candidate,
+ *   r = 0: token eos, raw = scores[i], L = len[i].  The W best candidates survive, by norm = raw * inv_lenpow[L] descending, then by
+ *   candidate number i*W + r.  Survivor b from (i, r): parent i, scores[b] = raw (the raw sums stay), len[b] = L,
+ *   fin[b] = fin[i] || token == eos; cur, logs, table, *step and *pos_inc as in fk_beam_select_grouped (a finished beam keeps feeding eos
+ *   and keeps appending its row).  Every block adds its unfinished survivors to *live_acc (atomic); the last block to finish stores the
+ *   sum to live[0] and clears *live_acc, beside *step += 1.  With no eos among the tokens and a table of ones every output equals
+ *   fk_beam_select_grouped's; a sentence whose beams are all finished is only sorted, and is a fixed point from the next step on.
+ *   live_acc: a zero-initialised uint32 word owned by the caller, like ticket.
+ * fk_beam_backtrack: the walk through the logs [log_rows, S, W] on the device, one block per sentence, one thread per final beam.
+ *   n = min(*step, log_rows); beam b's tokens are tok_log[t][x_t], x_{n-1} = b, x_{t-1} = clamp(parent_log[t][x_t], 0, W-1).  The beams of
+ *   a sentence are ranked by scores * inv_lenpow[len] descending, then beam number; rank 0 is the best.  Writes out_ids[(g*W + rank)*out_ld
+ *   + t0 + t] for t < n, `pad` into the columns t0+n .. out_cols-1 (columns < t0, the prompt, are the caller's), out_scores[g*W + rank]
+ *   (raw) and out_len[g*W + rank].  0 <= t0 <= out_cols <= out_ld; nothing is written at or beyond column out_cols.  A search without
+ *   eos passes fin = 0, len = n and a table of ones.
+ * fk_sample_topk_eos: fk_sample_topk with a per-row done[b] / len[b]: a done row draws nothing and writes eos to cur[b] / out[b][*step],
+ *   every other row draws exactly what fk_sample_topk draws (Philox keyed by *step and b), len[b] += 1, and a row that draws eos becomes
+ *   done.  live[0] = rows not done after the step, by the same live_acc / ticket hand-off.                                              */
+int fk_beam_select_eos(const float* top_lp, const int64_t* top_id, int64_t row_stride, int64_t group_stride, int64_t S, int64_t W, int64_t k,
+                       float* scores, const uint64_t* seed, int64_t* step, const int32_t* pos, int32_t* pos_inc, int64_t* cur, int32_t* parent_log,
+                       int64_t* tok_log, int64_t log_rows, int32_t* anc, int64_t anc_ld, uint32_t* ticket, int64_t eos, int32_t* fin, int32_t* len,
+                       const float* inv_lenpow, int64_t n_lenpow, uint32_t* live_acc, int32_t* live, void* stream);
+int fk_beam_backtrack(const int32_t* parent_log, const int64_t* tok_log, int64_t log_rows, int64_t S, int64_t W, const int64_t* step, const float* scores,
+                      const int32_t* len, const float* inv_lenpow, int64_t n_lenpow, int64_t* out_ids, int64_t out_ld, int64_t out_cols, int64_t t0,
+                      int64_t pad, float* out_scores, int32_t* out_len, void* stream);
+int fk_sample_topk_eos(const float* logits, int64_t ld, int64_t B, int64_t V, float temperature, int64_t top_k, const uint64_t* seed, int64_t* step,
+                       int32_t* pos_inc, int64_t* cur, int64_t* out, int64_t out_ld, int64_t out_cols, uint32_t* ticket, int64_t eos, int32_t* done,
+                       int32_t* len, uint32_t* live_acc, int32_t* live, void* stream);
+
 /* ---- VQ-VAE tokenizer convolutions (models/vq_brain.py), channels-last [B, T, C], causal left padding dil*(K-1):
  * fk_im2col1d: cols[b, t, k, :] = x[b, t*stride + k*dil - pad, :] (zeros outside), Tout = (T-1)/stride + 1, so that
  *   CausalConv1d (:22-28) = fk_gemm_nt(cols, W') with W'[o, k*Cin + c] = W[o, c, k], and CausalConvTranspose1d(kernel 2s,

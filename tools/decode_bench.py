@@ -4,6 +4,7 @@
     python tools/decode_bench.py --model nano --all-modes       # cfg1's gpt2-nano: re-forward vs kv-cache vs kv-cache + hipGraph
     python tools/decode_bench.py --model gpt2 --beam 5 --topk 20 --new-tokens 25     # generate_beam_search: cached (+ hipGraph) vs re-forward
     python tools/decode_bench.py --model gpt2 --beam 5 --sentences 1,2,3,4,8,16 --new-tokens 25    # S sentences in one search vs S searches
+    python tools/decode_bench.py --model gpt2 --beam 5 --eos --new-tokens 25         # end-of-text: step, poll, early exit, device backtrack
 
 Random weights, a 32-token brain prefix, one start token, top_k = 1.  A generate() call also pays the prefill and, in graph mode, the
 capture, so the per-token figure is the MARGINAL cost: (time of N new tokens - time of N/4 new tokens) / (3N/4), medians over the
@@ -125,6 +126,108 @@ def sentences_bench(g, a, d_model):
                   f"{S / t:11.1f}", flush=True)
 
 
+def eos_bench(g, a, prefix, start):
+    """--beam W --eos: what the end-of-text path costs and saves, all as hipGraph searches in one process with the repeats interleaved.
+    (1) the step with an end-of-text id that never ends anything against the plain step (marginal us/step), (2) the same search polled
+    every 1, 8 and never (check_every), (3) a call in which every beam ends early (topk = W collapses the search to its greedy chain; the
+    id is a token that chain first emits near the middle) against the plain call that runs all steps, (4) the host's walk through
+    the logs of 3 sentences against fk_beam_backtrack."""
+    from frankenstein_amd import kernels as K
+    W, n, n4 = a.beam, a.new_tokens, max(1, a.new_tokens // 4)
+    kw = dict(topk=a.topk, beam_width=W, use_cache=True, use_graph=True)
+    never = 50255                                              # an id a random-weight decoder is unlikely to draw; last_steps shows whether it did
+    ran = {}
+
+    def eos_call(name, **extra):
+        def fn(k):
+            g.generate_beam_search(start, k, prefix, eos_token_id=never, **kw, **extra)
+            ran[name] = g.last_steps
+        return fn
+
+    modes = {"plain": lambda k: g.generate_beam_search(start, k, prefix, **kw),
+             "eos, check_every 1e9": eos_call("eos, check_every 1e9", check_every=10 ** 9),
+             "eos, check_every 8": eos_call("eos, check_every 8", check_every=8),
+             "eos, check_every 1": eos_call("eos, check_every 1", check_every=1)}
+    times = {name: {n4: [], n: []} for name in modes}
+    for fn in modes.values():
+        for k in (n4, n):
+            fn(k)
+    for _ in range(a.repeats):
+        for k in (n4, n):
+            for name, fn in modes.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn(k)
+                torch.cuda.synchronize()
+                times[name][k].append(time.perf_counter() - t0)
+    for name in modes:
+        t4, t = statistics.median(times[name][n4]), statistics.median(times[name][n])
+        print(f"{name:24s}: {(t - t4) / max(1, n - n4) * 1e6:9.1f} us/step (marginal) | whole call {t * 1e3:8.2f} ms [{min(times[name][n]) * 1e3:.2f} .. "
+              f"{max(times[name][n]) * 1e3:.2f}]" + (f", ran {ran[name]} of {n} steps" if name in ran else ""), flush=True)
+    # ---- (3) early exit: the greedy chain of the topk = W search and a token it first emits near the middle
+    gk = dict(kw, topk=W)
+    chain = g.generate_beam_search(start, n, prefix, **gk).cpu().tolist()[start.shape[1]:]
+    js = [j for j in range(n // 3, n - 1) if chain[j] not in chain[:j]]
+    if not js:
+        print(f"early exit: the greedy chain of this model emits no new token between steps {n // 3} and {n - 1}; not measured")
+    else:
+        j = min(js, key=lambda j: abs(j + 1 - n // 2))
+        fns = {"plain, all steps": lambda: g.generate_beam_search(start, n, prefix, **gk),
+               "eos, early exit": lambda: g.generate_beam_search(start, n, prefix, eos_token_id=chain[j], **gk)}
+        ts = {name: [] for name in fns}
+        for fn in fns.values():
+            fn()
+        for _ in range(a.repeats):
+            for name, fn in fns.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                ts[name].append(time.perf_counter() - t0)
+        print(f"early exit (topk = W = {W}, the end-of-text id is the chain's token {j + 1} of {n}; ran {g.last_steps} steps): "
+              + ", ".join(f"{name} {statistics.median(v) * 1e3:.2f} ms" for name, v in ts.items()), flush=True)
+    # ---- (4) the walk through the logs: host against device, 3 sentences
+    S = 3
+    st = K.BeamState("cuda", W, n, 64, seed=list(range(S)), groups=S, eos=never)
+    st.parent_log.copy_(torch.randint(0, W, tuple(st.parent_log.shape), dtype=torch.int32))
+    st.tok_log.copy_(torch.randint(0, 50257, tuple(st.tok_log.shape)))
+    st.scores.copy_(-torch.rand(S * W))
+    st.step.fill_(n)
+    st.len.fill_(n)
+    prompts = torch.full((S, 1), 50256, dtype=torch.int64, device="cuda")
+
+    def host_walk():
+        parents, toks, scores = st.parent_log.cpu().tolist(), st.tok_log.cpu().tolist(), st.scores.cpu().view(S, W)
+        pr, out = prompts.cpu().tolist(), []
+        for s in range(S):
+            beams = []
+            for b in range(W):
+                seq = []
+                for t in range(n - 1, -1, -1):
+                    seq.append(toks[t][s * W + b])
+                    b = parents[t][s * W + b]
+                beams.append(pr[s] + seq[::-1])
+            out.append(beams[int(scores[s].argmax())])
+        return out
+
+    def device_walk():
+        ids = torch.empty((S, W, 1 + n), dtype=torch.int64, device="cuda")
+        ids[:, :, :1] = prompts[:, None, :]
+        scores, lens = K.beam_backtrack(st, ids, 1, never)
+        return ids.cpu().tolist(), scores.cpu().tolist(), lens.cpu().tolist()
+
+    for name, fn in (("host walk", host_walk), ("fk_beam_backtrack", device_walk)):
+        fn()
+        ts = []
+        for _ in range(max(a.repeats, 20)):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            ts.append(time.perf_counter() - t0)
+        print(f"backtrack of {S} sentences x {W} beams x {n} steps, {name:18s}: {statistics.median(ts) * 1e6:8.1f} us [{min(ts) * 1e6:.1f} .. {max(ts) * 1e6:.1f}]")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", choices=sorted(MODELS), default="nano")
@@ -137,6 +240,7 @@ def main():
     ap.add_argument("--topk", type=int, default=20, help="top-k of the beam search's draws (with --beam)")
     ap.add_argument("--sentences", type=lambda v: [int(x) for x in v.split(",")], default=None,
                     help="with --beam: sentences per batched search, one or a comma-separated list; each beside as many one-sentence searches")
+    ap.add_argument("--eos", action="store_true", help="with --beam: the end-of-text path (step against the plain step, cost of the poll, early exit, backtrack)")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "decode_bench needs the GPU"
 
@@ -157,6 +261,9 @@ def main():
     if a.beam:
         if B != 1:
             ap.error("--beam with --batch: give the number of sentences as --sentences")
+        if a.eos:
+            print(f"beam width {a.beam}, topk {a.topk}, end-of-text")
+            return eos_bench(g, a, prefix, start)
         print(f"beam width {a.beam}, topk {a.topk}")
         return beam_bench(g, a, prefix, start)
     for name, kw in MODES.items():
