@@ -10,6 +10,8 @@
 //                       LOCAL slots, fk_kv_append folded into the attention launch, one select block per sentence + a ticket
 //   fk_beam_select_eos / fk_beam_backtrack / fk_sample_topk_eos   end-of-text: finished beams and rows, length-normalised ranking, a live
 //                       count for the host's early exit, and the walk through the logs on the device
+// The select, the beam attention and the sampling are one kernel template each, and so are their host sides (beam_select,
+// check_ / launch_attn_decode_beam and sample_topk behind the kernels): the entry points of a family share their checks and their launch.
 #include "fk_common.h"
 
 namespace {
@@ -662,6 +664,65 @@ __global__ __launch_bounds__(BACKTRACK_THREADS) void beam_backtrack_kernel(const
 
 }  // namespace
 
+// What the entry points of a family share, written once: the argument checks, the launch and its check.  `fn` is the entry point's name, `ptrs`
+// whether all the pointers it needs are there; each returns FK_OK or the fk_set_error code.
+template <bool EOS>
+static int sample_topk(const char* fn, bool ptrs, const float* logits, int64_t ld, int64_t B, int64_t V, float temperature, int64_t top_k, const uint64_t* seed,
+                       int64_t* step, int32_t* pos_inc, int64_t* cur, int64_t* out, int64_t out_ld, int64_t out_cols, uint32_t* ticket, const EosArgs& ea, void* stream) {
+  FK_CHECK_ARG(out == nullptr || (out_cols > 0 && out_cols <= out_ld), "%s: out given without its width (out_cols=%lld, out_ld=%lld)", fn, (long long)out_cols,
+               (long long)out_ld);
+  FK_CHECK_ARG(ptrs, "%s: null pointer", fn);
+  FK_CHECK_ARG(B > 0 && B < 65536 && V > 0 && V < (1LL << 31) && ld >= V && temperature > 0.0f, "%s: bad arguments (B=%lld V=%lld temperature=%g)", fn,
+               (long long)B, (long long)V, (double)temperature);
+  hipLaunchKernelGGL(sample_topk_kernel<EOS>, dim3((unsigned)B), dim3(SAMPLE_THREADS), 0, (hipStream_t)stream, logits, ld, (int)V, 1.0f / temperature,
+                     (int)(top_k > 0 && top_k < V ? top_k : 0), (const unsigned long long*)seed, step, pos_inc, cur, out, out_ld, out_cols, ticket, ea);
+  FK_CHECK_LAUNCH(fn);
+  return FK_OK;
+}
+
+static int check_attn_decode_beam(const char* fn, bool ptrs, const void* kv, int64_t kv_bs, int64_t kv_rs, int64_t anc_ld, int64_t W, int64_t H, int64_t D, int dtype) {
+  FK_CHECK_ARG((dtype == FK_F32 || dtype == FK_BF16) && ptrs && W > 0 && W < 65536 && H > 0 && H < 65536 && anc_ld > 0, "%s: bad arguments", fn);
+  FK_CHECK_ARG(D == 16 || D == 32 || D == 64 || D == 128, "%s: head_dim %lld not in {16, 32, 64, 128}", fn, (long long)D);
+  const int64_t vn = dtype == FK_BF16 ? 8 : 4;
+  FK_CHECK_ARG(((uintptr_t)kv & 15) == 0 && kv_bs % vn == 0 && kv_rs % vn == 0 && kv_rs >= 2 * H * D,
+               "%s: cache rows must be 16-byte aligned and hold key|value (kv_bs=%lld, kv_rs=%lld)", fn, (long long)kv_bs, (long long)kv_rs);
+  return FK_OK;
+}
+
+// grid = (H, rows): GROUPED rows = S * W, the beams of S sentences; otherwise the W beams of one sentence, and tmax and append are not read
+template <bool GROUPED>
+static int launch_attn_decode_beam(const char* fn, const void* q, int64_t q_bs, void* kv, int64_t kv_bs, int64_t kv_rs, int64_t tmax, const int32_t* anc, int64_t anc_ld,
+                                   void* out, int64_t o_bs, const int32_t* pos, int64_t rows, int64_t W, int64_t H, int64_t D, float scale, int append, int dtype,
+                                   void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  dim3 grid((unsigned)H, (unsigned)rows), block(256);
+#define FK_ADB(TT, DD) hipLaunchKernelGGL((attn_decode_beam_kernel<TT, DD, GROUPED>), grid, block, 0, s, (const TT*)q, q_bs, (TT*)kv, kv_bs, kv_rs, (int)tmax, anc, anc_ld, (TT*)out, o_bs, pos, (int)W, (int)H, scale, append)
+  if (dtype == FK_BF16) { if (D == 16) FK_ADB(bf16_t, 16); else if (D == 32) FK_ADB(bf16_t, 32); else if (D == 64) FK_ADB(bf16_t, 64); else FK_ADB(bf16_t, 128); }
+  else { if (D == 16) FK_ADB(float, 16); else if (D == 32) FK_ADB(float, 32); else if (D == 64) FK_ADB(float, 64); else FK_ADB(float, 128); }
+#undef FK_ADB
+  FK_CHECK_LAUNCH(fn);
+  return FK_OK;
+}
+
+// GROUPED: one block per sentence, S sentences whose rows lie group_stride apart, and a ticket; otherwise S = 1, group_stride = 0 and no ticket
+template <bool GROUPED, bool EOS>
+static int beam_select(const char* fn, bool ptrs, const float* top_lp, const int64_t* top_id, int64_t row_stride, int64_t group_stride, int64_t S, int64_t W, int64_t k,
+                       float* scores, const uint64_t* seed, int64_t* step, const int32_t* pos, int32_t* pos_inc, int64_t* cur, int32_t* parent_log, int64_t* tok_log,
+                       int64_t log_rows, int32_t* anc, int64_t anc_ld, uint32_t* ticket, const EosArgs& ea, void* stream) {
+  FK_CHECK_ARG(ptrs, "%s: null pointer", fn);
+  FK_CHECK_ARG(W >= 1 && W <= BEAM_MAX_W && k >= W && k <= BEAM_MAX_K, "%s: need 1 <= W <= %d and W <= k <= %d (W=%lld k=%lld)", fn, BEAM_MAX_W, BEAM_MAX_K,
+               (long long)W, (long long)k);
+  FK_CHECK_ARG(S >= 1 && S * W < 65536, "%s: need S >= 1 and S * W < 65536 rows (S=%lld W=%lld)", fn, (long long)S, (long long)W);
+  FK_CHECK_ARG((row_stride == 0 || row_stride >= k) && (!GROUPED || group_stride >= (W - 1) * row_stride + k),
+               "%s: rows overlap (row_stride=%lld group_stride=%lld k=%lld)", fn, (long long)row_stride, (long long)group_stride, (long long)k);
+  FK_CHECK_ARG(anc_ld > 0 && log_rows >= 0 && (log_rows == 0 || (parent_log && tok_log)), "%s: bad arguments (anc_ld=%lld log_rows=%lld)", fn, (long long)anc_ld,
+               (long long)log_rows);
+  hipLaunchKernelGGL((beam_select_kernel<GROUPED, EOS>), dim3((unsigned)S), dim3(BEAM_SELECT_THREADS), 0, (hipStream_t)stream, top_lp, top_id, row_stride, group_stride,
+                     (int)W, (int)k, scores, (const unsigned long long*)seed, step, pos, pos_inc, cur, parent_log, tok_log, log_rows, anc, anc_ld, ticket, ea);
+  FK_CHECK_LAUNCH(fn);
+  return FK_OK;
+}
+
 extern "C" {
 
 int fk_gpt_embed_step(const int64_t* idx, const float* wte, const float* wpe, const int32_t* pos, void* out, int64_t B, int64_t dim,
@@ -697,35 +758,17 @@ int fk_attn_decode(const void* q, int64_t q_bs, const void* kv, int64_t kv_bs, i
   return FK_OK;
 }
 
-int fk_sample_topk(const float* logits, int64_t ld, int64_t B, int64_t V, float temperature, int64_t top_k, const uint64_t* seed,
-                   int64_t* step, int32_t* pos_inc, int64_t* cur, int64_t* out, int64_t out_ld, int64_t out_cols, uint32_t* ticket,
-                   void* stream) {
-  FK_CHECK_ARG(out == nullptr || (out_cols > 0 && out_cols <= out_ld), "fk_sample_topk: out given without its width (out_cols=%lld, out_ld=%lld)",
-               (long long)out_cols, (long long)out_ld);
-  FK_CHECK_ARG(logits && seed && step && cur && ticket && B > 0 && B < 65536 && V > 0 && V < (1LL << 31) && ld >= V && temperature > 0.0f,
-               "fk_sample_topk: bad arguments (B=%lld V=%lld temperature=%g)", (long long)B, (long long)V, (double)temperature);
-  hipLaunchKernelGGL(sample_topk_kernel<false>, dim3((unsigned)B), dim3(SAMPLE_THREADS), 0, (hipStream_t)stream, logits, ld, (int)V, 1.0f / temperature,
-                     (int)(top_k > 0 && top_k < V ? top_k : 0), (const unsigned long long*)seed, step, pos_inc, cur, out, out_ld, out_cols, ticket, EosArgs{});
-  FK_CHECK_LAUNCH("fk_sample_topk");
-  return FK_OK;
+int fk_sample_topk(const float* logits, int64_t ld, int64_t B, int64_t V, float temperature, int64_t top_k, const uint64_t* seed, int64_t* step,
+                   int32_t* pos_inc, int64_t* cur, int64_t* out, int64_t out_ld, int64_t out_cols, uint32_t* ticket, void* stream) {
+  return sample_topk<false>("fk_sample_topk", logits && seed && step && cur && ticket, logits, ld, B, V, temperature, top_k, seed, step, pos_inc, cur, out, out_ld,
+                            out_cols, ticket, EosArgs{}, stream);
 }
 
 int fk_attn_decode_beam(const void* q, int64_t q_bs, const void* kv, int64_t kv_bs, int64_t kv_rs, const int32_t* anc, int64_t anc_ld, void* out,
                         int64_t o_bs, const int32_t* pos, int64_t W, int64_t H, int64_t D, float scale, int dtype, void* stream) {
-  FK_CHECK_ARG((dtype == FK_F32 || dtype == FK_BF16) && q && kv && anc && out && pos && W > 0 && W < 65536 && H > 0 && H < 65536 && anc_ld > 0,
-               "fk_attn_decode_beam: bad arguments");
-  FK_CHECK_ARG(D == 16 || D == 32 || D == 64 || D == 128, "fk_attn_decode_beam: head_dim %lld not in {16, 32, 64, 128}", (long long)D);
-  const int64_t vn = dtype == FK_BF16 ? 8 : 4;
-  FK_CHECK_ARG(((uintptr_t)kv & 15) == 0 && kv_bs % vn == 0 && kv_rs % vn == 0 && kv_rs >= 2 * H * D,
-               "fk_attn_decode_beam: cache rows must be 16-byte aligned and hold key|value (kv_bs=%lld, kv_rs=%lld)", (long long)kv_bs, (long long)kv_rs);
-  hipStream_t s = (hipStream_t)stream;
-  dim3 grid((unsigned)H, (unsigned)W), block(256);
-#define FK_ADB(TT, DD) hipLaunchKernelGGL((attn_decode_beam_kernel<TT, DD, false>), grid, block, 0, s, (const TT*)q, q_bs, (TT*)kv, kv_bs, kv_rs, 0, anc, anc_ld, (TT*)out, o_bs, pos, (int)W, (int)H, scale, 0)
-  if (dtype == FK_BF16) { if (D == 16) FK_ADB(bf16_t, 16); else if (D == 32) FK_ADB(bf16_t, 32); else if (D == 64) FK_ADB(bf16_t, 64); else FK_ADB(bf16_t, 128); }
-  else { if (D == 16) FK_ADB(float, 16); else if (D == 32) FK_ADB(float, 32); else if (D == 64) FK_ADB(float, 64); else FK_ADB(float, 128); }
-#undef FK_ADB
-  FK_CHECK_LAUNCH("fk_attn_decode_beam");
-  return FK_OK;
+  const int rc = check_attn_decode_beam("fk_attn_decode_beam", q && kv && anc && out && pos, kv, kv_bs, kv_rs, anc_ld, W, H, D, dtype);
+  if (rc != FK_OK) return rc;
+  return launch_attn_decode_beam<false>("fk_attn_decode_beam", q, q_bs, (void*)kv, kv_bs, kv_rs, 0, anc, anc_ld, out, o_bs, pos, W, W, H, D, scale, 0, dtype, stream);
 }
 
 int fk_beam_topk(const float* logits, int64_t ld, int64_t R, int64_t V, float temperature, int64_t k, float* top_lp, int64_t* top_id, void* stream) {
@@ -742,78 +785,40 @@ int fk_beam_topk(const float* logits, int64_t ld, int64_t R, int64_t V, float te
 int fk_beam_select(const float* top_lp, const int64_t* top_id, int64_t row_stride, int64_t W, int64_t k, float* scores, const uint64_t* seed,
                    int64_t* step, const int32_t* pos, int32_t* pos_inc, int64_t* cur, int32_t* parent_log, int64_t* tok_log, int64_t log_rows,
                    int32_t* anc, int64_t anc_ld, void* stream) {
-  FK_CHECK_ARG(top_lp && top_id && scores && seed && step && pos && cur && anc, "fk_beam_select: null pointer");
-  FK_CHECK_ARG(W >= 1 && W <= BEAM_MAX_W && k >= W && k <= BEAM_MAX_K, "fk_beam_select: need 1 <= W <= %d and W <= k <= %d (W=%lld k=%lld)", BEAM_MAX_W,
-               BEAM_MAX_K, (long long)W, (long long)k);
-  FK_CHECK_ARG((row_stride == 0 || row_stride >= k) && anc_ld > 0 && log_rows >= 0 && (log_rows == 0 || (parent_log && tok_log)),
-               "fk_beam_select: bad arguments (row_stride=%lld anc_ld=%lld log_rows=%lld)", (long long)row_stride, (long long)anc_ld, (long long)log_rows);
-  hipLaunchKernelGGL((beam_select_kernel<false, false>), dim3(1), dim3(BEAM_SELECT_THREADS), 0, (hipStream_t)stream, top_lp, top_id, row_stride, (int64_t)0, (int)W,
-                     (int)k, scores, (const unsigned long long*)seed, step, pos, pos_inc, cur, parent_log, tok_log, log_rows, anc, anc_ld, (unsigned*)nullptr, EosArgs{});
-  FK_CHECK_LAUNCH("fk_beam_select");
-  return FK_OK;
+  return beam_select<false, false>("fk_beam_select", top_lp && top_id && scores && seed && step && pos && cur && anc, top_lp, top_id, row_stride, 0, 1, W, k, scores,
+                                   seed, step, pos, pos_inc, cur, parent_log, tok_log, log_rows, anc, anc_ld, nullptr, EosArgs{}, stream);
 }
 
 int fk_attn_decode_beam_grouped(const void* qkv, int64_t q_bs, void* kv, int64_t kv_bs, int64_t kv_rs, int64_t tmax, const int32_t* anc, int64_t anc_ld,
                                 void* out, int64_t o_bs, const int32_t* pos, int64_t S, int64_t W, int64_t H, int64_t D, float scale, int append, int dtype,
                                 void* stream) {
-  FK_CHECK_ARG((dtype == FK_F32 || dtype == FK_BF16) && qkv && kv && anc && out && pos && W > 0 && W < 65536 && H > 0 && H < 65536 && anc_ld > 0,
-               "fk_attn_decode_beam_grouped: bad arguments");
+  const int rc = check_attn_decode_beam("fk_attn_decode_beam_grouped", qkv && kv && anc && out && pos, kv, kv_bs, kv_rs, anc_ld, W, H, D, dtype);
+  if (rc != FK_OK) return rc;
   FK_CHECK_ARG(S >= 1 && S < 65536 && S * W < 65536, "fk_attn_decode_beam_grouped: need S >= 1 and S * W < 65536 rows (S=%lld W=%lld)", (long long)S, (long long)W);
   FK_CHECK_ARG(tmax > 0 && tmax < (1LL << 31), "fk_attn_decode_beam_grouped: tmax=%lld", (long long)tmax);
-  FK_CHECK_ARG(D == 16 || D == 32 || D == 64 || D == 128, "fk_attn_decode_beam_grouped: head_dim %lld not in {16, 32, 64, 128}", (long long)D);
-  const int64_t vn = dtype == FK_BF16 ? 8 : 4;
-  FK_CHECK_ARG(((uintptr_t)kv & 15) == 0 && kv_bs % vn == 0 && kv_rs % vn == 0 && kv_rs >= 2 * H * D,
-               "fk_attn_decode_beam_grouped: cache rows must be 16-byte aligned and hold key|value (kv_bs=%lld, kv_rs=%lld)", (long long)kv_bs, (long long)kv_rs);
-  FK_CHECK_ARG(!append || (((uintptr_t)qkv & 15) == 0 && q_bs % vn == 0 && q_bs >= 3 * H * D),
+  FK_CHECK_ARG(!append || (((uintptr_t)qkv & 15) == 0 && q_bs % (dtype == FK_BF16 ? 8 : 4) == 0 && q_bs >= 3 * H * D),
                "fk_attn_decode_beam_grouped: append reads [q | k | v] rows as 16-byte vectors (q_bs=%lld)", (long long)q_bs);
-  hipStream_t s = (hipStream_t)stream;
-  dim3 grid((unsigned)H, (unsigned)(S * W)), block(256);
-#define FK_ADB(TT, DD) hipLaunchKernelGGL((attn_decode_beam_kernel<TT, DD, true>), grid, block, 0, s, (const TT*)qkv, q_bs, (TT*)kv, kv_bs, kv_rs, (int)tmax, anc, anc_ld, (TT*)out, o_bs, pos, (int)W, (int)H, scale, append)
-  if (dtype == FK_BF16) { if (D == 16) FK_ADB(bf16_t, 16); else if (D == 32) FK_ADB(bf16_t, 32); else if (D == 64) FK_ADB(bf16_t, 64); else FK_ADB(bf16_t, 128); }
-  else { if (D == 16) FK_ADB(float, 16); else if (D == 32) FK_ADB(float, 32); else if (D == 64) FK_ADB(float, 64); else FK_ADB(float, 128); }
-#undef FK_ADB
-  FK_CHECK_LAUNCH("fk_attn_decode_beam_grouped");
-  return FK_OK;
+  return launch_attn_decode_beam<true>("fk_attn_decode_beam_grouped", qkv, q_bs, kv, kv_bs, kv_rs, tmax, anc, anc_ld, out, o_bs, pos, S * W, W, H, D, scale, append, dtype,
+                                       stream);
 }
 
 int fk_beam_select_grouped(const float* top_lp, const int64_t* top_id, int64_t row_stride, int64_t group_stride, int64_t S, int64_t W, int64_t k,
                            float* scores, const uint64_t* seed, int64_t* step, const int32_t* pos, int32_t* pos_inc, int64_t* cur, int32_t* parent_log,
                            int64_t* tok_log, int64_t log_rows, int32_t* anc, int64_t anc_ld, uint32_t* ticket, void* stream) {
-  FK_CHECK_ARG(top_lp && top_id && scores && seed && step && pos && cur && anc && ticket, "fk_beam_select_grouped: null pointer");
-  FK_CHECK_ARG(W >= 1 && W <= BEAM_MAX_W && k >= W && k <= BEAM_MAX_K, "fk_beam_select_grouped: need 1 <= W <= %d and W <= k <= %d (W=%lld k=%lld)",
-               BEAM_MAX_W, BEAM_MAX_K, (long long)W, (long long)k);
-  FK_CHECK_ARG(S >= 1 && S * W < 65536, "fk_beam_select_grouped: need S >= 1 and S * W < 65536 rows (S=%lld W=%lld)", (long long)S, (long long)W);
-  FK_CHECK_ARG((row_stride == 0 || row_stride >= k) && group_stride >= (W - 1) * row_stride + k,
-               "fk_beam_select_grouped: rows overlap (row_stride=%lld group_stride=%lld k=%lld)", (long long)row_stride, (long long)group_stride, (long long)k);
-  FK_CHECK_ARG(anc_ld > 0 && log_rows >= 0 && (log_rows == 0 || (parent_log && tok_log)), "fk_beam_select_grouped: bad arguments (anc_ld=%lld log_rows=%lld)",
-               (long long)anc_ld, (long long)log_rows);
-  hipLaunchKernelGGL((beam_select_kernel<true, false>), dim3((unsigned)S), dim3(BEAM_SELECT_THREADS), 0, (hipStream_t)stream, top_lp, top_id, row_stride, group_stride,
-                     (int)W, (int)k, scores, (const unsigned long long*)seed, step, pos, pos_inc, cur, parent_log, tok_log, log_rows, anc, anc_ld, ticket, EosArgs{});
-  FK_CHECK_LAUNCH("fk_beam_select_grouped");
-  return FK_OK;
+  return beam_select<true, false>("fk_beam_select_grouped", top_lp && top_id && scores && seed && step && pos && cur && anc && ticket, top_lp, top_id, row_stride,
+                                  group_stride, S, W, k, scores, seed, step, pos, pos_inc, cur, parent_log, tok_log, log_rows, anc, anc_ld, ticket, EosArgs{}, stream);
 }
 
 int fk_beam_select_eos(const float* top_lp, const int64_t* top_id, int64_t row_stride, int64_t group_stride, int64_t S, int64_t W, int64_t k,
                        float* scores, const uint64_t* seed, int64_t* step, const int32_t* pos, int32_t* pos_inc, int64_t* cur, int32_t* parent_log,
                        int64_t* tok_log, int64_t log_rows, int32_t* anc, int64_t anc_ld, uint32_t* ticket, int64_t eos, int32_t* fin, int32_t* len,
                        const float* inv_lenpow, int64_t n_lenpow, uint32_t* live_acc, int32_t* live, void* stream) {
-  FK_CHECK_ARG(top_lp && top_id && scores && seed && step && pos && cur && anc && ticket && fin && len && inv_lenpow && live_acc && live,
-               "fk_beam_select_eos: null pointer");
-  FK_CHECK_ARG(W >= 1 && W <= BEAM_MAX_W && k >= W && k <= BEAM_MAX_K, "fk_beam_select_eos: need 1 <= W <= %d and W <= k <= %d (W=%lld k=%lld)",
-               BEAM_MAX_W, BEAM_MAX_K, (long long)W, (long long)k);
-  FK_CHECK_ARG(S >= 1 && S * W < 65536, "fk_beam_select_eos: need S >= 1 and S * W < 65536 rows (S=%lld W=%lld)", (long long)S, (long long)W);
-  FK_CHECK_ARG((row_stride == 0 || row_stride >= k) && group_stride >= (W - 1) * row_stride + k,
-               "fk_beam_select_eos: rows overlap (row_stride=%lld group_stride=%lld k=%lld)", (long long)row_stride, (long long)group_stride, (long long)k);
-  FK_CHECK_ARG(anc_ld > 0 && log_rows >= 0 && (log_rows == 0 || (parent_log && tok_log)), "fk_beam_select_eos: bad arguments (anc_ld=%lld log_rows=%lld)",
-               (long long)anc_ld, (long long)log_rows);
   FK_CHECK_ARG(n_lenpow >= 1 && n_lenpow < (1LL << 31) && eos < (1LL << 31), "fk_beam_select_eos: need 1 <= n_lenpow < 2^31 and eos < 2^31 (n_lenpow=%lld eos=%lld)",
                (long long)n_lenpow, (long long)eos);
   const EosArgs ea{eos < 0 ? -1 : (int)eos, fin, len, inv_lenpow, (int)n_lenpow, live_acc, live};
-  hipLaunchKernelGGL((beam_select_kernel<true, true>), dim3((unsigned)S), dim3(BEAM_SELECT_THREADS), 0, (hipStream_t)stream, top_lp, top_id, row_stride,
-                     group_stride, (int)W, (int)k, scores, (const unsigned long long*)seed, step, pos, pos_inc, cur, parent_log, tok_log, log_rows, anc,
-                     anc_ld, ticket, ea);
-  FK_CHECK_LAUNCH("fk_beam_select_eos");
-  return FK_OK;
+  return beam_select<true, true>("fk_beam_select_eos", top_lp && top_id && scores && seed && step && pos && cur && anc && ticket && fin && len && inv_lenpow && live_acc && live,
+                                 top_lp, top_id, row_stride, group_stride, S, W, k, scores, seed, step, pos, pos_inc, cur, parent_log, tok_log, log_rows, anc, anc_ld,
+                                 ticket, ea, stream);
 }
 
 int fk_beam_backtrack(const int32_t* parent_log, const int64_t* tok_log, int64_t log_rows, int64_t S, int64_t W, const int64_t* step, const float* scores,
@@ -836,16 +841,10 @@ int fk_beam_backtrack(const int32_t* parent_log, const int64_t* tok_log, int64_t
 int fk_sample_topk_eos(const float* logits, int64_t ld, int64_t B, int64_t V, float temperature, int64_t top_k, const uint64_t* seed, int64_t* step,
                        int32_t* pos_inc, int64_t* cur, int64_t* out, int64_t out_ld, int64_t out_cols, uint32_t* ticket, int64_t eos, int32_t* done,
                        int32_t* len, uint32_t* live_acc, int32_t* live, void* stream) {
-  FK_CHECK_ARG(out == nullptr || (out_cols > 0 && out_cols <= out_ld), "fk_sample_topk_eos: out given without its width (out_cols=%lld, out_ld=%lld)",
-               (long long)out_cols, (long long)out_ld);
-  FK_CHECK_ARG(logits && seed && step && cur && ticket && done && len && live_acc && live, "fk_sample_topk_eos: null pointer");
-  FK_CHECK_ARG(B > 0 && B < 65536 && V > 0 && V < (1LL << 31) && ld >= V && temperature > 0.0f && eos < (1LL << 31),
-               "fk_sample_topk_eos: bad arguments (B=%lld V=%lld temperature=%g eos=%lld)", (long long)B, (long long)V, (double)temperature, (long long)eos);
+  FK_CHECK_ARG(eos < (1LL << 31), "fk_sample_topk_eos: need eos < 2^31 (eos=%lld)", (long long)eos);
   const EosArgs ea{eos < 0 ? -1 : (int)eos, done, len, nullptr, 0, live_acc, live};
-  hipLaunchKernelGGL(sample_topk_kernel<true>, dim3((unsigned)B), dim3(SAMPLE_THREADS), 0, (hipStream_t)stream, logits, ld, (int)V, 1.0f / temperature,
-                     (int)(top_k > 0 && top_k < V ? top_k : 0), (const unsigned long long*)seed, step, pos_inc, cur, out, out_ld, out_cols, ticket, ea);
-  FK_CHECK_LAUNCH("fk_sample_topk_eos");
-  return FK_OK;
+  return sample_topk<true>("fk_sample_topk_eos", logits && seed && step && cur && ticket && done && len && live_acc && live, logits, ld, B, V, temperature, top_k, seed,
+                           step, pos_inc, cur, out, out_ld, out_cols, ticket, ea, stream);
 }
 
 }  // extern "C"

@@ -580,10 +580,9 @@ class SampleState:
         self.ticket = torch.zeros(1, dtype=torch.int32, device=device)
 
 
-def sample_topk(logits: Tensor, temperature: float, top_k: Optional[int], state: SampleState, cur: Optional[Tensor] = None,
-                out: Optional[Tensor] = None, pos_inc: Optional[Tensor] = None) -> Tensor:
-    """One token per row of fp32 logits [B, V] (row stride >= V): temperature, top-k crop, softmax, multinomial — one launch
-    (models/gpt2_model.py:340-351).  Writes cur [B] int64 (returned), out[:, step] if given, then step += 1 (and pos_inc += 1)."""
+def _sample_topk_call(fn: str, logits: Tensor, temperature: float, top_k: Optional[int], state: SampleState, cur: Optional[Tensor],
+                      out: Optional[Tensor], pos_inc: Optional[Tensor], *tail) -> Tensor:
+    """The body of sample_topk / sample_topk_eos: the asserts and the call of `fn`; `tail` = its arguments behind the ticket."""
     assert logits.dim() == 2 and logits.dtype == torch.float32 and logits.stride(1) == 1
     B, V = logits.shape
     if cur is None:
@@ -595,9 +594,16 @@ def sample_topk(logits: Tensor, temperature: float, top_k: Optional[int], state:
         out_ld, out_cols = out.stride(0), out.shape[1]          # the kernel stops writing at column out_cols, whatever the step counter says
     if pos_inc is not None:
         assert pos_inc.dtype == torch.int32 and pos_inc.numel() == 1
-    call("fk_sample_topk", logits.data_ptr(), logits.stride(0), B, V, float(temperature), int(top_k or 0), state.seed.data_ptr(),
-         state.step.data_ptr(), _ptr(pos_inc), cur.data_ptr(), _ptr(out), out_ld, out_cols, state.ticket.data_ptr(), _stream())
+    call(fn, logits.data_ptr(), logits.stride(0), B, V, float(temperature), int(top_k or 0), state.seed.data_ptr(), state.step.data_ptr(),
+         _ptr(pos_inc), cur.data_ptr(), _ptr(out), out_ld, out_cols, state.ticket.data_ptr(), *tail, _stream())
     return cur
+
+
+def sample_topk(logits: Tensor, temperature: float, top_k: Optional[int], state: SampleState, cur: Optional[Tensor] = None,
+                out: Optional[Tensor] = None, pos_inc: Optional[Tensor] = None) -> Tensor:
+    """One token per row of fp32 logits [B, V] (row stride >= V): temperature, top-k crop, softmax, multinomial — one launch
+    (models/gpt2_model.py:340-351).  Writes cur [B] int64 (returned), out[:, step] if given, then step += 1 (and pos_inc += 1)."""
+    return _sample_topk_call("fk_sample_topk", logits, temperature, top_k, state, cur, out, pos_inc)
 
 
 class SampleEosState:
@@ -617,22 +623,9 @@ def sample_topk_eos(logits: Tensor, temperature: float, top_k: Optional[int], st
     """sample_topk with an end-of-text id (fk_sample_topk_eos): a done row emits eos_state.eos and draws nothing, every other row draws
     what sample_topk draws with the same seed and step, its length grows by one, and a row that draws the id becomes done;
     eos_state.live[0] = the rows still not done."""
-    assert logits.dim() == 2 and logits.dtype == torch.float32 and logits.stride(1) == 1
-    B, V = logits.shape
-    if cur is None:
-        cur = torch.empty(B, dtype=torch.int64, device=logits.device)
-    assert cur.dtype == torch.int64 and cur.is_contiguous() and cur.numel() == B
-    assert eos_state.done.numel() == B and eos_state.len.numel() == B
-    out_ld = out_cols = 0
-    if out is not None:
-        assert out.dtype == torch.int64 and out.dim() == 2 and out.shape[0] == B and out.stride(1) == 1
-        out_ld, out_cols = out.stride(0), out.shape[1]
-    if pos_inc is not None:
-        assert pos_inc.dtype == torch.int32 and pos_inc.numel() == 1
-    call("fk_sample_topk_eos", logits.data_ptr(), logits.stride(0), B, V, float(temperature), int(top_k or 0), state.seed.data_ptr(),
-         state.step.data_ptr(), _ptr(pos_inc), cur.data_ptr(), _ptr(out), out_ld, out_cols, state.ticket.data_ptr(), eos_state.eos,
-         eos_state.done.data_ptr(), eos_state.len.data_ptr(), eos_state.live_acc.data_ptr(), eos_state.live.data_ptr(), _stream())
-    return cur
+    assert eos_state.done.numel() == logits.shape[0] and eos_state.len.numel() == logits.shape[0]
+    return _sample_topk_call("fk_sample_topk_eos", logits, temperature, top_k, state, cur, out, pos_inc, eos_state.eos, eos_state.done.data_ptr(),
+                             eos_state.len.data_ptr(), eos_state.live_acc.data_ptr(), eos_state.live.data_ptr())
 
 
 def attn_decode(qkv: Tensor, kv: Tensor, pos: Tensor, n_head: int) -> Tensor:
@@ -721,21 +714,34 @@ def beam_topk(logits: Tensor, temperature: float, k: int, top_lp: Optional[Tenso
     return top_lp, top_id
 
 
+def _beam_select_call(fn: str, S: Optional[int], top_lp: Tensor, top_id: Tensor, state: BeamState, cur: Tensor, pos: Tensor,
+                      pos_inc: Optional[Tensor], broadcast: bool, *tail) -> Tensor:
+    """The body of beam_select (S = None: one block, rows [W, k] or any [R >= 1, k] with broadcast) and of beam_select_grouped /
+    beam_select_eos (S sentences, rows [S * W, k] or [S, k] with broadcast): the asserts and the call of `fn`; `tail` = its arguments
+    behind anc_ld."""
+    W, k = state.width, top_lp.shape[1]
+    assert top_lp.dtype == torch.float32 and top_id.dtype == torch.int64 and top_lp.is_contiguous() and top_id.is_contiguous()
+    if S is None:
+        assert top_lp.shape == top_id.shape and (broadcast or top_lp.shape[0] == W)
+        shape = (W, k)
+    else:
+        assert top_lp.shape == top_id.shape and top_lp.shape[0] == (S if broadcast else S * W)
+        shape = (k if broadcast else W * k, S, W, k)            # the stride between two sentences' rows, in front
+    assert cur.dtype == torch.int64 and cur.is_contiguous() and cur.numel() == (S or 1) * W
+    assert pos.dtype == torch.int32 and pos.numel() == 1 and (pos_inc is None or (pos_inc.dtype == torch.int32 and pos_inc.numel() == 1))
+    call(fn, top_lp.data_ptr(), top_id.data_ptr(), 0 if broadcast else k, *shape, state.scores.data_ptr(), state.seed.data_ptr(),
+         state.step.data_ptr(), pos.data_ptr(), _ptr(pos_inc), cur.data_ptr(), state.parent_log.data_ptr(), state.tok_log.data_ptr(),
+         state.parent_log.shape[0], state.anc.data_ptr(), state.anc.stride(0), *tail, _stream())
+    return cur
+
+
 def beam_select(top_lp: Tensor, top_id: Tensor, state: BeamState, cur: Tensor, pos: Tensor, pos_inc: Optional[Tensor] = None,
                 broadcast: bool = False) -> Tensor:
     """One beam-search step on the device (draw without replacement, keep the W best of W * W, logs, ancestry; see fk_beam_select in
     include/franken_hip.h).  top_lp / top_id [R, k] from beam_topk, R = W, or any R >= 1 with broadcast=True (every beam reads row 0:
     the first step, where all beams are one sequence).  Writes cur [W] int64 (returned) and state; pos int32 [1] is the row the step
     has just appended (negative: leave the ancestry alone); pos_inc (may be pos) is advanced by one."""
-    W, k = state.width, top_lp.shape[1]
-    assert top_lp.dtype == torch.float32 and top_id.dtype == torch.int64 and top_lp.is_contiguous() and top_id.is_contiguous()
-    assert top_lp.shape == top_id.shape and (broadcast or top_lp.shape[0] == W)
-    assert cur.dtype == torch.int64 and cur.is_contiguous() and cur.numel() == W
-    assert pos.dtype == torch.int32 and pos.numel() == 1 and (pos_inc is None or (pos_inc.dtype == torch.int32 and pos_inc.numel() == 1))
-    call("fk_beam_select", top_lp.data_ptr(), top_id.data_ptr(), 0 if broadcast else k, W, k, state.scores.data_ptr(), state.seed.data_ptr(),
-         state.step.data_ptr(), pos.data_ptr(), _ptr(pos_inc), cur.data_ptr(), state.parent_log.data_ptr(), state.tok_log.data_ptr(),
-         state.parent_log.shape[0], state.anc.data_ptr(), state.anc.stride(0), _stream())
-    return cur
+    return _beam_select_call("fk_beam_select", None, top_lp, top_id, state, cur, pos, pos_inc, broadcast)
 
 
 def attn_decode_beam_grouped(qkv: Tensor, kv: Tensor, anc: Tensor, pos: Tensor, n_head: int, groups: int, append: bool = False) -> Tensor:
@@ -761,16 +767,7 @@ def beam_select_grouped(top_lp: Tensor, top_id: Tensor, state: BeamState, cur: T
     """beam_select for state.groups sentences in one launch, one block each (fk_beam_select_grouped).  top_lp / top_id [groups * W, k]
     from beam_topk, or [groups, k] with broadcast=True (every beam of a sentence reads that sentence's row: the first step).  Writes cur
     [groups * W] int64 (returned) and state; the one step counter and pos_inc advance once, by the last block to finish."""
-    S, W, k = state.groups, state.width, top_lp.shape[1]
-    assert top_lp.dtype == torch.float32 and top_id.dtype == torch.int64 and top_lp.is_contiguous() and top_id.is_contiguous()
-    assert top_lp.shape == top_id.shape and top_lp.shape[0] == (S if broadcast else S * W)
-    assert cur.dtype == torch.int64 and cur.is_contiguous() and cur.numel() == S * W
-    assert pos.dtype == torch.int32 and pos.numel() == 1 and (pos_inc is None or (pos_inc.dtype == torch.int32 and pos_inc.numel() == 1))
-    call("fk_beam_select_grouped", top_lp.data_ptr(), top_id.data_ptr(), 0 if broadcast else k, k if broadcast else W * k, S, W, k,
-         state.scores.data_ptr(), state.seed.data_ptr(), state.step.data_ptr(), pos.data_ptr(), _ptr(pos_inc), cur.data_ptr(),
-         state.parent_log.data_ptr(), state.tok_log.data_ptr(), state.parent_log.shape[0], state.anc.data_ptr(), state.anc.stride(0),
-         state.ticket.data_ptr(), _stream())
-    return cur
+    return _beam_select_call("fk_beam_select_grouped", state.groups, top_lp, top_id, state, cur, pos, pos_inc, broadcast, state.ticket.data_ptr())
 
 
 def beam_select_eos(top_lp: Tensor, top_id: Tensor, state: BeamState, cur: Tensor, pos: Tensor, pos_inc: Optional[Tensor] = None,
@@ -778,17 +775,9 @@ def beam_select_eos(top_lp: Tensor, top_id: Tensor, state: BeamState, cur: Tenso
     """beam_select_grouped with the end-of-text rules (fk_beam_select_eos; state built with eos= / length_penalty=): a finished beam proposes
     itself once, with its score and its length, the survivors are the W best by score * inv_lenpow[length], state.fin / state.len follow
     them and state.live[0] = the unfinished beams of all sentences after the step.  state.groups = 1 is the one-sentence search."""
-    S, W, k = state.groups, state.width, top_lp.shape[1]
-    assert top_lp.dtype == torch.float32 and top_id.dtype == torch.int64 and top_lp.is_contiguous() and top_id.is_contiguous()
-    assert top_lp.shape == top_id.shape and top_lp.shape[0] == (S if broadcast else S * W)
-    assert cur.dtype == torch.int64 and cur.is_contiguous() and cur.numel() == S * W
-    assert pos.dtype == torch.int32 and pos.numel() == 1 and (pos_inc is None or (pos_inc.dtype == torch.int32 and pos_inc.numel() == 1))
-    call("fk_beam_select_eos", top_lp.data_ptr(), top_id.data_ptr(), 0 if broadcast else k, k if broadcast else W * k, S, W, k,
-         state.scores.data_ptr(), state.seed.data_ptr(), state.step.data_ptr(), pos.data_ptr(), _ptr(pos_inc), cur.data_ptr(),
-         state.parent_log.data_ptr(), state.tok_log.data_ptr(), state.parent_log.shape[0], state.anc.data_ptr(), state.anc.stride(0),
-         state.ticket.data_ptr(), -1 if state.eos is None else int(state.eos), state.fin.data_ptr(), state.len.data_ptr(),
-         state.inv_lenpow.data_ptr(), state.inv_lenpow.numel(), state.live_acc.data_ptr(), state.live.data_ptr(), _stream())
-    return cur
+    return _beam_select_call("fk_beam_select_eos", state.groups, top_lp, top_id, state, cur, pos, pos_inc, broadcast, state.ticket.data_ptr(),
+                             -1 if state.eos is None else int(state.eos), state.fin.data_ptr(), state.len.data_ptr(), state.inv_lenpow.data_ptr(),
+                             state.inv_lenpow.numel(), state.live_acc.data_ptr(), state.live.data_ptr())
 
 
 def beam_backtrack(state: BeamState, out_ids: Tensor, t0: int, pad: int):

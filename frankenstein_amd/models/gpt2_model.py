@@ -394,17 +394,17 @@ class GPT(nn.Module):
         t_ctx = 0 if prefix is None else prefix.shape[1]
         total = t_ctx + t0 + max_new_tokens
         cached = use_cache and total <= self.config.block_size and max_new_tokens > 0
+        if use_graph is None:
+            use_graph = max_new_tokens >= 64
         if eos_token_id is not None:
             return self._generate_eos(idx, max_new_tokens, prefix, temperature, top_k, cached, use_graph, int(eos_token_id), int(check_every))
         state = K.SampleState(idx.device) if idx.is_cuda else None      # one Philox stream per call, seeded from torch's generator
-        if use_graph is None:
-            use_graph = max_new_tokens >= 64
+        if cached and use_graph and idx.is_cuda:                        # _generate_dev draws its own seed BEHIND this one: keep both, or the tokens of a torch seed move
+            return self._generate_dev(idx, max_new_tokens, prefix, temperature, top_k, True)
         if cached:
             d = self.config.n_embd
             cache = [torch.empty((B, total, 2 * d), dtype=E.compute_dtype(), device=idx.device) for _ in self.transformer.h]
             logits, pos = self._cached_logits(idx, cache, 0, None if prefix is None else _prep(prefix))
-            if use_graph and idx.is_cuda:
-                return self._generate_graph(idx, logits, cache, pos, max_new_tokens, temperature, top_k)
         for it in range(max_new_tokens):
             if cached:
                 if it > 0:
@@ -416,47 +416,16 @@ class GPT(nn.Module):
             idx = torch.cat((idx, self._sample(logits, temperature, top_k, state)), dim=1)
         return idx[0]
 
-    @torch.no_grad()
-    def _generate_graph(self, idx, logits0, cache, pos0, max_new_tokens, temperature, top_k):
-        B, dev = idx.shape[0], idx.device
-        out = torch.empty((B, max_new_tokens), dtype=torch.int64, device=dev)
-        cur = torch.empty(B, dtype=torch.int64, device=dev)
-        state = K.SampleState(dev)                       # step counter = the column of `out` the next token goes to
-        lg0 = logits0.float()
-        K.sample_topk(lg0 if lg0.stride(-1) == 1 else lg0.contiguous(), temperature, top_k, state, cur=cur, out=out)
-        pos = torch.tensor([pos0], dtype=torch.int32, device=dev)
-
-        def step():
-            # the whole sampling tail is one launch: it writes cur / out[:, step] and advances both the step counter and `pos`
-            K.sample_topk(self._decode_logits_dev(cur, cache, pos), temperature, top_k, state, cur=cur, out=out, pos_inc=pos)
-
-        n_eager = min(2, max_new_tokens - 1)            # warm-up (allocator, lazy shadows) before the capture
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(n_eager):
-                step()
-            remaining = max_new_tokens - 1 - n_eager
-            if remaining > 0:
-                graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graph, stream=side):      # records the step, does not run it
-                    step()
-                for _ in range(remaining):
-                    graph.replay()
-        torch.cuda.current_stream().wait_stream(side)
-        return torch.cat((idx, out), dim=1)[0]
-
     @staticmethod
-    def _run_polled(step, max_new_tokens, use_graph, live, check_every):
-        """Steps 2 .. max_new_tokens of a decode loop whose first step the caller has run: eager, or (use_graph) two eager warm-up steps,
-        one capture and replays.  After every `check_every`-th step `live` (int32 [1] on the device, written by the step) is read with
-        one 4-byte copy and the loop ends when it is 0.  -> the number of steps run, the first included.
-        The warm-up / capture / replay sequence is the one of _generate_graph and the cached beam searches (kept apart so that the calls
-        without an end-of-text id run their code unchanged): a change to it there belongs here too."""
+    def _run_steps(step, max_new_tokens, use_graph, live=None, check_every=None):
+        """Steps 2 .. max_new_tokens of a decode loop whose first step the caller has run: eager on the current stream, or (use_graph) on a
+        side stream two eager warm-up steps, one capture and replays.  live (int32 [1], written by the step): before a step, after every
+        `check_every`-th one, it is read with one 4-byte copy and the loop ends when it is 0; None: never asked, all steps run.
+        -> the number of steps run, the first included."""
         n = 1
 
         def stopped():                                      # asked before a step: every check_every-th step is followed by one read
-            return n % check_every == 0 and int(live.item()) == 0
+            return live is not None and n % check_every == 0 and int(live.item()) == 0
 
         if not (use_graph and max_new_tokens > 1):
             while n < max_new_tokens and not stopped():
@@ -484,33 +453,47 @@ class GPT(nn.Module):
         return n
 
     @torch.no_grad()
+    def _generate_dev(self, idx, max_new_tokens, prefix, temperature, top_k, use_graph, eos=None, check_every=None):
+        """generate on the caches with the position on the device: prefill, then a step that is embed -> blocks -> head -> one sampling
+        launch, which writes cur / out[:, step] and advances both the step counter and `pos` (_run_steps).  eos: K.sample_topk_eos is
+        that launch (done rows, lengths and the live count live on the device) and last_tokens / last_lengths / last_steps are set."""
+        (B, t0), dev, d = idx.shape, idx.device, self.config.n_embd
+        t_ctx = 0 if prefix is None else prefix.shape[1]
+        cache = [torch.empty((B, t_ctx + t0 + max_new_tokens, 2 * d), dtype=E.compute_dtype(), device=dev) for _ in self.transformer.h]
+        logits0, pos0 = self._cached_logits(idx, cache, 0, None if prefix is None else _prep(prefix))
+        if eos is None:
+            out = torch.empty((B, max_new_tokens), dtype=torch.int64, device=dev)
+        else:
+            out = torch.full((B, max_new_tokens), eos, dtype=torch.int64, device=dev)
+        cur = torch.empty(B, dtype=torch.int64, device=dev)
+        state = K.SampleState(dev)                       # step counter = the column of `out` the next token goes to
+        es = None if eos is None else K.SampleEosState(dev, B, eos)
+
+        def sample(logits, pos_inc=None):
+            if es is None:
+                K.sample_topk(logits, temperature, top_k, state, cur=cur, out=out, pos_inc=pos_inc)
+            else:
+                K.sample_topk_eos(logits, temperature, top_k, state, es, cur=cur, out=out, pos_inc=pos_inc)
+
+        lg0 = logits0.float()
+        sample(lg0 if lg0.stride(-1) == 1 else lg0.contiguous())
+        pos = torch.tensor([pos0], dtype=torch.int32, device=dev)
+        steps = self._run_steps(lambda: sample(self._decode_logits_dev(cur, cache, pos), pos), max_new_tokens, use_graph,
+                                None if es is None else es.live, check_every)
+        tokens = torch.cat((idx, out), dim=1)
+        if es is not None:
+            self.last_steps, self.last_tokens, self.last_lengths = steps, tokens, es.len.to(torch.int64)
+        return tokens[0]
+
+    @torch.no_grad()
     def _generate_eos(self, idx, max_new_tokens, prefix, temperature, top_k, cached, use_graph, eos, check_every):
-        """generate with an end-of-text id.  On the caches the step is generate's graph step with K.sample_topk_eos as its tail (done rows,
-        lengths and the live count live on the device); the re-forward loop applies the same rule with torch.where on the host."""
+        """generate with an end-of-text id.  On the caches it is _generate_dev; the re-forward loop applies the same rule with torch.where
+        on the host."""
         assert 0 <= eos < self.config.vocab_size, f"eos_token_id {eos} outside the vocabulary"
         assert check_every >= 1
-        B, t0 = idx.shape
-        dev = idx.device
-        if use_graph is None:
-            use_graph = max_new_tokens >= 64
+        B, dev = idx.shape[0], idx.device
         if cached and idx.is_cuda:
-            d = self.config.n_embd
-            t_ctx = 0 if prefix is None else prefix.shape[1]
-            cache = [torch.empty((B, t_ctx + t0 + max_new_tokens, 2 * d), dtype=E.compute_dtype(), device=dev) for _ in self.transformer.h]
-            logits0, pos0 = self._cached_logits(idx, cache, 0, None if prefix is None else _prep(prefix))
-            out = torch.full((B, max_new_tokens), eos, dtype=torch.int64, device=dev)
-            cur = torch.empty(B, dtype=torch.int64, device=dev)
-            state, es = K.SampleState(dev), K.SampleEosState(dev, B, eos)
-            lg0 = logits0.float()
-            K.sample_topk_eos(lg0 if lg0.stride(-1) == 1 else lg0.contiguous(), temperature, top_k, state, es, cur=cur, out=out)
-            pos = torch.tensor([pos0], dtype=torch.int32, device=dev)
-
-            def step():
-                K.sample_topk_eos(self._decode_logits_dev(cur, cache, pos), temperature, top_k, state, es, cur=cur, out=out, pos_inc=pos)
-
-            self.last_steps = self._run_polled(step, max_new_tokens, use_graph, es.live, check_every)
-            self.last_tokens, self.last_lengths = torch.cat((idx, out), dim=1), es.len.to(torch.int64)
-            return self.last_tokens[0]
+            return self._generate_dev(idx, max_new_tokens, prefix, temperature, top_k, use_graph, eos, check_every)
         state = K.SampleState(dev) if idx.is_cuda else None
         done = torch.zeros(B, dtype=torch.bool, device=dev)
         lens = torch.zeros(B, dtype=torch.int64, device=dev)
@@ -540,9 +523,9 @@ class GPT(nn.Module):
         Default: host-side bookkeeping around the kernel forward (one batched forward of all beams per step, torch.multinomial draws).
         use_cache=True: the prefix and the prompt run once, every step is one cached decode step of all beams with the draw, the
         selection and the bookkeeping on the device (_beam_search_cached; its draws are a Philox stream seeded from torch's generator,
-        not torch.multinomial's); S > 1 sentences share that step (_beam_search_cached_batched: S * beam_width rows, one Philox key per
-        sentence, `seeds` = S ints fixes them).  Outside its envelope (sequence longer than block_size, beam_width > 16, topk > 64 or
-        > vocabulary, host tensors) the call takes the re-forward loop, sentence by sentence.
+        not torch.multinomial's); S > 1 sentences share that step (S * beam_width rows, one Philox key per sentence, `seeds` = S ints
+        fixes them).  Outside its envelope (sequence longer than block_size, beam_width > 16, topk > 64 or > vocabulary, host tensors)
+        the call takes the re-forward loop, sentence by sentence.
         eos_token_id / length_penalty (alpha): a beam that has emitted the id is finished: it stays a candidate with its score and its
         length and draws nothing more; candidates and final beams are ranked by score / length^alpha (length = generated tokens, the id
         counted once); the search stops once every beam of every sentence is finished, which the host asks the device every `check_every`
@@ -551,22 +534,21 @@ class GPT(nn.Module):
         if topk is None:
             topk = 2 * beam_width
         self.eval()
-        S = idx.shape[0]
         total = (0 if prefix is None else prefix.shape[1]) + idx.shape[1] + max_new_tokens
         in_envelope = (use_cache and idx.is_cuda and max_new_tokens > 0 and total <= self.config.block_size
                        and 1 <= beam_width <= K.BEAM_MAX_WIDTH and beam_width <= topk <= min(K.BEAM_MAX_TOPK, self.config.vocab_size))
-        if eos_token_id is not None or length_penalty != 0.0:
-            eos = None if eos_token_id is None else int(eos_token_id)
+        eos_mode = eos_token_id is not None or length_penalty != 0.0
+        eos = None if eos_token_id is None else int(eos_token_id)
+        if eos_mode:
             assert eos is None or 0 <= eos < self.config.vocab_size, f"eos_token_id {eos} outside the vocabulary"
             assert check_every >= 1
-            if in_envelope:
-                return self._beam_search_cached_eos(idx, max_new_tokens, prefix, temperature, topk, beam_width, use_graph, seeds, eos,
-                                                    float(length_penalty), int(check_every))
-            return self._beam_search_host_eos(idx, max_new_tokens, prefix, temperature, topk, beam_width, eos, float(length_penalty), int(check_every))
+            check_every = int(check_every)
         if in_envelope:
-            if S == 1:
-                return self._beam_search_cached(idx, max_new_tokens, prefix, temperature, topk, beam_width, use_graph, seeds)
-            return self._beam_search_cached_batched(idx, max_new_tokens, prefix, temperature, topk, beam_width, use_graph, seeds)
+            return self._beam_search_cached(idx, max_new_tokens, prefix, temperature, topk, beam_width, use_graph, seeds, eos,
+                                            float(length_penalty), check_every, eos_mode)
+        if eos_mode:
+            return self._beam_search_host_eos(idx, max_new_tokens, prefix, temperature, topk, beam_width, eos, float(length_penalty), check_every)
+        S = idx.shape[0]
         if S > 1:
             return torch.stack([self.generate_beam_search(idx[g:g + 1], max_new_tokens, None if prefix is None else prefix[g:g + 1], temperature,
                                                           topk, beam_width) for g in range(S)])
@@ -587,85 +569,34 @@ class GPT(nn.Module):
         return beams[scores.argmax()]
 
     @torch.no_grad()
-    def _beam_search_cached(self, idx, max_new_tokens, prefix, temperature, topk, W, use_graph, seeds=None):
-        """generate_beam_search on per-layer caches [W, total, 2d] that are never reordered: slot b holds the rows beam position b
-        wrote, the int32 ancestry table names the slot of every row of every beam, and K.beam_select rewrites that table when it
-        picks the survivors.  A step is embed -> blocks (K.attn_decode_beam) -> head -> K.beam_topk -> K.beam_select: nothing in
-        it waits for the host, so with use_graph (default: from 64 new tokens, as in generate) it is captured once and replayed.
-        Sets last_beams (W id lists, prompt included) and last_beam_scores."""
-        dev, d = idx.device, self.config.n_embd
-        t_ctx = 0 if prefix is None else prefix.shape[1]
-        p0 = t_ctx + idx.shape[1]
-        total = p0 + max_new_tokens
-        if use_graph is None:
-            use_graph = max_new_tokens >= 64
-        cache = [torch.empty((W, total, 2 * d), dtype=E.compute_dtype(), device=dev) for _ in self.transformer.h]
-        logits0, _ = self._cached_logits(idx, [c[:1] for c in cache], 0, None if prefix is None else _prep(prefix))   # slot 0 <- prefix + prompt
-        state = K.BeamState(dev, W, max_new_tokens, total, seed=seeds)
-        state.anc[:, :p0] = 0
-        cur = torch.empty(W, dtype=torch.int64, device=dev)
-        top_lp = torch.empty((W, topk), dtype=torch.float32, device=dev)
-        top_id = torch.empty((W, topk), dtype=torch.int64, device=dev)
-        lg0 = logits0.float()
-        # first step: all beams are the one prefilled sequence, they draw from the same row; no row has been appended, the table stays
-        K.beam_topk(lg0 if lg0.stride(-1) == 1 else lg0.contiguous(), temperature, topk, top_lp[:1], top_id[:1])
-        K.beam_select(top_lp[:1], top_id[:1], state, cur, torch.tensor([-1], dtype=torch.int32, device=dev), broadcast=True)
-        pos = torch.tensor([p0], dtype=torch.int32, device=dev)
-
-        def step():
-            K.beam_topk(self._decode_logits_dev(cur, cache, pos, state.anc), temperature, topk, top_lp, top_id)
-            K.beam_select(top_lp, top_id, state, cur, pos, pos_inc=pos)
-
-        if use_graph and max_new_tokens > 1:
-            n_eager = min(2, max_new_tokens - 1)            # warm-up (allocator, lazy shadows) before the capture
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                for _ in range(n_eager):
-                    step()
-                remaining = max_new_tokens - 1 - n_eager
-                if remaining > 0:
-                    graph = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(graph, stream=side):      # records the step, does not run it
-                        step()
-                    for _ in range(remaining):
-                        graph.replay()
-            torch.cuda.current_stream().wait_stream(side)
-        else:
-            for _ in range(max_new_tokens - 1):
-                step()
-        parents, toks, scores = state.parent_log.cpu().tolist(), state.tok_log.cpu().tolist(), state.scores.cpu()
-        prompt = idx[0].cpu().tolist()
-        beams = []
-        for b in range(W):                                  # walk every final beam back through its parents
-            seq = []
-            for t in range(max_new_tokens - 1, -1, -1):
-                seq.append(toks[t][b])
-                b = parents[t][b]
-            beams.append(prompt + seq[::-1])
-        self.last_beams = beams
-        self.last_beam_scores = scores.tolist()
-        return torch.tensor(beams[int(scores.argmax())], dtype=idx.dtype, device=dev)
-
-    @torch.no_grad()
-    def _beam_search_cached_batched(self, idx, max_new_tokens, prefix, temperature, topk, W, use_graph, seeds=None):
-        """_beam_search_cached for S sentences at once: S * W rows, row g * W + b is beam b of sentence g.  The caches [S * W, total, 2d] are
-        never reordered; the table holds slots counted inside the sentence, so the sentences cannot read each other's rows.  The prefix and
-        the prompts are prefilled in one pass into the slots g * W (the strided view cache[::W]); the first step draws every sentence's beams
-        from its one row; then a step is embed -> blocks (K.attn_decode_beam_grouped, which also appends the new key|value row) -> head ->
-        K.beam_topk -> K.beam_select_grouped (one block per sentence; one position and one step counter for all).  Up to 16 rows the
-        linear layers stream the weights once (K.gemv_nt), beyond that they are MFMA GEMMs (_step_linear).
-        Sets last_beams (S lists of W id lists, prompt included) and last_beam_scores (S lists); returns the best beam of every sentence."""
+    def _beam_search_cached(self, idx, max_new_tokens, prefix, temperature, topk, W, use_graph, seeds, eos=None, alpha=0.0, check_every=None,
+                            eos_mode=False):
+        """generate_beam_search for S >= 1 sentences on per-layer caches [S * W, total, 2d] that are never reordered: row g * W + b is beam b
+        of sentence g, slot b of a sentence holds the rows its beam position b wrote, the int32 ancestry table names the slot (counted
+        inside the sentence, so the sentences cannot read each other's rows) of every row of every beam, and the select kernel rewrites
+        that table when it picks the survivors.  The prefix and the prompts are prefilled in one pass into the slots g * W; the first step
+        draws every sentence's beams from its one row; then a step is embed -> blocks -> head -> K.beam_topk -> select.  Nothing in it
+        waits for the host, so with use_graph (default: from 64 new tokens, as in generate) it is captured once and replayed (_run_steps).
+        The blocks' attention is K.attn_decode_beam behind K.kv_append_ for one sentence and K.attn_decode_beam_grouped, which also appends
+        the new key|value row, for more; up to 16 rows the linear layers stream the weights once (K.gemv_nt), beyond that they are MFMA
+        GEMMs (_step_linear).  The select is K.beam_select (S = 1) or K.beam_select_grouped (one block per sentence; one position and one
+        step counter for all), and the host walks every final beam back through the logs: last_beams (W id lists, prompt included, in
+        beam order; S > 1: S such lists) and last_beam_scores are set and the best beam of every sentence is returned.
+        eos_mode (an end-of-text id `eos` or a length penalty `alpha`): K.beam_select_eos is the select (one block per sentence, S = 1
+        included), the live count is read every `check_every` steps, and K.beam_backtrack replaces the host's walk: the ids come back
+        ranked, [S, W, t0 + max_new_tokens], padded behind the steps that ran; last_beam_lengths and last_steps are set as well."""
         dev, d = idx.device, self.config.n_embd
         S, t0 = idx.shape
-        t_ctx = 0 if prefix is None else prefix.shape[1]
-        p0 = t_ctx + t0
+        p0 = (0 if prefix is None else prefix.shape[1]) + t0
         total = p0 + max_new_tokens
         if use_graph is None:
             use_graph = max_new_tokens >= 64
+        select = K.beam_select_eos if eos_mode else K.beam_select if S == 1 else K.beam_select_grouped
+        groups = None if S == 1 else S                      # one sentence: the one-sentence attention
         cache = [torch.empty((S * W, total, 2 * d), dtype=E.compute_dtype(), device=dev) for _ in self.transformer.h]
-        logits0, _ = self._cached_logits(idx, [c[::W] for c in cache], 0, None if prefix is None else _prep(prefix))   # slot g * W <- sentence g
-        state = K.BeamState(dev, W, max_new_tokens, total, seed=seeds, groups=S)
+        # slot g * W <- prefix + prompt of sentence g
+        logits0, _ = self._cached_logits(idx, [c[:1] if S == 1 else c[::W] for c in cache], 0, None if prefix is None else _prep(prefix))
+        state = K.BeamState(dev, W, max_new_tokens, total, seed=seeds, groups=S, eos=eos, length_penalty=alpha)     # plain: no end-of-text state
         state.anc[:, :p0] = 0
         cur = torch.empty(S * W, dtype=torch.int64, device=dev)
         top_lp = torch.empty((S * W, topk), dtype=torch.float32, device=dev)
@@ -673,87 +604,38 @@ class GPT(nn.Module):
         lg0 = logits0.float()
         # first step: the beams of a sentence are its one prefilled sequence and draw from the same row; no row has been appended, the table stays
         K.beam_topk(lg0 if lg0.stride(-1) == 1 else lg0.contiguous(), temperature, topk, top_lp[:S], top_id[:S])
-        K.beam_select_grouped(top_lp[:S], top_id[:S], state, cur, torch.tensor([-1], dtype=torch.int32, device=dev), broadcast=True)
+        select(top_lp[:S], top_id[:S], state, cur, torch.tensor([-1], dtype=torch.int32, device=dev), broadcast=True)
         pos = torch.tensor([p0], dtype=torch.int32, device=dev)
 
         def step():
-            K.beam_topk(self._decode_logits_dev(cur, cache, pos, state.anc, groups=S), temperature, topk, top_lp, top_id)
-            K.beam_select_grouped(top_lp, top_id, state, cur, pos, pos_inc=pos)
+            K.beam_topk(self._decode_logits_dev(cur, cache, pos, state.anc, groups=groups), temperature, topk, top_lp, top_id)
+            select(top_lp, top_id, state, cur, pos, pos_inc=pos)
 
-        if use_graph and max_new_tokens > 1:
-            n_eager = min(2, max_new_tokens - 1)            # warm-up (allocator, lazy shadows) before the capture
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                for _ in range(n_eager):
-                    step()
-                remaining = max_new_tokens - 1 - n_eager
-                if remaining > 0:
-                    graph = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(graph, stream=side):      # records the step, does not run it
-                        step()
-                    for _ in range(remaining):
-                        graph.replay()
-            torch.cuda.current_stream().wait_stream(side)
-        else:
-            for _ in range(max_new_tokens - 1):
-                step()
+        steps = self._run_steps(step, max_new_tokens, use_graph, state.live if eos_mode else None, check_every)
+        if eos_mode:
+            self.last_steps = steps
+            ids = torch.empty((S, W, t0 + max_new_tokens), dtype=torch.int64, device=dev)
+            ids[:, :, :t0] = idx[:, None, :]
+            scores, lens = K.beam_backtrack(state, ids, t0, 0 if eos is None else eos)
+            beams, scores, lens = ids.cpu().tolist(), scores.cpu().tolist(), lens.cpu().tolist()
+            if S == 1:
+                self.last_beams, self.last_beam_scores, self.last_beam_lengths = beams[0], scores[0], lens[0]
+                return ids[0, 0].to(idx.dtype)
+            self.last_beams, self.last_beam_scores, self.last_beam_lengths = beams, scores, lens
+            return ids[:, 0].to(idx.dtype)
         parents, toks, scores = state.parent_log.cpu().tolist(), state.tok_log.cpu().tolist(), state.scores.cpu().view(S, W)
         prompts = idx.cpu().tolist()
-        all_beams, best = [], []
+        beams = [[] for _ in range(S)]
         for g in range(S):
-            beams = []
             for b in range(W):                              # walk every final beam back through its parents (beam numbers inside the sentence)
                 seq = []
                 for t in range(max_new_tokens - 1, -1, -1):
                     seq.append(toks[t][g * W + b])
                     b = parents[t][g * W + b]
-                beams.append(prompts[g] + seq[::-1])
-            all_beams.append(beams)
-            best.append(beams[int(scores[g].argmax())])
-        self.last_beams = all_beams
-        self.last_beam_scores = scores.tolist()
-        return torch.tensor(best, dtype=idx.dtype, device=dev)
-
-    @torch.no_grad()
-    def _beam_search_cached_eos(self, idx, max_new_tokens, prefix, temperature, topk, W, use_graph, seeds, eos, alpha, check_every):
-        """_beam_search_cached / _beam_search_cached_batched with end-of-text: the same step with K.beam_select_eos as its tail (one block per
-        sentence, S = 1 included), replayed in chunks of `check_every` between reads of the live count, and K.beam_backtrack instead of the
-        host's walk through the logs: the ids come back ranked, [S, W, t0 + max_new_tokens], padded behind the steps that ran."""
-        dev, d = idx.device, self.config.n_embd
-        S, t0 = idx.shape
-        t_ctx = 0 if prefix is None else prefix.shape[1]
-        p0 = t_ctx + t0
-        total = p0 + max_new_tokens
-        if use_graph is None:
-            use_graph = max_new_tokens >= 64
-        cache = [torch.empty((S * W, total, 2 * d), dtype=E.compute_dtype(), device=dev) for _ in self.transformer.h]
-        logits0, _ = self._cached_logits(idx, [c[:1] if S == 1 else c[::W] for c in cache], 0, None if prefix is None else _prep(prefix))
-        state = K.BeamState(dev, W, max_new_tokens, total, seed=seeds, groups=S, eos=eos, length_penalty=alpha)
-        state.anc[:, :p0] = 0
-        cur = torch.empty(S * W, dtype=torch.int64, device=dev)
-        top_lp = torch.empty((S * W, topk), dtype=torch.float32, device=dev)
-        top_id = torch.empty((S * W, topk), dtype=torch.int64, device=dev)
-        lg0 = logits0.float()
-        K.beam_topk(lg0 if lg0.stride(-1) == 1 else lg0.contiguous(), temperature, topk, top_lp[:S], top_id[:S])
-        K.beam_select_eos(top_lp[:S], top_id[:S], state, cur, torch.tensor([-1], dtype=torch.int32, device=dev), broadcast=True)
-        pos = torch.tensor([p0], dtype=torch.int32, device=dev)
-        groups = None if S == 1 else S                      # one sentence: the one-sentence attention, as in _beam_search_cached
-
-        def step():
-            K.beam_topk(self._decode_logits_dev(cur, cache, pos, state.anc, groups=groups), temperature, topk, top_lp, top_id)
-            K.beam_select_eos(top_lp, top_id, state, cur, pos, pos_inc=pos)
-
-        self.last_steps = self._run_polled(step, max_new_tokens, use_graph, state.live, check_every)
-        ids = torch.empty((S, W, t0 + max_new_tokens), dtype=torch.int64, device=dev)
-        ids[:, :, :t0] = idx[:, None, :]
-        scores, lens = K.beam_backtrack(state, ids, t0, 0 if eos is None else eos)
-        beams, scores, lens = ids.cpu().tolist(), scores.cpu().tolist(), lens.cpu().tolist()
-        if S == 1:
-            self.last_beams, self.last_beam_scores, self.last_beam_lengths = beams[0], scores[0], lens[0]
-            return ids[0, 0].to(idx.dtype)
-        self.last_beams, self.last_beam_scores, self.last_beam_lengths = beams, scores, lens
-        return ids[:, 0].to(idx.dtype)
+                beams[g].append(prompts[g] + seq[::-1])
+        best = [beams[g][int(scores[g].argmax())] for g in range(S)]
+        self.last_beams, self.last_beam_scores = (beams[0], scores[0].tolist()) if S == 1 else (beams, scores.tolist())
+        return torch.tensor(best[0] if S == 1 else best, dtype=idx.dtype, device=dev)
 
     @torch.no_grad()
     def _beam_search_host_eos(self, idx, max_new_tokens, prefix, temperature, topk, W, eos, alpha, check_every):

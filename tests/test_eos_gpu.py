@@ -14,6 +14,8 @@ from tests.test_beam_gpu import (NEW5, ORDER_MARGIN, TMAX, TOPK5, W5, K, build_f
                                  seed_of, select_ref, small_gpt)
 from tests.test_decode_gpt2_gpu import inputs as inputs_124m
 from tests.test_decode_gpt2_gpu import model, z  # noqa: F401  (module-scoped fixtures: GPT-2 124M and its golden file)
+from tests.test_decode_loop_cpu import CASES as LOOP_CASES
+from tests.test_decode_loop_cpu import expected_steps, run_counted
 from tests.test_eos_cpu import eos_step_ref, lenpow_table
 from tests.test_kernels_gpu import dev, rnd
 
@@ -552,3 +554,40 @@ def test_franky_stop_trims_and_pads_and_the_defaults_are_unchanged(fp32_mode):  
             assert bool((many[s, 1 + lengths[s]:] == eot).all()) and eot not in many[s, 1:lengths[s]].tolist()
             assert lengths[s] == n_new or int(many[s, lengths[s]]) == eot
         assert min(lengths) < n_new
+
+
+# =============================================================================================== 11. the one step loop; the two re-forward loops against each other
+@pytest.mark.parametrize("check_every", [1, 3, 8])
+def test_run_steps_counts_alike_eager_and_as_a_graph(check_every):
+    """GPT._run_steps with a step of torch ops (no project kernel): every (max_new_tokens, die) of tests/test_decode_loop_cpu.py, eager on
+    the current stream and as warm-up + capture + replays; both stop where the arithmetic says and run exactly the steps they report."""
+    for max_new_tokens, ce, die in LOOP_CASES:
+        if ce != check_every:
+            continue
+        want = expected_steps(max_new_tokens, check_every, die)
+        eager = run_counted("cuda", max_new_tokens, check_every, die, use_graph=False)
+        graph = run_counted("cuda", max_new_tokens, check_every, die, use_graph=True)
+        assert eager == graph == (want, want - 1), (max_new_tokens, check_every, die, eager, graph)
+    for max_new_tokens in (1, 2, 3, 4, 9):
+        for use_graph in (False, True):
+            assert run_counted("cuda", max_new_tokens, None, 1, use_graph=use_graph, poll=False) == (max_new_tokens, max_new_tokens - 1)
+
+
+def test_plain_re_forward_search_is_the_end_of_text_loop_with_an_id_that_is_never_drawn(golden, fp32_mode):  # noqa: F811
+    """use_cache=False, gpt_small, W = 3, topk = 6, 6 new tokens, one torch seed: the call without an end-of-text id returns what the call
+    with one returns whose id no beam holds (same forwards, same torch.multinomial draws, the same selection with nothing finished), and it
+    records nothing.  The two calls run two loops (the tail of generate_beam_search and _beam_search_host_eos): this pins them to each other."""
+    g, zz, start, pf, _ = small_gpt(golden)
+    g.last_beams = None
+    torch.manual_seed(20260)
+    plain = g.generate_beam_search(start.clone(), 6, pf, topk=6, beam_width=3, use_cache=False)
+    assert g.last_beams is None
+    for eos in (210, 0, 1, 2, 105, 209):
+        torch.manual_seed(20260)
+        out = g.generate_beam_search(start.clone(), 6, pf, topk=6, beam_width=3, use_cache=False, eos_token_id=eos, length_penalty=0.0)
+        if all(tok != eos for beam in g.last_beams for tok in beam):
+            break
+    else:
+        pytest.fail("every candidate id occurs in some beam")
+    assert plain.shape == (4 + 6,) and torch.equal(plain, out)
+    assert g.last_steps == 6 and len(g.last_beams) == 3
