@@ -173,6 +173,67 @@ FK_DEV unsigned radix_select_kth(const float* row, int V, float inv_temp, int k,
   return *sel_prefix;
 }
 
+// Nucleus (top-p) threshold of fk_sample_topp: the smallest key v among the kept keys (>= kth) whose strictly larger kept keys hold less than
+// top_p of the kept mass, mass(i) = exp(row[i] * inv_temp - mx).  radix_select_kth with a histogram of MASS per bin instead of a count: four
+// passes of 8 bits from the top over the keys that match the prefix, the first wave walks the 256 bins from the top as a scan and stops in the
+// bin in which the running mass reaches the target.  The masses are summed as integers, floor(e * 2^32) <= 2^32 in 64-bit LDS words (V < 2^31
+// of them cannot overflow), so neither the histogram nor any comparison depends on the order in which the atomics land.  The target is
+// floor(top_p * total) + 1 units: key v stays iff mass_gt(v) <= floor(top_p * total), the rule `mass_gt < top_p * total` up to one unit of
+// 2^-32.  A target beyond the total (top_p = 1 always, by construction) is not reached: 0 comes back and everything >= kth stays.
+// Every thread of the block calls it and gets the same key.  mhist: 256 64-bit words of LDS, sel_prefix / sel_rem: one word each.
+FK_DEV unsigned mass_select_tau(const float* row, int V, float inv_temp, unsigned kth, float mx, float top_p, unsigned long long* mhist, unsigned* sel_prefix,
+                                unsigned long long* sel_rem) {
+  const int tid = threadIdx.x;
+  if (tid == 0) { *sel_prefix = 0u; *sel_rem = 0ull; }
+  for (int pass = 0; pass < 4; ++pass) {
+    const int shift = 24 - 8 * pass;
+    if (tid < 256) mhist[tid] = 0ull;
+    __syncthreads();
+    const unsigned prefix = *sel_prefix, mask_hi = pass == 0 ? 0u : (0xFFFFFFFFu << (shift + 8));
+    for (int i = tid; i < V; i += SAMPLE_THREADS) {
+      const float x = row[i] * inv_temp;
+      const unsigned key = f32_sortable(x);
+      if (key >= kth && (key & mask_hi) == prefix) {
+        const float e = __expf(x - mx);                   // <= 1: mx is the maximum of the kept values; NaN and 0 add nothing
+        const unsigned long long m = e > 0.0f ? (unsigned long long)(e * 4294967296.0f) : 0ull;
+        if (m) atomicAdd(&mhist[(key >> shift) & 255u], m);
+      }
+    }
+    __syncthreads();
+    if (tid < 64) {                                       // lane l owns the bins 255 - 4l .. 252 - 4l, as in radix_select_kth
+      unsigned long long h[4], mine = 0ull;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) { h[q] = mhist[255 - 4 * tid - q]; mine += h[q]; }
+      unsigned long long incl = mine;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const unsigned long long up = __shfl_up(incl, o, 64);
+        if (tid >= o) incl += up;
+      }
+      unsigned long long rem0 = *sel_rem;
+      if (pass == 0) {                                    // the first histogram holds every kept key: its sum is the total
+        const unsigned long long total = __shfl(incl, 63, 64);
+        rem0 = top_p >= 1.0f ? ~0ull : (unsigned long long)((double)top_p * (double)total) + 1ull;
+        if (rem0 > total) rem0 = 0ull;                    // not reached: no lane answers and *sel_rem stays 0
+      }
+      const unsigned long long before = incl - mine;      // mass in the bins above this lane's
+      if (before < rem0 && rem0 <= incl) {                // one lane: the bins above hold less than the target, with its own they reach it
+        unsigned long long rem = rem0 - before;
+        int q = 0;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          if (q == c && h[c] < rem) { rem -= h[c]; q = c + 1; }
+        }
+        *sel_prefix = prefix | ((unsigned)(255 - 4 * tid - q) << shift);
+        *sel_rem = rem;                                   // >= 1, and the chosen bin holds at least as much: the next pass reaches it too
+      }
+    }
+    __syncthreads();
+    if (pass == 0 && *sel_rem == 0ull) return 0u;         // block-uniform
+  }
+  return *sel_prefix;
+}
+
 // End-of-text state of the EOS variants below (all device pointers; unused and empty in the plain instantiations): fin[r] 0/1 (a finished
 // beam, a done row), len[r] the generated tokens so far with the end-of-text token counted once, inv_lenpow[L] = 1 / L^alpha for
 // L < n_lenpow (the kernels only multiply by it), live_acc the word the blocks add their unfinished rows to, live[0] what the last block
@@ -203,8 +264,10 @@ FK_DEV void eos_ticket_tail(const EosArgs& ea, unsigned n_live, unsigned* ticket
 
 // EOS: a row with fin[b] != 0 draws nothing and emits ea.eos; a row that draws ea.eos becomes done; len[b] counts the tokens of a row up to
 // and including its end-of-text token.  The draw of every other row is the plain kernel's (Philox keyed by step and row).
-template <bool EOS>
-__global__ __launch_bounds__(SAMPLE_THREADS) void sample_topk_kernel(const float* logits, int64_t ld, int V, float inv_temp, int top_k,
+// NUCLEUS: behind the top-k crop a second threshold key, mass_select_tau; everything after the selection asks key >= max(kth, tau), and the
+// Philox counter is the same, so top_p = 1 draws what the instantiation without it draws.  top_p is read by these instantiations only.
+template <bool EOS, bool NUCLEUS>
+__global__ __launch_bounds__(SAMPLE_THREADS) void sample_topk_kernel(const float* logits, int64_t ld, int V, float inv_temp, int top_k, float top_p,
                                                                      const unsigned long long* seed, int64_t* step, int32_t* pos_inc,
                                                                      int64_t* cur, int64_t* out, int64_t out_ld, int64_t out_cols, unsigned* ticket,
                                                                      EosArgs ea) {
@@ -237,6 +300,12 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_topk_kernel(const float
     if (f32_sortable(x) >= kth) mx = fmaxf(mx, x);
   }
   mx = block_reduce(mx, red, [](float a, float c) { return fmaxf(a, c); }, -INFINITY);
+  if constexpr (NUCLEUS) {                                // the most likely token always stays, so mx is the nucleus's maximum as well
+    __shared__ unsigned long long mhist[256];
+    __shared__ unsigned long long sel_rem;
+    const unsigned tau = mass_select_tau(row, V, inv_temp, kth, mx, top_p, mhist, &sel_prefix, &sel_rem);
+    kth = max(kth, tau);
+  }
   const int chunk = (V + SAMPLE_THREADS - 1) / SAMPLE_THREADS, i0 = tid * chunk, i1 = min(V, i0 + chunk);
   float part = 0.0f;
   for (int i = i0; i < i1; ++i) {
@@ -666,16 +735,18 @@ __global__ __launch_bounds__(BACKTRACK_THREADS) void beam_backtrack_kernel(const
 
 // What the entry points of a family share, written once: the argument checks, the launch and its check.  `fn` is the entry point's name, `ptrs`
 // whether all the pointers it needs are there; each returns FK_OK or the fk_set_error code.
-template <bool EOS>
-static int sample_topk(const char* fn, bool ptrs, const float* logits, int64_t ld, int64_t B, int64_t V, float temperature, int64_t top_k, const uint64_t* seed,
-                       int64_t* step, int32_t* pos_inc, int64_t* cur, int64_t* out, int64_t out_ld, int64_t out_cols, uint32_t* ticket, const EosArgs& ea, void* stream) {
+template <bool EOS, bool NUCLEUS>
+static int sample_topk(const char* fn, bool ptrs, const float* logits, int64_t ld, int64_t B, int64_t V, float temperature, int64_t top_k, float top_p,
+                       const uint64_t* seed, int64_t* step, int32_t* pos_inc, int64_t* cur, int64_t* out, int64_t out_ld, int64_t out_cols, uint32_t* ticket,
+                       const EosArgs& ea, void* stream) {
   FK_CHECK_ARG(out == nullptr || (out_cols > 0 && out_cols <= out_ld), "%s: out given without its width (out_cols=%lld, out_ld=%lld)", fn, (long long)out_cols,
                (long long)out_ld);
   FK_CHECK_ARG(ptrs, "%s: null pointer", fn);
   FK_CHECK_ARG(B > 0 && B < 65536 && V > 0 && V < (1LL << 31) && ld >= V && temperature > 0.0f, "%s: bad arguments (B=%lld V=%lld temperature=%g)", fn,
                (long long)B, (long long)V, (double)temperature);
-  hipLaunchKernelGGL(sample_topk_kernel<EOS>, dim3((unsigned)B), dim3(SAMPLE_THREADS), 0, (hipStream_t)stream, logits, ld, (int)V, 1.0f / temperature,
-                     (int)(top_k > 0 && top_k < V ? top_k : 0), (const unsigned long long*)seed, step, pos_inc, cur, out, out_ld, out_cols, ticket, ea);
+  FK_CHECK_ARG(!NUCLEUS || (top_p > 0.0f && top_p <= 1.0f), "%s: need 0 < top_p <= 1 (top_p=%g)", fn, (double)top_p);      // refuses NaN as well
+  hipLaunchKernelGGL((sample_topk_kernel<EOS, NUCLEUS>), dim3((unsigned)B), dim3(SAMPLE_THREADS), 0, (hipStream_t)stream, logits, ld, (int)V, 1.0f / temperature,
+                     (int)(top_k > 0 && top_k < V ? top_k : 0), top_p, (const unsigned long long*)seed, step, pos_inc, cur, out, out_ld, out_cols, ticket, ea);
   FK_CHECK_LAUNCH(fn);
   return FK_OK;
 }
@@ -760,8 +831,8 @@ int fk_attn_decode(const void* q, int64_t q_bs, const void* kv, int64_t kv_bs, i
 
 int fk_sample_topk(const float* logits, int64_t ld, int64_t B, int64_t V, float temperature, int64_t top_k, const uint64_t* seed, int64_t* step,
                    int32_t* pos_inc, int64_t* cur, int64_t* out, int64_t out_ld, int64_t out_cols, uint32_t* ticket, void* stream) {
-  return sample_topk<false>("fk_sample_topk", logits && seed && step && cur && ticket, logits, ld, B, V, temperature, top_k, seed, step, pos_inc, cur, out, out_ld,
-                            out_cols, ticket, EosArgs{}, stream);
+  return sample_topk<false, false>("fk_sample_topk", logits && seed && step && cur && ticket, logits, ld, B, V, temperature, top_k, 1.0f, seed, step, pos_inc, cur, out,
+                                   out_ld, out_cols, ticket, EosArgs{}, stream);
 }
 
 int fk_attn_decode_beam(const void* q, int64_t q_bs, const void* kv, int64_t kv_bs, int64_t kv_rs, const int32_t* anc, int64_t anc_ld, void* out,
@@ -843,8 +914,23 @@ int fk_sample_topk_eos(const float* logits, int64_t ld, int64_t B, int64_t V, fl
                        int32_t* len, uint32_t* live_acc, int32_t* live, void* stream) {
   FK_CHECK_ARG(eos < (1LL << 31), "fk_sample_topk_eos: need eos < 2^31 (eos=%lld)", (long long)eos);
   const EosArgs ea{eos < 0 ? -1 : (int)eos, done, len, nullptr, 0, live_acc, live};
-  return sample_topk<true>("fk_sample_topk_eos", logits && seed && step && cur && ticket && done && len && live_acc && live, logits, ld, B, V, temperature, top_k, seed,
-                           step, pos_inc, cur, out, out_ld, out_cols, ticket, ea, stream);
+  return sample_topk<true, false>("fk_sample_topk_eos", logits && seed && step && cur && ticket && done && len && live_acc && live, logits, ld, B, V, temperature, top_k,
+                                  1.0f, seed, step, pos_inc, cur, out, out_ld, out_cols, ticket, ea, stream);
+}
+
+int fk_sample_topp(const float* logits, int64_t ld, int64_t B, int64_t V, float temperature, int64_t top_k, float top_p, const uint64_t* seed, int64_t* step,
+                   int32_t* pos_inc, int64_t* cur, int64_t* out, int64_t out_ld, int64_t out_cols, uint32_t* ticket, int64_t eos, int32_t* done, int32_t* len,
+                   uint32_t* live_acc, int32_t* live, void* stream) {
+  const bool ptrs = logits && seed && step && cur && ticket;
+  if (!done) {                                           // the plain mode: no end-of-text state at all, eos is not read
+    FK_CHECK_ARG(!len && !live_acc && !live, "fk_sample_topp: len / live_acc / live given without done (all four or none)");
+    return sample_topk<false, true>("fk_sample_topp", ptrs, logits, ld, B, V, temperature, top_k, top_p, seed, step, pos_inc, cur, out, out_ld, out_cols, ticket,
+                                    EosArgs{}, stream);
+  }
+  FK_CHECK_ARG(len && live_acc && live, "fk_sample_topp: done given without len / live_acc / live (all four or none)");
+  FK_CHECK_ARG(eos < (1LL << 31), "fk_sample_topp: need eos < 2^31 (eos=%lld)", (long long)eos);
+  const EosArgs ea{eos < 0 ? -1 : (int)eos, done, len, nullptr, 0, live_acc, live};
+  return sample_topk<true, true>("fk_sample_topp", ptrs, logits, ld, B, V, temperature, top_k, top_p, seed, step, pos_inc, cur, out, out_ld, out_cols, ticket, ea, stream);
 }
 
 }  // extern "C"

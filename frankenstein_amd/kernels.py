@@ -581,8 +581,9 @@ class SampleState:
 
 
 def _sample_topk_call(fn: str, logits: Tensor, temperature: float, top_k: Optional[int], state: SampleState, cur: Optional[Tensor],
-                      out: Optional[Tensor], pos_inc: Optional[Tensor], *tail) -> Tensor:
-    """The body of sample_topk / sample_topk_eos: the asserts and the call of `fn`; `tail` = its arguments behind the ticket."""
+                      out: Optional[Tensor], pos_inc: Optional[Tensor], *tail, top_p: Optional[float] = None) -> Tensor:
+    """The body of sample_topk / sample_topk_eos / sample_topp: the asserts and the call of `fn`; `tail` = its arguments behind the ticket,
+    top_p (sample_topp only) = its argument behind top_k."""
     assert logits.dim() == 2 and logits.dtype == torch.float32 and logits.stride(1) == 1
     B, V = logits.shape
     if cur is None:
@@ -594,7 +595,8 @@ def _sample_topk_call(fn: str, logits: Tensor, temperature: float, top_k: Option
         out_ld, out_cols = out.stride(0), out.shape[1]          # the kernel stops writing at column out_cols, whatever the step counter says
     if pos_inc is not None:
         assert pos_inc.dtype == torch.int32 and pos_inc.numel() == 1
-    call(fn, logits.data_ptr(), logits.stride(0), B, V, float(temperature), int(top_k or 0), state.seed.data_ptr(), state.step.data_ptr(),
+    nucleus = () if top_p is None else (float(top_p),)
+    call(fn, logits.data_ptr(), logits.stride(0), B, V, float(temperature), int(top_k or 0), *nucleus, state.seed.data_ptr(), state.step.data_ptr(),
          _ptr(pos_inc), cur.data_ptr(), _ptr(out), out_ld, out_cols, state.ticket.data_ptr(), *tail, _stream())
     return cur
 
@@ -626,6 +628,22 @@ def sample_topk_eos(logits: Tensor, temperature: float, top_k: Optional[int], st
     assert eos_state.done.numel() == logits.shape[0] and eos_state.len.numel() == logits.shape[0]
     return _sample_topk_call("fk_sample_topk_eos", logits, temperature, top_k, state, cur, out, pos_inc, eos_state.eos, eos_state.done.data_ptr(),
                              eos_state.len.data_ptr(), eos_state.live_acc.data_ptr(), eos_state.live.data_ptr())
+
+
+def sample_topp(logits: Tensor, temperature: float, top_k: Optional[int], top_p: float, state: SampleState,
+                eos_state: Optional[SampleEosState] = None, cur: Optional[Tensor] = None, out: Optional[Tensor] = None,
+                pos_inc: Optional[Tensor] = None) -> Tensor:
+    """sample_topk with a nucleus crop behind the top-k crop, still one launch (fk_sample_topp): of the tokens the top-k crop keeps, token i
+    stays iff the tokens with a strictly larger logit hold less than top_p of the kept probability; so the most likely token always stays,
+    equal logits stay or go together, and top_p = 1 draws what sample_topk draws with the same seed and step.  eos_state: the end-of-text
+    rules of sample_topk_eos on top.  0 < top_p <= 1."""
+    assert 0.0 < float(top_p) <= 1.0, f"top_p {top_p} outside (0, 1]"
+    if eos_state is None:
+        tail = (-1, None, None, None, None)                # the plain mode: no end-of-text state, the id is not read
+    else:
+        assert eos_state.done.numel() == logits.shape[0] and eos_state.len.numel() == logits.shape[0]
+        tail = (eos_state.eos, eos_state.done.data_ptr(), eos_state.len.data_ptr(), eos_state.live_acc.data_ptr(), eos_state.live.data_ptr())
+    return _sample_topk_call("fk_sample_topp", logits, temperature, top_k, state, cur, out, pos_inc, *tail, top_p=top_p)
 
 
 def attn_decode(qkv: Tensor, kv: Tensor, pos: Tensor, n_head: int) -> Tensor:

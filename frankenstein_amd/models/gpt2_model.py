@@ -362,23 +362,42 @@ class GPT(nn.Module):
         return _step_linear(x, self.lm_head, ln=self.transformer.ln_f, head_vocab=self.config.vocab_size)
 
     @staticmethod
-    def _sample(logits, temperature, top_k, state=None):
-        """temperature -> top-k crop -> softmax -> multinomial (models/gpt2_model.py:340-351).  On the device this is ONE launch
-        (fk_sample_topk, Philox keyed by a seed drawn from torch's generator); the torch-op form is kept for host tensors."""
+    def _check_top_p(top_p):
+        """None or 1.0: no nucleus crop (None comes back and the calls are those without the argument); otherwise a float in (0, 1)"""
+        if top_p is None:
+            return None
+        if not 0.0 < float(top_p) <= 1.0:                               # NaN fails both comparisons
+            raise ValueError(f"top_p must lie in (0, 1], got {top_p}")
+        return None if float(top_p) >= 1.0 else float(top_p)
+
+    @staticmethod
+    def _sample(logits, temperature, top_k, state=None, top_p=None):
+        """temperature -> top-k crop -> [nucleus crop] -> softmax -> multinomial (models/gpt2_model.py:340-351).  On the device this is ONE
+        launch (fk_sample_topk or, with top_p, fk_sample_topp; Philox keyed by a seed drawn from torch's generator); the torch-op form is
+        kept for host tensors.  top_p: of the tokens the top-k crop keeps, token i stays iff the tokens with a strictly larger logit hold
+        less than top_p of the kept probability (include/franken_hip.h, fk_sample_topp)."""
+        top_p = GPT._check_top_p(top_p)
         if logits.is_cuda:
             lg = logits.float()
             lg = lg if lg.stride(-1) == 1 else lg.contiguous()
             st = state if state is not None else K.SampleState(logits.device)
+            if top_p is not None:
+                return K.sample_topp(lg, temperature, top_k, top_p, st).view(-1, 1).clone()
             return K.sample_topk(lg, temperature, top_k, st).view(-1, 1).clone()
         logits = logits.float() / temperature
         if top_k is not None:
             v, _ = torch.topk(logits, min(top_k, logits.size(-1)))
             logits = logits.masked_fill(logits < v[:, -1:], -float('Inf'))
+        if top_p is not None:
+            v, _ = torch.sort(logits, dim=-1, descending=True)
+            p = torch.softmax(v, dim=-1)
+            kept = ((p.cumsum(-1) - p) < top_p).sum(-1, keepdim=True)   # exclusive sum: at the first of equal values it is mass_gt, and the kept ones are a prefix
+            logits = logits.masked_fill(logits < v.gather(-1, kept - 1), -float('Inf'))     # below the smallest kept value, so ties stay
         return torch.multinomial(torch.softmax(logits, dim=-1), num_samples=1)
 
     @torch.no_grad()
     def generate(self, idx, max_new_tokens, prefix=None, temperature=1.0, top_k=None, use_cache=True, use_graph=None, eos_token_id=None,
-                 check_every=8):
+                 check_every=8, top_p=None):
         """Sampling loop of the reference (models/gpt2_model.py:328-353: temperature, top-k crop, softmax, multinomial; returns
         the first sample's ids).  With use_cache (default) the prefix + prompt are run once and every new token is one
         incremental step against per-layer key/value caches; with use_graph (default: on from 64 new tokens, where the one-off
@@ -389,7 +408,11 @@ class GPT(nn.Module):
         eos_token_id: a row that draws this id is done: it emits the id from then on and draws nothing (its tokens up to and including
         the id are the ones the call without it draws from the same seed); the loop asks the device every `check_every` steps whether any
         row is still live and stops early if none is.  Returns row 0 at full length, padded with the id, and sets last_tokens
-        [B, t0 + max_new_tokens], last_lengths [B] (generated tokens, the id counted once) and last_steps (steps run)."""
+        [B, t0 + max_new_tokens], last_lengths [B] (generated tokens, the id counted once) and last_steps (steps run).
+        top_p: nucleus sampling behind the top-k crop, on every path: of the tokens the crop keeps, the smallest set of most likely ones whose
+        probability reaches top_p stays (ties with its last member stay too; _sample has the rule).  None or 1.0: off, the calls and the
+        tokens of a torch seed are those without it; outside (0, 1] raises."""
+        top_p = self._check_top_p(top_p)
         B, t0 = idx.shape
         t_ctx = 0 if prefix is None else prefix.shape[1]
         total = t_ctx + t0 + max_new_tokens
@@ -397,10 +420,10 @@ class GPT(nn.Module):
         if use_graph is None:
             use_graph = max_new_tokens >= 64
         if eos_token_id is not None:
-            return self._generate_eos(idx, max_new_tokens, prefix, temperature, top_k, cached, use_graph, int(eos_token_id), int(check_every))
+            return self._generate_eos(idx, max_new_tokens, prefix, temperature, top_k, cached, use_graph, int(eos_token_id), int(check_every), top_p)
         state = K.SampleState(idx.device) if idx.is_cuda else None      # one Philox stream per call, seeded from torch's generator
         if cached and use_graph and idx.is_cuda:                        # _generate_dev draws its own seed BEHIND this one: keep both, or the tokens of a torch seed move
-            return self._generate_dev(idx, max_new_tokens, prefix, temperature, top_k, True)
+            return self._generate_dev(idx, max_new_tokens, prefix, temperature, top_k, True, top_p=top_p)
         if cached:
             d = self.config.n_embd
             cache = [torch.empty((B, total, 2 * d), dtype=E.compute_dtype(), device=idx.device) for _ in self.transformer.h]
@@ -413,7 +436,7 @@ class GPT(nn.Module):
                 idx_cond = idx if idx.size(1) <= self.config.block_size else idx[:, -self.config.block_size:]
                 _, lg = self(idx_cond, prefix=prefix)
                 logits = lg[:, -1, :]
-            idx = torch.cat((idx, self._sample(logits, temperature, top_k, state)), dim=1)
+            idx = torch.cat((idx, self._sample(logits, temperature, top_k, state, top_p)), dim=1)
         return idx[0]
 
     @staticmethod
@@ -453,10 +476,11 @@ class GPT(nn.Module):
         return n
 
     @torch.no_grad()
-    def _generate_dev(self, idx, max_new_tokens, prefix, temperature, top_k, use_graph, eos=None, check_every=None):
+    def _generate_dev(self, idx, max_new_tokens, prefix, temperature, top_k, use_graph, eos=None, check_every=None, top_p=None):
         """generate on the caches with the position on the device: prefill, then a step that is embed -> blocks -> head -> one sampling
         launch, which writes cur / out[:, step] and advances both the step counter and `pos` (_run_steps).  eos: K.sample_topk_eos is
-        that launch (done rows, lengths and the live count live on the device) and last_tokens / last_lengths / last_steps are set."""
+        that launch (done rows, lengths and the live count live on the device) and last_tokens / last_lengths / last_steps are set.
+        top_p (a float below 1, or None): K.sample_topp is that launch, with or without eos."""
         (B, t0), dev, d = idx.shape, idx.device, self.config.n_embd
         t_ctx = 0 if prefix is None else prefix.shape[1]
         cache = [torch.empty((B, t_ctx + t0 + max_new_tokens, 2 * d), dtype=E.compute_dtype(), device=dev) for _ in self.transformer.h]
@@ -470,7 +494,9 @@ class GPT(nn.Module):
         es = None if eos is None else K.SampleEosState(dev, B, eos)
 
         def sample(logits, pos_inc=None):
-            if es is None:
+            if top_p is not None:
+                K.sample_topp(logits, temperature, top_k, top_p, state, es, cur=cur, out=out, pos_inc=pos_inc)
+            elif es is None:
                 K.sample_topk(logits, temperature, top_k, state, cur=cur, out=out, pos_inc=pos_inc)
             else:
                 K.sample_topk_eos(logits, temperature, top_k, state, es, cur=cur, out=out, pos_inc=pos_inc)
@@ -486,14 +512,14 @@ class GPT(nn.Module):
         return tokens[0]
 
     @torch.no_grad()
-    def _generate_eos(self, idx, max_new_tokens, prefix, temperature, top_k, cached, use_graph, eos, check_every):
+    def _generate_eos(self, idx, max_new_tokens, prefix, temperature, top_k, cached, use_graph, eos, check_every, top_p=None):
         """generate with an end-of-text id.  On the caches it is _generate_dev; the re-forward loop applies the same rule with torch.where
         on the host."""
         assert 0 <= eos < self.config.vocab_size, f"eos_token_id {eos} outside the vocabulary"
         assert check_every >= 1
         B, dev = idx.shape[0], idx.device
         if cached and idx.is_cuda:
-            return self._generate_dev(idx, max_new_tokens, prefix, temperature, top_k, use_graph, eos, check_every)
+            return self._generate_dev(idx, max_new_tokens, prefix, temperature, top_k, use_graph, eos, check_every, top_p)
         state = K.SampleState(dev) if idx.is_cuda else None
         done = torch.zeros(B, dtype=torch.bool, device=dev)
         lens = torch.zeros(B, dtype=torch.int64, device=dev)
@@ -503,7 +529,7 @@ class GPT(nn.Module):
                 break
             idx_cond = idx if idx.size(1) <= self.config.block_size else idx[:, -self.config.block_size:]
             _, lg = self(idx_cond, prefix=prefix)
-            tok = torch.where(done, torch.full_like(lens, eos), self._sample(lg[:, -1, :], temperature, top_k, state).view(-1))
+            tok = torch.where(done, torch.full_like(lens, eos), self._sample(lg[:, -1, :], temperature, top_k, state, top_p).view(-1))
             lens += (~done).long()
             done = done | (tok == eos)
             idx = torch.cat((idx, tok[:, None]), dim=1)

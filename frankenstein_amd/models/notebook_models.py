@@ -74,16 +74,18 @@ class Franky(nn.Module):
         return self.llm_model.forward(idx=new_idx, prefix=features, targets=targets)
 
     @torch.no_grad()
-    def generate(self, x, max_new_tokens=25, temperature=1.0, top_k=10, eot=50256, stop=False):
+    def generate(self, x, max_new_tokens=25, temperature=1.0, top_k=10, eot=50256, stop=False, top_p=None):
         """x: numpy [T, C].  Returns generated token ids (the notebook's version is unfinished; this one runs).
         stop=True ends a sentence at its first generated `eot` (what the notebook's cell tried with its undefined stop_tokens): the ids come
         back trimmed behind that token; x: numpy [S, T, C] then decodes S trials, returns [S, 1 + max_new_tokens] padded with `eot` and sets
-        last_lengths [S] (generated tokens, `eot` included)."""
+        last_lengths [S] (generated tokens, `eot` included).
+        top_p: nucleus sampling behind the top-k crop (GPT.generate), with and without stop; None or 1.0: off, outside (0, 1] raises."""
+        self.llm_model._check_top_p(top_p)                                  # before the encoder runs
         if stop:
             xin = torch.from_numpy(x if x.ndim == 3 else x[None]).to(self.device).float()
             prefix = self.brain_model(xin)
             ids = torch.full((xin.shape[0], 1), eot, dtype=torch.long, device=self.device)
-            self.llm_model.generate(ids, max_new_tokens, prefix=prefix, temperature=temperature, top_k=top_k, eos_token_id=eot)
+            self.llm_model.generate(ids, max_new_tokens, prefix=prefix, temperature=temperature, top_k=top_k, eos_token_id=eot, top_p=top_p)
             self.last_lengths = self.llm_model.last_lengths.cpu()           # int64 on the host, as generate_beam leaves it
             if x.ndim == 3:
                 return self.llm_model.last_tokens
@@ -91,7 +93,7 @@ class Franky(nn.Module):
         xin = torch.from_numpy(x[None]).to(self.device).float()
         prefix = self.brain_model(xin)
         ids = torch.full((1, 1), eot, dtype=torch.long, device=self.device)
-        return self.llm_model.generate(ids, max_new_tokens, prefix=prefix, temperature=temperature, top_k=top_k)
+        return self.llm_model.generate(ids, max_new_tokens, prefix=prefix, temperature=temperature, top_k=top_k, top_p=top_p)
 
     @torch.no_grad()
     def generate_beam(self, x, max_new_tokens=25, temperature=1.0, topk=20, beam_width=5, eot=50256, batch_sentences=None, stop=False,

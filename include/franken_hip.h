@@ -315,6 +315,27 @@ int fk_sample_topk_eos(const float* logits, int64_t ld, int64_t B, int64_t V, fl
                        int32_t* pos_inc, int64_t* cur, int64_t* out, int64_t out_ld, int64_t out_cols, uint32_t* ticket, int64_t eos, int32_t* done,
                        int32_t* len, uint32_t* live_acc, int32_t* live, void* stream);
 
+/* ---- nucleus (top-p) sampling in the same one launch.
+ * fk_sample_topp: fk_sample_topk_eos's arguments with `float top_p` behind top_k.  The rule, with x_i = logits_i / temperature:
+ *   1. The top-k crop comes first and is unchanged: K is the set of i with x_i >= the k-th largest value, ties kept.  K is everything when
+ *      top_k is off.
+ *   2. e_i = exp(x_i - max_K x) and total = sum over K of e_i.
+ *   3. For i in K, mass_gt(i) = sum { e_j : j in K, x_j > x_i } (strictly larger).
+ *   4. Token i stays iff mass_gt(i) < top_p * total.
+ *   5. The draw is the existing one: inverse CDF in index order over the tokens that stay, with the Philox uniform keyed by
+ *      (*seed; *step, row).
+ *   So the most likely token always stays; equal logits stay or go together, the same tie rule as the top-k crop; with no tie at the
+ *   boundary this is exactly the usual "sorted cumulative probability" rule; top_p applies to the distribution renormalised after the
+ *   top-k crop; and a token whose exact |mass_gt / total - top_p| is below 1e-4 may fall on either side, because the kernel uses its own
+ *   exponential and its own summation (it sums floor(e_i * 2^32) as 64-bit integers, so the kept set does not depend on the order of
+ *   its atomics: the same inputs give the same tokens).  The Philox counter layout is fk_sample_topk's: top_p = 1 draws the tokens
+ *   fk_sample_topk (fk_sample_topk_eos) draws with the same seed and step.
+ *   done == NULL selects the plain mode (fk_sample_topk's outputs): len, live_acc and live must then be NULL too and eos is ignored.  All
+ *   four given selects the end-of-text mode with the rules of fk_sample_topk_eos.  A mixture is refused.  0 < top_p <= 1; NaN is refused. */
+int fk_sample_topp(const float* logits, int64_t ld, int64_t B, int64_t V, float temperature, int64_t top_k, float top_p, const uint64_t* seed,
+                   int64_t* step, int32_t* pos_inc, int64_t* cur, int64_t* out, int64_t out_ld, int64_t out_cols, uint32_t* ticket, int64_t eos,
+                   int32_t* done, int32_t* len, uint32_t* live_acc, int32_t* live, void* stream);
+
 /* ---- VQ-VAE tokenizer convolutions (models/vq_brain.py), channels-last [B, T, C], causal left padding dil*(K-1):
  * fk_im2col1d: cols[b, t, k, :] = x[b, t*stride + k*dil - pad, :] (zeros outside), Tout = (T-1)/stride + 1, so that
  *   CausalConv1d (:22-28) = fk_gemm_nt(cols, W') with W'[o, k*Cin + c] = W[o, c, k], and CausalConvTranspose1d(kernel 2s,

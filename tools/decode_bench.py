@@ -5,6 +5,7 @@
     python tools/decode_bench.py --model gpt2 --beam 5 --topk 20 --new-tokens 25     # generate_beam_search: cached (+ hipGraph) vs re-forward
     python tools/decode_bench.py --model gpt2 --beam 5 --sentences 1,2,3,4,8,16 --new-tokens 25    # S sentences in one search vs S searches
     python tools/decode_bench.py --model gpt2 --beam 5 --eos --new-tokens 25         # end-of-text: step, poll, early exit, device backtrack
+    python tools/decode_bench.py --model gpt2 --batch 1 --top-p 0.9                  # nucleus sampling: the step with and without top_p
 
 Random weights, a 32-token brain prefix, one start token, top_k = 1.  A generate() call also pays the prefill and, in graph mode, the
 capture, so the per-token figure is the MARGINAL cost: (time of N new tokens - time of N/4 new tokens) / (3N/4), medians over the
@@ -228,6 +229,39 @@ def eos_bench(g, a, prefix, start):
         print(f"backtrack of {S} sentences x {W} beams x {n} steps, {name:18s}: {statistics.median(ts) * 1e6:8.1f} us [{min(ts) * 1e6:.1f} .. {max(ts) * 1e6:.1f}]")
 
 
+def top_p_bench(g, a, prefix, start):
+    """--top-p P: what the nucleus crop costs a decode step.  generate() as a hipGraph in one process, the repeats of the modes interleaved:
+    greedy (top_k = 1, the figure of every other table), sampling without a crop and behind top_k = 10 (Franky.generate's default), each
+    with and without top_p = P.  A random-weight decoder's distribution is nearly flat, so without a top-k crop top_p keeps most of the
+    vocabulary and every logit adds its mass to the histograms: the expensive end of the mass select.  us/token is marginal like the
+    default mode's, the whole call is listed with its range.  With --top-k K (0: no crop) only that crop runs, with and without top_p: under
+    rocprofv3 each instantiation of the sampling kernel then has one mode's launches."""
+    n, n4, B = a.new_tokens, max(1, a.new_tokens // 4), start.shape[0]
+    kw = dict(prefix=prefix, use_cache=True, use_graph=True)
+    modes = {} if a.top_k is not None else {"top_k = 1 (greedy)": dict(top_k=1)}
+    for k in ((0, 10) if a.top_k is None else (a.top_k,)):
+        name = f"top_k = {k}" if k else "no crop"
+        modes[name] = dict(top_k=k or None)
+        modes[f"{name}, top_p = {a.top_p}"] = dict(top_k=k or None, top_p=a.top_p)
+    times = {name: {n4: [], n: []} for name in modes}
+    for extra in modes.values():                            # warm up both lengths of every mode
+        for k in (n4, n):
+            g.generate(start, k, **kw, **extra)
+    for _ in range(a.repeats):
+        for k in (n4, n):
+            for name, extra in modes.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                g.generate(start, k, **kw, **extra)
+                torch.cuda.synchronize()
+                times[name][k].append(time.perf_counter() - t0)
+    for name in modes:
+        t4, t = statistics.median(times[name][n4]), statistics.median(times[name][n])
+        step = (t - t4) / (n - n4) if n > n4 else t / n
+        print(f"{name:28s}: {step * 1e6:9.1f} us/token (marginal)  {B / step:9.0f} tokens/s   | whole call {t * 1e3:8.2f} ms [{min(times[name][n]) * 1e3:.2f} .. "
+              f"{max(times[name][n]) * 1e3:.2f}]", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", choices=sorted(MODELS), default="nano")
@@ -241,6 +275,8 @@ def main():
     ap.add_argument("--sentences", type=lambda v: [int(x) for x in v.split(",")], default=None,
                     help="with --beam: sentences per batched search, one or a comma-separated list; each beside as many one-sentence searches")
     ap.add_argument("--eos", action="store_true", help="with --beam: the end-of-text path (step against the plain step, cost of the poll, early exit, backtrack)")
+    ap.add_argument("--top-p", type=float, default=None, help="nucleus sampling: time generate with and without top_p = P (greedy, no crop, top_k = 10), interleaved")
+    ap.add_argument("--top-k", type=int, default=None, help="with --top-p: only this top-k crop (0: none), with and without top_p")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "decode_bench needs the GPU"
 
@@ -266,6 +302,9 @@ def main():
             return eos_bench(g, a, prefix, start)
         print(f"beam width {a.beam}, topk {a.topk}")
         return beam_bench(g, a, prefix, start)
+    if a.top_p is not None:
+        print(f"nucleus sampling, top_p = {a.top_p}")
+        return top_p_bench(g, a, prefix, start)
     for name, kw in MODES.items():
         if not a.all_modes and name != "kv-cache + hipGraph":
             continue
