@@ -60,6 +60,27 @@ template <typename T, int D> struct AT {
   static constexpr int VEC = 16 / ES;
 };
 
+// head hd of sample b in a [B, N, H, D] view with batch stride bs (elements)
+template <typename T, int D> FK_DEV const T* head_ptr(const void* base, int64_t bs, int b, int hd) { return (const T*)base + (int64_t)b * bs + hd * D; }
+template <typename T, int D> FK_DEV T* head_ptr(void* base, int64_t bs, int b, int hd) { return (T*)base + (int64_t)b * bs + hd * D; }
+// 1-D grid, XCD-aware: each XCD walks whole (batch, head) pairs (their K/V stay in its L2); blk = this workgroup's block within its head.
+// Query-block kernels take the heaviest (latest) query block first, key-block kernels key block 0 (seen by every query) first.
+FK_DEV void head_block(int H, int nblk, int& b, int& hd, int& blk) {
+  const unsigned L = xcd_remap(blockIdx.x, gridDim.x);
+  const int bh = (int)(L / nblk);
+  b = bh / H;
+  hd = bh % H;
+  blk = (int)(L % nblk);
+}
+FK_DEV void query_block(int H, int nqb, int bq, int& b, int& hd, int& q0) {
+  head_block(H, nqb, b, hd, q0);
+  q0 = (nqb - 1 - q0) * bq;
+}
+FK_DEV void key_block(int H, int nkb, int bk, int& b, int& hd, int& k0) {
+  head_block(H, nkb, b, hd, k0);
+  k0 *= bk;
+}
+
 FK_DEV bool visible(int kind, int c, int qpos, int kpos) {
   if (kind == FK_MASK_CAUSAL) return kpos <= qpos;
   if (kind == FK_MASK_BLOCK_CAUSAL) return (kpos / c) <= (qpos / c);
@@ -294,9 +315,6 @@ FK_DEV unsigned pack_bf16x2(float lo, float hi) {
   return __builtin_bit_cast(unsigned, v);
 }
 
-#ifndef FK_KEYPAD_NO_FREE
-#define FK_KEYPAD_NO_FREE 0      // 1: a key-padding mask sends every tile down the per-element path (the form before round 4; A/B switch)
-#endif
 #ifndef FK_NT_STORES_ATTN
 #define FK_NT_STORES_ATTN 0      // 1: O / dQ / dK / dV rows stored non-temporal (written once; the launch keeps re-reading K / V or Q / dO out of L2)
 #endif
@@ -413,14 +431,12 @@ __global__ __launch_bounds__(NW * 64) void attn_fwd_kernel(AttnArgs p) {
   auto vimg = [&](int i) -> char* { return smem + NSLOT * KIMG + i * VIMG; };
   const int tid = threadIdx.x, lane = tid & 63, li = lane & 31, lh = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform (SGPR): tile predicates become scalar branches
-  // 1-D grid, XCD-aware: each XCD walks whole (batch, head) pairs (their K/V stay in its L2), heaviest
-  // (latest) query block first.
   const int nqb = (p.Nq + BQ - 1) / BQ;
-  const unsigned L = xcd_remap(blockIdx.x, gridDim.x);
-  const int bh = (int)(L / nqb), b = bh / p.H, hd = bh % p.H, q0 = (nqb - 1 - (int)(L % nqb)) * BQ;
-  const T* Qp = (const T*)p.Q + (int64_t)b * p.q_bs + hd * D;
-  const T* Kp = (const T*)p.K + (int64_t)b * p.k_bs + hd * D;
-  const T* Vp = (const T*)p.V + (int64_t)b * p.v_bs + hd * D;
+  int b, hd, q0;
+  query_block(p.H, nqb, BQ, b, hd, q0);
+  const T* Qp = head_ptr<T, D>(p.Q, p.q_bs, b, hd);
+  const T* Kp = head_ptr<T, D>(p.K, p.k_bs, b, hd);
+  const T* Vp = head_ptr<T, D>(p.V, p.v_bs, b, hd);
   const int qrow = q0 + wave * 32 + li;
   const bool q_ok = qrow < p.Nq;
   const bool prefix = p.mask_kind == FK_MASK_PREFIX, keypad = p.mask_kind == FK_MASK_KEYPAD;
@@ -593,7 +609,7 @@ __global__ __launch_bounds__(NW * 64) void attn_fwd_kernel(AttnArgs p) {
 
   const float lt = l + __shfl_xor(l, 32, 64);
   const float inv = lt > 0.0f ? (p.drop_thresh ? p.drop_scale : 1.0f) / lt : 0.0f;   // fully masked row -> 0 (torch >= 2.1 CPU semantics)
-  T* Op = (T*)p.Out + (int64_t)b * p.o_bs + hd * D;
+  T* Op = head_ptr<T, D>(p.Out, p.o_bs, b, hd);
   store_rows_T<T, D>(Op, p.o_rs, qrow, q_ok, o, inv, lh);
   if (q_ok && lh == 0 && p.LSE)
     p.LSE[((int64_t)b * p.H + hd) * p.Nq + qrow] = lt > 0.0f ? m * p.scale + logf(lt) : INFINITY;
@@ -616,9 +632,9 @@ __global__ __launch_bounds__(FEWQ_NW * 64) void attn_fwd_fewq_kernel(AttnArgs p)
   const int tid = threadIdx.x, lane = tid & 63, li = lane & 31, lh = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int bh = blockIdx.x, b = bh / p.H, hd = bh % p.H;
-  const T* Qp = (const T*)p.Q + (int64_t)b * p.q_bs + hd * D;
-  const T* Kp = (const T*)p.K + (int64_t)b * p.k_bs + hd * D;
-  const T* Vp = (const T*)p.V + (int64_t)b * p.v_bs + hd * D;
+  const T* Qp = head_ptr<T, D>(p.Q, p.q_bs, b, hd);
+  const T* Kp = head_ptr<T, D>(p.K, p.k_bs, b, hd);
+  const T* Vp = head_ptr<T, D>(p.V, p.v_bs, b, hd);
   const int qrow = li;
   const bool q_ok = qrow < p.Nq;
   Frag<T> qf[4];
@@ -734,7 +750,7 @@ __global__ __launch_bounds__(FEWQ_NW * 64) void attn_fwd_fewq_kernel(AttnArgs p)
   }
   const float lt = L + __shfl_xor(L, 32, 64);
   const float inv = lt > 0.0f ? 1.0f / lt : 0.0f;
-  T* Op = (T*)p.Out + (int64_t)b * p.o_bs + hd * D;
+  T* Op = head_ptr<T, D>(p.Out, p.o_bs, b, hd);
   store_rows_T<T, D>(Op, p.o_rs, qrow, q_ok, o, inv, lh);
   if (q_ok && lh == 0 && p.LSE) p.LSE[((int64_t)b * p.H + hd) * p.Nq + qrow] = lt > 0.0f ? M * p.scale + logf(lt) : INFINITY;
 }
@@ -748,11 +764,11 @@ __global__ __launch_bounds__(FEWQ_NW * 64) void attn_bwd_dq_fewq_kernel(AttnArgs
   const int tid = threadIdx.x, lane = tid & 63, li = lane & 31, lh = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int bh = blockIdx.x, b = bh / p.H, hd = bh % p.H;
-  const T* Qp = (const T*)p.Q + (int64_t)b * p.q_bs + hd * D;
-  const T* Kp = (const T*)p.K + (int64_t)b * p.k_bs + hd * D;
-  const T* Vp = (const T*)p.V + (int64_t)b * p.v_bs + hd * D;
-  const T* Gp = (const T*)p.dO + (int64_t)b * p.o_bs + hd * D;
-  const T* Op = (const T*)p.O + (int64_t)b * p.o_bs + hd * D;
+  const T* Qp = head_ptr<T, D>(p.Q, p.q_bs, b, hd);
+  const T* Kp = head_ptr<T, D>(p.K, p.k_bs, b, hd);
+  const T* Vp = head_ptr<T, D>(p.V, p.v_bs, b, hd);
+  const T* Gp = head_ptr<T, D>(p.dO, p.o_bs, b, hd);
+  const T* Op = head_ptr<T, D>(p.O, p.o_bs, b, hd);
   const int qrow = li;
   const bool q_ok = qrow < p.Nq;
   Frag<T> qf[4], gf[4];
@@ -848,7 +864,7 @@ __global__ __launch_bounds__(FEWQ_NW * 64) void attn_bwd_dq_fewq_kernel(AttnArgs
 #pragma unroll
       for (int r = 0; r < 16; ++r) dq[dt][r] += theirs[(dt * 16 + r) * 64 + lane];
   }
-  T* dQp = (T*)p.dQ + (int64_t)b * p.q_bs + hd * D;
+  T* dQp = head_ptr<T, D>(p.dQ, p.q_bs, b, hd);
   store_rows_T<T, D>(dQp, p.q_rs, qrow, q_ok, dq, p.scale, lh);
 }
 
@@ -869,12 +885,12 @@ __global__ __launch_bounds__(NT) void attn_bwd_dq_kernel(AttnArgs p) {
   const int tid = threadIdx.x, lane = tid & 63, li = lane & 31, lh = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform (SGPR): tile predicates become scalar branches
   const int nqb = (p.Nq + BQ - 1) / BQ;
-  const unsigned L = xcd_remap(blockIdx.x, gridDim.x);
-  const int bh = (int)(L / nqb), b = bh / p.H, hd = bh % p.H, q0 = (nqb - 1 - (int)(L % nqb)) * BQ;
-  const T* Qp = (const T*)p.Q + (int64_t)b * p.q_bs + hd * D;
-  const T* Kp = (const T*)p.K + (int64_t)b * p.k_bs + hd * D;
-  const T* Vp = (const T*)p.V + (int64_t)b * p.v_bs + hd * D;
-  const T* Gp = (const T*)p.dO + (int64_t)b * p.o_bs + hd * D;
+  int b, hd, q0;
+  query_block(p.H, nqb, BQ, b, hd, q0);
+  const T* Qp = head_ptr<T, D>(p.Q, p.q_bs, b, hd);
+  const T* Kp = head_ptr<T, D>(p.K, p.k_bs, b, hd);
+  const T* Vp = head_ptr<T, D>(p.V, p.v_bs, b, hd);
+  const T* Gp = head_ptr<T, D>(p.dO, p.o_bs, b, hd);
   const int qrow = q0 + wave * 32 + li;
   const bool q_ok = qrow < p.Nq;
   const bool prefix = p.mask_kind == FK_MASK_PREFIX, keypad = p.mask_kind == FK_MASK_KEYPAD;
@@ -903,7 +919,7 @@ __global__ __launch_bounds__(NT) void attn_bwd_dq_kernel(AttnArgs p) {
   // publishes it for the dK/dV kernel, which is launched after this one; no separate delta launch
   float dl = 0.0f;
   {
-    const T* Op = (const T*)p.O + (int64_t)b * p.o_bs + hd * D;
+    const T* Op = head_ptr<T, D>(p.O, p.o_bs, b, hd);
     float part = 0.0f;
 #pragma unroll
     for (int s = 0; s < C::KSTEPS; ++s) {
@@ -1033,7 +1049,7 @@ __global__ __launch_bounds__(NT) void attn_bwd_dq_kernel(AttnArgs p) {
     tile_step(std::integral_constant<int, 0>{}, t);
     if (t + 1 < ntiles) tile_step(std::integral_constant<int, 1>{}, t + 1);
   }
-  T* dQp = (T*)p.dQ + (int64_t)b * p.q_bs + hd * D;
+  T* dQp = head_ptr<T, D>(p.dQ, p.q_bs, b, hd);
   if (p.rope_table)           // wave-uniform: the stores swap registers between the half-waves, every lane takes part
     store_rows_T_rope<T, D>(dQp, p.q_rs, qrow, q_ok, dq, p.scale, lh, p.rope_table + (int64_t)b * p.rope_bs + (int64_t)(p.rope_off + qrow) * D);
   else
@@ -1053,13 +1069,13 @@ __global__ __launch_bounds__(NT, (sizeof(T) == 2 && D <= 64) ? 2 : 1) void attn_
   float* stats = reinterpret_cast<float*>(smem + 4 * IMG);   // [2 buffers][2 (lse2, delta)][TQ]
   const int tid = threadIdx.x, lane = tid & 63, li = lane & 31, lh = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform (SGPR): tile predicates become scalar branches
-  const int nkb = (p.Nk + 127) / 128;   // XCD-aware 1-D grid; key block 0 (seen by every query) first
-  const unsigned L = xcd_remap(blockIdx.x, gridDim.x);
-  const int bh = (int)(L / nkb), b = bh / p.H, hd = bh % p.H, k0 = (int)(L % nkb) * 128;
-  const T* Qp = (const T*)p.Q + (int64_t)b * p.q_bs + hd * D;
-  const T* Kp = (const T*)p.K + (int64_t)b * p.k_bs + hd * D;
-  const T* Vp = (const T*)p.V + (int64_t)b * p.v_bs + hd * D;
-  const T* Gp = (const T*)p.dO + (int64_t)b * p.o_bs + hd * D;
+  const int nkb = (p.Nk + 127) / 128;
+  int b, hd, k0;
+  key_block(p.H, nkb, 128, b, hd, k0);
+  const T* Qp = head_ptr<T, D>(p.Q, p.q_bs, b, hd);
+  const T* Kp = head_ptr<T, D>(p.K, p.k_bs, b, hd);
+  const T* Vp = head_ptr<T, D>(p.V, p.v_bs, b, hd);
+  const T* Gp = head_ptr<T, D>(p.dO, p.o_bs, b, hd);
   const int krow = k0 + wave * 32 + li;
   const bool k_ok = krow < p.Nk;
   const bool prefix = p.mask_kind == FK_MASK_PREFIX, keypad = p.mask_kind == FK_MASK_KEYPAD;
@@ -1248,8 +1264,8 @@ __global__ __launch_bounds__(NT, (sizeof(T) == 2 && D <= 64) ? 2 : 1) void attn_
     tile_step(std::integral_constant<int, 0>{}, t);
     if (t + 1 < ntiles) tile_step(std::integral_constant<int, 1>{}, t + 1);
   }
-  T* dKp = (T*)p.dK + (int64_t)b * p.k_bs + hd * D;
-  T* dVp = (T*)p.dV + (int64_t)b * p.v_bs + hd * D;
+  T* dKp = head_ptr<T, D>(p.dK, p.k_bs, b, hd);
+  T* dVp = head_ptr<T, D>(p.dV, p.v_bs, b, hd);
   if (p.rope_table)           // wave-uniform: the stores swap registers between the half-waves, every lane takes part
     store_rows_T_rope<T, D>(dKp, p.k_rs, krow, k_ok, dk, p.scale, lh, p.rope_table + (int64_t)b * p.rope_bs + (int64_t)(p.rope_off + krow) * D);
   else
@@ -1295,6 +1311,92 @@ FK_DEV f32x16 mfma_bf16(const bf16x8& a, const bf16x8& b, const f32x16& c) {
 // every wave's LDS-DMA of the next tile has landed and every wave is done with the current one
 FK_DEV void dma_wait_barrier() { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
+// ---- shared by the kernels around the generated instruction streams (and, for the statistics and the stores, by the _ps kernels) ----
+// Tile requests of a stream (LDS-DMA): per wave two 8-row groups of a first image (row stride rs_a) and two of a second (rs_b), in the
+// Img<bf16, 64> layout: the chunk swizzle is applied to the source.  Address = wave-uniform 64-bit tile base (SGPR pair) + these
+// per-lane byte offsets, which never change.  (vo[4], where there is one, is the dK/dV kernels' statistics row: theirs to set.)
+template <int N> FK_DEV void lean_dma_offsets(unsigned (&vo)[N], int wave, int lane, int64_t rs_a, int64_t rs_b) {
+  static_assert(N >= 4, "two groups of each image");
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int row = (wave * 2 + j) * 8 + (lane >> 3);
+    const int g = (row >> 1) & 7, f = g ^ ((g & 1) << 2);
+    vo[j] = (__umul24((unsigned)row, (unsigned)rs_a) + (unsigned)(((lane & 7) ^ f) * 8)) * 2u;
+    vo[2 + j] = (__umul24((unsigned)row, (unsigned)rs_b) + (unsigned)(((lane & 7) ^ f) * 8)) * 2u;
+  }
+}
+// LDS addresses of a lane's fragments in ring slot 0 (the streams add the slot): aq[s] the row read of k-step s (image row lane % 32),
+// va0 / va1 the two transposed reads (ds_read_b64_tr_b16) of the first 32 x 32 block
+FK_DEV void lean_frag_addrs(unsigned (&aq)[4], unsigned& va0, unsigned& va1, unsigned lds0, int lane) {
+  const int li = lane & 31, lh = lane >> 5;
+#pragma unroll
+  for (int s_ = 0; s_ < 4; ++s_) aq[s_] = lds0 + (unsigned)Img<bf16_t, 64>::off(li, (16 * s_ + 8 * lh) * 2);
+  const int g4 = lane >> 4, i16 = lane & 15, hh = g4 >> 1;
+  const int rpart = (4 * hh + (i16 >> 2)) * 128 + (i16 & 1) * 8;
+  const int c0 = 2 * (g4 & 1) + ((i16 & 3) >> 1), gg0 = 2 * hh + (i16 >> 3), f0 = gg0 ^ ((gg0 & 1) << 2);
+  va0 = lds0 + (unsigned)(rpart + ((c0 ^ f0) << 4));
+  va1 = lds0 + (unsigned)(rpart + (((c0 ^ f0) ^ 4) << 4));
+}
+// One stream of ROWS-row tiles (K, V, Q, dO, or a statistics row with rs = 1) as the generated streams want it: the 64-bit address of
+// tile tt.  A stream requests two tiles ahead without looking at the tile count; past the end: the last tile again (never read).
+template <typename E, int ROWS> struct TileSrc {
+  const E* ptr; int64_t rs; int first, ntiles;           // row `first` is tile 0
+  FK_DEV uint64_t base(int tt) const { return (uint64_t)(uintptr_t)(ptr + (int64_t)(first + (tt < ntiles ? tt : ntiles - 1) * ROWS) * rs); }
+};
+// after a stream's last step: stray requests (past the last tile) have landed before the workgroup ends, and the stream's last MFMAs have
+// retired before the compiler reads the accumulators
+FK_DEV void stream_drain() { asm volatile("s_waitcnt vmcnt(0)\n\ts_nop 15\n\ts_nop 15" ::: "memory"); }
+
+FK_DEV const bf16x8& frag_v(const bf16x8& f) { return f; }
+FK_DEV const bf16x8& frag_v(const Frag<bf16_t>& f) { return f.v; }
+// Row statistics of the dQ kernels (this kernel already holds the dO row fragments gf): lse2 = LSE * log2(e) (+inf -> P = 0 for padded /
+// fully masked rows) and dl = delta = rowsum(dO * O), published for the dK/dV kernel, which is launched after this one, in the form it
+// consumes, as two rows of length nqp (Nq rounded up to its 64-row tile):
+//   ws[0][b, h, q] = -LSE * log2(e)   (-inf for rows past Nq and fully masked rows: P = 0),   ws[1][b, h, q] = -delta  (0 past Nq)
+// A kernel whose rows all exist passes q_ok = true and nqp = Nq.
+template <typename F>
+FK_DEV void dq_row_stats(const AttnArgs& p, int b, int hd, int qrow, bool q_ok, int nqp, int lh, const F (&gf)[4], float& lse2, float& dl) {
+  using T = bf16_t;
+  constexpr int D = 64;
+  const int64_t stat = ((int64_t)b * p.H + hd) * p.Nq + qrow;
+  lse2 = q_ok ? p.LSE[stat] * LOG2E : INFINITY;
+  const T* Op = head_ptr<T, D>(p.O, p.o_bs, b, hd);
+  float part = 0.0f;
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+    if (q_ok) {
+      const bf16x8 of = *reinterpret_cast<const bf16x8*>(Op + (int64_t)qrow * p.o_rs + 16 * s + 8 * lh);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) part += to_f32<T>(of[e]) * to_f32<T>(frag_v(gf[s])[e]);
+    }
+  }
+  dl = part + __shfl_xor(part, 32, 64);
+  if (lh == 0 && (q_ok || qrow < nqp)) {                   // (q_ok implies qrow < nqp)
+    const int64_t pst = ((int64_t)b * p.H + hd) * nqp + qrow;
+    p.delta[pst] = -lse2;
+    p.delta[(int64_t)p.B * p.H * nqp + pst] = q_ok ? -dl : 0.0f;
+  }
+}
+
+// O / dQ / dK rows with or without the inverse RoPE (p.rope_table is wave-uniform: the stores swap registers between the half-waves,
+// every lane takes part)
+template <typename T, int D>
+FK_DEV void store_rows_T_maybe_rope(const AttnArgs& p, int b, T* base, int64_t rs, int row, bool row_ok, const f32x16 (&acc)[AT<T, D>::DT], float mul, int lh) {
+  if (p.rope_table)
+    store_rows_T_rope<T, D>(base, rs, row, row_ok, acc, mul, lh, p.rope_table + (int64_t)b * p.rope_bs + (int64_t)(p.rope_off + row) * D);
+  else
+    store_rows_T<T, D>(base, rs, row, row_ok, acc, mul, lh);
+}
+// dQ of the pre-scaled-Q kernels: the softmax scale was left out of dS
+FK_DEV void store_dq(const AttnArgs& p, int b, int hd, int qrow, bool q_ok, const f32x16 (&dq)[2], int lh) {
+  store_rows_T_maybe_rope<bf16_t, 64>(p, b, head_ptr<bf16_t, 64>(p.dQ, p.q_bs, b, hd), p.q_rs, qrow, q_ok, dq, p.scale, lh);
+}
+// dK, dV of the pre-scaled-Q kernels: dK = scale * dS^T Q = ln(2) * dS^T Q'   (Q' = scale * log2(e) * Q)
+FK_DEV void store_dk_dv(const AttnArgs& p, int b, int hd, int krow, bool k_ok, const f32x16 (&dk)[2], const f32x16 (&dv)[2], int lh) {
+  store_rows_T_maybe_rope<bf16_t, 64>(p, b, head_ptr<bf16_t, 64>(p.dK, p.k_bs, b, hd), p.k_rs, krow, k_ok, dk, LN2, lh);
+  store_rows_T<bf16_t, 64>(head_ptr<bf16_t, 64>(p.dV, p.v_bs, b, hd), p.v_rs, krow, k_ok, dv, 1.0f, lh);
+}
+
 template <int NW>
 __global__ __launch_bounds__(NW * 64, 4) void attn_fwd_ps_kernel(AttnArgs p) {
   FK_LIFE_BEGIN
@@ -1307,18 +1409,18 @@ __global__ __launch_bounds__(NW * 64, 4) void attn_fwd_ps_kernel(AttnArgs p) {
   const int tid = threadIdx.x, lane = tid & 63, li = lane & 31, lh = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int nqb = (p.Nq + BQ - 1) / BQ;
-  const unsigned L = xcd_remap(blockIdx.x, gridDim.x);
-  const int bh = (int)(L / nqb), b = bh / p.H, hd = bh % p.H, q0 = (nqb - 1 - (int)(L % nqb)) * BQ;
-  const T* Qp = (const T*)p.Q + (int64_t)b * p.q_bs + hd * D;
-  const T* Kp = (const T*)p.K + (int64_t)b * p.k_bs + hd * D;
-  const T* Vp = (const T*)p.V + (int64_t)b * p.v_bs + hd * D;
+  int b, hd, q0;
+  query_block(p.H, nqb, BQ, b, hd, q0);
+  const T* Qp = head_ptr<T, D>(p.Q, p.q_bs, b, hd);
+  const T* Kp = head_ptr<T, D>(p.K, p.k_bs, b, hd);
+  const T* Vp = head_ptr<T, D>(p.V, p.v_bs, b, hd);
   const int qrow = q0 + wave * 32 + li;
   const bool q_ok = qrow < p.Nq;
   const bool prefix = p.mask_kind == FK_MASK_PREFIX, keypad = p.mask_kind == FK_MASK_KEYPAD;
   const int my_lim = ((prefix || keypad) && q_ok) ? p.limits[(int64_t)b * p.Nq + qrow] : 0;
   // key padding: keys in front of the sample's first padded key need no predicate for a wave whose own 32 queries are all valid
   int keypad_free = 0;
-  if (keypad && !FK_KEYPAD_NO_FREE) {
+  if (keypad) {
     keypad_free = keypad_valid_prefix(p.qfirst + (int64_t)b * p.Nk, p.Nk, lane);
     if (__builtin_amdgcn_ballot_w64(q_ok && my_lim == 0) != 0) keypad_free = 0;
   }
@@ -1492,7 +1594,7 @@ __global__ __launch_bounds__(NW * 64, 4) void attn_fwd_ps_kernel(AttnArgs p) {
 
   const float lt = l + __shfl_xor(l, 32, 64);
   const float inv = lt > 0.0f ? 1.0f / lt : 0.0f;   // fully masked row -> 0 (torch >= 2.1 CPU semantics)
-  T* Op = (T*)p.Out + (int64_t)b * p.o_bs + hd * D;
+  T* Op = head_ptr<T, D>(p.Out, p.o_bs, b, hd);
   store_rows_T<T, D>(Op, p.o_rs, qrow, q_ok, o, inv, lh);
   if (q_ok && lh == 0 && p.LSE)
     p.LSE[((int64_t)b * p.H + hd) * p.Nq + qrow] = lt > 0.0f ? m * LN2 + logf(lt) : INFINITY;
@@ -1515,12 +1617,12 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_bwd_dq_ps_kernel(AttnArgs p) 
   const int tid = threadIdx.x, lane = tid & 63, li = lane & 31, lh = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int nqb = (p.Nq + BQ - 1) / BQ;
-  const unsigned L = xcd_remap(blockIdx.x, gridDim.x);
-  const int bh = (int)(L / nqb), b = bh / p.H, hd = bh % p.H, q0 = (nqb - 1 - (int)(L % nqb)) * BQ;
-  const T* Qp = (const T*)p.Q + (int64_t)b * p.q_bs + hd * D;
-  const T* Kp = (const T*)p.K + (int64_t)b * p.k_bs + hd * D;
-  const T* Vp = (const T*)p.V + (int64_t)b * p.v_bs + hd * D;
-  const T* Gp = (const T*)p.dO + (int64_t)b * p.o_bs + hd * D;
+  int b, hd, q0;
+  query_block(p.H, nqb, BQ, b, hd, q0);
+  const T* Qp = head_ptr<T, D>(p.Q, p.q_bs, b, hd);
+  const T* Kp = head_ptr<T, D>(p.K, p.k_bs, b, hd);
+  const T* Vp = head_ptr<T, D>(p.V, p.v_bs, b, hd);
+  const T* Gp = head_ptr<T, D>(p.dO, p.o_bs, b, hd);
   const int qrow = q0 + wave * 32 + li;
   const bool q_ok = qrow < p.Nq;
   const bool prefix = p.mask_kind == FK_MASK_PREFIX, keypad = p.mask_kind == FK_MASK_KEYPAD;
@@ -1537,31 +1639,8 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_bwd_dq_ps_kernel(AttnArgs p) 
       frag_zero<T>(gf[s]);
     }
   }
-  const int64_t stat = ((int64_t)b * p.H + hd) * p.Nq + qrow;
-  const float lse2 = q_ok ? p.LSE[stat] * LOG2E : INFINITY;   // +inf -> P = 0 for padded / fully masked rows
-  float dl = 0.0f;                                             // delta = rowsum(dO * O), published for the dK/dV kernel
-  {
-    const T* Op = (const T*)p.O + (int64_t)b * p.o_bs + hd * D;
-    float part = 0.0f;
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      if (q_ok) {
-        Frag<T> of;
-        frag_load_contig<T>(of, Op + (int64_t)qrow * p.o_rs + 16 * s + 8 * lh);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) part += to_f32<T>(of.v[e]) * to_f32<T>(gf[s].v[e]);
-      }
-    }
-    dl = part + __shfl_xor(part, 32, 64);
-    // published for the dK/dV kernel in the form it consumes, as two rows of length Nq rounded up to its 64-row tile:
-    //   ws[0][b, h, q] = -LSE * log2(e)   (-inf for rows past Nq and fully masked rows: P = 0),   ws[1][b, h, q] = -delta  (0 past Nq)
-    const int nqp = (p.Nq + 63) / 64 * 64;
-    if (lh == 0 && qrow < nqp) {
-      const int64_t pst = ((int64_t)b * p.H + hd) * nqp + qrow;
-      p.delta[pst] = -lse2;
-      p.delta[(int64_t)p.B * p.H * nqp + pst] = q_ok ? -dl : 0.0f;
-    }
-  }
+  float lse2, dl;
+  dq_row_stats(p, b, hd, qrow, q_ok, (p.Nq + 63) / 64 * 64, lh, gf, lse2, dl);
   f32x16 cl, cd;       // the row constants as initial accumulators: S' = Q'K^T - lse2, dP' = dO V^T - delta
 #pragma unroll
   for (int r = 0; r < 16; ++r) { cl[r] = -lse2; cd[r] = -dl; }
@@ -1572,7 +1651,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_bwd_dq_ps_kernel(AttnArgs p) 
   const int wave_q_first = min(q0 + wave * 32, p.Nq - 1);
   // key padding: tiles in front of the sample's first padded key take the mask-free path; a padded QUERY needs no predicate here, its
   // statistic is +inf (the forward wrote LSE = +inf for a row that sees nothing), so P = exp2(S' - inf) = 0 either way
-  const int full_vis_end = keypad ? (FK_KEYPAD_NO_FREE ? 0 : keypad_valid_prefix(p.qfirst + (int64_t)b * p.Nk, p.Nk, lane)) : kv_limit(p, b, wave_q_first);
+  const int full_vis_end = keypad ? keypad_valid_prefix(p.qfirst + (int64_t)b * p.Nk, p.Nk, lane) : kv_limit(p, b, wave_q_first);
 
   DmaCursor<BKV, NW> kcur, vcur;
   static_assert(PCS == 4 || PCS == 2, "vmcnt immediates below");
@@ -1654,11 +1733,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_bwd_dq_ps_kernel(AttnArgs p) 
     if (t + 1 < ntiles) tile_step(std::integral_constant<int, 1>{}, t + 1);
     if (t + 2 < ntiles) tile_step(std::integral_constant<int, 2>{}, t + 2);
   }
-  T* dQp = (T*)p.dQ + (int64_t)b * p.q_bs + hd * D;
-  if (p.rope_table)           // wave-uniform: the stores swap registers between the half-waves, every lane takes part
-    store_rows_T_rope<T, D>(dQp, p.q_rs, qrow, q_ok, dq, p.scale, lh, p.rope_table + (int64_t)b * p.rope_bs + (int64_t)(p.rope_off + qrow) * D);
-  else
-    store_rows_T<T, D>(dQp, p.q_rs, qrow, q_ok, dq, p.scale, lh);
+  store_dq(p, b, hd, qrow, q_ok, dq, lh);
 }
 
 #ifndef FK_NO_FWD_ASM
@@ -1681,33 +1756,25 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_asm_kernel(AttnArgs p) {
   const int tid = threadIdx.x, lane = tid & 63, li = lane & 31, lh = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int nqb = p.Nq / BQ;
-  const unsigned L = xcd_remap(blockIdx.x, gridDim.x);
-  const int bh = (int)(L / nqb), b = bh / p.H, hd = bh % p.H, q0 = (nqb - 1 - (int)(L % nqb)) * BQ;
-  const T* Qp = (const T*)p.Q + (int64_t)b * p.q_bs + hd * D;
-  const T* Kp = (const T*)p.K + (int64_t)b * p.k_bs + hd * D;
-  const T* Vp = (const T*)p.V + (int64_t)b * p.v_bs + hd * D;
+  int b, hd, q0;
+  query_block(p.H, nqb, BQ, b, hd, q0);
+  const T* Qp = head_ptr<T, D>(p.Q, p.q_bs, b, hd);
+  const T* Kp = head_ptr<T, D>(p.K, p.k_bs, b, hd);
+  const T* Vp = head_ptr<T, D>(p.V, p.v_bs, b, hd);
   const int qrow = q0 + wave * 32 + li;
   const int ntiles = kv_limit(p, b, q0 + BQ - 1) / BKV;       // >= 1; every one of them fully visible to every row of the workgroup
 
   unsigned vo[4];
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int row = (wave * 2 + j) * 8 + (lane >> 3);
-    const int g = (row >> 1) & 7, f = g ^ ((g & 1) << 2);
-    vo[j] = (__umul24((unsigned)row, (unsigned)p.k_rs) + (unsigned)(((lane & 7) ^ f) * 8)) * 2u;
-    vo[2 + j] = (__umul24((unsigned)row, (unsigned)p.v_rs) + (unsigned)(((lane & 7) ^ f) * 8)) * 2u;
-  }
+  lean_dma_offsets(vo, wave, lane, p.k_rs, p.v_rs);
   const unsigned lds0 = (unsigned)(uintptr_t)(lds_void_t*)smem;
   const unsigned ldsw = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)wave * 2048u);
-  auto tile_row = [&](int tt) { return (tt < ntiles ? tt : ntiles - 1) * BKV; };             // past the end: the last tile again (never read)
-  auto k_base = [&](int tt) { return (uint64_t)(uintptr_t)(Kp + (int64_t)tile_row(tt) * p.k_rs); };
-  auto v_base = [&](int tt) { return (uint64_t)(uintptr_t)(Vp + (int64_t)tile_row(tt) * p.v_rs); };
+  const TileSrc<T, BKV> ksrc{Kp, p.k_rs, 0, ntiles}, vsrc{Vp, p.v_rs, 0, ntiles};
   auto request = [&](int tt) __attribute__((always_inline)) {                                // tile tt -> slot tt % 4
     switch (tt & 3) {
-      case 0: fwd_request_asm_slot0(vo, k_base(tt), v_base(tt), ldsw); break;
-      case 1: fwd_request_asm_slot1(vo, k_base(tt), v_base(tt), ldsw); break;
-      case 2: fwd_request_asm_slot2(vo, k_base(tt), v_base(tt), ldsw); break;
-      default: fwd_request_asm_slot3(vo, k_base(tt), v_base(tt), ldsw); break;
+      case 0: fwd_request_asm_slot0(vo, ksrc.base(tt), vsrc.base(tt), ldsw); break;
+      case 1: fwd_request_asm_slot1(vo, ksrc.base(tt), vsrc.base(tt), ldsw); break;
+      case 2: fwd_request_asm_slot2(vo, ksrc.base(tt), vsrc.base(tt), ldsw); break;
+      default: fwd_request_asm_slot3(vo, ksrc.base(tt), vsrc.base(tt), ldsw); break;
     }
   };
   request(0);
@@ -1716,15 +1783,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_asm_kernel(AttnArgs p) {
 #pragma unroll
   for (int s = 0; s < 4; ++s) qf[s] = *reinterpret_cast<const bf16x8*>(Qp + (int64_t)qrow * p.q_rs + 16 * s + 8 * lh);
   unsigned aq[4], va0, va1;
-#pragma unroll
-  for (int s_ = 0; s_ < 4; ++s_) aq[s_] = lds0 + (unsigned)Img<T, D>::off(li, (16 * s_ + 8 * lh) * 2);
-  {
-    const int g4 = lane >> 4, i16 = lane & 15, hh = g4 >> 1;
-    const int rpart = (4 * hh + (i16 >> 2)) * 128 + (i16 & 1) * 8;
-    const int c0 = 2 * (g4 & 1) + ((i16 & 3) >> 1), gg0 = 2 * hh + (i16 >> 3), f0 = gg0 ^ ((gg0 & 1) << 2);
-    va0 = lds0 + (unsigned)(rpart + ((c0 ^ f0) << 4));
-    va1 = lds0 + (unsigned)(rpart + (((c0 ^ f0) ^ 4) << 4));
-  }
+  lean_frag_addrs(aq, va0, va1, lds0, lane);
   // hipcc's wait for the Q fragments goes in front of this use; it is in order and so covers the two tile requests too
   asm volatile("" ::"v"(qf[0]), "v"(qf[1]), "v"(qf[2]), "v"(qf[3]));
   asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
@@ -1794,8 +1853,8 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_asm_kernel(AttnArgs p) {
   {                                                                                                                                 \
     const unsigned so_ = (unsigned)((tt) & 3) * (unsigned)IMG, sp_ = (unsigned)(((tt) + 3) & 3) * (unsigned)IMG;                    \
     const unsigned aqs_[4] = {aq[0] + so_, aq[1] + so_, aq[2] + so_, aq[3] + so_};                                                  \
-    fwd_##KIND##_asm_gen(o[0], o[1], sc1, l, rmax, qf, aqs_, va0 + so_, va1 + so_, va0 + sp_, va1 + sp_, vo, k_base((tt) + 2),      \
-                         v_base((tt) + 2), ldsw + (unsigned)(((tt) + 2) & 3) * (unsigned)IMG);                                      \
+    fwd_##KIND##_asm_gen(o[0], o[1], sc1, l, rmax, qf, aqs_, va0 + so_, va1 + so_, va0 + sp_, va1 + sp_, vo, ksrc.base((tt) + 2),   \
+                         vsrc.base((tt) + 2), ldsw + (unsigned)(((tt) + 2) & 3) * (unsigned)IMG);                                   \
   }
 
   int* flag = reinterpret_cast<int*>(smem + 2 * NS * IMG);
@@ -1823,7 +1882,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_asm_kernel(AttnArgs p) {
       // nothing of ITS memory traffic is pending (spill stores of the classic phase are vector-memory operations): otherwise its wait-count
       // pass puts a vmcnt(0) at the head of the loop below, which drains the streams' tile requests every fourth step.
       __builtin_amdgcn_s_waitcnt(0x0F70);
-#define FK_FWD_ARGS(tt) o[0], o[1], sc1, l, rmax, qf, aq, va0, va1, vo, k_base((tt) + 2), v_base((tt) + 2), ldsw
+#define FK_FWD_ARGS(tt) o[0], o[1], sc1, l, rmax, qf, aq, va0, va1, vo, ksrc.base((tt) + 2), vsrc.base((tt) + 2), ldsw
       for (; t + 4 <= ntiles; t += 4) {                        // no branch inside: four steps back to back
         fwd_steady_asm_slot0(FK_FWD_ARGS(t));
         fwd_steady_asm_slot1(FK_FWD_ARGS(t + 1));
@@ -1834,7 +1893,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_asm_kernel(AttnArgs p) {
 #undef FK_FWD_ARGS
       FK_FWD_STEP(drain, t)                                    // slot argument: the last tile's slot + 1
     }
-    asm volatile("s_waitcnt vmcnt(0)\n\ts_nop 15\n\ts_nop 15" ::: "memory");   // stray requests landed, the last MFMAs retired
+    stream_drain();
     if (!lean_ok) break;
 #ifdef FK_FWD_PROBE_NOREDO
     break;                                                       // timing builds of ablated streams (tools/stream_variants.sh): their sums mean nothing
@@ -1857,7 +1916,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_asm_kernel(AttnArgs p) {
 #undef FK_FWD_STEP
   const float lt = l + __shfl_xor(l, 32, 64);
   const float inv = lt > 0.0f ? 1.0f / lt : 0.0f;
-  T* Op = (T*)p.Out + (int64_t)b * p.o_bs + hd * D;
+  T* Op = head_ptr<T, D>(p.Out, p.o_bs, b, hd);
   store_rows_T<T, D>(Op, p.o_rs, qrow, true, o, inv, lh);
   if (lh == 0 && p.LSE) p.LSE[((int64_t)b * p.H + hd) * p.Nq + qrow] = lt > 0.0f ? m * LN2 + logf(lt) : INFINITY;
   FK_LIFE_END(3)
@@ -1880,32 +1939,22 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_asm_kernel(AttnArgs p) {
   const int tid = threadIdx.x, lane = tid & 63, li = lane & 31, lh = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int nqb = p.Nq / BQ;
-  const unsigned L = xcd_remap(blockIdx.x, gridDim.x);
-  const int bh = (int)(L / nqb), b = bh / p.H, hd = bh % p.H, q0 = (nqb - 1 - (int)(L % nqb)) * BQ;
-  const T* Qp = (const T*)p.Q + (int64_t)b * p.q_bs + hd * D;
-  const T* Kp = (const T*)p.K + (int64_t)b * p.k_bs + hd * D;
-  const T* Vp = (const T*)p.V + (int64_t)b * p.v_bs + hd * D;
-  const T* Gp = (const T*)p.dO + (int64_t)b * p.o_bs + hd * D;
+  int b, hd, q0;
+  query_block(p.H, nqb, BQ, b, hd, q0);
+  const T* Qp = head_ptr<T, D>(p.Q, p.q_bs, b, hd);
+  const T* Kp = head_ptr<T, D>(p.K, p.k_bs, b, hd);
+  const T* Vp = head_ptr<T, D>(p.V, p.v_bs, b, hd);
+  const T* Gp = head_ptr<T, D>(p.dO, p.o_bs, b, hd);
   const int qrow = q0 + wave * 32 + li;
   const int ntiles = kv_limit(p, b, q0 + BQ - 1) / BKV;       // >= 1; every one of them fully visible to every row of the workgroup
 
-  // tile requests: per wave two 8-row groups of the K image and two of the V image; address = 64-bit tile base (SGPR pair) + per-lane
-  // byte offset that never changes
   unsigned vo[4];
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int row = (wave * 2 + j) * 8 + (lane >> 3);
-    const int g = (row >> 1) & 7, f = g ^ ((g & 1) << 2);
-    vo[j] = (__umul24((unsigned)row, (unsigned)p.k_rs) + (unsigned)(((lane & 7) ^ f) * 8)) * 2u;
-    vo[2 + j] = (__umul24((unsigned)row, (unsigned)p.v_rs) + (unsigned)(((lane & 7) ^ f) * 8)) * 2u;
-  }
+  lean_dma_offsets(vo, wave, lane, p.k_rs, p.v_rs);
   const unsigned lds0 = (unsigned)(uintptr_t)(lds_void_t*)smem;
   const unsigned ldsw = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)wave * 2048u);
-  auto tile_row = [&](int tt) { return (tt < ntiles ? tt : ntiles - 1) * BKV; };             // past the end: the last tile again (never read)
-  auto k_base = [&](int tt) { return (uint64_t)(uintptr_t)(Kp + (int64_t)tile_row(tt) * p.k_rs); };
-  auto v_base = [&](int tt) { return (uint64_t)(uintptr_t)(Vp + (int64_t)tile_row(tt) * p.v_rs); };
-  dq_request_asm_slot0(vo, k_base(0), v_base(0), ldsw);
-  dq_request_asm_slot1(vo, k_base(1), v_base(1), ldsw);
+  const TileSrc<T, BKV> ksrc{Kp, p.k_rs, 0, ntiles}, vsrc{Vp, p.v_rs, 0, ntiles};
+  dq_request_asm_slot0(vo, ksrc.base(0), vsrc.base(0), ldsw);
+  dq_request_asm_slot1(vo, ksrc.base(1), vsrc.base(1), ldsw);
 
   bf16x8 qf[4], gf[4];
 #pragma unroll
@@ -1913,164 +1962,30 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_asm_kernel(AttnArgs p) {
     qf[s] = *reinterpret_cast<const bf16x8*>(Qp + (int64_t)qrow * p.q_rs + 16 * s + 8 * lh);
     gf[s] = *reinterpret_cast<const bf16x8*>(Gp + (int64_t)qrow * p.o_rs + 16 * s + 8 * lh);
   }
-  const int64_t stat = ((int64_t)b * p.H + hd) * p.Nq + qrow;
-  const float lse2 = p.LSE[stat] * LOG2E;
-  float dl;
-  {
-    const T* Op = (const T*)p.O + (int64_t)b * p.o_bs + hd * D;
-    float part = 0.0f;
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      const bf16x8 of = *reinterpret_cast<const bf16x8*>(Op + (int64_t)qrow * p.o_rs + 16 * s + 8 * lh);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) part += to_f32<T>(of[e]) * to_f32<T>(gf[s][e]);
-    }
-    dl = part + __shfl_xor(part, 32, 64);
-    if (lh == 0) {                                              // Nq is a multiple of 128 here: the workspace rows are Nq long
-      p.delta[stat] = -lse2;
-      p.delta[(int64_t)p.B * p.H * p.Nq + stat] = -dl;
-    }
-  }
+  float lse2, dl;
+  dq_row_stats(p, b, hd, qrow, true, p.Nq, lh, gf, lse2, dl);   // Nq is a multiple of 128 here: the workspace rows are Nq long
   f32x16 cl, cd;       // the row constants as initial accumulators: S' = Q'K^T - lse2, dP' = dO V^T - delta
 #pragma unroll
   for (int r = 0; r < 16; ++r) { cl[r] = -lse2; cd[r] = -dl; }
   f32x16 dq[2];
   zero_acc(dq);
   unsigned aq[4], va0, va1;
-#pragma unroll
-  for (int s_ = 0; s_ < 4; ++s_) aq[s_] = lds0 + (unsigned)Img<T, D>::off(li, (16 * s_ + 8 * lh) * 2);
-  {
-    const int g4 = lane >> 4, i16 = lane & 15, hh = g4 >> 1;
-    const int rpart = (4 * hh + (i16 >> 2)) * 128 + (i16 & 1) * 8;
-    const int c0 = 2 * (g4 & 1) + ((i16 & 3) >> 1), gg0 = 2 * hh + (i16 >> 3), f0 = gg0 ^ ((gg0 & 1) << 2);
-    va0 = lds0 + (unsigned)(rpart + ((c0 ^ f0) << 4));
-    va1 = lds0 + (unsigned)(rpart + (((c0 ^ f0) ^ 4) << 4));
-  }
+  lean_frag_addrs(aq, va0, va1, lds0, lane);
   // hipcc's wait for the register loads above goes in front of this use; it is in order and so covers the two tile requests too
   asm volatile("" ::"v"(qf[0]), "v"(qf[1]), "v"(qf[2]), "v"(qf[3]), "v"(gf[0]), "v"(gf[1]), "v"(gf[2]), "v"(gf[3]), "v"(cl), "v"(cd));
   asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
   for (int t = 0; t < ntiles; t += 3) {
-    dq_tile_asm_slot0(dq[0], dq[1], qf, gf, cl, cd, aq, va0, va1, vo, k_base(t + 2), v_base(t + 2), ldsw);
-    if (t + 1 < ntiles) dq_tile_asm_slot1(dq[0], dq[1], qf, gf, cl, cd, aq, va0, va1, vo, k_base(t + 3), v_base(t + 3), ldsw);
-    if (t + 2 < ntiles) dq_tile_asm_slot2(dq[0], dq[1], qf, gf, cl, cd, aq, va0, va1, vo, k_base(t + 4), v_base(t + 4), ldsw);
+    dq_tile_asm_slot0(dq[0], dq[1], qf, gf, cl, cd, aq, va0, va1, vo, ksrc.base(t + 2), vsrc.base(t + 2), ldsw);
+    if (t + 1 < ntiles) dq_tile_asm_slot1(dq[0], dq[1], qf, gf, cl, cd, aq, va0, va1, vo, ksrc.base(t + 3), vsrc.base(t + 3), ldsw);
+    if (t + 2 < ntiles) dq_tile_asm_slot2(dq[0], dq[1], qf, gf, cl, cd, aq, va0, va1, vo, ksrc.base(t + 4), vsrc.base(t + 4), ldsw);
   }
-  asm volatile("s_waitcnt vmcnt(0)\n\ts_nop 15\n\ts_nop 15" ::: "memory");   // stray requests landed, the stream's last MFMAs retired
-  T* dQp = (T*)p.dQ + (int64_t)b * p.q_bs + hd * D;
-  if (p.rope_table)
-    store_rows_T_rope<T, D>(dQp, p.q_rs, qrow, true, dq, p.scale, lh, p.rope_table + (int64_t)b * p.rope_bs + (int64_t)(p.rope_off + qrow) * D);
-  else
-    store_rows_T<T, D>(dQp, p.q_rs, qrow, true, dq, p.scale, lh);
+  stream_drain();
+  store_dq(p, b, hd, qrow, true, dq, lh);
   FK_LIFE_END(1)
 }
 #endif
 
-#ifdef FK_DQ16_ASM
-#include "attn_dq16_asm.inc"      // generated by tools/gen/gen_dq16_asm.py: the dQ tile step on v_mfma_f32_16x16x32_bf16
-// Same contract as attn_bwd_dq_asm_kernel (shapes, workspace rows for the dK/dV kernel), fragments and accumulators in the layouts of the
-// 16x16x32 MFMA: lane = (c, g) = (lane % 16, lane / 16); query blocks qb of 16 rows, d in 16-byte chunks 4 ks + tau(g), tau = [0, 3, 1, 2].
-__global__ __launch_bounds__(256, 2) void attn_bwd_dq16_asm_kernel(AttnArgs p) {
-  using T = bf16_t;
-  constexpr int D = 64, NW = 4, BQ = NW * 32, IMG = BKV * 128, NS = 3;
-  static_assert(BKV == 64, "the generated stream is written for 64-key tiles");
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int tid = threadIdx.x, lane = tid & 63, c = lane & 15, g = lane >> 4;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int nqb = p.Nq / BQ;
-  const unsigned L = xcd_remap(blockIdx.x, gridDim.x);
-  const int bh = (int)(L / nqb), b = bh / p.H, hd = bh % p.H, q0 = (nqb - 1 - (int)(L % nqb)) * BQ;
-  const T* Qp = (const T*)p.Q + (int64_t)b * p.q_bs + hd * D;
-  const T* Kp = (const T*)p.K + (int64_t)b * p.k_bs + hd * D;
-  const T* Vp = (const T*)p.V + (int64_t)b * p.v_bs + hd * D;
-  const T* Gp = (const T*)p.dO + (int64_t)b * p.o_bs + hd * D;
-  const T* Op = (const T*)p.O + (int64_t)b * p.o_bs + hd * D;
-  const int ntiles = kv_limit(p, b, q0 + BQ - 1) / BKV;
-  const int tau = (0x2130 >> (4 * g)) & 3;                        // d-chunk of lane group g within a k-step: 0, 3, 1, 2
-
-  unsigned vo[4];
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int row = (wave * 2 + j) * 8 + (lane >> 3);
-    const int gg = (row >> 1) & 7, f = gg ^ ((gg & 1) << 2);
-    vo[j] = (__umul24((unsigned)row, (unsigned)p.k_rs) + (unsigned)(((lane & 7) ^ f) * 8)) * 2u;
-    vo[2 + j] = (__umul24((unsigned)row, (unsigned)p.v_rs) + (unsigned)(((lane & 7) ^ f) * 8)) * 2u;
-  }
-  const unsigned lds0 = (unsigned)(uintptr_t)(lds_void_t*)smem;
-  const unsigned ldsw = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)wave * 2048u);
-  auto tile_row = [&](int tt) { return (tt < ntiles ? tt : ntiles - 1) * BKV; };
-  auto k_base = [&](int tt) { return (uint64_t)(uintptr_t)(Kp + (int64_t)tile_row(tt) * p.k_rs); };
-  auto v_base = [&](int tt) { return (uint64_t)(uintptr_t)(Vp + (int64_t)tile_row(tt) * p.v_rs); };
-  dq_request_asm_slot0(vo, k_base(0), v_base(0), ldsw);
-  dq_request_asm_slot1(vo, k_base(1), v_base(1), ldsw);
-
-  bf16x8 qf[2][2], gf[2][2];
-  f32x4 cl[2], cd[2];
-#pragma unroll
-  for (int qb = 0; qb < 2; ++qb) {
-    const int qrow = q0 + wave * 32 + 16 * qb + c;
-    float part = 0.0f;
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      const int d0 = 32 * ks + 8 * tau;
-      qf[qb][ks] = *reinterpret_cast<const bf16x8*>(Qp + (int64_t)qrow * p.q_rs + d0);
-      gf[qb][ks] = *reinterpret_cast<const bf16x8*>(Gp + (int64_t)qrow * p.o_rs + d0);
-      const bf16x8 of = *reinterpret_cast<const bf16x8*>(Op + (int64_t)qrow * p.o_rs + d0);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) part += to_f32<T>(of[e]) * to_f32<T>(gf[qb][ks][e]);
-    }
-    part += __shfl_xor(part, 16, 64);
-    part += __shfl_xor(part, 32, 64);                           // delta = rowsum(dO * O) over the four lane groups
-    const int64_t stat = ((int64_t)b * p.H + hd) * p.Nq + qrow;
-    const float lse2 = p.LSE[stat] * LOG2E;
-    if (g == 0) {
-      p.delta[stat] = -lse2;
-      p.delta[(int64_t)p.B * p.H * p.Nq + stat] = -part;
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) { cl[qb][r] = -lse2; cd[qb][r] = -part; }
-  }
-  f32x4 dq[4][2];
-#pragma unroll
-  for (int db = 0; db < 4; ++db)
-#pragma unroll
-    for (int qb = 0; qb < 2; ++qb) dq[db][qb] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-  unsigned aq[2], va[4];
-#pragma unroll
-  for (int ks = 0; ks < 2; ++ks) aq[ks] = lds0 + (unsigned)Img<T, D>::off(c, (4 * ks + tau) * 16);
-#pragma unroll
-  for (int db = 0; db < 4; ++db) va[db] = lds0 + (unsigned)Img<T, D>::off(4 * g + (c >> 2), (16 * db + 4 * (c & 3)) * 2);
-  asm volatile("" ::"v"(qf[0][0]), "v"(qf[0][1]), "v"(qf[1][0]), "v"(qf[1][1]), "v"(gf[0][0]), "v"(gf[0][1]), "v"(gf[1][0]), "v"(gf[1][1]),
-               "v"(cl[0]), "v"(cl[1]), "v"(cd[0]), "v"(cd[1]));
-  asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
-  for (int t = 0; t < ntiles; t += 3) {
-    dq16_tile_asm_slot0(dq, qf, gf, cl, cd, aq, va, vo, k_base(t + 2), v_base(t + 2), ldsw);
-    if (t + 1 < ntiles) dq16_tile_asm_slot1(dq, qf, gf, cl, cd, aq, va, vo, k_base(t + 3), v_base(t + 3), ldsw);
-    if (t + 2 < ntiles) dq16_tile_asm_slot2(dq, qf, gf, cl, cd, aq, va, vo, k_base(t + 4), v_base(t + 4), ldsw);
-  }
-  asm volatile("s_waitcnt vmcnt(0)\n\ts_nop 15\n\ts_nop 15" ::: "memory");
-  // store: block (db, qb) of this lane = dQ[query 16 qb + c][d = 16 db + 4 g .. + 3]
-  T* dQp = (T*)p.dQ + (int64_t)b * p.q_bs + hd * D;
-#pragma unroll
-  for (int qb = 0; qb < 2; ++qb) {
-    const int qrow = q0 + wave * 32 + 16 * qb + c;
-    const float* table = p.rope_table ? p.rope_table + (int64_t)b * p.rope_bs + (int64_t)(p.rope_off + qrow) * D : nullptr;
-#pragma unroll
-    for (int db = 0; db < 4; ++db) {
-      const int d = 16 * db + 4 * g;
-      const float a0 = dq[db][qb][0] * p.scale, a1 = dq[db][qb][1] * p.scale, a2 = dq[db][qb][2] * p.scale, a3 = dq[db][qb][3] * p.scale;
-      float o0 = a0, o1 = a1, o2 = a2, o3 = a3;
-      if (table) {                                              // inverse RoPE: pairs (d, d + 1) rotated by -angle, as store_rows_T_rope
-        const f32x4 cs = *reinterpret_cast<const f32x4*>(table + d);
-        o0 = a0 * cs[0] + a1 * cs[1]; o1 = -a0 * cs[1] + a1 * cs[0];
-        o2 = a2 * cs[2] + a3 * cs[3]; o3 = -a2 * cs[3] + a3 * cs[2];
-      }
-      const bf16x4 v = {(bf16_t)o0, (bf16_t)o1, (bf16_t)o2, (bf16_t)o3};
-      *reinterpret_cast<bf16x4*>(dQp + (int64_t)qrow * p.q_rs + d) = v;
-    }
-  }
-}
-#endif
-
-#ifndef FK_NO_DKDV_ASM
+#if !defined(FK_NO_DKDV_ASM) || !defined(FK_NO_DKDVW_ASM)   // (the wide kernel issues its tile requests with the narrow stream's request blocks)
 #include "attn_dkdv_asm.inc"      // generated by tools/gen/gen_dkdv_asm.py: hand-placed instruction stream of one fully visible tile step
 #endif
 // ------------------------------------------------------------------------------------------------- dK, dV (pre-scaled Q)
@@ -2088,12 +2003,12 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_bwd_dkdv_ps_kernel(AttnArgs p
   const int tid = threadIdx.x, lane = tid & 63, li = lane & 31, lh = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int nkb = (p.Nk + BK - 1) / BK;
-  const unsigned L = xcd_remap(blockIdx.x, gridDim.x);
-  const int bh = (int)(L / nkb), b = bh / p.H, hd = bh % p.H, k0 = (int)(L % nkb) * BK;
-  const T* Qp = (const T*)p.Q + (int64_t)b * p.q_bs + hd * D;
-  const T* Kp = (const T*)p.K + (int64_t)b * p.k_bs + hd * D;
-  const T* Vp = (const T*)p.V + (int64_t)b * p.v_bs + hd * D;
-  const T* Gp = (const T*)p.dO + (int64_t)b * p.o_bs + hd * D;
+  int b, hd, k0;
+  key_block(p.H, nkb, BK, b, hd, k0);
+  const T* Qp = head_ptr<T, D>(p.Q, p.q_bs, b, hd);
+  const T* Kp = head_ptr<T, D>(p.K, p.k_bs, b, hd);
+  const T* Vp = head_ptr<T, D>(p.V, p.v_bs, b, hd);
+  const T* Gp = head_ptr<T, D>(p.dO, p.o_bs, b, hd);
   const int krow = k0 + wave * 32 + li;
   const bool k_ok = krow < p.Nk;
   const bool prefix = p.mask_kind == FK_MASK_PREFIX, keypad = p.mask_kind == FK_MASK_KEYPAD;
@@ -2114,7 +2029,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_bwd_dkdv_ps_kernel(AttnArgs p
   const int ntiles = qs < p.Nq ? (p.Nq - qs + TQ - 1) / TQ : 0;
   // key padding: a wave whose 32 keys are all valid needs no predicate at all -- a padded query arrives with the staged statistic -inf
   // (its LSE is +inf), exactly like the rows past Nq of the last tile, so its P is 0 on the mask-free path too
-  const bool keypad_keys_valid = !FK_KEYPAD_NO_FREE && __builtin_amdgcn_ballot_w64(k_ok && my_qf == 0) == 0;
+  const bool keypad_keys_valid = __builtin_amdgcn_ballot_w64(k_ok && my_qf == 0) == 0;
   const int full_vis_q = keypad ? (keypad_keys_valid ? 0 : 0x3fffffff) : q_first(p, b, min(k0 + wave * 32 + 31, p.Nk - 1));
   // Row statistics: the dQ kernel has left -LSE*log2(e) and -delta in the workspace exactly as the accumulators want them (rows padded to
   // the tile, -inf / 0 past Nq), so a tile's 64 + 64 floats travel by LDS-DMA like the tile itself: one 256-byte piece each, issued by
@@ -2234,14 +2149,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_bwd_dkdv_ps_kernel(AttnArgs p
     if (t + 2 < ntiles) tile_step(std::integral_constant<int, 2>{}, t + 2);
   }
   FK_ST(6)
-  // dK = scale * dS^T Q = ln(2) * dS^T Q'   (Q' = scale * log2(e) * Q)
-  T* dKp = (T*)p.dK + (int64_t)b * p.k_bs + hd * D;
-  T* dVp = (T*)p.dV + (int64_t)b * p.v_bs + hd * D;
-  if (p.rope_table)           // wave-uniform: the stores swap registers between the half-waves, every lane takes part
-    store_rows_T_rope<T, D>(dKp, p.k_rs, krow, k_ok, dk, LN2, lh, p.rope_table + (int64_t)b * p.rope_bs + (int64_t)(p.rope_off + krow) * D);
-  else
-    store_rows_T<T, D>(dKp, p.k_rs, krow, k_ok, dk, LN2, lh);
-  store_rows_T<T, D>(dVp, p.v_rs, krow, k_ok, dv, 1.0f, lh);
+  store_dk_dv(p, b, hd, krow, k_ok, dk, dv, lh);
   FK_ST(7)
   FK_ST_FLUSH(0)
 }
@@ -2264,12 +2172,12 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_asm_kernel(AttnArgs p) {
   const int tid = threadIdx.x, lane = tid & 63, li = lane & 31, lh = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int nkb = p.Nk / BK;
-  const unsigned L = xcd_remap(blockIdx.x, gridDim.x);
-  const int bh = (int)(L / nkb), b = bh / p.H, hd = bh % p.H, k0 = (int)(L % nkb) * BK;
-  const T* Qp = (const T*)p.Q + (int64_t)b * p.q_bs + hd * D;
-  const T* Kp = (const T*)p.K + (int64_t)b * p.k_bs + hd * D;
-  const T* Vp = (const T*)p.V + (int64_t)b * p.v_bs + hd * D;
-  const T* Gp = (const T*)p.dO + (int64_t)b * p.o_bs + hd * D;
+  int b, hd, k0;
+  key_block(p.H, nkb, BK, b, hd, k0);
+  const T* Qp = head_ptr<T, D>(p.Q, p.q_bs, b, hd);
+  const T* Kp = head_ptr<T, D>(p.K, p.k_bs, b, hd);
+  const T* Vp = head_ptr<T, D>(p.V, p.v_bs, b, hd);
+  const T* Gp = head_ptr<T, D>(p.dO, p.o_bs, b, hd);
   const int krow = k0 + wave * 32 + li;
   const int qs = q_first(p, b, k0);                      // a multiple of the mask block, hence of TQ
   const int ntiles = (p.Nq - qs) / TQ;
@@ -2278,29 +2186,21 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_asm_kernel(AttnArgs p) {
   const float* nd_g = nl_g + (int64_t)p.B * p.H * nqp;
   // The tile requests (LDS-DMA): per wave two 8-row groups of the Q image, two of the dO image and one row of statistics (waves 2, 3
   // repeat the rows of waves 0, 1: same bytes to the same place, and every wave then has the same five requests per tile in flight).
-  // Address = wave-uniform 64-bit tile base (SGPR pair) + per-lane byte offset that never changes; the stream sets M0 itself.
+  // The stream sets M0 itself.
   unsigned vo[5];
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int row = (wave * 2 + j) * 8 + (lane >> 3);
-    const int g = (row >> 1) & 7, f = g ^ ((g & 1) << 2);
-    vo[j] = (__umul24((unsigned)row, (unsigned)p.q_rs) + (unsigned)(((lane & 7) ^ f) * 8)) * 2u;
-    vo[2 + j] = (__umul24((unsigned)row, (unsigned)p.o_rs) + (unsigned)(((lane & 7) ^ f) * 8)) * 2u;
-  }
+  lean_dma_offsets(vo, wave, lane, p.q_rs, p.o_rs);
   vo[4] = (unsigned)lane * 4u;
   const float* st_g = (wave & 1) ? nd_g : nl_g;
   const unsigned lds0 = (unsigned)(uintptr_t)(lds_void_t*)smem;
   const unsigned ldsw = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)wave * 2048u);
   const unsigned ldss = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)(2 * NS * IMG) + (unsigned)(wave & 1) * 256u);
-  auto tile_row = [&](int tt) { return qs + (tt < ntiles ? tt : ntiles - 1) * TQ; };      // past the end: the last tile again (never read)
-  auto q_base = [&](int tt) { return (uint64_t)(uintptr_t)(Qp + (int64_t)tile_row(tt) * p.q_rs); };
-  auto g_base = [&](int tt) { return (uint64_t)(uintptr_t)(Gp + (int64_t)tile_row(tt) * p.o_rs); };
-  auto s_base = [&](int tt) { return (uint64_t)(uintptr_t)(st_g + tile_row(tt)); };
+  const TileSrc<T, TQ> qsrc{Qp, p.q_rs, qs, ntiles}, gsrc{Gp, p.o_rs, qs, ntiles};
+  const TileSrc<float, TQ> ssrc{st_g, 1, qs, ntiles};
   // prologue: tiles 0 and 1 requested first, then this wave's K / V fragments (registers for the whole kernel); the wait for the
   // fragments, placed by hipcc in front of the dummy use below, is in order and so covers the tiles too
   if (ntiles > 0) {
-    dkdv_request_asm_slot0(vo, q_base(0), g_base(0), s_base(0), ldsw, ldss);
-    dkdv_request_asm_slot1(vo, q_base(1), g_base(1), s_base(1), ldsw, ldss);
+    dkdv_request_asm_slot0(vo, qsrc.base(0), gsrc.base(0), ssrc.base(0), ldsw, ldss);
+    dkdv_request_asm_slot1(vo, qsrc.base(1), gsrc.base(1), ssrc.base(1), ldsw, ldss);
   }
   bf16x8 kfv[4], vfv[4];
 #pragma unroll
@@ -2312,15 +2212,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_asm_kernel(AttnArgs p) {
   zero_acc(dk);
   zero_acc(dv);
   unsigned aq[4], va0, va1;
-#pragma unroll
-  for (int s_ = 0; s_ < 4; ++s_) aq[s_] = lds0 + (unsigned)Img<T, D>::off(li, (16 * s_ + 8 * lh) * 2);
-  {
-    const int g4 = lane >> 4, i16 = lane & 15, hh = g4 >> 1;
-    const int rpart = (4 * hh + (i16 >> 2)) * 128 + (i16 & 1) * 8;
-    const int c0 = 2 * (g4 & 1) + ((i16 & 3) >> 1), gg0 = 2 * hh + (i16 >> 3), f0 = gg0 ^ ((gg0 & 1) << 2);
-    va0 = lds0 + (unsigned)(rpart + ((c0 ^ f0) << 4));
-    va1 = lds0 + (unsigned)(rpart + (((c0 ^ f0) ^ 4) << 4));
-  }
+  lean_frag_addrs(aq, va0, va1, lds0, lane);
   const unsigned ast = lds0 + (unsigned)(2 * NS * IMG) + (unsigned)lh * 16u;
   if (ntiles > 0) {
     asm volatile("" ::"v"(kfv[0]), "v"(kfv[1]), "v"(kfv[2]), "v"(kfv[3]), "v"(vfv[0]), "v"(vfv[1]), "v"(vfv[2]), "v"(vfv[3]));
@@ -2328,24 +2220,17 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_asm_kernel(AttnArgs p) {
     // Each step: tile t from ring slot t % 3, with the requests of tile t + 2 issued from inside the stream and, at its end, the wait
     // for tile t + 1 and the barrier.
     for (int t = 0; t < ntiles; t += 3) {
-      dkdv_tile_asm_slot0(dk[0], dk[1], dv[0], dv[1], kfv, vfv, aq, va0, va1, ast, vo, q_base(t + 2), g_base(t + 2), s_base(t + 2), ldsw, ldss);
+      dkdv_tile_asm_slot0(dk[0], dk[1], dv[0], dv[1], kfv, vfv, aq, va0, va1, ast, vo, qsrc.base(t + 2), gsrc.base(t + 2), ssrc.base(t + 2), ldsw, ldss);
       if (t + 1 < ntiles) {
-        dkdv_tile_asm_slot1(dk[0], dk[1], dv[0], dv[1], kfv, vfv, aq, va0, va1, ast, vo, q_base(t + 3), g_base(t + 3), s_base(t + 3), ldsw, ldss);
+        dkdv_tile_asm_slot1(dk[0], dk[1], dv[0], dv[1], kfv, vfv, aq, va0, va1, ast, vo, qsrc.base(t + 3), gsrc.base(t + 3), ssrc.base(t + 3), ldsw, ldss);
       }
       if (t + 2 < ntiles) {
-        dkdv_tile_asm_slot2(dk[0], dk[1], dv[0], dv[1], kfv, vfv, aq, va0, va1, ast, vo, q_base(t + 4), g_base(t + 4), s_base(t + 4), ldsw, ldss);
+        dkdv_tile_asm_slot2(dk[0], dk[1], dv[0], dv[1], kfv, vfv, aq, va0, va1, ast, vo, qsrc.base(t + 4), gsrc.base(t + 4), ssrc.base(t + 4), ldsw, ldss);
       }
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the (unused) requests past the last tile have landed before the workgroup ends
   }
-  asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");    // the stream's last MFMAs have retired before the compiler reads the accumulators
-  T* dKp = (T*)p.dK + (int64_t)b * p.k_bs + hd * D;
-  T* dVp = (T*)p.dV + (int64_t)b * p.v_bs + hd * D;
-  if (p.rope_table)
-    store_rows_T_rope<T, D>(dKp, p.k_rs, krow, true, dk, LN2, lh, p.rope_table + (int64_t)b * p.rope_bs + (int64_t)(p.rope_off + krow) * D);
-  else
-    store_rows_T<T, D>(dKp, p.k_rs, krow, true, dk, LN2, lh);
-  store_rows_T<T, D>(dVp, p.v_rs, krow, true, dv, 1.0f, lh);
+  stream_drain();
+  store_dk_dv(p, b, hd, krow, true, dk, dv, lh);
   FK_LIFE_END(2)
 }
 #endif
@@ -2365,12 +2250,12 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkdvw_asm_kernel(AttnArgs p) 
   const int tid = threadIdx.x, lane = tid & 63, li = lane & 31, lh = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int nkb = p.Nk / BK;
-  const unsigned L = xcd_remap(blockIdx.x, gridDim.x);
-  const int bh = (int)(L / nkb), b = bh / p.H, hd = bh % p.H, k0 = (int)(L % nkb) * BK;
-  const T* Qp = (const T*)p.Q + (int64_t)b * p.q_bs + hd * D;
-  const T* Kp = (const T*)p.K + (int64_t)b * p.k_bs + hd * D;
-  const T* Vp = (const T*)p.V + (int64_t)b * p.v_bs + hd * D;
-  const T* Gp = (const T*)p.dO + (int64_t)b * p.o_bs + hd * D;
+  int b, hd, k0;
+  key_block(p.H, nkb, BK, b, hd, k0);
+  const T* Qp = head_ptr<T, D>(p.Q, p.q_bs, b, hd);
+  const T* Kp = head_ptr<T, D>(p.K, p.k_bs, b, hd);
+  const T* Vp = head_ptr<T, D>(p.V, p.v_bs, b, hd);
+  const T* Gp = head_ptr<T, D>(p.dO, p.o_bs, b, hd);
   const int krow0 = k0 + wave * 64 + li;                 // key block kb: krow0 + 32 kb
   const int qs = q_first(p, b, k0);                      // a multiple of the mask block, hence of TQ
   const int ntiles = (p.Nq - qs) / TQ;
@@ -2378,25 +2263,17 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkdvw_asm_kernel(AttnArgs p) 
   const float* nl_g = p.delta + ((int64_t)b * p.H + hd) * nqp;
   const float* nd_g = nl_g + (int64_t)p.B * p.H * nqp;
   unsigned vo[5];
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int row = (wave * 2 + j) * 8 + (lane >> 3);
-    const int g = (row >> 1) & 7, f = g ^ ((g & 1) << 2);
-    vo[j] = (__umul24((unsigned)row, (unsigned)p.q_rs) + (unsigned)(((lane & 7) ^ f) * 8)) * 2u;
-    vo[2 + j] = (__umul24((unsigned)row, (unsigned)p.o_rs) + (unsigned)(((lane & 7) ^ f) * 8)) * 2u;
-  }
+  lean_dma_offsets(vo, wave, lane, p.q_rs, p.o_rs);
   vo[4] = (unsigned)lane * 4u;
   const float* st_g = (wave & 1) ? nd_g : nl_g;
   const unsigned lds0 = (unsigned)(uintptr_t)(lds_void_t*)smem;
   const unsigned ldsw = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)wave * 2048u);
   const unsigned ldss = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)(2 * NS * IMG) + (unsigned)(wave & 1) * 256u);
-  auto tile_row = [&](int tt) { return qs + (tt < ntiles ? tt : ntiles - 1) * TQ; };
-  auto q_base = [&](int tt) { return (uint64_t)(uintptr_t)(Qp + (int64_t)tile_row(tt) * p.q_rs); };
-  auto g_base = [&](int tt) { return (uint64_t)(uintptr_t)(Gp + (int64_t)tile_row(tt) * p.o_rs); };
-  auto s_base = [&](int tt) { return (uint64_t)(uintptr_t)(st_g + tile_row(tt)); };
+  const TileSrc<T, TQ> qsrc{Qp, p.q_rs, qs, ntiles}, gsrc{Gp, p.o_rs, qs, ntiles};
+  const TileSrc<float, TQ> ssrc{st_g, 1, qs, ntiles};
   if (ntiles > 0) {
-    dkdv_request_asm_slot0(vo, q_base(0), g_base(0), s_base(0), ldsw, ldss);
-    dkdv_request_asm_slot1(vo, q_base(1), g_base(1), s_base(1), ldsw, ldss);
+    dkdv_request_asm_slot0(vo, qsrc.base(0), gsrc.base(0), ssrc.base(0), ldsw, ldss);
+    dkdv_request_asm_slot1(vo, qsrc.base(1), gsrc.base(1), ssrc.base(1), ldsw, ldss);
   }
   bf16x8 kfv[2][4], vfv[2][4];
 #pragma unroll
@@ -2410,15 +2287,7 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkdvw_asm_kernel(AttnArgs p) 
 #pragma unroll
   for (int kb = 0; kb < 2; ++kb) { zero_acc(dk[kb]); zero_acc(dv[kb]); }
   unsigned aq[4], va0, va1;
-#pragma unroll
-  for (int s_ = 0; s_ < 4; ++s_) aq[s_] = lds0 + (unsigned)Img<T, D>::off(li, (16 * s_ + 8 * lh) * 2);
-  {
-    const int g4 = lane >> 4, i16 = lane & 15, hh = g4 >> 1;
-    const int rpart = (4 * hh + (i16 >> 2)) * 128 + (i16 & 1) * 8;
-    const int c0 = 2 * (g4 & 1) + ((i16 & 3) >> 1), gg0 = 2 * hh + (i16 >> 3), f0 = gg0 ^ ((gg0 & 1) << 2);
-    va0 = lds0 + (unsigned)(rpart + ((c0 ^ f0) << 4));
-    va1 = lds0 + (unsigned)(rpart + (((c0 ^ f0) ^ 4) << 4));
-  }
+  lean_frag_addrs(aq, va0, va1, lds0, lane);
   const unsigned ast = lds0 + (unsigned)(2 * NS * IMG) + (unsigned)lh * 16u;
   if (ntiles > 0) {
     asm volatile("" ::"a"(kfv[0][0]), "a"(kfv[0][1]), "a"(kfv[0][2]), "a"(kfv[0][3]), "a"(vfv[0][0]), "a"(vfv[0][1]), "a"(vfv[0][2]), "a"(vfv[0][3]),
@@ -2430,24 +2299,14 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkdvw_asm_kernel(AttnArgs p) 
     f32x16 c0, c1, c2, c3, c4, c5;
     dkdvw_prefetch_asm(c0, c1, c2, c3, c4, c5, aq, ast);
     for (int t = 0; t < ntiles; t += 3) {
-      dkdvw_tile_asm_slot0(dk, dv, kfv, vfv, c0, c1, c2, c3, c4, c5, aq, va0, va1, ast, vo, q_base(t + 2), g_base(t + 2), s_base(t + 2), ldsw, ldss);
-      if (t + 1 < ntiles) dkdvw_tile_asm_slot1(dk, dv, kfv, vfv, c0, c1, c2, c3, c4, c5, aq, va0, va1, ast, vo, q_base(t + 3), g_base(t + 3), s_base(t + 3), ldsw, ldss);
-      if (t + 2 < ntiles) dkdvw_tile_asm_slot2(dk, dv, kfv, vfv, c0, c1, c2, c3, c4, c5, aq, va0, va1, ast, vo, q_base(t + 4), g_base(t + 4), s_base(t + 4), ldsw, ldss);
+      dkdvw_tile_asm_slot0(dk, dv, kfv, vfv, c0, c1, c2, c3, c4, c5, aq, va0, va1, ast, vo, qsrc.base(t + 2), gsrc.base(t + 2), ssrc.base(t + 2), ldsw, ldss);
+      if (t + 1 < ntiles) dkdvw_tile_asm_slot1(dk, dv, kfv, vfv, c0, c1, c2, c3, c4, c5, aq, va0, va1, ast, vo, qsrc.base(t + 3), gsrc.base(t + 3), ssrc.base(t + 3), ldsw, ldss);
+      if (t + 2 < ntiles) dkdvw_tile_asm_slot2(dk, dv, kfv, vfv, c0, c1, c2, c3, c4, c5, aq, va0, va1, ast, vo, qsrc.base(t + 4), gsrc.base(t + 4), ssrc.base(t + 4), ldsw, ldss);
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the (unused) requests past the last tile have landed before the workgroup ends
   }
-  asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");    // the stream's last MFMAs have retired before the compiler reads the accumulators
-  T* dKp = (T*)p.dK + (int64_t)b * p.k_bs + hd * D;
-  T* dVp = (T*)p.dV + (int64_t)b * p.v_bs + hd * D;
+  stream_drain();
 #pragma unroll
-  for (int kb = 0; kb < 2; ++kb) {
-    const int krow = krow0 + 32 * kb;
-    if (p.rope_table)
-      store_rows_T_rope<T, D>(dKp, p.k_rs, krow, true, dk[kb], LN2, lh, p.rope_table + (int64_t)b * p.rope_bs + (int64_t)(p.rope_off + krow) * D);
-    else
-      store_rows_T<T, D>(dKp, p.k_rs, krow, true, dk[kb], LN2, lh);
-    store_rows_T<T, D>(dVp, p.v_rs, krow, true, dv[kb], 1.0f, lh);
-  }
+  for (int kb = 0; kb < 2; ++kb) store_dk_dv(p, b, hd, krow0 + 32 * kb, true, dk[kb], dv[kb], lh);
 }
 #endif
 
@@ -2474,14 +2333,21 @@ template <typename K> void allow_lds(K kernel, size_t bytes) {
 #ifndef FK_DKDV_NW
 #define FK_DKDV_NW 4
 #endif
+// every tile of every workgroup fully visible and aligned (workgroups of `block` rows): what the generated instruction streams take
+bool fully_visible(const AttnArgs& a, int block) {
+  return a.q_off == 0 && a.k_off == 0 && (a.mask_kind == FK_MASK_NONE || (a.mask_kind == FK_MASK_BLOCK_CAUSAL && a.mask_c % block == 0));
+}
+// few queries, long context: the waves split the keys (attn_fwd_fewq_kernel, attn_bwd_dq_fewq_kernel)
+bool few_queries(const AttnArgs& a) {
+  static const bool no_fewq = getenv("FK_ATTN_NO_FEWQ") != nullptr;      // tuning knob
+  return !no_fewq && a.Nq <= 32 && a.Nk >= 1024 && a.mask_kind == FK_MASK_NONE && !a.drop_thresh;
+}
 template <typename T, int D> int launch_fwd(const AttnArgs& a, hipStream_t s) {
   constexpr int NW = Img<T, D>::SWZ ? 8 : 4;
   if constexpr (Img<T, D>::SWZ) {
     if (a.flags & FK_ATTN_Q_PRESCALED) {
 #ifndef FK_NO_FWD_ASM
-      // every tile of every workgroup fully visible and aligned -> the generated instruction streams
-      if (a.q_off == 0 && a.k_off == 0 && (a.mask_kind == FK_MASK_NONE || (a.mask_kind == FK_MASK_BLOCK_CAUSAL && a.mask_c % 128 == 0)) &&
-          a.Nq % 128 == 0 && a.Nk % 64 == 0) {
+      if (fully_visible(a, 128) && a.Nq % 128 == 0 && a.Nk % 64 == 0) {
         allow_lds(attn_fwd_asm_kernel, FWD_ASM_LDS);
         hipLaunchKernelGGL(attn_fwd_asm_kernel, dim3((unsigned)(a.Nq / 128 * a.H * a.B)), dim3(256), FWD_ASM_LDS, s, a);
         return 0;
@@ -2496,8 +2362,7 @@ template <typename T, int D> int launch_fwd(const AttnArgs& a, hipStream_t s) {
     }
   }
   if constexpr (Img<T, D>::SWZ) {
-    static const bool no_fewq = getenv("FK_ATTN_NO_FEWQ") != nullptr;      // tuning knob
-    if (!no_fewq && a.Nq <= 32 && a.Nk >= 1024 && a.mask_kind == FK_MASK_NONE && !a.drop_thresh) {   // few queries, long context: the waves split the keys
+    if (few_queries(a)) {
       allow_lds(attn_fwd_fewq_kernel, FEWQ_LDS);
       hipLaunchKernelGGL(attn_fwd_fewq_kernel, dim3((unsigned)(a.H * a.B)), dim3(FEWQ_NW * 64), FEWQ_LDS, s, a);
       return 0;
@@ -2520,18 +2385,12 @@ template <typename T, int D> int launch_bwd(const AttnArgs& a, hipStream_t s) {
     if (a.flags & FK_ATTN_Q_PRESCALED) {
       constexpr int NWQ = FK_DQ_NW, NWK = FK_DKDV_NW;
       dim3 gq2((unsigned)(((a.Nq + NWQ * 32 - 1) / (NWQ * 32)) * a.H * a.B)), gk2((unsigned)(((a.Nk + NWK * 32 - 1) / (NWK * 32)) * a.H * a.B));
-      // every tile of every workgroup fully visible and aligned -> the generated instruction streams
-      const bool vis_all = a.q_off == 0 && a.k_off == 0 && (a.mask_kind == FK_MASK_NONE || (a.mask_kind == FK_MASK_BLOCK_CAUSAL && a.mask_c % 128 == 0));
+      const bool vis_all = fully_visible(a, 128);
       bool dq_done = false;
 #ifndef FK_NO_DQ_ASM
       if (vis_all && a.Nq % 128 == 0 && a.Nk % 64 == 0) {
-#ifdef FK_DQ16_ASM
-        allow_lds(attn_bwd_dq16_asm_kernel, DQ_PS_LDS);
-        hipLaunchKernelGGL(attn_bwd_dq16_asm_kernel, dim3((unsigned)(a.Nq / 128 * a.H * a.B)), dim3(256), DQ_PS_LDS, s, a);
-#else
         allow_lds(attn_bwd_dq_asm_kernel, DQ_PS_LDS);
         hipLaunchKernelGGL(attn_bwd_dq_asm_kernel, dim3((unsigned)(a.Nq / 128 * a.H * a.B)), dim3(256), DQ_PS_LDS, s, a);
-#endif
         dq_done = true;
       }
 #endif
@@ -2541,8 +2400,7 @@ template <typename T, int D> int launch_bwd(const AttnArgs& a, hipStream_t s) {
       }
 #ifndef FK_NO_DKDVW_ASM
       static const bool no_wide = getenv("FK_ATTN_NO_DKDVW") != nullptr;    // tuning knob: the 32-keys-per-wave stream instead
-      const bool vis_256 = a.q_off == 0 && a.k_off == 0 && (a.mask_kind == FK_MASK_NONE || (a.mask_kind == FK_MASK_BLOCK_CAUSAL && a.mask_c % 256 == 0));
-      if (!no_wide && vis_256 && a.Nk % 256 == 0 && a.Nq % 64 == 0) {
+      if (!no_wide && fully_visible(a, 256) && a.Nk % 256 == 0 && a.Nq % 64 == 0) {
         allow_lds(attn_bwd_dkdvw_asm_kernel, DKDV_PS_LDS);
         hipLaunchKernelGGL(attn_bwd_dkdvw_asm_kernel, dim3((unsigned)(a.Nk / 256 * a.H * a.B)), dim3(256), DKDV_PS_LDS, s, a);
         return 0;
@@ -2562,9 +2420,8 @@ template <typename T, int D> int launch_bwd(const AttnArgs& a, hipStream_t s) {
   }
   bool dq_done = false;
   if constexpr (Img<T, D>::SWZ) {
-    static const bool no_fewq = getenv("FK_ATTN_NO_FEWQ") != nullptr;      // tuning knob
-    if (!no_fewq && a.Nq <= 32 && a.Nk >= 1024 && a.mask_kind == FK_MASK_NONE && !a.drop_thresh && !a.rope_table) {
-      allow_lds(attn_bwd_dq_fewq_kernel, FEWQ_LDS);                        // few queries, long context: the waves split the keys
+    if (few_queries(a) && !a.rope_table) {
+      allow_lds(attn_bwd_dq_fewq_kernel, FEWQ_LDS);
       hipLaunchKernelGGL(attn_bwd_dq_fewq_kernel, dim3((unsigned)(a.H * a.B)), dim3(FEWQ_NW * 64), FEWQ_LDS, s, a);
       dq_done = true;
     }
@@ -2595,6 +2452,26 @@ int check_common(const char* name, int64_t B, int64_t H, int64_t Nq, int64_t Nk,
                    "%s: bf16 D=64 path needs row strides < 2^24 elements and a head slab < 2^31 elements", name);
   }
   return FK_OK;
+}
+
+// the flag and the mask tables, for both entry points
+int check_flags_tables(const char* name, int64_t D, int dtype, int mask_kind, int64_t q_off, int64_t k_off, const int32_t* limits,
+                       const int32_t* qfirst, int flags) {
+  FK_CHECK_ARG((flags & ~FK_ATTN_Q_PRESCALED) == 0 && (!(flags & FK_ATTN_Q_PRESCALED) || (dtype == FK_BF16 && D == 64)),
+               "%s: bad flags %d (FK_ATTN_Q_PRESCALED needs bf16, D = 64)", name, flags);
+  FK_CHECK_ARG((mask_kind != FK_MASK_PREFIX && mask_kind != FK_MASK_KEYPAD) || (limits && qfirst), "%s: prefix / key-padding masks need both tables", name);
+  FK_CHECK_ARG(mask_kind != FK_MASK_DENSE || (limits && !(flags & FK_ATTN_Q_PRESCALED) && q_off >= 0 && q_off < (1LL << 31) && k_off == 0),
+               "%s: a dense mask needs its uint8 table in `limits`, its head stride (>= 0) in q_off, k_off = 0 and the generic kernels (no FK_ATTN_Q_PRESCALED)", name);
+  return FK_OK;
+}
+
+// the fields that forward and backward share (st: the eight strides in the order of the ABI)
+void fill_common(AttnArgs& a, const int64_t (&st)[8], int64_t B, int64_t H, int64_t Nq, int64_t Nk, int mask_kind, int64_t mask_c,
+                 int64_t q_off, int64_t k_off, const int32_t* limits, const int32_t* qfirst, float scale, int flags) {
+  a.q_bs = st[0]; a.q_rs = st[1]; a.k_bs = st[2]; a.k_rs = st[3]; a.v_bs = st[4]; a.v_rs = st[5]; a.o_bs = st[6]; a.o_rs = st[7];
+  a.B = (int)B; a.H = (int)H; a.Nq = (int)Nq; a.Nk = (int)Nk;
+  a.mask_kind = mask_kind; a.mask_c = (int)mask_c; a.q_off = (int)q_off; a.k_off = (int)k_off; a.scale = scale;
+  a.limits = limits; a.qfirst = qfirst; a.flags = flags;
 }
 
 int set_dropout(const char* name, AttnArgs& a, float drop_p, const uint32_t* drop_seed, uint32_t drop_site, int flags) {
@@ -2650,19 +2527,13 @@ int fk_attn_fwd_dropout(const void* Q, const void* K, const void* V, void* O, fl
   const int64_t st[8] = {q_bs, q_rs, k_bs, k_rs, v_bs, v_rs, o_bs, o_rs};
   int rc = check_common("fk_attn_fwd", B, H, Nq, Nk, D, dtype, mask_kind, mask_c, st, 8);
   if (rc) return rc;
-  FK_CHECK_ARG((flags & ~FK_ATTN_Q_PRESCALED) == 0 && (!(flags & FK_ATTN_Q_PRESCALED) || (dtype == FK_BF16 && D == 64)),
-               "fk_attn_fwd: bad flags %d (FK_ATTN_Q_PRESCALED needs bf16, D = 64)", flags);
+  rc = check_flags_tables("fk_attn_fwd", D, dtype, mask_kind, q_off, k_off, limits, qfirst, flags);
+  if (rc) return rc;
   FK_CHECK_ARG(Q && K && V && O, "fk_attn_fwd: null pointer");
   FK_CHECK_ARG((((uintptr_t)Q | (uintptr_t)K | (uintptr_t)V | (uintptr_t)O) & 15) == 0, "fk_attn_fwd: pointers must be 16-byte aligned");
   AttnArgs a{};
   a.Q = Q; a.K = K; a.V = V; a.Out = O; a.LSE = LSE;
-  a.q_bs = q_bs; a.q_rs = q_rs; a.k_bs = k_bs; a.k_rs = k_rs; a.v_bs = v_bs; a.v_rs = v_rs; a.o_bs = o_bs; a.o_rs = o_rs;
-  a.B = (int)B; a.H = (int)H; a.Nq = (int)Nq; a.Nk = (int)Nk;
-  a.mask_kind = mask_kind; a.mask_c = (int)mask_c; a.q_off = (int)q_off; a.k_off = (int)k_off; a.scale = scale;
-  FK_CHECK_ARG((mask_kind != FK_MASK_PREFIX && mask_kind != FK_MASK_KEYPAD) || (limits && qfirst), "fk_attn_fwd: prefix / key-padding masks need both tables");
-  FK_CHECK_ARG(mask_kind != FK_MASK_DENSE || (limits && !(flags & FK_ATTN_Q_PRESCALED) && q_off >= 0 && q_off < (1LL << 31) && k_off == 0),
-               "fk_attn_fwd: a dense mask needs its uint8 table in `limits`, its head stride (>= 0) in q_off, k_off = 0 and the generic kernels (no FK_ATTN_Q_PRESCALED)");
-  a.limits = limits; a.qfirst = qfirst; a.flags = flags;
+  fill_common(a, st, B, H, Nq, Nk, mask_kind, mask_c, q_off, k_off, limits, qfirst, scale, flags);
   rc = set_dropout("fk_attn_fwd", a, drop_p, drop_seed, drop_site, flags);
   if (rc) return rc;
   FK_ATTN_DISPATCH(launch_fwd, a, (hipStream_t)stream);
@@ -2687,23 +2558,17 @@ int fk_attn_bwd_dropout(const void* Q, const void* K, const void* V, const void*
   const int64_t st[8] = {q_bs, q_rs, k_bs, k_rs, v_bs, v_rs, o_bs, o_rs};
   int rc = check_common("fk_attn_bwd", B, H, Nq, Nk, D, dtype, mask_kind, mask_c, st, 8);
   if (rc) return rc;
-  FK_CHECK_ARG((flags & ~FK_ATTN_Q_PRESCALED) == 0 && (!(flags & FK_ATTN_Q_PRESCALED) || (dtype == FK_BF16 && D == 64)),
-               "fk_attn_bwd: bad flags %d (FK_ATTN_Q_PRESCALED needs bf16, D = 64)", flags);
+  rc = check_flags_tables("fk_attn_bwd", D, dtype, mask_kind, q_off, k_off, limits, qfirst, flags);
+  if (rc) return rc;
   FK_CHECK_ARG(Q && K && V && O && dO && LSE && dQ && dK && dV && delta_ws, "fk_attn_bwd: null pointer");
   FK_CHECK_ARG((((uintptr_t)Q | (uintptr_t)K | (uintptr_t)V | (uintptr_t)O | (uintptr_t)dO | (uintptr_t)dQ | (uintptr_t)dK | (uintptr_t)dV) & 15) == 0,
                "fk_attn_bwd: pointers must be 16-byte aligned");
   AttnArgs a{};
   a.Q = Q; a.K = K; a.V = V; a.O = O; a.dO = dO; a.LSE = const_cast<float*>(LSE); a.delta = delta_ws;
   a.dQ = dQ; a.dK = dK; a.dV = dV;
-  a.q_bs = q_bs; a.q_rs = q_rs; a.k_bs = k_bs; a.k_rs = k_rs; a.v_bs = v_bs; a.v_rs = v_rs; a.o_bs = o_bs; a.o_rs = o_rs;
-  a.B = (int)B; a.H = (int)H; a.Nq = (int)Nq; a.Nk = (int)Nk;
-  a.mask_kind = mask_kind; a.mask_c = (int)mask_c; a.q_off = (int)q_off; a.k_off = (int)k_off; a.scale = scale;
+  fill_common(a, st, B, H, Nq, Nk, mask_kind, mask_c, q_off, k_off, limits, qfirst, scale, flags);
   FK_CHECK_ARG(!rope_table || (Nq == Nk && D % 4 == 0 && ((uintptr_t)rope_table & 15) == 0), "fk_attn_bwd: fused inverse RoPE needs self-attention (Nq == Nk)");
   a.rope_table = rope_table; a.rope_bs = rope_bs; a.rope_off = (int)rope_off;
-  FK_CHECK_ARG((mask_kind != FK_MASK_PREFIX && mask_kind != FK_MASK_KEYPAD) || (limits && qfirst), "fk_attn_bwd: prefix / key-padding masks need both tables");
-  FK_CHECK_ARG(mask_kind != FK_MASK_DENSE || (limits && !(flags & FK_ATTN_Q_PRESCALED) && q_off >= 0 && q_off < (1LL << 31) && k_off == 0),
-               "fk_attn_bwd: a dense mask needs its uint8 table in `limits`, its head stride (>= 0) in q_off, k_off = 0 and the generic kernels (no FK_ATTN_Q_PRESCALED)");
-  a.limits = limits; a.qfirst = qfirst; a.flags = flags;
   rc = set_dropout("fk_attn_bwd", a, drop_p, drop_seed, drop_site, flags);
   if (rc) return rc;
   FK_ATTN_DISPATCH(launch_bwd, a, (hipStream_t)stream);

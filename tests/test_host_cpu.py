@@ -341,7 +341,7 @@ def test_bench_options():
     assert r.returncode == 2 and "--steps must be >= 1" in r.stderr
 
 
-STREAMS = {"dkdv": "attn_dkdv_asm.inc", "dq": "attn_dq_asm.inc", "fwd": "attn_fwd_asm.inc", "dq16": "attn_dq16_asm.inc", "dkdvw": "attn_dkdvw_asm.inc",
+STREAMS = {"dkdv": "attn_dkdv_asm.inc", "dq": "attn_dq_asm.inc", "fwd": "attn_fwd_asm.inc", "dkdvw": "attn_dkdvw_asm.inc",
            "mlpb": "mlp_bwd_asm.inc"}
 
 
