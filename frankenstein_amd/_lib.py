@@ -18,6 +18,8 @@ MASK_NONE, MASK_CAUSAL, MASK_BLOCK_CAUSAL, MASK_PREFIX, MASK_KEYPAD, MASK_DENSE 
 NORM_LAYER, NORM_RMS = 0, 1
 ATTN_Q_PRESCALED = 1
 GEMV_GELU = 1
+NT_RING2, NT_RING192, NT_RING128, NT_BIG, NT_GLDS4, NT_GLDS, NT_STAGED = range(7)     # fk_gemm_nt_route
+NT_ROUTE_F32 = -2
 
 _p, _i64, _int, _f32, _f64, _sz, _u32 = C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_double, C.c_size_t, C.c_uint32
 
@@ -31,6 +33,8 @@ SIGNATURES = {
     "fk_gemm_nt_swiglu": (_int, [_p, _i64, _p, _i64, _p, _i64, _p, _i64, _i64, _i64, _i64, _int, _p]),
     "fk_gemm_nt_dswiglu": (_int, [_p, _i64, _p, _i64, _p, _i64, _p, _i64, _i64, _i64, _i64, _int, _p]),
     "fk_mlp_bwd_fused": (_int, [_p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _i64, _i64, _i64, _int, _p]),
+    "fk_gemm_nt_route": (_int, [_i64, _i64, _i64, _int, _int, _int, _int]),
+    "fk_gemm_tn_route": (_int, [_i64, _i64, _i64, _int, _p, _p]),
     "fk_gemm_tn_workspace_bytes": (_sz, [_i64, _i64, _i64, _int]),
     "fk_gemm_tn": (_int, [_p, _i64, _p, _i64, _p, _i64, _i64, _i64, _i64, _int, _int, _p, _sz, _p]),
     "fk_colsum_workspace_bytes": (_sz, [_i64, _i64]),

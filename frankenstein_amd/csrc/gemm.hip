@@ -1561,6 +1561,30 @@ extern "C" {
 
 struct RopeSpec { const float* table; int64_t bs; int T, off, D, cols; int qcols; int64_t qoff; };
 
+// The kernel launch_nt runs for a bf16-operand problem (fp32 operands always take the register-staged kernel); fk_gemm_nt_route
+// answers with the same function, so the tests can say which kernel a shape reaches.
+static NtRoute nt_route(int64_t M, int64_t N, int64_t K, int dtype, bool vec_epi, int mode, bool has_rope) {
+  const int64_t nwg = fk_cdiv(M, BM) * fk_cdiv(N, BN);
+  const bool glds = dtype == FK_BF16 && (K % 64 == 0);
+  static const bool no_ring = getenv("FK_NT_NO_RING") != nullptr;       // tuning knob: the double-buffered kernels instead
+  // the persistent ring kernels want several 256-row tiles per CU; below half a tile per CU (SimpleMAE's 4800 visible-token rows at
+  // B = 32) the 128 x 128 kernels fill the chip better: graphed cfg5 step 5.9 -> 5.6 ms (profiles/r03_g_other_configs.txt)
+  // (read per call, not cached: the GPU suite switches it to send small shapes through the ring kernels)
+  const char* ring_min_env = getenv("FK_NT_RING_MIN_TILES");
+  const int ring_min = ring_min_env ? atoi(ring_min_env) : 128;
+  const bool wide = glds && M >= 4096 && vec_epi && !no_ring && fk_cdiv(M, 256) * fk_cdiv(N, 256) >= ring_min;
+  // 256 x 256 tiles, split A/B rings (N = 1152: the last column tile is half empty, still 4 % faster than 256 x 128 tiles)
+  if (wide && (N % 256 == 0 || (N % 128 == 0 && N >= 1024))) return NT_RING2;
+  static const bool no_192 = getenv("FK_NT_NO_192") != nullptr;        // tuning knob: 256 x 128 tiles for N = 384 / 768 too
+  if (wide && N % 192 == 0 && N % 256 != 0 && N <= 768 && mode == 0 && !has_rope && !no_192) return NT_RING192;   // N = 384: two 192-column tiles
+  if (wide && N % 128 == 0) return NT_RING128;           // N = 128 / 384 / 640 / 896: 256 x 128 ring
+  // large projections: 256 x 256 tiles, 1 block per CU (the 256x128 variant measured slower than 128x128 at N = 384)
+  if (glds && M >= 4096 && N % 256 == 0 && vec_epi) return NT_BIG;
+  static const bool no_g4 = getenv("FK_NT_NO_GLDS4") != nullptr;       // tuning knob
+  if (glds && nwg <= 256 && !no_g4) return NT_GLDS4;     // at most one tile per CU: the short-latency ring
+  return glds ? NT_GLDS : NT_STAGED;
+}
+
 static int launch_nt(const char* name, const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc, int64_t M,
                      int64_t N, int64_t K, const void* bias, const void* residual, int64_t ldr, int64_t res_rows, int dtype,
                      int out_dtype, int mode, void* aux, int64_t ldaux, void* stream, RopeSpec rope = RopeSpec{nullptr, 0, 1, 0, 2, 0, 0, 0}) {
@@ -1591,26 +1615,7 @@ static int launch_nt(const char* name, const void* A, int64_t lda, const void* B
            rope.table, rope.bs, rope.T, rope.off, rope.D, rope.cols, rope.qcols, rope.qoff};
   const int64_t nwg = fk_cdiv(M, BM) * fk_cdiv(N, BN);
   hipStream_t s = (hipStream_t)stream;
-  const bool glds = dtype == FK_BF16 && (K % 64 == 0);
-  static const bool no_ring = getenv("FK_NT_NO_RING") != nullptr;       // tuning knob: the double-buffered kernels instead
-  // the persistent ring kernels want several 256-row tiles per CU; below half a tile per CU (SimpleMAE's 4800 visible-token rows at
-  // B = 32) the 128 x 128 kernels fill the chip better: graphed cfg5 step 5.9 -> 5.6 ms (profiles/r03_g_other_configs.txt)
-  // (read per call, not cached: the GPU suite switches it to send small shapes through the ring kernels)
-  const char* ring_min_env = getenv("FK_NT_RING_MIN_TILES");
-  const int ring_min = ring_min_env ? atoi(ring_min_env) : 128;
-  const bool wide = glds && M >= 4096 && vec_epi && !no_ring && fk_cdiv(M, 256) * fk_cdiv(N, 256) >= ring_min;
-  const NtRoute route = [&] {
-    // 256 x 256 tiles, split A/B rings (N = 1152: the last column tile is half empty, still 4 % faster than 256 x 128 tiles)
-    if (wide && (N % 256 == 0 || (N % 128 == 0 && N >= 1024))) return NT_RING2;
-    static const bool no_192 = getenv("FK_NT_NO_192") != nullptr;        // tuning knob: 256 x 128 tiles for N = 384 / 768 too
-    if (wide && N % 192 == 0 && N % 256 != 0 && N <= 768 && mode == 0 && !rope.table && !no_192) return NT_RING192;   // N = 384: two 192-column tiles
-    if (wide && N % 128 == 0) return NT_RING128;           // N = 128 / 384 / 640 / 896: 256 x 128 ring
-    // large projections: 256 x 256 tiles, 1 block per CU (the 256x128 variant measured slower than 128x128 at N = 384)
-    if (glds && M >= 4096 && N % 256 == 0 && vec_epi) return NT_BIG;
-    static const bool no_g4 = getenv("FK_NT_NO_GLDS4") != nullptr;       // tuning knob
-    if (glds && nwg <= 256 && !no_g4) return NT_GLDS4;     // at most one tile per CU: the short-latency ring
-    return glds ? NT_GLDS : NT_STAGED;
-  }();
+  const NtRoute route = nt_route(M, N, K, dtype, vec_epi, mode, rope.table != nullptr);
   if (dtype == FK_F32)                                     // fp32 operands: the register-staged kernel only (route == NT_STAGED)
     hipLaunchKernelGGL((gemm_nt_kernel<float, float>), dim3((unsigned)nwg), dim3(NTHREADS), 4 * TILE_BYTES, s, p);
   else if (out_dtype == FK_BF16) launch_nt_route<bf16_t>(route, p, M, N, s);
@@ -1655,30 +1660,55 @@ int fk_gemm_nt_dswiglu(const void* dY, int64_t lda, const void* W2T, int64_t ldb
                    const_cast<void*>(H13), ldh, stream);
 }
 
+int fk_gemm_nt_route(int64_t M, int64_t N, int64_t K, int dtype, int vec_epi, int mode, int has_rope) {
+  FK_CHECK_ARG(dtype == FK_F32 || dtype == FK_BF16, "fk_gemm_nt_route: bad dtype %d", dtype);
+  FK_CHECK_ARG(M > 0 && N > 0 && K > 0 && mode >= 0 && mode <= 2, "fk_gemm_nt_route: bad problem M=%lld N=%lld K=%lld mode=%d", (long long)M, (long long)N, (long long)K, mode);
+  if (dtype == FK_F32) return FK_NT_ROUTE_F32;
+  return (int)nt_route(M, N, K, dtype, vec_epi != 0, mode, has_rope != 0);
+}
+
+// what fk_gemm_tn does with a shape: the kernel (tile columns of the large-tile kernel, 0 = the small one), the number of split slabs and
+// the rows of a split
+static int tn_plan(int64_t M, int64_t N1, int64_t N2, int dtype, int* nsplit, int64_t* rows_per_split) {
+  const bool big = tn_big_ok(M, N1, N2, dtype);
+  const int bkm = dtype == FK_BF16 ? 64 : 32;
+  const int ns = big ? tn_big_splits(M, N1, N2) : tn_splits(M, N1, N2, bkm);
+  if (nsplit) *nsplit = ns;
+  if (rows_per_split) *rows_per_split = fk_cdiv(fk_cdiv(M, ns), bkm) * bkm;
+  return big ? tn_big_tb(N1, N2) : 0;
+}
+
+int fk_gemm_tn_route(int64_t M, int64_t N1, int64_t N2, int dtype, int* nsplit, int64_t* rows_per_split) {
+  FK_CHECK_ARG(dtype == FK_F32 || dtype == FK_BF16, "fk_gemm_tn_route: bad dtype %d", dtype);
+  FK_CHECK_ARG(M > 0 && N1 > 0 && N2 > 0, "fk_gemm_tn_route: empty problem");
+  return tn_plan(M, N1, N2, dtype, nsplit, rows_per_split);
+}
+
 size_t fk_gemm_tn_workspace_bytes(int64_t M, int64_t N1, int64_t N2, int dtype) {
-  const int ns = tn_big_ok(M, N1, N2, dtype) ? tn_big_splits(M, N1, N2) : tn_splits(M, N1, N2, dtype == FK_BF16 ? 64 : 32);
+  int ns;
+  tn_plan(M, N1, N2, dtype, &ns, nullptr);
   return ns > 1 ? (size_t)ns * N1 * N2 * sizeof(float) : 0;
 }
 
 int fk_gemm_tn(const void* A, int64_t lda, const void* B, int64_t ldb, float* C, int64_t ldc, int64_t M, int64_t N1,
                int64_t N2, int accumulate, int dtype, void* workspace, size_t workspace_bytes, void* stream) {
   FK_CHECK_ARG(dtype == FK_F32 || dtype == FK_BF16, "fk_gemm_tn: bad dtype %d", dtype);
-  const int vec = dtype == FK_BF16 ? 8 : 4, bkm = dtype == FK_BF16 ? 64 : 32;
+  const int vec = dtype == FK_BF16 ? 8 : 4;
   FK_CHECK_ARG(M > 0 && N1 > 0 && N2 > 0, "fk_gemm_tn: empty problem");
   FK_CHECK_ARG(M < (1LL << 31) && N1 < (1LL << 31) && N2 < (1LL << 31), "fk_gemm_tn: dims must fit int32");
   FK_CHECK_ARG(N1 % vec == 0 && N2 % vec == 0 && lda % vec == 0 && ldb % vec == 0,
                "fk_gemm_tn: N1/N2/lda/ldb must be multiples of %d (N1=%lld N2=%lld)", vec, (long long)N1, (long long)N2);
   FK_CHECK_ARG(((uintptr_t)A & 15) == 0 && ((uintptr_t)B & 15) == 0, "fk_gemm_tn: A/B must be 16-byte aligned");
-  const bool big = tn_big_ok(M, N1, N2, dtype);
-  const int ns = big ? tn_big_splits(M, N1, N2) : tn_splits(M, N1, N2, bkm);
+  int ns;
+  int64_t rps;
+  const int tb = tn_plan(M, N1, N2, dtype, &ns, &rps);
+  const bool big = tb != 0;
   const size_t need = ns > 1 ? (size_t)ns * N1 * N2 * sizeof(float) : 0;
   FK_CHECK_ARG(workspace_bytes >= need && (need == 0 || workspace), "fk_gemm_tn: workspace too small (%zu < %zu)", workspace_bytes, need);
-  int64_t rps = fk_cdiv(fk_cdiv(M, ns), bkm) * bkm;
   TnArgs p{A, B, C, (float*)workspace, lda, ldb, ldc, (int)M, (int)N1, (int)N2, (int)rps, ns, accumulate};
   dim3 grid((unsigned)(fk_cdiv(N1, BM) * fk_cdiv(N2, BN) * ns)), block(NTHREADS);
   hipStream_t s = (hipStream_t)stream;
   if (big) {
-    const int tb = tn_big_tb(N1, N2);
     dim3 bgrid((unsigned)((N1 / TG_A) * (N2 / tb) * ns));
     if (tb == 192) {
       constexpr int LDS192 = TG_NS * (TG_A_BYTES + TG_K * 512);

@@ -195,6 +195,35 @@ def mlp_bwd_fused(dy: Tensor, w2t: Tensor, h13: Tensor, w13t: Tensor) -> Tuple[T
     return dh13, dx
 
 
+# the kernels fk_gemm_nt and its fused forms choose between (fk_gemm_nt_route); NT_ROUTE_F32: fp32 operands, the staged fp32 kernel
+NT_RING2, NT_RING192, NT_RING128, NT_BIG, NT_GLDS4, NT_GLDS, NT_STAGED = _lib.NT_RING2, _lib.NT_RING192, _lib.NT_RING128, _lib.NT_BIG, _lib.NT_GLDS4, _lib.NT_GLDS, _lib.NT_STAGED
+NT_ROUTE_F32 = _lib.NT_ROUTE_F32
+NT_ROUTE_NAMES = {NT_RING2: "NT_RING2", NT_RING192: "NT_RING192", NT_RING128: "NT_RING128", NT_BIG: "NT_BIG", NT_GLDS4: "NT_GLDS4",
+                  NT_GLDS: "NT_GLDS", NT_STAGED: "NT_STAGED", NT_ROUTE_F32: "NT_STAGED_F32"}
+TN_SMALL, TN_BIG128, TN_BIG192 = 0, 128, 192               # fk_gemm_tn_route
+
+
+def gemm_nt_route(M: int, N: int, K: int, dtype=torch.bfloat16, vec_epi: bool = True, mode: int = 0, has_rope: bool = False) -> int:
+    """The kernel gemm_nt (mode 0), gemm_nt_swiglu (mode 1, N = 2H), gemm_nt_dswiglu (mode 2, N = H) or gemm_nt_rope (has_rope) runs for
+    this problem: one of the NT_* constants (host-side query, no launch).  vec_epi: N and the output / residual strides are multiples of
+    8 and their pointers 16-byte aligned."""
+    r = lib().fk_gemm_nt_route(M, N, K, fk_dtype(dtype), int(vec_epi), mode, int(has_rope))
+    if r == -1:
+        _lib.check(r, "fk_gemm_nt_route")
+    return r
+
+
+def gemm_tn_route(M: int, N1: int, N2: int, dtype=torch.bfloat16) -> Tuple[int, int, int]:
+    """(kernel, nsplit, rows_per_split) of gemm_tn for this shape: kernel is TN_SMALL, TN_BIG128 or TN_BIG192; split s sums rows
+    [s * rows_per_split, min(M, (s + 1) * rows_per_split))."""
+    import ctypes
+    ns, rps = ctypes.c_int(0), ctypes.c_int64(0)
+    r = lib().fk_gemm_tn_route(M, N1, N2, fk_dtype(dtype), ctypes.byref(ns), ctypes.byref(rps))
+    if r < 0:
+        _lib.check(r, "fk_gemm_tn_route")
+    return r, ns.value, rps.value
+
+
 def gemm_tn(a: Tensor, b: Tensor, out: Optional[Tensor] = None, accumulate: bool = False) -> Tensor:
     """out[N1,N2] (fp32) (+)= a[M,N1]^T @ b[M,N2]."""
     assert a.dim() == 2 and b.dim() == 2 and a.shape[0] == b.shape[0] and a.dtype == b.dtype

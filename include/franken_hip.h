@@ -94,11 +94,24 @@ int fk_gemm_nt_dswiglu(const void* dY, int64_t lda, const void* W2T, int64_t ldb
 int fk_mlp_bwd_fused(const void* dY, int64_t lddy, const void* W2T, int64_t ldw2t, const void* H13, int64_t ldh, const void* W13T,
                      int64_t ldw13t, void* dH13, int64_t lddh, void* dX, int64_t lddx, int64_t M, int64_t H, int64_t D, int dtype,
                      void* stream);
+/* fk_gemm_nt_route: which kernel fk_gemm_nt and its fused forms run for a problem (host only, nothing is launched): one of the
+ *   FK_NT_* values below for bf16 operands, FK_NT_ROUTE_F32 for fp32 operands (always the register-staged kernel).  vec_epi: N, ldc
+ *   (and ldr) are multiples of 8 and C (and the residual) 16-byte aligned; mode: 0 plain / bias / residual / RoPE, 1 fk_gemm_nt_swiglu
+ *   (N = 2H), 2 fk_gemm_nt_dswiglu (N = H); has_rope: fk_gemm_nt_rope.  The token-on-the-lane kernels that fk_gemm_nt_rope and
+ *   fk_gemm_nt_swiglu put in front at K = 384 from 45 825 rows on are not part of the answer.  Follows the FK_NT_* environment knobs
+ *   exactly as the launch does.                                                                                                    */
+enum { FK_NT_RING2 = 0, FK_NT_RING192 = 1, FK_NT_RING128 = 2, FK_NT_BIG = 3, FK_NT_GLDS4 = 4, FK_NT_GLDS = 5, FK_NT_STAGED = 6 };
+#define FK_NT_ROUTE_F32 (-2)
+int fk_gemm_nt_route(int64_t M, int64_t N, int64_t K, int dtype, int vec_epi, int mode, int has_rope);
 /* fk_gemm_tn: C[N1,N2] (fp32) (+)= sum_m A[m,N1] * B[m,N2]  — the weight gradient dW = dY^T X of a Linear
  *   (autograd of the call sites above).  Split over m with deterministic slab reduction.                     */
 size_t fk_gemm_tn_workspace_bytes(int64_t M, int64_t N1, int64_t N2, int dtype);
 int fk_gemm_tn(const void* A, int64_t lda, const void* B, int64_t ldb, float* C, int64_t ldc, int64_t M, int64_t N1,
                int64_t N2, int accumulate, int dtype, void* workspace, size_t workspace_bytes, void* stream);
+/* fk_gemm_tn_route: what fk_gemm_tn does with a shape (host only): returns 0 for the 128 x 128 kernel, 128 or 192 for the large-tile
+ *   kernel (its B columns per tile); *nsplit = the number of row splits (slabs summed in order when > 1), *rows_per_split = the rows
+ *   of a split: split s covers rows [s * rows_per_split, min(M, (s + 1) * rows_per_split)), which may be empty.  Either may be NULL. */
+int fk_gemm_tn_route(int64_t M, int64_t N1, int64_t N2, int dtype, int* nsplit, int64_t* rows_per_split);
 /* fk_colsum: out[c] (+)= sum_r X[r,c]  (bias / space-embedding gradients).                                   */
 size_t fk_colsum_workspace_bytes(int64_t rows, int64_t cols);
 int fk_colsum(const void* X, int64_t ld, float* out, int64_t rows, int64_t cols, int accumulate, int dtype,

@@ -150,3 +150,98 @@ def train_accum(n_items: int = 10):
     xs = t(synth.make_inputs(n_items, 32, 16, seed=synth.SEED_INPUT + 17))
     ys = t(synth.make_motion_targets(n_items, 8, 12, seed=synth.SEED_INPUT + 18))
     return cfg, xs, ys
+
+
+# ------------------------------------------------------------------------------------------------ GEMM routes
+# The shapes of tests/test_gemm_routes_gpu.py, shared with tests/test_gemm_routes_cpu.py, which pins the kernel each of them reaches
+# (kernels.gemm_nt_route / gemm_tn_route).  Routes are named as in csrc/gemm.hip's NtRoute; "F32" = fp32 operands, the staged fp32 kernel.
+# ring_min: the FK_NT_RING_MIN_TILES the case runs under ("0": every M >= 4096 shape is sent to the ring kernels; None: the default of 128
+# tiles of 256 rows).  Rows are 4096 .. 8300 on the ring / NT_BIG routes and at most ~3100 elsewhere, every last row tile is ragged.
+
+# plain / bias / residual / periodic residual: (route, M, N, K, ring_min)
+NT_PLAIN_CASES = [
+    ("NT_RING2", 4168, 256, 64, "0"),            # one k-stage
+    ("NT_RING2", 8300, 1152, 384, None),         # default threshold (33 x 5 tiles), 6 stages, half-empty last column tile
+    ("NT_RING192", 4168, 384, 64, "0"),
+    ("NT_RING192", 4300, 576, 384, "0"),            # three 192-column tiles (N = 768 is NT_RING2's)
+    ("NT_RING192", 4104, 192, 128, "0"),         # a single 192-column tile
+    ("NT_RING128", 4168, 128, 64, "0"),
+    ("NT_RING128", 4104, 640, 320, "0"),
+    ("NT_RING128", 8300, 896, 192, None),        # default threshold (33 x 4 tiles of 256)
+    ("NT_BIG", 4096 + 72, 256, 64, None),
+    ("NT_BIG", 4096 + 72, 512, 384, None),
+    ("NT_GLDS4", 300, 200, 64, None),
+    ("NT_GLDS4", 1000, 1000, 128, None),
+    ("NT_GLDS4", 700, 333, 192, None),           # N % 8 != 0: scalar sweep
+    ("NT_GLDS", 2950, 1416, 64, None),           # 24 x 12 = 288 tiles (one per workgroup), N % 128 != 0, N % 8 == 0
+    ("NT_GLDS", 2821, 3080, 128, None),          # 23 x 25 = 575 tiles on 512 workgroups: 1 or 2 tiles each, 8 does not divide the count
+    ("NT_GLDS", 2950, 1413, 64, None),           # scalar sweep, clamped B rows in the last column tile
+    ("NT_GLDS", 2821, 3077, 192, None),          # scalar sweep over the multi-tile loop
+    ("NT_GLDS", 3100, 5760, 128, None),          # 25 x 45 = 1125 tiles: up to 3 per workgroup
+    ("NT_STAGED", 300, 200, 8, None),
+    ("NT_STAGED", 1000, 333, 72, None),
+    ("NT_STAGED", 700, 520, 200, None),
+    ("F32", 300, 200, 4, None),
+    ("F32", 700, 333, 36, None),
+    ("F32", 1000, 520, 100, None),
+]
+
+# SwiGLU forward (N = 2H columns): (route, M, H, K, ring_min)
+NT_SWIGLU_CASES = [
+    ("NT_RING2", 4168, 128, 128, "0"),
+    ("NT_RING2", 4200, 576, 64, "0"),            # N = 1152
+    ("NT_RING128", 4168, 192, 64, "0"),          # N = 384: the fused modes are kept off the 192-column tiles
+    ("NT_BIG", 4168, 128, 64, None),
+    ("NT_GLDS", 2950, 712, 64, None),            # N = 1424: 24 x 12 = 288 tiles
+    ("NT_GLDS4", 300, 96, 64, None),
+    ("NT_STAGED", 300, 96, 72, None),
+    ("F32", 300, 96, 36, None),
+]
+
+# SwiGLU backward (N = H accumulator columns, 2H columns of h13 / dh13): (route, M, H, K, ring_min)
+NT_DSWIGLU_CASES = [
+    ("NT_RING2", 4168, 256, 64, "0"),
+    ("NT_RING128", 4168, 384, 128, "0"),
+    ("NT_RING128", 4200, 128, 384, "0"),
+    ("NT_BIG", 4168, 256, 128, None),
+    ("NT_GLDS", 2950, 1416, 64, None),
+    ("NT_GLDS4", 300, 96, 64, None),
+    ("NT_STAGED", 300, 96, 72, None),
+    ("F32", 300, 96, 36, None),
+]
+
+# RoPE: (route, B, T, N, K, D, rot_cols, pos_off, q_cols, bias, per_sample_table, ring_min); M = B * T.  T = 5 (the table wrap runs more
+# than once per 8-row step), 57 (not a multiple of 8) and 300 (more than a row tile); q_cols > 0: those columns use the pre-scaled table
+NT_ROPE_CASES = [
+    ("NT_RING2", 821, 5, 256, 64, 8, 256, 3, 0, True, True, "0"),
+    ("NT_RING2", 14, 300, 512, 128, 128, 256, 0, 128, False, False, "0"),
+    ("NT_RING2", 73, 57, 1152, 64, 64, 768, 7, 384, False, True, "0"),
+    ("NT_RING128", 73, 57, 384, 64, 64, 256, 2, 128, True, True, "0"),
+    ("NT_RING128", 821, 5, 128, 384, 16, 128, 0, 0, False, False, "0"),
+    ("NT_RING128", 14, 300, 384, 128, 8, 384, 11, 0, False, True, "0"),
+    ("NT_BIG", 73, 57, 256, 64, 16, 192, 5, 64, True, True, None),
+    ("NT_BIG", 14, 300, 512, 64, 64, 512, 0, 0, False, False, None),
+    ("NT_BIG", 821, 5, 256, 128, 128, 128, 1, 0, False, True, None),
+    ("NT_GLDS", 10, 300, 1416, 64, 8, 1408, 4, 0, True, True, None),
+    ("NT_GLDS", 590, 5, 1416, 64, 64, 1408, 0, 704, False, False, None),
+    ("NT_GLDS", 50, 57, 1416, 128, 16, 1416 - 8, 9, 0, False, True, None),
+    ("NT_GLDS4", 4, 57, 200, 64, 8, 200, 6, 0, False, True, None),
+    ("NT_GLDS4", 60, 5, 384, 128, 128, 256, 2, 128, True, True, None),
+    ("NT_GLDS4", 3, 300, 192, 64, 64, 128, 0, 0, False, False, None),
+    ("NT_STAGED", 4, 57, 192, 72, 16, 128, 3, 64, True, True, None),
+    ("NT_STAGED", 60, 5, 256, 200, 128, 256, 0, 0, False, False, None),
+    ("F32", 60, 5, 192, 36, 64, 192, 1, 64, True, True, None),
+    ("F32", 2, 300, 128, 100, 8, 96, 0, 0, False, False, None),
+    ("F32", 4, 57, 256, 36, 128, 256, 4, 0, False, True, None),
+]
+
+# fk_gemm_tn: (kernel, dtype, M, N1, N2, nsplit, rows_per_split); kernel 0 = the 128 x 128 kernel, 128 / 192 = the large-tile kernel
+TN_CASES = [
+    (0, "bf16", 200, 136, 72, 1, 256),           # nsplit == 1: the kernel writes / accumulates into C itself
+    (0, "f32", 100, 136, 72, 1, 128),
+    (0, "bf16", 1000, 136, 72, 4, 256),
+    (0, "f32", 1000, 136, 72, 8, 128),
+    (0, "bf16", 4163, 904, 1000, 16, 320),       # splits 0 .. 12 full, split 13 has 3 rows, splits 14 and 15 start past M
+    (0, "f32", 2083, 904, 1000, 16, 160),        # the same in fp32: split 13 has 3 rows, 14 and 15 are empty
+    (128, "bf16", 16384, 384, 128, 32, 512),
+]

@@ -55,6 +55,7 @@ def test_gemm_nt_exact_integers(K, dtype):
     a = torch.randint(-3, 4, (M, Kd), generator=torch.Generator().manual_seed(1)).float()
     w = torch.randint(-3, 4, (N, Kd), generator=torch.Generator().manual_seed(2)).float()
     w[:, 0] += torch.arange(N) % 5
+    assert nt_route(K, M, N, Kd, dtype) == ("NT_STAGED" if dtype == torch.bfloat16 else "NT_STAGED_F32")      # K = 72: no LDS-DMA kernel
     got = K.gemm_nt(dev(a, dtype), dev(w, dtype), out_dtype=torch.float32)
     assert torch.equal(got.cpu(), a @ w.t())
 
@@ -63,6 +64,8 @@ def test_gemm_nt_exact_integers(K, dtype):
 @pytest.mark.parametrize("shape", [(300, 200, 64), (128, 128, 384), (1000, 1003, 128), (64, 32, 32), (777, 384, 1536)])
 def test_gemm_nt(K, dtype, shape):
     M, N, Kd = shape
+    want = "NT_STAGED_F32" if dtype == torch.float32 else ("NT_STAGED" if Kd % 64 else "NT_GLDS4")          # all of them at most 64 tiles
+    assert nt_route(K, M, N, Kd, dtype, vec_epi=N % 8 == 0) == want
     a, w = rnd(M, Kd, seed=1), rnd(N, Kd, seed=2, scale=1 / math.sqrt(Kd))
     bias, res = rnd(N, seed=3), rnd(M, N, seed=4)
     ref = q(a, dtype) @ q(w, dtype).t()
@@ -136,6 +139,17 @@ RING_SHAPES = [(4096, 384, 64), (4168, 128, 128), (8200, 1152, 384), (4104, 256,
                (4096, 512, 128), (33000, 768, 64),
                # long K, N = 384 class: the kernel with split request waves and the 4-slot A ring (one / several tiles per block, ragged rows)
                (4224, 384, 1536), (8200, 128, 1024), (70000, 384, 1088), (4096, 640, 3072)]
+# the kernel each of them reaches (kernels.gemm_nt_route; tests/test_gemm_routes_cpu.py pins the table): with FK_NT_RING_MIN_TILES=0 and
+# under the default threshold of 128 tiles of 256 rows, where the small grids take NT_BIG or the 128 x 128 short-latency kernel
+RING_ROUTES = {"ring": ["NT_RING192", "NT_RING128", "NT_RING2", "NT_RING2", "NT_RING2", "NT_RING192", "NT_RING2", "NT_RING2",
+                        "NT_RING192", "NT_RING128", "NT_RING192", "NT_RING128"],
+               "default": ["NT_GLDS4", "NT_GLDS4", "NT_RING2", "NT_BIG", "NT_RING2", "NT_RING192", "NT_BIG", "NT_RING2",
+                           "NT_GLDS4", "NT_GLDS4", "NT_RING192", "NT_GLDS4"]}
+
+
+def nt_route(K, M, N, Kd, dtype=torch.bfloat16, vec_epi=True, mode=0, has_rope=False):
+    """name of the kernel a gemm_nt / gemm_nt_swiglu (mode 1, N = 2H) / gemm_nt_dswiglu (mode 2) / gemm_nt_rope call reaches right now"""
+    return K.NT_ROUTE_NAMES[K.gemm_nt_route(M, N, Kd, dtype, vec_epi, mode, has_rope)]
 
 
 @pytest.mark.parametrize("routing", ["ring", "default"])
@@ -151,6 +165,7 @@ def test_gemm_nt_ring_kernels_exact_integers(K, shape, routing, monkeypatch):
     else:
         monkeypatch.delenv("FK_NT_RING_MIN_TILES", raising=False)
     M, N, Kd = shape
+    assert nt_route(K, M, N, Kd) == RING_ROUTES[routing][RING_SHAPES.index(shape)]
     g = torch.Generator().manual_seed(7)
     a = torch.randint(-2, 3, (M, Kd + 8), generator=g).float()
     w = torch.randint(-2, 3, (N, Kd), generator=g).float()
@@ -176,6 +191,7 @@ def test_gemm_nt_ring_fused_epilogues_match_small_kernel(K, monkeypatch):
     monkeypatch.setenv("FK_NT_RING_MIN_TILES", "0")            # these grids are under the default threshold of the ring kernels
     M, d, H = 4096 + 520, 128, 256
     x, w13 = dev(rnd(M, d, seed=1), torch.bfloat16), dev(rnd(2 * H, d, seed=2, scale=0.2), torch.bfloat16)
+    assert nt_route(K, M, 2 * H, d, mode=1) == "NT_RING2" and nt_route(K, 2000, 2 * H, d, mode=1) == nt_route(K, M - 4000, 2 * H, d, mode=1) == "NT_GLDS4"
     h13, gq = K.gemm_nt_swiglu(x, w13)
     for lo in range(0, M, 2000):
         h, g2 = K.gemm_nt_swiglu(x[lo:lo + 2000], w13)
@@ -184,6 +200,7 @@ def test_gemm_nt_ring_fused_epilogues_match_small_kernel(K, monkeypatch):
     ang = R.rope_angles(D, 640, 10000.0)
     table = dev(torch.stack([torch.cos(ang), torch.sin(ang)], -1).contiguous())
     xq, wq = dev(rnd(8 * T, d, seed=3), torch.bfloat16), dev(rnd(3 * Hh * D, d, seed=4, scale=0.2), torch.bfloat16)
+    assert nt_route(K, 8 * T, 3 * Hh * D, d, has_rope=True) == "NT_RING128" and nt_route(K, 4 * T, 3 * Hh * D, d, has_rope=True) == "NT_GLDS4"
     full = K.gemm_nt_rope(xq, wq, None, table, T, 10, D, 2 * Hh * D)
     for b in range(0, 8, 4):
         part = K.gemm_nt_rope(xq[b * T:(b + 4) * T], wq, None, table, T, 10, D, 2 * Hh * D)
@@ -704,35 +721,62 @@ DENSE_CASES = [
 ]
 
 
-@pytest.mark.parametrize("case", [(12, 4096, 6, True), (49, 1000, 3, False), (13, 4096, 2, True)])
+@pytest.mark.parametrize("case", [(12, 4096, 6, True), (49, 1000, 3, False), (13, 4096, 2, True), (47, 975, 3, True, "per-sample"), (47, 975, 6, False, "per-sample")])
 def test_qkv_projection_with_rope_token_on_the_lane_equals_the_tiled_kernel_bit_for_bit(K, case):
     """fk_gemm_nt_rope routes wide bf16 projections at d = 384, head_dim 64 (no bias; row counts whose 256-token workgroups fill at least
     70 % of their rounds of 256: from 45 825 rows on) to the token-on-the-lane kernel (qkv_rope_fused_kernel: rotation in registers, two
     waves per SIMD).  Its output must be the bits of the tiled kernel, which the same entry point runs below the threshold: the reference is the same call on two ranges of whole samples — with and without the
-    pre-scaled query table, with a position offset, heads != 6 — and the rotation against the fp32 formula."""
-    B, T, H, prescaled = case
+    pre-scaled query table, with a position offset, heads != 6 — and the rotation against the fp32 formula.
+    "per-sample": a 4-d table whose samples differ (angles drawn per sample, so a row rotated with another sample's pairs is a gross
+    error), at 47 x 975 = 45 825 rows, the smallest count the kernel takes: 256 does not divide T, so its 256-token workgroups straddle
+    samples ((mc / T) * table_bs per token).  The reference calls get the table sliced to their samples.  These cases use small-integer
+    operands (w scaled by 2^-4): the accumulator is exact, so the output is also held to the float64 rotation of the exact product within
+    one bf16 ulp of the reference plus 2e-5 (absolute, and relative to |re cos| + |im sin|)."""
+    B, T, H, prescaled = case[:4]
+    per_sample = len(case) > 4
     d, D = 384, 64
     M, N = B * T, 3 * H * D
     g = torch.Generator().manual_seed(B * T + H)
-    x = (torch.randn(M, d, generator=g) * 0.7).bfloat16().cuda()
-    w = (torch.randn(N, d, generator=g) / math.sqrt(d)).bfloat16().cuda()
+    if per_sample:
+        xf, wf = torch.randint(-2, 3, (M, d), generator=g).float(), torch.randint(-2, 3, (N, d), generator=g).float() / 16
+        xf[:, 5] += (torch.arange(M) % 7).float()
+        wf[:, 2] += (torch.arange(N) % 3).float() / 16
+        x, w = xf.bfloat16().cuda(), wf.bfloat16().cuda()
+    else:
+        x = (torch.randn(M, d, generator=g) * 0.7).bfloat16().cuda()
+        w = (torch.randn(N, d, generator=g) / math.sqrt(d)).bfloat16().cuda()
     Tc = T + 5
-    ang = torch.rand(Tc, D // 2, generator=g) * 6.28
+    ang = torch.rand(*((B,) if per_sample else ()), Tc, D // 2, generator=g) * 6.28
     both = torch.stack([torch.stack([ang.cos(), ang.sin()], -1), torch.stack([ang.cos(), ang.sin()], -1) * 0.1803]).contiguous().cuda()
     tab, qtab = both[0], both[1]
-    kw = dict(q_cols=H * D, q_table=qtab) if prescaled else {}
-    out = K.gemm_nt_rope(x, w, None, tab, T, 5, D, 2 * H * D, **kw)
+    sl = (lambda t, b0, b1: t[b0:b1]) if per_sample else (lambda t, b0, b1: t)
+    kw = (lambda b0, b1: dict(q_cols=H * D, q_table=sl(qtab, b0, b1))) if prescaled else (lambda b0, b1: {})
+    out = K.gemm_nt_rope(x, w, None, tab, T, 5, D, 2 * H * D, **kw(0, B))
     cut = (B // 2) * T
     assert M >= 45825 and cut < 45825 and M - cut < 45825
-    ref = torch.cat([K.gemm_nt_rope(x[a:b], w, None, tab, T, 5, D, 2 * H * D, **kw) for a, b in ((0, cut), (cut, M))])
+    ref = torch.cat([K.gemm_nt_rope(x[b0 * T:b1 * T], w, None, sl(tab, b0, b1), T, 5, D, 2 * H * D, **kw(b0, b1)) for b0, b1 in ((0, B // 2), (B // 2, B))])
     assert torch.equal(out, ref), float((out.float() - ref.float()).abs().max())
     y = (x.float().cpu() @ w.float().cpu().t()).view(B, T, 3 * H, D // 2, 2)
-    cs = torch.stack([ang.cos(), ang.sin()], -1)[5:5 + T][None, :, None]
+    cs = torch.stack([ang.cos(), ang.sin()], -1)[..., 5:5 + T, :, :]
+    cs = cs[:, :, None] if per_sample else cs[None, :, None]
     rot = torch.stack([y[..., 0] * cs[..., 0] - y[..., 1] * cs[..., 1], y[..., 0] * cs[..., 1] + y[..., 1] * cs[..., 0]], -1)
     want = torch.cat([rot[:, :, :2 * H], y[:, :, 2 * H:]], 2)
     if prescaled:
         want[:, :, :H] *= 0.1803
     torch.testing.assert_close(out.float().cpu().view(B, T, 3 * H, D // 2, 2), want, atol=4e-2, rtol=2e-2)
+    if per_sample:
+        y64 = (x.cpu().double() @ w.cpu().double().t()).view(B, T, 3 * H, D // 2, 2)
+        assert torch.equal(y64.float().double(), y64)                         # the exact product, representable in fp32
+        t64 = both.cpu().double()[:, :, 5:5 + T, None]                         # [2 tables, B, T, 1, D / 2, 2]
+        c = torch.cat([t64[1 if prescaled else 0].expand(B, T, H, D // 2, 2), t64[0].expand(B, T, H, D // 2, 2)], 2)
+        re, im = y64[:, :, :2 * H, :, 0], y64[:, :, :2 * H, :, 1]
+        r64 = torch.stack([re * c[..., 0] - im * c[..., 1], re * c[..., 1] + im * c[..., 0]], -1)
+        mag = torch.stack([(re * c[..., 0]).abs() + (im * c[..., 1]).abs(), (re * c[..., 1]).abs() + (im * c[..., 0]).abs()], -1)
+        got = out.cpu().double().view(B, T, 3 * H, D // 2, 2)
+        frac = ((got[:, :, :2 * H] - r64).abs() / (2.0 ** -8 * r64.abs() + 2e-5 + 2e-5 * mag)).max()
+        print(f"FRAC rope_lane per-sample prescaled={prescaled} {float(frac):.4f}")
+        assert float(frac) <= 1.0, float(frac)
+        assert torch.equal(got[:, :, 2 * H:], y64[:, :, 2 * H:].float().bfloat16().double())      # v: the exact product rounded once
 
 
 @pytest.mark.parametrize("case", [(49152, 64), (50_000 + 77, 1536), (49_000, 96)])
