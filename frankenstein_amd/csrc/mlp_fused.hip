@@ -20,6 +20,12 @@
 // slots and summation order are those of the two GEMM kernels this replaces (k in ascending 16-blocks), so dh13 and dx come out
 // bit-identical to them (tests/test_kernels_gpu.py).
 //
+// Layout of this file: what the four kernels share is written once in front of them — the lane geometry and the image swizzle
+// (LaneIds, swz_col), the stationary token fragments, the row-segment stores (row_segments, read_tile_rows, store_rows), the backward
+// kernels' weight ring with its request offsets and slot addresses (BwdRing), their two products, SwiGLU derivative and dx epilogue, and
+// the forward weight ring (FwdRing; mlp_up_fused_kernel keeps its own frame written out, for the measured reason given there).  The
+// kernels keep the order of their requests and the counted waits that depend on it.
+//
 // Built WITHOUT -amdgpu-mfma-vgpr-form (frankenstein_amd/build.py): the 208 accumulator registers live in the AGPR half, which is what
 // lets a wave keep 96 + 192 + 16 stationary registers at one wave per SIMD.
 #include "fk_common.h"
@@ -31,6 +37,7 @@ namespace {
 
 typedef __attribute__((address_space(3))) void lds_void_t;
 typedef __attribute__((address_space(1))) const void glb_void_t;
+extern __shared__ __attribute__((aligned(16))) char smem[];      // the dynamic LDS of whichever kernel is running
 
 struct MlpBwdArgs {
   const bf16_t* dy; const bf16_t* w2t; const bf16_t* h13; const bf16_t* w13t;
@@ -39,23 +46,16 @@ struct MlpBwdArgs {
   int M, H;
 };
 
-#ifndef MF_SPREAD
-#define MF_SPREAD 1        // 1: LDS-DMA requests placed one behind each MFMA group (-7 % per call, -0.44 ms per step); 0: in bursts
-#endif
-#ifndef MF_SPREAD_ST
-#define MF_SPREAD_ST 0
-#endif
-#ifndef MF_NT_DH13
-#define MF_NT_DH13 1
-#endif
 constexpr int MF_D = 384, MF_NW = 4, MF_TOK = MF_NW * 32;
 constexpr int MF_KT = MF_D / 64;                          // k-tile images of a W2T chunk (6)
+constexpr int MF_NT = MF_D / 32;                          // feature tiles of dx^T (12)
 constexpr int MF_W2 = MF_KT * 32 * ROW_BYTES;            // 24 KiB
 constexpr int MF_W13 = MF_D * ROW_BYTES;                 // 48 KiB
 constexpr int MF_SLOT = MF_W2 + MF_W13;                  // 72 KiB
 constexpr int MF_HREG = 32 * ROW_BYTES;                  // per wave: the 32 x 128-byte h13 / dh13 tile of a chunk (4 KiB)
 constexpr int MF_LDS = 2 * MF_SLOT + MF_NW * MF_HREG;    // 160 KiB: the whole LDS of a CU
-constexpr int MF_PIECES = MF_SLOT / 1024 / MF_NW;        // LDS-DMA wave instructions per wave and chunk (18)
+constexpr int MF_P2 = MF_W2 / 1024 / MF_NW;              // LDS-DMA wave instructions per wave and chunk: W2T part (6) ...
+constexpr int MF_P13 = MF_W13 / 1024 / MF_NW;            // ... and W13T part (12)
 constexpr int MF_ROWP = MF_D * 2 + 16;                   // padded bf16 row of the dx staging (784 B: 16-byte aligned, bank step 4)
 static_assert(MF_LDS <= 160 * 1024 && MF_TOK * MF_ROWP <= MF_LDS, "LDS of a CU");
 static_assert(MF_SLOT % (1024 * MF_NW) == 0, "whole pieces per wave");
@@ -68,9 +68,208 @@ template <bool FAST_SIGMOID> FK_DEV float mf_sigmoid(float x) {
 // One LDS-DMA request of 1 KiB (64 lanes x 16 B): wave-uniform 64-bit base + per-lane 32-bit byte offset -> LDS address `dst` (wave-uniform,
 // through M0).  Issued as asm: the scalar-base form costs no address arithmetic per request (hipcc's builtin takes a per-lane 64-bit pointer:
 // two or three VALU instructions per request on a wave that has no partner to hide them), and hipcc's wait-count pass does not see it
-// (the waits are counted by hand below).  M0 is written one instruction ahead of its use.
+// (the waits are counted by hand in the kernels).  M0 is written one instruction ahead of its use.
 FK_DEV void mf_dma(const void* base, unsigned voff, unsigned dst) {
   asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(base), "s"(dst) : "memory");
+}
+FK_DEV void wait_all_barrier() { asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+// ---- the lane of all four kernels: token li of the wave's 32, k-half lh of a fragment; as a mover of 128-byte rows (LDS-DMA pieces, row
+//      segment stores) it is 16-byte piece ch of row row8 of eight
+struct LaneIds {
+  int lane, li, lh, wave, row8, ch;
+  FK_DEV LaneIds() {
+    const int tid = threadIdx.x;
+    lane = tid & 63, li = lane & 31, lh = lane >> 5;
+    wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    row8 = lane >> 3, ch = lane & 7;
+  }
+};
+// XOR swizzle of an NT image (nt_off) applied on the SOURCE side of a request: the column (in elements) whose 16-byte piece lands in place ch of image row r
+FK_DEV int swz_col(int r, int ch) { return (ch ^ ((r >> 1) & 7)) << 3; }
+FK_DEV unsigned row_byte_off(int row, int64_t ld, int col) { return (unsigned)(((int64_t)row * ld + col) * 2); }      // the launchers check 32 bits
+
+// stationary B operand of a kernel's first product: the fragments of this lane's token row (k = 16 t + 8 lh .. + 8)
+FK_DEV void load_token_frags(Frag<bf16_t> (&f)[MF_D / 16], const bf16_t* base, int row, int64_t ld, int lh) {
+  const bf16_t* src = base + (int64_t)row * ld + 8 * lh;
+#pragma unroll
+  for (int t = 0; t < MF_D / 16; ++t) frag_load_contig<bf16_t>(f[t], src + 16 * t);
+}
+template <int N> FK_DEV void zero_acc(f32x16 (&a)[N]) {
+#pragma unroll
+  for (int t = 0; t < N; ++t)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) a[t][r] = 0.0f;
+}
+
+// ---- outputs leave as whole row segments: a wave-private LDS tile takes the lanes' pieces and is read back N rows-of-segments at a time
+//      (per-lane row accesses, 16-byte pieces of 64 different rows per instruction, cost the backward kernel 190 us in loads and 530 us
+//      in stores per cfg2 call).  Row j of a lane is row0 + j * step; rows past the end are clamped and never stored.
+template <int N> FK_DEV void row_segments(bf16_t* (&dst)[N], bool (&ok)[N], bf16_t* base, int64_t ld, int row0, int step, int M, int col) {
+#pragma unroll
+  for (int j = 0; j < N; ++j) {
+    const int mr = row0 + j * step;
+    ok[j] = mr < M;
+    dst[j] = base + (int64_t)(ok[j] ? mr : M - 1) * ld + col;
+  }
+}
+// the 128-byte rows of a swizzled 32-row tile, eight lanes per row (LDS instructions of a wave execute in order: these reads see its own writes)
+FK_DEV void read_tile_rows(bf16x8 (&rb)[4], const char* tile, const LaneIds& L) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) rb[j] = *reinterpret_cast<const bf16x8*>(tile + nt_off(j * 8 + L.row8, L.ch));
+}
+// whole wave (wave-uniform): no per-lane predicate and no branch per store; else per row
+template <int N, bool NT> FK_DEV void store_rows(bf16_t* const (&dst)[N], const bool (&ok)[N], bool wave_full, int col, const bf16x8 (&v)[N]) {
+  if (wave_full) {
+#pragma unroll
+    for (int j = 0; j < N; ++j) fk_st<NT>(reinterpret_cast<bf16x8*>(dst[j] + col), v[j]);
+  } else {
+#pragma unroll
+    for (int j = 0; j < N; ++j)
+      if (ok[j]) fk_st<NT>(reinterpret_cast<bf16x8*>(dst[j] + col), v[j]);
+  }
+}
+
+// ---- the backward kernels' weight ring.  LDS: W2T ring (two 24-KiB slots), W13T ring (two 48-KiB slots), the waves' h13 tiles.
+//      LDS-DMA of one weight chunk: pieces of 8 image rows x 128 B (1 KiB per wave instruction); every wave moves six pieces of the W2T
+//      part (k-tile images s6 = 0..5 of 32 rows each) and twelve of the 384-row W13T image; XOR swizzle on the SOURCE column.  The
+//      per-lane byte offsets inside a chunk are constants: chunk c starts at w2t + c * 32 rows / w13t + c * 64 columns (wave-uniform).
+//      The wave's h13 rows of a chunk (32 tokens x 64 interleaved columns = 4 KiB) also arrive by LDS-DMA, into a wave-private tile
+//      with the image's swizzle; the lane reads its four 16-byte pieces from there, the dh13 pieces go back into the SAME places and
+//      leave as whole 128-byte row segments.
+struct BwdRing {
+  const MlpBwdArgs& p;
+  const LaneIds& L;
+  unsigned lds0, off2[MF_P2], off13[MF_P13];
+  FK_DEV BwdRing(const MlpBwdArgs& p_, const LaneIds& L_) : p(p_), L(L_), lds0((unsigned)(uintptr_t)(lds_void_t*)smem) {
+#pragma unroll
+    for (int j = 0; j < MF_P2; ++j) {
+      const int q = L.wave * MF_P2 + j, s6 = q >> 2, r = (q & 3) * 8 + L.row8;
+      off2[j] = (unsigned)((r * (int)p.ldw2t + s6 * 64 + swz_col(r, L.ch)) * 2);
+    }
+#pragma unroll
+    for (int j = 0; j < MF_P13; ++j) {
+      const int r = (L.wave * MF_P13 + j) * 8 + L.row8;
+      off13[j] = (unsigned)((r * (int)p.ldw13t + swz_col(r, L.ch)) * 2);
+    }
+  }
+  // the slots and this wave's tile (behind both weight rings), from base = smem (pointers) or lds0 (LDS byte addresses)
+  template <typename B> static FK_DEV B w2_at(B base, int slot) { return base + slot * MF_W2; }
+  template <typename B> static FK_DEV B w13_at(B base, int slot) { return base + 2 * MF_W2 + slot * MF_W13; }
+  template <typename B> FK_DEV B tile_at(B base) const { return base + 2 * MF_SLOT + L.wave * MF_HREG; }
+  FK_DEV const char* w2img(int slot) const { return w2_at(smem, slot); }
+  FK_DEV const char* w13img(int slot) const { return w13_at(smem, slot); }
+  FK_DEV char* tile() const { return tile_at(smem); }
+  FK_DEV unsigned tile_lds() const { return __builtin_amdgcn_readfirstlane(tile_at(lds0)); }
+  // source of chunk c (wave-uniform) and this wave's share of a slot as a request's LDS destination
+  FK_DEV const bf16_t* w2_src(int c) const { return p.w2t + (int64_t)c * 32 * p.ldw2t; }
+  FK_DEV const bf16_t* w13_src(int c) const { return p.w13t + (int64_t)c * 64; }
+  FK_DEV const bf16_t* h_src(int c) const { return p.h13 + (int64_t)c * 64; }
+  FK_DEV unsigned w2_dst(int slot) const { return __builtin_amdgcn_readfirstlane(w2_at(lds0, slot) + L.wave * (MF_W2 / MF_NW)); }
+  FK_DEV unsigned w13_dst(int slot) const { return __builtin_amdgcn_readfirstlane(w13_at(lds0, slot) + L.wave * (MF_W13 / MF_NW)); }
+  // one request (piece j of this wave's share) at a time: inside the chunk loops they are placed one behind each MFMA group, so that a wave
+  // without a partner on its SIMD issues them in the shadow of its own matrix work instead of in bursts (-7 % per call, -0.44 ms per step)
+  FK_DEV void dma_w2(int c, int slot, int j) const { mf_dma(w2_src(c), off2[j], w2_dst(slot) + j * 1024); }
+  FK_DEV void dma_w13(int c, int slot, int j) const { mf_dma(w13_src(c), off13[j], w13_dst(slot) + j * 1024); }
+  // tile request piece j (rows j * 8 + row8 of the tile): byte offset of token row `row` (the caller clamps it where M is ragged)
+  FK_DEV unsigned h_off(int j, int row) const { return row_byte_off(row, p.ldh, swz_col(j * 8 + L.row8, L.ch)); }
+  FK_DEV void dma_h(int c, int j, unsigned hoff, unsigned tile_dst) const { mf_dma(h_src(c), hoff, tile_dst + j * 1024); }
+  // whole chunks, as the prologues request them
+  FK_DEV void issue_w2(int c, int slot) const {
+#pragma unroll
+    for (int j = 0; j < MF_P2; ++j) dma_w2(c, slot, j);
+  }
+  FK_DEV void issue_w13(int c, int slot) const {
+#pragma unroll
+    for (int j = 0; j < MF_P13; ++j) dma_w13(c, slot, j);
+  }
+  FK_DEV void issue_h(int c, const unsigned (&hoff)[4], unsigned tile_dst) const {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) dma_h(c, j, hoff[j], tile_dst);
+  }
+};
+
+// ---- dg^T = W2T_c dy^T: 24 MFMAs over MF_KT groups, the A fragments read one group (four) ahead (one wave per SIMD: nobody else hides the
+//      LDS latency); behind(s6) is what the caller places behind group s6
+template <typename F>
+FK_DEV void first_product(f32x16& dg, Frag<bf16_t> (&fa)[2][4], const char* w2img, const Frag<bf16_t> (&dyf)[MF_D / 16], const LaneIds& L, const F& behind) {
+#pragma unroll
+  for (int r = 0; r < 16; ++r) dg[r] = 0.0f;
+#pragma unroll
+  for (int s = 0; s < 4; ++s) nt_frag<bf16_t>(fa[0][s], w2img, L.li, s, L.lh);
+#pragma unroll
+  for (int s6 = 0; s6 < MF_KT; ++s6) {
+    if (s6 + 1 < MF_KT) {
+#pragma unroll
+      for (int s = 0; s < 4; ++s) nt_frag<bf16_t>(fa[(s6 + 1) & 1][s], w2img + (s6 + 1) * 32 * ROW_BYTES, L.li, s, L.lh);
+    }
+#pragma unroll
+    for (int s = 0; s < 4; ++s) mma32<bf16_t>(dg, fa[s6 & 1][s], dyf[s6 * 4 + s]);
+    behind(s6);
+    // the next group's four LDS reads FIRST, then this group's four MFMAs (left alone hipcc puts the reads behind three of the MFMAs
+    // and waits for them 32 cycles later)
+    __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
+    __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
+// ---- SwiGLU derivative of one 16-byte h13 piece: lane (token, lh) holds dg of the hidden units 4 (2 s + lh) + e, e = 0..3, in dg[4 s + e];
+//      the piece is (h1 | h3) of those four units, the result (dh1 | dh3) rounded to bf16
+FK_DEV bf16x8 dswiglu_piece(const bf16x8& hv, const f32x16& dg, int s) {
+  bf16x8 o;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const float a1 = (float)hv[e], a3 = (float)hv[4 + e], g = dg[4 * s + e];
+    const float sg = mf_sigmoid<true>(a1), ds = g * sg;
+    o[e] = (bf16_t)(ds * a3 * (1.0f + a1 * (1.0f - sg)));
+    o[4 + e] = (bf16_t)(ds * a1);
+  }
+  return o;
+}
+
+// ---- dx^T += W13T_c dh13^T: 48 MFMAs, fragments of feature tile t + 1 read while tile t multiplies; behind(t) is what the caller places
+//      behind tile t
+template <typename F>
+FK_DEV void second_product(f32x16 (&dx)[MF_NT], Frag<bf16_t> (&fa)[2][4], const char* w13img, const Frag<bf16_t> (&bf)[4], const LaneIds& L, const F& behind) {
+#pragma unroll
+  for (int s = 0; s < 4; ++s) nt_frag<bf16_t>(fa[0][s], w13img, L.li, s, L.lh);
+#pragma unroll
+  for (int t = 0; t < MF_NT; ++t) {
+    if (t + 1 < MF_NT) {
+#pragma unroll
+      for (int s = 0; s < 4; ++s) nt_frag<bf16_t>(fa[(t + 1) & 1][s], w13img, 32 * (t + 1) + L.li, s, L.lh);
+    }
+#pragma unroll
+    for (int s = 0; s < 4; ++s) mma32<bf16_t>(dx[t], fa[t & 1][s], bf[s]);
+    behind(t);
+    __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
+    __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
+// ---- dx: accumulators (lane = token, 4 consecutive features per register group) -> padded bf16 rows staged in LDS (wave-private: the caller
+//      has made sure the LDS is free) -> 16-byte row stores of the wave's rows m0w .. below row_end
+FK_DEV void store_dx(const MlpBwdArgs& p, const f32x16 (&dx)[MF_NT], const LaneIds& L, int m0w, int row_end) {
+  char* stg = smem + L.wave * 32 * MF_ROWP;
+#pragma unroll
+  for (int t = 0; t < MF_NT; ++t)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      bf16x4 v;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[e] = (bf16_t)dx[t][4 * g + e];
+      *reinterpret_cast<bf16x4*>(stg + L.li * MF_ROWP + (32 * t + 8 * g + 4 * L.lh) * 2) = v;
+    }
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // wave-private staging: no barrier needed
+  if (L.lane < MF_D / 8) {
+    for (int r = 0; r < 32; ++r) {
+      if (m0w + r >= row_end) break;
+      const bf16x8 v = *reinterpret_cast<const bf16x8*>(stg + r * MF_ROWP + L.lane * 16);
+      fk_st<true>(reinterpret_cast<bf16x8*>(p.dx + (int64_t)(m0w + r) * p.lddx + L.lane * 8), v);
+    }
+  }
 }
 
 #ifdef MF_STAMP
@@ -79,85 +278,30 @@ FK_DEV void mf_dma(const void* base, unsigned voff, unsigned dst) {
 __device__ unsigned long long mf_stamp_acc[16];
 #define MF_ST_DECL unsigned long long st_acc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; unsigned long long st_t = __builtin_amdgcn_s_memtime(); const unsigned long long st_t0 = st_t;
 #define MF_ST(i) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); st_acc[i] += t_ - st_t; st_t = t_; }
-#define MF_ST_FLUSH if (lane == 0) { for (int i_ = 0; i_ < 10; ++i_) atomicAdd(&mf_stamp_acc[i_], st_acc[i_]); atomicAdd(&mf_stamp_acc[15], __builtin_amdgcn_s_memtime() - st_t0); }
+#define MF_ST_FLUSH(lane) if ((lane) == 0) { for (int i_ = 0; i_ < 10; ++i_) atomicAdd(&mf_stamp_acc[i_], st_acc[i_]); atomicAdd(&mf_stamp_acc[15], __builtin_amdgcn_s_memtime() - st_t0); }
 #else
 #define MF_ST_DECL
 #define MF_ST(i)
-#define MF_ST_FLUSH
+#define MF_ST_FLUSH(lane)
 #endif
 
+// Ragged M, and everything with FK_MLP_BWD_ASM=0: the chain as hipcc schedules it.
 __global__ __launch_bounds__(MF_NW * 64, 1) void mlp_bwd_fused_kernel(MlpBwdArgs p) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
   using T = bf16_t;
-  const int tid = threadIdx.x, lane = tid & 63, li = lane & 31, lh = lane >> 5;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int m = blockIdx.x * MF_TOK + wave * 32 + li;
-  const bool m_ok = m < p.M;
-  const int mc = m_ok ? m : p.M - 1;                      // rows past the end: clamped loads, no stores
-  const int nchunks = p.H / 32;
-
-  // ---- LDS-DMA of one weight chunk: pieces of 8 image rows x 128 B (1 KiB per wave instruction); every wave moves six pieces of the W2T
-  //      part (k-tile images s6 = 0..5 of 32 rows each) and twelve of the 384-row W13T image; XOR swizzle on the SOURCE column.  The
-  //      per-lane byte offsets inside a chunk are constants: chunk c starts at w2t + c * 32 rows / w13t + c * 64 columns (wave-uniform)
-  const int row8 = lane >> 3, ch = lane & 7;
-  unsigned off2[MF_W2 / 1024 / MF_NW], off13[MF_W13 / 1024 / MF_NW];
-#pragma unroll
-  for (int j = 0; j < MF_W2 / 1024 / MF_NW; ++j) {
-    const int q = wave * (MF_W2 / 1024 / MF_NW) + j, s6 = q >> 2, r = (q & 3) * 8 + row8;
-    off2[j] = (unsigned)((r * (int)p.ldw2t + s6 * 64 + ((ch ^ ((r >> 1) & 7)) << 3)) * 2);
-  }
-#pragma unroll
-  for (int j = 0; j < MF_W13 / 1024 / MF_NW; ++j) {
-    const int r = (wave * (MF_W13 / 1024 / MF_NW) + j) * 8 + row8;
-    off13[j] = (unsigned)((r * (int)p.ldw13t + ((ch ^ ((r >> 1) & 7)) << 3)) * 2);
-  }
-  // LDS: W2T ring (two 24-KiB slots), W13T ring (two 48-KiB slots), the waves' h13 tiles
-  const unsigned lds0 = (unsigned)(uintptr_t)(lds_void_t*)smem;
-  auto w2slot = [&](int i) -> char* { return smem + i * MF_W2; };
-  auto w13slot = [&](int i) -> char* { return smem + 2 * MF_W2 + i * MF_W13; };
-  // one request (piece j of this wave's share) at a time: inside the chunk loop they are placed one behind each MFMA group (MF_SPREAD), so
-  // that a wave without a partner on its SIMD issues them in the shadow of its own matrix work instead of in bursts
-  auto dma_w2 = [&](int c, int slot, int j) __attribute__((always_inline)) {
-    const void* g2 = p.w2t + (int64_t)c * 32 * p.ldw2t;
-    const unsigned d0 = __builtin_amdgcn_readfirstlane(lds0 + slot * MF_W2 + wave * (MF_W2 / MF_NW));
-    mf_dma(g2, off2[j], d0 + j * 1024);
-  };
-  auto dma_w13 = [&](int c, int slot, int j) __attribute__((always_inline)) {
-    const void* g13 = p.w13t + (int64_t)c * 64;
-    const unsigned d0 = __builtin_amdgcn_readfirstlane(lds0 + 2 * MF_W2 + slot * MF_W13 + wave * (MF_W13 / MF_NW));
-    mf_dma(g13, off13[j], d0 + j * 1024);
-  };
-  auto issue_w2 = [&](int c, int slot) __attribute__((always_inline)) {
-#pragma unroll
-    for (int j = 0; j < MF_W2 / 1024 / MF_NW; ++j) dma_w2(c, slot, j);
-  };
-  auto issue_w13 = [&](int c, int slot) __attribute__((always_inline)) {
-#pragma unroll
-    for (int j = 0; j < MF_W13 / 1024 / MF_NW; ++j) dma_w13(c, slot, j);
-  };
-  // ---- the wave's h13 rows of a chunk (32 tokens x 64 interleaved columns = 4 KiB) also arrive by LDS-DMA, into a wave-private tile
-  //      with the image's swizzle; the lane reads its four 16-byte pieces from there, the dh13 pieces go back into the SAME places and
-  //      leave as whole 128-byte row segments (eight lanes per row): per-lane row accesses (16-byte pieces of 64 different rows per
-  //      instruction) cost this kernel 190 us in loads and 530 us in stores per cfg2 call
-  char* hreg = smem + 2 * MF_SLOT + wave * MF_HREG;       // behind both weight rings
-  const int m0w = blockIdx.x * MF_TOK + wave * 32;
+  const LaneIds L;
+  const BwdRing ring(p, L);
+  const int m0w = blockIdx.x * MF_TOK + L.wave * 32, m = m0w + L.li;
+  const int mc = m < p.M ? m : p.M - 1;                   // rows past the end: clamped loads, no stores
   const bool wave_full = m0w + 32 <= p.M;
-  unsigned hoff[4];
-  T* hdst[4];
+  const int nchunks = p.H / 32, last = nchunks - 1;
+  char* hreg = ring.tile();
+  const unsigned hreg_lds = ring.tile_lds();
+  T* hdst[4];                                             // dh13 store: logical piece ch of tile row j * 8 + row8
   bool hrow_ok[4];
+  row_segments(hdst, hrow_ok, p.dh13, p.lddh, m0w + L.row8, 8, p.M, L.ch << 3);
+  unsigned hoff[4];                                       // h13 tile request: the swizzled column piece of the same (clamped) rows
 #pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int r = j * 8 + row8, mr = m0w + r;
-    hrow_ok[j] = mr < p.M;
-    hoff[j] = (unsigned)(((int64_t)(hrow_ok[j] ? mr : p.M - 1) * p.ldh + ((ch ^ ((r >> 1) & 7)) << 3)) * 2);      // DMA source: swizzled column piece (the launcher checks 32 bits)
-    hdst[j] = p.dh13 + (int64_t)(hrow_ok[j] ? mr : p.M - 1) * p.lddh + (ch << 3);                                 // store: logical piece ch of row r
-  }
-  const unsigned hreg_lds = __builtin_amdgcn_readfirstlane(lds0 + 2 * MF_SLOT + wave * MF_HREG);
-  auto dma_h = [&](int c, int j) __attribute__((always_inline)) { mf_dma(p.h13 + (int64_t)c * 64, hoff[j], hreg_lds + j * 1024); };
-  auto issue_h = [&](int c) __attribute__((always_inline)) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) dma_h(c, j);
-  };
+  for (int j = 0; j < 4; ++j) hoff[j] = ring.h_off(j, hrow_ok[j] ? m0w + j * 8 + L.row8 : p.M - 1);
 
   // ---- Request stream and waits.  Loads retire in order, so "s_waitcnt vmcnt(N)" with N = the number of YOUNGER loads of this wave says
   //      that a given request has landed (outstanding stores only make it wait longer, never less).  Per chunk c, per wave:
@@ -168,156 +312,46 @@ __global__ __launch_bounds__(MF_NW * 64, 1) void mlp_bwd_fused_kernel(MlpBwdArgs
   //        at B2(c): W2T(c+1) 6 + tile(c) 4 + W13T(c+1) 12 = 22.
   //      Past the last chunk the requests are repeated with the last chunk's addresses (into slots nobody reads any more), so that the
   //      counts hold to the end.
-  const int last = nchunks - 1;
-  issue_w2(0, 0);
-  issue_w13(0, 0);
-  issue_w2(last < 1 ? last : 1, 1);
-  issue_h(0);
-  // ---- stationary B operand of the first product: dy^T fragments of this lane's token (k = 16 t + 8 lh .. + 8)
+  ring.issue_w2(0, 0);
+  ring.issue_w13(0, 0);
+  ring.issue_w2(last < 1 ? last : 1, 1);
+  ring.issue_h(0, hoff, hreg_lds);
   Frag<T> dyf[MF_D / 16];
-  const T* dyrow = p.dy + (int64_t)mc * p.lddy + 8 * lh;
-#pragma unroll
-  for (int t = 0; t < MF_D / 16; ++t) frag_load_contig<T>(dyf[t], dyrow + 16 * t);
-  f32x16 dx[MF_D / 32];
-#pragma unroll
-  for (int t = 0; t < MF_D / 32; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) dx[t][r] = 0.0f;
-  asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");     // B1(0): everything requested so far (and the dy fragments) has landed
+  load_token_frags(dyf, p.dy, mc, p.lddy, L.lh);
+  f32x16 dx[MF_NT];
+  zero_acc(dx);
+  wait_all_barrier();                                     // B1(0): everything requested so far (and the dy fragments) has landed
 
   for (int c = 0; c < nchunks; ++c) {
-    const char* w2img = w2slot(c & 1);
-    const char* w13img = w13slot(c & 1);
     if (c > 0) asm volatile("s_waitcnt vmcnt(26)\n\ts_barrier" ::: "memory");              // B1(c)
     const int cn1 = c + 1 < nchunks ? c + 1 : last, cn2 = c + 2 < nchunks ? c + 2 : last;
-#if !defined(MF_ABL_NODMA) && !MF_SPREAD                // MF_ABL_*: timing builds only (wrong results)
-    issue_w13(cn1, (c + 1) & 1);                          // that slot was last read by the second product of chunk c - 1
-#endif
-    // ---- dg^T = W2T_c dy^T: 24 MFMAs, the A fragments read four ahead (one wave per SIMD: nobody else hides the LDS latency)
     f32x16 dg;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) dg[r] = 0.0f;
     Frag<T> fa[2][4];
-#pragma unroll
-    for (int s = 0; s < 4; ++s) nt_frag<T>(fa[0][s], w2img, li, s, lh);
-#pragma unroll
-    for (int s6 = 0; s6 < MF_KT; ++s6) {
-      if (s6 + 1 < MF_KT) {
-#pragma unroll
-        for (int s = 0; s < 4; ++s) nt_frag<T>(fa[(s6 + 1) & 1][s], w2img + (s6 + 1) * 32 * ROW_BYTES, li, s, lh);
-      }
-#pragma unroll
-      for (int s = 0; s < 4; ++s) mma32<T>(dg, fa[s6 & 1][s], dyf[s6 * 4 + s]);
-#if !defined(MF_ABL_NODMA) && MF_SPREAD
-      dma_w13(cn1, (c + 1) & 1, 2 * s6);                  // W13T(c + 1): two of this wave's twelve requests behind each of the six groups
-      dma_w13(cn1, (c + 1) & 1, 2 * s6 + 1);
-#endif
-      // the next group's four LDS reads FIRST, then this group's four MFMAs (left alone hipcc puts the reads behind three of the MFMAs
-      // and waits for them 32 cycles later)
-      __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
-      __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-#ifndef MF_ABL_NOLD
+    // W13T(c + 1): two of this wave's twelve requests behind each of the six groups (that slot was last read by the second product of chunk c - 1)
+    first_product(dg, fa, ring.w2img(c & 1), dyf, L, [&](int s6) __attribute__((always_inline)) {
+      ring.dma_w13(cn1, (c + 1) & 1, 2 * s6);
+      ring.dma_w13(cn1, (c + 1) & 1, 2 * s6 + 1);
+    });
     asm volatile("s_waitcnt vmcnt(12)" ::: "memory");       // this wave's h13 tile of chunk c has landed (wave-private: no barrier)
-#endif
-    // ---- SwiGLU derivative: lane (token, lh) holds dg of the hidden units 4 (2 s + lh) + e, e = 0..3, in dg[4 s + e]
     Frag<T> bf[4];
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
-      const bf16x8 hv = *reinterpret_cast<const bf16x8*>(hreg + nt_off(li, 2 * s + lh));
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float a1 = (float)hv[e], a3 = (float)hv[4 + e], g = dg[4 * s + e];
-#ifdef MF_ABL_NOMATH
-        bf[s].v[e] = (T)(g + a1);
-        bf[s].v[4 + e] = (T)(g + a3);
-#else
-        const float sg = mf_sigmoid<true>(a1), ds = g * sg;
-        bf[s].v[e] = (T)(ds * a3 * (1.0f + a1 * (1.0f - sg)));
-        bf[s].v[4 + e] = (T)(ds * a1);
-#endif
-      }
-      *reinterpret_cast<bf16x8*>(hreg + nt_off(li, 2 * s + lh)) = bf[s].v;       // the place this lane just read
+      bf[s].v = dswiglu_piece(*reinterpret_cast<const bf16x8*>(hreg + nt_off(L.li, 2 * s + L.lh)), dg, s);
+      *reinterpret_cast<bf16x8*>(hreg + nt_off(L.li, 2 * s + L.lh)) = bf[s].v;       // the place this lane just read
     }
-    // dh13 leaves as whole row segments (eight lanes per row): read back here (LDS instructions of a wave execute in order: these reads see
-    // the writes above), stored behind the barrier so that the LDS latency hides in the wait
+    // dh13 leaves as whole row segments: read back here, stored behind the barrier so that the LDS latency hides in the wait
     bf16x8 rb[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) rb[j] = *reinterpret_cast<const bf16x8*>(hreg + nt_off(j * 8 + row8, ch));
+    read_tile_rows(rb, hreg, L);
     asm volatile("s_waitcnt vmcnt(22)\n\ts_barrier" ::: "memory");               // B2(c): W13T(c) has landed; everyone is done with W2T(c)
-#if !defined(MF_ABL_NODMA) && !MF_SPREAD
-    issue_w2(cn2, c & 1);
-#endif
-#ifndef MF_ABL_NOST
-    if (wave_full) {                                      // wave-uniform: no per-lane predicate (and no branch per store) for whole tiles
-#if !MF_SPREAD_ST
-#pragma unroll
-      for (int j = 0; j < 4; ++j) fk_st<MF_NT_DH13 != 0>(reinterpret_cast<bf16x8*>(hdst[j] + c * 64), rb[j]);      // written once, read by the weight-gradient GEMMs later
-#else
-      asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(rb[0]), "+v"(rb[1]), "+v"(rb[2]), "+v"(rb[3])::"memory");        // the read-back is in registers: the tile is free
-#endif
-    } else {
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        if (hrow_ok[j]) fk_st<MF_NT_DH13 != 0>(reinterpret_cast<bf16x8*>(hdst[j] + c * 64), rb[j]);
-    }
-#else
-    asm volatile("" ::"v"(rb[0]), "v"(rb[1]), "v"(rb[2]), "v"(rb[3]));
-#endif
-#if !defined(MF_ABL_NOLD) && !MF_SPREAD
-    issue_h(cn1);                                         // the tile is free: its read-back sits in registers (the stores above waited for it)
-#endif
-    // ---- dx^T += W13T_c dh13^T: 48 MFMAs, fragments of feature tile t + 1 read while tile t multiplies
-    constexpr int NT12 = MF_D / 32;
-#pragma unroll
-    for (int s = 0; s < 4; ++s) nt_frag<T>(fa[0][s], w13img, li, s, lh);
-#pragma unroll
-    for (int t = 0; t < NT12; ++t) {
-      if (t + 1 < NT12) {
-#pragma unroll
-        for (int s = 0; s < 4; ++s) nt_frag<T>(fa[(t + 1) & 1][s], w13img, 32 * (t + 1) + li, s, lh);
-      }
-#pragma unroll
-      for (int s = 0; s < 4; ++s) mma32<T>(dx[t], fa[t & 1][s], bf[s]);
-#if MF_SPREAD                                             // W2T(c + 2) behind the first six groups, then the h13 tile of chunk c + 1 (same order as the bursts: the counts hold)
-#ifndef MF_ABL_NODMA
-      if (t < 6) dma_w2(cn2, c & 1, t);
-#endif
-#ifndef MF_ABL_NOLD
-      if (t >= 6 && t < 10) dma_h(cn1, t - 6);
-#endif
-#if MF_SPREAD_ST && !defined(MF_ABL_NOST)
-      if (wave_full && t >= 6 && t < 10) fk_st<MF_NT_DH13 != 0>(reinterpret_cast<bf16x8*>(hdst[t - 6] + c * 64), rb[t - 6]);
-#endif
-#endif
-      __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
-      __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
-      __builtin_amdgcn_sched_barrier(0);
-    }
+    store_rows<4, true>(hdst, hrow_ok, wave_full, c * 64, rb);                   // written once, read by the weight-gradient GEMMs later
+    // W2T(c + 2) behind the first six tiles, then the h13 tile of chunk c + 1 (free: its read-back sits in registers)
+    second_product(dx, fa, ring.w13img(c & 1), bf, L, [&](int t) __attribute__((always_inline)) {
+      if (t < MF_P2) ring.dma_w2(cn2, c & 1, t);
+      else if (t < MF_P2 + 4) ring.dma_h(cn1, t - MF_P2, hoff[t - MF_P2], hreg_lds);
+    });
   }
-  asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");     // the repeated requests of the tail have landed: the LDS is free for the dx staging
-
-  // ---- dx: accumulators (lane = token, 4 consecutive features per register group) -> bf16 rows staged in LDS -> 16-byte row stores
-  char* stg = smem + wave * 32 * MF_ROWP;
-#pragma unroll
-  for (int t = 0; t < MF_D / 32; ++t)
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      bf16x4 v;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] = (T)dx[t][4 * g + e];
-      *reinterpret_cast<bf16x4*>(stg + li * MF_ROWP + (32 * t + 8 * g + 4 * lh) * 2) = v;
-    }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // wave-private staging: no barrier needed
-  if (lane < MF_D / 8) {
-    const int m0 = blockIdx.x * MF_TOK + wave * 32;
-    for (int r = 0; r < 32; ++r) {
-      if (m0 + r >= p.M) break;
-      const bf16x8 v = *reinterpret_cast<const bf16x8*>(stg + r * MF_ROWP + lane * 16);
-      fk_st<true>(reinterpret_cast<bf16x8*>(p.dx + (int64_t)(m0 + r) * p.lddx + lane * 8), v);
-    }
-  }
+  wait_all_barrier();                                     // the repeated requests of the tail have landed: the LDS is free for the dx staging
+  store_dx(p, dx, L, m0w, p.M);
 }
 
 
@@ -334,6 +368,8 @@ __global__ __launch_bounds__(MF_NW * 64, 1) void mlp_bwd_fused_kernel(MlpBwdArgs
 //              every gap filled to the same issue budget
 //   Same products and summation order, same arithmetic instruction for instruction: dh13 and dx are the bits of the kernel above.
 //   Whole 128-token tiles only (M % 128 == 0); the launcher keeps the kernel above for the rest (and FK_MLP_BWD_ASM=0 for everything).
+//   The prologue (chunk 0's first product and derivative) and the tail (the last chunk's second product, the dx epilogue) are the shared
+//   blocks above; A(c) is written out here, because barrier B(c) and the stream's first operands sit INSIDE its last group.
 //
 //   Requests and waits (loads retire in order; N = the younger loads of this wave).  Issue order per wave:
 //        A(c): W13T(c + 1) [12]      B(c): W2T(c + 3) [6], dh13(c + 1) stores, h13 tile(c + 2) [4]      A(c + 1): W13T(c + 2) [12] ...
@@ -351,134 +387,79 @@ typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
 
 __global__ __launch_bounds__(MF_NW * 64, 1) void mlp_bwd_fused_asm_kernel(MlpBwdArgs p) {
   MF_ST_DECL
-  extern __shared__ __attribute__((aligned(16))) char smem[];
   using T = bf16_t;
-  const int tid = threadIdx.x, lane = tid & 63, li = lane & 31, lh = lane >> 5;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int m = blockIdx.x * MF_TOK + wave * 32 + li;       // < M: whole tiles only
+  const LaneIds L;
+  const BwdRing ring(p, L);
+  const int m0w = blockIdx.x * MF_TOK + L.wave * 32;        // + li < M: whole tiles only
   const int nchunks = p.H / 32, last = nchunks - 1;
   auto cl = [&](int k) { return k < last ? k : last; };
-  const int row8 = lane >> 3, ch = lane & 7;
-  unsigned off2[MF_W2 / 1024 / MF_NW], off13[MF_W13 / 1024 / MF_NW];
-#pragma unroll
-  for (int j = 0; j < MF_W2 / 1024 / MF_NW; ++j) {
-    const int q = wave * (MF_W2 / 1024 / MF_NW) + j, s6 = q >> 2, r = (q & 3) * 8 + row8;
-    off2[j] = (unsigned)((r * (int)p.ldw2t + s6 * 64 + ((ch ^ ((r >> 1) & 7)) << 3)) * 2);
-  }
-#pragma unroll
-  for (int j = 0; j < MF_W13 / 1024 / MF_NW; ++j) {
-    const int r = (wave * (MF_W13 / 1024 / MF_NW) + j) * 8 + row8;
-    off13[j] = (unsigned)((r * (int)p.ldw13t + ((ch ^ ((r >> 1) & 7)) << 3)) * 2);
-  }
-  const unsigned lds0 = (unsigned)(uintptr_t)(lds_void_t*)smem;
-  auto w2slot = [&](int i) -> char* { return smem + i * MF_W2; };
-  auto w13slot = [&](int i) -> char* { return smem + 2 * MF_W2 + i * MF_W13; };
-  auto dma_w2 = [&](int c, int slot, int j) __attribute__((always_inline)) {
-    mf_dma(p.w2t + (int64_t)c * 32 * p.ldw2t, off2[j], __builtin_amdgcn_readfirstlane(lds0 + slot * MF_W2 + wave * (MF_W2 / MF_NW)) + j * 1024);
-  };
-  auto dma_w13 = [&](int c, int slot, int j) __attribute__((always_inline)) {
-    mf_dma(p.w13t + (int64_t)c * 64, off13[j], __builtin_amdgcn_readfirstlane(lds0 + 2 * MF_W2 + slot * MF_W13 + wave * (MF_W13 / MF_NW)) + j * 1024);
-  };
-  char* hreg = smem + 2 * MF_SLOT + wave * MF_HREG;
-  const int m0w = blockIdx.x * MF_TOK + wave * 32;
-  const unsigned hreg_lds = __builtin_amdgcn_readfirstlane(lds0 + 2 * MF_SLOT + wave * MF_HREG);
+  char* hreg = ring.tile();
+  const unsigned hreg_lds = ring.tile_lds();
   // the stream's address operands: LDS byte addresses (adr) and global byte offsets (ofs); adr[0..3] and adr[12..15] follow the ring slots
   u32x16 adr, ofs;
-  unsigned ax[4];
+  unsigned ax[4], hoff[4];
 #pragma unroll
   for (int s = 0; s < 4; ++s) {
-    ax[s] = (unsigned)nt_off(li, 2 * s + lh);
+    ax[s] = (unsigned)nt_off(L.li, 2 * s + L.lh);
     adr[4 + s] = hreg_lds + ax[s];                                          // AH: the lane's pieces of its tile
-    adr[8 + s] = hreg_lds + (unsigned)nt_off(s * 8 + row8, ch);             // AR: tile rows, eight lanes per row
+    adr[8 + s] = hreg_lds + (unsigned)nt_off(s * 8 + L.row8, L.ch);         // AR: tile rows, eight lanes per row
   }
 #pragma unroll
-  for (int j = 0; j < 6; ++j) ofs[j] = off2[j];
+  for (int j = 0; j < MF_P2; ++j) ofs[j] = ring.off2[j];
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    const int r = j * 8 + row8;
-    ofs[6 + j] = (unsigned)(((int64_t)(m0w + r) * p.ldh + ((ch ^ ((r >> 1) & 7)) << 3)) * 2);     // HOFF: tile request pieces (swizzled source column)
-    ofs[10 + j] = (unsigned)(((int64_t)(m0w + r) * p.lddh + (ch << 3)) * 2);                       // VST: row stores (logical piece ch of row r)
+    hoff[j] = ring.h_off(j, m0w + j * 8 + L.row8);
+    ofs[6 + j] = hoff[j];                                                                        // HOFF: tile request pieces (swizzled source column)
+    ofs[10 + j] = row_byte_off(m0w + j * 8 + L.row8, p.lddh, L.ch << 3);                        // VST: row stores (logical piece ch of row r)
   }
   ofs[14] = 0;
   ofs[15] = 0;
 
   // ---- prologue: W2T(0), W13T(0), W2T(1), tile(0); dy^T fragments; chunk 0's first product and SwiGLU derivative alone
-#pragma unroll
-  for (int j = 0; j < MF_W2 / 1024 / MF_NW; ++j) dma_w2(0, 0, j);
-#pragma unroll
-  for (int j = 0; j < MF_W13 / 1024 / MF_NW; ++j) dma_w13(0, 0, j);
-#pragma unroll
-  for (int j = 0; j < MF_W2 / 1024 / MF_NW; ++j) dma_w2(cl(1), 1, j);
-#pragma unroll
-  for (int j = 0; j < 4; ++j) mf_dma(p.h13, ofs[6 + j], hreg_lds + j * 1024);
+  ring.issue_w2(0, 0);
+  ring.issue_w13(0, 0);
+  ring.issue_w2(cl(1), 1);
+  ring.issue_h(0, hoff, hreg_lds);
   Frag<T> dyf[MF_D / 16];
-  const T* dyrow = p.dy + (int64_t)m * p.lddy + 8 * lh;
-#pragma unroll
-  for (int t = 0; t < MF_D / 16; ++t) frag_load_contig<T>(dyf[t], dyrow + 16 * t);
-  f32x16 dx[MF_D / 32];
-#pragma unroll
-  for (int t = 0; t < MF_D / 32; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) dx[t][r] = 0.0f;
+  load_token_frags(dyf, p.dy, m0w + L.li, p.lddy, L.lh);
+  f32x16 dx[MF_NT];
+  zero_acc(dx);
   MF_ST(4)                                                  // (stamp build: requests issued, dy fragments requested)
-  asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
+  wait_all_barrier();
   MF_ST(5)                                                  // (stamp build: the first wait)
   Frag<T> fa[2][4];
   f32x16 dg;
   u32x16 fa0, bfc, bfn, hvv;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) dg[r] = 0.0f;
-#pragma unroll
-  for (int s = 0; s < 4; ++s) nt_frag<T>(fa[0][s], w2slot(0), li, s, lh);
-#pragma unroll
-  for (int s6 = 0; s6 < MF_KT; ++s6) {
-    if (s6 + 1 < MF_KT) {
-#pragma unroll
-      for (int s = 0; s < 4; ++s) nt_frag<T>(fa[(s6 + 1) & 1][s], w2slot(0) + (s6 + 1) * 32 * ROW_BYTES, li, s, lh);
-    }
-#pragma unroll
-    for (int s = 0; s < 4; ++s) mma32<T>(dg, fa[s6 & 1][s], dyf[s6 * 4 + s]);
-  }
+  first_product(dg, fa, ring.w2img(0), dyf, L, [](int) {});
   {
     bf16x8 rb[4];
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
-      const bf16x8 hv = *reinterpret_cast<const bf16x8*>(hreg + nt_off(li, 2 * s + lh));
-      bf16x8 o;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float a1 = (float)hv[e], a3 = (float)hv[4 + e], g = dg[4 * s + e];
-        const float sg = mf_sigmoid<true>(a1), ds = g * sg;
-        o[e] = (T)(ds * a3 * (1.0f + a1 * (1.0f - sg)));
-        o[4 + e] = (T)(ds * a1);
-      }
-      *reinterpret_cast<bf16x8*>(hreg + nt_off(li, 2 * s + lh)) = o;
+      const bf16x8 o = dswiglu_piece(*reinterpret_cast<const bf16x8*>(hreg + nt_off(L.li, 2 * s + L.lh)), dg, s);
+      *reinterpret_cast<bf16x8*>(hreg + nt_off(L.li, 2 * s + L.lh)) = o;
       const u32x4v w = __builtin_bit_cast(u32x4v, o);
 #pragma unroll
       for (int k = 0; k < 4; ++k) bfc[4 * s + k] = w[k];
     }
+    read_tile_rows(rb, hreg, L);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) rb[j] = *reinterpret_cast<const bf16x8*>(hreg + nt_off(j * 8 + row8, ch));
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      fk_st<true>(reinterpret_cast<bf16x8*>(p.dh13 + (int64_t)(m0w + j * 8 + row8) * p.lddh + (ch << 3)), rb[j]);
+    for (int j = 0; j < 4; ++j)                             // whole tiles: no row is past the end; non-temporal like every dh13 store
+      fk_st<true>(reinterpret_cast<bf16x8*>(p.dh13 + (int64_t)(m0w + j * 8 + L.row8) * p.lddh + (L.ch << 3)), rb[j]);
   }
   asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");    // everyone is done with W2T(0); this wave's tile rows are in registers
-#pragma unroll
-  for (int j = 0; j < MF_W2 / 1024 / MF_NW; ++j) dma_w2(cl(2), 0, j);
-#pragma unroll
-  for (int j = 0; j < 4; ++j) mf_dma(p.h13 + (int64_t)cl(1) * 64, ofs[6 + j], hreg_lds + j * 1024);
+  ring.issue_w2(cl(2), 0);
+  ring.issue_h(cl(1), hoff, hreg_lds);
 #pragma unroll
   for (int s = 0; s < 4; ++s) {                                       // A(0)'s first fragments: W2T(1) landed in front of the first barrier
-    const u32x4v w = *reinterpret_cast<const u32x4v*>(w2slot(1) + ax[s]);
+    const u32x4v w = *reinterpret_cast<const u32x4v*>(ring.w2img(1) + ax[s]);
 #pragma unroll
     for (int k = 0; k < 4; ++k) fa0[4 * s + k] = w[k];
   }
 
   MF_ST(0)                                                  // prologue
   for (int c = 0; c < last; ++c) {
-    const char* w2img = w2slot((c + 1) & 1);
-    const char* w13img = w13slot(c & 1);
+    const char* w2img = ring.w2img((c + 1) & 1);
+    const char* w13img = ring.w13img(c & 1);
     // ---- A(c): dg^T(c + 1), 24 MFMAs, fragments one group ahead; the last group behind barrier B(c)
 #pragma unroll
     for (int r = 0; r < 16; ++r) dg[r] = 0.0f;
@@ -491,7 +472,7 @@ __global__ __launch_bounds__(MF_NW * 64, 1) void mlp_bwd_fused_asm_kernel(MlpBwd
     for (int s6 = 0; s6 < MF_KT; ++s6) {
       if (s6 + 1 < MF_KT) {
 #pragma unroll
-        for (int s = 0; s < 4; ++s) nt_frag<T>(fa[(s6 + 1) & 1][s], w2img + (s6 + 1) * 32 * ROW_BYTES, li, s, lh);
+        for (int s = 0; s < 4; ++s) nt_frag<T>(fa[(s6 + 1) & 1][s], w2img + (s6 + 1) * 32 * ROW_BYTES, L.li, s, L.lh);
       } else {
         __builtin_amdgcn_sched_barrier(0);
         MF_ST(1)                                            // first product, groups 0-4
@@ -507,8 +488,8 @@ __global__ __launch_bounds__(MF_NW * 64, 1) void mlp_bwd_fused_asm_kernel(MlpBwd
       }
 #pragma unroll
       for (int s = 0; s < 4; ++s) mma32<T>(dg, fa[s6 & 1][s], dyf[s6 * 4 + s]);
-      dma_w13(cl(c + 1), (c + 1) & 1, 2 * s6);
-      dma_w13(cl(c + 1), (c + 1) & 1, 2 * s6 + 1);
+      ring.dma_w13(cl(c + 1), (c + 1) & 1, 2 * s6);
+      ring.dma_w13(cl(c + 1), (c + 1) & 1, 2 * s6 + 1);
       if (s6 + 1 < MF_KT) __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
       else __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);
       __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
@@ -516,14 +497,14 @@ __global__ __launch_bounds__(MF_NW * 64, 1) void mlp_bwd_fused_asm_kernel(MlpBwd
     }
     MF_ST(3)                                                // group 5
     // ---- B(c): the generated step
-    const unsigned w13a = lds0 + 2 * MF_W2 + (c & 1) * MF_W13, w2a = lds0 + (c & 1) * MF_W2;
+    const unsigned w13a = ring.w13_at(ring.lds0, c & 1), w2a = ring.w2_at(ring.lds0, c & 1);
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
       adr[s] = w13a + ax[s];
       adr[12 + s] = w2a + ax[s];
     }
-    mlpb_step_asm(dx, dg, fa0, bfc, bfn, hvv, adr, ofs, p.w2t + (int64_t)cl(c + 3) * 32 * p.ldw2t, p.h13 + (int64_t)cl(c + 2) * 64,
-                  p.dh13 + (int64_t)(c + 1) * 64, __builtin_amdgcn_readfirstlane(lds0 + ((c + 1) & 1) * MF_W2 + wave * (MF_W2 / MF_NW)), hreg_lds);
+    mlpb_step_asm(dx, dg, fa0, bfc, bfn, hvv, adr, ofs, ring.w2_src(cl(c + 3)), ring.h_src(cl(c + 2)), p.dh13 + (int64_t)(c + 1) * 64,
+                  ring.w2_dst((c + 1) & 1), hreg_lds);
     bfc = bfn;
     MF_ST(6)                                                // the generated step (barrier A inside)
   }
@@ -531,52 +512,19 @@ __global__ __launch_bounds__(MF_NW * 64, 1) void mlp_bwd_fused_asm_kernel(MlpBwd
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");     // W13T(last) and the repeated requests of the tail have landed
   MF_ST(7)
   {
-    const char* w13img = w13slot(last & 1);
-    constexpr int NT12 = MF_D / 32;
     Frag<T> bf[4];
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
       const u32x4v w = {bfc[4 * s], bfc[4 * s + 1], bfc[4 * s + 2], bfc[4 * s + 3]};
       bf[s].v = __builtin_bit_cast(bf16x8, w);
     }
-#pragma unroll
-    for (int s = 0; s < 4; ++s) nt_frag<T>(fa[0][s], w13img, li, s, lh);
-#pragma unroll
-    for (int t = 0; t < NT12; ++t) {
-      if (t + 1 < NT12) {
-#pragma unroll
-        for (int s = 0; s < 4; ++s) nt_frag<T>(fa[(t + 1) & 1][s], w13img, 32 * (t + 1) + li, s, lh);
-      }
-#pragma unroll
-      for (int s = 0; s < 4; ++s) mma32<T>(dx[t], fa[t & 1][s], bf[s]);
-      __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
-      __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
-      __builtin_amdgcn_sched_barrier(0);
-    }
+    second_product(dx, fa, ring.w13img(last & 1), bf, L, [](int) {});
   }
   MF_ST(8)                                                  // the last chunk's second product
   asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");     // every wave has its last fragments: the LDS is free for the dx staging
-
-  // ---- dx: accumulators -> bf16 rows staged in LDS -> 16-byte row stores (as in the kernel above)
-  char* stg = smem + wave * 32 * MF_ROWP;
-#pragma unroll
-  for (int t = 0; t < MF_D / 32; ++t)
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      bf16x4 v;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] = (T)dx[t][4 * g + e];
-      *reinterpret_cast<bf16x4*>(stg + li * MF_ROWP + (32 * t + 8 * g + 4 * lh) * 2) = v;
-    }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  if (lane < MF_D / 8) {
-    for (int r = 0; r < 32; ++r) {
-      const bf16x8 v = *reinterpret_cast<const bf16x8*>(stg + r * MF_ROWP + lane * 16);
-      fk_st<true>(reinterpret_cast<bf16x8*>(p.dx + (int64_t)(m0w + r) * p.lddx + lane * 8), v);
-    }
-  }
+  store_dx(p, dx, L, m0w, m0w + 32);
   MF_ST(9)                                                  // dx epilogue
-  MF_ST_FLUSH
+  MF_ST_FLUSH(L.lane)
 }
 
 
@@ -590,6 +538,12 @@ __global__ __launch_bounds__(MF_NW * 64, 1) void mlp_bwd_fused_asm_kernel(MlpBwd
 //   tiles as whole row segments; the stores of chunk c are issued at the head of chunk c + 1 (from registers), i.e. BEFORE the next weight
 //   request, so that the end-of-chunk wait finds only requests that are a whole chunk old.  Same products and summation order as
 //   gemm_nt_ring2_kernel<.., 1>: bit-identical H13 and G.
+//   This kernel keeps its frame WRITTEN OUT (its own lane ids, request offsets, issue_w, row segments and stores) although
+//   qkv_rope_fused_kernel below has the same frame from LaneIds / FwdRing / row_segments / store_rows: hipcc's schedule of the chunk loop
+//   (where the exponentials and reciprocals of the SwiGLU land between the other VALU work) and its register assignment move with any of
+//   them, and every shared form measured 1.5-2.5 % slower at the cfg2 shape (536-545 us against 526-533; the numbers:
+//   profiles/mlp_fused_shared_scaffolding_ab.txt) — also the one whose chunk loop is the same instruction sequence.  As written it
+//   compiles to the code it has always had; whoever next changes its schedule on purpose can move it onto FwdRing in the same step.
 struct MlpUpArgs {
   const bf16_t* x; const bf16_t* w13; bf16_t* h13; bf16_t* g;
   int64_t ldx, ldw, ldh, ldg;
@@ -597,14 +551,37 @@ struct MlpUpArgs {
 };
 constexpr int MU_NW = 8, MU_TOK = MU_NW * 32;
 constexpr int MU_TILE = MF_KT * 32 * ROW_BYTES;          // one 32-row tile of a chunk: six k-tile images (24 KiB)
-constexpr int MU_SLOT = 2 * MU_TILE;                     // h1 rows + h3 rows (48 KiB)
+constexpr int MU_SLOT = 2 * MU_TILE;                     // two tiles (48 KiB)
 constexpr int MU_HT = 32 * ROW_BYTES, MU_GT = 32 * 64;   // per wave: h13 tile (32 x 128 B), g tile (32 x 64 B)
 constexpr int MU_LDS = 2 * MU_SLOT + MU_NW * (MU_HT + MU_GT);
 static_assert(MU_LDS <= 160 * 1024, "LDS of a CU");
 constexpr int MU_PIECES = MU_SLOT / 1024 / MU_NW;        // 6 requests per wave and chunk
 
+// ---- the forward kernels' weight ring (qkv_rope_fused_kernel; mlp_up_fused_kernel has the same, written out: see there): two slots of
+//      two 32-row tiles each, a chunk = 64 weight rows.  Piece q = wave * 6 + j of a slot is
+//      tile q / 24, k-tile image (q % 24) >> 2, image rows (q & 3) * 8 + row8; wrow(tile, n) says which of the chunk's 64 weight rows image
+//      row n of that tile is.
+struct FwdRing {
+  const bf16_t* w;
+  int64_t ldw;
+  unsigned lds0, woff[MU_PIECES];
+  int wave;
+  template <typename RowMap> FK_DEV FwdRing(const bf16_t* w_, int64_t ldw_, const LaneIds& L, const RowMap& wrow) : w(w_), ldw(ldw_), lds0((unsigned)(uintptr_t)(lds_void_t*)smem), wave(L.wave) {
+#pragma unroll
+    for (int j = 0; j < MU_PIECES; ++j) {
+      const int q = L.wave * MU_PIECES + j, tile = q / 24, s6 = (q % 24) >> 2, n = (q & 3) * 8 + L.row8;
+      woff[j] = (unsigned)((wrow(tile, n) * (int)ldw + s6 * 64 + swz_col(n, L.ch)) * 2);
+    }
+  }
+  FK_DEV void issue_w(int c, int slot) const {
+    const void* gw = w + (int64_t)c * 64 * ldw;
+    const unsigned d = __builtin_amdgcn_readfirstlane(lds0 + slot * MU_SLOT + wave * (MU_SLOT / MU_NW));      // this wave's share of the slot
+#pragma unroll
+    for (int j = 0; j < MU_PIECES; ++j) mf_dma(gw, woff[j], d + j * 1024);
+  }
+};
+
 __global__ __launch_bounds__(MU_NW * 64, 2) void mlp_up_fused_kernel(MlpUpArgs p) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
   using T = bf16_t;
   const int tid = threadIdx.x, lane = tid & 63, li = lane & 31, lh = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -622,7 +599,7 @@ __global__ __launch_bounds__(MU_NW * 64, 2) void mlp_up_fused_kernel(MlpUpArgs p
   for (int j = 0; j < MU_PIECES; ++j) {
     const int q = wave * MU_PIECES + j, tile = q / 24, s6 = (q % 24) >> 2, n = (q & 3) * 8 + row8;
     const int wrow = 8 * (n >> 2) + (n & 3) + 4 * tile;
-    woff[j] = (unsigned)((wrow * (int)p.ldw + s6 * 64 + ((ch ^ ((n >> 1) & 7)) << 3)) * 2);
+    woff[j] = (unsigned)((wrow * (int)p.ldw + s6 * 64 + swz_col(n, ch)) * 2);
   }
   auto issue_w = [&](int c, int slot) __attribute__((always_inline)) {
     const void* gw = p.w13 + (int64_t)c * 64 * p.ldw;
@@ -654,7 +631,7 @@ __global__ __launch_bounds__(MU_NW * 64, 2) void mlp_up_fused_kernel(MlpUpArgs p
   const T* xrow = p.x + (int64_t)mc * p.ldx + 8 * lh;
 #pragma unroll
   for (int t = 0; t < MF_D / 16; ++t) frag_load_contig<T>(xf[t], xrow + 16 * t);
-  asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");     // chunk 0 and the x fragments have landed
+  wait_all_barrier();     // chunk 0 and the x fragments have landed
 
   bf16x8 rbh[4] = {}, rbg[2] = {};
   for (int c = 0; c < nchunks; ++c) {
@@ -728,7 +705,7 @@ __global__ __launch_bounds__(MU_NW * 64, 2) void mlp_up_fused_kernel(MlpUpArgs p
       const int r = j * 16 + (lane >> 2);
       rbg[j] = *reinterpret_cast<const bf16x8*>(gtile + r * 64 + ((((lane & 3) + r) & 3) << 4));
     }
-    asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");   // chunk c + 1 has landed (requested a chunk ago, like the stores in front of it); everyone is done with this slot
+    wait_all_barrier();   // chunk c + 1 has landed (requested a chunk ago, like the stores in front of it); everyone is done with this slot
   }
   if (wave_full) {
 #pragma unroll
@@ -748,9 +725,9 @@ __global__ __launch_bounds__(MU_NW * 64, 2) void mlp_up_fused_kernel(MlpUpArgs p
 
 // ================================================================================================================================
 // The packed q | k | v projection with fused RoPE and pre-scaled queries (what fk_gemm_nt_rope computes) with the token on the lane.
-//   Same frame as mlp_up_fused_kernel: x^T stationary, two waves per SIMD, a chunk = 64 output columns = ONE head (two 32-column
-//   accumulator tiles), no accumulator outlives a chunk.  A lane owns 4 consecutive columns per register group = two complex pairs, so the
-//   rotation is register arithmetic; its (cos, sin) pairs — 16 bytes per register group, 8 groups per chunk, from the lane's own token row
+//   The frame of mlp_up_fused_kernel, from the shared blocks (FwdRing, the stationary x^T, the row-segment stores): two waves per SIMD, a chunk = 64 output
+//   columns = ONE head (two 32-column accumulator tiles), no accumulator outlives a chunk.  A lane owns 4 consecutive columns per register
+//   group = two complex pairs, so the rotation is register arithmetic; its (cos, sin) pairs — 16 bytes per register group, 8 groups per chunk, from the lane's own token row
 //   of the L2-resident table (the pre-scaled copy for the query heads) — are requested at the head of the chunk, in front of the next
 //   weight request, and waited for with a counted vmcnt (loads retire in order: 6 younger requests).  Same products, summation order and
 //   rotation arithmetic as gemm_nt_ring2_kernel<.., 3>: bit-identical output.
@@ -763,63 +740,32 @@ constexpr int QK_LDS = 2 * MU_SLOT + MU_NW * MU_HT;
 static_assert(QK_LDS <= 160 * 1024, "LDS of a CU");
 
 __global__ __launch_bounds__(MU_NW * 64, 2) void qkv_rope_fused_kernel(QkvArgs p) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
   using T = bf16_t;
-  const int tid = threadIdx.x, lane = tid & 63, li = lane & 31, lh = lane >> 5;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int m0w = blockIdx.x * MU_TOK + wave * 32;
-  const int m = m0w + li, mc = m < p.M ? m : p.M - 1;
+  const LaneIds L;
+  const int lh = L.lh;
+  const int m0w = blockIdx.x * MU_TOK + L.wave * 32;
+  const int m = m0w + L.li, mc = m < p.M ? m : p.M - 1;
   const bool wave_full = m0w + 32 <= p.M;
   const int nchunks = p.N / 64, last = nchunks - 1;
-  const int row8 = lane >> 3, ch = lane & 7;
-  const unsigned lds0 = (unsigned)(uintptr_t)(lds_void_t*)smem;
-
-  // requests: piece q = wave * 6 + j: tile q / 24 (columns 0..31 / 32..63 of the head), k-tile image (q % 24) >> 2, image rows (q & 3) * 8 + row8
-  unsigned woff[MU_PIECES];
-#pragma unroll
-  for (int j = 0; j < MU_PIECES; ++j) {
-    const int q = wave * MU_PIECES + j, tile = q / 24, s6 = (q % 24) >> 2, n = (q & 3) * 8 + row8;
-    woff[j] = (unsigned)(((32 * tile + n) * (int)p.ldw + s6 * 64 + ((ch ^ ((n >> 1) & 7)) << 3)) * 2);
-  }
-  auto issue_w = [&](int c, int slot) __attribute__((always_inline)) {
-    const void* gw = p.w + (int64_t)c * 64 * p.ldw;
-    const unsigned d0 = __builtin_amdgcn_readfirstlane(lds0 + slot * MU_SLOT + wave * (MU_SLOT / MU_NW));
-#pragma unroll
-    for (int j = 0; j < MU_PIECES; ++j) mf_dma(gw, woff[j], d0 + j * 1024);
-  };
-  char* htile = smem + 2 * MU_SLOT + wave * MU_HT;
+  // tile 0 / 1: columns 0..31 / 32..63 of the head, image row n = column 32 tile + n
+  const FwdRing ring(p.w, p.ldw, L, [](int tile, int n) { return 32 * tile + n; });
+  char* htile = smem + 2 * MU_SLOT + L.wave * MU_HT;
   T* odst[4];
   bool ook[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int mr = m0w + j * 8 + row8;
-    ook[j] = mr < p.M;
-    odst[j] = p.out + (int64_t)(ook[j] ? mr : p.M - 1) * p.ldo + (ch << 3);
-  }
+  row_segments(odst, ook, p.out, p.ldo, m0w + L.row8, 8, p.M, L.ch << 3);
   // this lane's (cos, sin) row: token mc is position pos_off + mc % T of sample mc / T; the lane's pairs start at pair 2 lh (4 floats per piece)
   const float* trow = p.table + (int64_t)(mc / p.T) * p.table_bs + (int64_t)(p.pos_off + mc % p.T) * 64 + 4 * lh;
 
-  issue_w(0, 0);
+  ring.issue_w(0, 0);
   Frag<T> xf[MF_D / 16];
-  const T* xrow = p.x + (int64_t)mc * p.ldx + 8 * lh;
-#pragma unroll
-  for (int t = 0; t < MF_D / 16; ++t) frag_load_contig<T>(xf[t], xrow + 16 * t);
-  asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");     // chunk 0 and the x fragments have landed
+  load_token_frags(xf, p.x, mc, p.ldx, lh);
+  wait_all_barrier();                                     // chunk 0 and the x fragments have landed
 
   bf16x8 rb[4] = {};
   for (int c = 0; c < nchunks; ++c) {
     const char* t0 = smem + (c & 1) * MU_SLOT;
     const char* t1 = t0 + MU_TILE;
-    if (c > 0) {                                          // the previous head's rows (in registers since its read-back)
-      if (wave_full) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) fk_st<true>(reinterpret_cast<bf16x8*>(odst[j] + (c - 1) * 64), rb[j]);
-      } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          if (ook[j]) fk_st<true>(reinterpret_cast<bf16x8*>(odst[j] + (c - 1) * 64), rb[j]);
-      }
-    }
+    if (c > 0) store_rows<4, true>(odst, ook, wave_full, (c - 1) * 64, rb);      // the previous head's rows (in registers since its read-back)
     const bool rot = c < p.rot_chunks;                    // workgroup-uniform
     f32x4 cs[8];
     if (rot) {
@@ -831,20 +777,20 @@ __global__ __launch_bounds__(MU_NW * 64, 2) void qkv_rope_fused_kernel(QkvArgs p
                    : "=&v"(cs[0]), "=&v"(cs[1]), "=&v"(cs[2]), "=&v"(cs[3]), "=&v"(cs[4]), "=&v"(cs[5]), "=&v"(cs[6]), "=&v"(cs[7])
                    : "v"(tq) : "memory");
     }
-    issue_w(c + 1 < nchunks ? c + 1 : last, (c + 1) & 1);          // that slot was read in chunk c - 1: every wave is past the barrier behind it
+    ring.issue_w(c + 1 < nchunks ? c + 1 : last, (c + 1) & 1);     // that slot was read in chunk c - 1: every wave is past the barrier behind it
     // ---- two accumulator tiles of the head: 48 MFMAs, four fragments read ahead (tile 0 and tile 1 of a k-tile alternate)
     f32x16 acc[2];
 #pragma unroll
     for (int r = 0; r < 16; ++r) { acc[0][r] = 0.0f; acc[1][r] = 0.0f; }
     Frag<T> f[2][4];
 #pragma unroll
-    for (int s = 0; s < 4; ++s) nt_frag<T>(f[0][s], t0, li, s, lh);
+    for (int s = 0; s < 4; ++s) nt_frag<T>(f[0][s], t0, L.li, s, lh);
 #pragma unroll
     for (int gq = 0; gq < 2 * MF_KT; ++gq) {               // group gq: tile gq & 1 of k-tile gq >> 1
       if (gq + 1 < 2 * MF_KT) {
         const char* nx = ((gq + 1) & 1 ? t1 : t0) + ((gq + 1) >> 1) * 32 * ROW_BYTES;
 #pragma unroll
-        for (int s = 0; s < 4; ++s) nt_frag<T>(f[(gq + 1) & 1][s], nx, li, s, lh);
+        for (int s = 0; s < 4; ++s) nt_frag<T>(f[(gq + 1) & 1][s], nx, L.li, s, lh);
       }
 #pragma unroll
       for (int s = 0; s < 4; ++s) mma32<T>(acc[gq & 1], f[gq & 1][s], xf[(gq >> 1) * 4 + s]);
@@ -872,20 +818,12 @@ __global__ __launch_bounds__(MU_NW * 64, 2) void qkv_rope_fused_kernel(QkvArgs p
         bf16x4 o;
 #pragma unroll
         for (int e = 0; e < 4; ++e) o[e] = (T)v[e];
-        *reinterpret_cast<bf16x4*>(htile + nt_off(li, 4 * tl + g4) + 8 * lh) = o;
+        *reinterpret_cast<bf16x4*>(htile + nt_off(L.li, 4 * tl + g4) + 8 * lh) = o;
       }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) rb[j] = *reinterpret_cast<const bf16x8*>(htile + nt_off(j * 8 + row8, ch));
-    asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");   // chunk c + 1 has landed (requested a chunk ago); everyone is done with this slot
+    read_tile_rows(rb, htile, L);
+    wait_all_barrier();                                   // chunk c + 1 has landed (requested a chunk ago); everyone is done with this slot
   }
-  if (wave_full) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) fk_st<true>(reinterpret_cast<bf16x8*>(odst[j] + last * 64), rb[j]);
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      if (ook[j]) fk_st<true>(reinterpret_cast<bf16x8*>(odst[j] + last * 64), rb[j]);
-  }
+  store_rows<4, true>(odst, ook, wave_full, last * 64, rb);
 }
 
 }  // namespace
