@@ -37,6 +37,7 @@ SIGNATURES = {
     "fk_gemm_tn_route": (_int, [_i64, _i64, _i64, _int, _p, _p]),
     "fk_gemm_tn_workspace_bytes": (_sz, [_i64, _i64, _i64, _int]),
     "fk_gemm_tn": (_int, [_p, _i64, _p, _i64, _p, _i64, _i64, _i64, _i64, _int, _int, _p, _sz, _p]),
+    "fk_gemm_tn_swiglu": (_int, [_p, _i64, _p, _i64, _p, _p, _i64, _i64, _i64, _i64, _int, _p, _sz, _p]),
     "fk_colsum_workspace_bytes": (_sz, [_i64, _i64]),
     "fk_colsum": (_int, [_p, _i64, _p, _i64, _i64, _int, _int, _p, _sz, _p]),
     "fk_attn_fwd": (_int, [_p, _p, _p, _p, _p] + [_i64] * 13 + [_int, _i64, _i64, _i64, _p, _p, _f32, _int, _int, _p]),

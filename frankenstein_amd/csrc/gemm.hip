@@ -1256,10 +1256,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_tn_kernel(TnArgs p) {
 // applied on the DMA *source* column (the LDS side of an LDS-DMA is lane-linear).  Wave w: rows 96*(w>>1) of the tile's A
 // columns (3 MFMA tiles) x columns 64*(w&1) (2 tiles).  Requires M % 64 == 0, N1 % 384 == 0, N2 % 128 == 0.
 constexpr int TG_A = 384, TG_B = 128, TG_K = 32;               // 32-row k-stages (32 KiB)
-#ifndef FK_TG_NS
-#define FK_TG_NS 4
-#endif
-constexpr int TG_NS = FK_TG_NS;                           // ring slots: TG_NS - 1 stages in flight
+constexpr int TG_NS = 4;                                  // ring slots: TG_NS - 1 stages requested ahead of the one being multiplied
 constexpr int TG_A_ROW = TG_A * 2, TG_B_ROW = TG_B * 2;
 constexpr int TG_A_BYTES = TG_K * TG_A_ROW, TG_B_BYTES = TG_K * TG_B_ROW, TG_STAGE = TG_A_BYTES + TG_B_BYTES;   // 24 + 8 KiB
 
@@ -1324,17 +1321,15 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_big_kernel(TnArgs p) {
     srcB[j] = (const T*)p.B + (int64_t)(mbeg + row) * p.ldb + b0 + sc / 2;
   }
   const int64_t astep = (int64_t)TG_K * p.lda, bstep = (int64_t)TG_K * p.ldb;
-  auto stage = [&](int buf) {
+  // request j of a stage (A pieces first), with its source's step to the next stage beside it
+  auto piece = [&](int buf, int j) __attribute__((always_inline)) {
     char* as = smem + buf * STAGE;
-#pragma unroll
-    for (int j = 0; j < APW; ++j) {
+    if (j < APW) {
       __builtin_amdgcn_global_load_lds((glb_void_t*)srcA[j], (lds_void_t*)(as + (wave * APW + j) * 1024), 16, 0, 0);
       srcA[j] += astep;
-    }
-#pragma unroll
-    for (int j = 0; j < BPW; ++j) {
-      __builtin_amdgcn_global_load_lds((glb_void_t*)srcB[j], (lds_void_t*)(as + TG_A_BYTES + (wave * BPW + j) * 1024), 16, 0, 0);
-      srcB[j] += bstep;
+    } else {
+      __builtin_amdgcn_global_load_lds((glb_void_t*)srcB[j - APW], (lds_void_t*)(as + TG_A_BYTES + (wave * BPW + j - APW) * 1024), 16, 0, 0);
+      srcB[j - APW] += bstep;
     }
   };
 
@@ -1356,42 +1351,88 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_big_kernel(TnArgs p) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
 
-  // The k-stages stream through TG_NS ring slots with counted waits (see gemm_nt_ring_kernel): stage kt+TG_NS-1 is issued when stage kt
-  // starts computing; `s_waitcnt vmcnt((TG_NS-2) PER)` = this wave's part of stage kt has landed, the barrier = everybody's has and
-  // everybody is done reading the slot refilled next.
-#pragma unroll
-  for (int s = 0; s < TG_NS - 1; ++s)
-    if (s < nk) stage(s);
+  // The k-stages stream through TG_NS ring slots with counted waits (see gemm_nt_ring_kernel), and the stage loop is rotated so that the
+  // matrix pipe never waits for a stage's preamble.  Stage kt, per wave:
+  //   read its k16-step-1 fragments (f1) -> wait for its step-0 fragments (f0, read during stage kt-1) -> step-0 MFMAs
+  //   -> `s_waitcnt vmcnt(PER)` + barrier for stage kt+1: this wave's pieces of it have landed (one younger stage stays in flight: no
+  //      drain), the barrier = everybody's have, and everybody has issued its step-0 MFMAs of stage kt, so has finished reading stage kt-1
+  //   -> step-1 MFMAs, and behind them, a few at a time: stage kt+1's step-0 fragments into f0 (an MFMA has consumed its sources once it
+  //      is issued) and the requests of stage kt+TG_NS-1 into the slot of stage kt-1.
+  // Products per accumulator and their order are those of the plain loop (stage by stage, step 0 then 1): the same bits.
+  static_assert(TG_NS == 4, "the waits below count one stage in flight behind the awaited one");
+  constexpr int NF = 3 + NJ, NM = 3 * NJ;              // fragments per k16-step (2 reads each), MFMAs per k16-step
+  // behind step-1 MFMA m: fragments 2m and 2m+1 of the next stage (they are wanted first), then, from MFMA DMA0 on, one request each; the
+  // last MFMA carries nothing.  Measured against one fragment and one request per MFMA from MFMA 0 on (<192> 4 % slower) and against two or three
+  // fragments per MFMA with the requests from MFMA 0 or 1 on (<192> back at the plain loop's time): profiles/tn_big_pipelined_ab.txt
+  constexpr int RPG = 2, DMA0 = NM - 1 - PER;
+  Frag<T> f0[NF], f1[NF];
+  auto frag = [&](Frag<T>* f, auto S, int q, unsigned bo) __attribute__((always_inline)) {
+    if (q < 3) tg_frag<TG_A_ROW, decltype(S)::value>(f[q], fbase[q] + bo);
+    else tg_frag<B_ROW, decltype(S)::value>(f[q], fbase[q] + bo);
+  };
+  auto mma = [&](Frag<T>* f, int m) __attribute__((always_inline)) {
+#ifndef FK_TN_PROBE_NOMMA             // probe builds: the fetch stream and the fragment reads only
+    mma32<T>(acc[m / NJ][m % NJ], f[m / NJ], f[3 + m % NJ]);
+#endif
+  };
+  using S0 = std::integral_constant<int, 0>;
+  using S1 = std::integral_constant<int, 1>;
   int slot = 0;                                     // ring slot of the stage being computed
-  for (int kt = 0; kt < nk; ++kt) {
-    const int after = nk - 1 - kt;                  // stages behind this one: min(after, TG_NS - 2) of them are in flight
-    if (after >= TG_NS - 2) vm_wait_barrier<(TG_NS - 2) * PER>();
-    else if (after == 3) vm_wait_barrier<3 * PER>();
-    else if (after == 2) vm_wait_barrier<2 * PER>();
-    else if (after == 1) vm_wait_barrier<PER>();
-    else vm_wait_barrier<0>();
-    if (kt + TG_NS - 1 < nk) stage(slot == 0 ? TG_NS - 1 : slot - 1);
+  // NEXT: a stage follows (its wait, barrier and step-0 fragment reads are in this one); DMA: stage kt+TG_NS-1 exists; VM: requests of
+  // this wave that may stay in flight at the wait
+  auto step = [&](auto NEXT, auto DMA, auto VM) __attribute__((always_inline)) {
     const unsigned bo = slot * STAGE;
+    const int prev = slot == 0 ? TG_NS - 1 : slot - 1;
     slot = slot == TG_NS - 1 ? 0 : slot + 1;
-    Frag<T> f0[3 + NJ], f1[3 + NJ];
+    const unsigned nbo = slot * STAGE;
+#ifndef FK_TN_PROBE_HOIST             // probe builds: the fragments are read once, in front of the loop
 #pragma unroll
-    for (int q = 0; q < 3; ++q) tg_frag<TG_A_ROW, 0>(f0[q], fbase[q] + bo);
+    for (int q = 0; q < NF; ++q) frag(f1, S1{}, q, bo);
+#endif
+    lgkm_wait<2 * NF>();                             // f0 has landed (LDS reads return in order); f1 stays in flight
 #pragma unroll
-    for (int q = 0; q < NJ; ++q) tg_frag<B_ROW, 0>(f0[3 + q], fbase[3 + q] + bo);
-#pragma unroll
-    for (int q = 0; q < 3; ++q) tg_frag<TG_A_ROW, 1>(f1[q], fbase[q] + bo);
-#pragma unroll
-    for (int q = 0; q < NJ; ++q) tg_frag<B_ROW, 1>(f1[3 + q], fbase[3 + q] + bo);
-    lgkm_wait<2 * (3 + NJ)>();                       // the first k16-step's fragments (LDS reads return in order)
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) mma32<T>(acc[i][j], f0[i], f0[3 + j]);
+    for (int m = 0; m < NM; ++m) mma(f0, m);
+    __builtin_amdgcn_sched_barrier(0);
+    if constexpr (decltype(NEXT)::value) vm_wait_barrier<decltype(VM)::value>();
     lgkm_wait<0>();
 #pragma unroll
-    for (int i = 0; i < 3; ++i)
+    for (int m = 0; m < NM; ++m) {
+      mma(f1, m);
+      __builtin_amdgcn_sched_barrier(0);
+#ifndef FK_TN_PROBE_HOIST
+      if constexpr (decltype(NEXT)::value)
 #pragma unroll
-      for (int j = 0; j < NJ; ++j) mma32<T>(acc[i][j], f1[i], f1[3 + j]);
+        for (int q = RPG * m; q < RPG * (m + 1); ++q)
+          if (q < NF) frag(f0, S0{}, q, nbo);
+#endif
+#ifndef FK_TN_PROBE_NODMA             // probe builds (tools/build_variant.py NAME gemm.hip -DFK_TN_PROBE_NODMA; tools/gemm_bench.py 7 tn): every stage is read from a slot filled once
+      if constexpr (decltype(DMA)::value) if (m >= DMA0 && m < DMA0 + PER) piece(prev, m - DMA0);
+#endif
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  };
+  using Yes = std::true_type;
+  using No = std::false_type;
+  using Vm0 = std::integral_constant<int, 0>;
+  using Vm1 = std::integral_constant<int, PER>;
+#pragma unroll
+  for (int s = 0; s < TG_NS - 1; ++s)
+    if (s < nk)
+#pragma unroll
+      for (int j = 0; j < PER; ++j) piece(s, j);
+  if (nk > 0) {                                      // a split that starts past M has no stage: it writes its all-zero slab
+    if (nk >= 3) vm_wait_barrier<2 * PER>(); else if (nk == 2) vm_wait_barrier<PER>(); else vm_wait_barrier<0>();
+#pragma unroll
+    for (int q = 0; q < NF; ++q) frag(f0, S0{}, q, 0);
+#ifdef FK_TN_PROBE_HOIST
+#pragma unroll
+    for (int q = 0; q < NF; ++q) frag(f1, S1{}, q, 0);
+#endif
+    int kt = 0;
+    for (; kt + TG_NS - 1 < nk; ++kt) step(Yes{}, Yes{}, Vm1{});
+    if (kt + 2 < nk) { step(Yes{}, No{}, Vm1{}); ++kt; }         // the last stages: nothing left to request, then nothing left in flight
+    if (kt + 1 < nk) step(Yes{}, No{}, Vm0{});
+    step(No{}, No{}, Vm0{});
   }
 
   float* out = (p.nsplit > 1) ? p.ws + (int64_t)split * p.N1 * p.N2 : p.C;
@@ -1411,8 +1452,10 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_big_kernel(TnArgs p) {
   }
 }
 
-// the same sum in the same order (slab 0, 1, 2, ...) on 16-byte vectors with eight slab loads in flight per thread
-__global__ __launch_bounds__(256) void reduce_slabs4_kernel(const float* ws, float* C, int64_t ldc, int N1, int N2, int nsplit, int accumulate) {
+// the same sum in the same order (slab 0, 1, 2, ...) on 16-byte vectors with eight slab loads in flight per thread.  IL: the rows are the
+// SwiGLU-interleaved [up 4 | gate 4] groups of a W13 gradient and go to two destinations: row r -> (r % 8 < 4 ? C : C1) row (r / 8) * 4 + r % 4
+template <bool IL>
+__global__ __launch_bounds__(256) void reduce_slabs4_kernel(const float* ws, float* C, float* C1, int64_t ldc, int N1, int N2, int nsplit, int accumulate) {
   const int64_t total = (int64_t)N1 * N2, total4 = total >> 2;
   const int n2v = N2 >> 2;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total4; i += (int64_t)gridDim.x * blockDim.x) {
@@ -1427,7 +1470,13 @@ __global__ __launch_bounds__(256) void reduce_slabs4_kernel(const float* ws, flo
       for (int u = 0; u < 8; ++u) s += v[u];
     }
     for (; k < nsplit; ++k) s += src[(int64_t)k * total4];
-    f32x4* dst = reinterpret_cast<f32x4*>(C + (i / n2v) * ldc + (i % n2v) * 4);
+    int64_t r = i / n2v;
+    float* base = C;
+    if constexpr (IL) {
+      if (r & 4) base = C1;
+      r = (r >> 3) * 4 + (r & 3);
+    }
+    f32x4* dst = reinterpret_cast<f32x4*>(base + r * ldc + (i % n2v) * 4);
     if (accumulate) s += *dst;
     *dst = s;
   }
@@ -1690,8 +1739,9 @@ size_t fk_gemm_tn_workspace_bytes(int64_t M, int64_t N1, int64_t N2, int dtype) 
   return ns > 1 ? (size_t)ns * N1 * N2 * sizeof(float) : 0;
 }
 
-int fk_gemm_tn(const void* A, int64_t lda, const void* B, int64_t ldb, float* C, int64_t ldc, int64_t M, int64_t N1,
-               int64_t N2, int accumulate, int dtype, void* workspace, size_t workspace_bytes, void* stream) {
+// C1 != nullptr: the SwiGLU-interleaved rows of the result are added to the two gradients C (up) and C1 (gate) by the slab reduction
+static int launch_tn(const void* A, int64_t lda, const void* B, int64_t ldb, float* C, float* C1, int64_t ldc, int64_t M, int64_t N1,
+                     int64_t N2, int accumulate, int dtype, void* workspace, size_t workspace_bytes, void* stream) {
   FK_CHECK_ARG(dtype == FK_F32 || dtype == FK_BF16, "fk_gemm_tn: bad dtype %d", dtype);
   const int vec = dtype == FK_BF16 ? 8 : 4;
   FK_CHECK_ARG(M > 0 && N1 > 0 && N2 > 0, "fk_gemm_tn: empty problem");
@@ -1705,6 +1755,9 @@ int fk_gemm_tn(const void* A, int64_t lda, const void* B, int64_t ldb, float* C,
   const bool big = tb != 0;
   const size_t need = ns > 1 ? (size_t)ns * N1 * N2 * sizeof(float) : 0;
   FK_CHECK_ARG(workspace_bytes >= need && (need == 0 || workspace), "fk_gemm_tn: workspace too small (%zu < %zu)", workspace_bytes, need);
+  if (C1)
+    FK_CHECK_ARG(ns > 1 && N1 % 8 == 0 && N2 % 4 == 0 && ldc % 4 == 0 && (((uintptr_t)C | (uintptr_t)C1 | (uintptr_t)workspace) & 15) == 0,
+                 "fk_gemm_tn_swiglu: needs a split plan (see fk_gemm_tn_route), N1 %% 8 == 0, N2 %% 4 == 0 and 16-byte aligned destinations");
   TnArgs p{A, B, C, (float*)workspace, lda, ldb, ldc, (int)M, (int)N1, (int)N2, (int)rps, ns, accumulate};
   dim3 grid((unsigned)(fk_cdiv(N1, BM) * fk_cdiv(N2, BN) * ns)), block(NTHREADS);
   hipStream_t s = (hipStream_t)stream;
@@ -1724,7 +1777,8 @@ int fk_gemm_tn(const void* A, int64_t lda, const void* B, int64_t ldb, float* C,
     if (N2 % 4 == 0 && ldc % 4 == 0 && (((uintptr_t)C | (uintptr_t)workspace) & 15) == 0) {
       int nb = (int)fk_cdiv(total / 4, 256);
       if (nb > 2048) nb = 2048;
-      hipLaunchKernelGGL(reduce_slabs4_kernel, dim3(nb), dim3(256), 0, s, (const float*)workspace, C, ldc, (int)N1, (int)N2, ns, accumulate);
+      if (C1) hipLaunchKernelGGL(reduce_slabs4_kernel<true>, dim3(nb), dim3(256), 0, s, (const float*)workspace, C, C1, ldc, (int)N1, (int)N2, ns, accumulate);
+      else hipLaunchKernelGGL(reduce_slabs4_kernel<false>, dim3(nb), dim3(256), 0, s, (const float*)workspace, C, C1, ldc, (int)N1, (int)N2, ns, accumulate);
     } else {
       int nb = (int)fk_cdiv(total, 256);
       if (nb > 2048) nb = 2048;
@@ -1733,6 +1787,17 @@ int fk_gemm_tn(const void* A, int64_t lda, const void* B, int64_t ldb, float* C,
     FK_CHECK_LAUNCH("fk_gemm_tn(reduce)");
   }
   return FK_OK;
+}
+
+int fk_gemm_tn(const void* A, int64_t lda, const void* B, int64_t ldb, float* C, int64_t ldc, int64_t M, int64_t N1,
+               int64_t N2, int accumulate, int dtype, void* workspace, size_t workspace_bytes, void* stream) {
+  return launch_tn(A, lda, B, ldb, C, nullptr, ldc, M, N1, N2, accumulate, dtype, workspace, workspace_bytes, stream);
+}
+
+int fk_gemm_tn_swiglu(const void* A, int64_t lda, const void* B, int64_t ldb, float* d_up, float* d_gate, int64_t ldc, int64_t M,
+                      int64_t H, int64_t N2, int dtype, void* workspace, size_t workspace_bytes, void* stream) {
+  FK_CHECK_ARG(d_up && d_gate && H > 0 && H % 4 == 0, "fk_gemm_tn_swiglu: needs both destinations and H %% 4 == 0");
+  return launch_tn(A, lda, B, ldb, d_up, d_gate, ldc, M, 2 * H, N2, 1, dtype, workspace, workspace_bytes, stream);
 }
 
 size_t fk_colsum_workspace_bytes(int64_t rows, int64_t cols) { return (size_t)colsum_blocks(rows) * cols * sizeof(float); }

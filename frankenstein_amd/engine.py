@@ -91,7 +91,9 @@ def wgrad(a: Tensor, b: Tensor, params: Sequence[Tensor], swiglu_interleaved: bo
     with torch.cuda.stream(side if side is not None else torch.cuda.current_stream()):
         Kd = b.shape[1]
         adjacent = all(grads[i + 1].data_ptr() == grads[i].data_ptr() + grads[i].numel() * 4 for i in range(len(grads) - 1))
-        if swiglu_interleaved:
+        if swiglu_interleaved and K.gemm_tn_swiglu_ok(a, b, grads[0], grads[1]):
+            K.gemm_tn_swiglu_(a, b, grads[0], grads[1])            # the slab reduction adds the de-interleaved rows to both gradients
+        elif swiglu_interleaved:
             dw = K.gemm_tn(a, b)                                   # [2H, K] interleaved rows
             H = params[0].shape[0]
             v = dw.view(H // 4, 8 * Kd)

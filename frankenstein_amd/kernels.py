@@ -241,6 +241,29 @@ def gemm_tn(a: Tensor, b: Tensor, out: Optional[Tensor] = None, accumulate: bool
     return out
 
 
+def gemm_tn_swiglu_ok(a: Tensor, b: Tensor, d_up: Tensor, d_gate: Tensor) -> bool:
+    """gemm_tn_swiglu_ takes this problem: a split plan (the slab reduction does the de-interleaving) and vector-aligned destinations."""
+    M, N1 = a.shape
+    N2 = b.shape[1]
+    return (gemm_tn_route(M, N1, N2, a.dtype)[1] > 1 and N1 % 8 == 0 and N2 % 4 == 0 and d_up.is_contiguous() and d_gate.is_contiguous()
+            and d_up.data_ptr() % 16 == 0 and d_gate.data_ptr() % 16 == 0)
+
+
+def gemm_tn_swiglu_(a: Tensor, b: Tensor, d_up: Tensor, d_gate: Tensor) -> None:
+    """d_up, d_gate ([H, N2] fp32 each) += the de-interleaved rows of a[M, 2H]^T @ b[M, N2], a's columns in the SwiGLU-interleaved
+    [up 4 | gate 4] order: what gemm_tn into a temporary and two add2d_ compute, written by the slab reduction itself."""
+    assert a.dim() == 2 and b.dim() == 2 and a.shape[0] == b.shape[0] and a.dtype == b.dtype
+    assert a.stride(1) == 1 and b.stride(1) == 1
+    M, N1 = a.shape
+    N2 = b.shape[1]
+    for d in (d_up, d_gate):
+        assert d.shape == (N1 // 2, N2) and d.dtype == torch.float32 and d.is_contiguous()
+    ws, nb = _ws(lib().fk_gemm_tn_workspace_bytes(M, N1, N2, fk_dtype(a)), a.device)
+    with _timed(f"gemm_tn_swiglu:{M}x{N1}x{N2}"):
+        call("fk_gemm_tn_swiglu", a.data_ptr(), a.stride(0), b.data_ptr(), b.stride(0), d_up.data_ptr(), d_gate.data_ptr(), N2, M, N1 // 2,
+             N2, fk_dtype(a), _ptr(ws), nb, _stream())
+
+
 def colsum(x: Tensor, out: Optional[Tensor] = None, accumulate: bool = False) -> Tensor:
     assert x.dim() == 2 and x.stride(1) == 1
     rows, cols = x.shape

@@ -108,6 +108,13 @@ int fk_gemm_nt_route(int64_t M, int64_t N, int64_t K, int dtype, int vec_epi, in
 size_t fk_gemm_tn_workspace_bytes(int64_t M, int64_t N1, int64_t N2, int dtype);
 int fk_gemm_tn(const void* A, int64_t lda, const void* B, int64_t ldb, float* C, int64_t ldc, int64_t M, int64_t N1,
                int64_t N2, int accumulate, int dtype, void* workspace, size_t workspace_bytes, void* stream);
+/* fk_gemm_tn_swiglu: the gradient of a SwiGLU-interleaved W13 ([2H, N2]: groups of 4 up rows, 4 gate rows), ADDED to the two plain
+ *   gradients: d_up[(r / 8) * 4 + r % 4] += row r for r % 8 < 4, d_gate likewise for r % 8 >= 4 (both [H, N2] fp32, leading dimension
+ *   ldc).  The slab reduction writes both (slabs summed in order, then + destination: the bits of fk_gemm_tn into a temporary followed
+ *   by fk_add2d).  Needs a split plan (fk_gemm_tn_route(M, 2H, N2): nsplit > 1) and 16-byte aligned destinations with N2 % 4 == 0,
+ *   ldc % 4 == 0; workspace as for fk_gemm_tn(M, 2H, N2).                                                                          */
+int fk_gemm_tn_swiglu(const void* A, int64_t lda, const void* B, int64_t ldb, float* d_up, float* d_gate, int64_t ldc, int64_t M,
+                      int64_t H, int64_t N2, int dtype, void* workspace, size_t workspace_bytes, void* stream);
 /* fk_gemm_tn_route: what fk_gemm_tn does with a shape (host only): returns 0 for the 128 x 128 kernel, 128 or 192 for the large-tile
  *   kernel (its B columns per tile); *nsplit = the number of row splits (slabs summed in order when > 1), *rows_per_split = the rows
  *   of a split: split s covers rows [s * rows_per_split, min(M, (s + 1) * rows_per_split)), which may be empty.  Either may be NULL. */

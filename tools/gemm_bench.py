@@ -1,5 +1,6 @@
 """Isolated timing of every GEMM shape of the cfg2 step (per encoder layer), interleaved rounds in one process.
-Usage: python tools/gemm_bench.py [rounds]   -> one line per shape: us, TFLOP/s, algorithmic GB/s."""
+Usage: python tools/gemm_bench.py [rounds] [prefix]   -> one line per shape (those whose name starts with prefix, e.g. tn): us, TFLOP/s,
+algorithmic GB/s."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -31,6 +32,8 @@ cases = {
     "tn dW_proj   384x384": (lambda: K.gemm_tn(dy, x), 2 * M * 384 * 384, M * (384 + 384) * 2),
 }
 rounds = int(sys.argv[1]) if len(sys.argv) > 1 else 5
+if len(sys.argv) > 2:
+    cases = {k: v for k, v in cases.items() if k.startswith(sys.argv[2])}
 for f, _, _ in cases.values():
     f()
 torch.cuda.synchronize()
