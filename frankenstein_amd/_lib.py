@@ -78,6 +78,7 @@ SIGNATURES = {
     "fk_beam_backtrack": (_int, [_p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _i64, _p, _i64, _i64, _i64, _i64, _p, _p, _p]),
     "fk_sample_topk_eos": (_int, [_p, _i64, _i64, _i64, _f32, _i64, _p, _p, _p, _p, _p, _i64, _i64, _p, _i64, _p, _p, _p, _p, _p]),
     "fk_sample_topp": (_int, [_p, _i64, _i64, _i64, _f32, _i64, _f32, _p, _p, _p, _p, _p, _i64, _i64, _p, _i64, _p, _p, _p, _p, _p]),
+    "fk_logit_rules": (_int, [_p, _i64, _i64, _i64, _f32, _i64, _i64, _i64, _p, _p, _p, _p, _i64, _i64, _i64, _p, _i64, _i64, _int, _p]),
     "fk_im2col1d": (_int, [_p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _int, _p]),
     "fk_col2im1d": (_int, [_p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _int, _p]),
     "fk_elu_fwd": (_int, [_p, _p, _i64, _int, _p]),

@@ -10,6 +10,8 @@
 //                       LOCAL slots, fk_kv_append folded into the attention launch, one select block per sentence + a ticket
 //   fk_beam_select_eos / fk_beam_backtrack / fk_sample_topk_eos   end-of-text: finished beams and rows, length-normalised ranking, a live
 //                       count for the host's early exit, and the walk through the logs on the device
+//   fk_logit_rules      repetition penalty, n-gram ban and minimum length on the fp32 logits, in front of the sampling / fk_beam_topk launch;
+//                       it keeps the token history of every row on the device (two buffers swapped by step parity under a beam search)
 // The select, the beam attention and the sampling are one kernel template each, and so are their host sides (beam_select,
 // check_ / launch_attn_decode_beam and sample_topk behind the kernels): the entry points of a family share their checks and their launch.
 #include "fk_common.h"
@@ -334,8 +336,9 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_topk_kernel(const float
     for (int i = i0; i < i1; ++i) {
       const float x = row[i] * inv_temp;
       if (f32_sortable(x) >= kth) {
-        acc += __expf(x - mx);
-        pick = i;                                         // last kept index seen: the fallback when rounding leaves acc <= target
+        const float e = __expf(x - mx);
+        acc += e;
+        if (e > 0.0f) pick = i;                           // last kept index WITH MASS seen: the fallback when rounding leaves acc <= target
         if (acc > target) break;
       }
     }
@@ -344,7 +347,13 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_topk_kernel(const float
   __syncthreads();
   if (tid == 0) {
     int w = winner;
-    if (w < 0) {                                          // target >= total by rounding: the last kept index
+    if (w < 0) {                                          // target >= total by rounding: the last kept index with mass (a -inf entry is kept by the
+      for (int i = V - 1; i >= 0; --i) {                  // crop whenever top_k is off, and is never a token to emit)
+        const float x = row[i] * inv_temp;
+        if (f32_sortable(x) >= kth && __expf(x - mx) > 0.0f) { w = i; break; }
+      }
+    }
+    if (w < 0) {                                          // a row without any mass (all -inf, NaN): the last kept index, as ever
       for (int i = V - 1; i >= 0; --i)
         if (f32_sortable(row[i] * inv_temp) >= kth) { w = i; break; }
     }
@@ -365,6 +374,90 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_topk_kernel(const float
       }
     }
   }
+}
+
+// ---- rules that depend on the tokens already emitted (include/franken_hip.h, fk_logit_rules, has the rule).  One block per logits row, the
+// threads stride over the row's history h[0 .. L), L = t0 + *step, which this launch first brings up to date and copies into LDS:
+//   plain (hist_b == NULL): the row's buffer gets cur[r] at column L - 1 (step > 0);
+//   beam: the buffers swap by the parity of the step: new[r, :L-1] = old[g * W + clamp(parent_log[step - 1, r]), :L-1], new[r, L-1] = cur[r],
+//         so no block reads what another block of the launch writes; `broadcast` (the first step: one logits row per sentence) reads row g * W
+//         and appends nothing.
+// Then read-all, barrier, write-all: every history position loads the logit of its token, the block meets, and the penalised values are
+// stored, so a token that occurs several times is penalised once and its occurrences store the same value; behind a second barrier the
+// bans store -inf, which therefore win over the penalty.  A step counter that is negative, past the history buffer or (beam) past the logs
+// leaves the launch without any write.
+constexpr int RULES_THREADS = 256, RULES_MAX_HIST = 4096;
+
+__global__ __launch_bounds__(RULES_THREADS) void logit_rules_kernel(float* logits, int64_t ld, int V, float p, float inv_p, int n, int m, int eos, const int64_t* step,
+                                                                    const int64_t* cur, int32_t* hist_a, int32_t* hist_b, int64_t hist_ld, int t0,
+                                                                    const int32_t* parent_log, int64_t log_rows, int W, int broadcast) {
+  __shared__ int32_t h[RULES_MAX_HIST];
+  __shared__ float zs[RULES_MAX_HIST];
+  const int r = blockIdx.x, tid = threadIdx.x;
+  const int64_t s = step[0];
+  const bool beam = hist_b != nullptr;
+  if (s < 0 || (int64_t)t0 + s > hist_ld || (int64_t)t0 + s > RULES_MAX_HIST || (beam && s > log_rows)) return;      // block-uniform
+  const int L = t0 + (int)s;
+  const int32_t* src;
+  int32_t* dst;
+  bool append = s > 0;
+  if (!beam) {
+    src = dst = hist_a + (int64_t)r * hist_ld;
+  } else {
+    int32_t* nw = (s & 1) ? hist_b : hist_a;
+    int32_t* od = (s & 1) ? hist_a : hist_b;
+    if (broadcast) {
+      src = dst = nw + (int64_t)r * W * hist_ld;
+      append = false;
+    } else if (!append) {
+      src = dst = nw + (int64_t)r * hist_ld;
+    } else {
+      int pr = parent_log[(s - 1) * (int64_t)gridDim.x + r];
+      pr = pr < 0 ? 0 : (pr >= W ? W - 1 : pr);           // a corrupt log reads a wrong row of its own sentence, never outside the buffer
+      src = od + (int64_t)((r / W) * W + pr) * hist_ld;
+      dst = nw + (int64_t)r * hist_ld;
+    }
+  }
+  for (int j = tid; j < L; j += RULES_THREADS) {
+    int32_t v;
+    if (append && j == L - 1) {
+      const int64_t c = cur[r];
+      v = (c < 0 || c >= V) ? -1 : (int32_t)c;
+      dst[j] = v;
+    } else {
+      v = src[j];
+      if (dst != src) dst[j] = v;
+    }
+    h[j] = v;
+  }
+  __syncthreads();
+  float* z = logits + (int64_t)r * ld;
+  if (p != 1.0f) {                                        // block-uniform
+    for (int j = tid; j < L; j += RULES_THREADS) {
+      const int v = h[j];
+      if (v >= 0 && v < V && v != eos) zs[j] = z[v];
+    }
+    __syncthreads();
+    for (int j = tid; j < L; j += RULES_THREADS) {
+      const int v = h[j];
+      if (v >= 0 && v < V && v != eos) {
+        const float x = zs[j];
+        z[v] = x > 0.0f ? x * inv_p : x * p;              // one fp32 multiply: the host restatement agrees bit for bit
+      }
+    }
+    __syncthreads();
+  }
+  if (n >= 1 && L >= n) {
+    const int32_t* tail = h + (L - n + 1);                // the last n - 1 tokens
+    for (int i = n - 1 + tid; i < L; i += RULES_THREADS) {
+      const int v = h[i];
+      if (v < 0 || v >= V || v == eos) continue;
+      bool match = true;
+      for (int c = 0; c < n - 1; ++c) match = match && h[i - n + 1 + c] == tail[c];
+      if (match) z[v] = -INFINITY;
+    }
+  }
+  if (tid == 0 && eos >= 0 && eos < V && s < (int64_t)m) z[eos] = -INFINITY;
 }
 
 // ---- beam search on the caches (models/gpt2_model.py:355-416).  The W beams share ONE set of caches [W, Tmax, 2d]: slot b holds the rows
@@ -931,6 +1024,33 @@ int fk_sample_topp(const float* logits, int64_t ld, int64_t B, int64_t V, float 
   FK_CHECK_ARG(eos < (1LL << 31), "fk_sample_topp: need eos < 2^31 (eos=%lld)", (long long)eos);
   const EosArgs ea{eos < 0 ? -1 : (int)eos, done, len, nullptr, 0, live_acc, live};
   return sample_topk<true, true>("fk_sample_topp", ptrs, logits, ld, B, V, temperature, top_k, top_p, seed, step, pos_inc, cur, out, out_ld, out_cols, ticket, ea, stream);
+}
+
+int fk_logit_rules(float* logits, int64_t ld, int64_t R, int64_t V, float penalty, int64_t ngram, int64_t min_new, int64_t eos, const int64_t* step,
+                   const int64_t* cur, int32_t* hist, int32_t* hist2, int64_t hist_ld, int64_t t0, int64_t steps, const int32_t* parent_log,
+                   int64_t log_rows, int64_t W, int broadcast, void* stream) {
+  FK_CHECK_ARG(logits && step && cur && hist, "fk_logit_rules: null pointer");
+  FK_CHECK_ARG((hist2 == nullptr) == (parent_log == nullptr), "fk_logit_rules: hist2 and parent_log select the beam mode together (both or none)");
+  FK_CHECK_ARG(R > 0 && R < 65536 && V > 0 && V < (1LL << 31) && ld >= V, "fk_logit_rules: bad arguments (R=%lld V=%lld ld=%lld)", (long long)R, (long long)V,
+               (long long)ld);
+  FK_CHECK_ARG(penalty > 0.0f && penalty <= 3.402823466e38f, "fk_logit_rules: need a finite penalty > 0 (penalty=%g)", (double)penalty);      // refuses NaN as well
+  FK_CHECK_ARG(ngram >= 0 && ngram < (1LL << 31) && min_new >= 0 && min_new < (1LL << 31) && eos < (1LL << 31),
+               "fk_logit_rules: need 0 <= ngram, min_new < 2^31 and eos < 2^31 (ngram=%lld min_new=%lld eos=%lld)", (long long)ngram, (long long)min_new, (long long)eos);
+  FK_CHECK_ARG(t0 >= 0 && steps >= 0 && t0 + steps <= RULES_MAX_HIST && hist_ld >= t0 + steps,
+               "fk_logit_rules: a history row holds t0 + steps <= %d ids and hist_ld >= that (t0=%lld steps=%lld hist_ld=%lld)", RULES_MAX_HIST, (long long)t0,
+               (long long)steps, (long long)hist_ld);
+  if (hist2) {
+    FK_CHECK_ARG(W >= 1 && W <= BEAM_MAX_W && log_rows >= 0, "fk_logit_rules: need 1 <= W <= %d and log_rows >= 0 (W=%lld log_rows=%lld)", BEAM_MAX_W, (long long)W,
+                 (long long)log_rows);
+    FK_CHECK_ARG(broadcast ? R * W < 65536 : R % W == 0, "fk_logit_rules: the rows are S sentences x W beams, or S with broadcast (R=%lld W=%lld)", (long long)R, (long long)W);
+  } else {
+    FK_CHECK_ARG(!broadcast, "fk_logit_rules: broadcast belongs to the beam mode");
+  }
+  const float inv_p = (float)(1.0 / (double)penalty);
+  hipLaunchKernelGGL(logit_rules_kernel, dim3((unsigned)R), dim3(RULES_THREADS), 0, (hipStream_t)stream, logits, ld, (int)V, penalty, inv_p, (int)ngram, (int)min_new,
+                     eos < 0 ? -1 : (int)eos, step, cur, hist, hist2, hist_ld, (int)t0, parent_log, log_rows, (int)W, broadcast);
+  FK_CHECK_LAUNCH("fk_logit_rules");
+  return FK_OK;
 }
 
 }  // extern "C"

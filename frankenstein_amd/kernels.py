@@ -698,6 +698,63 @@ def sample_topp(logits: Tensor, temperature: float, top_k: Optional[int], top_p:
     return _sample_topk_call("fk_sample_topp", logits, temperature, top_k, state, cur, out, pos_inc, *tail, top_p=top_p)
 
 
+LOGIT_RULES_MAX_HISTORY = 4096                  # the envelope of fk_logit_rules: prompt + new tokens of a row
+
+
+def inv_penalty(penalty: float):
+    """(p, 1 / p) as the fp32 values fk_logit_rules multiplies by: p rounded to fp32, 1 / p computed in float64 and rounded once."""
+    p = torch.tensor(float(penalty), dtype=torch.float32)
+    return float(p), float((1.0 / p.double()).to(torch.float32))
+
+
+class LogitRules:
+    """The rules of fk_logit_rules and the device-side token history they read: repetition_penalty p (with inv_p, both fp32 values),
+    no_repeat_ngram_size n, min_new_tokens m, the end-of-text id e (-1: none), and hist int32 [rows, t0 + steps] whose first t0 columns
+    hold `prompt` (int64 [S, t0]) and which the kernel appends to.  width = W: the state of a beam search, rows = S * W (every beam of a
+    sentence starts from its prompt) and a second buffer hist2, swapped with hist by the parity of the step."""
+
+    def __init__(self, prompt: Tensor, steps: int, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, min_new_tokens: int = 0,
+                 eos: Optional[int] = None, width: Optional[int] = None):
+        assert prompt.dim() == 2
+        S, t0 = prompt.shape
+        assert t0 + steps <= LOGIT_RULES_MAX_HISTORY, f"fk_logit_rules holds histories of up to {LOGIT_RULES_MAX_HISTORY} tokens, got {t0 + steps}"
+        self.p, self.inv_p = inv_penalty(repetition_penalty)
+        self.n, self.m, self.e = int(no_repeat_ngram_size), int(min_new_tokens), -1 if eos is None else int(eos)
+        self.t0, self.steps, self.width = t0, int(steps), width
+        rows = S * (width or 1)
+        self.hist = torch.empty((rows, t0 + self.steps), dtype=torch.int32, device=prompt.device)
+        self.hist[:, :t0] = prompt.to(torch.int32) if width is None else prompt.to(torch.int32).repeat_interleave(width, dim=0)
+        self.hist2 = None if width is None else torch.empty_like(self.hist)
+
+
+def logit_rules_(logits: Tensor, rules: LogitRules, step: Tensor, cur: Tensor, parent_log: Optional[Tensor] = None, broadcast: bool = False) -> Tensor:
+    """Repetition penalty, n-gram ban and minimum length on fp32 logits [R, V] (row stride >= V) in place, one launch in front of the
+    sampling / beam_topk launch (fk_logit_rules has the rule).  step int64 [1]: the device-side count of generated tokens (SampleState.step,
+    BeamState.step); cur int64 [rows]: the tokens of the previous step, which the kernel appends to rules.hist before it applies the rules.
+    Beam mode (rules.width = W, parent_log = BeamState.parent_log): the histories follow the parents of the last select; broadcast=True is
+    the first step, logits [S, V], one row per sentence."""
+    assert logits.dim() == 2 and logits.dtype == torch.float32 and logits.stride(1) == 1
+    R, V = logits.shape
+    rows = rules.hist.shape[0]
+    assert step.dtype == torch.int64 and step.numel() == 1
+    assert cur.dtype == torch.int64 and cur.is_contiguous() and cur.numel() == rows
+    assert rules.hist.dtype == torch.int32 and rules.hist.stride(1) == 1
+    if rules.width is None:
+        assert parent_log is None and not broadcast and R == rows
+        tail = (None, 0, 0, 0)
+        hist2 = None
+    else:
+        W = rules.width
+        assert parent_log is not None and parent_log.dtype == torch.int32 and parent_log.dim() == 2 and parent_log.is_contiguous()
+        assert parent_log.shape[1] == rows and R == (rows // W if broadcast else rows)
+        assert rules.hist2.shape == rules.hist.shape and rules.hist2.stride() == rules.hist.stride()
+        tail = (parent_log.data_ptr(), parent_log.shape[0], W, int(bool(broadcast)))
+        hist2 = rules.hist2
+    call("fk_logit_rules", logits.data_ptr(), logits.stride(0), R, V, rules.p, rules.n, rules.m, rules.e, step.data_ptr(), cur.data_ptr(),
+         rules.hist.data_ptr(), _ptr(hist2), rules.hist.stride(0), rules.t0, rules.steps, *tail, _stream())
+    return logits
+
+
 def attn_decode(qkv: Tensor, kv: Tensor, pos: Tensor, n_head: int) -> Tensor:
     """one causal query per sample against the cache rows 0..pos[0]: q = qkv[:, :d] -> o [B, d]."""
     B, d3 = qkv.shape

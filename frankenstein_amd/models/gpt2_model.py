@@ -10,6 +10,7 @@ configure_optimizers :286-310, estimate_mfu :312-326, generate :328-353).
 from __future__ import annotations
 
 import math
+import numbers
 from dataclasses import dataclass
 
 import torch
@@ -371,12 +372,85 @@ class GPT(nn.Module):
         return None if float(top_p) >= 1.0 else float(top_p)
 
     @staticmethod
-    def _sample(logits, temperature, top_k, state=None, top_p=None):
+    def _check_logit_rules(repetition_penalty, no_repeat_ngram_size, min_new_tokens, eos_token_id, vocab_size, total_len, keep):
+        """The arguments of the history rules (_apply_logit_rules), checked before any GPU work.  All three at their defaults: None comes back
+        and the calls are those without them; otherwise the keyword arguments of _apply_logit_rules.  repetition_penalty must be finite and
+        > 0, the other two integers >= 0, min_new_tokens needs an eos_token_id, and since the rules can remove at most total_len + 1 tokens
+        (total_len = prompt + new tokens) the vocabulary must keep `keep` (the top-k of the draw) candidates: V - (total_len + 1) >= keep."""
+        try:
+            p = float(repetition_penalty)
+        except (TypeError, ValueError):
+            raise ValueError(f"repetition_penalty must be a finite number > 0, got {repetition_penalty!r}") from None
+        if not (math.isfinite(p) and p > 0.0):
+            raise ValueError(f"repetition_penalty must be a finite number > 0, got {repetition_penalty!r}")
+        for name, v in (("no_repeat_ngram_size", no_repeat_ngram_size), ("min_new_tokens", min_new_tokens)):
+            if isinstance(v, bool) or not isinstance(v, numbers.Integral) or v < 0:
+                raise ValueError(f"{name} must be an integer >= 0, got {v!r}")
+        n, m = int(no_repeat_ngram_size), int(min_new_tokens)
+        if m > 0 and eos_token_id is None:
+            raise ValueError("min_new_tokens needs an eos_token_id: it keeps that token from being emitted")
+        if p == 1.0 and n == 0 and m == 0:
+            return None
+        if vocab_size - (int(total_len) + 1) < max(int(keep), 1):
+            raise ValueError(f"the rules can remove up to {int(total_len) + 1} tokens of a vocabulary of {vocab_size}: fewer than {max(int(keep), 1)} candidates may be left")
+        return dict(repetition_penalty=p, no_repeat_ngram_size=n, min_new_tokens=m, eos_token_id=None if eos_token_id is None else int(eos_token_id))
+
+    @staticmethod
+    def _device_rules(rules, prompt, steps, width=None):
+        """the device-side state (K.LogitRules) of the checked rules `rules` (_check_logit_rules), or None"""
+        if rules is None:
+            return None
+        if prompt.shape[1] + steps > K.LOGIT_RULES_MAX_HISTORY:
+            raise ValueError(f"the history rules on the caches hold up to {K.LOGIT_RULES_MAX_HISTORY} tokens per row, got {prompt.shape[1] + steps}")
+        return K.LogitRules(prompt, steps, rules["repetition_penalty"], rules["no_repeat_ngram_size"], rules["min_new_tokens"], rules["eos_token_id"], width)
+
+    @staticmethod
+    def _apply_logit_rules(logits, history, generated, repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, eos_token_id=None):
+        """The rules that depend on the tokens already emitted, as torch ops (the restatement of fk_logit_rules, include/franken_hip.h, bit for
+        bit): logits fp32 [B, V], history int [B, L] (prompt ids, then the generated tokens; the brain prefix is not part of it), generated =
+        the number of generated tokens.  In this order, before the temperature:
+        1. every distinct in-range token v of the history except the end-of-text id: z[v] = z[v] * (1 / p) if z[v] > 0 else z[v] * p, one fp32
+           multiply with 1 / p rounded once from float64; 2. with n = no_repeat_ngram_size >= 1 and L >= n, every token that would complete
+           an n-gram the history already holds (its last n - 1 tokens, followed by that token) becomes -inf, except the end-of-text id;
+        3. while generated < min_new_tokens the end-of-text id is -inf.  A banned token is -inf whatever 1 made of it; ids outside [0, V)
+        are ignored.  The end-of-text id is exempt from 1 and 2, unlike the usual implementations: Franky's prompt is that marker itself, and
+        penalising it would push every sentence away from ending.  Defaults: the input comes back as it is."""
+        p, n, m = float(repetition_penalty), int(no_repeat_ngram_size), int(min_new_tokens)
+        if p == 1.0 and n == 0 and m == 0:
+            return logits
+        z = logits.float().clone()
+        B, V = z.shape
+        e = -1 if eos_token_id is None else int(eos_token_id)
+        h = history.long().to(z.device)
+        L = h.shape[1]
+        ok = (h >= 0) & (h < V) & (h != e)                              # the positions whose token a rule may touch
+        at = torch.where(ok, h, torch.full_like(h, V))                  # everything else lands in a column behind the row
+        if p != 1.0 and L > 0:
+            pf, inv = (torch.tensor(x, dtype=torch.float32, device=z.device) for x in K.inv_penalty(p))
+            seen = torch.zeros((B, V + 1), dtype=torch.bool, device=z.device).scatter_(1, at, True)[:, :V]
+            z = torch.where(seen, torch.where(z > 0, z * inv, z * pf), z)
+        if n >= 1 and L >= n:
+            match = torch.ones((B, L - n + 1), dtype=torch.bool, device=z.device)
+            if n > 1:                                                   # window j = h[j .. j+n-2] against the last n - 1 tokens, j = 0 .. L - n
+                match = (h.unfold(1, n - 1, 1)[:, :L - n + 1] == h[:, None, L - n + 1:]).all(-1)
+            hit = torch.where(match, at[:, n - 1:], torch.full_like(at[:, n - 1:], V))
+            banned = torch.zeros((B, V + 1), dtype=torch.bool, device=z.device).scatter_(1, hit, True)[:, :V]
+            z = z.masked_fill(banned, -float('Inf'))
+        if generated < m and 0 <= e < V:
+            z[:, e] = -float('Inf')
+        return z
+
+    @staticmethod
+    def _sample(logits, temperature, top_k, state=None, top_p=None, rules=None, history=None, generated=0):
         """temperature -> top-k crop -> [nucleus crop] -> softmax -> multinomial (models/gpt2_model.py:340-351).  On the device this is ONE
         launch (fk_sample_topk or, with top_p, fk_sample_topp; Philox keyed by a seed drawn from torch's generator); the torch-op form is
         kept for host tensors.  top_p: of the tokens the top-k crop keeps, token i stays iff the tokens with a strictly larger logit hold
-        less than top_p of the kept probability (include/franken_hip.h, fk_sample_topp)."""
+        less than top_p of the kept probability (include/franken_hip.h, fk_sample_topp).
+        rules (the dict _check_logit_rules returns, or None) with history [B, L] and generated: those rules run first, as torch ops (the
+        paths whose token ids the Python loop holds; the cached paths run fk_logit_rules instead and pass no rules here)."""
         top_p = GPT._check_top_p(top_p)
+        if rules is not None:
+            logits = GPT._apply_logit_rules(logits, history, generated, **rules)
         if logits.is_cuda:
             lg = logits.float()
             lg = lg if lg.stride(-1) == 1 else lg.contiguous()
@@ -397,7 +471,7 @@ class GPT(nn.Module):
 
     @torch.no_grad()
     def generate(self, idx, max_new_tokens, prefix=None, temperature=1.0, top_k=None, use_cache=True, use_graph=None, eos_token_id=None,
-                 check_every=8, top_p=None):
+                 check_every=8, top_p=None, repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0):
         """Sampling loop of the reference (models/gpt2_model.py:328-353: temperature, top-k crop, softmax, multinomial; returns
         the first sample's ids).  With use_cache (default) the prefix + prompt are run once and every new token is one
         incremental step against per-layer key/value caches; with use_graph (default: on from 64 new tokens, where the one-off
@@ -411,19 +485,29 @@ class GPT(nn.Module):
         [B, t0 + max_new_tokens], last_lengths [B] (generated tokens, the id counted once) and last_steps (steps run).
         top_p: nucleus sampling behind the top-k crop, on every path: of the tokens the crop keeps, the smallest set of most likely ones whose
         probability reaches top_p stays (ties with its last member stay too; _sample has the rule).  None or 1.0: off, the calls and the
-        tokens of a torch seed are those without it; outside (0, 1] raises."""
+        tokens of a torch seed are those without it; outside (0, 1] raises.
+        repetition_penalty / no_repeat_ngram_size / min_new_tokens: rules on the tokens already emitted (prompt and generated; not the
+        prefix), applied to the logits before the temperature on every path (_apply_logit_rules has the rule; on the caches it is one more
+        launch, K.logit_rules_, which keeps the history on the device): seen tokens are penalised once, a token that would repeat an n-gram
+        of that size is never emitted, and the end-of-text id is never emitted among the first min_new_tokens.  The end-of-text id is
+        exempt from the first two, a deliberate departure from the usual implementations: Franky's prompt is that marker itself.  On the
+        caches a row's history (prompt + new tokens) holds up to 4096 tokens (K.LOGIT_RULES_MAX_HISTORY); a longer one raises ValueError
+        before any GPU work.  All three at their defaults: off, the calls and the tokens are those without them."""
         top_p = self._check_top_p(top_p)
         B, t0 = idx.shape
+        rules = self._check_logit_rules(repetition_penalty, no_repeat_ngram_size, min_new_tokens, eos_token_id, self.config.vocab_size,
+                                        t0 + max_new_tokens, top_k or 1)
         t_ctx = 0 if prefix is None else prefix.shape[1]
         total = t_ctx + t0 + max_new_tokens
         cached = use_cache and total <= self.config.block_size and max_new_tokens > 0
         if use_graph is None:
             use_graph = max_new_tokens >= 64
         if eos_token_id is not None:
-            return self._generate_eos(idx, max_new_tokens, prefix, temperature, top_k, cached, use_graph, int(eos_token_id), int(check_every), top_p)
+            return self._generate_eos(idx, max_new_tokens, prefix, temperature, top_k, cached, use_graph, int(eos_token_id), int(check_every), top_p, rules)
         state = K.SampleState(idx.device) if idx.is_cuda else None      # one Philox stream per call, seeded from torch's generator
         if cached and use_graph and idx.is_cuda:                        # _generate_dev draws its own seed BEHIND this one: keep both, or the tokens of a torch seed move
-            return self._generate_dev(idx, max_new_tokens, prefix, temperature, top_k, True, top_p=top_p)
+            return self._generate_dev(idx, max_new_tokens, prefix, temperature, top_k, True, top_p=top_p, rules=rules)
+        dev_rules = self._device_rules(rules, idx, max_new_tokens) if cached and idx.is_cuda else None      # refuses before the prefill runs
         if cached:
             d = self.config.n_embd
             cache = [torch.empty((B, total, 2 * d), dtype=E.compute_dtype(), device=idx.device) for _ in self.transformer.h]
@@ -436,7 +520,13 @@ class GPT(nn.Module):
                 idx_cond = idx if idx.size(1) <= self.config.block_size else idx[:, -self.config.block_size:]
                 _, lg = self(idx_cond, prefix=prefix)
                 logits = lg[:, -1, :]
-            idx = torch.cat((idx, self._sample(logits, temperature, top_k, state, top_p)), dim=1)
+            if dev_rules is not None:                                   # the sampler advances state.step, which counts the generated tokens
+                logits = logits.float()
+                logits = K.logit_rules_(logits if logits.stride(-1) == 1 else logits.contiguous(), dev_rules, state.step, idx[:, -1].contiguous())
+                tok = self._sample(logits, temperature, top_k, state, top_p)
+            else:
+                tok = self._sample(logits, temperature, top_k, state, top_p, rules, idx, it)
+            idx = torch.cat((idx, tok), dim=1)
         return idx[0]
 
     @staticmethod
@@ -476,12 +566,15 @@ class GPT(nn.Module):
         return n
 
     @torch.no_grad()
-    def _generate_dev(self, idx, max_new_tokens, prefix, temperature, top_k, use_graph, eos=None, check_every=None, top_p=None):
+    def _generate_dev(self, idx, max_new_tokens, prefix, temperature, top_k, use_graph, eos=None, check_every=None, top_p=None, rules=None):
         """generate on the caches with the position on the device: prefill, then a step that is embed -> blocks -> head -> one sampling
         launch, which writes cur / out[:, step] and advances both the step counter and `pos` (_run_steps).  eos: K.sample_topk_eos is
         that launch (done rows, lengths and the live count live on the device) and last_tokens / last_lengths / last_steps are set.
-        top_p (a float below 1, or None): K.sample_topp is that launch, with or without eos."""
+        top_p (a float below 1, or None): K.sample_topp is that launch, with or without eos.
+        rules (_check_logit_rules): K.logit_rules_ runs in front of that launch, on the prefill logits and inside the step; it reads the step
+        counter of the sampler and its `cur`, so it records into the captured step like everything else."""
         (B, t0), dev, d = idx.shape, idx.device, self.config.n_embd
+        lr = self._device_rules(rules, idx, max_new_tokens)
         t_ctx = 0 if prefix is None else prefix.shape[1]
         cache = [torch.empty((B, t_ctx + t0 + max_new_tokens, 2 * d), dtype=E.compute_dtype(), device=dev) for _ in self.transformer.h]
         logits0, pos0 = self._cached_logits(idx, cache, 0, None if prefix is None else _prep(prefix))
@@ -494,6 +587,8 @@ class GPT(nn.Module):
         es = None if eos is None else K.SampleEosState(dev, B, eos)
 
         def sample(logits, pos_inc=None):
+            if lr is not None:
+                K.logit_rules_(logits, lr, state.step, cur)
             if top_p is not None:
                 K.sample_topp(logits, temperature, top_k, top_p, state, es, cur=cur, out=out, pos_inc=pos_inc)
             elif es is None:
@@ -512,14 +607,14 @@ class GPT(nn.Module):
         return tokens[0]
 
     @torch.no_grad()
-    def _generate_eos(self, idx, max_new_tokens, prefix, temperature, top_k, cached, use_graph, eos, check_every, top_p=None):
+    def _generate_eos(self, idx, max_new_tokens, prefix, temperature, top_k, cached, use_graph, eos, check_every, top_p=None, rules=None):
         """generate with an end-of-text id.  On the caches it is _generate_dev; the re-forward loop applies the same rule with torch.where
         on the host."""
         assert 0 <= eos < self.config.vocab_size, f"eos_token_id {eos} outside the vocabulary"
         assert check_every >= 1
         B, dev = idx.shape[0], idx.device
         if cached and idx.is_cuda:
-            return self._generate_dev(idx, max_new_tokens, prefix, temperature, top_k, use_graph, eos, check_every, top_p)
+            return self._generate_dev(idx, max_new_tokens, prefix, temperature, top_k, use_graph, eos, check_every, top_p, rules)
         state = K.SampleState(dev) if idx.is_cuda else None
         done = torch.zeros(B, dtype=torch.bool, device=dev)
         lens = torch.zeros(B, dtype=torch.int64, device=dev)
@@ -529,7 +624,7 @@ class GPT(nn.Module):
                 break
             idx_cond = idx if idx.size(1) <= self.config.block_size else idx[:, -self.config.block_size:]
             _, lg = self(idx_cond, prefix=prefix)
-            tok = torch.where(done, torch.full_like(lens, eos), self._sample(lg[:, -1, :], temperature, top_k, state, top_p).view(-1))
+            tok = torch.where(done, torch.full_like(lens, eos), self._sample(lg[:, -1, :], temperature, top_k, state, top_p, rules, idx, n).view(-1))
             lens += (~done).long()
             done = done | (tok == eos)
             idx = torch.cat((idx, tok[:, None]), dim=1)
@@ -540,7 +635,7 @@ class GPT(nn.Module):
 
     @torch.no_grad()
     def generate_beam_search(self, idx, max_new_tokens, prefix, temperature=1.0, topk=20, beam_width=5, use_cache=False, use_graph=None, seeds=None,
-                             eos_token_id=None, length_penalty=0.0, check_every=8):
+                             eos_token_id=None, length_penalty=0.0, check_every=8, repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0):
         """Stochastic beam search of the reference (models/gpt2_model.py:355-416): every step each of the `beam_width` beams draws
         `beam_width` continuations WITHOUT replacement from its `topk` most likely tokens, the `beam_width` best-scoring
         (cumulative log-probability) of the beam_width^2 candidates survive; returns the best beam's ids.
@@ -556,9 +651,15 @@ class GPT(nn.Module):
         length and draws nothing more; candidates and final beams are ranked by score / length^alpha (length = generated tokens, the id
         counted once); the search stops once every beam of every sentence is finished, which the host asks the device every `check_every`
         steps.  The result is padded with the id to t0 + max_new_tokens; last_beams / last_beam_scores (raw sums) are ordered best
-        first, last_beam_lengths and last_steps are set as well.  Both arguments at their defaults: the search above, unchanged."""
+        first, last_beam_lengths and last_steps are set as well.  Both arguments at their defaults: the search above, unchanged.
+        repetition_penalty / no_repeat_ngram_size / min_new_tokens: the rules of generate (_apply_logit_rules) on every beam's own history,
+        applied to its logits before the temperature and the log-softmax; the end-of-text id is exempt from the first two (a deliberate
+        departure from the usual implementations).  On the caches it is one more launch in front of K.beam_topk, which also carries the
+        histories along with the beams (K.logit_rules_).  All three at their defaults: off, the calls are those without them."""
         if topk is None:
             topk = 2 * beam_width
+        rules = self._check_logit_rules(repetition_penalty, no_repeat_ngram_size, min_new_tokens, eos_token_id, self.config.vocab_size,
+                                        idx.shape[1] + max_new_tokens, topk)
         self.eval()
         total = (0 if prefix is None else prefix.shape[1]) + idx.shape[1] + max_new_tokens
         in_envelope = (use_cache and idx.is_cuda and max_new_tokens > 0 and total <= self.config.block_size
@@ -571,19 +672,23 @@ class GPT(nn.Module):
             check_every = int(check_every)
         if in_envelope:
             return self._beam_search_cached(idx, max_new_tokens, prefix, temperature, topk, beam_width, use_graph, seeds, eos,
-                                            float(length_penalty), check_every, eos_mode)
+                                            float(length_penalty), check_every, eos_mode, rules)
         if eos_mode:
-            return self._beam_search_host_eos(idx, max_new_tokens, prefix, temperature, topk, beam_width, eos, float(length_penalty), check_every)
+            return self._beam_search_host_eos(idx, max_new_tokens, prefix, temperature, topk, beam_width, eos, float(length_penalty), check_every, rules)
         S = idx.shape[0]
         if S > 1:
+            kw = {} if rules is None else {k: v for k, v in rules.items() if k != "eos_token_id"}
             return torch.stack([self.generate_beam_search(idx[g:g + 1], max_new_tokens, None if prefix is None else prefix[g:g + 1], temperature,
-                                                          topk, beam_width) for g in range(S)])
+                                                          topk, beam_width, **kw) for g in range(S)])
         beams = idx.repeat(beam_width, 1)
         scores = torch.zeros(beam_width, device=idx.device)
         prefix = prefix.expand(beam_width, -1, -1)
-        for _ in range(max_new_tokens):
+        for it in range(max_new_tokens):
             _, logits = self(beams, prefix=prefix.contiguous())
-            logp = torch.log_softmax(logits[:, -1, :].float() / temperature, dim=-1)
+            last = logits[:, -1, :].float()
+            if rules is not None:
+                last = self._apply_logit_rules(last, beams, it, **rules)
+            logp = torch.log_softmax(last / temperature, dim=-1)
             top_lp, top_ix = logp.topk(topk, dim=-1)
             picks = torch.multinomial(top_lp.exp(), beam_width, replacement=False)           # [beam, beam_width] indices into top-k
             cand_score = (scores[:, None] + top_lp.gather(1, picks)).reshape(-1)
@@ -596,7 +701,7 @@ class GPT(nn.Module):
 
     @torch.no_grad()
     def _beam_search_cached(self, idx, max_new_tokens, prefix, temperature, topk, W, use_graph, seeds, eos=None, alpha=0.0, check_every=None,
-                            eos_mode=False):
+                            eos_mode=False, rules=None):
         """generate_beam_search for S >= 1 sentences on per-layer caches [S * W, total, 2d] that are never reordered: row g * W + b is beam b
         of sentence g, slot b of a sentence holds the rows its beam position b wrote, the int32 ancestry table names the slot (counted
         inside the sentence, so the sentences cannot read each other's rows) of every row of every beam, and the select kernel rewrites
@@ -610,9 +715,12 @@ class GPT(nn.Module):
         beam order; S > 1: S such lists) and last_beam_scores are set and the best beam of every sentence is returned.
         eos_mode (an end-of-text id `eos` or a length penalty `alpha`): K.beam_select_eos is the select (one block per sentence, S = 1
         included), the live count is read every `check_every` steps, and K.beam_backtrack replaces the host's walk: the ids come back
-        ranked, [S, W, t0 + max_new_tokens], padded behind the steps that ran; last_beam_lengths and last_steps are set as well."""
+        ranked, [S, W, t0 + max_new_tokens], padded behind the steps that ran; last_beam_lengths and last_steps are set as well.
+        rules (_check_logit_rules): K.logit_rules_ runs in front of both K.beam_topk calls; it follows the parents in the log of the last
+        select, so every row's history is that of the beam it now continues."""
         dev, d = idx.device, self.config.n_embd
         S, t0 = idx.shape
+        lr = self._device_rules(rules, idx, max_new_tokens, width=W)
         p0 = (0 if prefix is None else prefix.shape[1]) + t0
         total = p0 + max_new_tokens
         if use_graph is None:
@@ -629,12 +737,18 @@ class GPT(nn.Module):
         top_id = torch.empty((S * W, topk), dtype=torch.int64, device=dev)
         lg0 = logits0.float()
         # first step: the beams of a sentence are its one prefilled sequence and draw from the same row; no row has been appended, the table stays
-        K.beam_topk(lg0 if lg0.stride(-1) == 1 else lg0.contiguous(), temperature, topk, top_lp[:S], top_id[:S])
+        lg0 = lg0 if lg0.stride(-1) == 1 else lg0.contiguous()
+        if lr is not None:
+            K.logit_rules_(lg0, lr, state.step, cur, state.parent_log, broadcast=True)
+        K.beam_topk(lg0, temperature, topk, top_lp[:S], top_id[:S])
         select(top_lp[:S], top_id[:S], state, cur, torch.tensor([-1], dtype=torch.int32, device=dev), broadcast=True)
         pos = torch.tensor([p0], dtype=torch.int32, device=dev)
 
         def step():
-            K.beam_topk(self._decode_logits_dev(cur, cache, pos, state.anc, groups=groups), temperature, topk, top_lp, top_id)
+            lg = self._decode_logits_dev(cur, cache, pos, state.anc, groups=groups)
+            if lr is not None:
+                K.logit_rules_(lg, lr, state.step, cur, state.parent_log)
+            K.beam_topk(lg, temperature, topk, top_lp, top_id)
             select(top_lp, top_id, state, cur, pos, pos_inc=pos)
 
         steps = self._run_steps(step, max_new_tokens, use_graph, state.live if eos_mode else None, check_every)
@@ -664,7 +778,7 @@ class GPT(nn.Module):
         return torch.tensor(best[0] if S == 1 else best, dtype=idx.dtype, device=dev)
 
     @torch.no_grad()
-    def _beam_search_host_eos(self, idx, max_new_tokens, prefix, temperature, topk, W, eos, alpha, check_every):
+    def _beam_search_host_eos(self, idx, max_new_tokens, prefix, temperature, topk, W, eos, alpha, check_every, rules=None):
         """The re-forward loop of generate_beam_search with the end-of-text rules (_beam_step_host), sentence by sentence; draws by
         torch.multinomial.  Sets last_beams, last_beam_scores, last_beam_lengths (best first) and last_steps like the cached search."""
         S, t0 = idx.shape
@@ -684,7 +798,10 @@ class GPT(nn.Module):
                     break
                 cond = beams if beams.size(1) <= self.config.block_size else beams[:, -self.config.block_size:]
                 _, logits = self(cond, prefix=pf)
-                logp = torch.log_softmax(logits[:, -1, :].float() / temperature, dim=-1)
+                last = logits[:, -1, :].float()
+                if rules is not None:
+                    last = self._apply_logit_rules(last, beams, n, **rules)
+                logp = torch.log_softmax(last / temperature, dim=-1)
                 top_lp, top_ix = logp.topk(topk, dim=-1)
                 picks = torch.multinomial(top_lp.exp(), W, replacement=False)
                 parent, tok, scores, lens, fin = _beam_step_host(top_lp, top_ix, picks, scores, lens, fin, -1 if eos is None else eos, table)

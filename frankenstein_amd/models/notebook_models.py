@@ -74,18 +74,23 @@ class Franky(nn.Module):
         return self.llm_model.forward(idx=new_idx, prefix=features, targets=targets)
 
     @torch.no_grad()
-    def generate(self, x, max_new_tokens=25, temperature=1.0, top_k=10, eot=50256, stop=False, top_p=None):
+    def generate(self, x, max_new_tokens=25, temperature=1.0, top_k=10, eot=50256, stop=False, top_p=None, repetition_penalty=1.0,
+                 no_repeat_ngram_size=0, min_new_tokens=0):
         """x: numpy [T, C].  Returns generated token ids (the notebook's version is unfinished; this one runs).
         stop=True ends a sentence at its first generated `eot` (what the notebook's cell tried with its undefined stop_tokens): the ids come
         back trimmed behind that token; x: numpy [S, T, C] then decodes S trials, returns [S, 1 + max_new_tokens] padded with `eot` and sets
         last_lengths [S] (generated tokens, `eot` included).
-        top_p: nucleus sampling behind the top-k crop (GPT.generate), with and without stop; None or 1.0: off, outside (0, 1] raises."""
+        top_p: nucleus sampling behind the top-k crop (GPT.generate), with and without stop; None or 1.0: off, outside (0, 1] raises.
+        repetition_penalty / no_repeat_ngram_size / min_new_tokens: GPT.generate's rules on the tokens already emitted.  `eot`, which is the
+        prompt here, is exempt from the penalty and from the n-gram ban (a deliberate departure from the usual implementations: penalising
+        it would push every sentence away from ending); min_new_tokens keeps it from being emitted too early and needs stop=True."""
         self.llm_model._check_top_p(top_p)                                  # before the encoder runs
+        rules = self._rules(repetition_penalty, no_repeat_ngram_size, min_new_tokens, eot if stop else None, max_new_tokens, top_k or 1)
         if stop:
             xin = torch.from_numpy(x if x.ndim == 3 else x[None]).to(self.device).float()
             prefix = self.brain_model(xin)
             ids = torch.full((xin.shape[0], 1), eot, dtype=torch.long, device=self.device)
-            self.llm_model.generate(ids, max_new_tokens, prefix=prefix, temperature=temperature, top_k=top_k, eos_token_id=eot, top_p=top_p)
+            self.llm_model.generate(ids, max_new_tokens, prefix=prefix, temperature=temperature, top_k=top_k, eos_token_id=eot, top_p=top_p, **rules)
             self.last_lengths = self.llm_model.last_lengths.cpu()           # int64 on the host, as generate_beam leaves it
             if x.ndim == 3:
                 return self.llm_model.last_tokens
@@ -93,11 +98,17 @@ class Franky(nn.Module):
         xin = torch.from_numpy(x[None]).to(self.device).float()
         prefix = self.brain_model(xin)
         ids = torch.full((1, 1), eot, dtype=torch.long, device=self.device)
-        return self.llm_model.generate(ids, max_new_tokens, prefix=prefix, temperature=temperature, top_k=top_k, top_p=top_p)
+        return self.llm_model.generate(ids, max_new_tokens, prefix=prefix, temperature=temperature, top_k=top_k, top_p=top_p, **rules)
+
+    def _rules(self, repetition_penalty, no_repeat_ngram_size, min_new_tokens, eos, max_new_tokens, keep):
+        """GPT._check_logit_rules for a prompt of one token, before the encoder runs -> the keyword arguments to pass on ({}: all off)"""
+        rules = self.llm_model._check_logit_rules(repetition_penalty, no_repeat_ngram_size, min_new_tokens, eos, self.llm_model.config.vocab_size,
+                                                  1 + max_new_tokens, keep)
+        return {} if rules is None else {k: v for k, v in rules.items() if k != "eos_token_id"}
 
     @torch.no_grad()
     def generate_beam(self, x, max_new_tokens=25, temperature=1.0, topk=20, beam_width=5, eot=50256, batch_sentences=None, stop=False,
-                      length_penalty=0.0):
+                      length_penalty=0.0, repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0):
         """x: numpy [T, C].  Brain features -> prefix -> the stochastic beam search of the decoder on its key/value caches
         (GPT.generate_beam_search, use_cache=True).  Returns the best beam's ids, `eot` first.
         x: numpy [S, T, C] decodes S trials and returns ids [S, 1 + max_new_tokens]: the encoder and the search run in chunks of
@@ -105,14 +116,18 @@ class Franky(nn.Module):
         weight-streaming route of the decode step).
         stop=True makes `eot` the end-of-text id of the search (finished beams, ranking by score / length^length_penalty, early exit):
         [T, C] returns the best beam trimmed behind its first generated `eot`, [S, T, C] the padded [S, 1 + max_new_tokens] and sets
-        last_lengths [S]."""
+        last_lengths [S].
+        repetition_penalty / no_repeat_ngram_size / min_new_tokens: GPT.generate_beam_search's rules on every beam's own tokens; `eot` is
+        exempt from the penalty and the n-gram ban (see generate), min_new_tokens needs stop=True."""
+        rules = self._rules(repetition_penalty, no_repeat_ngram_size, min_new_tokens, eot if stop else None, max_new_tokens,
+                            2 * beam_width if topk is None else topk)
         eos_kw = dict(eos_token_id=eot if stop else None, length_penalty=length_penalty) if (stop or length_penalty != 0.0) else {}
         if x.ndim == 2:
             xin = torch.from_numpy(x[None]).to(self.device).float()
             prefix = self.brain_model(xin)
             ids = torch.full((1, 1), eot, dtype=torch.long, device=self.device)
             out = self.llm_model.generate_beam_search(ids, max_new_tokens, prefix, temperature=temperature, topk=topk, beam_width=beam_width,
-                                                      use_cache=True, **eos_kw)
+                                                      use_cache=True, **eos_kw, **rules)
             if eos_kw:
                 self.last_lengths = torch.tensor([self.llm_model.last_beam_lengths[0]])
             return out[:1 + int(self.last_lengths[0])] if stop else out
@@ -124,7 +139,7 @@ class Franky(nn.Module):
             prefix = self.brain_model(xin)
             ids = torch.full((xin.shape[0], 1), eot, dtype=torch.long, device=self.device)
             out = self.llm_model.generate_beam_search(ids, max_new_tokens, prefix, temperature=temperature, topk=topk, beam_width=beam_width,
-                                                      use_cache=True, **eos_kw)
+                                                      use_cache=True, **eos_kw, **rules)
             outs.append(out.view(xin.shape[0], -1))
             if eos_kw:
                 lens = self.llm_model.last_beam_lengths

@@ -356,6 +356,37 @@ int fk_sample_topp(const float* logits, int64_t ld, int64_t B, int64_t V, float 
                    int64_t* step, int32_t* pos_inc, int64_t* cur, int64_t* out, int64_t out_ld, int64_t out_cols, uint32_t* ticket, int64_t eos,
                    int32_t* done, int32_t* len, uint32_t* live_acc, int32_t* live, void* stream);
 
+/* ---- rules that depend on the tokens already emitted: repetition penalty, n-gram ban, minimum length.
+ * fk_logit_rules rewrites fp32 logits [R, V] (row stride ld >= V; nothing at or behind column V is touched) in place, in front of
+ *   fk_sample_topk / _eos / fk_sample_topp or fk_beam_topk, and keeps the token history of every row on the device.  One block per row.
+ *   Per row: z = the row's logits, h[0 .. L) = its history (the prompt ids, then the tokens generated so far), g = *step = the number of
+ *   generated tokens, L = t0 + g, e = eos (eos < 0: none), p = penalty, inv_p = 1 / p computed in float64 and rounded once to fp32.
+ *   The rules run in this order, before any temperature:
+ *   1. Repetition.  For every distinct token v in h with 0 <= v < V and v != e:  z[v] = z[v] > 0 ? z[v] * inv_p : z[v] * p, exactly one fp32
+ *      multiply; a token that occurs several times is penalised once.  penalty == 1 leaves every logit as it is.
+ *   2. n-gram ban, n = ngram >= 1 and L >= n: for every j in [0, L - n] with h[j .. j+n-2] == h[L-n+1 .. L-1] (ids compared as they are),
+ *      z[h[j+n-1]] = -inf unless that token is e or outside [0, V).  n = 1 bans every token of h; L < n bans nothing.
+ *   3. Minimum length: while g < min_new and 0 <= e < V, z[e] = -inf.
+ *   4. A token that 2 or 3 bans is -inf whatever 1 made of it.
+ *   History ids outside [0, V) are never used as an index; NaN logits stay NaN unless banned.  e is exempt from 1 and 2 on purpose (a
+ *   prompt that is the end-of-text marker itself must not push every sentence away from ending).
+ *   The history is int32, row stride hist_ld >= t0 + steps, t0 + steps <= 4096; the caller fills columns [0, t0) of every row of `hist`
+ *   with the prompt before step 0 and the kernel appends: at *step > 0 column L - 1 gets cur[r], the token the previous sampling / select
+ *   launch wrote (-1 if it lies outside [0, V)), before the rules are applied.
+ *   Plain mode (hist2 == NULL and parent_log == NULL): rows never move, row r of `hist` is row r's history.
+ *   Beam mode (both given): the rows are S sentences x W beams, r = g*W + b, which fk_beam_select* reorders every step, so two buffers
+ *   [S*W, hist_ld] swap by the parity of *step: new = (*step odd ? hist2 : hist), old = the other, and at *step > 0
+ *   new[r][:L-1] = old[g*W + clamp(parent_log[(*step-1)*R + r], 0, W-1)][:L-1], new[r][L-1] = cur[r]; no block reads what another block of
+ *   the launch writes.  broadcast != 0 is the first step, R = S logits rows: row g uses the history in row g*W of the buffer of the step's
+ *   parity and appends nothing (so every row of `hist` holds its sentence's prompt).  parent_log: the int32 [log_rows, S*W] log of the select.
+ *   *step < 0, t0 + *step > min(hist_ld, 4096) or (beam mode) *step > log_rows: the launch writes nothing at all, neither history nor logits.
+ *   Refused: a null logits / step / cur / hist, hist2 without parent_log or the reverse, R or V out of range, ld < V, a penalty that is
+ *   not finite or <= 0, ngram or min_new < 0, hist_ld < t0 + steps, t0 + steps > 4096, W outside 1 .. 16 in beam mode, R not a multiple of W
+ *   there (without broadcast), broadcast in plain mode.                                                                             */
+int fk_logit_rules(float* logits, int64_t ld, int64_t R, int64_t V, float penalty, int64_t ngram, int64_t min_new, int64_t eos, const int64_t* step,
+                   const int64_t* cur, int32_t* hist, int32_t* hist2, int64_t hist_ld, int64_t t0, int64_t steps, const int32_t* parent_log,
+                   int64_t log_rows, int64_t W, int broadcast, void* stream);
+
 /* ---- VQ-VAE tokenizer convolutions (models/vq_brain.py), channels-last [B, T, C], causal left padding dil*(K-1):
  * fk_im2col1d: cols[b, t, k, :] = x[b, t*stride + k*dil - pad, :] (zeros outside), Tout = (T-1)/stride + 1, so that
  *   CausalConv1d (:22-28) = fk_gemm_nt(cols, W') with W'[o, k*Cin + c] = W[o, c, k], and CausalConvTranspose1d(kernel 2s,

@@ -6,6 +6,8 @@
     python tools/decode_bench.py --model gpt2 --beam 5 --sentences 1,2,3,4,8,16 --new-tokens 25    # S sentences in one search vs S searches
     python tools/decode_bench.py --model gpt2 --beam 5 --eos --new-tokens 25         # end-of-text: step, poll, early exit, device backtrack
     python tools/decode_bench.py --model gpt2 --batch 1 --top-p 0.9                  # nucleus sampling: the step with and without top_p
+    python tools/decode_bench.py --model gpt2 --batch 1 --repetition-penalty 1.3 --no-repeat-ngram 3 --min-new-tokens 10    # the history rules
+    python tools/decode_bench.py --model gpt2 --beam 5 --repetition-penalty 1.3 --no-repeat-ngram 3 --min-new-tokens 10     # ... in the beam search
 
 Random weights, a 32-token brain prefix, one start token, top_k = 1.  A generate() call also pays the prefill and, in graph mode, the
 capture, so the per-token figure is the MARGINAL cost: (time of N new tokens - time of N/4 new tokens) / (3N/4), medians over the
@@ -262,6 +264,47 @@ def top_p_bench(g, a, prefix, start):
               f"{max(times[name][n]) * 1e3:.2f}]", flush=True)
 
 
+def rules_bench(g, a, prefix, start):
+    """--repetition-penalty / --no-repeat-ngram / --min-new-tokens: what the history rules (one more launch per step, fk_logit_rules) cost a
+    decode step.  generate() (top_k = 1), or with --beam W generate_beam_search on the caches, as a hipGraph in one process, the repeats of the
+    modes interleaved: rules off; with --min-new-tokens (which needs an end-of-text id) the same call with that id alone, an id a
+    random-weight decoder is unlikely to draw (a call that does draw it and ends early fails the run: its time would not be a step's); and the
+    rules on.  us/step is marginal like every other figure of this file."""
+    n, n4, B = a.new_tokens, max(1, a.new_tokens // 4), start.shape[0]
+    rules = dict(repetition_penalty=a.repetition_penalty, no_repeat_ngram_size=a.no_repeat_ngram, min_new_tokens=a.min_new_tokens)
+    eos = dict(eos_token_id=50255) if a.min_new_tokens > 0 else {}
+
+    def call(k, kw):
+        if a.beam:
+            g.generate_beam_search(start, k, prefix, topk=a.topk, beam_width=a.beam, use_cache=True, use_graph=True, **kw)
+        else:
+            g.generate(start, k, prefix=prefix, top_k=1, use_cache=True, use_graph=True, **kw)
+        # a call that carries the id may end early, and the marginal figure of two calls of different lengths would then mean nothing
+        assert "eos_token_id" not in kw or g.last_steps == k, f"the decoder emitted the end-of-text id {kw['eos_token_id']}: {g.last_steps} of {k} steps ran; not a timing"
+
+    modes = {"rules off": {}}
+    if eos:
+        modes["end-of-text id only"] = eos
+    modes["rules on"] = dict(rules, **eos)
+    times = {name: {n4: [], n: []} for name in modes}
+    for kw in modes.values():                               # warm up both lengths of every mode
+        for k in (n4, n):
+            call(k, kw)
+    for _ in range(a.repeats):
+        for k in (n4, n):
+            for name, kw in modes.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                call(k, kw)
+                torch.cuda.synchronize()
+                times[name][k].append(time.perf_counter() - t0)
+    for name in modes:
+        t4, t = statistics.median(times[name][n4]), statistics.median(times[name][n])
+        step = (t - t4) / (n - n4) if n > n4 else t / n
+        print(f"{name:20s}: {step * 1e6:9.1f} us/step (marginal)  {B / step:9.0f} tokens/s   | whole call {t * 1e3:8.2f} ms [{min(times[name][n]) * 1e3:.2f} .. "
+              f"{max(times[name][n]) * 1e3:.2f}]", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", choices=sorted(MODELS), default="nano")
@@ -277,6 +320,9 @@ def main():
     ap.add_argument("--eos", action="store_true", help="with --beam: the end-of-text path (step against the plain step, cost of the poll, early exit, backtrack)")
     ap.add_argument("--top-p", type=float, default=None, help="nucleus sampling: time generate with and without top_p = P (greedy, no crop, top_k = 10), interleaved")
     ap.add_argument("--top-k", type=int, default=None, help="with --top-p: only this top-k crop (0: none), with and without top_p")
+    ap.add_argument("--repetition-penalty", type=float, default=1.0, help="history rules: time generate (or, with --beam, the cached search) with and without them, interleaved")
+    ap.add_argument("--no-repeat-ngram", type=int, default=0, help="history rules: no_repeat_ngram_size")
+    ap.add_argument("--min-new-tokens", type=int, default=0, help="history rules: min_new_tokens (the calls then carry an end-of-text id)")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "decode_bench needs the GPU"
 
@@ -291,6 +337,12 @@ def main():
     floor = wbytes / HBM_PEAK
     print(f"model {a.model} ({sum(p.numel() for p in g.parameters()) / 1e6:.1f} M parameters), {a.dtype}, batch {B}, {n} new tokens, "
           f"{a.repeats} repeats; weights per step {wbytes / 1e6:.1f} MB -> ceiling {floor * 1e6:.1f} us/step = {B / floor:.0f} tokens/s")
+    if a.repetition_penalty != 1.0 or a.no_repeat_ngram or a.min_new_tokens:
+        if a.beam and B != 1:
+            ap.error("--beam with --batch: one sentence only")
+        print(f"history rules: repetition_penalty {a.repetition_penalty}, no_repeat_ngram_size {a.no_repeat_ngram}, min_new_tokens {a.min_new_tokens}"
+              + (f"; beam width {a.beam}, topk {a.topk}" if a.beam else ""))
+        return rules_bench(g, a, prefix, start)
     if a.beam and a.sentences:
         print(f"beam width {a.beam}, topk {a.topk}, sentences {a.sentences}")
         return sentences_bench(g, a, m["n_embd"])
