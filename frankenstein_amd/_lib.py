@@ -20,6 +20,9 @@ ATTN_Q_PRESCALED = 1
 GEMV_GELU = 1
 NT_RING2, NT_RING192, NT_RING128, NT_BIG, NT_GLDS4, NT_GLDS, NT_STAGED = range(7)     # fk_gemm_nt_route
 NT_ROUTE_F32 = -2
+ATTN_FWD_GENERIC, ATTN_FWD_FEWQ, ATTN_FWD_PS, ATTN_FWD_ASM = range(4)                 # fk_attn_route
+ATTN_DQ_GENERIC, ATTN_DQ_FEWQ, ATTN_DQ_PS, ATTN_DQ_ASM = range(4)
+ATTN_DKDV_GENERIC, ATTN_DKDV_PS, ATTN_DKDV_ASM, ATTN_DKDVW_ASM = range(4)
 
 _p, _i64, _int, _f32, _f64, _sz, _u32 = C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_double, C.c_size_t, C.c_uint32
 
@@ -44,6 +47,7 @@ SIGNATURES = {
     "fk_attn_bwd": (_int, [_p] * 10 + [_i64] * 13 + [_int, _i64, _i64, _i64, _p, _p, _f32, _p, _i64, _i64, _int, _int, _p]),
     "fk_attn_fwd_dropout": (_int, [_p, _p, _p, _p, _p] + [_i64] * 13 + [_int, _i64, _i64, _i64, _p, _p, _f32, _int, _f32, _p, _u32, _int, _p]),
     "fk_attn_bwd_dropout": (_int, [_p] * 10 + [_i64] * 13 + [_int, _i64, _i64, _i64, _p, _p, _f32, _p, _i64, _i64, _int, _f32, _p, _u32, _int, _p]),
+    "fk_attn_route": (_int, [_i64, _i64, _i64, _int, _int, _i64, _i64, _i64, _int, _int, _int, _p, _p, _p]),
     "fk_dropout": (_int, [_p, _p, _p, _i64, _f32, _p, _u32, _int, _p]),
     "fk_norm_fwd": (_int, [_p, _p, _p, _p, _p, _p, _i64, _i64, _f32, _int, _int, _p]),
     "fk_norm_bwd_workspace_bytes": (_sz, [_i64, _i64]),

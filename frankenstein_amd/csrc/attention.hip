@@ -2342,17 +2342,49 @@ bool few_queries(const AttnArgs& a) {
   static const bool no_fewq = getenv("FK_ATTN_NO_FEWQ") != nullptr;      // tuning knob
   return !no_fewq && a.Nq <= 32 && a.Nk >= 1024 && a.mask_kind == FK_MASK_NONE && !a.drop_thresh;
 }
+// The kernels a problem runs on (the FK_ATTN_* values of franken_hip.h): the one place where that is decided.  launch_fwd / launch_bwd
+// launch what it says and fk_attn_route answers with it, so the tests can say which kernel a shape reaches.  swz: bf16 with D = 64 (the
+// swizzled LDS image; the only layout the few-query, pre-scaled and generated-stream kernels exist for).
+struct AttnRoute { int fwd, dq, dkdv; };
+AttnRoute attn_route(const AttnArgs& a, bool swz, bool has_rope) {
+  AttnRoute r{FK_ATTN_FWD_GENERIC, FK_ATTN_DQ_GENERIC, FK_ATTN_DKDV_GENERIC};
+  if (swz && (a.flags & FK_ATTN_Q_PRESCALED)) {
+    const bool vis_all = fully_visible(a, 128);
+    r.fwd = FK_ATTN_FWD_PS; r.dq = FK_ATTN_DQ_PS; r.dkdv = FK_ATTN_DKDV_PS;
+#ifndef FK_NO_FWD_ASM
+    if (vis_all && a.Nq % 128 == 0 && a.Nk % 64 == 0) r.fwd = FK_ATTN_FWD_ASM;
+#endif
+#ifndef FK_NO_DQ_ASM
+    if (vis_all && a.Nq % 128 == 0 && a.Nk % 64 == 0) r.dq = FK_ATTN_DQ_ASM;
+#endif
+#ifndef FK_NO_DKDV_ASM
+    if (vis_all && a.Nk % 128 == 0 && a.Nq % 64 == 0) r.dkdv = FK_ATTN_DKDV_ASM;
+#endif
+#ifndef FK_NO_DKDVW_ASM
+    static const bool no_wide = getenv("FK_ATTN_NO_DKDVW") != nullptr;    // tuning knob: the 32-keys-per-wave stream instead
+    if (!no_wide && fully_visible(a, 256) && a.Nk % 256 == 0 && a.Nq % 64 == 0) r.dkdv = FK_ATTN_DKDVW_ASM;
+#endif
+    return r;
+  }
+  if (swz && few_queries(a)) {
+    r.fwd = FK_ATTN_FWD_FEWQ;
+    if (!has_rope) r.dq = FK_ATTN_DQ_FEWQ;
+  }
+  return r;
+}
+
 template <typename T, int D> int launch_fwd(const AttnArgs& a, hipStream_t s) {
   constexpr int NW = Img<T, D>::SWZ ? 8 : 4;
+  const int route = attn_route(a, Img<T, D>::SWZ, false).fwd;
   if constexpr (Img<T, D>::SWZ) {
-    if (a.flags & FK_ATTN_Q_PRESCALED) {
 #ifndef FK_NO_FWD_ASM
-      if (fully_visible(a, 128) && a.Nq % 128 == 0 && a.Nk % 64 == 0) {
-        allow_lds(attn_fwd_asm_kernel, FWD_ASM_LDS);
-        hipLaunchKernelGGL(attn_fwd_asm_kernel, dim3((unsigned)(a.Nq / 128 * a.H * a.B)), dim3(256), FWD_ASM_LDS, s, a);
-        return 0;
-      }
+    if (route == FK_ATTN_FWD_ASM) {
+      allow_lds(attn_fwd_asm_kernel, FWD_ASM_LDS);
+      hipLaunchKernelGGL(attn_fwd_asm_kernel, dim3((unsigned)(a.Nq / 128 * a.H * a.B)), dim3(256), FWD_ASM_LDS, s, a);
+      return 0;
+    }
 #endif
+    if (route == FK_ATTN_FWD_PS) {
       constexpr int NWF = FK_FWD_NW;
       dim3 grid((unsigned)(((a.Nq + NWF * 32 - 1) / (NWF * 32)) * a.H * a.B));
       const size_t lds = fwd_lds<T, D>();
@@ -2360,9 +2392,7 @@ template <typename T, int D> int launch_fwd(const AttnArgs& a, hipStream_t s) {
       hipLaunchKernelGGL((attn_fwd_ps_kernel<NWF>), grid, dim3(NWF * 64), lds, s, a);
       return 0;
     }
-  }
-  if constexpr (Img<T, D>::SWZ) {
-    if (few_queries(a)) {
+    if (route == FK_ATTN_FWD_FEWQ) {
       allow_lds(attn_fwd_fewq_kernel, FEWQ_LDS);
       hipLaunchKernelGGL(attn_fwd_fewq_kernel, dim3((unsigned)(a.H * a.B)), dim3(FEWQ_NW * 64), FEWQ_LDS, s, a);
       return 0;
@@ -2381,14 +2411,14 @@ template <typename T, int D> int launch_bwd(const AttnArgs& a, hipStream_t s) {
   allow_lds(attn_bwd_dkdv_kernel<T, D>, lds_kv);
   allow_lds(attn_bwd_dq_kernel<T, D>, lds_q);
   dim3 gq((unsigned)(((a.Nq + BQ - 1) / BQ) * a.H * a.B));
+  const AttnRoute route = attn_route(a, Img<T, D>::SWZ, a.rope_table != nullptr);
   if constexpr (Img<T, D>::SWZ) {
-    if (a.flags & FK_ATTN_Q_PRESCALED) {
+    if (route.dq == FK_ATTN_DQ_ASM || route.dq == FK_ATTN_DQ_PS) {         // the pre-scaled kernels: dQ and dK/dV both
       constexpr int NWQ = FK_DQ_NW, NWK = FK_DKDV_NW;
       dim3 gq2((unsigned)(((a.Nq + NWQ * 32 - 1) / (NWQ * 32)) * a.H * a.B)), gk2((unsigned)(((a.Nk + NWK * 32 - 1) / (NWK * 32)) * a.H * a.B));
-      const bool vis_all = fully_visible(a, 128);
       bool dq_done = false;
 #ifndef FK_NO_DQ_ASM
-      if (vis_all && a.Nq % 128 == 0 && a.Nk % 64 == 0) {
+      if (route.dq == FK_ATTN_DQ_ASM) {
         allow_lds(attn_bwd_dq_asm_kernel, DQ_PS_LDS);
         hipLaunchKernelGGL(attn_bwd_dq_asm_kernel, dim3((unsigned)(a.Nq / 128 * a.H * a.B)), dim3(256), DQ_PS_LDS, s, a);
         dq_done = true;
@@ -2399,15 +2429,14 @@ template <typename T, int D> int launch_bwd(const AttnArgs& a, hipStream_t s) {
         hipLaunchKernelGGL(attn_bwd_dq_ps_kernel<NWQ>, gq2, dim3(NWQ * 64), DQ_PS_LDS, s, a);
       }
 #ifndef FK_NO_DKDVW_ASM
-      static const bool no_wide = getenv("FK_ATTN_NO_DKDVW") != nullptr;    // tuning knob: the 32-keys-per-wave stream instead
-      if (!no_wide && fully_visible(a, 256) && a.Nk % 256 == 0 && a.Nq % 64 == 0) {
+      if (route.dkdv == FK_ATTN_DKDVW_ASM) {
         allow_lds(attn_bwd_dkdvw_asm_kernel, DKDV_PS_LDS);
         hipLaunchKernelGGL(attn_bwd_dkdvw_asm_kernel, dim3((unsigned)(a.Nk / 256 * a.H * a.B)), dim3(256), DKDV_PS_LDS, s, a);
         return 0;
       }
 #endif
 #ifndef FK_NO_DKDV_ASM
-      if (vis_all && a.Nk % 128 == 0 && a.Nq % 64 == 0) {
+      if (route.dkdv == FK_ATTN_DKDV_ASM) {
         allow_lds(attn_bwd_dkdv_asm_kernel, DKDV_PS_LDS);
         hipLaunchKernelGGL(attn_bwd_dkdv_asm_kernel, gk2, dim3(256), DKDV_PS_LDS, s, a);
         return 0;
@@ -2420,7 +2449,7 @@ template <typename T, int D> int launch_bwd(const AttnArgs& a, hipStream_t s) {
   }
   bool dq_done = false;
   if constexpr (Img<T, D>::SWZ) {
-    if (few_queries(a) && !a.rope_table) {
+    if (route.dq == FK_ATTN_DQ_FEWQ) {
       allow_lds(attn_bwd_dq_fewq_kernel, FEWQ_LDS);
       hipLaunchKernelGGL(attn_bwd_dq_fewq_kernel, dim3((unsigned)(a.H * a.B)), dim3(FEWQ_NW * 64), FEWQ_LDS, s, a);
       dq_done = true;
@@ -2585,6 +2614,27 @@ int fk_attn_bwd(const void* Q, const void* K, const void* V, const void* O, cons
   return fk_attn_bwd_dropout(Q, K, V, O, dO, LSE, dQ, dK, dV, delta_ws, B, H, Nq, Nk, D, q_bs, q_rs, k_bs, k_rs, v_bs, v_rs, o_bs, o_rs,
                              mask_kind, mask_c, q_off, k_off, limits, qfirst, scale, rope_table, rope_bs, rope_off, flags, 0.0f, nullptr, 0,
                              dtype, stream);
+}
+
+int fk_attn_route(int64_t Nq, int64_t Nk, int64_t D, int dtype, int mask_kind, int64_t mask_c, int64_t q_off, int64_t k_off, int flags,
+                  int has_dropout, int has_rope, int* fwd, int* dq, int* dkdv) {
+  const int64_t st[1] = {0};
+  int rc = check_common("fk_attn_route", 1, 1, Nq, Nk, D, dtype, mask_kind, mask_c, st, 0);
+  if (rc) return rc;
+  FK_CHECK_ARG((flags & ~FK_ATTN_Q_PRESCALED) == 0 && (!(flags & FK_ATTN_Q_PRESCALED) || (dtype == FK_BF16 && D == 64)),
+               "fk_attn_route: bad flags %d (FK_ATTN_Q_PRESCALED needs bf16, D = 64)", flags);
+  FK_CHECK_ARG(!(flags & FK_ATTN_Q_PRESCALED) || (mask_kind != FK_MASK_DENSE && !has_dropout),
+               "fk_attn_route: dense masks and dropout run on the generic kernels (no FK_ATTN_Q_PRESCALED)");
+  FK_CHECK_ARG(!has_rope || Nq == Nk, "fk_attn_route: fused inverse RoPE needs self-attention (Nq == Nk)");
+  AttnArgs a{};
+  a.Nq = (int)Nq; a.Nk = (int)Nk; a.mask_kind = mask_kind; a.mask_c = (int)mask_c; a.q_off = (int)q_off; a.k_off = (int)k_off;
+  a.flags = flags; a.drop_thresh = has_dropout ? 1u : 0u;
+  static_assert(Img<bf16_t, 64>::SWZ && !Img<bf16_t, 32>::SWZ && !Img<bf16_t, 128>::SWZ && !Img<float, 64>::SWZ, "the swizzled image: bf16, D = 64");
+  const AttnRoute r = attn_route(a, dtype == FK_BF16 && D == 64, has_rope != 0);
+  if (fwd) *fwd = r.fwd;
+  if (dq) *dq = r.dq;
+  if (dkdv) *dkdv = r.dkdv;
+  return FK_OK;
 }
 
 }  // extern "C"

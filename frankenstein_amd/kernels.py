@@ -397,6 +397,29 @@ def attn_bwd(q: Tensor, k: Tensor, v: Tensor, o: Tensor, do: Tensor, lse: Tensor
         call("fk_attn_bwd_dropout", *head, dropout[0], dropout[1].data_ptr(), dropout[2], fk_dtype(q), _stream())
 
 
+# the kernels fk_attn_fwd / fk_attn_bwd choose between (fk_attn_route), one table per launch: forward, dQ, dK/dV
+ATTN_FWD_ROUTE_NAMES = {_lib.ATTN_FWD_GENERIC: "FWD_GENERIC", _lib.ATTN_FWD_FEWQ: "FWD_FEWQ", _lib.ATTN_FWD_PS: "FWD_PS", _lib.ATTN_FWD_ASM: "FWD_ASM"}
+ATTN_DQ_ROUTE_NAMES = {_lib.ATTN_DQ_GENERIC: "DQ_GENERIC", _lib.ATTN_DQ_FEWQ: "DQ_FEWQ", _lib.ATTN_DQ_PS: "DQ_PS", _lib.ATTN_DQ_ASM: "DQ_ASM"}
+ATTN_DKDV_ROUTE_NAMES = {_lib.ATTN_DKDV_GENERIC: "DKDV_GENERIC", _lib.ATTN_DKDV_PS: "DKDV_PS", _lib.ATTN_DKDV_ASM: "DKDV_ASM", _lib.ATTN_DKDVW_ASM: "DKDVW_ASM"}
+
+
+def attn_route(Nq: int, Nk: int, D: int, dtype=torch.bfloat16, mask: Mask = NO_MASK, q_prescaled: bool = False, dropout: bool = False,
+               rope: bool = False) -> Tuple[int, int, int]:
+    """(fwd, dq, dkdv): the kernels attn_fwd and attn_bwd run for this problem, keys of ATTN_FWD_ / ATTN_DQ_ / ATTN_DKDV_ROUTE_NAMES
+    (host-side query, no launch; the launchers ask the same function).  dropout: a dropout tuple is passed; rope: attn_bwd gets a
+    rope_table."""
+    import ctypes
+    f, q, kv = ctypes.c_int(-1), ctypes.c_int(-1), ctypes.c_int(-1)
+    call("fk_attn_route", Nq, Nk, D, fk_dtype(dtype), mask.kind, mask.c, mask.q_off, mask.k_off, ATTN_Q_PRESCALED if q_prescaled else 0,
+         int(dropout), int(rope), ctypes.byref(f), ctypes.byref(q), ctypes.byref(kv))
+    return f.value, q.value, kv.value
+
+
+def attn_route_names(*args, **kw) -> Tuple[str, str, str]:
+    f, q, kv = attn_route(*args, **kw)
+    return ATTN_FWD_ROUTE_NAMES[f], ATTN_DQ_ROUTE_NAMES[q], ATTN_DKDV_ROUTE_NAMES[kv]
+
+
 def attn_combine(parts: Tensor, lse_parts: Optional[Tensor] = None, want_lse: bool = True):
     """parts [B, S, T, H, D] (+ lse_parts [B, S, H, T]) -> (out [B, T, H, D], lse [B, H, T] or None): fk_attn_combine."""
     B, S, T, H, D = parts.shape

@@ -166,6 +166,19 @@ int fk_attn_bwd_dropout(const void* Q, const void* K, const void* V, const void*
                         int64_t o_rs, int mask_kind, int64_t mask_c, int64_t q_off, int64_t k_off, const int32_t* limits,
                         const int32_t* qfirst, float scale, const float* rope_table, int64_t rope_bs, int64_t rope_off, int flags,
                         float drop_p, const uint32_t* drop_seed, uint32_t drop_site, int dtype, void* stream);
+/* fk_attn_route: which kernels fk_attn_fwd / fk_attn_bwd (and their *_dropout forms) run for a problem (host only, nothing is launched;
+ *   the launchers ask the same function).  Takes everything the decision reads: Nq, Nk, D, dtype, the mask (kind, mask_c, q_off, k_off as
+ *   in the calls above; for FK_MASK_DENSE mask_c / q_off are the table strides), flags, has_dropout (drop_p != 0) and has_rope (a
+ *   rope_table is given to the backward).  Writes the forward, dQ and dK/dV kernels (any of the three pointers may be NULL):
+ *   GENERIC = the kernels for every dtype / head_dim / mask; FEWQ = the waves split the keys (Nq <= 32, Nk >= 1024, no mask, no dropout;
+ *   the dQ form also needs no RoPE table); PS = the FK_ATTN_Q_PRESCALED tile loops; ASM = the generated instruction streams (every tile
+ *   fully visible and aligned); DKDVW_ASM = the stream with 64 keys per wave.  Follows FK_ATTN_NO_FEWQ / FK_ATTN_NO_DKDVW exactly as the
+ *   launch does.  Returns FK_OK, or FK_EINVAL for a problem the entry points refuse.                                                   */
+enum { FK_ATTN_FWD_GENERIC = 0, FK_ATTN_FWD_FEWQ = 1, FK_ATTN_FWD_PS = 2, FK_ATTN_FWD_ASM = 3 };
+enum { FK_ATTN_DQ_GENERIC = 0, FK_ATTN_DQ_FEWQ = 1, FK_ATTN_DQ_PS = 2, FK_ATTN_DQ_ASM = 3 };
+enum { FK_ATTN_DKDV_GENERIC = 0, FK_ATTN_DKDV_PS = 1, FK_ATTN_DKDV_ASM = 2, FK_ATTN_DKDVW_ASM = 3 };
+int fk_attn_route(int64_t Nq, int64_t Nk, int64_t D, int dtype, int mask_kind, int64_t mask_c, int64_t q_off, int64_t k_off, int flags,
+                  int has_dropout, int has_rope, int* fwd, int* dq, int* dkdv);
 
 /* ---- dropout (nn.Dropout in training mode: models/gpt2_model.py:40,75 resid_dropout, :85,91 MLP, :129 embeddings).
  *      y[i] = (res ? res[i] : 0) + (keep(i) ? x[i] / (1 - p) : 0), n contiguous elements (multiple of 16 bytes), y may alias x.  The backward

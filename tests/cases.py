@@ -245,3 +245,77 @@ TN_CASES = [
     (0, "f32", 2083, 904, 1000, 16, 160),        # the same in fp32: split 13 has 3 rows, 14 and 15 are empty
     (128, "bf16", 16384, 384, 128, 32, 512),
 ]
+
+
+# ------------------------------------------------------------------------------------------------ attention routes
+# The shapes of tests/test_attn_routes_gpu.py, shared with tests/test_attn_routes_cpu.py, which pins the (forward, dQ, dK/dV) kernels each
+# of them reaches (kernels.attn_route) and checks that the inputs of tests/attn_inputs.py turn a lost key into a gross error on it.
+# mask: ("none",) | ("causal",) | ("block", c) | ("sliced", "causal" | "block", c, full_q, full_k) (the [-Nq:, -Nk:] slice of a full mask:
+# position offsets) | ("prefix", block, n_full) (MAE sub-mask of sorted token ids) | ("keypad",) | ("dense", Bm, Hm) (1 = broadcast).
+# ps: FK_ATTN_Q_PRESCALED (bf16, D = 64).
+def _attn(dtype, B, H, Nq, Nk, D, mask, routes, ps=False, **kw):
+    name = "-".join([".".join(routes), dtype, f"{B}x{H}x{Nq}x{Nk}x{D}", "_".join(map(str, mask))]
+                    + (["ps"] if ps else []) + [f"{k}{v}" for k, v in kw.items()])
+    return dict(id=name, dtype=dtype, B=B, H=H, Nq=Nq, Nk=Nk, D=D, mask=mask, routes=routes, ps=ps, **kw)
+
+
+_GEN = ("FWD_GENERIC", "DQ_GENERIC", "DKDV_GENERIC")
+_FEWQ = ("FWD_FEWQ", "DQ_FEWQ", "DKDV_GENERIC")
+_PS = ("FWD_PS", "DQ_PS", "DKDV_PS")
+ATTN_ROUTE_CASES = [
+    # generic kernels: fp32 D 8 / 16 / 32 / 64, bf16 D 8 / 16 / 32 / 64 / 128, every mask kind, ragged, more than one workgroup
+    _attn("f32", 2, 3, 40, 130, 8, ("none",), _GEN),
+    _attn("f32", 2, 2, 150, 150, 16, ("causal",), _GEN),
+    _attn("f32", 1, 2, 40, 200, 32, ("sliced", "block", 8, 256, 256), _GEN),
+    _attn("f32", 2, 2, 70, 100, 64, ("dense", 2, 2), _GEN),
+    _attn("f32", 2, 2, 139, 139, 32, ("keypad",), _GEN),
+    _attn("bf16", 2, 2, 130, 130, 8, ("keypad",), _GEN),
+    _attn("bf16", 2, 2, 140, 140, 16, ("prefix", 16, 400), _GEN),
+    _attn("bf16", 2, 3, 70, 100, 32, ("dense", 1, 3), _GEN),
+    _attn("bf16", 2, 2, 200, 200, 128, ("causal",), _GEN),
+    _attn("bf16", 2, 2, 130, 130, 64, ("block", 16), _GEN),
+    _attn("bf16", 1, 2, 150, 90, 64, ("dense", 1, 1), _GEN),
+    # few queries, long context: the waves split the keys (forward and dQ)
+    _attn("bf16", 2, 2, 8, 1024, 64, ("none",), _FEWQ),
+    _attn("bf16", 2, 2, 32, 1100, 64, ("none",), _FEWQ),
+    # the pre-scaled tile loops: ragged, causal, block-causal 8 and 128, sliced offsets, prefix and key-padding tables
+    _attn("bf16", 2, 2, 333, 333, 64, ("causal",), _PS, ps=True),
+    _attn("bf16", 2, 2, 200, 200, 64, ("block", 8), _PS, ps=True),
+    _attn("bf16", 1, 2, 300, 300, 64, ("block", 128), _PS, ps=True),
+    _attn("bf16", 1, 2, 40, 300, 64, ("none",), _PS, ps=True),
+    _attn("bf16", 2, 2, 256, 384, 64, ("sliced", "block", 128, 512, 512), _PS, ps=True),
+    _attn("bf16", 2, 2, 260, 260, 64, ("prefix", 16, 700), _PS, ps=True),
+    _attn("bf16", 2, 2, 270, 270, 64, ("keypad",), _PS, ps=True),
+    _attn("bf16", 2, 1, 1100, 1100, 64, ("keypad",), _PS, ps=True),
+    # the generated forward and dQ streams (128 queries per workgroup, 64-key tiles): 1 .. 9 key tiles, every ring phase; dK/dV takes the
+    # narrow stream at Nk % 128 == 0 (2 query tiles), the wide one at Nk % 256 == 0, the tile loop otherwise
+    _attn("bf16", 2, 2, 128, 64, 64, ("none",), ("FWD_ASM", "DQ_ASM", "DKDV_PS"), ps=True),
+    _attn("bf16", 2, 2, 128, 128, 64, ("none",), ("FWD_ASM", "DQ_ASM", "DKDV_ASM"), ps=True),
+    _attn("bf16", 1, 2, 128, 192, 64, ("none",), ("FWD_ASM", "DQ_ASM", "DKDV_PS"), ps=True),
+    _attn("bf16", 2, 2, 128, 256, 64, ("none",), ("FWD_ASM", "DQ_ASM", "DKDVW_ASM"), ps=True),
+    _attn("bf16", 2, 1, 128, 320, 64, ("none",), ("FWD_ASM", "DQ_ASM", "DKDV_PS"), ps=True),
+    _attn("bf16", 1, 2, 128, 384, 64, ("none",), ("FWD_ASM", "DQ_ASM", "DKDV_ASM"), ps=True),
+    _attn("bf16", 1, 1, 128, 448, 64, ("none",), ("FWD_ASM", "DQ_ASM", "DKDV_PS"), ps=True),
+    _attn("bf16", 1, 2, 256, 512, 64, ("none",), ("FWD_ASM", "DQ_ASM", "DKDVW_ASM"), ps=True),
+    _attn("bf16", 1, 2, 128, 576, 64, ("none",), ("FWD_ASM", "DQ_ASM", "DKDV_PS"), ps=True),
+    # the narrow dK/dV stream (64 queries per tile): 1 and 5 query tiles (2 above), and block-causal 128: 6, 4, 2 tiles
+    _attn("bf16", 2, 2, 64, 128, 64, ("none",), ("FWD_PS", "DQ_PS", "DKDV_ASM"), ps=True),
+    _attn("bf16", 1, 3, 320, 128, 64, ("none",), ("FWD_PS", "DQ_PS", "DKDV_ASM"), ps=True),
+    _attn("bf16", 2, 2, 384, 384, 64, ("block", 128), ("FWD_ASM", "DQ_ASM", "DKDV_ASM"), ps=True),
+    # the wide dK/dV stream (ring of 3 query tiles): 1, 3, 4, 7 query tiles (2 above), and block-causal 256: 8 and 4 tiles
+    _attn("bf16", 2, 2, 64, 256, 64, ("none",), ("FWD_PS", "DQ_PS", "DKDVW_ASM"), ps=True),
+    _attn("bf16", 2, 1, 192, 256, 64, ("none",), ("FWD_PS", "DQ_PS", "DKDVW_ASM"), ps=True),
+    _attn("bf16", 1, 2, 256, 256, 64, ("none",), ("FWD_ASM", "DQ_ASM", "DKDVW_ASM"), ps=True),
+    _attn("bf16", 1, 2, 448, 256, 64, ("none",), ("FWD_PS", "DQ_PS", "DKDVW_ASM"), ps=True),
+    _attn("bf16", 2, 2, 512, 512, 64, ("block", 256), ("FWD_ASM", "DQ_ASM", "DKDVW_ASM"), ps=True),
+]
+
+# online-softmax stress on the pre-scaled forward kernels (GPU file; the CPU file pins their routes): spike > 0: one late key outscores
+# everything its row has seen by far (reference-0 loop -> exact loop, and on the generated stream the workgroup's redo); spike < 0: every
+# score of head 0 lies that many log2 units down, far below the window of reference 0 (the classic loop throughout)
+ATTN_SPIKE_CASES = [
+    _attn("bf16", 1, 2, 200, 330, 64, ("none",), _PS, ps=True, spike=40.0),
+    _attn("bf16", 1, 2, 384, 384, 64, ("none",), ("FWD_ASM", "DQ_ASM", "DKDV_ASM"), ps=True, spike=40.0),
+    _attn("bf16", 1, 2, 200, 200, 64, ("block", 8), _PS, ps=True, spike=-2048.0),
+    _attn("bf16", 1, 2, 256, 256, 64, ("none",), ("FWD_ASM", "DQ_ASM", "DKDVW_ASM"), ps=True, spike=-2048.0),
+]
