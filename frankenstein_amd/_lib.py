@@ -107,7 +107,15 @@ SIGNATURES = {
     "fk_ce_chunk_finish": (_int, [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _p, _sz, _p]),
     "fk_ce_chunk_bwd": (_int, [_p, _i64, _p, _i64, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _int, _p]),
     "fk_adamw_step": (_int, [_p, _p, _p, _p, _i64, _f64, _f64, _f64, _f64, _f64, _i64, _f64, _f64, _int, _p]),
+    "fk_grad_sumsq": (_int, [_p, _i64, _p, _i64, _p, _int, _p]),
+    "fk_adamw_step_groups": (_int, [_p, _p, _p, _p, _i64, _p, _i64, _p, _int, _f64, _f64, _int, _f64, _p, _int, _p, _p]),
 }
+ADAMW_MAX_SLOTS, GRAD_SUMSQ_MAX_BLOCKS = 16, 1024
+
+
+class AdamwGroup(C.Structure):
+    """fk_adamw_group: one slot's hyper-parameters as the host hands them to fk_adamw_step_groups"""
+    _fields_ = [("lr", _f64), ("beta1", _f64), ("beta2", _f64), ("eps", _f64), ("weight_decay", _f64), ("step", _i64)]
 
 _lib = None
 

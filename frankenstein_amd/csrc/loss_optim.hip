@@ -2,6 +2,7 @@
 //   fk_l1_loss_*  F.l1_loss / F.mse_loss (mean)         models/brainformer.py:557, :473
 //   fk_ce_*       F.cross_entropy(ignore_index, mean)   models/gpt2_model.py:210; train_brainformer.ipynb cell 3
 //   fk_adamw_step clip_grad_value_ + AdamW.step         utils/train_utils.py:117-119,142-143
+//   fk_adamw_step_groups / fk_grad_sumsq   the same over a segment table: parameter groups + clip_grad_norm_ in one (two) launches
 //   fk_api        version / last-error
 #include <stdarg.h>
 #include <stdio.h>
@@ -213,6 +214,121 @@ __global__ void adamw_kernel(float* p, float* g, float* m, float* v, int64_t n, 
   }
 }
 
+// ---- AdamW over a segment table: parameter groups, skipped parameters and the global-norm clip in one launch ---------------------
+// segs: nseg records sorted by begin, disjoint, edges multiples of 4 elements; an element in no segment is neither read nor written.
+// Lookup "which segment holds element e" = the last k with segs[k].begin <= e, by a two-level binary search: every stride-th begin
+// (stride = ceil(nseg / SEG_TILE), so at most SEG_TILE of them whatever nseg is) is staged in LDS, the <= stride records between two
+// staged ones are searched in the table itself (L2-resident).  nseg <= SEG_TILE: stride 1, the whole search runs in LDS.
+struct AdamwSlot { float lr, omb1, b2, omb2, eps, wd, bc1, sqrt_bc2; };
+struct AdamwSlots { AdamwSlot s[FK_ADAMW_MAX_SLOTS]; };
+constexpr int SEG_TILE = 1024;
+constexpr int SUMSQ_TPB = 1024;
+
+FK_DEV void seg_stage(const fk_adamw_seg* segs, int nseg, int stride, int64_t* sh_begin) {
+  const int nc = (nseg + stride - 1) / stride;
+  for (int c = threadIdx.x; c < nc; c += blockDim.x) sh_begin[c] = segs[(int64_t)c * stride].begin;
+  __syncthreads();
+}
+FK_DEV int seg_find(const fk_adamw_seg* segs, int nseg, int stride, const int64_t* sh_begin, int64_t e) {   // needs segs[0].begin <= e
+  int lo = 0, hi = (nseg + stride - 1) / stride;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (sh_begin[mid] <= e) lo = mid; else hi = mid;
+  }
+  lo *= stride;
+  hi = lo + stride < nseg ? lo + stride : nseg;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (segs[mid].begin <= e) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+// float4 index range [lo4, hi4) the table spans, clamped to the buffer
+FK_DEV void seg_span(const fk_adamw_seg* segs, int nseg, int64_t n, int64_t& lo4, int64_t& hi4) {
+  const int64_t b = segs[0].begin, e = segs[nseg - 1].end;
+  lo4 = (b > 0 ? b : 0) >> 2;
+  hi4 = (e < n ? e : n) >> 2;
+}
+
+// part[blk] = sum of g^2 over the covered elements this block visits: fixed grid, fixed order (per thread in index order, then
+// wave butterfly, then the waves in order) -> the same bits every run; no atomics
+__global__ void __launch_bounds__(SUMSQ_TPB) grad_sumsq_kernel(const float* g, int64_t n, const fk_adamw_seg* segs, int nseg, int stride,
+                                                               float* part) {
+  __shared__ int64_t sh_begin[SEG_TILE];
+  __shared__ float sh[SUMSQ_TPB / 64];
+  seg_stage(segs, nseg, stride, sh_begin);
+  int64_t lo4, hi4, ce = 0;
+  seg_span(segs, nseg, n, lo4, hi4);
+  float s = 0.0f;
+  for (int64_t i = lo4 + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < hi4; i += (int64_t)gridDim.x * blockDim.x) {
+    if (i >= ce) ce = segs[seg_find(segs, nseg, stride, sh_begin, i << 2)].end >> 2;
+    if (i >= ce) continue;                               // between two segments
+    const f32x4 gv = reinterpret_cast<const f32x4*>(g)[i];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) s += gv[j] * gv[j];
+  }
+  s = block_sum(s, sh);
+  if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+// adamw_kernel's arithmetic, statement for statement, with the hyper-parameters of the element's slot.  max_norm > 0: every block sums
+// the npart partials of grad_sumsq_kernel in the same order (so every block holds the same bits), total = gscale * sqrt(sum),
+// coef = min(1, max_norm / (total + 1e-6)) (torch.nn.utils.clip_grad_norm_), gradient = g * gscale * coef; block 0 stores total.
+__global__ void adamw_groups_kernel(float* p, float* g, float* m, float* v, int64_t n, const fk_adamw_seg* segs, int nseg, int stride,
+                                    AdamwSlots slots, int nslots, float clip, float gscale, int zero_grad, float max_norm,
+                                    const float* part, int npart, float* norm_out) {
+  __shared__ int64_t sh_begin[SEG_TILE];
+  __shared__ AdamwSlot sh_slot[FK_ADAMW_MAX_SLOTS];
+  __shared__ float sh[4];
+  float coef = 1.0f;
+  if (max_norm > 0.0f) {
+    float s = 0.0f;
+    for (int i = threadIdx.x; i < npart; i += blockDim.x) s += part[i];
+    s = block_sum(s, sh);
+    const float total = gscale * (float)sqrt((double)s);        // correctly rounded fp32 square root whatever the build's fp32 sqrt is
+    const float c = max_norm / (total + 1e-6f);
+    coef = c > 1.0f ? 1.0f : c;                                 // a NaN norm stays a NaN coefficient (torch.clamp)
+    if (blockIdx.x == 0 && threadIdx.x == 0) norm_out[0] = total;
+  }
+  if (threadIdx.x < FK_ADAMW_MAX_SLOTS * 8) reinterpret_cast<float*>(sh_slot)[threadIdx.x] = reinterpret_cast<const float*>(&slots)[threadIdx.x];
+  seg_stage(segs, nseg, stride, sh_begin);
+  int64_t lo4, hi4, ce = 0;
+  seg_span(segs, nseg, n, lo4, hi4);
+  int slot = -1;
+  float omb1 = 0.0f, b2 = 0.0f, omb2 = 0.0f, eps = 0.0f, sqrt_bc2 = 1.0f, step_size = 0.0f, decay = 1.0f;
+  for (int64_t i = lo4 + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < hi4; i += (int64_t)gridDim.x * blockDim.x) {
+    if (i >= ce) {                                       // left the segment of the previous iteration (or first iteration)
+      const fk_adamw_seg sg = segs[seg_find(segs, nseg, stride, sh_begin, i << 2)];
+      ce = sg.end >> 2;
+      slot = sg.slot;
+      if ((unsigned)slot < (unsigned)nslots) {
+        const AdamwSlot a = sh_slot[slot];
+        const float lr = a.lr, wd = a.wd, bc1 = a.bc1;
+        omb1 = a.omb1; b2 = a.b2; omb2 = a.omb2; eps = a.eps; sqrt_bc2 = a.sqrt_bc2;
+        step_size = lr / bc1;
+        decay = 1.0f - lr * wd;
+      }
+    }
+    if (i >= ce || (unsigned)slot >= (unsigned)nslots) continue;      // between two segments (or a slot the call does not carry)
+    f32x4 pv = reinterpret_cast<f32x4*>(p)[i], gv = reinterpret_cast<f32x4*>(g)[i];
+    f32x4 mv = reinterpret_cast<f32x4*>(m)[i], vv = reinterpret_cast<f32x4*>(v)[i];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float gg = gv[j] * gscale;
+      gg *= coef;
+      if (clip > 0.0f) gg = fminf(fmaxf(gg, -clip), clip);
+      pv[j] *= decay;
+      mv[j] += omb1 * (gg - mv[j]);
+      vv[j] = b2 * vv[j] + omb2 * gg * gg;
+      pv[j] -= step_size * (mv[j] / (sqrtf(vv[j]) / sqrt_bc2 + eps));
+    }
+    reinterpret_cast<f32x4*>(p)[i] = pv;
+    reinterpret_cast<f32x4*>(m)[i] = mv;
+    reinterpret_cast<f32x4*>(v)[i] = vv;
+    if (zero_grad) reinterpret_cast<f32x4*>(g)[i] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+  }
+}
+
 inline unsigned grid_for(int64_t work, int64_t cap) {
   int64_t b = fk_cdiv(work, TPB);
   if (b > cap) b = cap;
@@ -325,6 +441,43 @@ int fk_adamw_step(float* p, float* g, float* m, float* v, int64_t n, double lr, 
   hipLaunchKernelGGL(adamw_kernel, dim3(grid_for(n / 4 + 1, 4096)), dim3(TPB), 0, (hipStream_t)stream, p, g, m, v, n, (float)lr, (float)(1.0 - beta1),
                      (float)beta2, (float)(1.0 - beta2), (float)eps, (float)weight_decay, (float)bc1, (float)sqrt(bc2), (float)clip, (float)grad_scale, zero_grad);
   FK_CHECK_LAUNCH("fk_adamw_step");
+  return FK_OK;
+}
+
+int fk_grad_sumsq(const float* g, int64_t n, const fk_adamw_seg* segs, int64_t nseg, float* partials, int npartials, void* stream) {
+  FK_CHECK_ARG(g && segs && partials, "fk_grad_sumsq: null pointer");
+  FK_CHECK_ARG((((uintptr_t)g) & 15) == 0 && (((uintptr_t)segs) & 7) == 0, "fk_grad_sumsq: g must be 16-byte aligned, the segment table 8-byte");
+  FK_CHECK_ARG(n >= 4 && nseg > 0 && nseg < (1LL << 31), "fk_grad_sumsq: n = %lld, nseg = %lld", (long long)n, (long long)nseg);
+  FK_CHECK_ARG(npartials >= 1 && npartials <= FK_GRAD_SUMSQ_MAX_BLOCKS, "fk_grad_sumsq: npartials = %d, must be 1..%d", npartials, FK_GRAD_SUMSQ_MAX_BLOCKS);
+  hipLaunchKernelGGL(grad_sumsq_kernel, dim3((unsigned)npartials), dim3(SUMSQ_TPB), 0, (hipStream_t)stream, g, n, segs, (int)nseg,
+                     (int)fk_cdiv(nseg, SEG_TILE), partials);
+  FK_CHECK_LAUNCH("fk_grad_sumsq");
+  return FK_OK;
+}
+
+int fk_adamw_step_groups(float* p, float* g, float* m, float* v, int64_t n, const fk_adamw_seg* segs, int64_t nseg,
+                         const fk_adamw_group* groups, int nslots, double clip, double grad_scale, int zero_grad, double max_norm,
+                         const float* partials, int npartials, float* norm_out, void* stream) {
+  FK_CHECK_ARG(p && g && m && v && segs && groups, "fk_adamw_step_groups: null pointer");
+  FK_CHECK_ARG((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0 && (((uintptr_t)segs) & 7) == 0,
+               "fk_adamw_step_groups: buffers must be 16-byte aligned, the segment table 8-byte");
+  FK_CHECK_ARG(n >= 4 && nseg > 0 && nseg < (1LL << 31), "fk_adamw_step_groups: n = %lld, nseg = %lld", (long long)n, (long long)nseg);
+  FK_CHECK_ARG(nslots >= 1 && nslots <= FK_ADAMW_MAX_SLOTS, "fk_adamw_step_groups: nslots = %d, must be 1..%d", nslots, FK_ADAMW_MAX_SLOTS);
+  FK_CHECK_ARG(max_norm >= 0.0, "fk_adamw_step_groups: max_norm = %g, must be >= 0 (0: no norm clip)", max_norm);
+  FK_CHECK_ARG(!(max_norm > 0.0) || (partials && norm_out && npartials >= 1 && npartials <= FK_GRAD_SUMSQ_MAX_BLOCKS),
+               "fk_adamw_step_groups: max_norm > 0 needs the partials of fk_grad_sumsq (1..%d of them) and norm_out", FK_GRAD_SUMSQ_MAX_BLOCKS);
+  AdamwSlots slots = {};
+  for (int i = 0; i < nslots; ++i) {
+    const fk_adamw_group& q = groups[i];
+    FK_CHECK_ARG(q.step >= 1, "fk_adamw_step_groups: slot %d has step %lld (1-based)", i, (long long)q.step);
+    const double bc1 = 1.0 - pow(q.beta1, (double)q.step), bc2 = 1.0 - pow(q.beta2, (double)q.step);
+    slots.s[i] = AdamwSlot{(float)q.lr, (float)(1.0 - q.beta1), (float)q.beta2, (float)(1.0 - q.beta2), (float)q.eps, (float)q.weight_decay,
+                           (float)bc1, (float)sqrt(bc2)};
+  }
+  hipLaunchKernelGGL(adamw_groups_kernel, dim3(grid_for(n / 4 + 1, 4096)), dim3(TPB), 0, (hipStream_t)stream, p, g, m, v, n, segs, (int)nseg,
+                     (int)fk_cdiv(nseg, SEG_TILE), slots, nslots, (float)clip, (float)grad_scale, zero_grad, (float)max_norm, partials,
+                     npartials, norm_out);
+  FK_CHECK_LAUNCH("fk_adamw_step_groups");
   return FK_OK;
 }
 

@@ -1139,3 +1139,54 @@ def adamw_step_(p: Tensor, g: Tensor, m: Tensor, v: Tensor, step: int, lr: float
         assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == p.numel()
     call("fk_adamw_step", p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), lr, beta1, beta2, eps,
          weight_decay, step, clip, grad_scale, int(zero_grad), _stream())
+
+
+ADAMW_MAX_SLOTS, GRAD_SUMSQ_BLOCKS = _lib.ADAMW_MAX_SLOTS, _lib.GRAD_SUMSQ_MAX_BLOCKS
+
+
+def adamw_segments(segments, device) -> Tensor:
+    """The device table of fk_adamw_step_groups / fk_grad_sumsq from [(begin, end, slot)] (element offsets, multiples of 4, sorted by
+    begin, disjoint): int64 [nseg, 3], the record layout of fk_adamw_seg (slot in the low half of the third word)."""
+    rows = [(int(b), int(e), int(s)) for b, e, s in segments]
+    prev = 0
+    for b, e, s in rows:
+        if b % 4 or e % 4 or not (prev <= b < e) or not (0 <= s < ADAMW_MAX_SLOTS):
+            raise ValueError(f"segment ({b}, {e}, {s}): edges must be multiples of 4, segments sorted and disjoint, slot in 0..{ADAMW_MAX_SLOTS - 1}")
+        prev = e
+    return torch.tensor(rows, dtype=torch.int64).reshape(-1, 3).to(device)
+
+
+def _check_segments(g: Tensor, segs: Tensor) -> None:
+    assert segs.dtype == torch.int64 and segs.dim() == 2 and segs.shape[1] == 3 and segs.is_contiguous() and segs.device == g.device
+
+
+def grad_sumsq_(g: Tensor, segs: Tensor, partials: Optional[Tensor] = None) -> Tensor:
+    """partials [GRAD_SUMSQ_BLOCKS] fp32 whose sum is sum g^2 over the segments of `segs` (adamw_segments); fixed order, the same
+    bits on every run.  adamw_step_groups_(max_norm > 0) adds them up itself."""
+    assert g.dtype == torch.float32 and g.is_contiguous()
+    _check_segments(g, segs)
+    if partials is None:
+        partials = torch.empty(GRAD_SUMSQ_BLOCKS, dtype=torch.float32, device=g.device)
+    assert partials.dtype == torch.float32 and partials.is_contiguous() and 1 <= partials.numel() <= GRAD_SUMSQ_BLOCKS
+    call("fk_grad_sumsq", g.data_ptr(), g.numel(), segs.data_ptr(), segs.shape[0], partials.data_ptr(), partials.numel(), _stream())
+    return partials
+
+
+def adamw_step_groups_(p: Tensor, g: Tensor, m: Tensor, v: Tensor, segs: Tensor, slots, clip: float = 0.0, grad_scale: float = 1.0,
+                       zero_grad: bool = False, max_norm: float = 0.0, partials: Optional[Tensor] = None,
+                       norm_out: Optional[Tensor] = None) -> None:
+    """fk_adamw_step_groups: AdamW over the segments of `segs` (adamw_segments) in one launch; `slots` is a sequence of at most
+    ADAMW_MAX_SLOTS (lr, beta1, beta2, eps, weight_decay, step) and a segment's slot picks one.  max_norm > 0: the gradient is
+    also scaled by min(1, max_norm / (grad_scale * sqrt(sum(partials)) + 1e-6)) with `partials` from grad_sumsq_ on the same
+    gradient, and that norm is stored in norm_out[0]."""
+    for t in (p, g, m, v):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == p.numel()
+    _check_segments(g, segs)
+    arr = (_lib.AdamwGroup * max(1, len(slots)))(*[_lib.AdamwGroup(float(lr), float(b1), float(b2), float(eps), float(wd), int(step))
+                                                  for lr, b1, b2, eps, wd, step in slots])
+    if max_norm > 0:
+        assert partials is not None and norm_out is not None and partials.dtype == torch.float32 and norm_out.dtype == torch.float32
+        assert partials.is_contiguous() and partials.device == g.device and norm_out.device == g.device and norm_out.numel() >= 1
+    call("fk_adamw_step_groups", p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), segs.data_ptr(), segs.shape[0],
+         arr, len(slots), clip, grad_scale, int(zero_grad), max_norm, _ptr(partials), 0 if partials is None else partials.numel(),
+         _ptr(norm_out), _stream())

@@ -327,9 +327,13 @@ class GPT(nn.Module):
         return model
 
     def configure_optimizers(self, weight_decay, learning_rate, betas, device_type):
-        decay = [p for _, p in self.named_parameters() if p.requires_grad and p.dim() >= 2]
-        nodecay = [p for _, p in self.named_parameters() if p.requires_grad and p.dim() < 2]
-        groups = [{'params': decay, 'weight_decay': weight_decay}, {'params': nodecay, 'weight_decay': 0.0}]
+        """models/gpt2_model.py:286-310: tensors with dim() >= 2 decayed, biases and LayerNorm weights not.  device_type 'cuda' (where the
+        reference picks torch's fused AdamW) with the parameters on the GPU: the arena optimizer train_step, GraphedTrainStep and
+        run_train_model drive (utils.train_utils.FusedAdamW), with these two groups; otherwise torch.optim.AdamW."""
+        from ..utils import train_utils as tu
+        groups = tu.decay_groups(self, weight_decay)
+        if device_type == 'cuda' and all(p.is_cuda for g in groups for p in g['params']):
+            return tu.FusedAdamW(self, lr=learning_rate, betas=betas, param_groups=groups)
         return torch.optim.AdamW(groups, lr=learning_rate, betas=betas)
 
     def estimate_mfu(self, fwdbwd_per_iter, dt, peak_flops=2.5e15):

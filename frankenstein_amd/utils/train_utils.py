@@ -49,6 +49,7 @@ class TrainConfig():
     pin_memory: bool = True
 
     grad_clip: float = 1.0
+    grad_clip_norm: float = 0.0          # > 0: clip the global gradient norm (clip_grad_norm_) instead of the values; needs grad_clip = 0
     mixed_precision: bool = True
 
     visualize_predictions: bool = False
@@ -256,13 +257,72 @@ class GradSync:
         return 1.0 / self.world if self.enabled else 1.0
 
 
+def decay_groups(model: torch.nn.Module, weight_decay: float) -> List[dict]:
+    """The two parameter groups of the reference's GPT.configure_optimizers (models/gpt2_model.py:286-298): trainable tensors with
+    dim() >= 2 (matmul weights, embeddings) decayed, the rest (biases, norm weights) not; a tied tensor appears once."""
+    ps = _unique_trainable(model)
+    return [{'params': [p for p in ps if p.dim() >= 2], 'weight_decay': weight_decay},
+            {'params': [p for p in ps if p.dim() < 2], 'weight_decay': 0.0}]
+
+
+def adamw_tables(offsets, sizes, group_of, touched, lag, t: int, max_slots: int = K.ADAMW_MAX_SLOTS):
+    """The launches of one grouped update, from the arena layout (element offset and size of each parameter, in arena order), the
+    group index of each parameter, which parameters received a gradient, how many steps each has sat out (None: none ever did) and the
+    optimizer's step count t (including this step).  A pure function: nothing is modified.
+
+    Returns a list of (segments, slots), one entry per launch: segments = [(begin, end, slot)] sorted by begin, edges multiples of 4,
+    adjacent parameters of equal slot merged; slots = [(group, step)], step = t - lag being the parameter's own bias-correction count.
+    A parameter without a gradient is in no segment (torch.optim.AdamW: `if p.grad is None: continue`).  A launch carries at most
+    max_slots slots: the distinct (group, step) pairs are numbered in order of first appearance, and launch k takes the segments of
+    pairs k * max_slots .. (k + 1) * max_slots - 1 -- one launch unless many parameters have sat out different numbers of steps."""
+    keys, merged = {}, []                               # (group, step) -> number; [(begin, end, number)]
+    for i, (o, n) in enumerate(zip(offsets, sizes)):
+        if not touched[i]:
+            continue
+        key = (int(group_of[i]), int(t) - (0 if lag is None else int(lag[i])))
+        k = keys.setdefault(key, len(keys))
+        e = o + (n + 3) // 4 * 4
+        if merged and merged[-1][1] == o and merged[-1][2] == k:
+            merged[-1] = (merged[-1][0], e, k)
+        else:
+            merged.append((o, e, k))
+    order = list(keys)
+    launches = []
+    for first in range(0, len(order), max_slots):
+        segs = [(b, e, k - first) for b, e, k in merged if first <= k < first + max_slots]
+        launches.append((segs, order[first:first + max_slots]))
+    return launches
+
+
 class FusedAdamW:
-    """torch.optim.AdamW(model.parameters(), lr, weight_decay) semantics (betas .9/.999, eps 1e-8, decoupled decay on
-    every parameter, utils/train_utils.py:117-119) + clip_grad_value_ (:142), as one kernel over the arena."""
+    """torch.optim.AdamW semantics (betas .9/.999, eps 1e-8, decoupled decay, utils/train_utils.py:117-119) + clip_grad_value_ (:142),
+    as one kernel over the arena.  Without `param_groups` every parameter is in one group, as in the reference's training loop.
+
+    param_groups: a list of dicts with `params` and any of `weight_decay`, `betas`, `eps`, `lr`, `lr_scale` (the rest comes from the
+    constructor's arguments); trainable parameters that no dict lists form a last, default group.  train_step / GraphedTrainStep set
+    each group's lr to the schedule's value times its `lr_scale`.  The arena keeps model.parameters() order whatever the groups are.
+    grad_clip_norm > 0: torch.nn.utils.clip_grad_norm_ (global L2 norm over the parameters that received a gradient, after the
+    data-parallel mean) instead of the value clip; `last_grad_norm` is then a one-element device tensor holding the norm of the last
+    step (reading it synchronises; the optimizer never does).  Groups or the norm clip take fk_adamw_step_groups: one launch for the
+    whole arena (two with the norm), driven by a segment table that is uploaded only when its content changes."""
 
     def __init__(self, model: torch.nn.Module, lr: float = 1e-3, weight_decay: float = 1e-2, betas=(0.9, 0.999),
                  eps: float = 1e-8, grad_clip: Optional[float] = None, group=None, bucket_bytes: int = 8 << 20,
-                 overlap_wgrad: Optional[bool] = None, sync_always: bool = False):
+                 overlap_wgrad: Optional[bool] = None, sync_always: bool = False, param_groups: Optional[List[dict]] = None,
+                 grad_clip_norm: Optional[float] = None):
+        if (grad_clip or 0.0) > 0 and (grad_clip_norm or 0.0) > 0:
+            raise ValueError("grad_clip (clip_grad_value_) and grad_clip_norm (clip_grad_norm_) are alternatives: set one of them")
+        if param_groups is not None:                      # checked before the arena takes the parameters over
+            param_groups = [dict(g) for g in param_groups]
+            trainable, listed = {id(p) for p in _unique_trainable(model)}, set()
+            for gi, g in enumerate(param_groups):
+                g['params'] = list(g['params'])
+                for p in g['params']:
+                    if id(p) not in trainable:
+                        raise ValueError(f"param_groups[{gi}] lists a tensor {tuple(p.shape)} that is not a trainable parameter of the model")
+                    if id(p) in listed:
+                        raise ValueError(f"param_groups[{gi}] lists a parameter {tuple(p.shape)} that is already in a group")
+                    listed.add(id(p))
         self.arena = ParamArena(model)
         if overlap_wgrad is None:
             overlap_wgrad = os.environ.get("FK_WGRAD_STREAM", "0") == "1"        # off by default: see engine.py (no speed-up with one-block-per-CU grids)
@@ -270,8 +330,24 @@ class FusedAdamW:
             E.enable_wgrad_stream(True)
         self.m = torch.zeros_like(self.arena.flat)
         self.v = torch.zeros_like(self.arena.flat)
-        self.param_groups = [dict(params=self.arena.params, lr=lr, weight_decay=weight_decay, betas=betas, eps=eps)]
+        if param_groups is None:
+            self.param_groups = [dict(params=self.arena.params, lr=lr, weight_decay=weight_decay, betas=betas, eps=eps)]
+            self._group_of = [0] * len(self.arena.params)
+        else:
+            rest = [p for p in self.arena.params if id(p) not in listed]
+            self.param_groups = []
+            for g in param_groups + ([dict(params=rest)] if rest else []):
+                scale = float(g.get('lr_scale', 1.0))
+                self.param_groups.append({**g, 'lr': g.get('lr', lr * scale), 'weight_decay': g.get('weight_decay', weight_decay),
+                                          'betas': tuple(g.get('betas', betas)), 'eps': g.get('eps', eps), 'lr_scale': scale})
+            where = {id(p): gi for gi, g in enumerate(self.param_groups) for p in g['params']}
+            self._group_of = [where[id(p)] for p in self.arena.params]
         self.grad_clip = grad_clip
+        self.grad_clip_norm = grad_clip_norm
+        self.last_grad_norm: Optional[torch.Tensor] = None      # device scalar, set by a norm-clipped step
+        self._tables = {}                # (touched, lag) -> [(segments, [(group, -lag)])]: the launches of adamw_tables at t = 0
+        self._seg_dev = {}               # segments -> their device table
+        self._sumsq = None               # (partials, norm) device buffers of the norm clip
         self.t = 0
         # torch.optim.AdamW leaves a parameter alone whose .grad is None (after the reference's zero_grad(set_to_none=True),
         # utils/train_utils.py:134, that is a parameter the backward never reached): no decay, no moment update, its own step count.
@@ -350,12 +426,60 @@ class FusedAdamW:
                           "if the gradients were written into arena.grad directly (or by a replayed graph), call mark_touched() first",
                           RuntimeWarning, stacklevel=2)
         self.t += 1
-        for s0, s1, t in self._update_ranges():
-            K.adamw_step_(a.flat[s0:s1], a.grad[s0:s1], self.m[s0:s1], self.v[s0:s1], t, g['lr'], g['betas'][0], g['betas'][1],
-                          g['eps'], g['weight_decay'], clip=self.grad_clip or 0.0, grad_scale=scale, zero_grad=True)
+        if len(self.param_groups) == 1 and not (self.grad_clip_norm or 0.0) > 0:
+            for s0, s1, t in self._update_ranges():
+                K.adamw_step_(a.flat[s0:s1], a.grad[s0:s1], self.m[s0:s1], self.v[s0:s1], t, g['lr'], g['betas'][0], g['betas'][1],
+                              g['eps'], g['weight_decay'], clip=self.grad_clip or 0.0, grad_scale=scale, zero_grad=True)
+        else:
+            self._step_groups(scale)
         self._touched = [False] * len(a.params)
         E.bump_weight_epoch()
         E.refresh_shadows(self.arena.params)       # every weight shadow re-packed from the new masters in one launch
+
+    def _device_table(self, segs) -> torch.Tensor:
+        key = tuple(segs)
+        tab = self._seg_dev.get(key)
+        if tab is None:                                   # a new table (first step, or the set of reached parameters changed): upload it
+            if len(self._seg_dev) >= 8:
+                self._seg_dev.clear()
+            tab = self._seg_dev[key] = K.adamw_segments(segs, self.arena.flat.device)
+        return tab
+
+    def _step_groups(self, scale: float) -> None:
+        """The grouped update: per launch of adamw_tables one fk_adamw_step_groups over the whole arena (one launch unless more than 16
+        (group, step) pairs are alive), preceded by one fk_grad_sumsq when the global norm is clipped.  The per-step numbers (learning
+        rates, bias-correction steps, the 1/world scale) travel by value with the launch; the device table only changes when the set
+        of reached parameters or their lags change, so a steady-state step uploads nothing and never synchronises."""
+        a = self.arena
+        if self._lag is None and not all(self._touched):
+            self._lag = [0] * len(a.params)
+        key = (tuple(self._touched), None if self._lag is None else tuple(self._lag))
+        launches = self._tables.get(key)
+        if launches is None:
+            if len(self._tables) >= 8:
+                self._tables.clear()
+            launches = self._tables[key] = adamw_tables(a.offsets, [p.numel() for p in a.params], self._group_of, self._touched, self._lag, 0)
+        if self._lag is not None:                         # a parameter without a gradient sits this step out
+            self._lag = [l + (not tch) for l, tch in zip(self._lag, self._touched)]
+        max_norm = float(self.grad_clip_norm or 0.0)
+        partials = norm = None
+        if max_norm > 0 and launches:
+            if self._sumsq is None:
+                self._sumsq = (torch.empty(K.GRAD_SUMSQ_BLOCKS, dtype=torch.float32, device=a.flat.device),
+                               torch.zeros(1, dtype=torch.float32, device=a.flat.device))
+            partials, norm = self._sumsq
+            # the norm is over every reached parameter: the one launch's own table, or the union of the launches' tables
+            cover = launches[0][0] if len(launches) == 1 else sorted((b, e, 0) for segs, _ in launches for b, e, _ in segs)
+            K.grad_sumsq_(a.grad, self._device_table(cover), partials)
+        for segs, slots in launches:
+            hyper = []
+            for gi, neg_lag in slots:
+                g = self.param_groups[gi]
+                hyper.append((g['lr'], g['betas'][0], g['betas'][1], g['eps'], g['weight_decay'], self.t + neg_lag))
+            K.adamw_step_groups_(a.flat, a.grad, self.m, self.v, self._device_table(segs), hyper, clip=self.grad_clip or 0.0,
+                                 grad_scale=scale, zero_grad=True, max_norm=max_norm, partials=partials, norm_out=norm)
+        if norm is not None:
+            self.last_grad_norm = norm
 
     def state_dict(self):
         return dict(t=self.t, m=self.m, v=self.v, lag=None if self._lag is None else list(self._lag),
@@ -423,7 +547,7 @@ def train_step(model, batch, optimizer: FusedAdamW, step: int, cfg: TrainConfig,
     get_lr = scheduler or init_lr_scheduler(cfg)
     lr = get_lr(step)
     for g in optimizer.param_groups:
-        g['lr'] = lr
+        g['lr'] = lr * g.get('lr_scale', 1.0)
     inputs, labels, date_info = batch
     k = max(1, cfg.grad_accum)
     mode = accumulate or ACCUMULATE
@@ -493,7 +617,7 @@ class GraphedTrainStep:
                 dst.copy_(src, non_blocking=True)
         lr = self.get_lr(step)
         for g in self.optimizer.param_groups:
-            g['lr'] = lr
+            g['lr'] = lr * g.get('lr_scale', 1.0)
         self.graph.replay()
         self.optimizer.mark_touched(self._touched)
         self.optimizer.sync.enabled = True             # no bucket went out during the replay: finish() exchanges all of them
@@ -702,7 +826,8 @@ def _train_loop(model, datasets, config, save_folder, logger, rank: int, world: 
     train_loader, val_loader = prepare_data_loaders(train_dataset, val_dataset, config)
     train_loader, val_loader = ShardedLoader(train_loader, rank, world, device), ShardedLoader(val_loader, rank, world, device)
     model.to(device).float()
-    optimizer = FusedAdamW(model, lr=config.learning_rate, weight_decay=config.weight_decay, grad_clip=config.grad_clip)
+    optimizer = FusedAdamW(model, lr=config.learning_rate, weight_decay=config.weight_decay, grad_clip=config.grad_clip,
+                           grad_clip_norm=getattr(config, 'grad_clip_norm', 0.0))
     scheduler = init_lr_scheduler(config)
     overall_step, best_val = 0, float('inf')
     accum = GradAccumulation(config.grad_accum)
@@ -716,7 +841,10 @@ def _train_loop(model, datasets, config, save_folder, logger, rank: int, world: 
             if rank == 0:
                 print('*', end='')
                 if logger is not None:
-                    logger({'train/loss': float(loss), 'lr': optimizer.param_groups[0]['lr']}, overall_step)
+                    log = {'train/loss': float(loss), 'lr': optimizer.param_groups[0]['lr']}
+                    if optimizer.last_grad_norm is not None:          # float(loss) has synchronised already
+                        log['train/grad_norm'] = float(optimizer.last_grad_norm)
+                    logger(log, overall_step)
             if overall_step % config.eval_interval == 0:
                 model.eval()
                 with torch.no_grad():
@@ -745,5 +873,5 @@ def _train_loop(model, datasets, config, save_folder, logger, rank: int, world: 
 
 def simple_train_model(model, datasets, config, project_name='transformer'):
     """Single-process variant (utils/train_utils.py:189-260): no gradient clipping."""
-    cfg = TrainConfig(**{**config.__dict__, 'grad_clip': 0.0})
+    cfg = TrainConfig(**{**config.__dict__, 'grad_clip': 0.0, 'grad_clip_norm': 0.0})
     return run_train_model(model, datasets, cfg, project_name, Path('logs'))

@@ -510,6 +510,26 @@ int fk_transpose2d(const void* src, int64_t lds, void* dst, int64_t ldd, int64_t
 int fk_adamw_step(float* p, float* g, float* m, float* v, int64_t n, double lr, double beta1, double beta2, double eps,
                   double weight_decay, int64_t step, double clip, double grad_scale, int zero_grad, void* stream);
 
+/* ---- the same update for several parameter groups, skipped parameters and torch.nn.utils.clip_grad_norm_, in ONE launch over the arena.
+ *      segs: DEVICE array of nseg records sorted by begin, disjoint, begin / end multiples of 4 elements (the arena pads every tensor
+ *      to 4); elements of [0, n) that lie in no segment are neither read nor written.  slot indexes `groups`, a HOST array of nslots
+ *      (1..FK_ADAMW_MAX_SLOTS) hyper-parameter sets -- one per distinct (parameter group, bias-correction step) -- that is turned into
+ *      floats exactly as fk_adamw_step does and travels by value with the launch; the per-element arithmetic is fk_adamw_step's, so
+ *      one segment [0, n) with one slot gives its bits.  clip, grad_scale, zero_grad: as in fk_adamw_step.
+ *   fk_grad_sumsq : partials[b] = block b's share of sum g^2 over the segments (the slots are ignored), b < npartials
+ *                   (1..FK_GRAD_SUMSQ_MAX_BLOCKS blocks).  Fixed grid and summation order, no atomics: the same bits on every run.
+ *   max_norm > 0  : every block of fk_adamw_step_groups adds the npartials partials in one fixed order, total = grad_scale * sqrt(sum),
+ *                   coef = min(1, max_norm / (total + 1e-6)), and the gradient is g * grad_scale * coef; norm_out[0] = total (device
+ *                   float).  max_norm == 0: no norm clip, partials / norm_out may be NULL.                                          */
+#define FK_ADAMW_MAX_SLOTS 16
+#define FK_GRAD_SUMSQ_MAX_BLOCKS 1024
+typedef struct fk_adamw_seg { int64_t begin, end; int32_t slot, reserved; } fk_adamw_seg;
+typedef struct fk_adamw_group { double lr, beta1, beta2, eps, weight_decay; int64_t step; } fk_adamw_group;
+int fk_grad_sumsq(const float* g, int64_t n, const fk_adamw_seg* segs, int64_t nseg, float* partials, int npartials, void* stream);
+int fk_adamw_step_groups(float* p, float* g, float* m, float* v, int64_t n, const fk_adamw_seg* segs, int64_t nseg,
+                         const fk_adamw_group* groups, int nslots, double clip, double grad_scale, int zero_grad, double max_norm,
+                         const float* partials, int npartials, float* norm_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
