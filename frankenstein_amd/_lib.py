@@ -109,8 +109,15 @@ SIGNATURES = {
     "fk_adamw_step": (_int, [_p, _p, _p, _p, _i64, _f64, _f64, _f64, _f64, _f64, _i64, _f64, _f64, _int, _p]),
     "fk_grad_sumsq": (_int, [_p, _i64, _p, _i64, _p, _int, _p]),
     "fk_adamw_step_groups": (_int, [_p, _p, _p, _p, _i64, _p, _i64, _p, _int, _f64, _f64, _int, _f64, _p, _int, _p, _p]),
+    "fk_vq_route": (_int, [_i64, _i64, _int]),
+    "fk_vq_assign": (_int, [_p, _i64, _p, _p, _p, _p, _i64, _p, _i64, _p, _p, _f32, _p, _i64, _i64, _i64, _int, _p]),
+    "fk_vq_bwd": (_int, [_p, _p, _p, _p, _f32, _p, _i64, _int, _p]),
+    "fk_vq_codebook_update": (_int, [_p, _p, _p, _p, _i64, _p, _i64, _p, _p, _i64, _i64, _f32, _f32, _f32, _int, _p]),
 }
 ADAMW_MAX_SLOTS, GRAD_SUMSQ_MAX_BLOCKS = 16, 1024
+VQ_CHAIN, VQ_FUSED = 0, 1                                                             # fk_vq_route
+VQ_EMA, VQ_KMEANS = 0, 1                                                              # fk_vq_codebook_update modes
+VQ_ROWS = 32                                                                          # data rows per workgroup of fk_vq_assign
 
 
 class AdamwGroup(C.Structure):

@@ -1026,6 +1026,38 @@ class StraightThrough(torch.autograd.Function):
         return dq, None
 
 
+class VQLookupFn(torch.autograd.Function):
+    """(x [..., D], codes fp32 [K, D], commitment_weight) -> (q, idx, commit): the nearest unit-norm code of every row in one launch
+    (fk_vq_assign: exact fp32 cosine similarity for either compute dtype, lowest index on a tie), q = codes[idx] in x's dtype as the
+    straight-through output, idx int64 [...], commit = commitment_weight * mean((x - q)^2) as an fp32 scalar.  counts [K] / sums [K, D]
+    (K.vq_stats) collect the per-code row counts and unit-norm row sums of the same launch.  Backward: dx = dq + dcommit * 2 *
+    commitment_weight / numel * (x - q) in one launch (fk_vq_bwd); no gradient goes to the codes."""
+
+    @staticmethod
+    def forward(ctx, x, codes, commitment_weight, counts=None, sums=None):
+        D = x.shape[-1]
+        x2 = x.detach().reshape(-1, D)
+        if x2.stride(1) != 1 or x2.stride(0) % 4 != 0:
+            x2 = x2.contiguous()
+        idx, q, commit = K.vq_assign(x2, codes.detach(), True, counts, sums, commitment_weight / x2.numel())
+        ctx.save_for_backward(x2, q)
+        ctx.c_scale = 2.0 * commitment_weight / x2.numel()
+        ctx.xshape = x.shape
+        idx = idx.view(x.shape[:-1])
+        ctx.mark_non_differentiable(idx)
+        return q.view(x.shape), idx, commit.view(())
+
+    @staticmethod
+    def backward(ctx, dq, _didx, dcommit):
+        x2, q = ctx.saved_tensors
+        if dq is not None:
+            dq = dq.reshape(x2.shape).contiguous()
+        if dcommit is not None:
+            dcommit = dcommit.reshape(1).float().contiguous()
+        dx = K.vq_bwd(x2.contiguous(), q, dq, dcommit, ctx.c_scale)
+        return dx.view(ctx.xshape), None, None, None, None
+
+
 # --------------------------------------------------------------------------------------------- MAE pieces (SURVEY §8f)
 class GatherRows(torch.autograd.Function):
     """out[b, i, :] = src[b, idx[b, i], :]  (models/brainformer.py:441,468); idx rows are unique per sample."""

@@ -986,6 +986,82 @@ def argmax_rows(x: Tensor) -> Tensor:
     return idx
 
 
+# ------------------------------------------------------------------------------------------- vector quantiser (csrc/vq.hip)
+VQ_EMA, VQ_KMEANS = _lib.VQ_EMA, _lib.VQ_KMEANS
+_vq_tickets = {}          # device index -> the uint32 word fk_vq_assign's last workgroup is found with (0 between launches)
+
+
+def vq_route(D: int, K: int, dtype=torch.float32) -> bool:
+    """True when vq_assign takes a [*, D] problem with K codes in this dtype (fk_vq_route; host-side query, no launch); a dtype the
+    library does not know is outside the envelope like any other."""
+    code = {torch.float32: FK_F32, torch.bfloat16: FK_BF16}.get(dtype, -1)
+    return lib().fk_vq_route(D, K, code) == _lib.VQ_FUSED
+
+
+def vq_stats(K: int, D: int, device) -> Tuple[Tensor, Tensor, Tensor]:
+    """-> (packed, counts, sums): one cleared fp32 [K, D + 1] tensor and its views sums = packed[:, :D], counts = packed[:, D] — what
+    vq_assign accumulates into, vq_codebook_update reads and data parallel all-reduces as ONE tensor."""
+    packed = torch.zeros((K, D + 1), dtype=torch.float32, device=device)
+    return packed, packed[:, D], packed[:, :D]
+
+
+def vq_assign(x: Tensor, codes: Tensor, want_q: bool = True, counts: Optional[Tensor] = None, sums: Optional[Tensor] = None,
+              commit_scale: Optional[float] = None):
+    """Nearest code of every row in one launch: x [R, D] (fp32 / bf16, any row stride), codes fp32 [K, D] -> (idx int64 [R], q [R, D] in
+    x's dtype or None, commit fp32 [1] = commit_scale * sum (x - q)^2 or None).  counts [K] / sums [K, D] (fp32 views, see vq_stats) are
+    accumulated into when given."""
+    assert x.dim() == 2 and x.stride(1) == 1 and codes.dim() == 2 and codes.dtype == torch.float32 and codes.is_contiguous()
+    R, D = x.shape
+    Kc = codes.shape[0]
+    assert codes.shape[1] == D and R > 0
+    idx = torch.empty(R, dtype=torch.int64, device=x.device)
+    q = torch.empty((R, D), dtype=x.dtype, device=x.device) if want_q else None
+    if counts is not None:
+        assert counts.dtype == torch.float32 and counts.shape == (Kc,)
+    if sums is not None:
+        assert sums.dtype == torch.float32 and sums.shape == (Kc, D) and sums.stride(1) == 1
+    partials = commit = ticket = None
+    if commit_scale is not None:
+        partials = torch.empty((R + _lib.VQ_ROWS - 1) // _lib.VQ_ROWS, dtype=torch.float32, device=x.device)
+        commit = torch.empty(1, dtype=torch.float32, device=x.device)
+        ticket = _vq_tickets.get(x.device.index)
+        if ticket is None:
+            ticket = _vq_tickets[x.device.index] = torch.zeros(1, dtype=torch.int32, device=x.device)
+    with _timed("vq_assign"):
+        call("fk_vq_assign", x.data_ptr(), x.stride(0), codes.data_ptr(), idx.data_ptr(), _ptr(q), _ptr(counts),
+             counts.stride(0) if counts is not None else 0, _ptr(sums), sums.stride(0) if sums is not None else 0, _ptr(partials),
+             _ptr(commit), commit_scale or 0.0, _ptr(ticket), R, Kc, D, fk_dtype(x), _stream())
+    return idx, q, commit
+
+
+def vq_bwd(x: Tensor, q: Tensor, dq: Optional[Tensor], d_commit: Optional[Tensor], c_scale: float) -> Tensor:
+    """dx = dq + d_commit * c_scale * (x - q)  (contiguous tensors of one dtype; d_commit a one-element fp32 device tensor)."""
+    assert x.is_contiguous() and q.is_contiguous() and q.shape == x.shape and q.dtype == x.dtype
+    assert dq is None or (dq.is_contiguous() and dq.shape == x.shape and dq.dtype == x.dtype)
+    assert d_commit is None or (d_commit.dtype == torch.float32 and d_commit.numel() == 1)
+    dx = torch.empty_like(x)
+    with _timed("vq_bwd"):
+        call("fk_vq_bwd", x.data_ptr(), q.data_ptr(), _ptr(dq), _ptr(d_commit), c_scale, dx.data_ptr(), x.numel(), fk_dtype(x), _stream())
+    return dx
+
+
+def vq_codebook_update(embed: Tensor, counts: Tensor, sums: Tensor, mode: int, embed_avg: Optional[Tensor] = None,
+                       cluster_size: Optional[Tensor] = None, seed: Optional[Tensor] = None, decay: float = 0.0, eps: float = 0.0,
+                       dead: float = 0.0) -> Tensor:
+    """In place over the K codes (fp32): VQ_EMA — the EMA step with dead-code re-seeding from `seed` [K, D]; VQ_KMEANS — embed_j =
+    normalize(sums_j / counts_j) where counts_j > 0 (include/franken_hip.h, fk_vq_codebook_update)."""
+    Kc, D = embed.shape
+    assert embed.dtype == torch.float32 and embed.is_contiguous()
+    assert counts.dtype == torch.float32 and counts.shape == (Kc,) and sums.dtype == torch.float32 and sums.shape == (Kc, D) and sums.stride(1) == 1
+    for t, shape in ((embed_avg, (Kc, D)), (cluster_size, (Kc,)), (seed, (Kc, D))):
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape)
+    n_ws = torch.empty(1, dtype=torch.float32, device=embed.device) if mode == VQ_EMA else None
+    with _timed("vq_codebook_update"):
+        call("fk_vq_codebook_update", embed.data_ptr(), _ptr(embed_avg), _ptr(cluster_size), counts.data_ptr(), counts.stride(0),
+             sums.data_ptr(), sums.stride(0), _ptr(seed), _ptr(n_ws), Kc, D, decay, eps, dead, mode, _stream())
+    return embed
+
+
 # ------------------------------------------------------------------------------------------- losses
 def l1_loss_fwd(pred: Tensor, target: Tensor, squared: bool = False, row_weight: Optional[Tensor] = None) -> Tensor:
     """-> loss2 fp32[2] = {mean (weighted) |d| or d^2, weight sum}; row_weight: fp32 [rows] with rows = numel / last dim."""

@@ -530,6 +530,41 @@ int fk_adamw_step_groups(float* p, float* g, float* m, float* v, int64_t n, cons
                          const fk_adamw_group* groups, int nslots, double clip, double grad_scale, int zero_grad, double max_norm,
                          const float* partials, int npartials, float* norm_out, void* stream);
 
+/* ---- vector quantiser of the VQ-VAE tokenizer (frankenstein_amd/models/vq_brain.py VectorQuantize: cosine-similarity codebook, build-defined
+ *      semantics).  R data rows, K codes, D code dimension; codes / embed / embed_avg / sums fp32 [K, D], cluster_size / counts fp32 [K].
+ * fk_vq_route: FK_VQ_FUSED when fk_vq_assign takes the problem (dtype FK_F32 / FK_BF16, D % 4 == 0, 4 <= D <= 128, 1 <= K < 2^31),
+ *   else FK_VQ_CHAIN: the caller keeps the chain fk_norm_fwd, fk_gemm_nt, fk_argmax_rows, fk_gather_rows.  Host only, nothing is launched.
+ * fk_vq_assign: one launch.  xn_r = x_r / max(|x_r|, 1e-12);  idx[r] = argmax_j <xn_r, codes_j>, the lowest index on an exact tie (a row
+ *   of NaNs gives 0, as fk_argmax_rows); the similarity is exact fp32 (v_mfma_f32_32x32x2_f32) for either dtype of x, the codes are
+ *   always the fp32 buffer.  x [R, D] in `dtype`, row stride ldx (elements, a multiple of 4).  Optional outputs (NULL = not written):
+ *     q [R, D] in `dtype`, contiguous: codes[idx[r]] rounded to `dtype`;
+ *     counts[j * counts_stride] += #rows with idx == j,  sums[j * ld_sums + d] += sum of xn_r[d] over those rows (fp32 atomics: the
+ *       caller clears them; one packed [K, D + 1] tensor serves both);
+ *     commit[0] = commit_scale * sum_r,d (x - q)^2 with q as rounded above: commit_partials holds ceil(R / 32) floats, one per workgroup,
+ *       every one written; the last workgroup to finish adds them in index order (the same bits on every run).  ticket: a device word
+ *       that is 0 before the launch and 0 again after it; launches that share it must be ordered on one stream.
+ * fk_vq_bwd: dx[i] = dq[i] + d_commit[0] * c_scale * (x[i] - q[i]) over n contiguous elements of `dtype`: the straight-through gradient
+ *   plus the commitment gradient (c_scale = 2 * commitment_weight / (R * D)).  dq == NULL counts as 0, d_commit == NULL as 0.
+ * fk_vq_codebook_update: over the K codes; the EMA mode is two launches (the cluster sizes and their sum n by one workgroup into
+ *   n_ws[0], one float of device scratch; then the codes), the k-means mode one.
+ *   FK_VQ_EMA   : cs = decay * cs + (1 - decay) * counts;  avg = decay * avg + (1 - decay) * sums;  n = sum cs;
+ *                 smoothed = (cs + eps) / (n + K * eps) * n;  embed = normalize(avg / smoothed);  codes with cs < dead are re-seeded:
+ *                 embed = normalize(seed), avg = embed * dead, cs = dead.  seed fp32 [K, D]: rows of the batch (any positive length).
+ *   FK_VQ_KMEANS: embed_j = normalize(sums_j / counts_j) where counts_j > 0, unchanged elsewhere; embed_avg, cluster_size, seed and n_ws
+ *                 are not touched and may be NULL.
+ *   normalize(v) = v / max(|v|, 1e-12).                                                                                              */
+enum { FK_VQ_CHAIN = 0, FK_VQ_FUSED = 1 };
+enum { FK_VQ_EMA = 0, FK_VQ_KMEANS = 1 };
+int fk_vq_route(int64_t D, int64_t K, int dtype);
+int fk_vq_assign(const void* x, int64_t ldx, const float* codes, int64_t* idx, void* q, float* counts, int64_t counts_stride, float* sums,
+                 int64_t ld_sums, float* commit_partials, float* commit, float commit_scale, uint32_t* ticket, int64_t R, int64_t K,
+                 int64_t D, int dtype, void* stream);
+int fk_vq_bwd(const void* x, const void* q, const void* dq, const float* d_commit, float c_scale, void* dx, int64_t n, int dtype,
+              void* stream);
+int fk_vq_codebook_update(float* embed, float* embed_avg, float* cluster_size, const float* counts, int64_t counts_stride,
+                          const float* sums, int64_t ld_sums, const float* seed, float* n_ws, int64_t K, int64_t D, float decay, float eps,
+                          float dead, int mode, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
