@@ -11,18 +11,10 @@
 
 namespace {
 
-constexpr int TPB = 256;
-inline unsigned grid_for(int64_t work, int64_t cap = 1 << 20) {
-  int64_t b = fk_cdiv(work, TPB);
-  if (b > cap) b = cap;
-  if (b < 1) b = 1;
-  return (unsigned)b;
-}
-template <typename T> struct VW { static constexpr int N = 16 / sizeof(T); };
 
 template <typename T>
 __global__ void im2col1d_kernel(const T* x, T* cols, int64_t B, int64_t Tin, int64_t Tout, int Cin, int K, int stride, int dil, int pad) {
-  constexpr int N = VW<T>::N;
+  constexpr int N = VecIO<T>::N;
   const int cv = Cin / N;
   const int64_t total = B * Tout * K * cv;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
@@ -38,7 +30,7 @@ __global__ void im2col1d_kernel(const T* x, T* cols, int64_t B, int64_t Tin, int
 
 template <typename T>
 __global__ void col2im1d_kernel(const T* dcols, T* dx, int64_t B, int64_t Tin, int64_t Tout, int Cin, int K, int stride, int dil, int pad) {
-  constexpr int N = VW<T>::N;
+  constexpr int N = VecIO<T>::N;
   const int cv = Cin / N;
   const int64_t total = B * Tin * cv;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
@@ -117,7 +109,7 @@ __global__ void argmax_rows_kernel(const T* x, int64_t ld, int64_t* idx, int64_t
 extern "C" {
 
 #define FK_CONV_CHECK(name)                                                                                                    \
-  FK_CHECK_ARG(dtype == FK_F32 || dtype == FK_BF16, name ": bad dtype %d", dtype);                                             \
+  FK_DT_CHECK(name);                                                                                                           \
   const int vec = dtype == FK_BF16 ? 8 : 4;                                                                                    \
   FK_CHECK_ARG(B > 0 && T > 0 && Cin > 0 && K > 0 && stride > 0 && dil > 0 && Cin % vec == 0, name ": bad shape (Cin %% %d)", vec); \
   const int64_t Tout = (T - 1) / stride + 1, pad = dil * (K - 1)
@@ -127,8 +119,8 @@ int fk_im2col1d(const void* x, void* cols, int64_t B, int64_t T, int64_t Cin, in
   FK_CHECK_ARG(x && cols && ((uintptr_t)x & 15) == 0 && ((uintptr_t)cols & 15) == 0, "fk_im2col1d: pointers must be 16-byte aligned");
   hipStream_t s = (hipStream_t)stream;
   const int64_t work = B * Tout * K * (Cin / vec);
-  if (dtype == FK_BF16) hipLaunchKernelGGL(im2col1d_kernel<bf16_t>, dim3(grid_for(work, 65536)), dim3(TPB), 0, s, (const bf16_t*)x, (bf16_t*)cols, B, T, Tout, (int)Cin, (int)K, (int)stride, (int)dil, (int)pad);
-  else hipLaunchKernelGGL(im2col1d_kernel<float>, dim3(grid_for(work, 65536)), dim3(TPB), 0, s, (const float*)x, (float*)cols, B, T, Tout, (int)Cin, (int)K, (int)stride, (int)dil, (int)pad);
+  // `E`: T is the sequence length here
+  FK_BY_DTYPE(dtype, E, hipLaunchKernelGGL(im2col1d_kernel<E>, dim3(fk_grid(work, 65536)), dim3(FK_TPB), 0, s, (const E*)x, (E*)cols, B, T, Tout, (int)Cin, (int)K, (int)stride, (int)dil, (int)pad));
   FK_CHECK_LAUNCH("fk_im2col1d");
   return FK_OK;
 }
@@ -138,8 +130,7 @@ int fk_col2im1d(const void* dcols, void* dx, int64_t B, int64_t T, int64_t Cin, 
   FK_CHECK_ARG(dcols && dx && ((uintptr_t)dx & 15) == 0 && ((uintptr_t)dcols & 15) == 0, "fk_col2im1d: pointers must be 16-byte aligned");
   hipStream_t s = (hipStream_t)stream;
   const int64_t work = B * T * (Cin / vec);
-  if (dtype == FK_BF16) hipLaunchKernelGGL(col2im1d_kernel<bf16_t>, dim3(grid_for(work, 65536)), dim3(TPB), 0, s, (const bf16_t*)dcols, (bf16_t*)dx, B, T, Tout, (int)Cin, (int)K, (int)stride, (int)dil, (int)pad);
-  else hipLaunchKernelGGL(col2im1d_kernel<float>, dim3(grid_for(work, 65536)), dim3(TPB), 0, s, (const float*)dcols, (float*)dx, B, T, Tout, (int)Cin, (int)K, (int)stride, (int)dil, (int)pad);
+  FK_BY_DTYPE(dtype, E, hipLaunchKernelGGL(col2im1d_kernel<E>, dim3(fk_grid(work, 65536)), dim3(FK_TPB), 0, s, (const E*)dcols, (E*)dx, B, T, Tout, (int)Cin, (int)K, (int)stride, (int)dil, (int)pad));
   FK_CHECK_LAUNCH("fk_col2im1d");
   return FK_OK;
 }
@@ -147,16 +138,14 @@ int fk_col2im1d(const void* dcols, void* dx, int64_t B, int64_t T, int64_t Cin, 
 int fk_elu_fwd(const void* x, void* y, int64_t n, int dtype, void* stream) {
   FK_CHECK_ARG((dtype == FK_F32 || dtype == FK_BF16) && x && y && n > 0, "fk_elu_fwd: bad arguments");
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == FK_BF16) hipLaunchKernelGGL(elu_fwd_kernel<bf16_t>, dim3(grid_for(n, 65536)), dim3(TPB), 0, s, (const bf16_t*)x, (bf16_t*)y, n);
-  else hipLaunchKernelGGL(elu_fwd_kernel<float>, dim3(grid_for(n, 65536)), dim3(TPB), 0, s, (const float*)x, (float*)y, n);
+  FK_BY_DTYPE(dtype, T, hipLaunchKernelGGL(elu_fwd_kernel<T>, dim3(fk_grid(n, 65536)), dim3(FK_TPB), 0, s, (const T*)x, (T*)y, n));
   FK_CHECK_LAUNCH("fk_elu_fwd");
   return FK_OK;
 }
 int fk_elu_bwd(const void* x, const void* dy, void* dx, int64_t n, int dtype, void* stream) {
   FK_CHECK_ARG((dtype == FK_F32 || dtype == FK_BF16) && x && dy && dx && n > 0, "fk_elu_bwd: bad arguments");
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == FK_BF16) hipLaunchKernelGGL(elu_bwd_kernel<bf16_t>, dim3(grid_for(n, 65536)), dim3(TPB), 0, s, (const bf16_t*)x, (const bf16_t*)dy, (bf16_t*)dx, n);
-  else hipLaunchKernelGGL(elu_bwd_kernel<float>, dim3(grid_for(n, 65536)), dim3(TPB), 0, s, (const float*)x, (const float*)dy, (float*)dx, n);
+  FK_BY_DTYPE(dtype, T, hipLaunchKernelGGL(elu_bwd_kernel<T>, dim3(fk_grid(n, 65536)), dim3(FK_TPB), 0, s, (const T*)x, (const T*)dy, (T*)dx, n));
   FK_CHECK_LAUNCH("fk_elu_bwd");
   return FK_OK;
 }
@@ -165,8 +154,7 @@ int fk_argmax_rows(const void* x, int64_t ld, int64_t* idx, int64_t rows, int64_
   FK_CHECK_ARG((dtype == FK_F32 || dtype == FK_BF16) && x && idx && rows > 0 && cols > 0 && cols < (1LL << 31), "fk_argmax_rows: bad arguments");
   hipStream_t s = (hipStream_t)stream;
   const unsigned nb = (unsigned)fk_cdiv(rows, 4);
-  if (dtype == FK_BF16) hipLaunchKernelGGL(argmax_rows_kernel<bf16_t>, dim3(nb), dim3(TPB), 0, s, (const bf16_t*)x, ld, idx, rows, (int)cols);
-  else hipLaunchKernelGGL(argmax_rows_kernel<float>, dim3(nb), dim3(TPB), 0, s, (const float*)x, ld, idx, rows, (int)cols);
+  FK_BY_DTYPE(dtype, T, hipLaunchKernelGGL(argmax_rows_kernel<T>, dim3(nb), dim3(FK_TPB), 0, s, (const T*)x, ld, idx, rows, (int)cols));
   FK_CHECK_LAUNCH("fk_argmax_rows");
   return FK_OK;
 }

@@ -478,7 +478,7 @@ template <typename T, int D, bool GROUPED>
 __global__ __launch_bounds__(256) void attn_decode_beam_kernel(const T* q, int64_t q_bs, T* kv, int64_t kv_bs, int64_t kv_rs, int tmax, const int32_t* anc,
                                                                int64_t anc_ld, T* out, int64_t o_bs, const int32_t* pos, int W, int H, float scale,
                                                                int append) {
-  constexpr int VN = Vec16<T>::N, LPK = D / VN, GROUPS = 256 / LPK;
+  constexpr int VN = VecIO<T>::N, LPK = D / VN, GROUPS = 256 / LPK;
   typedef T vec_t __attribute__((ext_vector_type(VN)));
   __shared__ float red[4][D + 2];
   const int h = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, wave = tid >> 6;
@@ -893,8 +893,7 @@ int fk_gpt_embed_step(const int64_t* idx, const float* wte, const float* wpe, co
                       int64_t vocab, int dtype, void* stream) {
   FK_CHECK_ARG((dtype == FK_F32 || dtype == FK_BF16) && idx && wte && wpe && pos && out && B > 0 && dim > 0 && vocab > 0, "fk_gpt_embed_step: bad arguments");
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == FK_BF16) hipLaunchKernelGGL(gpt_embed_step_kernel<bf16_t>, dim3((unsigned)B), dim3(128), 0, s, idx, wte, wpe, pos, (bf16_t*)out, (int)dim, vocab);
-  else hipLaunchKernelGGL(gpt_embed_step_kernel<float>, dim3((unsigned)B), dim3(128), 0, s, idx, wte, wpe, pos, (float*)out, (int)dim, vocab);
+  FK_BY_DTYPE(dtype, T, hipLaunchKernelGGL(gpt_embed_step_kernel<T>, dim3((unsigned)B), dim3(128), 0, s, idx, wte, wpe, pos, (T*)out, (int)dim, vocab));
   FK_CHECK_LAUNCH("fk_gpt_embed_step");
   return FK_OK;
 }
@@ -902,8 +901,7 @@ int fk_gpt_embed_step(const int64_t* idx, const float* wte, const float* wpe, co
 int fk_kv_append(const void* qkv, void* kv, const int32_t* pos, int64_t B, int64_t d, int64_t tmax, int dtype, void* stream) {
   FK_CHECK_ARG((dtype == FK_F32 || dtype == FK_BF16) && qkv && kv && pos && B > 0 && d > 0 && tmax > 0, "fk_kv_append: bad arguments");
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == FK_BF16) hipLaunchKernelGGL(kv_append_kernel<bf16_t>, dim3((unsigned)B), dim3(256), 0, s, (const bf16_t*)qkv, (bf16_t*)kv, pos, (int)d, tmax);
-  else hipLaunchKernelGGL(kv_append_kernel<float>, dim3((unsigned)B), dim3(256), 0, s, (const float*)qkv, (float*)kv, pos, (int)d, tmax);
+  FK_BY_DTYPE(dtype, T, hipLaunchKernelGGL(kv_append_kernel<T>, dim3((unsigned)B), dim3(256), 0, s, (const T*)qkv, (T*)kv, pos, (int)d, tmax));
   FK_CHECK_LAUNCH("fk_kv_append");
   return FK_OK;
 }

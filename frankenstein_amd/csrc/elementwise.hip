@@ -10,49 +10,11 @@
 
 namespace {
 
-constexpr int TPB = 256;
-inline unsigned grid_for(int64_t work, int64_t cap = 1 << 20) {
-  int64_t b = fk_cdiv(work, TPB);
-  if (b > cap) b = cap;
-  if (b < 1) b = 1;
-  return (unsigned)b;
-}
-
-template <typename T> struct V16;
-template <> struct V16<bf16_t> {
-  static constexpr int N = 8;
-  FK_DEV static void ld(const bf16_t* p, float (&v)[8]) {
-    bf16x8 a = *reinterpret_cast<const bf16x8*>(p);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) v[i] = (float)a[i];
-  }
-  FK_DEV static void st(bf16_t* p, const float (&v)[8]) {
-    bf16x8 a;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) a[i] = (bf16_t)v[i];
-    *reinterpret_cast<bf16x8*>(p) = a;
-  }
-};
-template <> struct V16<float> {
-  static constexpr int N = 4;
-  FK_DEV static void ld(const float* p, float (&v)[4]) {
-    f32x4 a = *reinterpret_cast<const f32x4*>(p);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) v[i] = a[i];
-  }
-  FK_DEV static void st(float* p, const float (&v)[4]) {
-    f32x4 a;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) a[i] = v[i];
-    *reinterpret_cast<f32x4*>(p) = a;
-  }
-};
-
 // ---------------------------------------------------------------------------------------------- RoPE
 template <typename T>
 __global__ void rope_kernel(T* x, int64_t B, int64_t T_, int64_t ld, int rot_cols, int D, const float* table,
                             int64_t table_bs, int64_t pos_off, float sgn) {
-  constexpr int N = V16<T>::N;
+  constexpr int N = VecIO<T>::N;
   const int cpr = rot_cols / N;   // vector chunks per row
   const int64_t total = B * T_ * cpr;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
@@ -62,14 +24,14 @@ __global__ void rope_kernel(T* x, int64_t B, int64_t T_, int64_t ld, int rot_col
     T* px = x + row * ld + col;
     const float* tb = table + b * table_bs + ((pos_off + t) * (D / 2) + d / 2) * 2;
     float v[N], o[N];
-    V16<T>::ld(px, v);
+    VecIO<T>::load(px, v);
 #pragma unroll
     for (int j = 0; j < N / 2; ++j) {
       const float c = tb[2 * j], s = sgn * tb[2 * j + 1];
       o[2 * j] = v[2 * j] * c - v[2 * j + 1] * s;
       o[2 * j + 1] = v[2 * j] * s + v[2 * j + 1] * c;
     }
-    V16<T>::st(px, o);
+    VecIO<T>::store(px, o);
   }
 }
 
@@ -94,62 +56,62 @@ FK_DEV float sigmoidf_(float x) { return 1.0f / (1.0f + __expf(-x)); }
 
 template <typename T>
 __global__ void swiglu_fwd_kernel(const T* h13, T* g, int64_t rows, int H) {
-  constexpr int N = V16<T>::N;
+  constexpr int N = VecIO<T>::N;
   const int cpr = H / N;
   const int64_t total = rows * cpr;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
     const int64_t r = i / cpr;
     const int c = (int)(i % cpr) * N;
     float a[N], b[N], o[N];
-    V16<T>::ld(h13 + r * 2 * H + c, a);
-    V16<T>::ld(h13 + r * 2 * H + H + c, b);
+    VecIO<T>::load(h13 + r * 2 * H + c, a);
+    VecIO<T>::load(h13 + r * 2 * H + H + c, b);
 #pragma unroll
     for (int j = 0; j < N; ++j) o[j] = a[j] * sigmoidf_(a[j]) * b[j];
-    V16<T>::st(g + r * H + c, o);
+    VecIO<T>::store(g + r * H + c, o);
   }
 }
 template <typename T>
 __global__ void swiglu_bwd_kernel(const T* h13, const T* dg, T* dh13, int64_t rows, int H) {
-  constexpr int N = V16<T>::N;
+  constexpr int N = VecIO<T>::N;
   const int cpr = H / N;
   const int64_t total = rows * cpr;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
     const int64_t r = i / cpr;
     const int c = (int)(i % cpr) * N;
     float a[N], b[N], d[N], oa[N], ob[N];
-    V16<T>::ld(h13 + r * 2 * H + c, a);
-    V16<T>::ld(h13 + r * 2 * H + H + c, b);
-    V16<T>::ld(dg + r * H + c, d);
+    VecIO<T>::load(h13 + r * 2 * H + c, a);
+    VecIO<T>::load(h13 + r * 2 * H + H + c, b);
+    VecIO<T>::load(dg + r * H + c, d);
 #pragma unroll
     for (int j = 0; j < N; ++j) {
       const float sg = sigmoidf_(a[j]);
       oa[j] = d[j] * b[j] * sg * (1.0f + a[j] * (1.0f - sg));
       ob[j] = d[j] * a[j] * sg;
     }
-    V16<T>::st(dh13 + r * 2 * H + c, oa);
-    V16<T>::st(dh13 + r * 2 * H + H + c, ob);
+    VecIO<T>::store(dh13 + r * 2 * H + c, oa);
+    VecIO<T>::store(dh13 + r * 2 * H + H + c, ob);
   }
 }
 template <typename T>
 __global__ void gelu_fwd_kernel(const T* x, T* y, int64_t nvec) {
-  constexpr int N = V16<T>::N;
+  constexpr int N = VecIO<T>::N;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < nvec; i += (int64_t)gridDim.x * blockDim.x) {
     float a[N], o[N];
-    V16<T>::ld(x + i * N, a);
+    VecIO<T>::load(x + i * N, a);
 #pragma unroll
     for (int j = 0; j < N; ++j) o[j] = fk_gelu(a[j]);
-    V16<T>::st(y + i * N, o);
+    VecIO<T>::store(y + i * N, o);
   }
 }
 // y = [res +] keep(i) ? x * 1/(1-p) : 0     (nn.Dropout in training mode; the backward is the same kernel on dy without `res`)
 template <typename T>
 __global__ void dropout_kernel(const T* x, const T* res, T* y, int64_t nvec, const unsigned* seed, unsigned site, unsigned thresh, float ks) {
-  constexpr int N = V16<T>::N;
+  constexpr int N = VecIO<T>::N;
   const DropKey key = drop_key(seed, site, thresh);
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < nvec; i += (int64_t)gridDim.x * blockDim.x) {
     float a[N], o[N];
-    V16<T>::ld(x + i * N, a);
-    if (res) V16<T>::ld(res + i * N, o);
+    VecIO<T>::load(x + i * N, a);
+    if (res) VecIO<T>::load(res + i * N, o);
     const int64_t e0 = i * N;
     const unsigned row = drop_row(key, (unsigned)(e0 >> 32));       // N divides 2^32: the vector never straddles a change of the high word
 #pragma unroll
@@ -157,23 +119,23 @@ __global__ void dropout_kernel(const T* x, const T* res, T* y, int64_t nvec, con
       const float v = drop_keep(key, row, (unsigned)e0 + j) ? a[j] * ks : 0.0f;
       o[j] = res ? o[j] + v : v;
     }
-    V16<T>::st(y + i * N, o);
+    VecIO<T>::store(y + i * N, o);
   }
 }
 template <typename T>
 __global__ void gelu_bwd_kernel(const T* x, const T* dy, T* dx, int64_t nvec) {
-  constexpr int N = V16<T>::N;
+  constexpr int N = VecIO<T>::N;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < nvec; i += (int64_t)gridDim.x * blockDim.x) {
     float a[N], d[N], o[N];
-    V16<T>::ld(x + i * N, a);
-    V16<T>::ld(dy + i * N, d);
+    VecIO<T>::load(x + i * N, a);
+    VecIO<T>::load(dy + i * N, d);
 #pragma unroll
     for (int j = 0; j < N; ++j) {
       const float cdf = 0.5f * (1.0f + erff(a[j] * 0.70710678118654752f));
       const float pdf = 0.3989422804014327f * __expf(-0.5f * a[j] * a[j]);
       o[j] = d[j] * (cdf + a[j] * pdf);
     }
-    V16<T>::st(dx + i * N, o);
+    VecIO<T>::store(dx + i * N, o);
   }
 }
 
@@ -438,8 +400,6 @@ __global__ void attn_combine_kernel(const T* parts, const float* lse, T* out, fl
 
 }  // namespace
 
-#define FK_DT_CHECK(name) FK_CHECK_ARG(dtype == FK_F32 || dtype == FK_BF16, name ": bad dtype %d", dtype)
-
 extern "C" {
 
 int fk_rope(void* x, int64_t B, int64_t T, int64_t ld, int64_t nheads, int64_t D, const float* table, int64_t table_bs,
@@ -452,10 +412,8 @@ int fk_rope(void* x, int64_t B, int64_t T, int64_t ld, int64_t nheads, int64_t D
   const int64_t work = B * T * (nheads * D / vec);
   hipStream_t s = (hipStream_t)stream;
   const float sgn = conj ? -1.0f : 1.0f;
-  if (dtype == FK_BF16)
-    hipLaunchKernelGGL(rope_kernel<bf16_t>, dim3(grid_for(work, 16384)), dim3(TPB), 0, s, (bf16_t*)x, B, T, ld, (int)(nheads * D), (int)D, table, table_bs, pos_off, sgn);
-  else
-    hipLaunchKernelGGL(rope_kernel<float>, dim3(grid_for(work, 16384)), dim3(TPB), 0, s, (float*)x, B, T, ld, (int)(nheads * D), (int)D, table, table_bs, pos_off, sgn);
+  // `E`: this entry point has a parameter named T
+  FK_BY_DTYPE(dtype, E, hipLaunchKernelGGL(rope_kernel<E>, dim3(fk_grid(work, 16384)), dim3(FK_TPB), 0, s, (E*)x, B, T, ld, (int)(nheads * D), (int)D, table, table_bs, pos_off, sgn));
   FK_CHECK_LAUNCH("fk_rope");
   return FK_OK;
 }
@@ -468,8 +426,7 @@ int fk_patchify(const float* x, void* tok, int64_t B, int64_t T, int64_t C, int6
   FK_CHECK_ARG(B * (T / P) < (1LL << 31), "fk_patchify: too many patches");
   dim3 grid((unsigned)(B * (T / P)));
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == FK_BF16) hipLaunchKernelGGL(patchify_kernel<bf16_t>, grid, dim3(TPB), sh, s, x, (bf16_t*)tok, (int)T, (int)C, (int)P, (int)ldp);
-  else hipLaunchKernelGGL(patchify_kernel<float>, grid, dim3(TPB), sh, s, x, (float*)tok, (int)T, (int)C, (int)P, (int)ldp);
+  FK_BY_DTYPE(dtype, E, hipLaunchKernelGGL(patchify_kernel<E>, grid, dim3(FK_TPB), sh, s, x, (E*)tok, (int)T, (int)C, (int)P, (int)ldp));
   FK_CHECK_LAUNCH("fk_patchify");
   return FK_OK;
 }
@@ -480,8 +437,7 @@ int fk_swiglu_fwd(const void* h13, void* g, int64_t rows, int64_t H, int dtype, 
   FK_CHECK_ARG(h13 && g && rows > 0 && H > 0 && H % vec == 0, "fk_swiglu_fwd: H must be a multiple of %d", vec);
   hipStream_t s = (hipStream_t)stream;
   const int64_t work = rows * (H / vec);
-  if (dtype == FK_BF16) hipLaunchKernelGGL(swiglu_fwd_kernel<bf16_t>, dim3(grid_for(work, 16384)), dim3(TPB), 0, s, (const bf16_t*)h13, (bf16_t*)g, rows, (int)H);
-  else hipLaunchKernelGGL(swiglu_fwd_kernel<float>, dim3(grid_for(work, 16384)), dim3(TPB), 0, s, (const float*)h13, (float*)g, rows, (int)H);
+  FK_BY_DTYPE(dtype, T, hipLaunchKernelGGL(swiglu_fwd_kernel<T>, dim3(fk_grid(work, 16384)), dim3(FK_TPB), 0, s, (const T*)h13, (T*)g, rows, (int)H));
   FK_CHECK_LAUNCH("fk_swiglu_fwd");
   return FK_OK;
 }
@@ -491,8 +447,7 @@ int fk_swiglu_bwd(const void* h13, const void* dg, void* dh13, int64_t rows, int
   FK_CHECK_ARG(h13 && dg && dh13 && rows > 0 && H > 0 && H % vec == 0, "fk_swiglu_bwd: H must be a multiple of %d", vec);
   hipStream_t s = (hipStream_t)stream;
   const int64_t work = rows * (H / vec);
-  if (dtype == FK_BF16) hipLaunchKernelGGL(swiglu_bwd_kernel<bf16_t>, dim3(grid_for(work, 16384)), dim3(TPB), 0, s, (const bf16_t*)h13, (const bf16_t*)dg, (bf16_t*)dh13, rows, (int)H);
-  else hipLaunchKernelGGL(swiglu_bwd_kernel<float>, dim3(grid_for(work, 16384)), dim3(TPB), 0, s, (const float*)h13, (const float*)dg, (float*)dh13, rows, (int)H);
+  FK_BY_DTYPE(dtype, T, hipLaunchKernelGGL(swiglu_bwd_kernel<T>, dim3(fk_grid(work, 16384)), dim3(FK_TPB), 0, s, (const T*)h13, (const T*)dg, (T*)dh13, rows, (int)H));
   FK_CHECK_LAUNCH("fk_swiglu_bwd");
   return FK_OK;
 }
@@ -501,8 +456,7 @@ int fk_gelu_fwd(const void* x, void* y, int64_t n, int dtype, void* stream) {
   const int vec = dtype == FK_BF16 ? 8 : 4;
   FK_CHECK_ARG(x && y && n > 0 && n % vec == 0, "fk_gelu_fwd: n must be a multiple of %d", vec);
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == FK_BF16) hipLaunchKernelGGL(gelu_fwd_kernel<bf16_t>, dim3(grid_for(n / vec, 16384)), dim3(TPB), 0, s, (const bf16_t*)x, (bf16_t*)y, n / vec);
-  else hipLaunchKernelGGL(gelu_fwd_kernel<float>, dim3(grid_for(n / vec, 16384)), dim3(TPB), 0, s, (const float*)x, (float*)y, n / vec);
+  FK_BY_DTYPE(dtype, T, hipLaunchKernelGGL(gelu_fwd_kernel<T>, dim3(fk_grid(n / vec, 16384)), dim3(FK_TPB), 0, s, (const T*)x, (T*)y, n / vec));
   FK_CHECK_LAUNCH("fk_gelu_fwd");
   return FK_OK;
 }
@@ -515,8 +469,7 @@ int fk_dropout(const void* x, const void* res, void* y, int64_t n, float p, cons
   const unsigned thresh = t >= 4294967295.0 ? 4294967295u : (t < 1.0 ? 1u : (unsigned)t);
   const float ks = 1.0f / (1.0f - p);
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == FK_BF16) hipLaunchKernelGGL(dropout_kernel<bf16_t>, dim3(grid_for(n / vec, 16384)), dim3(TPB), 0, s, (const bf16_t*)x, (const bf16_t*)res, (bf16_t*)y, n / vec, seed, site, thresh, ks);
-  else hipLaunchKernelGGL(dropout_kernel<float>, dim3(grid_for(n / vec, 16384)), dim3(TPB), 0, s, (const float*)x, (const float*)res, (float*)y, n / vec, seed, site, thresh, ks);
+  FK_BY_DTYPE(dtype, T, hipLaunchKernelGGL(dropout_kernel<T>, dim3(fk_grid(n / vec, 16384)), dim3(FK_TPB), 0, s, (const T*)x, (const T*)res, (T*)y, n / vec, seed, site, thresh, ks));
   FK_CHECK_LAUNCH("fk_dropout");
   return FK_OK;
 }
@@ -525,8 +478,7 @@ int fk_gelu_bwd(const void* x, const void* dy, void* dx, int64_t n, int dtype, v
   const int vec = dtype == FK_BF16 ? 8 : 4;
   FK_CHECK_ARG(x && dy && dx && n > 0 && n % vec == 0, "fk_gelu_bwd: n must be a multiple of %d", vec);
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == FK_BF16) hipLaunchKernelGGL(gelu_bwd_kernel<bf16_t>, dim3(grid_for(n / vec, 16384)), dim3(TPB), 0, s, (const bf16_t*)x, (const bf16_t*)dy, (bf16_t*)dx, n / vec);
-  else hipLaunchKernelGGL(gelu_bwd_kernel<float>, dim3(grid_for(n / vec, 16384)), dim3(TPB), 0, s, (const float*)x, (const float*)dy, (float*)dx, n / vec);
+  FK_BY_DTYPE(dtype, T, hipLaunchKernelGGL(gelu_bwd_kernel<T>, dim3(fk_grid(n / vec, 16384)), dim3(FK_TPB), 0, s, (const T*)x, (const T*)dy, (T*)dx, n / vec));
   FK_CHECK_LAUNCH("fk_gelu_bwd");
   return FK_OK;
 }
@@ -537,8 +489,7 @@ int fk_cast_pack_rows(const float* src, int64_t lds, void* dst, int64_t ldd, int
   FK_CHECK_ARG(src && dst && rows > 0 && cols > 0 && rows < (1LL << 31) && cols < (1LL << 31), "fk_cast_pack: bad shape");
   FK_CHECK_ARG(rblk >= 0 && (rblk == 0 || (rstride >= rblk && roff >= 0)), "fk_cast_pack: bad row map");
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == FK_BF16) hipLaunchKernelGGL(cast_pack_kernel<bf16_t>, dim3(grid_for(rows * cols, 8192)), dim3(TPB), 0, s, src, lds, (bf16_t*)dst, ldd, (int)rows, (int)cols, transpose, (int)rblk, (int)rstride, (int)roff);
-  else hipLaunchKernelGGL(cast_pack_kernel<float>, dim3(grid_for(rows * cols, 8192)), dim3(TPB), 0, s, src, lds, (float*)dst, ldd, (int)rows, (int)cols, transpose, (int)rblk, (int)rstride, (int)roff);
+  FK_BY_DTYPE(dtype, T, hipLaunchKernelGGL(cast_pack_kernel<T>, dim3(fk_grid(rows * cols, 8192)), dim3(FK_TPB), 0, s, src, lds, (T*)dst, ldd, (int)rows, (int)cols, transpose, (int)rblk, (int)rstride, (int)roff));
   FK_CHECK_LAUNCH("fk_cast_pack");
   return FK_OK;
 }
@@ -549,11 +500,10 @@ int fk_cast_pack(const float* src, int64_t lds, void* dst, int64_t ldd, int64_t 
 int fk_cast_pack_multi(const fk_pack_job* jobs, int64_t njobs, int64_t total_chunks, int dtype, void* stream) {
   FK_DT_CHECK("fk_cast_pack_multi");
   FK_CHECK_ARG(jobs && njobs > 0 && njobs < (1LL << 31) && total_chunks > 0, "fk_cast_pack_multi: bad arguments");
-  static_assert(TPB == 256, "a chunk is 4 x 256 elements");
+  static_assert(FK_TPB == 256, "a chunk is 4 x 256 elements");
   hipStream_t s = (hipStream_t)stream;
   const unsigned nb = (unsigned)(total_chunks < 8192 ? total_chunks : 8192);
-  if (dtype == FK_BF16) hipLaunchKernelGGL(cast_pack_multi_kernel<bf16_t>, dim3(nb), dim3(TPB), 0, s, jobs, (int)njobs, total_chunks);
-  else hipLaunchKernelGGL(cast_pack_multi_kernel<float>, dim3(nb), dim3(TPB), 0, s, jobs, (int)njobs, total_chunks);
+  FK_BY_DTYPE(dtype, T, hipLaunchKernelGGL(cast_pack_multi_kernel<T>, dim3(nb), dim3(FK_TPB), 0, s, jobs, (int)njobs, total_chunks));
   FK_CHECK_LAUNCH("fk_cast_pack_multi");
   return FK_OK;
 }
@@ -561,11 +511,7 @@ int fk_cast(const void* src, int src_dtype, void* dst, int dst_dtype, int64_t n,
   FK_CHECK_ARG((src_dtype == FK_F32 || src_dtype == FK_BF16) && (dst_dtype == FK_F32 || dst_dtype == FK_BF16), "fk_cast: bad dtype");
   FK_CHECK_ARG(src && dst && n > 0, "fk_cast: bad arguments");
   hipStream_t s = (hipStream_t)stream;
-  dim3 g(grid_for(n, 16384)), b(TPB);
-  if (src_dtype == FK_F32 && dst_dtype == FK_BF16) hipLaunchKernelGGL((cast_kernel<float, bf16_t>), g, b, 0, s, (const float*)src, (bf16_t*)dst, n);
-  else if (src_dtype == FK_BF16 && dst_dtype == FK_F32) hipLaunchKernelGGL((cast_kernel<bf16_t, float>), g, b, 0, s, (const bf16_t*)src, (float*)dst, n);
-  else if (src_dtype == FK_F32) hipLaunchKernelGGL((cast_kernel<float, float>), g, b, 0, s, (const float*)src, (float*)dst, n);
-  else hipLaunchKernelGGL((cast_kernel<bf16_t, bf16_t>), g, b, 0, s, (const bf16_t*)src, (bf16_t*)dst, n);
+  FK_BY_DTYPE2(src_dtype, TS, dst_dtype, TD, hipLaunchKernelGGL((cast_kernel<TS, TD>), dim3(fk_grid(n, 16384)), dim3(FK_TPB), 0, s, (const TS*)src, (TD*)dst, n));
   FK_CHECK_LAUNCH("fk_cast");
   return FK_OK;
 }
@@ -573,8 +519,7 @@ int fk_add(const void* a, const void* b, void* y, int64_t n, int dtype, void* st
   FK_DT_CHECK("fk_add");
   FK_CHECK_ARG(a && b && y && n > 0, "fk_add: bad arguments");
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == FK_BF16) hipLaunchKernelGGL(add_kernel<bf16_t>, dim3(grid_for(n, 16384)), dim3(TPB), 0, s, (const bf16_t*)a, (const bf16_t*)b, (bf16_t*)y, n);
-  else hipLaunchKernelGGL(add_kernel<float>, dim3(grid_for(n, 16384)), dim3(TPB), 0, s, (const float*)a, (const float*)b, (float*)y, n);
+  FK_BY_DTYPE(dtype, T, hipLaunchKernelGGL(add_kernel<T>, dim3(fk_grid(n, 16384)), dim3(FK_TPB), 0, s, (const T*)a, (const T*)b, (T*)y, n));
   FK_CHECK_LAUNCH("fk_add");
   return FK_OK;
 }
@@ -582,8 +527,7 @@ int fk_copy2d(const void* src, int64_t lds, void* dst, int64_t ldd, int64_t rows
   FK_DT_CHECK("fk_copy2d");
   FK_CHECK_ARG(src && dst && rows > 0 && cols > 0, "fk_copy2d: bad arguments");
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == FK_BF16) hipLaunchKernelGGL(copy2d_kernel<bf16_t>, dim3(grid_for(rows * cols, 16384)), dim3(TPB), 0, s, (const bf16_t*)src, lds, (bf16_t*)dst, ldd, rows, cols);
-  else hipLaunchKernelGGL(copy2d_kernel<float>, dim3(grid_for(rows * cols, 16384)), dim3(TPB), 0, s, (const float*)src, lds, (float*)dst, ldd, rows, cols);
+  FK_BY_DTYPE(dtype, T, hipLaunchKernelGGL(copy2d_kernel<T>, dim3(fk_grid(rows * cols, 16384)), dim3(FK_TPB), 0, s, (const T*)src, lds, (T*)dst, ldd, rows, cols));
   FK_CHECK_LAUNCH("fk_copy2d");
   return FK_OK;
 }
@@ -595,15 +539,14 @@ int fk_attn_combine(const void* parts, const float* lse_parts, void* out, float*
   FK_CHECK_ARG(lse_parts || !lse_out, "fk_attn_combine: lse_out without lse_parts");
   hipStream_t s = (hipStream_t)stream;
   const int64_t work = B * T * H * D;
-  if (dtype == FK_BF16) hipLaunchKernelGGL(attn_combine_kernel<bf16_t>, dim3(grid_for(work, 16384)), dim3(TPB), 0, s, (const bf16_t*)parts, lse_parts, (bf16_t*)out, lse_out, (int)B, (int)S, (int)T, (int)H, (int)D);
-  else hipLaunchKernelGGL(attn_combine_kernel<float>, dim3(grid_for(work, 16384)), dim3(TPB), 0, s, (const float*)parts, lse_parts, (float*)out, lse_out, (int)B, (int)S, (int)T, (int)H, (int)D);
+  FK_BY_DTYPE(dtype, E, hipLaunchKernelGGL(attn_combine_kernel<E>, dim3(fk_grid(work, 16384)), dim3(FK_TPB), 0, s, (const E*)parts, lse_parts, (E*)out, lse_out, (int)B, (int)S, (int)T, (int)H, (int)D));
   FK_CHECK_LAUNCH("fk_attn_combine");
   return FK_OK;
 }
 
 int fk_add2d(const float* src, int64_t lds, float* dst, int64_t ldd, int64_t rows, int64_t cols, void* stream) {
   FK_CHECK_ARG(src && dst && rows > 0 && cols > 0, "fk_add2d: bad arguments");
-  hipLaunchKernelGGL(add2d_kernel, dim3(grid_for(rows * cols, 16384)), dim3(TPB), 0, (hipStream_t)stream, src, lds, dst, ldd, rows, cols);
+  hipLaunchKernelGGL(add2d_kernel, dim3(fk_grid(rows * cols, 16384)), dim3(FK_TPB), 0, (hipStream_t)stream, src, lds, dst, ldd, rows, cols);
   FK_CHECK_LAUNCH("fk_add2d");
   return FK_OK;
 }
@@ -615,8 +558,7 @@ int fk_gpt_embed_fwd(const int64_t* idx, const void* prefix, const float* wte, c
   FK_CHECK_ARG(t_ctx == 0 || prefix, "fk_gpt_embed_fwd: prefix is NULL but t_ctx > 0");
   hipStream_t s = (hipStream_t)stream;
   const int64_t work = B * (t_ctx + t_words) * dim;
-  if (dtype == FK_BF16) hipLaunchKernelGGL(gpt_embed_kernel<bf16_t>, dim3(grid_for(work, 16384)), dim3(TPB), 0, s, idx, (const bf16_t*)prefix, wte, wpe, (bf16_t*)out, (int)B, (int)t_ctx, (int)t_words, (int)dim, (int)vocab);
-  else hipLaunchKernelGGL(gpt_embed_kernel<float>, dim3(grid_for(work, 16384)), dim3(TPB), 0, s, idx, (const float*)prefix, wte, wpe, (float*)out, (int)B, (int)t_ctx, (int)t_words, (int)dim, (int)vocab);
+  FK_BY_DTYPE(dtype, T, hipLaunchKernelGGL(gpt_embed_kernel<T>, dim3(fk_grid(work, 16384)), dim3(FK_TPB), 0, s, idx, (const T*)prefix, wte, wpe, (T*)out, (int)B, (int)t_ctx, (int)t_words, (int)dim, (int)vocab));
   FK_CHECK_LAUNCH("fk_gpt_embed_fwd");
   return FK_OK;
 }
@@ -626,8 +568,7 @@ int fk_gpt_embed_bwd_wte(const int64_t* idx, const void* dout, float* dwte, int6
   FK_CHECK_ARG(idx && dout && dwte && B > 0 && t_words > 0 && dim > 0, "fk_gpt_embed_bwd_wte: bad arguments");
   hipStream_t s = (hipStream_t)stream;
   const int64_t work = B * t_words * dim;
-  if (dtype == FK_BF16) hipLaunchKernelGGL(embed_bwd_kernel<bf16_t>, dim3(grid_for(work, 16384)), dim3(TPB), 0, s, idx, (const bf16_t*)dout, t_ctx + t_words, (int)t_ctx, (int)t_words, dwte, (int)B, (int)dim, (int)vocab);
-  else hipLaunchKernelGGL(embed_bwd_kernel<float>, dim3(grid_for(work, 16384)), dim3(TPB), 0, s, idx, (const float*)dout, t_ctx + t_words, (int)t_ctx, (int)t_words, dwte, (int)B, (int)dim, (int)vocab);
+  FK_BY_DTYPE(dtype, T, hipLaunchKernelGGL(embed_bwd_kernel<T>, dim3(fk_grid(work, 16384)), dim3(FK_TPB), 0, s, idx, (const T*)dout, t_ctx + t_words, (int)t_ctx, (int)t_words, dwte, (int)B, (int)dim, (int)vocab));
   FK_CHECK_LAUNCH("fk_gpt_embed_bwd_wte");
   return FK_OK;
 }
@@ -637,23 +578,17 @@ int fk_gather_rows(const void* src, int64_t src_bs, int src_dtype, const int64_t
   FK_CHECK_ARG((src_dtype == FK_F32 || src_dtype == FK_BF16) && (dst_dtype == FK_F32 || dst_dtype == FK_BF16), "fk_gather_rows: bad dtype");
   FK_CHECK_ARG(src && idx && dst && B > 0 && n > 0 && W > 0 && B * n < (1LL << 31) && W < (1LL << 31), "fk_gather_rows: bad arguments");
   hipStream_t s = (hipStream_t)stream;
-  dim3 g(grid_for(B * n * W, 16384)), b(TPB);
+  dim3 g(fk_grid(B * n * W, 16384)), b(FK_TPB);
   // whole 8-element chunks, rows and batches on 16-byte boundaries on both sides: the vector kernel
   const bool vec = W % 8 == 0 && src_bs % 8 == 0 && dst_bs % 8 == 0 && (((uintptr_t)src | (uintptr_t)dst) & 15) == 0;
   if (vec) {
     const int64_t cpr = W / 8, rpw = cpr >= 64 ? 1 : 64 / cpr, waves = fk_cdiv(B * n, rpw);
-    g = dim3((unsigned)(fk_cdiv(waves, TPB / 64) < 4096 ? fk_cdiv(waves, TPB / 64) : 4096));
+    g = dim3((unsigned)(fk_cdiv(waves, FK_TPB / 64) < 4096 ? fk_cdiv(waves, FK_TPB / 64) : 4096));
   }
-#define FK_GR(TS, TD)                                                                                                                              \
-  do {                                                                                                                                             \
-    if (vec) hipLaunchKernelGGL((gather_rows_vec_kernel<TS, TD>), g, b, 0, s, (const TS*)src, src_bs, idx, idx_mod, (TD*)dst, (int)B, (int)n, (int)W, scatter, dst_bs); \
-    else hipLaunchKernelGGL((gather_rows_kernel<TS, TD>), g, b, 0, s, (const TS*)src, src_bs, idx, idx_mod, (TD*)dst, (int)B, (int)n, (int)W, scatter, dst_bs); \
-  } while (0)
-  if (src_dtype == FK_F32 && dst_dtype == FK_F32) FK_GR(float, float);
-  else if (src_dtype == FK_F32) FK_GR(float, bf16_t);
-  else if (dst_dtype == FK_F32) FK_GR(bf16_t, float);
-  else FK_GR(bf16_t, bf16_t);
-#undef FK_GR
+  FK_BY_DTYPE2(src_dtype, TS, dst_dtype, TD, {
+    const auto kernel = vec ? gather_rows_vec_kernel<TS, TD> : gather_rows_kernel<TS, TD>;      // one signature
+    hipLaunchKernelGGL(kernel, g, b, 0, s, (const TS*)src, src_bs, idx, idx_mod, (TD*)dst, (int)B, (int)n, (int)W, scatter, dst_bs);
+  });
   FK_CHECK_LAUNCH("fk_gather_rows");
   return FK_OK;
 }
@@ -662,15 +597,14 @@ int fk_scatter_add_rows(const void* src, int src_dtype, const int64_t* idx, int6
   FK_CHECK_ARG(src_dtype == FK_F32 || src_dtype == FK_BF16, "fk_scatter_add_rows: bad dtype");
   FK_CHECK_ARG(src && idx && table && rows > 0 && W > 0, "fk_scatter_add_rows: bad arguments");
   hipStream_t s = (hipStream_t)stream;
-  if (src_dtype == FK_BF16) hipLaunchKernelGGL(scatter_add_rows_kernel<bf16_t>, dim3(grid_for(rows * W, 16384)), dim3(TPB), 0, s, (const bf16_t*)src, idx, idx_mod, table, rows, (int)W);
-  else hipLaunchKernelGGL(scatter_add_rows_kernel<float>, dim3(grid_for(rows * W, 16384)), dim3(TPB), 0, s, (const float*)src, idx, idx_mod, table, rows, (int)W);
+  FK_BY_DTYPE(src_dtype, TS, hipLaunchKernelGGL(scatter_add_rows_kernel<TS>, dim3(fk_grid(rows * W, 16384)), dim3(FK_TPB), 0, s, (const TS*)src, idx, idx_mod, table, rows, (int)W));
   FK_CHECK_LAUNCH("fk_scatter_add_rows");
   return FK_OK;
 }
 int fk_prefix_mask(const int64_t* q_ids, const int64_t* k_ids, int64_t block, int32_t* limits, int32_t* qfirst, int64_t B,
                    int64_t nq, int64_t nk, void* stream) {
   FK_CHECK_ARG(q_ids && k_ids && limits && qfirst && block > 0 && B > 0 && nq > 0 && nk > 0, "fk_prefix_mask: bad arguments");
-  hipLaunchKernelGGL(prefix_mask_kernel, dim3(grid_for(B * (nq + nk), 4096)), dim3(TPB), 0, (hipStream_t)stream, q_ids, k_ids, (int)block,
+  hipLaunchKernelGGL(prefix_mask_kernel, dim3(fk_grid(B * (nq + nk), 4096)), dim3(FK_TPB), 0, (hipStream_t)stream, q_ids, k_ids, (int)block,
                      limits, qfirst, (int)B, (int)nq, (int)nk);
   FK_CHECK_LAUNCH("fk_prefix_mask");
   return FK_OK;

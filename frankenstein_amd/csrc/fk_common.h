@@ -45,7 +45,27 @@ int fk_set_error(int code, const char* fmt, ...);
     if (e__ != hipSuccess) return fk_set_error(FK_ELAUNCH, "%s: %s", name, hipGetErrorString(e__)); \
   } while (0)
 
+#define FK_DT_CHECK(name) FK_CHECK_ARG(dtype == FK_F32 || dtype == FK_BF16, name ": bad dtype %d", dtype)
+
 static inline int64_t fk_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// the pointwise kernels: FK_TPB threads per block, grid-stride loops over `work` items on at most `cap` blocks
+constexpr int FK_TPB = 256;
+static inline unsigned fk_grid(int64_t work, int64_t cap) {
+  int64_t b = fk_cdiv(work, FK_TPB);
+  if (b > cap) b = cap;
+  if (b < 1) b = 1;
+  return (unsigned)b;
+}
+
+// Host dtype dispatch: the statement(s) are compiled once with `T` = bf16_t and once with `T` = float and the arm of `dtype` (checked by
+// the caller: FK_BF16 or FK_F32) runs, so a dtype-templated launch and its (const T*) casts are written once.  Nests for two dtypes.
+#define FK_BY_DTYPE(dtype, T, ...)                                \
+  do {                                                            \
+    if ((dtype) == FK_BF16) { using T = bf16_t; __VA_ARGS__; }    \
+    else { using T = float; __VA_ARGS__; }                        \
+  } while (0)
+#define FK_BY_DTYPE2(dtype_a, TA, dtype_b, TB, ...) FK_BY_DTYPE(dtype_a, TA, FK_BY_DTYPE(dtype_b, TB, __VA_ARGS__))
 
 // Launch of a kernel that takes one argument struct and more dynamic LDS than the 64 KiB every kernel may have: the kernel's limit is
 // raised on the first launch of each instantiation (once per process and kernel), then it is launched.
@@ -65,11 +85,6 @@ template <> FK_DEV float to_f32<bf16_t>(bf16_t v) { return (float)v; }
 template <typename T> FK_DEV T from_f32(float v);
 template <> FK_DEV float from_f32<float>(float v) { return v; }
 template <> FK_DEV bf16_t from_f32<bf16_t>(float v) { return (bf16_t)v; }  // RNE, NaN preserving (v_cvt_pk_bf16_f32)
-
-// 16-byte vector of T (8 bf16 or 4 fp32)
-template <typename T> struct Vec16;
-template <> struct Vec16<bf16_t> { static constexpr int N = 8; };
-template <> struct Vec16<float> { static constexpr int N = 4; };
 
 // ------------------------------------------------------------------------------------------------
 // MFMA fragment (8 k-slots per lane)
@@ -180,6 +195,37 @@ template <bool NT, typename V> FK_DEV void fk_st(V* q, const V& v) {
   if constexpr (NT) __builtin_nontemporal_store(v, q);
   else *q = v;
 }
+
+// 16-byte vector of T (N = 8 bf16 or 4 fp32) to and from fp32 registers.  NT: the bf16 store is non-temporal; the fp32 store stays plain.
+template <typename T, bool NT = false> struct VecIO;
+template <bool NT> struct VecIO<bf16_t, NT> {
+  static constexpr int N = 8;
+  FK_DEV static void load(const bf16_t* p, float (&v)[8]) {
+    bf16x8 a = *reinterpret_cast<const bf16x8*>(p);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) v[i] = (float)a[i];
+  }
+  FK_DEV static void store(bf16_t* p, const float (&v)[8]) {
+    bf16x8 a;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) a[i] = (bf16_t)v[i];
+    fk_st<NT>(reinterpret_cast<bf16x8*>(p), a);
+  }
+};
+template <bool NT> struct VecIO<float, NT> {
+  static constexpr int N = 4;
+  FK_DEV static void load(const float* p, float (&v)[4]) {
+    f32x4 a = *reinterpret_cast<const f32x4*>(p);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) v[i] = a[i];
+  }
+  FK_DEV static void store(float* p, const float (&v)[4]) {
+    f32x4 a;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) a[i] = v[i];
+    *reinterpret_cast<f32x4*>(p) = a;
+  }
+};
 
 // XCD-aware block remap (bijective for any grid size): blocks b and b+8 share an XCD (round-robin
 // dispatch), so give each XCD a contiguous chunk of logical tile ids -> neighbouring tiles share L2.

@@ -39,18 +39,6 @@ struct GemvArgs {
   int gelu, out_f32;
 };
 
-template <typename T> FK_DEV void gv_load16(const T* p, float (&v)[Vec16<T>::N]);
-template <> FK_DEV void gv_load16<bf16_t>(const bf16_t* p, float (&v)[8]) {
-  const bf16x8 r = *reinterpret_cast<const bf16x8*>(p);
-#pragma unroll
-  for (int e = 0; e < 8; ++e) v[e] = (float)r[e];
-}
-template <> FK_DEV void gv_load16<float>(const float* p, float (&v)[4]) {
-  const f32x4 r = *reinterpret_cast<const f32x4*>(p);
-#pragma unroll
-  for (int e = 0; e < 4; ++e) v[e] = r[e];
-}
-
 // element e of a 16-byte weight piece held as four dwords
 template <typename T> FK_DEV float gv_welem(const u32x4& w, int e);
 template <> FK_DEV float gv_welem<bf16_t>(const u32x4& w, int e) {
@@ -91,7 +79,7 @@ template <int NV> FK_DEV int gv_owned(int lane) { return gv_owned_step<NV, 32>(l
 
 template <typename T, int MB, int CW>
 __global__ __launch_bounds__(GV_WAVES * 64) void gemv_nt_kernel(const GemvArgs a) {
-  constexpr int E = Vec16<T>::N;            // elements per 16-byte piece
+  constexpr int E = VecIO<T>::N;            // elements per 16-byte piece
   constexpr int F = gv_chunk(MB);           // fp32 elements of a row in LDS
   constexpr int FP = F / E;                 // = pieces of a chunk
   constexpr int PLANE = F / (E / 4);        // bf16: elements 0-3 of every piece in plane 0, 4-7 in plane 1
@@ -146,13 +134,13 @@ __global__ __launch_bounds__(GV_WAVES * 64) void gemv_nt_kernel(const GemvArgs a
         const T* xr = A + (int64_t)m * a.lda;
         float v[E], s = 0.0f, q = 0.0f;
         for (int p = lane; p < np; p += 64) {
-          gv_load16<T>(xr + p * E, v);
+          VecIO<T>::load(xr + p * E, v);
 #pragma unroll
           for (int e = 0; e < E; ++e) s += v[e];
         }
         const float mean = wave_sum(s) / K;
         for (int p = lane; p < np; p += 64) {
-          gv_load16<T>(xr + p * E, v);
+          VecIO<T>::load(xr + p * E, v);
 #pragma unroll
           for (int e = 0; e < E; ++e) q = __builtin_fmaf(v[e] - mean, v[e] - mean, q);
         }
@@ -318,7 +306,7 @@ template <typename T> void gv_launch(const GemvArgs& a, hipStream_t s) {
 extern "C" int fk_gemv_nt(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc, int64_t M, int64_t N, int64_t K,
                           const void* bias, const void* residual, int64_t ldr, const float* ln_gamma, const float* ln_beta, float ln_eps,
                           int flags, int dtype, int out_dtype, void* stream) {
-  FK_CHECK_ARG(dtype == FK_F32 || dtype == FK_BF16, "fk_gemv_nt: bad dtype %d", dtype);
+  FK_DT_CHECK("fk_gemv_nt");
   FK_CHECK_ARG(out_dtype == dtype || out_dtype == FK_F32, "fk_gemv_nt: out_dtype must be dtype or FK_F32");
   FK_CHECK_ARG(M >= 1 && M <= 16, "fk_gemv_nt: M = %lld outside 1..16 (larger products belong to fk_gemm_nt)", (long long)M);
   const int64_t esz = dtype == FK_BF16 ? 2 : 4, vec = 16 / esz, lim = INT32_MAX;
@@ -333,8 +321,7 @@ extern "C" int fk_gemv_nt(const void* A, int64_t lda, const void* W, int64_t ldw
   FK_CHECK_ARG(ln_gamma || !ln_beta, "fk_gemv_nt: ln_beta without ln_gamma");
   GemvArgs a{A, W, C, bias, residual, ln_gamma, ln_beta, lda, ldw, ldc, ldr, (int)M, (int)N, (int)K, ln_eps,
              (flags & FK_GEMV_GELU) ? 1 : 0, (out_dtype == FK_F32 && dtype != FK_F32) ? 1 : 0};
-  if (dtype == FK_BF16) gv_launch<bf16_t>(a, (hipStream_t)stream);
-  else gv_launch<float>(a, (hipStream_t)stream);
+  FK_BY_DTYPE(dtype, T, gv_launch<T>(a, (hipStream_t)stream));
   FK_CHECK_LAUNCH("fk_gemv_nt");
   return FK_OK;
 }

@@ -222,7 +222,7 @@ size_t fk_head_ce_workspace_bytes(int64_t rows, int64_t V) { return (size_t)rows
 int fk_head_ce_fwd(const void* H, int64_t ldh, const void* W, int64_t ldw, int64_t wrows, const void* bias, const int64_t* targets,
                    float* row_m, float* row_s, float* row_t, int64_t rows, int64_t V, int64_t K, int dtype, void* workspace,
                    size_t workspace_bytes, void* stream) {
-  FK_CHECK_ARG(dtype == FK_F32 || dtype == FK_BF16, "fk_head_ce_fwd: bad dtype %d", dtype);
+  FK_DT_CHECK("fk_head_ce_fwd");
   const int vec = dtype == FK_BF16 ? 8 : 4;
   FK_CHECK_ARG(H && W && targets && row_m && row_s && row_t && rows > 0 && V > 0 && K > 0 && wrows >= V, "fk_head_ce_fwd: bad arguments");
   FK_CHECK_ARG(rows < (1LL << 24) && V < (1LL << 30) && K < (1LL << 30) && fk_cdiv(rows, BM) * fk_cdiv(V, BN) < (1LL << 31), "fk_head_ce_fwd: problem too large");
@@ -237,8 +237,7 @@ int fk_head_ce_fwd(const void* H, int64_t ldh, const void* W, int64_t ldw, int64
   p.pmax = (float*)workspace; p.psum = p.pmax + rows * (int64_t)p.npart; p.tlogit = row_t;
   if (hipMemsetAsync(row_t, 0, (size_t)rows * sizeof(float), s) != hipSuccess) return fk_set_error(FK_ELAUNCH, "fk_head_ce_fwd: memset failed");
   const dim3 grid((unsigned)(fk_cdiv(rows, BM) * fk_cdiv(V, BN))), block(NTHREADS);
-  if (dtype == FK_BF16) hipLaunchKernelGGL((head_ce_kernel<bf16_t, 0>), grid, block, 4 * TILE_BYTES, s, p);
-  else hipLaunchKernelGGL((head_ce_kernel<float, 0>), grid, block, 4 * TILE_BYTES, s, p);
+  FK_BY_DTYPE(dtype, T, hipLaunchKernelGGL((head_ce_kernel<T, 0>), grid, block, 4 * TILE_BYTES, s, p));
   FK_CHECK_LAUNCH("fk_head_ce_fwd");
   hipLaunchKernelGGL(head_ce_merge_kernel, dim3((unsigned)rows), dim3(64), 0, s, (const float*)p.pmax, (const float*)p.psum, row_m, row_s, (int)rows, p.npart);
   FK_CHECK_LAUNCH("fk_head_ce_fwd(merge)");
@@ -248,7 +247,7 @@ int fk_head_ce_fwd(const void* H, int64_t ldh, const void* W, int64_t ldw, int64
 int fk_head_ce_bwd(const void* H, int64_t ldh, const void* W, int64_t ldw, int64_t wrows, const void* bias, const int64_t* targets,
                    const float* row_lse, const float* loss2, const float* grad_out, void* dlT, int64_t lddl, int64_t rows_pad,
                    int64_t vpad, float* dbpart, int64_t rows, int64_t V, int64_t K, int64_t ignore_index, int dtype, void* stream) {
-  FK_CHECK_ARG(dtype == FK_F32 || dtype == FK_BF16, "fk_head_ce_bwd: bad dtype %d", dtype);
+  FK_DT_CHECK("fk_head_ce_bwd");
   const int vec = dtype == FK_BF16 ? 8 : 4;
   FK_CHECK_ARG(H && W && targets && row_lse && loss2 && grad_out && dlT && rows > 0 && V > 0 && K > 0 && wrows >= V, "fk_head_ce_bwd: bad arguments");
   FK_CHECK_ARG(rows < (1LL << 24) && V < (1LL << 30) && K < (1LL << 30) && fk_cdiv(rows, BM) * fk_cdiv(V, BN) < (1LL << 31), "fk_head_ce_bwd: problem too large");
@@ -262,8 +261,7 @@ int fk_head_ce_bwd(const void* H, int64_t ldh, const void* W, int64_t ldw, int64
   p.rows = (int)rows; p.V = (int)V; p.wrows = (int)wrows; p.K = (int)K;
   p.lse = row_lse; p.loss2 = loss2; p.gout = grad_out; p.dlT = dlT; p.lddl = lddl; p.rows_pad = (int)rows_pad; p.vpad = (int)vpad; p.dbpart = dbpart;
   const dim3 grid((unsigned)(fk_cdiv(rows, BM) * fk_cdiv(V, BN))), block(NTHREADS);
-  if (dtype == FK_BF16) hipLaunchKernelGGL((head_ce_kernel<bf16_t, 1>), grid, block, 4 * TILE_BYTES, s, p);
-  else hipLaunchKernelGGL((head_ce_kernel<float, 1>), grid, block, 4 * TILE_BYTES, s, p);
+  FK_BY_DTYPE(dtype, T, hipLaunchKernelGGL((head_ce_kernel<T, 1>), grid, block, 4 * TILE_BYTES, s, p));
   FK_CHECK_LAUNCH("fk_head_ce_bwd");
   return FK_OK;
 }
@@ -273,8 +271,7 @@ int fk_transpose2d(const void* src, int64_t lds, void* dst, int64_t ldd, int64_t
                cols < (1LL << 31) && fk_cdiv(rows, 32) < 65536, "fk_transpose2d: bad arguments");
   const dim3 grid((unsigned)fk_cdiv(cols, 32), (unsigned)fk_cdiv(rows, 32)), block(256);
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == FK_BF16) hipLaunchKernelGGL(transpose2d_kernel<bf16_t>, grid, block, 0, s, (const bf16_t*)src, lds, (bf16_t*)dst, ldd, (int)rows, (int)cols);
-  else hipLaunchKernelGGL(transpose2d_kernel<float>, grid, block, 0, s, (const float*)src, lds, (float*)dst, ldd, (int)rows, (int)cols);
+  FK_BY_DTYPE(dtype, T, hipLaunchKernelGGL(transpose2d_kernel<T>, grid, block, 0, s, (const T*)src, lds, (T*)dst, ldd, (int)rows, (int)cols));
   FK_CHECK_LAUNCH("fk_transpose2d");
   return FK_OK;
 }

@@ -21,8 +21,6 @@ int fk_set_error(int code, const char* fmt, ...) {
 
 namespace {
 
-constexpr int TPB = 256;
-
 FK_DEV float block_sum(float v, float* sh) {   // sh: >= 4 floats; result valid in all threads
   v = wave_sum(v);
   __syncthreads();
@@ -329,13 +327,6 @@ __global__ void adamw_groups_kernel(float* p, float* g, float* m, float* v, int6
   }
 }
 
-inline unsigned grid_for(int64_t work, int64_t cap) {
-  int64_t b = fk_cdiv(work, TPB);
-  if (b > cap) b = cap;
-  if (b < 1) b = 1;
-  return (unsigned)b;
-}
-
 }  // namespace
 
 extern "C" {
@@ -343,29 +334,27 @@ extern "C" {
 int fk_version(void) { return FK_VERSION; }
 const char* fk_last_error(void) { return g_err; }
 
-size_t fk_loss_workspace_bytes(int64_t n) { return (size_t)grid_for(n, 1024) * 2 * sizeof(float); }
+size_t fk_loss_workspace_bytes(int64_t n) { return (size_t)fk_grid(n, 1024) * 2 * sizeof(float); }
 
 int fk_l1_loss_fwd(const void* pred, const void* target, float* loss2, int64_t n, int squared, const float* row_weight,
                    int64_t row_len, int dtype, void* workspace, size_t workspace_bytes, void* stream) {
-  FK_CHECK_ARG(dtype == FK_F32 || dtype == FK_BF16, "fk_l1_loss_fwd: bad dtype %d", dtype);
+  FK_DT_CHECK("fk_l1_loss_fwd");
   FK_CHECK_ARG(pred && target && loss2 && n > 0 && (!row_weight || (row_len > 0 && n % row_len == 0)), "fk_l1_loss_fwd: bad arguments");
-  const unsigned nb = grid_for(n, 1024);
+  const unsigned nb = fk_grid(n, 1024);
   FK_CHECK_ARG(workspace && workspace_bytes >= (size_t)nb * 2 * sizeof(float), "fk_l1_loss_fwd: workspace too small");
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == FK_BF16) hipLaunchKernelGGL(l1_partial_kernel<bf16_t>, dim3(nb), dim3(TPB), 0, s, (const bf16_t*)pred, (const bf16_t*)target, (float*)workspace, n, squared, row_weight, row_len);
-  else hipLaunchKernelGGL(l1_partial_kernel<float>, dim3(nb), dim3(TPB), 0, s, (const float*)pred, (const float*)target, (float*)workspace, n, squared, row_weight, row_len);
+  FK_BY_DTYPE(dtype, T, hipLaunchKernelGGL(l1_partial_kernel<T>, dim3(nb), dim3(FK_TPB), 0, s, (const T*)pred, (const T*)target, (float*)workspace, n, squared, row_weight, row_len));
   FK_CHECK_LAUNCH("fk_l1_loss_fwd");
-  hipLaunchKernelGGL(l1_final_kernel, dim3(1), dim3(TPB), 0, s, (const float*)workspace, (int)nb, loss2);
+  hipLaunchKernelGGL(l1_final_kernel, dim3(1), dim3(FK_TPB), 0, s, (const float*)workspace, (int)nb, loss2);
   FK_CHECK_LAUNCH("fk_l1_loss_fwd(final)");
   return FK_OK;
 }
 int fk_l1_loss_bwd(const void* pred, const void* target, const float* grad_out, void* dpred, int64_t n, int squared,
                    const float* row_weight, int64_t row_len, const float* loss2, int dtype, void* stream) {
-  FK_CHECK_ARG(dtype == FK_F32 || dtype == FK_BF16, "fk_l1_loss_bwd: bad dtype %d", dtype);
+  FK_DT_CHECK("fk_l1_loss_bwd");
   FK_CHECK_ARG(pred && target && grad_out && dpred && n > 0 && (!row_weight || (row_len > 0 && loss2)), "fk_l1_loss_bwd: bad arguments");
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == FK_BF16) hipLaunchKernelGGL(l1_bwd_kernel<bf16_t>, dim3(grid_for(n, 4096)), dim3(TPB), 0, s, (const bf16_t*)pred, (const bf16_t*)target, grad_out, (bf16_t*)dpred, n, squared, row_weight, row_len, loss2);
-  else hipLaunchKernelGGL(l1_bwd_kernel<float>, dim3(grid_for(n, 4096)), dim3(TPB), 0, s, (const float*)pred, (const float*)target, grad_out, (float*)dpred, n, squared, row_weight, row_len, loss2);
+  FK_BY_DTYPE(dtype, T, hipLaunchKernelGGL(l1_bwd_kernel<T>, dim3(fk_grid(n, 4096)), dim3(FK_TPB), 0, s, (const T*)pred, (const T*)target, grad_out, (T*)dpred, n, squared, row_weight, row_len, loss2));
   FK_CHECK_LAUNCH("fk_l1_loss_bwd");
   return FK_OK;
 }
@@ -374,27 +363,25 @@ size_t fk_ce_workspace_bytes(int64_t rows) { return (size_t)rows * 2 * sizeof(fl
 
 int fk_ce_loss_fwd(const void* logits, int64_t ld, const int64_t* targets, float* loss2, float* row_lse, int64_t rows,
                    int64_t V, int64_t ignore_index, int dtype, void* workspace, size_t workspace_bytes, void* stream) {
-  FK_CHECK_ARG(dtype == FK_F32 || dtype == FK_BF16, "fk_ce_loss_fwd: bad dtype %d", dtype);
+  FK_DT_CHECK("fk_ce_loss_fwd");
   FK_CHECK_ARG(logits && targets && loss2 && row_lse && rows > 0 && V > 0 && rows < (1LL << 31) && V < (1LL << 31), "fk_ce_loss_fwd: bad arguments");
   FK_CHECK_ARG(workspace && workspace_bytes >= (size_t)rows * 2 * sizeof(float), "fk_ce_loss_fwd: workspace too small");
   float* nll = (float*)workspace;
   float* valid = nll + rows;
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == FK_BF16) hipLaunchKernelGGL(ce_row_kernel<bf16_t>, dim3((unsigned)rows), dim3(TPB), 0, s, (const bf16_t*)logits, ld, targets, row_lse, nll, valid, (int)V, ignore_index);
-  else hipLaunchKernelGGL(ce_row_kernel<float>, dim3((unsigned)rows), dim3(TPB), 0, s, (const float*)logits, ld, targets, row_lse, nll, valid, (int)V, ignore_index);
+  FK_BY_DTYPE(dtype, T, hipLaunchKernelGGL(ce_row_kernel<T>, dim3((unsigned)rows), dim3(FK_TPB), 0, s, (const T*)logits, ld, targets, row_lse, nll, valid, (int)V, ignore_index));
   FK_CHECK_LAUNCH("fk_ce_loss_fwd(rows)");
-  hipLaunchKernelGGL(ce_final_kernel, dim3(1), dim3(TPB), 0, s, (const float*)nll, (const float*)valid, loss2, (int)rows);
+  hipLaunchKernelGGL(ce_final_kernel, dim3(1), dim3(FK_TPB), 0, s, (const float*)nll, (const float*)valid, loss2, (int)rows);
   FK_CHECK_LAUNCH("fk_ce_loss_fwd(final)");
   return FK_OK;
 }
 int fk_ce_loss_bwd(const void* logits, int64_t ld, const int64_t* targets, const float* row_lse, const float* loss2,
                    const float* grad_out, void* dlogits, int64_t ldd, int64_t rows, int64_t V, int64_t ignore_index,
                    int dtype, void* stream) {
-  FK_CHECK_ARG(dtype == FK_F32 || dtype == FK_BF16, "fk_ce_loss_bwd: bad dtype %d", dtype);
+  FK_DT_CHECK("fk_ce_loss_bwd");
   FK_CHECK_ARG(logits && targets && row_lse && loss2 && grad_out && dlogits && rows > 0 && V > 0, "fk_ce_loss_bwd: bad arguments");
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == FK_BF16) hipLaunchKernelGGL(ce_bwd_kernel<bf16_t>, dim3(grid_for(rows * V, 16384)), dim3(TPB), 0, s, (const bf16_t*)logits, ld, targets, row_lse, loss2, grad_out, (bf16_t*)dlogits, ldd, rows, (int)V, ignore_index);
-  else hipLaunchKernelGGL(ce_bwd_kernel<float>, dim3(grid_for(rows * V, 16384)), dim3(TPB), 0, s, (const float*)logits, ld, targets, row_lse, loss2, grad_out, (float*)dlogits, ldd, rows, (int)V, ignore_index);
+  FK_BY_DTYPE(dtype, T, hipLaunchKernelGGL(ce_bwd_kernel<T>, dim3(fk_grid(rows * V, 16384)), dim3(FK_TPB), 0, s, (const T*)logits, ld, targets, row_lse, loss2, grad_out, (T*)dlogits, ldd, rows, (int)V, ignore_index));
   FK_CHECK_LAUNCH("fk_ce_loss_bwd");
   return FK_OK;
 }
@@ -403,7 +390,7 @@ int fk_ce_chunk_fwd(const float* logits, int64_t ld, const int64_t* targets, int
                     int64_t rows, int64_t cw, int first, void* stream) {
   FK_CHECK_ARG(logits && targets && row_m && row_s && row_t && rows > 0 && rows < (1LL << 31) && cw > 0 && cw < (1LL << 31) && ld >= cw && col0 >= 0,
                "fk_ce_chunk_fwd: bad arguments");
-  hipLaunchKernelGGL(ce_chunk_fwd_kernel, dim3((unsigned)rows), dim3(TPB), 0, (hipStream_t)stream, logits, ld, targets, col0, row_m, row_s, row_t, (int)cw, first);
+  hipLaunchKernelGGL(ce_chunk_fwd_kernel, dim3((unsigned)rows), dim3(FK_TPB), 0, (hipStream_t)stream, logits, ld, targets, col0, row_m, row_s, row_t, (int)cw, first);
   FK_CHECK_LAUNCH("fk_ce_chunk_fwd");
   return FK_OK;
 }
@@ -414,21 +401,20 @@ int fk_ce_chunk_finish(const float* row_m, const float* row_s, const float* row_
   float* nll = (float*)workspace;
   float* valid = nll + rows;
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(ce_chunk_rows_kernel, dim3(grid_for(rows, 1024)), dim3(TPB), 0, s, row_m, row_s, row_t, targets, row_lse, nll, valid, rows, V, ignore_index);
+  hipLaunchKernelGGL(ce_chunk_rows_kernel, dim3(fk_grid(rows, 1024)), dim3(FK_TPB), 0, s, row_m, row_s, row_t, targets, row_lse, nll, valid, rows, V, ignore_index);
   FK_CHECK_LAUNCH("fk_ce_chunk_finish(rows)");
-  hipLaunchKernelGGL(ce_final_kernel, dim3(1), dim3(TPB), 0, s, (const float*)nll, (const float*)valid, loss2, (int)rows);
+  hipLaunchKernelGGL(ce_final_kernel, dim3(1), dim3(FK_TPB), 0, s, (const float*)nll, (const float*)valid, loss2, (int)rows);
   FK_CHECK_LAUNCH("fk_ce_chunk_finish(final)");
   return FK_OK;
 }
 int fk_ce_chunk_bwd(const float* logits, int64_t ld, const int64_t* targets, int64_t col0, const float* row_lse, const float* loss2,
                     const float* grad_out, void* dlogits, int64_t ldd, int64_t rows, int64_t cw, int64_t cw_valid, int64_t V,
                     int64_t ignore_index, int dtype, void* stream) {
-  FK_CHECK_ARG(dtype == FK_F32 || dtype == FK_BF16, "fk_ce_chunk_bwd: bad dtype %d", dtype);
+  FK_DT_CHECK("fk_ce_chunk_bwd");
   FK_CHECK_ARG(logits && targets && row_lse && loss2 && grad_out && dlogits && rows > 0 && cw > 0 && cw_valid >= 0 && cw_valid <= cw && ld >= cw_valid && ldd >= cw,
                "fk_ce_chunk_bwd: bad arguments");
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == FK_BF16) hipLaunchKernelGGL(ce_chunk_bwd_kernel<bf16_t>, dim3(grid_for(rows * cw, 16384)), dim3(TPB), 0, s, logits, ld, targets, col0, row_lse, loss2, grad_out, (bf16_t*)dlogits, ldd, rows, (int)cw, (int)cw_valid, V, ignore_index);
-  else hipLaunchKernelGGL(ce_chunk_bwd_kernel<float>, dim3(grid_for(rows * cw, 16384)), dim3(TPB), 0, s, logits, ld, targets, col0, row_lse, loss2, grad_out, (float*)dlogits, ldd, rows, (int)cw, (int)cw_valid, V, ignore_index);
+  FK_BY_DTYPE(dtype, T, hipLaunchKernelGGL(ce_chunk_bwd_kernel<T>, dim3(fk_grid(rows * cw, 16384)), dim3(FK_TPB), 0, s, logits, ld, targets, col0, row_lse, loss2, grad_out, (T*)dlogits, ldd, rows, (int)cw, (int)cw_valid, V, ignore_index));
   FK_CHECK_LAUNCH("fk_ce_chunk_bwd");
   return FK_OK;
 }
@@ -438,7 +424,7 @@ int fk_adamw_step(float* p, float* g, float* m, float* v, int64_t n, double lr, 
   FK_CHECK_ARG(p && g && m && v && n > 0 && step >= 1, "fk_adamw_step: bad arguments");
   FK_CHECK_ARG((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0, "fk_adamw_step: buffers must be 16-byte aligned");
   const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
-  hipLaunchKernelGGL(adamw_kernel, dim3(grid_for(n / 4 + 1, 4096)), dim3(TPB), 0, (hipStream_t)stream, p, g, m, v, n, (float)lr, (float)(1.0 - beta1),
+  hipLaunchKernelGGL(adamw_kernel, dim3(fk_grid(n / 4 + 1, 4096)), dim3(FK_TPB), 0, (hipStream_t)stream, p, g, m, v, n, (float)lr, (float)(1.0 - beta1),
                      (float)beta2, (float)(1.0 - beta2), (float)eps, (float)weight_decay, (float)bc1, (float)sqrt(bc2), (float)clip, (float)grad_scale, zero_grad);
   FK_CHECK_LAUNCH("fk_adamw_step");
   return FK_OK;
@@ -474,7 +460,7 @@ int fk_adamw_step_groups(float* p, float* g, float* m, float* v, int64_t n, cons
     slots.s[i] = AdamwSlot{(float)q.lr, (float)(1.0 - q.beta1), (float)q.beta2, (float)(1.0 - q.beta2), (float)q.eps, (float)q.weight_decay,
                            (float)bc1, (float)sqrt(bc2)};
   }
-  hipLaunchKernelGGL(adamw_groups_kernel, dim3(grid_for(n / 4 + 1, 4096)), dim3(TPB), 0, (hipStream_t)stream, p, g, m, v, n, segs, (int)nseg,
+  hipLaunchKernelGGL(adamw_groups_kernel, dim3(fk_grid(n / 4 + 1, 4096)), dim3(FK_TPB), 0, (hipStream_t)stream, p, g, m, v, n, segs, (int)nseg,
                      (int)fk_cdiv(nseg, SEG_TILE), slots, nslots, (float)clip, (float)grad_scale, zero_grad, (float)max_norm, partials,
                      npartials, norm_out);
   FK_CHECK_LAUNCH("fk_adamw_step_groups");

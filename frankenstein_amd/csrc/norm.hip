@@ -6,6 +6,8 @@
 // wave-shuffle reductions, fp32 statistics saved for the backward.  The backward fuses the
 // residual-branch gradient add (dx = dres + norm_bwd(dy)).  dgamma/dbeta are column reductions
 // through a [chunks, 2, dim] fp32 workspace (deterministic).
+#include <type_traits>
+
 #include "fk_common.h"
 
 namespace {
@@ -13,40 +15,12 @@ namespace {
 #ifndef FK_NT_STORES_NORM
 #define FK_NT_STORES_NORM 0
 #endif
-template <typename T> struct VecIO;
-template <> struct VecIO<bf16_t> {
-  static constexpr int N = 8;
-  FK_DEV static void load(const bf16_t* p, float (&v)[8]) {
-    bf16x8 a = *reinterpret_cast<const bf16x8*>(p);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) v[i] = (float)a[i];
-  }
-  FK_DEV static void store(bf16_t* p, const float (&v)[8]) {
-    bf16x8 a;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) a[i] = (bf16_t)v[i];
-    fk_st<FK_NT_STORES_NORM != 0>(reinterpret_cast<bf16x8*>(p), a);
-  }
-};
-template <> struct VecIO<float> {
-  static constexpr int N = 4;
-  FK_DEV static void load(const float* p, float (&v)[4]) {
-    f32x4 a = *reinterpret_cast<const f32x4*>(p);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) v[i] = a[i];
-  }
-  FK_DEV static void store(float* p, const float (&v)[4]) {
-    f32x4 a;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) a[i] = v[i];
-    *reinterpret_cast<f32x4*>(p) = a;
-  }
-};
+template <typename T> using VIO = VecIO<T, FK_NT_STORES_NORM != 0>;
 
 template <typename T>
 __global__ __launch_bounds__(256) void norm_fwd_kernel(const T* x, const float* gamma, const float* beta, T* y,
                                                         float* mean, float* rstd, int64_t rows, int dim, float eps, int kind) {
-  constexpr int N = VecIO<T>::N;
+  constexpr int N = VIO<T>::N;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t wstride = (int64_t)gridDim.x * 4;
   for (int64_t row = (int64_t)blockIdx.x * 4 + wave; row < rows; row += wstride) {
@@ -55,7 +29,7 @@ __global__ __launch_bounds__(256) void norm_fwd_kernel(const T* x, const float* 
     float v[N];
     if (kind == FK_NORM_LAYER) {
       for (int c = lane * N; c < dim; c += 64 * N) {
-        VecIO<T>::load(xr + c, v);
+        VIO<T>::load(xr + c, v);
 #pragma unroll
         for (int i = 0; i < N; ++i) s += v[i];
       }
@@ -63,7 +37,7 @@ __global__ __launch_bounds__(256) void norm_fwd_kernel(const T* x, const float* 
     const float mu = kind == FK_NORM_LAYER ? wave_sum(s) / dim : 0.0f;
     float q = 0.0f;
     for (int c = lane * N; c < dim; c += 64 * N) {
-      VecIO<T>::load(xr + c, v);
+      VIO<T>::load(xr + c, v);
 #pragma unroll
       for (int i = 0; i < N; ++i) q += (v[i] - mu) * (v[i] - mu);
     }
@@ -74,7 +48,7 @@ __global__ __launch_bounds__(256) void norm_fwd_kernel(const T* x, const float* 
     }
     T* yr = y + row * dim;
     for (int c = lane * N; c < dim; c += 64 * N) {
-      VecIO<T>::load(xr + c, v);
+      VIO<T>::load(xr + c, v);
       float o[N];
 #pragma unroll
       for (int i = 0; i < N; ++i) {
@@ -82,49 +56,62 @@ __global__ __launch_bounds__(256) void norm_fwd_kernel(const T* x, const float* 
         if (kind == FK_NORM_RMS && sizeof(T) == 2) t = (float)(bf16_t)t;   // reference: _norm(x.float()).type_as(x) * weight
         o[i] = t * gamma[c + i] + (beta ? beta[c + i] : 0.0f);
       }
-      VecIO<T>::store(yr + c, o);
+      VIO<T>::store(yr + c, o);
     }
   }
 }
 
 // Fast path: LPR lanes per row (16 -> 4 rows per wave, or 64), the row lives in registers (read once), exact two-pass
-// variance, LPR-wide shuffle reductions.  lane-in-row l owns columns l*N + it*LPR*N.
+// variance, LPR-wide shuffle reductions.
 template <int LPR> FK_DEV float row_sum(float v) {
 #pragma unroll
   for (int o = LPR / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+// The row frame of the fast forward and the fused backward: lane-in-row l of row group `sub` owns the N-vectors at columns
+// col(it) = l*N + it*LPR*N, it < MAXIT.  dim % N == 0 on these paths, so a whole vector is in or out of range: one predicate per vector.
+// The predicated row loads stay written out in the two kernels: as a shared call (one per tensor, each with its fill value) they cost
+// the forward SGPR spills at <bf16, 16, 4> and the backward, which loads three tensors under one predicate, up to 100 instructions.
+template <typename T, int LPR, int MAXIT> struct RowFrame {
+  static constexpr int N = VIO<T>::N, RPW = 64 / LPR;
+  const int l = (threadIdx.x & 63) % LPR, sub = (threadIdx.x & 63) / LPR;
+  FK_DEV int col(int it) const { return l * N + it * LPR * N; }
+  // vector `it` of gamma / beta by 16-byte loads, zeros unless `in` (48 branchy scalar loads per wave made the prologue as long as
+  // the three row iterations it served)
+  FK_DEV void load_param(const float* p, bool in, int it, float (&v)[N]) const {
+#pragma unroll
+    for (int i = 0; i < N; i += 4) {
+      const f32x4 p4 = in ? *reinterpret_cast<const f32x4*>(p + col(it) + i) : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[i + e] = p4[e];
+    }
+  }
+};
 template <typename T, int LPR, int MAXIT>
 __global__ __launch_bounds__(256) void norm_fwd_fast_kernel(const T* x, const float* gamma, const float* beta, T* y,
                                                              float* mean, float* rstd, int64_t rows, int dim, float eps, int kind) {
-  constexpr int N = VecIO<T>::N, RPW = 64 / LPR;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l = lane % LPR, sub = lane / LPR;
-  // gamma / beta: dim % N == 0 on this path, so a whole N-vector is in or out of range: 16-byte loads, one predicate per vector
-  // (48 branchy scalar loads per wave made the prologue as long as the three row iterations it served)
+  using Frame = RowFrame<T, LPR, MAXIT>;
+  constexpr int N = Frame::N, RPW = Frame::RPW;
+  const Frame f{};
+  const int wave = threadIdx.x >> 6;
   float gm[MAXIT][N], bt[MAXIT][N];
 #pragma unroll
   for (int it = 0; it < MAXIT; ++it) {
-    const int c = l * N + it * LPR * N;
-    const bool in = c < dim;
-#pragma unroll
-    for (int i = 0; i < N; i += 4) {
-      const f32x4 g4 = in ? *reinterpret_cast<const f32x4*>(gamma + c + i) : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-      const f32x4 b4 = (in && beta) ? *reinterpret_cast<const f32x4*>(beta + c + i) : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { gm[it][i + e] = g4[e]; bt[it][i + e] = b4[e]; }
-    }
+    const bool in = f.col(it) < dim;
+    f.load_param(gamma, in, it, gm[it]);
+    f.load_param(beta, in && beta, it, bt[it]);
   }
   const float inv = 1.0f / dim;
   const int64_t stride = (int64_t)gridDim.x * 4 * RPW;
   for (int64_t base = ((int64_t)blockIdx.x * 4 + wave) * RPW; base < rows; base += stride) {   // wave-uniform trip count
-    const int64_t row = base + sub;
+    const int64_t row = base + f.sub;
     const bool ok = row < rows;
     float v[MAXIT][N];
     float s = 0.0f;
 #pragma unroll
     for (int it = 0; it < MAXIT; ++it) {
-      const int c = l * N + it * LPR * N;
-      if (ok && c < dim) VecIO<T>::load(x + row * dim + c, v[it]);
+      const int c = f.col(it);
+      if (ok && c < dim) VIO<T>::load(x + row * dim + c, v[it]);
       else {
 #pragma unroll
         for (int i = 0; i < N; ++i) v[it][i] = 0.0f;
@@ -136,23 +123,21 @@ __global__ __launch_bounds__(256) void norm_fwd_fast_kernel(const T* x, const fl
     float q = 0.0f;
 #pragma unroll
     for (int it = 0; it < MAXIT; ++it) {
-      const int c = l * N + it * LPR * N;
 #pragma unroll
       for (int i = 0; i < N; ++i) {
-        const float d = (c + i < dim) ? v[it][i] - mu : 0.0f;
+        const float d = (f.col(it) + i < dim) ? v[it][i] - mu : 0.0f;
         q += d * d;
       }
     }
     const float rs = rsqrtf(row_sum<LPR>(q) * inv + eps);
     if (ok) {
-      if (l == 0) {
+      if (f.l == 0) {
         if (mean) mean[row] = mu;
         rstd[row] = rs;
       }
 #pragma unroll
       for (int it = 0; it < MAXIT; ++it) {
-        const int c = l * N + it * LPR * N;
-        if (c < dim) {
+        if (f.col(it) < dim) {
           float o[N];
 #pragma unroll
           for (int i = 0; i < N; ++i) {
@@ -160,7 +145,7 @@ __global__ __launch_bounds__(256) void norm_fwd_fast_kernel(const T* x, const fl
             if (kind == FK_NORM_RMS && sizeof(T) == 2) t = (float)(bf16_t)t;
             o[i] = t * gm[it][i] + bt[it][i];
           }
-          VecIO<T>::store(y + row * dim + c, o);
+          VIO<T>::store(y + row * dim + f.col(it), o);
         }
       }
     }
@@ -170,7 +155,7 @@ __global__ __launch_bounds__(256) void norm_fwd_fast_kernel(const T* x, const fl
 template <typename T>
 __global__ __launch_bounds__(256) void norm_bwd_dx_kernel(const T* dy, const T* x, const float* gamma, const float* mean,
                                                            const float* rstd, const T* dres, T* dx, int64_t rows, int dim, int kind) {
-  constexpr int N = VecIO<T>::N;
+  constexpr int N = VIO<T>::N;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t wstride = (int64_t)gridDim.x * 4;
   for (int64_t row = (int64_t)blockIdx.x * 4 + wave; row < rows; row += wstride) {
@@ -180,8 +165,8 @@ __global__ __launch_bounds__(256) void norm_bwd_dx_kernel(const T* dy, const T* 
     float s1 = 0.0f, s2 = 0.0f;
     float xv[N], gv[N];
     for (int c = lane * N; c < dim; c += 64 * N) {
-      VecIO<T>::load(xr + c, xv);
-      VecIO<T>::load(gr + c, gv);
+      VIO<T>::load(xr + c, xv);
+      VIO<T>::load(gr + c, gv);
 #pragma unroll
       for (int i = 0; i < N; ++i) {
         const float dg = gv[i] * gamma[c + i];
@@ -192,60 +177,51 @@ __global__ __launch_bounds__(256) void norm_bwd_dx_kernel(const T* dy, const T* 
     const float c1 = (kind == FK_NORM_LAYER) ? wave_sum(s1) / dim : 0.0f;
     const float c2 = wave_sum(s2) / dim;
     for (int c = lane * N; c < dim; c += 64 * N) {
-      VecIO<T>::load(xr + c, xv);
-      VecIO<T>::load(gr + c, gv);
+      VIO<T>::load(xr + c, xv);
+      VIO<T>::load(gr + c, gv);
       float o[N], rv[N];
-      if (dres) VecIO<T>::load(dres + row * dim + c, rv);
+      if (dres) VIO<T>::load(dres + row * dim + c, rv);
 #pragma unroll
       for (int i = 0; i < N; ++i) {
         const float xh = (xv[i] - mu) * rs;
         o[i] = rs * (gv[i] * gamma[c + i] - c1 - xh * c2) + (dres ? rv[i] : 0.0f);
       }
-      VecIO<T>::store(dx + row * dim + c, o);
+      VIO<T>::store(dx + row * dim + c, o);
     }
   }
 }
 
 // Fused backward: dx (+ residual-branch gradient) AND this block's partial dgamma/dbeta in one sweep; each row is read
-// once into registers (LPR lanes per row, lane-in-row l owns columns l*N + it*LPR*N), column partials live in registers
-// across the block's rows and are combined across row groups (shuffles) and the 4 waves (LDS).
+// once into registers (RowFrame), column partials live in registers across the block's rows and are combined across row groups
+// (shuffles) and the 4 waves (LDS).
 // part layout: [gridDim.x][2][dim].
 template <typename T, int LPR, int MAXIT>
 __global__ __launch_bounds__(256) void norm_bwd_fused_kernel(const T* dy, const T* x, const float* gamma, const float* mean,
                                                               const float* rstd, const T* dres, T* dx, float* part,
                                                               int64_t rows, int dim, int kind) {
-  constexpr int N = VecIO<T>::N, RPW = 64 / LPR;
+  using Frame = RowFrame<T, LPR, MAXIT>;
+  constexpr int N = Frame::N, RPW = Frame::RPW;
   extern __shared__ float red[];   // [4 waves][2][dim]
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l = lane % LPR, sub = lane / LPR;
-  float ag[MAXIT][N], ab[MAXIT][N], gm[MAXIT][N];
+  const Frame f{};
+  const int wave = threadIdx.x >> 6;
+  float ag[MAXIT][N] = {}, ab[MAXIT][N] = {}, gm[MAXIT][N];
 #pragma unroll
-  for (int it = 0; it < MAXIT; ++it) {
-    const int c = l * N + it * LPR * N;
-#pragma unroll
-    for (int i = 0; i < N; ++i) { ag[it][i] = 0.0f; ab[it][i] = 0.0f; }
-    const bool in = c < dim;                              // dim % N == 0: whole vectors in or out, 16-byte gamma loads
-#pragma unroll
-    for (int i = 0; i < N; i += 4) {
-      const f32x4 g4 = in ? *reinterpret_cast<const f32x4*>(gamma + c + i) : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-      for (int e = 0; e < 4; ++e) gm[it][i + e] = g4[e];
-    }
-  }
+  for (int it = 0; it < MAXIT; ++it) f.load_param(gamma, f.col(it) < dim, it, gm[it]);
   const float inv = 1.0f / dim;
   const int64_t stride = (int64_t)gridDim.x * 4 * RPW;
   for (int64_t base = ((int64_t)blockIdx.x * 4 + wave) * RPW; base < rows; base += stride) {
-    const int64_t row = base + sub;
+    const int64_t row = base + f.sub;
     const bool ok = row < rows;
     const float mu = (ok && kind == FK_NORM_LAYER) ? mean[row] : 0.0f, rs = ok ? rstd[row] : 0.0f;
     float xv[MAXIT][N], gv[MAXIT][N], rv[MAXIT][N];
     float s1 = 0.0f, s2 = 0.0f;
 #pragma unroll
     for (int it = 0; it < MAXIT; ++it) {
-      const int c = l * N + it * LPR * N;
+      const int c = f.col(it);
       if (ok && c < dim) {
-        VecIO<T>::load(x + row * dim + c, xv[it]);
-        VecIO<T>::load(dy + row * dim + c, gv[it]);
-        if (dres) VecIO<T>::load(dres + row * dim + c, rv[it]);      // issued with the other loads: its latency hides under the sums
+        VIO<T>::load(x + row * dim + c, xv[it]);
+        VIO<T>::load(dy + row * dim + c, gv[it]);
+        if (dres) VIO<T>::load(dres + row * dim + c, rv[it]);        // issued with the other loads: its latency hides under the sums
       } else {
 #pragma unroll
         for (int i = 0; i < N; ++i) { xv[it][i] = mu; gv[it][i] = 0.0f; }
@@ -262,8 +238,7 @@ __global__ __launch_bounds__(256) void norm_bwd_fused_kernel(const T* dy, const 
     const float c2 = row_sum<LPR>(s2) * inv;
 #pragma unroll
     for (int it = 0; it < MAXIT; ++it) {
-      const int c = l * N + it * LPR * N;
-      if (ok && c < dim) {
+      if (ok && f.col(it) < dim) {
         float o[N];
 #pragma unroll
         for (int i = 0; i < N; ++i) {
@@ -271,7 +246,7 @@ __global__ __launch_bounds__(256) void norm_bwd_fused_kernel(const T* dy, const 
           ag[it][i] += gv[it][i] * xv[it][i];
           ab[it][i] += gv[it][i];
         }
-        VecIO<T>::store(dx + row * dim + c, o);
+        VIO<T>::store(dx + row * dim + f.col(it), o);
       }
     }
   }
@@ -286,10 +261,10 @@ __global__ __launch_bounds__(256) void norm_bwd_fused_kernel(const T* dy, const 
         ab[it][i] += __shfl_xor(ab[it][i], o, 64);
       }
     }
-  if (sub == 0) {
+  if (f.sub == 0) {
 #pragma unroll
     for (int it = 0; it < MAXIT; ++it) {
-      const int c = l * N + it * LPR * N;
+      const int c = f.col(it);
       if (c < dim) {
 #pragma unroll
         for (int i = 0; i < N; ++i) {
@@ -366,6 +341,29 @@ int nchunks(int64_t rows) {
   if (n < 1) n = 1;
   return (int)n;
 }
+// blocks of the fused backward = rows of partials it leaves in the workspace
+int64_t fused_bwd_blocks(int64_t rows) {
+  const int64_t n = fk_cdiv(rows, 16);
+  return n > 1024 ? 1024 : (n < 1 ? 1 : n);
+}
+
+// The <LPR, MAXIT> ladder of norm_fwd_fast_kernel and norm_bwd_fused_kernel: a row takes the first rung with dim <= MAXIT * LPR * N.
+struct Rung { int lpr, maxit; };
+template <typename T> struct Ladder;
+template <> struct Ladder<bf16_t> { static constexpr Rung rung[] = {{16, 1}, {16, 2}, {16, 3}, {16, 4}, {64, 2}, {64, 4}}; };
+template <> struct Ladder<float> { static constexpr Rung rung[] = {{16, 2}, {16, 4}, {16, 6}, {64, 2}, {64, 4}}; };
+template <typename T> constexpr int RUNGS = sizeof(Ladder<T>::rung) / sizeof(Rung);
+template <typename T, int I> constexpr int64_t RUNG_DIM = (int64_t)Ladder<T>::rung[I].maxit * Ladder<T>::rung[I].lpr * VIO<T>::N;
+
+// launch(LPR, MAXIT) (as std::integral_constant values) on dim's rung; false, and nothing launched, above the last rung
+template <typename T, int I = 0, typename F> bool on_rung(int64_t dim, const F& launch) {
+  if constexpr (I < RUNGS<T>) {
+    if (dim > RUNG_DIM<T, I>) return on_rung<T, I + 1>(dim, launch);
+    launch(std::integral_constant<int, Ladder<T>::rung[I].lpr>{}, std::integral_constant<int, Ladder<T>::rung[I].maxit>{});
+    return true;
+  }
+  return false;
+}
 
 }  // namespace
 
@@ -373,85 +371,56 @@ extern "C" {
 
 int fk_norm_fwd(const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd, int64_t rows,
                 int64_t dim, float eps, int kind, int dtype, void* stream) {
-  FK_CHECK_ARG(dtype == FK_F32 || dtype == FK_BF16, "fk_norm_fwd: bad dtype %d", dtype);
+  FK_DT_CHECK("fk_norm_fwd");
   FK_CHECK_ARG(kind == FK_NORM_LAYER || kind == FK_NORM_RMS, "fk_norm_fwd: bad kind %d", kind);
   const int vec = dtype == FK_BF16 ? 8 : 4;
   FK_CHECK_ARG(rows > 0 && dim > 0 && dim % vec == 0 && dim < (1 << 24), "fk_norm_fwd: dim %lld must be a multiple of %d", (long long)dim, vec);
   FK_CHECK_ARG(x && y && gamma && rstd && (kind == FK_NORM_RMS || mean), "fk_norm_fwd: null pointer");
   FK_CHECK_ARG((((uintptr_t)x | (uintptr_t)y) & 15) == 0, "fk_norm_fwd: x/y must be 16-byte aligned");
   hipStream_t s = (hipStream_t)stream;
-  const int per16 = 16 * vec, per64 = 64 * vec;
-#define FK_NF(TT, LPR, MI)                                                                                                 \
-  do {                                                                                                                     \
-    int64_t nbf = fk_cdiv(rows, 4 * (64 / LPR));                                                                           \
-    if (nbf > 2048) nbf = 2048;                                                                                            \
-    hipLaunchKernelGGL((norm_fwd_fast_kernel<TT, LPR, MI>), dim3((unsigned)nbf), dim3(256), 0, s, (const TT*)x, gamma, beta, \
-                       (TT*)y, mean, rstd, rows, (int)dim, eps, kind);                                                     \
-  } while (0)
   bool done = (((uintptr_t)gamma | (uintptr_t)beta) & 15) == 0;       // the fast kernels read gamma / beta as 16-byte vectors
-  if (!done) {
-  } else if (dtype == FK_BF16) {
-    if (dim <= per16) FK_NF(bf16_t, 16, 1); else if (dim <= 2 * per16) FK_NF(bf16_t, 16, 2); else if (dim <= 3 * per16) FK_NF(bf16_t, 16, 3);
-    else if (dim <= 4 * per16) FK_NF(bf16_t, 16, 4); else if (dim <= 2 * per64) FK_NF(bf16_t, 64, 2); else if (dim <= 4 * per64) FK_NF(bf16_t, 64, 4);
-    else done = false;
-  } else {
-    if (dim <= 2 * per16) FK_NF(float, 16, 2); else if (dim <= 4 * per16) FK_NF(float, 16, 4); else if (dim <= 6 * per16) FK_NF(float, 16, 6);
-    else if (dim <= 2 * per64) FK_NF(float, 64, 2); else if (dim <= 4 * per64) FK_NF(float, 64, 4);
-    else done = false;
-  }
-#undef FK_NF
+  if (done)
+    FK_BY_DTYPE(dtype, T, done = on_rung<T>(dim, [&](auto lpr, auto maxit) {
+      int64_t nbf = fk_cdiv(rows, 4 * (64 / lpr));
+      if (nbf > 2048) nbf = 2048;
+      hipLaunchKernelGGL((norm_fwd_fast_kernel<T, lpr, maxit>), dim3((unsigned)nbf), dim3(256), 0, s, (const T*)x, gamma, beta, (T*)y, mean, rstd, rows, (int)dim, eps, kind);
+    }));
   if (!done) {
     int64_t nb = fk_cdiv(rows, 4);
     if (nb > 8192) nb = 8192;
-    if (dtype == FK_BF16)
-      hipLaunchKernelGGL(norm_fwd_kernel<bf16_t>, dim3((unsigned)nb), dim3(256), 0, s, (const bf16_t*)x, gamma, beta, (bf16_t*)y, mean, rstd, rows, (int)dim, eps, kind);
-    else
-      hipLaunchKernelGGL(norm_fwd_kernel<float>, dim3((unsigned)nb), dim3(256), 0, s, (const float*)x, gamma, beta, (float*)y, mean, rstd, rows, (int)dim, eps, kind);
+    FK_BY_DTYPE(dtype, T, hipLaunchKernelGGL(norm_fwd_kernel<T>, dim3((unsigned)nb), dim3(256), 0, s, (const T*)x, gamma, beta, (T*)y, mean, rstd, rows, (int)dim, eps, kind));
   }
   FK_CHECK_LAUNCH("fk_norm_fwd");
   return FK_OK;
 }
 
 size_t fk_norm_bwd_workspace_bytes(int64_t rows, int64_t dim) {
-  int64_t nbf = fk_cdiv(rows, 16);
-  if (nbf > 1024) nbf = 1024;
-  if (nbf < 1) nbf = 1;
-  const int64_t n = nbf > nchunks(rows) ? nbf : nchunks(rows);
+  const int64_t nbf = fused_bwd_blocks(rows), n = nbf > nchunks(rows) ? nbf : nchunks(rows);
   return (size_t)n * 2 * dim * sizeof(float);
 }
 
 int fk_norm_bwd(const void* dy, const void* x, const float* gamma, const float* mean, const float* rstd, const void* dres,
                 void* dx, float* dgamma, float* dbeta, int64_t rows, int64_t dim, int kind, int accumulate, int dtype,
                 void* workspace, size_t workspace_bytes, void* stream) {
-  FK_CHECK_ARG(dtype == FK_F32 || dtype == FK_BF16, "fk_norm_bwd: bad dtype %d", dtype);
+  FK_DT_CHECK("fk_norm_bwd");
   FK_CHECK_ARG(kind == FK_NORM_LAYER || kind == FK_NORM_RMS, "fk_norm_bwd: bad kind %d", kind);
   const int vec = dtype == FK_BF16 ? 8 : 4;
   FK_CHECK_ARG(rows > 0 && dim > 0 && dim % vec == 0, "fk_norm_bwd: dim %lld must be a multiple of %d", (long long)dim, vec);
   FK_CHECK_ARG(dy && x && gamma && rstd && dx && (kind == FK_NORM_RMS || mean), "fk_norm_bwd: null pointer");
   hipStream_t s = (hipStream_t)stream;
-  const int per16 = 16 * vec, per64 = 64 * vec;
-  const bool fits = (dtype == FK_BF16 ? dim <= 4 * per64 : dim <= 4 * per64) && (size_t)8 * dim * sizeof(float) <= 65536 &&
-                    ((uintptr_t)gamma & 15) == 0;     // the fused kernel reads gamma as 16-byte vectors
+  int64_t top;
+  FK_BY_DTYPE(dtype, T, (top = RUNG_DIM<T, RUNGS<T> - 1>));
+  const size_t sh = (size_t)8 * dim * sizeof(float);                  // [4 waves][2][dim]
+  const bool fits = dim <= top && sh <= 65536 && ((uintptr_t)gamma & 15) == 0;     // the fused kernel reads gamma as 16-byte vectors
   if (fits) {
     // fused sweep: dx + per-block dgamma/dbeta partials
     const bool want = dgamma || dbeta;
-    int64_t nbf = fk_cdiv(rows, 16);
-    if (nbf > 1024) nbf = 1024;
-    if (nbf < 1) nbf = 1;
+    const int64_t nbf = fused_bwd_blocks(rows);
     if (want) FK_CHECK_ARG(workspace && workspace_bytes >= (size_t)nbf * 2 * dim * sizeof(float), "fk_norm_bwd: workspace too small");
     float* part = want ? (float*)workspace : nullptr;
-    const size_t sh = (size_t)8 * dim * sizeof(float);
-#define FK_NB(TT, LPR, MI)                                                                                                  \
-  hipLaunchKernelGGL((norm_bwd_fused_kernel<TT, LPR, MI>), dim3((unsigned)nbf), dim3(256), sh, s, (const TT*)dy, (const TT*)x, \
-                     gamma, mean, rstd, (const TT*)dres, (TT*)dx, part, rows, (int)dim, kind)
-    if (dtype == FK_BF16) {
-      if (dim <= per16) FK_NB(bf16_t, 16, 1); else if (dim <= 2 * per16) FK_NB(bf16_t, 16, 2); else if (dim <= 3 * per16) FK_NB(bf16_t, 16, 3);
-      else if (dim <= 4 * per16) FK_NB(bf16_t, 16, 4); else if (dim <= 2 * per64) FK_NB(bf16_t, 64, 2); else FK_NB(bf16_t, 64, 4);
-    } else {
-      if (dim <= 2 * per16) FK_NB(float, 16, 2); else if (dim <= 4 * per16) FK_NB(float, 16, 4); else if (dim <= 6 * per16) FK_NB(float, 16, 6);
-      else if (dim <= 2 * per64) FK_NB(float, 64, 2); else FK_NB(float, 64, 4);
-    }
-#undef FK_NB
+    FK_BY_DTYPE(dtype, T, on_rung<T>(dim, [&](auto lpr, auto maxit) {
+      hipLaunchKernelGGL((norm_bwd_fused_kernel<T, lpr, maxit>), dim3((unsigned)nbf), dim3(256), sh, s, (const T*)dy, (const T*)x, gamma, mean, rstd, (const T*)dres, (T*)dx, part, rows, (int)dim, kind);
+    }));
     FK_CHECK_LAUNCH("fk_norm_bwd(fused)");
     if (want) {
       hipLaunchKernelGGL(norm_bwd_fused_final, dim3((unsigned)fk_cdiv(dim, 16), 2), dim3(1024), 0, s, (const float*)part, dgamma, dbeta, (int)dim, (int)nbf, accumulate);
@@ -461,20 +430,14 @@ int fk_norm_bwd(const void* dy, const void* x, const float* gamma, const float* 
   }
   int64_t nb = fk_cdiv(rows, 4);
   if (nb > 8192) nb = 8192;
-  if (dtype == FK_BF16)
-    hipLaunchKernelGGL(norm_bwd_dx_kernel<bf16_t>, dim3((unsigned)nb), dim3(256), 0, s, (const bf16_t*)dy, (const bf16_t*)x, gamma, mean, rstd, (const bf16_t*)dres, (bf16_t*)dx, rows, (int)dim, kind);
-  else
-    hipLaunchKernelGGL(norm_bwd_dx_kernel<float>, dim3((unsigned)nb), dim3(256), 0, s, (const float*)dy, (const float*)x, gamma, mean, rstd, (const float*)dres, (float*)dx, rows, (int)dim, kind);
+  FK_BY_DTYPE(dtype, T, hipLaunchKernelGGL(norm_bwd_dx_kernel<T>, dim3((unsigned)nb), dim3(256), 0, s, (const T*)dy, (const T*)x, gamma, mean, rstd, (const T*)dres, (T*)dx, rows, (int)dim, kind));
   FK_CHECK_LAUNCH("fk_norm_bwd(dx)");
   if (dgamma || dbeta) {
     const int nc = nchunks(rows);
     FK_CHECK_ARG(workspace && workspace_bytes >= (size_t)nc * 2 * dim * sizeof(float), "fk_norm_bwd: workspace too small");
     const int rpc = (int)fk_cdiv(rows, nc);
     dim3 grid((unsigned)fk_cdiv(dim, 128), (unsigned)nc);
-    if (dtype == FK_BF16)
-      hipLaunchKernelGGL(norm_bwd_param_partial<bf16_t>, grid, dim3(128), 0, s, (const bf16_t*)dy, (const bf16_t*)x, mean, rstd, (float*)workspace, rows, (int)dim, rpc, kind);
-    else
-      hipLaunchKernelGGL(norm_bwd_param_partial<float>, grid, dim3(128), 0, s, (const float*)dy, (const float*)x, mean, rstd, (float*)workspace, rows, (int)dim, rpc, kind);
+    FK_BY_DTYPE(dtype, T, hipLaunchKernelGGL(norm_bwd_param_partial<T>, grid, dim3(128), 0, s, (const T*)dy, (const T*)x, mean, rstd, (float*)workspace, rows, (int)dim, rpc, kind));
     FK_CHECK_LAUNCH("fk_norm_bwd(partial)");
     hipLaunchKernelGGL(norm_bwd_param_final, dim3((unsigned)fk_cdiv(dim, 128)), dim3(128), 0, s, (const float*)workspace, dgamma, dbeta, (int)dim, nc, accumulate);
     FK_CHECK_LAUNCH("fk_norm_bwd(final)");

@@ -323,7 +323,7 @@ int fk_vq_route(int64_t D, int64_t K, int dtype) { return vq_fused(D, K, dtype) 
 int fk_vq_assign(const void* x, int64_t ldx, const float* codes, int64_t* idx, void* q, float* counts, int64_t counts_stride, float* sums,
                  int64_t ld_sums, float* commit_partials, float* commit, float commit_scale, uint32_t* ticket, int64_t R, int64_t K,
                  int64_t D, int dtype, void* stream) {
-  FK_CHECK_ARG(dtype == FK_F32 || dtype == FK_BF16, "fk_vq_assign: bad dtype %d", dtype);
+  FK_DT_CHECK("fk_vq_assign");
   FK_CHECK_ARG(x && codes && idx, "fk_vq_assign: null pointer");
   FK_CHECK_ARG(R > 0 && R < (1LL << 36) && K > 0 && D > 0 && ldx >= D, "fk_vq_assign: bad shape (R %lld, K %lld, D %lld, ldx %lld)", (long long)R,
                (long long)K, (long long)D, (long long)ldx);
@@ -336,20 +336,18 @@ int fk_vq_assign(const void* x, int64_t ldx, const float* codes, int64_t* idx, v
                "fk_vq_assign: x / q rows must be aligned to 4 elements, codes to 16 bytes");
   if (!vq_fused(D, K, dtype)) return fk_set_error(FK_EUNSUPPORTED, "fk_vq_assign: outside the envelope (D %% 4 == 0, 4 <= D <= 128, K < 2^31): see fk_vq_route");
   const VqArgs a{x, ldx, codes, idx, q, counts, counts_stride, sums, ld_sums, commit_partials, commit, commit_scale, ticket, R, K, (int)D};
-  if (dtype == FK_BF16) vq_assign_launch<bf16_t>(a, (hipStream_t)stream);
-  else vq_assign_launch<float>(a, (hipStream_t)stream);
+  FK_BY_DTYPE(dtype, T, vq_assign_launch<T>(a, (hipStream_t)stream));
   FK_CHECK_LAUNCH("fk_vq_assign");
   return FK_OK;
 }
 
 int fk_vq_bwd(const void* x, const void* q, const void* dq, const float* d_commit, float c_scale, void* dx, int64_t n, int dtype,
               void* stream) {
-  FK_CHECK_ARG(dtype == FK_F32 || dtype == FK_BF16, "fk_vq_bwd: bad dtype %d", dtype);
+  FK_DT_CHECK("fk_vq_bwd");
   FK_CHECK_ARG(x && q && dx && n > 0, "fk_vq_bwd: bad arguments");
   hipStream_t s = (hipStream_t)stream;
   const unsigned nb = (unsigned)(fk_cdiv(n, 256) < 65536 ? fk_cdiv(n, 256) : 65536);
-  if (dtype == FK_BF16) hipLaunchKernelGGL(vq_bwd_kernel<bf16_t>, dim3(nb), dim3(256), 0, s, (const bf16_t*)x, (const bf16_t*)q, (const bf16_t*)dq, d_commit, c_scale, (bf16_t*)dx, n);
-  else hipLaunchKernelGGL(vq_bwd_kernel<float>, dim3(nb), dim3(256), 0, s, (const float*)x, (const float*)q, (const float*)dq, d_commit, c_scale, (float*)dx, n);
+  FK_BY_DTYPE(dtype, T, hipLaunchKernelGGL(vq_bwd_kernel<T>, dim3(nb), dim3(256), 0, s, (const T*)x, (const T*)q, (const T*)dq, d_commit, c_scale, (T*)dx, n));
   FK_CHECK_LAUNCH("fk_vq_bwd");
   return FK_OK;
 }

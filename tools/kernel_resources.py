@@ -5,7 +5,7 @@ The generated instruction streams (csrc/attn_*_asm.inc) hard-code their temporar
 addresses to hipcc; a compiler update that spills inside the loop or pushes a kernel past 256 registers (one wave per SIMD instead of
 two) would be silent until a performance run.  tests/test_codegen_cpu.py holds the compiled kernels to the documented bounds.
 
-    python tools/kernel_resources.py            # table for the hand-scheduled kernels (all nine sources are compiled)
+    python tools/kernel_resources.py            # table for the hand-scheduled kernels (all twelve sources are compiled)
 """
 from __future__ import annotations
 
@@ -19,12 +19,13 @@ ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
 
 
-def compile_isa(src: str, outdir: Path):
-    """device-only assembly + resource remarks of csrc/<src> with the build's own flags -> (path of the .s, remark text)"""
+def compile_isa(src: str, outdir: Path, root: Path = ROOT):
+    """device-only assembly + resource remarks of csrc/<src> with the build's own flags -> (path of the .s, remark text); `root`: the
+    tree whose source is compiled (another checkout for tools/device_asm_diff.py), the flags are this tree's either way"""
     from frankenstein_amd import build as B
     out = Path(outdir) / (src + ".s")
-    cmd = [B.HIPCC, *B.flags_for(src), "-S", "--cuda-device-only", f"-I{ROOT / 'include'}", "-Rpass-analysis=kernel-resource-usage",
-           "-o", str(out), str(B.CSRC / src)]
+    cmd = [B.HIPCC, *B.flags_for(src), "-S", "--cuda-device-only", f"-I{Path(root) / 'include'}", "-Rpass-analysis=kernel-resource-usage",
+           "-o", str(out), str(Path(root) / B.CSRC.relative_to(ROOT) / src)]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError(f"hipcc failed for {src}:\n{r.stderr[-4000:]}")
