@@ -369,9 +369,6 @@ FK_DEV void store_rows_T_rope(T* base, int64_t rs, int row, bool row_ok, const f
     const int d = dt * 32 + 8 * g + 4 * lh;
     f32x4 cs = {1.0f, 0.0f, 1.0f, 0.0f};
     if (row_ok) cs = *reinterpret_cast<const f32x4*>(table + d);   // (c0, s0, c1, s1) for pairs d/2, d/2+1
-#ifdef FK_ROPE_EPI_NOPS
-    asm volatile("s_waitcnt vmcnt(0)\n\ts_nop 15" ::: "memory");
-#endif
     const float a0 = acc[dt][4 * g] * mul, a1 = acc[dt][4 * g + 1] * mul, a2 = acc[dt][4 * g + 2] * mul, a3 = acc[dt][4 * g + 3] * mul;
     o[0] = a0 * cs[0] + a1 * cs[1];
     o[1] = -a0 * cs[1] + a1 * cs[0];
@@ -1287,7 +1284,7 @@ __global__ __launch_bounds__(NT, (sizeof(T) == 2 && D <= 64) ? 2 : 1) void attn_
 //             bf16 has fp32's exponent range, so P up to 2^40 keeps the same relative precision as P <= 1.
 //   backward: S' = Q'K^T - LSE*log2(e) and dP' = dO V^T - delta start from the row constants, P = exp2(S'), dS = P * dP'.
 #ifdef FK_STAMP
-// diagnostic build only (tools/build_variant.sh stamp ... -DFK_STAMP): cycles per loop segment, summed over waves; never in the product
+// diagnostic build only (tools/build_variant.py stamp attention.hip -DFK_STAMP): cycles per loop segment, summed over waves; never in the product
 __device__ unsigned long long fk_stamp_acc[16];
 #define FK_ST_DECL unsigned long long st_t0 = __builtin_amdgcn_s_memtime(), st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #define FK_ST(i) { const unsigned long long st_t1 = __builtin_amdgcn_s_memtime(); st_acc[i] += st_t1 - st_t0; st_t0 = st_t1; }
@@ -1736,7 +1733,6 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_bwd_dq_ps_kernel(AttnArgs p) 
   store_dq(p, b, hd, qrow, q_ok, dq, lh);
 }
 
-#ifndef FK_NO_FWD_ASM
 #include "attn_fwd_asm.inc"       // generated by tools/gen/gen_fwd_asm.py: hand-placed, software-pipelined lean forward tile steps
 // Forward for shapes where every tile of every wave is fully visible and aligned (launch_fwd checks).  Same algorithm as
 // attn_fwd_ps_kernel: classic online softmax until every row's maximum lies in the window, then reference 0 (P = exp2(S'), nothing else
@@ -1896,7 +1892,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_asm_kernel(AttnArgs p) {
     stream_drain();
     if (!lean_ok) break;
 #ifdef FK_FWD_PROBE_NOREDO
-    break;                                                       // timing builds of ablated streams (tools/stream_variants.sh): their sums mean nothing
+    break;                                                       // timing builds of ablated streams (the generators' FK_GEN_ABLATE_*): their sums mean nothing
 #endif
     // 3. did any wave of the workgroup see a half-row sum outside the safe range?  (rare: then everything again, classic only)
     const bool trip = __builtin_amdgcn_ballot_w64(!(rmax <= PS_REDO)) != 0;
@@ -1923,9 +1919,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_asm_kernel(AttnArgs p) {
 }
 constexpr size_t FWD_ASM_LDS = 2 * 4 * 64 * 128 + 16;
 static_assert(FWD_ASM_LDS <= 160 * 1024, "LDS of a CU");
-#endif
 
-#ifndef FK_NO_DQ_ASM
 #include "attn_dq_asm.inc"        // generated by tools/gen/gen_dq_asm.py: hand-placed instruction stream of one fully visible tile step
 // dQ for shapes where every tile of every wave is fully visible and aligned (launch_bwd checks): the tile step is the generated stream,
 // which also issues the K / V tile requests of the step after next and ends with the wait + barrier; the C++ around it is the prologue
@@ -1983,11 +1977,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_asm_kernel(AttnArgs p) {
   store_dq(p, b, hd, qrow, true, dq, lh);
   FK_LIFE_END(1)
 }
-#endif
 
-#if !defined(FK_NO_DKDV_ASM) || !defined(FK_NO_DKDVW_ASM)   // (the wide kernel issues its tile requests with the narrow stream's request blocks)
 #include "attn_dkdv_asm.inc"      // generated by tools/gen/gen_dkdv_asm.py: hand-placed instruction stream of one fully visible tile step
-#endif
 // ------------------------------------------------------------------------------------------------- dK, dV (pre-scaled Q)
 template <int NW>
 __global__ __launch_bounds__(NW * 64, 2) void attn_bwd_dkdv_ps_kernel(AttnArgs p) {
@@ -2154,7 +2145,6 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_bwd_dkdv_ps_kernel(AttnArgs p
   FK_ST_FLUSH(0)
 }
 
-#ifndef FK_NO_DKDV_ASM
 // ------------------------------------------------------------------------------------------------- dK, dV: hand-placed stream
 // The fully visible, fully aligned case (every tile of every workgroup visible to all its keys: no mask or a block-causal mask whose
 // block is a multiple of 128 keys and of the 64-query tile, no offsets, Nk % 128 == 0, Nq % 64 == 0 — the benchmark's shape) runs the
@@ -2233,9 +2223,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_asm_kernel(AttnArgs p) {
   store_dk_dv(p, b, hd, krow, true, dk, dv, lh);
   FK_LIFE_END(2)
 }
-#endif
 
-#ifndef FK_NO_DKDVW_ASM
 #include "attn_dkdvw_asm.inc"     // generated by tools/gen/gen_dkdvw_asm.py: the tile step of the wide dK/dV kernel
 // ------------------------------------------------------------------------------------------------- dK, dV: 64 keys per wave, one wave per SIMD
 // Same algorithm, ring and requests as attn_bwd_dkdv_asm_kernel; a wave owns 64 keys (two 32-key blocks), a workgroup 256, so every LDS
@@ -2308,7 +2296,6 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkdvw_asm_kernel(AttnArgs p) 
 #pragma unroll
   for (int kb = 0; kb < 2; ++kb) store_dk_dv(p, b, hd, krow0 + 32 * kb, true, dk[kb], dv[kb], lh);
 }
-#endif
 
 // ------------------------------------------------------------------------------------------------- host
 template <typename T, int D> size_t fwd_lds() {
@@ -2324,23 +2311,21 @@ template <typename K> void allow_lds(K kernel, size_t bytes) {
   if (bytes > 65536) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 }
 
-#ifndef FK_FWD_NW
-#define FK_FWD_NW 8
-#endif
-#ifndef FK_DQ_NW
-#define FK_DQ_NW 4
-#endif
-#ifndef FK_DKDV_NW
-#define FK_DKDV_NW 4
-#endif
+// launch of a kernel with the dynamic LDS it asks for allowed first; attn_grid: one workgroup per `rows` of the n query / key rows of a (batch, head)
+template <auto Kernel> void launch_attn(unsigned grid, int threads, size_t lds, hipStream_t s, const AttnArgs& a) {
+  allow_lds(Kernel, lds);
+  hipLaunchKernelGGL(Kernel, dim3(grid), dim3((unsigned)threads), lds, s, a);
+}
+unsigned attn_grid(const AttnArgs& a, int n, int rows) { return (unsigned)(((n + rows - 1) / rows) * a.H * a.B); }
+
+constexpr int FK_FWD_NW = 8, FK_DQ_NW = 4, FK_DKDV_NW = 4;   // waves (of 32 rows) per workgroup of the pre-scaled hipcc kernels
 // every tile of every workgroup fully visible and aligned (workgroups of `block` rows): what the generated instruction streams take
 bool fully_visible(const AttnArgs& a, int block) {
   return a.q_off == 0 && a.k_off == 0 && (a.mask_kind == FK_MASK_NONE || (a.mask_kind == FK_MASK_BLOCK_CAUSAL && a.mask_c % block == 0));
 }
 // few queries, long context: the waves split the keys (attn_fwd_fewq_kernel, attn_bwd_dq_fewq_kernel)
 bool few_queries(const AttnArgs& a) {
-  static const bool no_fewq = getenv("FK_ATTN_NO_FEWQ") != nullptr;      // tuning knob
-  return !no_fewq && a.Nq <= 32 && a.Nk >= 1024 && a.mask_kind == FK_MASK_NONE && !a.drop_thresh;
+  return a.Nq <= 32 && a.Nk >= 1024 && a.mask_kind == FK_MASK_NONE && !a.drop_thresh;
 }
 // The kernels a problem runs on (the FK_ATTN_* values of franken_hip.h): the one place where that is decided.  launch_fwd / launch_bwd
 // launch what it says and fk_attn_route answers with it, so the tests can say which kernel a shape reaches.  swz: bf16 with D = 64 (the
@@ -2351,19 +2336,10 @@ AttnRoute attn_route(const AttnArgs& a, bool swz, bool has_rope) {
   if (swz && (a.flags & FK_ATTN_Q_PRESCALED)) {
     const bool vis_all = fully_visible(a, 128);
     r.fwd = FK_ATTN_FWD_PS; r.dq = FK_ATTN_DQ_PS; r.dkdv = FK_ATTN_DKDV_PS;
-#ifndef FK_NO_FWD_ASM
     if (vis_all && a.Nq % 128 == 0 && a.Nk % 64 == 0) r.fwd = FK_ATTN_FWD_ASM;
-#endif
-#ifndef FK_NO_DQ_ASM
     if (vis_all && a.Nq % 128 == 0 && a.Nk % 64 == 0) r.dq = FK_ATTN_DQ_ASM;
-#endif
-#ifndef FK_NO_DKDV_ASM
     if (vis_all && a.Nk % 128 == 0 && a.Nq % 64 == 0) r.dkdv = FK_ATTN_DKDV_ASM;
-#endif
-#ifndef FK_NO_DKDVW_ASM
-    static const bool no_wide = getenv("FK_ATTN_NO_DKDVW") != nullptr;    // tuning knob: the 32-keys-per-wave stream instead
-    if (!no_wide && fully_visible(a, 256) && a.Nk % 256 == 0 && a.Nq % 64 == 0) r.dkdv = FK_ATTN_DKDVW_ASM;
-#endif
+    if (fully_visible(a, 256) && a.Nk % 256 == 0 && a.Nq % 64 == 0) r.dkdv = FK_ATTN_DKDVW_ASM;
     return r;
   }
   if (swz && few_queries(a)) {
@@ -2373,90 +2349,34 @@ AttnRoute attn_route(const AttnArgs& a, bool swz, bool has_rope) {
   return r;
 }
 
+// launch_fwd / launch_bwd launch what attn_route says.  It names another kernel than the generic one only for the swizzled image, the one
+// layout those kernels are compiled for, so in every other instantiation the switches always take their default.
 template <typename T, int D> int launch_fwd(const AttnArgs& a, hipStream_t s) {
-  constexpr int NW = Img<T, D>::SWZ ? 8 : 4;
-  const int route = attn_route(a, Img<T, D>::SWZ, false).fwd;
-  if constexpr (Img<T, D>::SWZ) {
-#ifndef FK_NO_FWD_ASM
-    if (route == FK_ATTN_FWD_ASM) {
-      allow_lds(attn_fwd_asm_kernel, FWD_ASM_LDS);
-      hipLaunchKernelGGL(attn_fwd_asm_kernel, dim3((unsigned)(a.Nq / 128 * a.H * a.B)), dim3(256), FWD_ASM_LDS, s, a);
-      return 0;
-    }
-#endif
-    if (route == FK_ATTN_FWD_PS) {
-      constexpr int NWF = FK_FWD_NW;
-      dim3 grid((unsigned)(((a.Nq + NWF * 32 - 1) / (NWF * 32)) * a.H * a.B));
-      const size_t lds = fwd_lds<T, D>();
-      allow_lds(attn_fwd_ps_kernel<NWF>, lds);
-      hipLaunchKernelGGL((attn_fwd_ps_kernel<NWF>), grid, dim3(NWF * 64), lds, s, a);
-      return 0;
-    }
-    if (route == FK_ATTN_FWD_FEWQ) {
-      allow_lds(attn_fwd_fewq_kernel, FEWQ_LDS);
-      hipLaunchKernelGGL(attn_fwd_fewq_kernel, dim3((unsigned)(a.H * a.B)), dim3(FEWQ_NW * 64), FEWQ_LDS, s, a);
-      return 0;
-    }
+  constexpr bool SWZ = Img<T, D>::SWZ;
+  constexpr int NW = SWZ ? 8 : 4;
+  switch (attn_route(a, SWZ, false).fwd) {
+    case FK_ATTN_FWD_ASM: launch_attn<attn_fwd_asm_kernel>(attn_grid(a, a.Nq, 128), 256, FWD_ASM_LDS, s, a); break;
+    case FK_ATTN_FWD_PS: launch_attn<attn_fwd_ps_kernel<FK_FWD_NW>>(attn_grid(a, a.Nq, FK_FWD_NW * 32), FK_FWD_NW * 64, fwd_lds<bf16_t, 64>(), s, a); break;
+    case FK_ATTN_FWD_FEWQ: launch_attn<attn_fwd_fewq_kernel>((unsigned)(a.H * a.B), FEWQ_NW * 64, FEWQ_LDS, s, a); break;
+    default: launch_attn<attn_fwd_kernel<T, D, NW>>(attn_grid(a, a.Nq, NW * 32), NW * 64, fwd_lds<T, D>(), s, a); break;
   }
-  dim3 grid((unsigned)(((a.Nq + NW * 32 - 1) / (NW * 32)) * a.H * a.B));
-  const size_t lds = fwd_lds<T, D>();
-  allow_lds(attn_fwd_kernel<T, D, NW>, lds);
-  hipLaunchKernelGGL((attn_fwd_kernel<T, D, NW>), grid, dim3(NW * 64), lds, s, a);
   return 0;
 }
 template <typename T, int D> int launch_bwd(const AttnArgs& a, hipStream_t s) {
-  // dQ first: it also writes delta = rowsum(dO * O) [B, H, Nq], which the dK/dV kernel reads
-  dim3 gk((unsigned)(((a.Nk + 127) / 128) * a.H * a.B));
-  const size_t lds_kv = dkdv_lds<T, D>(), lds_q = dq_lds<T, D>();
-  allow_lds(attn_bwd_dkdv_kernel<T, D>, lds_kv);
-  allow_lds(attn_bwd_dq_kernel<T, D>, lds_q);
-  dim3 gq((unsigned)(((a.Nq + BQ - 1) / BQ) * a.H * a.B));
   const AttnRoute route = attn_route(a, Img<T, D>::SWZ, a.rope_table != nullptr);
-  if constexpr (Img<T, D>::SWZ) {
-    if (route.dq == FK_ATTN_DQ_ASM || route.dq == FK_ATTN_DQ_PS) {         // the pre-scaled kernels: dQ and dK/dV both
-      constexpr int NWQ = FK_DQ_NW, NWK = FK_DKDV_NW;
-      dim3 gq2((unsigned)(((a.Nq + NWQ * 32 - 1) / (NWQ * 32)) * a.H * a.B)), gk2((unsigned)(((a.Nk + NWK * 32 - 1) / (NWK * 32)) * a.H * a.B));
-      bool dq_done = false;
-#ifndef FK_NO_DQ_ASM
-      if (route.dq == FK_ATTN_DQ_ASM) {
-        allow_lds(attn_bwd_dq_asm_kernel, DQ_PS_LDS);
-        hipLaunchKernelGGL(attn_bwd_dq_asm_kernel, dim3((unsigned)(a.Nq / 128 * a.H * a.B)), dim3(256), DQ_PS_LDS, s, a);
-        dq_done = true;
-      }
-#endif
-      if (!dq_done) {
-        allow_lds(attn_bwd_dq_ps_kernel<NWQ>, DQ_PS_LDS);
-        hipLaunchKernelGGL(attn_bwd_dq_ps_kernel<NWQ>, gq2, dim3(NWQ * 64), DQ_PS_LDS, s, a);
-      }
-#ifndef FK_NO_DKDVW_ASM
-      if (route.dkdv == FK_ATTN_DKDVW_ASM) {
-        allow_lds(attn_bwd_dkdvw_asm_kernel, DKDV_PS_LDS);
-        hipLaunchKernelGGL(attn_bwd_dkdvw_asm_kernel, dim3((unsigned)(a.Nk / 256 * a.H * a.B)), dim3(256), DKDV_PS_LDS, s, a);
-        return 0;
-      }
-#endif
-#ifndef FK_NO_DKDV_ASM
-      if (route.dkdv == FK_ATTN_DKDV_ASM) {
-        allow_lds(attn_bwd_dkdv_asm_kernel, DKDV_PS_LDS);
-        hipLaunchKernelGGL(attn_bwd_dkdv_asm_kernel, gk2, dim3(256), DKDV_PS_LDS, s, a);
-        return 0;
-      }
-#endif
-      allow_lds(attn_bwd_dkdv_ps_kernel<NWK>, DKDV_PS_LDS);
-      hipLaunchKernelGGL(attn_bwd_dkdv_ps_kernel<NWK>, gk2, dim3(NWK * 64), DKDV_PS_LDS, s, a);
-      return 0;
-    }
+  // dQ first: it also writes delta = rowsum(dO * O) [B, H, Nq], which the dK/dV kernel reads
+  switch (route.dq) {
+    case FK_ATTN_DQ_ASM: launch_attn<attn_bwd_dq_asm_kernel>(attn_grid(a, a.Nq, 128), 256, DQ_PS_LDS, s, a); break;
+    case FK_ATTN_DQ_PS: launch_attn<attn_bwd_dq_ps_kernel<FK_DQ_NW>>(attn_grid(a, a.Nq, FK_DQ_NW * 32), FK_DQ_NW * 64, DQ_PS_LDS, s, a); break;
+    case FK_ATTN_DQ_FEWQ: launch_attn<attn_bwd_dq_fewq_kernel>((unsigned)(a.H * a.B), FEWQ_NW * 64, FEWQ_LDS, s, a); break;
+    default: launch_attn<attn_bwd_dq_kernel<T, D>>(attn_grid(a, a.Nq, BQ), NT, dq_lds<T, D>(), s, a); break;
   }
-  bool dq_done = false;
-  if constexpr (Img<T, D>::SWZ) {
-    if (route.dq == FK_ATTN_DQ_FEWQ) {
-      allow_lds(attn_bwd_dq_fewq_kernel, FEWQ_LDS);
-      hipLaunchKernelGGL(attn_bwd_dq_fewq_kernel, dim3((unsigned)(a.H * a.B)), dim3(FEWQ_NW * 64), FEWQ_LDS, s, a);
-      dq_done = true;
-    }
+  switch (route.dkdv) {
+    case FK_ATTN_DKDVW_ASM: launch_attn<attn_bwd_dkdvw_asm_kernel>(attn_grid(a, a.Nk, 256), 256, DKDV_PS_LDS, s, a); break;
+    case FK_ATTN_DKDV_ASM: launch_attn<attn_bwd_dkdv_asm_kernel>(attn_grid(a, a.Nk, 128), 256, DKDV_PS_LDS, s, a); break;
+    case FK_ATTN_DKDV_PS: launch_attn<attn_bwd_dkdv_ps_kernel<FK_DKDV_NW>>(attn_grid(a, a.Nk, FK_DKDV_NW * 32), FK_DKDV_NW * 64, DKDV_PS_LDS, s, a); break;
+    default: launch_attn<attn_bwd_dkdv_kernel<T, D>>(attn_grid(a, a.Nk, 128), NT, dkdv_lds<T, D>(), s, a); break;
   }
-  if (!dq_done) hipLaunchKernelGGL((attn_bwd_dq_kernel<T, D>), gq, dim3(NT), lds_q, s, a);
-  hipLaunchKernelGGL((attn_bwd_dkdv_kernel<T, D>), gk, dim3(NT), lds_kv, s, a);
   return 0;
 }
 

@@ -64,8 +64,8 @@ template <typename T> FK_DEV float sigmoid_f(float x) {
 }
 
 // Epilogue shared by the NT kernels: acc are C^T tiles (lane = output row m, registers = 4 consecutive n).
-// EPI < 0: every fused mode decided at run time (one code body); EPI = 0 plain / bias / residual, 1 SwiGLU forward, 2 SwiGLU backward,
-// 3 RoPE (+ bias): the same code with the other modes compiled out (the 256 x 256 kernel is instantiated per mode).
+// EPI < 0: every fused mode decided at run time (one code body: the double-buffered, short-ring and staged kernels); EPI = 0 plain / bias /
+// residual, 1 SwiGLU forward, 2 SwiGLU backward, 3 RoPE (+ bias): the same code with the other modes compiled out (the ring kernels, with_epi).
 template <typename T, typename TO, bool VEC_ONLY = false, int NI = 2, bool PRE_RES = false, int EPI = -1>
 FK_DEV void nt_epilogue(const NtArgs& p, f32x16 (&acc)[NI][2], char* stg, int mrow0, int ncol0, int lane, bool sync) {
   // acc = one wave's (32 NI) x 64 sub-tile whose top-left output element is (mrow0, ncol0); stg = that wave's 8 NI KiB of LDS
@@ -1095,12 +1095,9 @@ template <typename TO> static void launch_nt_route(NtRoute route, const NtArgs& 
   const dim3 grid((unsigned)nwg), block(NTHREADS), block8(512);
   auto tiles256 = [&](int bn) { return dim3(persistent_grid(fk_cdiv(M, 256) * fk_cdiv(N, bn))); };   // persistent grid over 256 x bn tiles
   switch (route) {
-    case NT_RING2: {
-      static const bool generic = getenv("FK_NT_RING2_GENERIC") != nullptr;    // tuning knob: one epilogue body for every mode
-      if (generic) fk_launch_lds<gemm_nt_ring2_kernel<TO, -1>>(tiles256(256), block8, R2_LDS, s, p);
-      else with_epi(p, [&](auto epi) { fk_launch_lds<gemm_nt_ring2_kernel<TO, decltype(epi)::value>>(tiles256(256), block8, R2_LDS, s, p); });
+    case NT_RING2:
+      with_epi(p, [&](auto epi) { fk_launch_lds<gemm_nt_ring2_kernel<TO, decltype(epi)::value>>(tiles256(256), block8, R2_LDS, s, p); });
       break;
-    }
     case NT_RING192: fk_launch_lds<gemm_nt_ring192_kernel<TO, 0>>(tiles256(192), block8, R192_LDS, s, p); break;
     case NT_RING128:
       with_epi(p, [&](auto epi) { fk_launch_lds<gemm_nt_ring_kernel<TO, 128, 128, 3, decltype(epi)::value>>(tiles256(128), block8, Ring<128, 128, 3>::LDS, s, p); });
@@ -1576,15 +1573,14 @@ bool tn_big_ok(int64_t M, int64_t N1, int64_t N2, int dtype) {
 // cfg2 shapes: 3072 x 384 -7 %, 1152 x 384 and 384 x 1536 +-1 %, 384 x 384 +10 % (more split slabs, 25 % padding in the B requests) -> only
 // for N1 >= 2048.
 int tn_big_tb(int64_t N1, int64_t N2) {
-  static const bool no192 = getenv("FK_TN_NO_192") != nullptr;
   if (N2 % TG_B != 0) return 192;
-  return (N2 % 192 == 0 && N1 >= 2048 && !no192) ? 192 : TG_B;
+  return (N2 % 192 == 0 && N1 >= 2048) ? 192 : TG_B;
 }
 int tn_big_splits(int64_t M, int64_t N1, int64_t N2) {
   const int64_t tiles = (N1 / TG_A) * (N2 / tn_big_tb(N1, N2));
   // one wave of blocks, one block per CU; FK_TN_SPLIT_MULT = m (default 1) cuts the contraction m times finer: m waves of shorter units,
   // so that a CU another kernel holds (a collective's channel) costs the launch 1/m of a unit, at the price of m times the slab traffic
-  // (bench.py's launcher sets 2 for data-parallel runs; tools/occupant_probe.py measures both sides)
+  // (nothing sets it by default: no multi-rank run has been measured; tools/occupant_probe.py measures both sides on one GPU)
   static const int mult = [] { const char* e = getenv("FK_TN_SPLIT_MULT"); const int v = e ? atoi(e) : 1; return v < 1 ? 1 : (v > 8 ? 8 : v); }();
   int64_t want = 256 / tiles * mult;
   const int64_t maxs = M / 512;                             // >= 512 rows (16 k-stages) per split
@@ -1615,22 +1611,19 @@ struct RopeSpec { const float* table; int64_t bs; int T, off, D, cols; int qcols
 static NtRoute nt_route(int64_t M, int64_t N, int64_t K, int dtype, bool vec_epi, int mode, bool has_rope) {
   const int64_t nwg = fk_cdiv(M, BM) * fk_cdiv(N, BN);
   const bool glds = dtype == FK_BF16 && (K % 64 == 0);
-  static const bool no_ring = getenv("FK_NT_NO_RING") != nullptr;       // tuning knob: the double-buffered kernels instead
   // the persistent ring kernels want several 256-row tiles per CU; below half a tile per CU (SimpleMAE's 4800 visible-token rows at
   // B = 32) the 128 x 128 kernels fill the chip better: graphed cfg5 step 5.9 -> 5.6 ms (profiles/r03_g_other_configs.txt)
   // (read per call, not cached: the GPU suite switches it to send small shapes through the ring kernels)
   const char* ring_min_env = getenv("FK_NT_RING_MIN_TILES");
   const int ring_min = ring_min_env ? atoi(ring_min_env) : 128;
-  const bool wide = glds && M >= 4096 && vec_epi && !no_ring && fk_cdiv(M, 256) * fk_cdiv(N, 256) >= ring_min;
+  const bool wide = glds && M >= 4096 && vec_epi && fk_cdiv(M, 256) * fk_cdiv(N, 256) >= ring_min;
   // 256 x 256 tiles, split A/B rings (N = 1152: the last column tile is half empty, still 4 % faster than 256 x 128 tiles)
   if (wide && (N % 256 == 0 || (N % 128 == 0 && N >= 1024))) return NT_RING2;
-  static const bool no_192 = getenv("FK_NT_NO_192") != nullptr;        // tuning knob: 256 x 128 tiles for N = 384 / 768 too
-  if (wide && N % 192 == 0 && N % 256 != 0 && N <= 768 && mode == 0 && !has_rope && !no_192) return NT_RING192;   // N = 384: two 192-column tiles
+  if (wide && N % 192 == 0 && N % 256 != 0 && N <= 768 && mode == 0 && !has_rope) return NT_RING192;   // N = 384: two 192-column tiles
   if (wide && N % 128 == 0) return NT_RING128;           // N = 128 / 384 / 640 / 896: 256 x 128 ring
   // large projections: 256 x 256 tiles, 1 block per CU (the 256x128 variant measured slower than 128x128 at N = 384)
   if (glds && M >= 4096 && N % 256 == 0 && vec_epi) return NT_BIG;
-  static const bool no_g4 = getenv("FK_NT_NO_GLDS4") != nullptr;       // tuning knob
-  if (glds && nwg <= 256 && !no_g4) return NT_GLDS4;     // at most one tile per CU: the short-latency ring
+  if (glds && nwg <= 256) return NT_GLDS4;     // at most one tile per CU: the short-latency ring
   return glds ? NT_GLDS : NT_STAGED;
 }
 

@@ -29,7 +29,6 @@
 // Built WITHOUT -amdgpu-mfma-vgpr-form (frankenstein_amd/build.py): the 208 accumulator registers live in the AGPR half, which is what
 // lets a wave keep 96 + 192 + 16 stationary registers at one wave per SIMD.
 #include "fk_common.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -285,7 +284,7 @@ __device__ unsigned long long mf_stamp_acc[16];
 #define MF_ST_FLUSH(lane)
 #endif
 
-// Ragged M, and everything with FK_MLP_BWD_ASM=0: the chain as hipcc schedules it.
+// Ragged M (and dh13 blocks past 32-bit byte offsets): the chain as hipcc schedules it.
 __global__ __launch_bounds__(MF_NW * 64, 1) void mlp_bwd_fused_kernel(MlpBwdArgs p) {
   using T = bf16_t;
   const LaneIds L;
@@ -367,7 +366,7 @@ __global__ __launch_bounds__(MF_NW * 64, 1) void mlp_bwd_fused_kernel(MlpBwdArgs
 //              and h13 tile(c + 2) requests, the barrier         48 MFMAs: mlpb_step_asm (tools/gen/gen_mlpb_asm.py -> mlp_bwd_asm.inc),
 //              every gap filled to the same issue budget
 //   Same products and summation order, same arithmetic instruction for instruction: dh13 and dx are the bits of the kernel above.
-//   Whole 128-token tiles only (M % 128 == 0); the launcher keeps the kernel above for the rest (and FK_MLP_BWD_ASM=0 for everything).
+//   Whole 128-token tiles only (M % 128 == 0); the launcher keeps the kernel above for the rest.
 //   The prologue (chunk 0's first product and derivative) and the tail (the last chunk's second product, the dx epilogue) are the shared
 //   blocks above; A(c) is written out here, because barrier B(c) and the stream's first operands sit INSIDE its last group.
 //
@@ -831,7 +830,7 @@ __global__ __launch_bounds__(MU_NW * 64, 2) void qkv_rope_fused_kernel(QkvArgs p
 // the token-on-the-lane form of fk_gemm_nt_rope (called from gemm.hip's entry point)
 // One 8-wave workgroup of 256 tokens per CU at a time: the launch runs in rounds of 256 workgroups, so its time is a step function of M
 // (150 / 293 / 460 us at <= 65 536 / 131 072 / 196 608 rows for the up-projection) where the tiled kernels' is linear.  Measured over
-// M = 19 200 ... 196 608 (tools/mlp_size_sweep.py, profiles/r04_mlp_size_sweep.txt): these kernels win wherever the last round is at least
+// M = 19 200 ... 196 608 (profiles/r04_mlp_size_sweep.txt): these kernels win wherever the last round is at least
 // ~40 % full, i.e. the grid fills >= 70 % of its rounds (49 152: 0.75 wins; 38 400 and 76 800: 0.59 lose by 5-12 %).
 static bool mu_grid_fills(int64_t M) {
   const int64_t wg = fk_cdiv(M, MU_TOK), rounds = fk_cdiv(wg, 256);
@@ -839,9 +838,8 @@ static bool mu_grid_fills(int64_t M) {
 }
 bool fk_qkv_rope_fused_ok(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, const void* bias, int64_t T, int64_t D, int64_t rot_cols,
                           int64_t q_cols, int dtype) {
-  static const bool off = getenv("FK_QKV_FUSED") != nullptr && getenv("FK_QKV_FUSED")[0] == '0';
   // anything launch_nt would refuse (an empty problem, a leading dimension shorter than its row) is left to it: this kernel has no checks of its own
-  return !off && dtype == FK_BF16 && K == MF_D && D == 64 && N > 0 && N < (1LL << 31) && N % 64 == 0 && rot_cols % 64 == 0 && q_cols % 64 == 0 && rot_cols <= N && !bias &&
+  return dtype == FK_BF16 && K == MF_D && D == 64 && N > 0 && N < (1LL << 31) && N % 64 == 0 && rot_cols % 64 == 0 && q_cols % 64 == 0 && rot_cols <= N && !bias &&
          mu_grid_fills(M) && M < (1LL << 31) && T > 0 && M % T == 0 && lda % 8 == 0 && ldb % 8 == 0 && ldc % 8 == 0 && lda >= K && ldb >= K && ldc >= N &&
          64 * ldb * 2 < (1LL << 32);
 }
@@ -856,8 +854,7 @@ int fk_qkv_rope_fused_launch(const void* A, int64_t lda, const void* W, int64_t 
 
 // the token-on-the-lane form of fk_gemm_nt_swiglu for the shapes it is built for (called from gemm.hip's entry point)
 bool fk_mlp_up_fused_ok(int64_t M, int64_t H, int64_t K, int64_t lda, int64_t ldb, int64_t ldh, int64_t ldg, int dtype) {
-  static const bool off = getenv("FK_MLP_UP_FUSED") != nullptr && getenv("FK_MLP_UP_FUSED")[0] == '0';
-  return !off && dtype == FK_BF16 && K == MF_D && H > 0 && H < (1LL << 30) && H % 32 == 0 && mu_grid_fills(M) && M < (1LL << 31) && lda % 8 == 0 && ldb % 8 == 0 &&
+  return dtype == FK_BF16 && K == MF_D && H > 0 && H < (1LL << 30) && H % 32 == 0 && mu_grid_fills(M) && M < (1LL << 31) && lda % 8 == 0 && ldb % 8 == 0 &&
          ldh % 8 == 0 && ldg % 8 == 0 && lda >= K && ldb >= K && ldh >= 2 * H && ldg >= H && 64 * ldb * 2 < (1LL << 32);      // the rest: launch_nt's refusals
 }
 int fk_mlp_up_fused_launch(const void* A, int64_t lda, const void* W13, int64_t ldb, void* H13, int64_t ldh, void* G, int64_t ldg, int64_t M, int64_t H,
@@ -893,9 +890,8 @@ extern "C" int fk_mlp_bwd_fused(const void* dY, int64_t lddy, const void* W2T, i
                "fk_mlp_bwd_fused: pointers must be 16-byte aligned");
   MlpBwdArgs a{(const bf16_t*)dY, (const bf16_t*)W2T, (const bf16_t*)H13, (const bf16_t*)W13T, (bf16_t*)dH13, (bf16_t*)dX,
                lddy, ldw2t, ldh, ldw13t, lddh, lddx, (int)M, (int)H};
-  static const bool asm_off = getenv("FK_MLP_BWD_ASM") != nullptr && getenv("FK_MLP_BWD_ASM")[0] == '0';
   // whole 128-token tiles, and the dh13 rows addressable with 32-bit byte offsets from a per-chunk scalar base: the generated-stream kernel
-  if (!asm_off && M % MF_TOK == 0 && M * lddh * 2 < (1LL << 32))
+  if (M % MF_TOK == 0 && M * lddh * 2 < (1LL << 32))
     fk_launch_lds<mlp_bwd_fused_asm_kernel>(dim3((unsigned)(M / MF_TOK)), dim3(MF_NW * 64), MF_LDS, (hipStream_t)stream, a);
   else
     fk_launch_lds<mlp_bwd_fused_kernel>(dim3((unsigned)fk_cdiv(M, MF_TOK)), dim3(MF_NW * 64), MF_LDS, (hipStream_t)stream, a);

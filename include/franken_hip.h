@@ -172,8 +172,8 @@ int fk_attn_bwd_dropout(const void* Q, const void* K, const void* V, const void*
  *   rope_table is given to the backward).  Writes the forward, dQ and dK/dV kernels (any of the three pointers may be NULL):
  *   GENERIC = the kernels for every dtype / head_dim / mask; FEWQ = the waves split the keys (Nq <= 32, Nk >= 1024, no mask, no dropout;
  *   the dQ form also needs no RoPE table); PS = the FK_ATTN_Q_PRESCALED tile loops; ASM = the generated instruction streams (every tile
- *   fully visible and aligned); DKDVW_ASM = the stream with 64 keys per wave.  Follows FK_ATTN_NO_FEWQ / FK_ATTN_NO_DKDVW exactly as the
- *   launch does.  Returns FK_OK, or FK_EINVAL for a problem the entry points refuse.                                                   */
+ *   fully visible and aligned); DKDVW_ASM = the stream with 64 keys per wave.  Returns FK_OK, or FK_EINVAL for a problem the entry
+ *   points refuse.                                                                                                                    */
 enum { FK_ATTN_FWD_GENERIC = 0, FK_ATTN_FWD_FEWQ = 1, FK_ATTN_FWD_PS = 2, FK_ATTN_FWD_ASM = 3 };
 enum { FK_ATTN_DQ_GENERIC = 0, FK_ATTN_DQ_FEWQ = 1, FK_ATTN_DQ_PS = 2, FK_ATTN_DQ_ASM = 3 };
 enum { FK_ATTN_DKDV_GENERIC = 0, FK_ATTN_DKDV_PS = 1, FK_ATTN_DKDV_ASM = 2, FK_ATTN_DKDVW_ASM = 3 };

@@ -472,3 +472,20 @@ def test_gpt_from_pretrained_maps_a_hugging_face_state_dict(monkeypatch):
         assert torch.equal(sd[k], hf_sd[k])
     with pytest.raises(AssertionError):
         g2.GPT.from_pretrained("gpt2", dict(bias=False))              # only dropout may be overridden (models/gpt2_model.py:233)
+
+
+def test_environment_switches_read_by_the_library_are_the_documented_ones():
+    """Every FK_* variable the library reads (getenv in csrc, os.environ in the package) is named in INTEGRATION.md's environment
+    paragraph, and that paragraph names no other: a switch cannot come or go without its documentation."""
+    import re
+    from pathlib import Path
+    root = Path(__file__).resolve().parents[1]
+    read = set()
+    for f in [*(root / "frankenstein_amd" / "csrc").glob("*.hip"), *(root / "frankenstein_amd" / "csrc").glob("*.h")]:
+        read |= set(re.findall(r'getenv\(\s*"(FK_\w+)"', f.read_text()))
+    for f in (root / "frankenstein_amd").rglob("*.py"):
+        read |= set(re.findall(r'os\.environ(?:\.get|\.setdefault|\.pop)?\s*[(\[]\s*["\'](FK_\w+)', f.read_text()))
+    paragraphs = [p for p in (root / "INTEGRATION.md").read_text().split("\n\n") if p.startswith("Environment (")]
+    assert len(paragraphs) == 1
+    documented = set(re.findall(r"\bFK_[A-Z0-9_]+\b", paragraphs[0]))
+    assert read and read == documented, (sorted(read - documented), sorted(documented - read))

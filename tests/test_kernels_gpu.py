@@ -1249,12 +1249,18 @@ def test_head_ce_fused_kernels(K, dtype, rows, V, Kd, bias):
     close(dw, want_dw, dtype, atol32=1e-5, rtol32=1e-4, atol16=2e-3 * float(want_dw.abs().max()) + 1e-6, rtol16=3e-2)
 
 
+def _replicate(K, x, S):
+    """x [B, ...] -> [B * S, ...] with every sample repeated S times (one gather launch; queries / outputs of split-key attention)"""
+    B = x.shape[0]
+    idx = torch.zeros((B, S), dtype=torch.int64, device=x.device)
+    return K.gather_rows(x.reshape(B, 1, -1), idx).view(B * S, *x.shape[1:])
+
+
 @pytest.mark.parametrize("dtype", DT)
 def test_split_key_attention_equals_the_single_pass(K, dtype):
     """fk_attn_combine: a few queries against a long unmasked context (perceiver read-out, models/brainformer.py:204-215) with the keys
     split into S ranges folded into the batch dimension — forward output / LSE and all three gradients equal the unsplit kernels
-    (the way engine.CrossAttnBranch runs it), and the fp32 result matches torch's SDPA."""
-    from frankenstein_amd import engine as E
+    (the way a caller of the public entry point runs it), and the fp32 result matches torch's SDPA."""
     B, T, H, D, Nc, S = 2, 32, 4, 64, 2048, 8
     HD = H * D
     qf = q(rnd(B, T, H, D, seed=1), dtype)
@@ -1266,7 +1272,7 @@ def test_split_key_attention_equals_the_single_pass(K, dtype):
     o1, l1 = K.attn_fwd(qd, k_, v_)
     kvs = kv.view(B * S, Nc // S, 2 * HD)
     ks, vs = kvs[..., :HD].unflatten(-1, (H, D)), kvs[..., HD:].unflatten(-1, (H, D))
-    o_s, l_s = K.attn_fwd(E._replicate(qd, S), ks, vs)
+    o_s, l_s = K.attn_fwd(_replicate(K, qd, S), ks, vs)
     o2, l2 = K.attn_combine(o_s.view(B, S, T, H, D), l_s.view(B, S, H, T))
     close(o2, o1, dtype, atol32=2e-6, rtol32=1e-5, atol16=1e-2)
     torch.testing.assert_close(l2, l1, atol=1e-5, rtol=1e-5)
@@ -1281,7 +1287,7 @@ def test_split_key_attention_equals_the_single_pass(K, dtype):
     dkv2 = torch.empty_like(kv)
     d2 = dkv2.view(B * S, Nc // S, 2 * HD)
     dq_s = torch.empty((B * S, T, H, D), dtype=dtype, device="cuda")
-    K.attn_bwd(E._replicate(qd, S), ks, vs, E._replicate(o1, S), E._replicate(dod, S), E._replicate(l1, S), dq_s,
+    K.attn_bwd(_replicate(K, qd, S), ks, vs, _replicate(K, o1, S), _replicate(K, dod, S), _replicate(K, l1, S), dq_s,
                d2[..., :HD].unflatten(-1, (H, D)), d2[..., HD:].unflatten(-1, (H, D)))
     dq2 = K.attn_combine(dq_s.view(B, S, T, H, D))[0]
     close(dq2, dq1, dtype, atol32=2e-6, rtol32=1e-4, atol16=2e-2 * float(dq1.float().abs().max()))

@@ -1,4 +1,4 @@
-"""Shader clock during the cfg2 attention launches: -DFK_STAMP build (tools/build_variant.sh stamp frankenstein_amd/csrc/attention.hip
+"""Shader clock during the cfg2 attention launches: -DFK_STAMP build (tools/build_variant.py stamp attention.hip
 -DFK_STAMP), FRANKEN_HIP_LIB=.../lib_stamp.so python tools/clock_attn.py.  Sum of wave lifetimes (s_memtime) / (wave slots x event time)."""
 import sys, os, ctypes
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

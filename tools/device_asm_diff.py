@@ -20,10 +20,11 @@ FIGURES = ("VGPRs", "TotalSGPRs", "ScratchSize", "VGPRs Spill", "SGPRs Spill", "
 
 
 def functions(asm: str) -> dict:
-    """symbol -> its lines from the label to .Lfunc_end, the function's ordinal in local labels masked"""
+    """symbol -> its lines from the label to .Lfunc_end, the function's ordinal in local labels masked (and the padding between a label
+    and its loop comment, which depends on the ordinal's width)"""
     names = set(re.findall(r"^\s*\.type\s+(\S+),@function", asm, re.M))
     out, cur = {}, None
-    for line in re.sub(r"BB\d+_", "BB_", asm).splitlines():
+    for line in re.sub(r"(?m)^(\.LBB_\d+:) +;", r"\1 ;", re.sub(r"BB\d+_", "BB_", asm)).splitlines():
         m = re.match(r"^([A-Za-z_][\w$.]*):", line)
         if m and m.group(1) in names:
             cur = out.setdefault(m.group(1), [])

@@ -1,4 +1,4 @@
-"""Cycle breakdown of the dK/dV attention kernel from an -DFK_STAMP build (tools/build_variant.sh stamp <src> -DFK_STAMP):
+"""Cycle breakdown of the dK/dV attention kernel from an -DFK_STAMP build (tools/build_variant.py stamp attention.hip -DFK_STAMP):
 FRANKEN_HIP_LIB=frankenstein_amd/variants/lib_stamp.so python tools/stamp_attn.py"""
 import sys, os, ctypes
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
