@@ -100,6 +100,11 @@ SIGNATURES = {
     "fk_head_ce_fwd": (_int, [_p, _i64, _p, _i64, _i64, _p, _p, _p, _p, _p, _i64, _i64, _i64, _int, _p, _sz, _p]),
     "fk_head_ce_bwd": (_int, [_p, _i64, _p, _i64, _i64, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _p, _i64, _i64, _i64, _i64, _int, _p]),
     "fk_transpose2d": (_int, [_p, _i64, _p, _i64, _i64, _i64, _int, _p]),
+    "fk_ctc_route": (_int, [_i64]),
+    "fk_ctc_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "fk_ctc_loss_fwd": (_int, [_p, _i64, _i64, _p, _i64, _p, _p, _i64, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _int, _int, _int, _int, _p, _sz, _p]),
+    "fk_ctc_loss_bwd": (_int, [_p, _i64, _i64, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _int, _int, _int, _p, _sz, _p]),
+    "fk_ctc_collapse": (_int, [_p, _i64, _p, _p, _i64, _p, _i64, _i64, _i64, _i64, _p]),
     "fk_ce_workspace_bytes": (_sz, [_i64]),
     "fk_ce_loss_fwd": (_int, [_p, _i64, _p, _p, _p, _i64, _i64, _i64, _int, _p, _sz, _p]),
     "fk_ce_loss_bwd": (_int, [_p, _i64, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _int, _p]),
@@ -117,6 +122,8 @@ SIGNATURES = {
 ADAMW_MAX_SLOTS, GRAD_SUMSQ_MAX_BLOCKS = 16, 1024
 VQ_CHAIN, VQ_FUSED = 0, 1                                                             # fk_vq_route
 VQ_EMA, VQ_KMEANS = 0, 1                                                              # fk_vq_codebook_update modes
+CTC_WAVE, CTC_LDS = 0, 1                                                             # fk_ctc_route
+CTC_NONE, CTC_SUM, CTC_MEAN = 0, 1, 2                                                 # fk_ctc_loss_* reductions
 VQ_ROWS = 32                                                                          # data rows per workgroup of fk_vq_assign
 
 

@@ -800,6 +800,45 @@ def cross_entropy(logits: Tensor, targets: Tensor, ignore_index: int = -100) -> 
     return CrossEntropy.apply(lg, targets.reshape(-1), ignore_index)
 
 
+class CTCLoss(torch.autograd.Function):
+    """F.ctc_loss over logits [B, T, C] with the log-softmax folded in (csrc/ctc.hip): alpha and beta run side by side in the forward, the
+    backward is one row-parallel launch.  'sum' / 'mean' return a scalar, 'none' the [B] losses.  Nothing here waits for the host."""
+
+    @staticmethod
+    def forward(ctx, logits, targets, input_lengths, target_lengths, blank, reduction, zero_infinity, pad_value):
+        st = K.ctc_loss_fwd(logits, targets, input_lengths, target_lengths, blank, reduction, zero_infinity, pad_value,
+                            want_grad=ctx.needs_input_grad[0])
+        ctx.st = st
+        ctx.save_for_backward(logits)
+        return st.nll if reduction == "none" else st.loss2[0]
+
+    @staticmethod
+    def backward(ctx, gout):
+        (logits,) = ctx.saved_tensors
+        g = gout.reshape(-1).float().contiguous()
+        return K.ctc_loss_bwd(logits, ctx.st, g), None, None, None, None, None, None, None
+
+
+def ctc_loss(logits: Tensor, targets: Tensor, input_lengths: Optional[Tensor] = None, target_lengths: Optional[Tensor] = None, blank: int = 0,
+             reduction: str = "mean", zero_infinity: bool = False, pad_value: int = -100) -> Tensor:
+    """logits [B, T, C] (fp32 / bf16, batch first, NOT log-softmaxed), targets int64 [B, Lmax].  target_lengths None: a target ends at its
+    first `pad_value` (the -100 label padding of utils.data_utils.pad_token_list), counted on the device; input_lengths None: T frames
+    each.  Up to 255 labels per target."""
+    if logits.stride(-1) != 1:
+        logits = logits.contiguous()
+    if targets.dim() == 2 and targets.shape[1] > 0 and targets.stride(1) != 1:
+        targets = targets.contiguous()
+    return CTCLoss.apply(logits, targets, input_lengths, target_lengths, blank, reduction, zero_infinity, pad_value)
+
+
+@torch.no_grad()
+def ctc_greedy_decode(logits: Tensor, input_lengths: Optional[Tensor] = None, blank: int = 0, pad: int = -100):
+    """Best-path decoding: per-frame argmax, repeats merged, blanks dropped -> (ids int64 [B, T] padded with `pad`, lengths int64 [B])."""
+    B, T, Cn = logits.shape
+    lg = logits.reshape(B * T, Cn) if logits.is_contiguous() else logits.contiguous().view(B * T, Cn)
+    return K.ctc_collapse(K.argmax_rows(lg).view(B, T), input_lengths, blank, pad)
+
+
 class HeadCrossEntropy(torch.autograd.Function):
     """loss = mean CE(Linear([LN](x)), targets) over the rows whose target != ignore_index, WITHOUT a [rows, V] tensor in either
     direction: lm_head + F.cross_entropy of models/gpt2_model.py:205-210 and the `to_words` head of the notebook CE BrainFormer, used when

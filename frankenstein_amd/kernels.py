@@ -1107,6 +1107,97 @@ def ce_loss_bwd(logits: Tensor, targets: Tensor, lse: Tensor, loss2: Tensor, gou
     return dlogits
 
 
+# ------------------------------------------------------------------------------------------- CTC (csrc/ctc.hip)
+CTC_ROUTE_NAMES = {_lib.CTC_WAVE: "CTC_WAVE", _lib.CTC_LDS: "CTC_LDS"}
+CTC_REDUCTIONS = {"none": _lib.CTC_NONE, "sum": _lib.CTC_SUM, "mean": _lib.CTC_MEAN}
+
+
+def ctc_route(Lmax: int) -> int:
+    """The lattice kernel a target width takes (fk_ctc_route; host-side query, no launch): CTC_WAVE up to 31 labels, CTC_LDS up to 255;
+    raises beyond."""
+    rc = lib().fk_ctc_route(Lmax)
+    _lib.check(0 if rc >= 0 else rc, "fk_ctc_route")
+    return rc
+
+
+class CtcState:
+    """What one forward leaves for the backward (and for tests): nll [B] and loss2 = {reduced loss, B}, row_lse [B, T], the workspace and,
+    with the lattice, alpha / beta as fp32 [B, T, S_pad] views into it."""
+    __slots__ = ("nll", "loss2", "row_lse", "ws", "ws_bytes", "alpha", "beta", "shape", "blank", "reduction", "zero_infinity")
+
+
+def _ctc_lengths(t: Optional[Tensor], B: int, device) -> Optional[Tensor]:
+    if t is None:
+        return None
+    assert t.dtype == torch.int64 and t.shape == (B,) and t.device == device
+    return t.contiguous()
+
+
+def ctc_loss_fwd(logits: Tensor, targets: Tensor, input_lengths: Optional[Tensor] = None, target_lengths: Optional[Tensor] = None,
+                 blank: int = 0, reduction: str = "mean", zero_infinity: bool = False, pad_value: int = -100, want_grad: bool = True,
+                 want_lattice: bool = False) -> CtcState:
+    """logits [B, T, C] (fp32 / bf16, unit column stride, any row and batch stride), targets int64 [B, Lmax] (unit column stride) ->
+    CtcState.  want_grad runs the beta recursion beside the alpha recursion and keeps both lattices for ctc_loss_bwd; want_lattice also
+    exposes them (state.alpha, state.beta; tests)."""
+    assert logits.dim() == 3 and logits.stride(2) == 1 and targets.dim() == 2 and targets.dtype == torch.int64
+    B, T, Cn = logits.shape
+    Lmax = targets.shape[1]
+    assert targets.shape[0] == B and (Lmax == 0 or targets.stride(1) == 1)
+    lattice = want_grad or want_lattice
+    st = CtcState()
+    dev = logits.device
+    st.nll = torch.empty(B, dtype=torch.float32, device=dev)
+    st.loss2 = torch.empty(2, dtype=torch.float32, device=dev)
+    st.row_lse = torch.empty((B, T), dtype=torch.float32, device=dev)
+    st.ws_bytes = lib().fk_ctc_workspace_bytes(B, T if lattice else 0, Lmax)
+    st.ws, _ = _ws(st.ws_bytes, dev)
+    st.shape, st.blank, st.reduction, st.zero_infinity = (B, T, Cn, Lmax), blank, CTC_REDUCTIONS[reduction], bool(zero_infinity)
+    il, tl = _ctc_lengths(input_lengths, B, dev), _ctc_lengths(target_lengths, B, dev)
+    with _timed("ctc_loss_fwd"):
+        call("fk_ctc_loss_fwd", logits.data_ptr(), logits.stride(0), logits.stride(1), targets.data_ptr() if Lmax else None,
+             targets.stride(0) if Lmax else 0, _ptr(il), _ptr(tl), pad_value, st.nll.data_ptr(), st.loss2.data_ptr(), st.row_lse.data_ptr(),
+             B, T, Cn, Lmax, blank, st.reduction, int(st.zero_infinity), int(lattice), fk_dtype(logits), _ptr(st.ws), st.ws_bytes, _stream())
+    st.alpha = st.beta = None
+    if want_lattice:
+        s_pad = (2 * Lmax + 1 + 63) // 64 * 64
+        n = B * T * s_pad
+        lat = st.ws[st.ws_bytes - 2 * _ctc_a256(4 * n):].view(torch.float32)
+        st.alpha, st.beta = lat[:n].view(B, T, s_pad), lat[_ctc_a256(4 * n) // 4:][:n].view(B, T, s_pad)
+    return st
+
+
+def _ctc_a256(nbytes: int) -> int:
+    return (nbytes + 255) // 256 * 256
+
+
+def ctc_loss_bwd(logits: Tensor, st: CtcState, gout: Tensor, dlogits: Optional[Tensor] = None) -> Tensor:
+    """dlogits (logits' dtype) from the state of a forward that ran with want_grad; gout: fp32 device tensor, one element for 'sum' /
+    'mean', [B] for 'none' (the reduction's own factor is applied by the kernel)."""
+    B, T, Cn, Lmax = st.shape
+    assert tuple(logits.shape) == (B, T, Cn) and logits.stride(2) == 1
+    assert gout.dtype == torch.float32 and gout.is_contiguous() and gout.numel() == (B if st.reduction == _lib.CTC_NONE else 1)
+    if dlogits is None:
+        dlogits = torch.empty((B, T, Cn), dtype=logits.dtype, device=logits.device)
+    assert dlogits.shape == logits.shape and dlogits.stride(2) == 1 and dlogits.dtype == logits.dtype
+    with _timed("ctc_loss_bwd"):
+        call("fk_ctc_loss_bwd", logits.data_ptr(), logits.stride(0), logits.stride(1), st.row_lse.data_ptr(), gout.data_ptr(),
+             dlogits.data_ptr(), dlogits.stride(0), dlogits.stride(1), B, T, Cn, Lmax, st.blank, st.reduction, int(st.zero_infinity),
+             fk_dtype(logits), st.ws.data_ptr(), st.ws_bytes, _stream())
+    return dlogits
+
+
+def ctc_collapse(argmax: Tensor, input_lengths: Optional[Tensor] = None, blank: int = 0, pad: int = -100) -> Tuple[Tensor, Tensor]:
+    """Per-frame argmax int64 [B, T] -> (ids int64 [B, T] padded with `pad`, lengths int64 [B]): repeats merged, blanks dropped."""
+    assert argmax.dim() == 2 and argmax.dtype == torch.int64 and argmax.stride(1) == 1
+    B, T = argmax.shape
+    il = _ctc_lengths(input_lengths, B, argmax.device)
+    ids = torch.empty((B, T), dtype=torch.int64, device=argmax.device)
+    lengths = torch.empty(B, dtype=torch.int64, device=argmax.device)
+    call("fk_ctc_collapse", argmax.data_ptr(), argmax.stride(0), _ptr(il), ids.data_ptr(), ids.stride(0), lengths.data_ptr(), B, T, blank, pad,
+         _stream())
+    return ids, lengths
+
+
 class CeChunkState:
     """per-row running statistics of the chunked cross entropy (fk_ce_chunk_*)"""
 

@@ -3,6 +3,7 @@
   BrainEncoder   notebooks_trainer/franky_baseline_gpt2.ipynb cell 3  (encoder + perceiver -> ``to_words`` features)
   Franky         notebooks_trainer/franky_baseline_gpt2.ipynb cell 4  (brain features as GPT prefix, CE loss)
   BrainFormerCE  notebooks_trainer/train_brainformer.ipynb cell 3     (``BrainFormer`` there: vocab head + CE)
+  BrainFormerCTC no counterpart in the reference: the same read-out under a CTC loss, with greedy decoding
 
 Same constructor / forward signatures and state-dict keys as the notebook classes, so a notebook can
 ``from frankenstein_amd.models.notebook_models import BrainEncoder, Franky`` instead of defining them inline.
@@ -44,6 +45,36 @@ class BrainFormerCE(_FileBrainFormer):
         if targets is None:
             return None, logits
         return E.cross_entropy(logits, targets, -100), logits
+
+
+class BrainFormerCTC(_FileBrainFormer):
+    """The read-out of BrainFormerCE under a CTC loss: the `n_output_tokens` read-out tokens are the time axis, `output_dim` is the number
+    of classes with the blank among them.  The blank defaults to the LAST class (output_dim - 1), so GPT-2 BPE targets keep their ids
+    (50258 classes, blank 50257) and a phoneme inventory keeps its numbering.
+
+    forward(x, targets) -> (CTC loss, logits [B, n_output_tokens, output_dim]); targets int64 [B, Lmax] padded with -100, at most 255
+    labels.  The loss is the mean of torch's F.ctc_loss with zero_infinity=True: a sentence that does not fit into the read-out (more
+    labels plus adjacent repeats than read-out tokens) contributes 0 and no gradient instead of turning the run into inf.
+    decode(x) -> (ids int64 [B, n_output_tokens] padded with -100, lengths int64 [B]): the best path, repeats merged and blanks dropped.
+    utils.metrics.token_error_rate(targets, ids) of that result is the phoneme / token error rate."""
+    config = Config
+    head_name = 'to_words'
+
+    def __init__(self, config: Config, blank=None):
+        super().__init__(config)
+        self.blank = config.output_dim - 1 if blank is None else int(blank)
+        if not 0 <= self.blank < config.output_dim:
+            raise ValueError(f"blank = {self.blank} outside [0, output_dim = {config.output_dim})")
+
+    def forward(self, x, targets=None, date_info=None):
+        logits = self.features(x)
+        if targets is None:
+            return None, logits
+        return E.ctc_loss(logits, targets, blank=self.blank, reduction='mean', zero_infinity=True, pad_value=-100), logits
+
+    @torch.no_grad()
+    def decode(self, x):
+        return E.ctc_greedy_decode(self.features(x), blank=self.blank, pad=-100)
 
 
 class Franky(nn.Module):

@@ -503,6 +503,48 @@ int fk_head_ce_bwd(const void* H, int64_t ldh, const void* W, int64_t ldw, int64
                    int64_t vpad, float* dbpart, int64_t rows, int64_t V, int64_t K, int64_t ignore_index, int dtype, void* stream);
 int fk_transpose2d(const void* src, int64_t lds, void* dst, int64_t ldd, int64_t rows, int64_t cols, int dtype, void* stream);
 
+/* ---- CTC (csrc/ctc.hip): F.ctc_loss(log_softmax(logits, -1).transpose(0, 1), targets, input_lengths, target_lengths, blank, reduction,
+ *      zero_infinity) with the log-softmax folded in, its gradient, and the greedy collapse.  The reference has no CTC: the yardstick is
+ *      torch's float64 CPU loss (tests/ctc_ref.py).
+ *   logits [B, T, C] fp32 / bf16 (batch stride ldb, row stride ldt >= C, unit column stride); all recursion arithmetic is fp32.
+ *   targets int64 [B, Lmax] (row stride ldtgt).  target_lengths int64 [B] or NULL: the number of leading entries that differ from
+ *   pad_value (the -100 label padding), counted on the device.  input_lengths int64 [B] or NULL: every sample has T frames.
+ *   blank: any class in [0, C).  reduction: FK_CTC_NONE / SUM / MEAN (torch's mean: nll_b / max(L_b, 1) averaged over all B).
+ *   Extended states l' = (blank, l_1, blank, ..., l_L, blank), S = 2 L + 1.  fk_ctc_route: FK_CTC_WAVE (2 Lmax + 1 <= 64: one wave, the
+ *   state vector in registers), FK_CTC_LDS (2 Lmax + 1 <= 511: one workgroup, the state vector in LDS), FK_EINVAL beyond; no launch.
+ *   fk_ctc_loss_fwd: row_lse [B T]; nll [B] (+inf for a sample without alignment, T_b < L_b + adjacent repeats; 0 under zero_infinity);
+ *     loss2 = {reduced loss (the sum for FK_CTC_NONE), B}.  want_lattice != 0 runs the beta recursion beside the alpha recursion and
+ *     leaves what fk_ctc_loss_bwd reads in the workspace: alpha and beta, fp32 [B, T, S_pad] with S_pad = 2 Lmax + 1 rounded up to a
+ *     multiple of 64, log-domain, both including the frame's own log-probability (alpha_t(s) + beta_t(s) - lp_t(l'_s) sums to -nll at
+ *     every t < T_b; states s >= 2 L_b + 1 hold -inf; frames t >= T_b are not written), the clamped lengths and classes, and per label
+ *     the chain of its states.  workspace: fk_ctc_workspace_bytes(B, T, Lmax) with the lattice, fk_ctc_workspace_bytes(B, 0, Lmax) without.
+ *   fk_ctc_loss_bwd: dlogits[b,t,c] = g_b (exp(logit - lse) - exp(logsumexp_{s: l'_s = c}(alpha_t(s) + beta_t(s)) + nll_b - (logit - lse)))
+ *     with g_b from the DEVICE-resident grad_out (a scalar for SUM / MEAN, [B] for NONE; the reduction's factor is applied here).  Rows
+ *     t >= T_b are exactly 0; every row of a sample without alignment is 0 under zero_infinity (NaN without, as torch's).  The states of
+ *     one class are summed in a fixed order, no atomics: nll, loss2 and dlogits are the same bits every run.  Takes the workspace of
+ *     the forward (same B, T, Lmax).
+ *   Clamped on the device, so that every access stays inside the buffers: input_length into [0, T], target_length into [0, Lmax], a
+ *     label into [0, C) and off the blank (label == blank becomes blank - 1, or 1 when blank is 0); the loss of a clamped label is
+ *     meaningless but defined.
+ *   fk_ctc_collapse: greedy decoding of the per-frame argmax int64 [B, T] (fk_argmax_rows): repeated frames merged, blanks dropped,
+ *     order kept ("a _ a" -> "a a", "a a _" -> "a"); ids int64 [B, T] padded with `pad`, lengths int64 [B].                          */
+#define FK_CTC_WAVE 0
+#define FK_CTC_LDS 1
+#define FK_CTC_NONE 0
+#define FK_CTC_SUM 1
+#define FK_CTC_MEAN 2
+int fk_ctc_route(int64_t Lmax);
+size_t fk_ctc_workspace_bytes(int64_t B, int64_t T, int64_t Lmax);
+int fk_ctc_loss_fwd(const void* logits, int64_t ldb, int64_t ldt, const int64_t* targets, int64_t ldtgt, const int64_t* input_lengths,
+                    const int64_t* target_lengths, int64_t pad_value, float* nll, float* loss2, float* row_lse, int64_t B, int64_t T,
+                    int64_t C, int64_t Lmax, int64_t blank, int reduction, int zero_infinity, int want_lattice, int dtype, void* workspace,
+                    size_t workspace_bytes, void* stream);
+int fk_ctc_loss_bwd(const void* logits, int64_t ldb, int64_t ldt, const float* row_lse, const float* grad_out, void* dlogits, int64_t lddb,
+                    int64_t lddt, int64_t B, int64_t T, int64_t C, int64_t Lmax, int64_t blank, int reduction, int zero_infinity, int dtype,
+                    const void* workspace, size_t workspace_bytes, void* stream);
+int fk_ctc_collapse(const int64_t* argmax, int64_t lda, const int64_t* input_lengths, int64_t* ids, int64_t ldi, int64_t* lengths, int64_t B,
+                    int64_t T, int64_t blank, int64_t pad, void* stream);
+
 /* ---- optimizer: torch.optim.AdamW step fused with clip_grad_value_ (utils/train_utils.py:117-119,142-143) over a
  *      flat fp32 arena: g' = clamp(g * grad_scale, -clip, clip) (clip <= 0: no clamp); p *= 1 - lr*wd;
  *      m = b1 m + (1-b1) g'; v = b2 v + (1-b2) g'^2; p -= lr/(1-b1^step) * m / (sqrt(v)/sqrt(1-b2^step) + eps).
