@@ -16,6 +16,11 @@
 //                    the softmax term is a vector sweep of the row; the states of one class are summed in a fixed order (blank states: a
 //                    tree; a label: its first occurrence walks the chain of later occurrences that the forward recorded) — no atomics.
 //   fk_ctc_collapse  greedy decoding behind fk_argmax_rows: merge repeated frames, drop blanks, ordered compaction by ballot + prefix count
+//   fk_ctc_beam_search  prefix beam search, n-best with scores (semantics: include/franken_hip.h; float64 restatement tests/ctc_beam_ref.py)
+//                    launch 1  ctc_beam_prune_kernel  row-parallel like row_lse: one sweep of the row gives row_lse, lp[blank] and the K best
+//                              non-blank (lp, id); a wave appends what beats its K-th best so far to an LDS buffer and compacts it when full
+//                    launch 2  ctc_beam_kernel        one workgroup per sample, sequential over the frames: beam state in LDS, prefixes as a
+//                              trie in the workspace, the W best of at most W + W K keys (in registers) by two rank counts
 //
 // Device-side clamps (every access stays inside the buffers whatever the integers say): input_length into [0, T], target_length into
 // [0, Lmax], a label into [0, C) and off the blank (a label equal to the blank becomes blank - 1, or 1 when the blank is 0).  With a
@@ -450,6 +455,477 @@ __global__ __launch_bounds__(256) void ctc_collapse_kernel(const int64_t* am, in
   if (threadIdx.x == 0) lengths[b] = run;
 }
 
+// ---- prefix beam search -----------------------------------------------------------------------------------------------------------
+// launch 1  ctc_beam_prune_kernel  per row (b, t < T_b): row_lse, lp[blank] and the Kc = min(K, C - 1) non-blank classes with the largest
+//                                  RAW logit (equal logits by ascending id: fk_beam_topk's rule), as (lp, id) in that order
+// launch 2  ctc_beam_kernel        one workgroup per sample, sequential over the frames, the beam in LDS, the prefixes as a trie in the
+//                                  workspace; after the last frame the chains are walked backwards into ids
+constexpr int BEAM_MAX = 32;                                   // W and K at the top of the envelope
+constexpr int BEAM_THREADS = 256;
+constexpr int BEAM_ROW = 256;                                  // rows up to this many classes are loaded a frame ahead with the frame's record
+static_assert(BEAM_ROW <= BEAM_THREADS, "one class per thread");
+constexpr int BEAM_EPT = (BEAM_MAX + BEAM_MAX * BEAM_MAX + BEAM_THREADS - 1) / BEAM_THREADS;   // table entries per thread: 5
+constexpr int PRUNE_CAP = 256;                                 // a wave's candidate buffer (keys)
+constexpr int PRUNE_U = 4;                                     // vectors a lane loads ahead in the row sweep
+static_assert(BEAM_MAX + 64 <= PRUNE_CAP && PRUNE_CAP % 64 == 0, "a compacted buffer takes one more wave of appends");
+static_assert(4 * BEAM_MAX <= BEAM_THREADS, "the merge of the four waves' lists: one thread per entry");
+static_assert(4 * PRUNE_CAP * sizeof(unsigned long long) <= 16 * 1024, "ctc_beam_prune_kernel: LDS budget");
+
+struct BeamWs {
+  float* lse;      // [B T]      row_lse
+  float* lpb;      // [B T]      lp[blank]
+  float* clp;      // [B T][K]   lp of the candidates, best first; -inf behind the Kc-th
+  int* cid;        // [B T][K]   their classes; -1 behind the Kc-th
+  int4* nodes;     // [B][T W + 1] the trie: {parent node, label, first child, next sibling}, node 0 the empty prefix
+};
+static inline size_t beam_ws_carve(BeamWs& w, void* base, int64_t B, int64_t T, int64_t W, int64_t K) {
+  char* p = (char*)base;
+  size_t o = 0;
+  w.lse = (float*)(p + o);  o += a256((size_t)B * T * sizeof(float));
+  w.lpb = (float*)(p + o);  o += a256((size_t)B * T * sizeof(float));
+  w.clp = (float*)(p + o);  o += a256((size_t)B * T * K * sizeof(float));
+  w.cid = (int*)(p + o);    o += a256((size_t)B * T * K * sizeof(int));
+  w.nodes = (int4*)(p + o); o += a256((size_t)B * (T * W + 1) * sizeof(int4));
+  return o;
+}
+
+// a float as an unsigned that orders the same way (-0 ordered as +0: the candidates are ordered by exact float compares)
+FK_DEV unsigned f32_ordered(float x) {
+  const unsigned u = __float_as_uint(x + 0.0f);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+FK_DEV float f32_unordered(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
+// (value, index) as one key: the larger value first, of equal values the LOWER index; 0 is no entry (no value maps to the high word 0)
+FK_DEV unsigned long long beam_key(float x, int idx) { return ((unsigned long long)f32_ordered(x) << 32) | (unsigned)(0x7fffffff - idx); }
+FK_DEV int key_index(unsigned long long k) { return 0x7fffffff - (int)(unsigned)(k & 0xffffffffull); }
+FK_DEV float key_value(unsigned long long k) { return f32_unordered((unsigned)(k >> 32)); }
+FK_DEV unsigned long long wave_max_u64(unsigned long long v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned long long w = __shfl_xor(v, o, 64);
+    v = w > v ? w : v;
+  }
+  return v;
+}
+// LDS that the lanes of ONE wave hand to each other: the accesses stay in program order for the compiler and the LDS serves a wave's
+// instructions in order
+FK_DEV void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
+
+// The wave's buffer buf[0 .. n) of distinct keys -> its K largest, descending, in buf[0 .. min(n, K)); returns the new count.  Rank
+// counting: every lane ranks the up to PRUNE_CAP / 64 keys it holds against the whole buffer.
+FK_DEV int prune_compact(unsigned long long* buf, int n, int K, int lane) {
+  constexpr int Q = PRUNE_CAP / 64;
+  unsigned long long mine[Q];
+  int rank[Q];
+#pragma unroll
+  for (int q = 0; q < Q; ++q) {
+    mine[q] = lane + 64 * q < n ? buf[lane + 64 * q] : 0ull;
+    rank[q] = 0;
+  }
+  for (int i0 = 0; i0 < n; i0 += 8) {                      // eight LDS reads in flight: a read a step would be a chain of LDS latencies
+    unsigned long long x[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) x[u] = buf[i0 + u];        // (inside the buffer: PRUNE_CAP is a multiple of 8)
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const unsigned long long xv = i0 + u < n ? x[u] : 0ull;
+#pragma unroll
+      for (int q = 0; q < Q; ++q) rank[q] += xv > mine[q] ? 1 : 0;
+    }
+  }
+  wave_lds_sync();
+#pragma unroll
+  for (int q = 0; q < Q; ++q)
+    if (mine[q] != 0ull && rank[q] < K) buf[rank[q]] = mine[q];
+  wave_lds_sync();
+  return n < K ? n : K;
+}
+
+// One wave's view of a row: the candidates that beat the wave's K-th best so far are appended to the wave's LDS buffer in lane order
+// (ballot + prefix count); a buffer that could not take another wave of appends is compacted to its K best first, which raises the bar.
+struct PruneState {
+  unsigned long long* buf;
+  unsigned long long bar;     // key of the K-th best so far, 0 while there are fewer
+  float bar_x;                // its logit (-inf while there are fewer): the cheap test in front of the keys
+  int cnt, K, lane;
+};
+FK_DEV void prune_push(PruneState& p, float x, int c, bool valid) {   // called by all lanes of the wave together
+  if (__ballot(valid && x >= p.bar_x) == 0ull) return;                 // the cheap test: no lane reaches the bar's logit
+  unsigned long long key = valid ? beam_key(x, c) : 0ull;
+  bool pass = key > p.bar;
+  unsigned long long bal = __ballot(pass);
+  if (bal == 0ull) return;
+  if (p.cnt + 64 > PRUNE_CAP) {
+    p.cnt = prune_compact(p.buf, p.cnt, p.K, p.lane);
+    if (p.cnt == p.K) { p.bar = p.buf[p.K - 1]; p.bar_x = key_value(p.bar); }
+    pass = key > p.bar;
+    bal = __ballot(pass);
+  }
+  if (pass) p.buf[p.cnt + __popcll(bal & ((1ull << p.lane) - 1ull))] = key;
+  p.cnt += __popcll(bal);
+}
+
+template <typename T, bool BLOCK>
+__global__ __launch_bounds__(256) void ctc_beam_prune_kernel(const T* logits, int64_t ldb, int64_t ldt, const int64_t* input_lengths, BeamWs w,
+                                                              int64_t rows, int T_, int C, int blank, int K, int Kc) {
+  constexpr int N = VecIO<T>::N, G = BLOCK ? 256 : 64, RPB = BLOCK ? 1 : 4;
+  __shared__ float sh[8];
+  __shared__ unsigned long long sh_buf[4][PRUNE_CAP];
+  const int gl = BLOCK ? threadIdx.x : (threadIdx.x & 63), sub = BLOCK ? 0 : (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int64_t base = (int64_t)blockIdx.x * RPB; base < rows; base += (int64_t)gridDim.x * RPB) {   // block-uniform trip count
+    const int64_t row = base + sub;
+    bool live = row < rows;                             // wave-uniform; block-uniform under BLOCK
+    if (live && input_lengths) {
+      const int64_t v = input_lengths[row / T_];
+      live = (row % T_) < (v < 0 ? 0 : (v > T_ ? T_ : v));
+    }
+    float m = -INFINITY, s = 0.0f;
+    PruneState p{sh_buf[wave], 0ull, -INFINITY, 0, Kc, lane};
+    const T* lr = logits;
+    if (live) {
+      lr = logits + (row / T_) * ldb + (row % T_) * ldt;
+      const int head = row_head<T>(lr, C), nvec = (C - head) / N, tail = head + nvec * N;
+      if (head > 0) {                                   // fewer than N elements: one step of the group
+        const bool ok = gl < head;
+        const float x = ok ? to_f32<T>(lr[gl]) : -INFINITY;
+        if (ok) lse_push(m, s, x);
+        prune_push(p, x, gl, ok && gl != blank);
+      }
+      for (int i0 = 0; i0 < nvec; i0 += PRUNE_U * G) {  // wave-uniform trip count: prune_push holds ballots
+        float v[PRUNE_U][N];
+#pragma unroll
+        for (int u = 0; u < PRUNE_U; ++u) {             // PRUNE_U vectors a lane in flight before the first is looked at
+          const int i = i0 + u * G + gl;
+          if (i < nvec) {
+            VecIO<T>::load(lr + head + i * N, v[u]);
+          } else {
+#pragma unroll
+            for (int e = 0; e < N; ++e) v[u][e] = -INFINITY;
+          }
+        }
+#pragma unroll
+        for (int u = 0; u < PRUNE_U; ++u) {
+          const int i = i0 + u * G + gl, c0 = head + i * N;
+          const bool ok = i < nvec;
+          float best = v[u][0];
+#pragma unroll
+          for (int e = 1; e < N; ++e) best = fmaxf(best, v[u][e]);
+          const float vm = fmaxf(m, best);
+          if (ok && vm > -INFINITY) {
+            float acc = s * __expf(m - vm);
+#pragma unroll
+            for (int e = 0; e < N; ++e) acc += __expf(v[u][e] - vm);
+            s = acc;
+            m = vm;
+          }
+          if (__ballot(ok && best >= p.bar_x) != 0ull) {
+#pragma unroll
+            for (int e = 0; e < N; ++e) prune_push(p, v[u][e], c0 + e, ok && c0 + e != blank);
+          }
+        }
+      }
+      if (tail < C) {
+        const int c = tail + gl;
+        const bool ok = c < C;
+        const float x = ok ? to_f32<T>(lr[c]) : -INFINITY;
+        if (ok) lse_push(m, s, x);
+        prune_push(p, x, c, ok && c != blank);
+      }
+      p.cnt = prune_compact(p.buf, p.cnt, Kc, lane);    // the wave's best, descending
+      if (lane >= p.cnt && lane < BEAM_MAX) p.buf[lane] = 0ull;
+    }
+    const float M = group_max<BLOCK>(m, sh);
+    const float tot = group_sum<BLOCK>(m > -INFINITY ? s * __expf(m - M) : 0.0f, sh);   // its barriers order sh_buf for the merge
+    if (live) {
+      const float lse = M + logf(tot);
+      if (gl == 0) { w.lse[row] = lse; w.lpb[row] = to_f32<T>(lr[blank]) - lse; }
+      // the lists of the group's waves merged by rank; a slot behind the Kc-th holds (-inf, -1)
+      constexpr int NW = BLOCK ? 4 : 1;
+      if (gl < NW * BEAM_MAX) {
+        const int lw = BLOCK ? (gl >> 5) : wave, q = gl & (BEAM_MAX - 1);
+        const unsigned long long mine = q < Kc ? sh_buf[lw][q] : 0ull;
+        int rank = BLOCK ? 0 : q;
+        if constexpr (BLOCK) {
+          for (int w2 = 0; w2 < 4; ++w2) {
+#pragma unroll
+            for (int q2 = 0; q2 < BEAM_MAX; ++q2) rank += (q2 < Kc && sh_buf[w2][q2] > mine) ? 1 : 0;   // constant bounds: the reads go out together
+          }
+        }
+        if (mine != 0ull && rank < Kc) {
+          w.clp[row * K + rank] = key_value(mine) - lse;
+          w.cid[row * K + rank] = key_index(mine);
+        }
+        if (gl >= Kc && gl < K) { w.clp[row * K + gl] = -INFINITY; w.cid[row * K + gl] = -1; }
+      }
+    }
+    if constexpr (BLOCK) __syncthreads();               // sh_buf is rewritten by the next row
+  }
+}
+
+struct BeamArgs {
+  const void* logits;
+  int64_t ldb, ldt;
+  const int64_t* input_lengths;
+  BeamWs w;
+  int64_t* ids;
+  int64_t ld_ids_b, ld_ids_h;
+  int64_t* lengths;
+  float* scores;
+  int64_t pad;
+  int T, C, blank, W, K, Kc, nbest;
+};
+
+FK_DEV float log_add(float a, float b) {
+  const float m = fmaxf(a, b);
+  return m == -INFINITY ? -INFINITY : m + log1pf(expf(-fabsf(a - b)));
+}
+
+// A beam slot is (node, parent node, last label, length, pb, pnb, total); the slots are kept in the order of the selection, total
+// descending.  Node ids are canonical: a prefix is looked up among the children of its parent's node before a node is made for it, so a
+// prefix that left the beam and is proposed again comes back under the id its descendants still point to, and "candidate (i, c) is beam
+// j" is exactly "parent[j] == node[i] and last[j] == c".  The look-up seldom leaves LDS: a slot also carries its node's first child and
+// a 64-bit filter of the labels (mod 64) its node ever got a child for, and only a chosen child whose bit is set walks the sibling
+// list in the workspace (a node that comes back has lost its filter: all bits set).  Ties of the selection: a resident prefix before
+// a new one, then the lower slot / parent slot, then the better candidate (the table index decides).
+template <typename T>
+__global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(BeamArgs a) {
+  constexpr int M = BEAM_MAX;
+  __shared__ int s_node[2][M], s_par[2][M], s_last[2][M], s_len[2][M];
+  __shared__ float s_pb[2][M], s_pnb[2][M], s_tot[2][M];
+  __shared__ int s_first[2][M];                         // the node's first child, as nodes[node].z
+  __shared__ unsigned long long s_kids[2][M];           // bit (label & 63): the node may have a child with that label
+  __shared__ float s_npb[M], s_npnb[M];                 // this frame's pb' and pnb' of the resident prefixes
+  __shared__ int s_pslot[M], s_ck[M];                   // slot of the parent prefix / rank of the last label among the candidates, -1: none
+  __shared__ unsigned s_merged[M];                      // bit k: candidate k of slot i is a resident prefix
+  __shared__ float s_clp[2][M], s_fr[2][2];             // the frame's candidates, {lp[blank], row_lse}; double-buffered over t
+  __shared__ int s_cid[2][M];
+  __shared__ float s_row[2][BEAM_ROW];                  // C <= BEAM_ROW: the frame's logits, for a last label that is no candidate
+  __shared__ unsigned long long s_tmax[BEAM_THREADS], s_surv[M * BEAM_EPT + 16], s_selkey[M];   // the selection: see there
+  __shared__ int s_selpar[M], s_sellab[M], s_selnode[M], s_selfirst[M];   // the chosen new prefixes: parent slot, label, node, its first child
+  static_assert((10 * 2 * M + 2 * M + 3 * M + 4 * M + 4 + 4 * M + 2 * BEAM_ROW) * 4 + (BEAM_THREADS + M * BEAM_EPT + 16 + M) * 8 <= 16 * 1024, "ctc_beam_kernel: LDS budget");
+  const int tid = threadIdx.x, b = blockIdx.x, W = a.W, Kc = a.Kc;
+  int Tb = a.T;
+  if (a.input_lengths) {
+    const int64_t v = a.input_lengths[b];
+    Tb = v < 0 ? 0 : (v > a.T ? a.T : (int)v);
+  }
+  int4* nodes = a.w.nodes + (size_t)b * ((size_t)a.T * W + 1);
+  const T* lg = (const T*)a.logits + (int64_t)b * a.ldb;
+  const int64_t row0 = (int64_t)b * a.T;
+
+  // the table of a frame: entries [0, W) are the resident slots, entry W + i Kc + k is candidate k behind slot i
+  const int n_ent = W + W * Kc;
+  const int n_thr = n_ent < BEAM_THREADS ? n_ent : BEAM_THREADS;   // threads that hold a key
+  int ei[BEAM_EPT], ek[BEAM_EPT];
+#pragma unroll
+  for (int r = 0; r < BEAM_EPT; ++r) {
+    const int e = tid + BEAM_THREADS * r;
+    const bool fresh = e >= W && e < n_ent;
+    ei[r] = fresh ? (e - W) / Kc : -1;
+    ek[r] = fresh ? (e - W) % Kc : 0;
+  }
+  if (tid < M) {
+    s_node[0][tid] = 0; s_par[0][tid] = -1; s_last[0][tid] = -1; s_len[0][tid] = 0;
+    s_pb[0][tid] = 0.0f; s_pnb[0][tid] = -INFINITY; s_tot[0][tid] = 0.0f; s_first[0][tid] = -1; s_kids[0][tid] = 0ull;
+    s_cid[0][tid] = s_cid[1][tid] = -1;                 // the frames write [0, Kc)
+  }
+  if (tid == 0) nodes[0] = make_int4(-1, -1, -1, -1);
+  int cur = 0, nb = 1;
+
+  // the frame's record is loaded one frame ahead: threads [0, Kc) a candidate each, thread M lp[blank], thread M + 1 row_lse
+  float pf_f = 0.0f, pf_x = 0.0f;
+  int pf_i = 0;
+  const bool small_row = a.C <= BEAM_ROW;
+  auto fetch = [&](int t) {
+    const int64_t row = row0 + t;
+    if (small_row && tid < a.C) pf_x = to_f32<T>(lg[(int64_t)t * a.ldt + tid]);
+    if (tid < Kc) { pf_f = a.w.clp[row * a.K + tid]; pf_i = a.w.cid[row * a.K + tid]; }
+    else if (tid == M) pf_f = a.w.lpb[row];
+    else if (tid == M + 1) pf_f = a.w.lse[row];
+  };
+  if (Tb > 0) fetch(0);
+
+  for (int t = 0; t < Tb; ++t) {
+    const int f = t & 1;
+    if (tid < Kc) { s_clp[f][tid] = pf_f; s_cid[f][tid] = pf_i; }
+    else if (tid == M || tid == M + 1) s_fr[f][tid - M] = pf_f;
+    if (small_row && tid < a.C) s_row[f][tid] = pf_x;
+    __syncthreads();                                    // the record; the beam the last frame left
+    if (t + 1 < Tb) fetch(t + 1);
+
+    // resident prefixes: blank, the repeat of the last label, and what the parent prefix sends through that label
+    if (tid < nb) {
+      const int j = tid, e = s_last[cur][j];
+      int ck = -1, ps = -1;
+      float lp_e = -INFINITY, npnb = -INFINITY;
+      if (e >= 0) {
+#pragma unroll
+        for (int k = 0; k < M; ++k) ck = s_cid[f][k] == e ? k : ck;                       // (entries behind Kc hold -1)
+        lp_e = ck >= 0 ? s_clp[f][ck] : (small_row ? s_row[f][e] : to_f32<T>(lg[(int64_t)t * a.ldt + e])) - s_fr[f][1];
+        npnb = s_pnb[cur][j] + lp_e;
+        const int par = s_par[cur][j];
+#pragma unroll
+        for (int i = 0; i < M; ++i) ps = (i < nb && s_node[cur][i] == par) ? i : ps;
+        if (ps >= 0) npnb = log_add(npnb, (e == s_last[cur][ps] ? s_pb[cur][ps] : s_tot[cur][ps]) + lp_e);
+      }
+      s_npb[j] = s_tot[cur][j] + s_fr[f][0];
+      s_npnb[j] = npnb;
+      s_pslot[j] = ps;
+      s_ck[j] = ck;
+    }
+    __syncthreads();
+    if (tid < nb) {
+      unsigned mk = 0u;
+#pragma unroll
+      for (int j = 0; j < M; ++j) mk |= (j < nb && s_pslot[j] == tid && s_ck[j] >= 0) ? (1u << s_ck[j]) : 0u;
+      s_merged[tid] = mk;
+    }
+    __syncthreads();
+
+    // the table's keys, in registers
+    unsigned long long key[BEAM_EPT];
+#pragma unroll
+    for (int r = 0; r < BEAM_EPT; ++r) {
+      const int e = tid + BEAM_THREADS * r;
+      float v = -INFINITY;
+      if (e < nb) {
+        v = log_add(s_npb[e], s_npnb[e]);
+      } else if (ei[r] >= 0 && ei[r] < nb) {
+        const int i = ei[r], k = ek[r];
+        if (!((s_merged[i] >> k) & 1u)) v = (s_cid[f][k] == s_last[cur][i] ? s_pb[cur][i] : s_tot[cur][i]) + s_clp[f][k];
+      }
+      key[r] = v > -INFINITY ? beam_key(v, e) : 0ull;   // (a NaN total is no entry either)
+    }
+
+    // The W largest keys.  Only the W threads with the largest own maximum can hold one of them: every thread ranks its maximum among
+    // the BEAM_THREADS maxima, those W threads lay all their keys out, and the at most W BEAM_EPT keys laid out are ranked among
+    // themselves.  Three barriers whatever W is; keys are distinct, so ranks are.  Thread r picks up the key of rank r.
+    unsigned long long mx = key[0];
+#pragma unroll
+    for (int q = 1; q < BEAM_EPT; ++q) mx = key[q] > mx ? key[q] : mx;
+    s_tmax[tid] = mx;
+    if (tid < M * BEAM_EPT + 16) s_surv[tid] = 0ull;
+    if (tid < M) s_selkey[tid] = 0ull;
+    __syncthreads();
+    if (mx != 0ull) {
+      int rank = 0;
+      for (int i0 = 0; i0 < n_thr; i0 += 16) {            // (threads behind the table hold 0; sixteen LDS reads go out together)
+#pragma unroll
+        for (int u = 0; u < 16; ++u) rank += s_tmax[i0 + u] > mx ? 1 : 0;
+      }
+      if (rank < W) {
+#pragma unroll
+        for (int q = 0; q < BEAM_EPT; ++q) s_surv[rank * BEAM_EPT + q] = key[q];
+      }
+    }
+    __syncthreads();
+    if (tid < W * BEAM_EPT) {
+      const unsigned long long mine = s_surv[tid];
+      if (mine != 0ull) {
+        int rank = 0;
+        for (int i0 = 0; i0 < W * BEAM_EPT; i0 += 16) {   // (what is not laid out is 0)
+#pragma unroll
+          for (int u = 0; u < 16; ++u) rank += s_surv[i0 + u] > mine ? 1 : 0;
+        }
+        if (rank < W) s_selkey[rank] = mine;
+      }
+    }
+    __syncthreads();
+    const unsigned long long mysel = tid < M ? s_selkey[tid] : 0ull;
+    const int nsel = __popcll(__ballot((tid & 63) < W && s_selkey[tid & 63] != 0ull));   // the same in every wave
+
+    // nodes of the new prefixes: thread i looks its slot's chosen children up among the children of node[i], makes what is missing
+    const int sel_e = tid < nsel ? key_index(mysel) : 0;
+    if (tid < nsel) {
+      const bool fresh = sel_e >= W;
+      s_selpar[tid] = fresh ? (sel_e - W) / Kc : -1;
+      s_sellab[tid] = fresh ? s_cid[f][(sel_e - W) % Kc] : -1;
+      s_selnode[tid] = -1;
+      s_selfirst[tid] = -1;
+    }
+    __syncthreads();
+    if (tid < nb) {
+      unsigned long long want = 0ull;                   // the labels of this slot's chosen children
+      unsigned mine = 0u;                               // bit r: chosen entry r is a child of this slot
+      int lab[M];
+#pragma unroll
+      for (int r = 0; r < M; ++r) {                     // constant bounds: the LDS reads go out together
+        lab[r] = s_sellab[r];
+        if (r < nsel && s_selpar[r] == tid) { mine |= 1u << r; want |= 1ull << (lab[r] & 63); }
+      }
+      if (mine != 0u) {                                 // (a thread without chosen children does not touch the trie)
+        const int n = s_node[cur][tid], first = s_first[cur][tid];
+        unsigned found = 0u;
+        if (want & s_kids[cur][tid]) {                  // one of them may have a node already
+          for (int ch = first; ch >= 0;) {
+            const int4 nd = nodes[ch];
+#pragma unroll
+            for (int r = 0; r < M; ++r)
+              if (((mine >> r) & 1u) && lab[r] == nd.y) { s_selnode[r] = ch; s_selfirst[r] = nd.z; found |= 1u << r; }
+            ch = nd.w;
+          }
+        }
+        int head = first;
+#pragma unroll
+        for (int r = 0; r < M; ++r)
+          if (((mine & ~found) >> r) & 1u) {
+            const int id = 1 + t * W + r;               // <= T W: inside the sample's table
+            nodes[id] = make_int4(n, lab[r], -1, head);
+            head = id;
+            s_selnode[r] = -2 - id;                     // made here (the build step below tells it from a node that came back)
+          }
+        if (head != first) { nodes[n].z = head; s_first[cur][tid] = head; }
+        s_kids[cur][tid] |= want;
+      }
+    }
+    __syncthreads();
+
+    // the next beam, in the order of the selection
+    const int nx = cur ^ 1;
+    if (tid < nsel) {
+      const float tot = key_value(mysel);
+      if (sel_e < W) {
+        s_node[nx][tid] = s_node[cur][sel_e]; s_par[nx][tid] = s_par[cur][sel_e]; s_last[nx][tid] = s_last[cur][sel_e];
+        s_len[nx][tid] = s_len[cur][sel_e]; s_pb[nx][tid] = s_npb[sel_e]; s_pnb[nx][tid] = s_npnb[sel_e];
+        s_first[nx][tid] = s_first[cur][sel_e]; s_kids[nx][tid] = s_kids[cur][sel_e];
+      } else {
+        const int i = s_selpar[tid], nd = s_selnode[tid];
+        const bool made = nd < -1;
+        s_node[nx][tid] = made ? -2 - nd : nd; s_par[nx][tid] = s_node[cur][i]; s_last[nx][tid] = s_sellab[tid];
+        s_len[nx][tid] = s_len[cur][i] + 1; s_pb[nx][tid] = -INFINITY; s_pnb[nx][tid] = tot;
+        s_first[nx][tid] = made ? -1 : s_selfirst[tid]; s_kids[nx][tid] = made ? 0ull : ~0ull;
+      }
+      s_tot[nx][tid] = tot;
+    }
+    cur = nx;
+    nb = nsel;
+  }
+  __syncthreads();
+
+  // the result: slot h is hypothesis h; its chain is walked backwards
+  for (int64_t i = tid; i < (int64_t)a.nbest * a.T; i += BEAM_THREADS) {
+    const int h = (int)(i / a.T), t = (int)(i % a.T);
+    if (t >= (h < nb ? s_len[cur][h] : 0)) a.ids[(int64_t)b * a.ld_ids_b + (int64_t)h * a.ld_ids_h + t] = a.pad;
+  }
+  if (tid < a.nbest) {
+    const bool have = tid < nb;
+    const int len = have ? s_len[cur][tid] : 0;
+    a.lengths[(int64_t)b * a.nbest + tid] = len;
+    a.scores[(int64_t)b * a.nbest + tid] = have ? s_tot[cur][tid] : -INFINITY;
+    int64_t* o = a.ids + (int64_t)b * a.ld_ids_b + (int64_t)tid * a.ld_ids_h;
+    int n = have ? s_node[cur][tid] : 0;
+    for (int s = len - 1; s >= 0 && n > 0; --s) {
+      const int4 nd = nodes[n];
+      o[s] = nd.y;
+      n = nd.x;
+    }
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -542,6 +1018,48 @@ int fk_ctc_collapse(const int64_t* argmax, int64_t lda, const int64_t* input_len
                (long long)B, (long long)T, (long long)lda, (long long)ldi);
   hipLaunchKernelGGL(ctc_collapse_kernel, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, argmax, lda, input_lengths, ids, ldi, lengths, (int)T, blank, pad);
   FK_CHECK_LAUNCH("fk_ctc_collapse");
+  return FK_OK;
+}
+
+size_t fk_ctc_beam_workspace_bytes(int64_t B, int64_t T, int64_t W, int64_t K) {
+  if (B <= 0 || T <= 0 || W < 1 || W > BEAM_MAX || K < 1 || K > BEAM_MAX) return 0;
+  BeamWs w;
+  return beam_ws_carve(w, nullptr, B, T, W, K);
+}
+
+int fk_ctc_beam_search(const void* logits, int64_t ldb, int64_t ldt, const int64_t* input_lengths, int64_t B, int64_t T, int64_t C, int64_t blank,
+                       int64_t W, int64_t K, int64_t nbest, int64_t pad, int64_t* ids, int64_t ld_ids_b, int64_t ld_ids_h, int64_t* lengths,
+                       float* scores, int dtype, void* workspace, size_t workspace_bytes, void* stream) {
+  FK_DT_CHECK("fk_ctc_beam_search");
+  FK_CHECK_ARG(logits && ids && lengths && scores, "fk_ctc_beam_search: null pointer");
+  FK_CHECK_ARG(B > 0 && T > 0 && B * T < (1LL << 31), "fk_ctc_beam_search: B = %lld, T = %lld", (long long)B, (long long)T);
+  FK_CHECK_ARG(C >= 2 && C < (1LL << 31), "fk_ctc_beam_search: C = %lld, must be >= 2 (a class beside the blank)", (long long)C);
+  FK_CHECK_ARG(blank >= 0 && blank < C, "fk_ctc_beam_search: blank = %lld outside [0, C = %lld)", (long long)blank, (long long)C);
+  FK_CHECK_ARG(W >= 1 && W <= BEAM_MAX && K >= 1 && K <= BEAM_MAX, "fk_ctc_beam_search: W = %lld, K = %lld outside the envelope (1 .. %d each)",
+               (long long)W, (long long)K, BEAM_MAX);
+  FK_CHECK_ARG(T * W < (1LL << 31) - 1, "fk_ctc_beam_search: T W = %lld nodes per sample", (long long)(T * W));
+  FK_CHECK_ARG(nbest >= 1 && nbest <= W, "fk_ctc_beam_search: nbest = %lld outside 1 .. W = %lld", (long long)nbest, (long long)W);
+  FK_CHECK_ARG(ldt >= C && ldb >= ldt, "fk_ctc_beam_search: row stride %lld below C = %lld (batch stride %lld)", (long long)ldt, (long long)C,
+               (long long)ldb);
+  FK_CHECK_ARG(ld_ids_h >= T && ld_ids_b >= (nbest - 1) * ld_ids_h + T, "fk_ctc_beam_search: ids strides %lld / %lld below [nbest = %lld, T = %lld]",
+               (long long)ld_ids_b, (long long)ld_ids_h, (long long)nbest, (long long)T);
+  BeamArgs a;
+  const size_t need = beam_ws_carve(a.w, workspace, B, T, W, K);
+  FK_CHECK_ARG(workspace && workspace_bytes >= need, "fk_ctc_beam_search: workspace too small (%zu bytes, fk_ctc_beam_workspace_bytes gives %zu)", workspace_bytes,
+               need);
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t rows = B * T;
+  const int Kc = (int)(K < C - 1 ? K : C - 1);
+  if (C > 1024)
+    FK_BY_DTYPE(dtype, TT, hipLaunchKernelGGL((ctc_beam_prune_kernel<TT, true>), dim3((unsigned)(rows < 8192 ? rows : 8192)), dim3(256), 0, s, (const TT*)logits, ldb, ldt, input_lengths, a.w, rows, (int)T, (int)C, (int)blank, (int)K, Kc));
+  else
+    FK_BY_DTYPE(dtype, TT, hipLaunchKernelGGL((ctc_beam_prune_kernel<TT, false>), dim3((unsigned)(fk_cdiv(rows, 4) < 8192 ? fk_cdiv(rows, 4) : 8192)), dim3(256), 0, s, (const TT*)logits, ldb, ldt, input_lengths, a.w, rows, (int)T, (int)C, (int)blank, (int)K, Kc));
+  FK_CHECK_LAUNCH("fk_ctc_beam_search(prune)");
+  a.logits = logits; a.ldb = ldb; a.ldt = ldt; a.input_lengths = input_lengths;
+  a.ids = ids; a.ld_ids_b = ld_ids_b; a.ld_ids_h = ld_ids_h; a.lengths = lengths; a.scores = scores; a.pad = pad;
+  a.T = (int)T; a.C = (int)C; a.blank = (int)blank; a.W = (int)W; a.K = (int)K; a.Kc = Kc; a.nbest = (int)nbest;
+  FK_BY_DTYPE(dtype, TT, hipLaunchKernelGGL((ctc_beam_kernel<TT>), dim3((unsigned)B), dim3(BEAM_THREADS), 0, s, a));
+  FK_CHECK_LAUNCH("fk_ctc_beam_search(recursion)");
   return FK_OK;
 }
 

@@ -839,6 +839,17 @@ def ctc_greedy_decode(logits: Tensor, input_lengths: Optional[Tensor] = None, bl
     return K.ctc_collapse(K.argmax_rows(lg).view(B, T), input_lengths, blank, pad)
 
 
+@torch.no_grad()
+def ctc_beam_decode(logits: Tensor, input_lengths: Optional[Tensor] = None, blank: int = 0, beam_width: int = 8, topk: Optional[int] = None,
+                    nbest: int = 1, pad: int = -100):
+    """Prefix beam search: the nbest most probable LABELLINGS (the best path is the most probable alignment) -> (ids int64 [B, nbest, T]
+    padded with `pad`, lengths int64 [B, nbest], scores fp32 [B, nbest], best first).  Logits fp32 or bf16 as the model gives them; two
+    launches, nothing waits for the host.  The n-best list with its scores is what a language model rescores."""
+    if logits.stride(-1) != 1:
+        logits = logits.contiguous()
+    return K.ctc_beam_search(logits, input_lengths, blank, beam_width, topk, nbest, pad)
+
+
 class HeadCrossEntropy(torch.autograd.Function):
     """loss = mean CE(Linear([LN](x)), targets) over the rows whose target != ignore_index, WITHOUT a [rows, V] tensor in either
     direction: lm_head + F.cross_entropy of models/gpt2_model.py:205-210 and the `to_words` head of the notebook CE BrainFormer, used when

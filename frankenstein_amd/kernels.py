@@ -1198,6 +1198,28 @@ def ctc_collapse(argmax: Tensor, input_lengths: Optional[Tensor] = None, blank: 
     return ids, lengths
 
 
+def ctc_beam_search(logits: Tensor, input_lengths: Optional[Tensor] = None, blank: int = 0, beam_width: int = 8, topk: Optional[int] = None,
+                    nbest: int = 1, pad: int = -100) -> Tuple[Tensor, Tensor, Tensor]:
+    """Prefix beam search over logits [B, T, C] (fp32 / bf16, unit column stride, any row and batch stride; NOT log-softmaxed) ->
+    (ids int64 [B, nbest, T] padded with `pad`, lengths int64 [B, nbest], scores fp32 [B, nbest]): the nbest most probable labellings
+    the beam found, best first, with their log-probability mass (semantics: include/franken_hip.h).  beam_width and topk (new prefixes
+    proposed per resident prefix and frame; None: min(32, C - 1)) up to 32.  A slot without hypothesis: length 0, score -inf."""
+    assert logits.dim() == 3 and logits.stride(2) == 1 and logits.dtype in (torch.float32, torch.bfloat16)
+    B, T, Cn = logits.shape
+    K = min(32, Cn - 1) if topk is None else int(topk)
+    dev = logits.device
+    il = _ctc_lengths(input_lengths, B, dev)
+    ids = torch.empty((B, nbest, T), dtype=torch.int64, device=dev)
+    lengths = torch.empty((B, nbest), dtype=torch.int64, device=dev)
+    scores = torch.empty((B, nbest), dtype=torch.float32, device=dev)
+    nbytes = lib().fk_ctc_beam_workspace_bytes(B, T, beam_width, K)
+    ws, _ = _ws(nbytes, dev)
+    with _timed("ctc_beam_search"):
+        call("fk_ctc_beam_search", logits.data_ptr(), logits.stride(0), logits.stride(1), _ptr(il), B, T, Cn, blank, beam_width, K, nbest, pad,
+             ids.data_ptr(), ids.stride(0), ids.stride(1), lengths.data_ptr(), scores.data_ptr(), fk_dtype(logits), _ptr(ws), nbytes, _stream())
+    return ids, lengths, scores
+
+
 class CeChunkState:
     """per-row running statistics of the chunked cross entropy (fk_ce_chunk_*)"""
 

@@ -3,7 +3,7 @@
   BrainEncoder   notebooks_trainer/franky_baseline_gpt2.ipynb cell 3  (encoder + perceiver -> ``to_words`` features)
   Franky         notebooks_trainer/franky_baseline_gpt2.ipynb cell 4  (brain features as GPT prefix, CE loss)
   BrainFormerCE  notebooks_trainer/train_brainformer.ipynb cell 3     (``BrainFormer`` there: vocab head + CE)
-  BrainFormerCTC no counterpart in the reference: the same read-out under a CTC loss, with greedy decoding
+  BrainFormerCTC no counterpart in the reference: the same read-out under a CTC loss, with greedy and prefix-beam decoding
 
 Same constructor / forward signatures and state-dict keys as the notebook classes, so a notebook can
 ``from frankenstein_amd.models.notebook_models import BrainEncoder, Franky`` instead of defining them inline.
@@ -56,6 +56,8 @@ class BrainFormerCTC(_FileBrainFormer):
     labels.  The loss is the mean of torch's F.ctc_loss with zero_infinity=True: a sentence that does not fit into the read-out (more
     labels plus adjacent repeats than read-out tokens) contributes 0 and no gradient instead of turning the run into inf.
     decode(x) -> (ids int64 [B, n_output_tokens] padded with -100, lengths int64 [B]): the best path, repeats merged and blanks dropped.
+    decode(x, beam_width=W, topk=None, nbest=1): prefix beam search (engine.ctc_beam_decode), the most probable labelling in the same
+    form; nbest > 1 -> (ids [B, nbest, n_output_tokens], lengths [B, nbest], scores [B, nbest]), best first, for rescoring.
     utils.metrics.token_error_rate(targets, ids) of that result is the phoneme / token error rate."""
     config = Config
     head_name = 'to_words'
@@ -73,8 +75,12 @@ class BrainFormerCTC(_FileBrainFormer):
         return E.ctc_loss(logits, targets, blank=self.blank, reduction='mean', zero_infinity=True, pad_value=-100), logits
 
     @torch.no_grad()
-    def decode(self, x):
-        return E.ctc_greedy_decode(self.features(x), blank=self.blank, pad=-100)
+    def decode(self, x, beam_width=None, topk=None, nbest=1):
+        logits = self.features(x)
+        if beam_width is None:
+            return E.ctc_greedy_decode(logits, blank=self.blank, pad=-100)
+        ids, lengths, scores = E.ctc_beam_decode(logits, blank=self.blank, beam_width=beam_width, topk=topk, nbest=nbest, pad=-100)
+        return (ids[:, 0], lengths[:, 0]) if nbest == 1 else (ids, lengths, scores)
 
 
 class Franky(nn.Module):

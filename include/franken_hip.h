@@ -545,6 +545,29 @@ int fk_ctc_loss_bwd(const void* logits, int64_t ldb, int64_t ldt, const float* r
 int fk_ctc_collapse(const int64_t* argmax, int64_t lda, const int64_t* input_lengths, int64_t* ids, int64_t ldi, int64_t* lengths, int64_t B,
                     int64_t T, int64_t blank, int64_t pad, void* stream);
 
+/* ---- CTC prefix beam search (csrc/ctc.hip): the most probable LABELLINGS of logits [B, T, C] (fp32 / bf16, strides as above), n-best
+ *      with scores.  Semantics of this build (tests/ctc_beam_ref.py restates them in float64); all arithmetic is fp32.
+ *   A beam is at most W distinct prefixes (tuples of non-blank labels), each with pb / pnb, the log-mass of the alignments of the frames
+ *   so far that end in blank / in its last label; total = logaddexp(pb, pnb); it starts as {(): (0, -inf)}.  Per frame t < T_b, with
+ *   lp = log_softmax(logits[b, t, :]): the candidates are the min(K, C - 1) non-blank classes with the largest RAW logit (exact
+ *   compares, equal logits by ascending class id: fk_beam_topk's rule).  Every prefix p of the beam, last label e, sends
+ *     to p:         pb'  += total + lp[blank];   pnb' += pnb + lp[e]  (p non-empty; whether or not e is a candidate)
+ *     to p + (c,):  pnb' += (c == e ? pb : total) + lp[c]   for every c that is a candidate OR for which p + (c,) is in the beam
+ *   (pruning limits which NEW prefixes are proposed, never the flow of probability between resident prefixes).  The W entries with the
+ *   largest total survive, an entry with total -inf never; exact ties: a resident prefix before a new one, then the lower slot /
+ *   parent slot (slots are in the order of the last selection), then the better candidate.  The same bits every run; no atomics.
+ *   Result: the final beam by total descending, the first nbest: ids int64 [B, nbest, T] (strides ld_ids_b, ld_ids_h >= T) padded with
+ *   `pad`, lengths int64 [B, nbest], scores fp32 [B, nbest] = total.  A slot without hypothesis: length 0, score -inf, a row of pad.
+ *   A score never exceeds the labelling's true log-probability (-nll of fk_ctc_loss_fwd) and equals it when nothing was pruned.
+ *   Envelope: 1 <= W <= 32, 1 <= K <= 32, 1 <= nbest <= W, C >= 2, blank in [0, C), ldt >= C, T W < 2^31 - 1; FK_EINVAL beyond, no
+ *   launch.  input_lengths int64 [B] (clamped into [0, T] on the device) or NULL: T frames each.  workspace:
+ *   fk_ctc_beam_workspace_bytes(B, T, W, K) (0 outside the envelope): per row row_lse, lp[blank] and the K candidates, per sample a trie
+ *   of at most T W + 1 prefixes {parent, label, first child, next sibling}.  Two launches, nothing waits for the host.                */
+size_t fk_ctc_beam_workspace_bytes(int64_t B, int64_t T, int64_t W, int64_t K);
+int fk_ctc_beam_search(const void* logits, int64_t ldb, int64_t ldt, const int64_t* input_lengths, int64_t B, int64_t T, int64_t C, int64_t blank,
+                       int64_t W, int64_t K, int64_t nbest, int64_t pad, int64_t* ids, int64_t ld_ids_b, int64_t ld_ids_h, int64_t* lengths,
+                       float* scores, int dtype, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- optimizer: torch.optim.AdamW step fused with clip_grad_value_ (utils/train_utils.py:117-119,142-143) over a
  *      flat fp32 arena: g' = clamp(g * grad_scale, -clip, clip) (clip <= 0: no clamp); p *= 1 - lr*wd;
  *      m = b1 m + (1-b1) g'; v = b2 v + (1-b2) g'^2; p -= lr/(1-b1^step) * m / (sqrt(v)/sqrt(1-b2^step) + eps).

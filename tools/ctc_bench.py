@@ -1,16 +1,27 @@
 """Isolated timing of the CTC loss, forward + backward (csrc/ctc.hip), and beside it torch.nn.functional.ctc_loss on the same GPU and the
 same inputs (log_softmax + ctc_loss + autograd backward: what a user would otherwise call).  Interleaved rounds in one process, median.
 Usage: python tools/ctc_bench.py [rounds] [reps]   -> one line per shape (B, T, C, L): ours fwd, ours bwd, ours fwd + bwd, torch fwd + bwd, us.
-No parent commit has this path: torch's number is the only yardstick."""
-import sys, os
+No parent commit has this path: torch's number is the only yardstick.
+
+python tools/ctc_bench.py --beam W [rounds] [reps]: the prefix beam search (engine.ctc_beam_decode, beam width W, both launches) beside the
+greedy decode on the same GPU and the same logits, and beside the float64 host restatement (tests/ctc_beam_ref.py) on the host, at the
+project's vocabulary (32 frames, 50258 classes, 20 candidates) and at a phoneme head (768 frames, 41 classes, min(32, C - 1) candidates),
+B = 32 each.  torch has no CTC beam search: the host restatement is the only alternative a user has."""
+import sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import torch.nn.functional as F
+from frankenstein_amd import engine as E
 from frankenstein_amd import kernels as K
 
 SHAPES = [(32, 32, 50258, 25), (32, 128, 41, 40), (32, 768, 41, 120)]
-rounds = int(sys.argv[1]) if len(sys.argv) > 1 else 7
-reps = int(sys.argv[2]) if len(sys.argv) > 2 else 10
+BEAM_SHAPES = [(32, 32, 50258, 20), (32, 768, 41, 32)]         # B, T, C, K
+argv = sys.argv[1:]
+beam = int(argv.pop(argv.index("--beam") + 1)) if "--beam" in argv else None
+if beam is not None:
+    argv.remove("--beam")
+rounds = int(argv[0]) if len(argv) > 0 else 7
+reps = int(argv[1]) if len(argv) > 1 else 10
 dev = torch.device("cuda")
 g = torch.Generator(device=dev).manual_seed(0)
 
@@ -25,7 +36,34 @@ def timed(f):
     return a.elapsed_time(b) / reps * 1e3
 
 
-for B, T, C, L in SHAPES:
+for B, T, C, Kc in (BEAM_SHAPES if beam is not None else []):
+    from tests import ctc_beam_ref as BR
+    blank = C - 1
+    logits = 2.0 * torch.randn(B, T, C, device=dev, generator=g)
+    logits[:, :, blank] += 3.0
+    cases = {"beam": lambda: E.ctc_beam_decode(logits, None, blank, beam, Kc, beam), "greedy": lambda: E.ctc_greedy_decode(logits, None, blank)}
+    for f in cases.values():
+        f()
+    torch.cuda.synchronize()
+    times = {k: [] for k in cases}
+    for _ in range(rounds):
+        for k, f in cases.items():
+            times[k].append(timed(f))
+    med = {k: sorted(v)[len(v) // 2] for k, v in times.items()}
+    ids, lengths, scores = cases["beam"]()
+    g_ids, g_len = cases["greedy"]()
+    differ = int(((lengths[:, 0] != g_len) | (ids[:, 0] != g_ids).any(1)).sum())
+    n_host = min(B, 2)                                         # the host walks sample after sample: two are timed, B are charged
+    x = logits[:n_host].cpu().numpy()
+    t0 = time.perf_counter()
+    ref = BR.beam_search(x, None, blank, beam, Kc, beam)
+    host = (time.perf_counter() - t0) / n_host * B
+    same = bool((ids[:n_host, 0].cpu().numpy() == ref["ids"][:, 0]).all())
+    print(f"(B, T, C) = ({B}, {T}, {C})  W {beam} K {Kc} nbest {beam}:  " + "  ".join(f"{k} {t:9.1f} us" for k, t in med.items())
+          + f"  host float64 restatement {host * 1e3:9.1f} ms ({n_host} samples timed, scaled to {B})  best hypothesis differs from greedy in {differ} of {B}"
+          + f"  best ids equal the restatement's: {same}", flush=True)
+
+for B, T, C, L in (SHAPES if beam is None else []):
     blank = C - 1
     logits = 3.0 * torch.randn(B, T, C, device=dev, generator=g)
     targets = torch.randint(0, C - 1, (B, L), device=dev, generator=g)
