@@ -107,6 +107,10 @@ SIGNATURES = {
     "fk_ctc_collapse": (_int, [_p, _i64, _p, _p, _i64, _p, _i64, _i64, _i64, _i64, _p]),
     "fk_ctc_beam_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),
     "fk_ctc_beam_search": (_int, [_p, _i64, _i64, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _p, _i64, _i64, _p, _p, _int, _p, _sz, _p]),
+    "fk_nbest_trie": (_int, [_p, _i64, _i64, _p, _p] + [_i64] * 8 + [_p] * 8),
+    "fk_nbest_trie_mask": (_int, [_p, _p, _p, _i64, _i64, _i64, _p]),
+    "fk_gpt_embed_pos": (_int, [_p] * 6 + [_i64] * 6 + [_int, _p]),
+    "fk_nbest_rescore": (_int, [_p] * 8 + [_i64, _i64, _p, _p] + [_i64] * 4 + [_int, _f32, _f32, _f32, _i64] + [_p] * 9),
     "fk_ce_workspace_bytes": (_sz, [_i64]),
     "fk_ce_loss_fwd": (_int, [_p, _i64, _p, _p, _p, _i64, _i64, _i64, _int, _p, _sz, _p]),
     "fk_ce_loss_bwd": (_int, [_p, _i64, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _int, _p]),
@@ -126,6 +130,7 @@ VQ_CHAIN, VQ_FUSED = 0, 1                                                       
 VQ_EMA, VQ_KMEANS = 0, 1                                                              # fk_vq_codebook_update modes
 CTC_WAVE, CTC_LDS = 0, 1                                                             # fk_ctc_route
 CTC_NONE, CTC_SUM, CTC_MEAN = 0, 1, 2                                                 # fk_ctc_loss_* reductions
+NBEST_MAX_HYPS, NBEST_MAX_T, NBEST_MAX_NODES, NBEST_MAX_ROWS = 32, 1024, 32769, 4096         # the envelope of fk_nbest_* (csrc/rescore.hip)
 VQ_ROWS = 32                                                                          # data rows per workgroup of fk_vq_assign
 
 

@@ -1273,6 +1273,23 @@ def head_ce_fwd(h: Tensor, w: Tensor, bias: Optional[Tensor], targets: Tensor, V
     return ce_chunk_finish(st, targets, V, ignore_index)
 
 
+def head_ce_stats(h: Tensor, w: Tensor, bias: Optional[Tensor], targets: Tensor, V: int):
+    """The per-row statistics of fk_head_ce_fwd that head_ce_fwd folds into a loss: (row_m, row_s, row_t) fp32 [rows] = running maximum, sum
+    of exp(logit - row_m) and target logit of h @ w[:V]^T (+ bias), so that log p(target) = row_t - (row_m + log(row_s)); no [rows, V] logits.
+    A target outside [0, V) (-100) leaves row_t = 0."""
+    assert h.dim() == 2 and w.dim() == 2 and h.shape[1] == w.shape[1] and h.dtype == w.dtype and h.stride(1) == 1 and w.stride(1) == 1
+    assert w.shape[0] >= V and targets.dtype == torch.int64 and targets.is_contiguous() and targets.numel() == h.shape[0]
+    rows, Kd = h.shape
+    if bias is not None:
+        assert bias.dtype == h.dtype and bias.is_contiguous() and bias.numel() >= V
+    st = CeChunkState(rows, h.device)
+    ws, nb = _ws(lib().fk_head_ce_workspace_bytes(rows, V), h.device)
+    with _timed(f"head_ce_fwd:{rows}x{V}x{Kd}"):
+        call("fk_head_ce_fwd", h.data_ptr(), h.stride(0), w.data_ptr(), w.stride(0), w.shape[0], _ptr(bias), targets.data_ptr(),
+             st.m.data_ptr(), st.s.data_ptr(), st.t.data_ptr(), rows, V, Kd, fk_dtype(h), _ptr(ws), nb, _stream())
+    return st.m, st.s, st.t
+
+
 def head_ce_bwd(h: Tensor, w: Tensor, bias: Optional[Tensor], targets: Tensor, lse: Tensor, loss2: Tensor, gout: Tensor, V: int,
                 vpad: int, rows_pad: int, want_bias: bool, ignore_index: int = -100):
     """dlT [vpad, rows_pad] (transposed d-logits, zero padded) and, for a head with bias, its gradient [V] (fk_head_ce_bwd)."""
@@ -1310,6 +1327,22 @@ def gpt_embed_fwd(idx: Tensor, prefix: Optional[Tensor], wte: Tensor, wpe: Tenso
     out = torch.empty((B, t_ctx + t_words, dim), dtype=dtype, device=idx.device)
     call("fk_gpt_embed_fwd", idx.data_ptr(), _ptr(prefix), wte.data_ptr(), wpe.data_ptr(), out.data_ptr(), B, t_ctx,
          t_words, dim, wte.shape[0], fk_dtype(dtype), _stream())
+    return out
+
+
+def gpt_embed_pos(tok: Tensor, depth: Tensor, prefix: Optional[Tensor], wte: Tensor, wpe: Tensor, dtype: torch.dtype) -> Tensor:
+    """The input rows of a packed n-best forward (fk_gpt_embed_pos): out[b, t] = prefix[b, t] + wpe[t] for t < P, out[b, P + i] =
+    wte[tok[b, i]] + wpe[P + depth[b, i]]; tok / depth int32 [B, N] (nbest_trie) -> [B, P + N, dim] in `dtype`.  Inference only."""
+    B, N = tok.shape
+    P = 0 if prefix is None else prefix.shape[1]
+    dim = wte.shape[1]
+    assert tok.dtype == torch.int32 and depth.dtype == torch.int32 and tok.is_contiguous() and depth.is_contiguous() and depth.shape == (B, N)
+    assert wte.dtype == torch.float32 and wpe.dtype == torch.float32 and wte.is_contiguous() and wpe.is_contiguous() and wpe.shape[1] == dim
+    if prefix is not None:
+        assert prefix.is_contiguous() and prefix.dtype == dtype and prefix.shape == (B, P, dim)
+    out = torch.empty((B, P + N, dim), dtype=dtype, device=tok.device)
+    call("fk_gpt_embed_pos", tok.data_ptr(), depth.data_ptr(), _ptr(prefix), wte.data_ptr(), wpe.data_ptr(), out.data_ptr(), B, P, N, dim,
+         wte.shape[0], wpe.shape[0], fk_dtype(dtype), _stream())
     return out
 
 
@@ -1379,3 +1412,78 @@ def adamw_step_groups_(p: Tensor, g: Tensor, m: Tensor, v: Tensor, segs: Tensor,
     call("fk_adamw_step_groups", p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), segs.data_ptr(), segs.shape[0],
          arr, len(slots), clip, grad_scale, int(zero_grad), max_norm, _ptr(partials), 0 if partials is None else partials.numel(),
          _ptr(norm_out), _stream())
+
+
+# ------------------------------------------------------------------------------------------- n-best rescoring (csrc/rescore.hip)
+NBEST_MAX_HYPS, NBEST_MAX_T, NBEST_MAX_NODES, NBEST_MAX_ROWS = _lib.NBEST_MAX_HYPS, _lib.NBEST_MAX_T, _lib.NBEST_MAX_NODES, _lib.NBEST_MAX_ROWS
+
+
+class NbestTrie:
+    """what nbest_trie leaves on the device: tok / depth / parent int32 [B, node_cap], leaf int32 [B, n], n_nodes int32 [B] and (heads=True)
+    head_src / head_tgt int64 [B, node_cap - 1 + n]; P is the number of prefix rows the head rows count from"""
+    __slots__ = ("tok", "depth", "parent", "leaf", "n_nodes", "head_src", "head_tgt", "node_cap", "P")
+
+
+def _nbest_ids(ids: Tensor, lengths: Tensor, am: Optional[Tensor]):
+    assert ids.dim() == 3 and ids.dtype == torch.int64 and ids.stride(2) == 1, "ids: int64 [B, n, T] with unit token stride"
+    B, n, T = ids.shape
+    assert lengths.dtype == torch.int64 and lengths.shape == (B, n) and lengths.is_contiguous(), "lengths: contiguous int64 [B, n]"
+    if am is not None:
+        assert am.dtype == torch.float32 and am.shape == (B, n) and am.is_contiguous(), "am: contiguous fp32 [B, n]"
+    return B, n, T
+
+
+def nbest_trie(ids: Tensor, lengths: Tensor, am: Optional[Tensor], V: int, bos: int, eos: Optional[int], node_cap: int, P: int = 0,
+               heads: bool = True) -> NbestTrie:
+    """The trie of every sentence's n-best list (fk_nbest_trie; semantics: include/franken_hip.h).  ids int64 [B, n, T] (any batch and
+    hypothesis stride), lengths int64 [B, n], am fp32 [B, n] or None, eos None: no end-of-text row.  heads=False: the head-row lists are
+    not written (a sizing pass that only wants n_nodes)."""
+    B, n, T = _nbest_ids(ids, lengths, am)
+    dev = ids.device
+    t = NbestTrie()
+    t.node_cap, t.P = int(node_cap), int(P)
+    cap = max(t.node_cap, 1)
+    t.tok, t.depth, t.parent = (torch.empty((B, cap), dtype=torch.int32, device=dev) for _ in range(3))
+    t.leaf = torch.empty((B, n), dtype=torch.int32, device=dev)
+    t.n_nodes = torch.empty(B, dtype=torch.int32, device=dev)
+    t.head_src = torch.empty((B, cap - 1 + n), dtype=torch.int64, device=dev) if heads else None
+    t.head_tgt = torch.empty((B, cap - 1 + n), dtype=torch.int64, device=dev) if heads else None
+    with _timed("nbest_trie"):
+        call("fk_nbest_trie", ids.data_ptr(), ids.stride(0), ids.stride(1), lengths.data_ptr(), _ptr(am), B, n, T, V, bos, -1 if eos is None else eos,
+             t.node_cap, t.P, t.tok.data_ptr(), t.depth.data_ptr(), t.parent.data_ptr(), t.leaf.data_ptr(), t.n_nodes.data_ptr(), _ptr(t.head_src),
+             _ptr(t.head_tgt), _stream())
+    return t
+
+
+def nbest_trie_mask(parent: Tensor, n_nodes: Tensor, P: int) -> Mask:
+    """The visibility table of the packed forward as a dense attention mask (fk_nbest_trie_mask): uint8 [B, 1, P + N, P + N]."""
+    assert parent.dtype == torch.int32 and parent.dim() == 2 and parent.is_contiguous() and n_nodes.dtype == torch.int32 and n_nodes.is_contiguous()
+    B, N = parent.shape
+    R = P + N
+    table = torch.empty((B, 1, R, R), dtype=torch.uint8, device=parent.device)
+    with _timed("nbest_trie_mask"):
+        call("fk_nbest_trie_mask", parent.data_ptr(), n_nodes.data_ptr(), table.data_ptr(), B, P, N, _stream())
+    return Mask(MASK_DENSE, 0 if B == 1 else R * R, 0, 0, table, None)
+
+
+def nbest_rescore(stats, trie: NbestTrie, ids: Tensor, lengths: Tensor, am: Optional[Tensor], has_eos: bool, am_weight: float = 1.0,
+                  lm_weight: float = 1.0, length_bonus: float = 0.0, pad: int = -100):
+    """stats = (row_m, row_s, row_t) of head_ce_stats on the trie's head rows -> (lm fp32 [B, n] in input order, ranked) with ranked =
+    (ids [B, n, T] padded with `pad`, lengths, am, lm, total, order int64 [B, n], n_scored int64 [B]) in the new order (fk_nbest_rescore)."""
+    B, n, T = _nbest_ids(ids, lengths, am)
+    N, dev = trie.node_cap, ids.device
+    row_m, row_s, row_t = stats
+    for r in stats:
+        assert r.dtype == torch.float32 and r.is_contiguous() and r.numel() == B * (N - 1 + n)
+    lm = torch.empty((B, n), dtype=torch.float32, device=dev)
+    ids_out = torch.empty((B, n, T), dtype=torch.int64, device=dev)
+    len_out = torch.empty((B, n), dtype=torch.int64, device=dev)
+    am_out, lm_out, total = (torch.empty((B, n), dtype=torch.float32, device=dev) for _ in range(3))
+    order = torch.empty((B, n), dtype=torch.int64, device=dev)
+    n_scored = torch.empty(B, dtype=torch.int64, device=dev)
+    with _timed("nbest_rescore"):
+        call("fk_nbest_rescore", row_m.data_ptr(), row_s.data_ptr(), row_t.data_ptr(), trie.depth.data_ptr(), trie.parent.data_ptr(),
+             trie.leaf.data_ptr(), trie.n_nodes.data_ptr(), ids.data_ptr(), ids.stride(0), ids.stride(1), lengths.data_ptr(), _ptr(am), B, n, T, N,
+             int(has_eos), am_weight, lm_weight, length_bonus, pad, lm.data_ptr(), ids_out.data_ptr(), len_out.data_ptr(), am_out.data_ptr(),
+             lm_out.data_ptr(), total.data_ptr(), order.data_ptr(), n_scored.data_ptr(), _stream())
+    return lm, (ids_out, len_out, am_out, lm_out, total, order, n_scored)

@@ -47,8 +47,9 @@ class CausalSelfAttention(nn.Module):
         self.n_embd = config.n_embd
         self.dropout = config.dropout
 
-    def branch(self, x, ln, residual: bool):
-        spec = (self.n_head, self.n_embd // self.n_head, CAUSAL, None, residual, 0.0 if ln is None else ln.eps, K.NORM_LAYER)
+    def branch(self, x, ln, residual: bool, mask=None):
+        """mask: a kernels.Mask in place of the causal one (the ancestor table of a packed n-best forward); None: CAUSAL"""
+        spec = (self.n_head, self.n_embd // self.n_head, CAUSAL if mask is None else mask, None, residual, 0.0 if ln is None else ln.eps, K.NORM_LAYER)
         if self.dropout and self.training:          # SDPA dropout_p + resid_dropout (models/gpt2_model.py:64,75): two sites
             spec = spec + (E.drop_spec(self.dropout, x.device, 2),)
         return E.AttnBranch.apply(x, None if ln is None else ln.weight, None if ln is None else ln.bias,
@@ -85,8 +86,8 @@ class Block(nn.Module):
         self.ln_2 = LayerNorm(config.n_embd, bias=config.bias)
         self.mlp = MLP(config)
 
-    def forward(self, x):
-        x = self.attn.branch(_prep(x), self.ln_1, True)
+    def forward(self, x, mask=None):
+        x = self.attn.branch(_prep(x), self.ln_1, True, mask)
         return self.mlp.branch(x, self.ln_2, True)
 
     @torch.no_grad()
@@ -295,6 +296,76 @@ class GPT(nn.Module):
             logits = E.NormLinear.apply(last, ln.weight, ln.bias, self.lm_head.weight, None, ln.eps, False)
             loss = None
         return loss, logits
+
+    @torch.no_grad()
+    def _nbest_packed(self, ids, lengths, prefix, am_scores, bos_token_id, eos_token_id, max_nodes, am_weight=1.0, lm_weight=1.0, length_bonus=0.0):
+        """The one route of score_nbest and rescore_nbest: trie -> ancestor mask -> packed forward -> head statistics -> scores and ranking
+        (csrc/rescore.hip; semantics in include/franken_hip.h) -> (lm in input order, n_nodes, the ranked outputs)."""
+        cfg = self.config
+        if ids.dim() != 3 or ids.dtype != torch.int64:
+            raise ValueError(f"ids must be int64 [B, n, T], got {ids.dtype} {tuple(ids.shape)}")
+        B, n, T = ids.shape
+        if not 1 <= n <= K.NBEST_MAX_HYPS or not 1 <= T <= K.NBEST_MAX_T:
+            raise ValueError(f"n = {n} hypotheses of T = {T} tokens outside the envelope (1 .. {K.NBEST_MAX_HYPS}, 1 .. {K.NBEST_MAX_T})")
+        P = 0 if prefix is None else prefix.shape[1]
+        if P + 1 + T > cfg.block_size:
+            raise ValueError(f"prefix ({P}) + start token + T ({T}) exceeds block_size = {cfg.block_size}")
+        V = cfg.vocab_size
+        bos = int(bos_token_id)
+        eos = None if eos_token_id is None else int(eos_token_id)
+        if not 0 <= bos < V or (eos is not None and not 0 <= eos < V):
+            raise ValueError(f"bos_token_id {bos} / eos_token_id {eos} outside the vocabulary of {V}")
+        if ids.stride(2) != 1:
+            ids = ids.contiguous()
+        lengths = lengths.to(torch.int64).contiguous()
+        am = None if am_scores is None else am_scores.float().contiguous()
+        if prefix is not None:
+            prefix = _prep(prefix)
+        if max_nodes is None:                               # the worst case (index arrays only), then ONE host read sizes the forward
+            nmax = int(K.nbest_trie(ids, lengths, am, V, bos, eos, 1 + n * T, P, heads=False).n_nodes.max())
+            N = (P + nmax + 7) // 8 * 8 - P                 # whole 8-row groups for the GEMMs
+        else:
+            N = int(max_nodes)
+        if N < 1 or P + N > K.NBEST_MAX_ROWS:
+            raise ValueError(f"{N} node rows behind {P} prefix rows outside the envelope (N >= 1, P + N <= {K.NBEST_MAX_ROWS})")
+        trie = K.nbest_trie(ids, lengths, am, V, bos, eos, N, P)
+        mask = K.nbest_trie_mask(trie.parent, trie.n_nodes, P)
+        x = K.gpt_embed_pos(trie.tok, trie.depth, prefix, self.transformer.wte.weight.detach(), self.transformer.wpe.weight.detach(), E.compute_dtype())
+        for block in self.transformer.h:
+            x = block(x, mask)
+        ln = self.transformer.ln_f
+        rows = K.gather_rows(_prep(x), trie.head_src)        # [B, N - 1 + n, d]: every head row's hidden row
+        h, _, _ = K.norm_fwd(rows.view(-1, rows.shape[-1]), ln.weight.detach(), None if ln.bias is None else ln.bias.detach(), ln.eps)
+        vec = 8 if h.dtype == torch.bfloat16 else 4
+        wsh = E.shadow([self.lm_head.weight], pad_n=(V + vec - 1) // vec * vec)
+        stats = K.head_ce_stats(h, wsh, None, trie.head_tgt.view(-1), V)
+        lm, ranked = K.nbest_rescore(stats, trie, ids, lengths, am, eos is not None, float(am_weight), float(lm_weight), float(length_bonus))
+        return lm, trie.n_nodes, ranked
+
+    @torch.no_grad()
+    def score_nbest(self, ids, lengths, prefix=None, am_scores=None, bos_token_id=50256, eos_token_id=None, max_nodes=None):
+        """Log-probability of every hypothesis of every sentence's n-best list under this model: ids int64 [B, n, T] (what
+        engine.ctc_beam_decode returns; entries behind a length are never read), lengths [B, n], prefix [B, P, d] or None ->
+        (lm fp32 [B, n] in input order, n_nodes int32 [B]).  lm[h] = sum_j log p(ids[h, j] | prefix, bos, ids[h, :j]), plus
+        log p(eos | ...) with an eos_token_id.  The hypotheses of a sentence are packed as a trie: every distinct token prefix is ONE row of
+        ONE forward under an ancestor mask (exact, not an approximation), the head never forms [rows, V] logits, nothing is copied back.
+        Unscored (lm = -inf): a slot whose am_scores entry is not finite (the beam search's empty slot), a token outside the vocabulary
+        inside the length, or a hypothesis that does not fit max_nodes.  A length 0 with a finite score is the empty hypothesis.
+        max_nodes=None: the trie is first built at the worst-case capacity 1 + n T (index arrays only, a few KB) and ONE host read of
+        n_nodes.max() sizes the forward, padded up to whole 8-row groups.  max_nodes=int: that many node rows per sentence, nothing waits
+        for the host (graph-capturable like the rest of the decode path); a hypothesis whose new nodes do not all fit is unscored and later
+        ones are still tried.  Raises ValueError before any launch when P + 1 + T > block_size."""
+        lm, n_nodes, _ = self._nbest_packed(ids, lengths, prefix, am_scores, bos_token_id, eos_token_id, max_nodes)
+        return lm, n_nodes
+
+    @torch.no_grad()
+    def rescore_nbest(self, ids, lengths, scores, prefix=None, lm_weight=1.0, am_weight=1.0, length_bonus=0.0, bos_token_id=50256,
+                      eos_token_id=None, max_nodes=None):
+        """Re-rank an n-best list by total = am_weight * scores + lm_weight * lm + length_bonus * length (fp32), lm as in score_nbest ->
+        (ids [B, n, T] padded with -100, lengths, am, lm, total, order int64 [B, n], n_scored int64 [B]), everything in the new order:
+        scored hypotheses by total descending (exact ties by original index), unscored ones (lm = total = -inf) behind them in original
+        order; order[b, r] is the original index of place r.  The same bits every run; arguments as score_nbest."""
+        return self._nbest_packed(ids, lengths, prefix, scores, bos_token_id, eos_token_id, max_nodes, am_weight, lm_weight, length_bonus)[2]
 
     def crop_block_size(self, block_size):
         assert block_size <= self.config.block_size

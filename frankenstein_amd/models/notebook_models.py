@@ -58,6 +58,10 @@ class BrainFormerCTC(_FileBrainFormer):
     decode(x) -> (ids int64 [B, n_output_tokens] padded with -100, lengths int64 [B]): the best path, repeats merged and blanks dropped.
     decode(x, beam_width=W, topk=None, nbest=1): prefix beam search (engine.ctc_beam_decode), the most probable labelling in the same
     form; nbest > 1 -> (ids [B, nbest, n_output_tokens], lengths [B, nbest], scores [B, nbest]), best first, for rescoring.
+    decode(x, beam_width=W, nbest=k, lm=gpt, lm_prefix=None, lm_weight=1.0, length_bonus=0.0, eos_token_id=None): the whole final beam
+    (W hypotheses) is rescored by the GPT `lm` on the device (GPT.rescore_nbest: total = CTC score + lm_weight * log p_lm + length_bonus *
+    length; lm_prefix = the brain features a Franky conditions on) and the first k of the new order come back in the same forms, the
+    scores being the totals.  A hypothesis that holds the blank id or another token outside the LM's vocabulary is not scored and ranks last.
     utils.metrics.token_error_rate(targets, ids) of that result is the phoneme / token error rate."""
     config = Config
     head_name = 'to_words'
@@ -75,12 +79,22 @@ class BrainFormerCTC(_FileBrainFormer):
         return E.ctc_loss(logits, targets, blank=self.blank, reduction='mean', zero_infinity=True, pad_value=-100), logits
 
     @torch.no_grad()
-    def decode(self, x, beam_width=None, topk=None, nbest=1):
+    def decode(self, x, beam_width=None, topk=None, nbest=1, lm=None, lm_prefix=None, lm_weight=1.0, length_bonus=0.0, eos_token_id=None,
+               am_weight=1.0, bos_token_id=50256, max_nodes=None):
         logits = self.features(x)
         if beam_width is None:
+            if lm is not None:
+                raise ValueError("decode(lm=...) rescores a beam: give a beam_width")
             return E.ctc_greedy_decode(logits, blank=self.blank, pad=-100)
-        ids, lengths, scores = E.ctc_beam_decode(logits, blank=self.blank, beam_width=beam_width, topk=topk, nbest=nbest, pad=-100)
-        return (ids[:, 0], lengths[:, 0]) if nbest == 1 else (ids, lengths, scores)
+        if lm is None:
+            ids, lengths, scores = E.ctc_beam_decode(logits, blank=self.blank, beam_width=beam_width, topk=topk, nbest=nbest, pad=-100)
+            return (ids[:, 0], lengths[:, 0]) if nbest == 1 else (ids, lengths, scores)
+        # the WHOLE final beam is rescored (GPT.rescore_nbest) and the first nbest places of the new order come back; scores = total
+        ids, lengths, scores = E.ctc_beam_decode(logits, blank=self.blank, beam_width=beam_width, topk=topk, nbest=beam_width, pad=-100)
+        ids, lengths, _, _, total, _, _ = lm.rescore_nbest(ids, lengths, scores, prefix=lm_prefix, lm_weight=lm_weight, am_weight=am_weight,
+                                                           length_bonus=length_bonus, bos_token_id=bos_token_id, eos_token_id=eos_token_id,
+                                                           max_nodes=max_nodes)
+        return (ids[:, 0], lengths[:, 0]) if nbest == 1 else (ids[:, :nbest], lengths[:, :nbest], total[:, :nbest])
 
 
 class Franky(nn.Module):
@@ -109,6 +123,13 @@ class Franky(nn.Module):
         new_idx = targets.clone()
         new_idx[new_idx == -100] = 50256
         return self.llm_model.forward(idx=new_idx, prefix=features, targets=targets)
+
+    @torch.no_grad()
+    def rescore(self, x, ids, lengths, scores, **weights):
+        """Re-rank the n-best lists (ids [S, n, T], lengths, scores [S, n]: BrainFormerCTC.decode(..., nbest=n) of the same trials) under the
+        decoder conditioned on the brain features of x (tensor [S, T, C]): brain_model(x) is the prefix of llm_model.rescore_nbest, whose
+        keyword arguments (lm_weight, am_weight, length_bonus, eos_token_id, max_nodes, ...) and ranked outputs these are."""
+        return self.llm_model.rescore_nbest(ids, lengths, scores, prefix=self.brain_model(x), **weights)
 
     @torch.no_grad()
     def generate(self, x, max_new_tokens=25, temperature=1.0, top_k=10, eot=50256, stop=False, top_p=None, repetition_penalty=1.0,

@@ -568,6 +568,56 @@ int fk_ctc_beam_search(const void* logits, int64_t ldb, int64_t ldt, const int64
                        int64_t W, int64_t K, int64_t nbest, int64_t pad, int64_t* ids, int64_t ld_ids_b, int64_t ld_ids_h, int64_t* lengths,
                        float* scores, int dtype, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- n-best rescoring with a language model (csrc/rescore.hip): the hypotheses of one sentence (fk_ctc_beam_search's n-best list) share
+ *      token prefixes, so every DISTINCT prefix is scored once: the list becomes a trie, the trie one packed GPT forward under an ancestor
+ *      mask, the head goes through fk_head_ce_fwd (no [rows, V] logits), and the sums, the combination with the acoustic score and the
+ *      ranking stay on the device.  The packing is exact: a node sees the causal context of its own flat sequence.  Semantics of this
+ *      build (tests/rescore_ref.py restates them in float64).  One workgroup per sentence b < B unless noted; no atomics on global memory.
+ *   Inputs: ids int64 [B, n, T] (strides ld_ids_b, ld_ids_h >= T; entries at or beyond a hypothesis' length are never read), lengths int64
+ *   [B, n] (clamped into [0, T] on the device), am fp32 [B, n] or NULL (every slot present with am = 0).
+ *   A hypothesis is UNSCORED when its am is not finite (the beam search's empty slot: length 0, score -inf), when a token inside its length
+ *   lies outside [0, V), or when it does not fit the node capacity (below).  Length 0 with a finite am is the empty hypothesis and is scored.
+ *   fk_nbest_trie: node 0 is the start token bos at depth 0 (parent -1).  Hypotheses are walked in order h = 0 .. n-1, tokens in order: a
+ *     node is created the first time a (parent, token) pair is seen and gets the next free number, so parent[i] < i and depth[i] =
+ *     depth[parent[i]] + 1.  leaf[h] = the node of h's last token, 0 for the empty hypothesis, -1 for an unscored one; equal hypotheses share
+ *     a leaf; n_nodes[b] counts the root.  Overflow: a hypothesis whose new nodes do not ALL fit into node_cap - n_nodes becomes unscored and
+ *     creates no node; later hypotheses are still tried.  tok / depth / parent int32 [B, node_cap]; dead nodes i >= n_nodes[b] hold bos, 0, -1.
+ *     head_src / head_tgt int64 [B, node_cap - 1 + n] (both NULL: not written; a sizing pass reads only n_nodes), the rows of the vocabulary
+ *     head for a packed forward with N = node_cap node rows behind P prefix rows: row i - 1 (1 <= i < N) is node i, hidden row P + parent[i],
+ *     target tok[i] (a dead node: row P, target -100); row N - 1 + h is hypothesis h, hidden row P + leaf[h], target eos (row P and -100
+ *     when eos is -1 or h is unscored).
+ *   fk_nbest_trie_mask: every byte of the visibility table uint8 [B, P + N, P + N] (fk_attn_fwd's FK_MASK_DENSE, batch stride (P + N)^2):
+ *     prefix row q sees prefix rows k <= q; a live node sees every prefix row and its ancestors-or-self; a dead node sees only itself.
+ *     parent int32 [B, N].  One workgroup per row.
+ *   fk_gpt_embed_pos: out[b, t] = prefix[b, t] + wpe[t] (t < P), out[b, P + i] = wte[tok[b, i]] + wpe[P + depth[b, i]]; tok / depth int32
+ *     [B, N]; wte / wpe the fp32 master tables, prefix / out in `dtype` (fk_gpt_embed_fwd with a position per row; inference only).  A token
+ *     is clamped into [0, vocab), a position below wpe_rows.
+ *   fk_nbest_rescore: row_m / row_s / row_t fp32 [B, N - 1 + n] = fk_head_ce_fwd on the rows above; lp = row_t - (row_m + log(row_s)).
+ *     cum[0] = 0, cum[i] = cum[parent[i]] + lp[i - 1] (one fp32 add per node, evaluated level by level: the adds of the sequential rule);
+ *     lm[h] = cum[leaf[h]] (+ lp[N - 1 + h] with has_eos); total[h] = am_weight am[h] + lm_weight lm[h] + length_bonus len[h] in fp32;
+ *     unscored (leaf < 0): lm = total = -inf.  Rank: scored hypotheses by total descending, exact ties by ascending original index, the
+ *     unscored ones behind them in original order.  lm fp32 [B, n] in INPUT order; in the new order: ids_out int64 [B, n, T] (padded with
+ *     `pad` behind the length), lengths_out int64 (clamped), am_out, lm_out, total_out fp32 [B, n], order int64 [B, n] (the original index
+ *     of each place), n_scored int64 [B].  The same bits every run.  A NaN total leaves the order among the scored ones unspecified.
+ *   Envelope (FK_EINVAL beyond, no launch): 1 <= n <= FK_NBEST_MAX_HYPS, 1 <= T <= FK_NBEST_MAX_T, 1 <= node_cap <= FK_NBEST_MAX_NODES
+ *   (= 1 + 32 * 1024, the worst case of the largest list), N >= 1 and P + N <= FK_NBEST_MAX_ROWS for the mask and N <= FK_NBEST_MAX_ROWS
+ *   for the scores, 0 <= bos < V, eos = -1 or in [0, V).  Nothing waits for the host.                                                   */
+#define FK_NBEST_MAX_HYPS 32
+#define FK_NBEST_MAX_T 1024
+#define FK_NBEST_MAX_NODES 32769
+#define FK_NBEST_MAX_ROWS 4096
+int fk_nbest_trie(const int64_t* ids, int64_t ld_ids_b, int64_t ld_ids_h, const int64_t* lengths, const float* am, int64_t B, int64_t n, int64_t T,
+                  int64_t V, int64_t bos, int64_t eos, int64_t node_cap, int64_t P, int32_t* tok, int32_t* depth, int32_t* parent, int32_t* leaf,
+                  int32_t* n_nodes, int64_t* head_src, int64_t* head_tgt, void* stream);
+int fk_nbest_trie_mask(const int32_t* parent, const int32_t* n_nodes, uint8_t* mask, int64_t B, int64_t P, int64_t N, void* stream);
+int fk_gpt_embed_pos(const int32_t* tok, const int32_t* depth, const void* prefix, const float* wte, const float* wpe, void* out, int64_t B, int64_t P,
+                     int64_t N, int64_t dim, int64_t vocab, int64_t wpe_rows, int dtype, void* stream);
+int fk_nbest_rescore(const float* row_m, const float* row_s, const float* row_t, const int32_t* depth, const int32_t* parent, const int32_t* leaf,
+                     const int32_t* n_nodes, const int64_t* ids, int64_t ld_ids_b, int64_t ld_ids_h, const int64_t* lengths, const float* am, int64_t B,
+                     int64_t n, int64_t T, int64_t N, int has_eos, float am_weight, float lm_weight, float length_bonus, int64_t pad, float* lm,
+                     int64_t* ids_out, int64_t* lengths_out, float* am_out, float* lm_out, float* total_out, int64_t* order, int64_t* n_scored,
+                     void* stream);
+
 /* ---- optimizer: torch.optim.AdamW step fused with clip_grad_value_ (utils/train_utils.py:117-119,142-143) over a
  *      flat fp32 arena: g' = clamp(g * grad_scale, -clip, clip) (clip <= 0: no clamp); p *= 1 - lr*wd;
  *      m = b1 m + (1-b1) g'; v = b2 v + (1-b2) g'^2; p -= lr/(1-b1^step) * m / (sqrt(v)/sqrt(1-b2^step) + eps).
