@@ -9,38 +9,47 @@
 
 namespace {
 
-// partial[i][c] = (sum, sum of squares) of trial i, channel c
+// partial[i][c] = (mean, sum of squared deviations from it) of trial i, channel c.  The sums run on x - (the trial's first sample): a
+// constant channel gives exactly (its value, 0), where sum x^2 / n - mean^2 leaves a rounding residue that std == 0 -> 1 then misses.
 __global__ void trial_sums_kernel(const float* x, const int64_t* off, int64_t C, double* partial) {
   const int64_t i = blockIdx.x;
   const int64_t r0 = off[i], r1 = off[i + 1];
   for (int64_t c = blockIdx.y * (int64_t)blockDim.x + threadIdx.x; c < C; c += (int64_t)gridDim.y * blockDim.x) {
+    const double v0 = r1 > r0 ? (double)x[r0 * C + c] : 0.0;
     double s = 0.0, q = 0.0;
     for (int64_t r = r0; r < r1; ++r) {
-      const double v = (double)x[r * C + c];
+      const double v = (double)x[r * C + c] - v0;
       s += v;
       q += v * v;
     }
-    partial[(i * C + c) * 2] = s;
-    partial[(i * C + c) * 2 + 1] = q;
+    const double len = (double)(r1 - r0);
+    partial[(i * C + c) * 2] = r1 > r0 ? v0 + s / len : 0.0;
+    partial[(i * C + c) * 2 + 1] = r1 > r0 ? fmax(q - s * s / len, 0.0) : 0.0;
   }
 }
+// the block's trials merged in trial order: mean = sum len_i mean_i / n, var = sum (M2_i + len_i (mean_i - mean)^2) / n
 __global__ void block_stats_kernel(const double* partial, const int64_t* off, const int32_t* block, int64_t ntrials, int64_t C,
                                    float* mean, float* stdv) {
   const int64_t b = blockIdx.y;
   const int64_t c = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (c >= C) return;
-  double s = 0.0, q = 0.0, n = 0.0;
+  double s = 0.0, n = 0.0;
   for (int64_t i = 0; i < ntrials; ++i) {
     if (block[i] != (int32_t)b) continue;
-    s += partial[(i * C + c) * 2];
-    q += partial[(i * C + c) * 2 + 1];
-    n += (double)(off[i + 1] - off[i]);
+    const double len = (double)(off[i + 1] - off[i]);
+    s += len * partial[(i * C + c) * 2];
+    n += len;
   }
   double m = 0.0, sd = 1.0;
   if (n > 0.0) {
     m = s / n;
-    const double var = fmax(q / n - m * m, 0.0);
-    sd = sqrt(var);
+    double q = 0.0;
+    for (int64_t i = 0; i < ntrials; ++i) {
+      if (block[i] != (int32_t)b) continue;
+      const double d = partial[(i * C + c) * 2] - m;
+      q += partial[(i * C + c) * 2 + 1] + (double)(off[i + 1] - off[i]) * d * d;
+    }
+    sd = sqrt(q / n);
     if (sd == 0.0) sd = 1.0;
   }
   mean[b * C + c] = (float)m;

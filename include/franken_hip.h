@@ -486,10 +486,14 @@ int fk_ce_chunk_bwd(const float* logits, int64_t ld, const int64_t* targets, int
  *      and the `to_words` head of the notebook CE BrainFormer (notebooks_trainer/train_brainformer.ipynb cell 3) when only the loss is
  *      needed (utils/train_utils.py:138-139).  No [rows, V] tensor in either direction.
  *   fk_head_ce_fwd : row_m / row_s / row_t (running maximum, sum of exponentials, target logit; the inputs of fk_ce_chunk_finish) of
- *                    logits = H W^T (+ bias) straight from the MFMA accumulators.  H [rows, K] (ldh), W [wrows >= V, K] (ldw, rows past V
- *                    unused), bias [>= V] or NULL in the compute dtype, targets int64 [rows].  workspace: fk_head_ce_workspace_bytes.
- *   fk_head_ce_bwd : dlT [vpad, rows_pad] (row stride lddl) = TRANSPOSED d-logits, (exp(logit - row_lse) - onehot) * grad_out[0] / loss2[1]
- *                    on rows whose target != ignore_index and vocabulary entries < V, zero elsewhere (the padding feeds GEMMs):
+ *                    logits = H W^T (+ bias) straight from the MFMA accumulators.  H [rows, K] (ldh), W [wrows >= V, K] (ldw; rows past V
+ *                    may be loaded with a tile but enter no result, whatever they hold), bias [>= V] or NULL in the compute dtype,
+ *                    targets int64 [rows]; a target outside [0, V) leaves row_t = 0.  workspace: fk_head_ce_workspace_bytes.
+ *   fk_head_ce_bwd : dlT [vpad, rows_pad] (row stride lddl) = TRANSPOSED d-logits, (exp(logit - row_lse) - onehot) * grad_out[0] /
+ *                    max(loss2[1], 1) on rows whose target is in [0, V) and != ignore_index and vocabulary entries < V, zero elsewhere
+ *                    (the padding feeds GEMMs).  When no row is valid the forward gives loss2 = {NaN, 0} (the mean over nothing, as
+ *                    F.cross_entropy); the backward then writes zeros everywhere, dbpart included — the divisor is 1, not the count,
+ *                    so that no Inf / NaN reaches the gradient products.
  *                    dH = fk_gemm_tn(dlT, W), dW = fk_gemm_nt(dlT, H^T).  dbpart (nullable): [2 * ceil(rows / 128), vpad] partial column
  *                    sums of the d-logits (bias gradient = their column sum).  rows <= rows_pad <= ceil(rows/128)*128, rows_pad % 4 == 0,
  *                    V <= vpad <= ceil(V/128)*128.

@@ -86,7 +86,8 @@ PRODUCT_MODULES = ("frankenstein_amd.kernels", "frankenstein_amd.engine", "frank
                    "frankenstein_amd.models.simple_mae", "frankenstein_amd.models.vq_brain", "frankenstein_amd.models.notebook_models",
                    "frankenstein_amd.utils.train_utils", "frankenstein_amd.utils.data_utils")
 TEST_MODULES = ("tests.test_kernels_gpu", "tests.test_coresidency_gpu", "tests.test_envelope_gpu", "tests.test_rowwise_gpu",
-                "tests.test_gemm_routes_gpu", "tests.test_attn_routes_gpu")        # kernel-level tests allocate their own outputs
+                "tests.test_gemm_routes_gpu", "tests.test_attn_routes_gpu", "tests.test_head_ce_gpu",
+                "tests.test_conv_pipeline_gpu")                                     # kernel-level tests allocate their own outputs
 
 
 def install():
