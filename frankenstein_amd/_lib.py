@@ -107,6 +107,9 @@ SIGNATURES = {
     "fk_ctc_collapse": (_int, [_p, _i64, _p, _p, _i64, _p, _i64, _i64, _i64, _i64, _p]),
     "fk_ctc_beam_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),
     "fk_ctc_beam_search": (_int, [_p, _i64, _i64, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _p, _i64, _i64, _p, _p, _int, _p, _sz, _p]),
+    "fk_ngram_hash": (_u32, [_u32, _u32]),
+    "fk_ctc_beam_search_lm": (_int, [_p, _i64, _i64, _p] + [_i64] * 8 + [_p, _i64, _i64, _p, _p, _i64, _p, _p, _i64, _i64, _f32, _f32, _int, _p, _i64, _i64,
+                                     _p, _p, _p, _p, _int, _p, _sz, _p]),
     "fk_nbest_trie": (_int, [_p, _i64, _i64, _p, _p] + [_i64] * 8 + [_p] * 8),
     "fk_nbest_trie_mask": (_int, [_p, _p, _p, _i64, _i64, _i64, _p]),
     "fk_gpt_embed_pos": (_int, [_p] * 6 + [_i64] * 6 + [_int, _p]),

@@ -21,6 +21,9 @@
 //                              non-blank (lp, id); a wave appends what beats its K-th best so far to an LDS buffer and compacts it when full
 //                    launch 2  ctc_beam_kernel        one workgroup per sample, sequential over the frames: beam state in LDS, prefixes as a
 //                              trie in the workspace, the W best of at most W + W K keys (in registers) by two rank counts
+//   fk_ctc_beam_search_lm  the same search with a backoff n-gram model inside the selection (shallow fusion; float64 restatement
+//                    tests/ctc_lm_ref.py): launch 1 as above, launch 2 the LM instantiation of ctc_beam_kernel, whose slots also carry the
+//                    LM term, the LM sum and the LM state of their prefix (in LDS); the model is a state machine over one hash table
 //
 // Device-side clamps (every access stays inside the buffers whatever the integers say): input_length into [0, T], target_length into
 // [0, Lmax], a label into [0, C) and off the blank (a label equal to the blank becomes blank - 1, or 1 when the blank is 0).  With a
@@ -691,9 +694,130 @@ FK_DEV float log_add(float a, float b) {
 // a 64-bit filter of the labels (mod 64) its node ever got a child for, and only a chosen child whose bit is set walks the sibling
 // list in the workspace (a node that comes back has lost its filter: all bits set).  Ties of the selection: a resident prefix before
 // a new one, then the lower slot / parent slot, then the better candidate (the table index decides).
-template <typename T>
-__global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(BeamArgs a) {
+//
+// LM (fk_ctc_beam_search_lm): shallow fusion with a backoff n-gram model.  The acoustic recursion is the one above; a slot also carries
+// lmw (the weighted LM term of its prefix), lm (the unweighted sum) and the LM state of its prefix, and the selection runs on
+// total + lmw.  A fresh candidate's term comes from one look-up (state of slot i, candidate k), made for the whole table right behind the
+// frame's first barrier, so that the waves without resident prefixes look up while the first wave runs the resident step; the values of
+// the chosen entries are picked up again from LDS when the next beam is built.  A resident prefix keeps its own values, and a prefix that
+// returns is the same sum from the same parent value.  The plain instantiation holds none of this: same LDS, same code as without it.
+struct BeamLmArgs : BeamArgs {
+  const int4* table;      // [cap] {state, token, bits of ln p, next state}, state -1: empty
+  const float* bow;       // [S]
+  const int* backoff;     // [S]
+  const float* uni_lp;    // [C + 1]
+  const int* uni_next;    // [C + 1]
+  float* lm_out;          // [B, nbest]
+  float* total_out;       // [B, nbest]
+  float lm_weight, length_bonus;
+  int S, cap_mask, max_probe, order, start_state, use_eos;
+};
+
+// the home slot of (state, token) is ngram_hash & (cap - 1): fk_ngram_hash of include/franken_hip.h
+__host__ __device__ inline unsigned ngram_hash(unsigned state, unsigned token) {
+  unsigned h = state * 0x9E3779B1u ^ token * 0x85EBCA6Bu;
+  h ^= h >> 15;
+  h *= 0x2C1B3C6Du;
+  h ^= h >> 12;
+  return h;
+}
+FK_DEV int clamp_state(int s, int S) { return s < 0 ? 0 : (s >= S ? S - 1 : s); }
+// w lp + bonus, rounded after the product and after the sum: the term has the same bits wherever it is formed
+FK_DEV float lm_term(float w, float lp, float bonus) {
+#pragma clang fp contract(off)
+  const float p = w * lp;
+  return p + bonus;
+}
+
+// N look-ups side by side.  A look-up is a chain of dependent loads, so everything whose address is known goes out at once: the unigram
+// of the token at the start, and per step of a look-up LM_AHEAD consecutive entries of the probe sequence (linear probing: their
+// addresses follow from the first) with the state's backoff weight and backoff state; a round is then one load latency unless a probe
+// sequence is longer than LM_AHEAD.  The entries are looked at in probe order, none behind max_probe.  Every loop is bounded by
+// order * max_probe steps, every state read from a table is clamped into [0, S), a token into [0, C] and a table index by the mask: a
+// malformed table gives wrong scores, never an access outside the tables.
+//   at most `order` rounds: state 0 -> the dense table; else probe at most max_probe entries from the hash slot: a hit gives
+//   (acc + ln p, next), an empty entry or the last probe ends the round with acc += bow[s], s = backoff[s]; behind the last round: unigram
+constexpr int LM_AHEAD = 4;                            // (768 x 41, W 32, order 3: 25.6 ms with 1, 21.6 ms with 2, 19.6 ms with 4)
+template <int N>
+FK_DEV void lm_lookup(const BeamLmArgs& a, const int (&state)[N], const int (&token)[N], const bool (&want)[N], float (&lp)[N], int (&next)[N]) {
+  int s[N], tok[N], p[N], rd[N], unx[N];
+  float acc[N], ulp[N];
+  bool open[N];
+#pragma unroll
+  for (int r = 0; r < N; ++r) {
+    s[r] = clamp_state(state[r], a.S);
+    tok[r] = token[r] < 0 ? 0 : (token[r] > a.C ? a.C : token[r]);
+    p[r] = 0; rd[r] = 0; acc[r] = 0.0f;
+    open[r] = want[r];
+    lp[r] = 0.0f; next[r] = 0;
+    ulp[r] = 0.0f; unx[r] = 0;
+    if (want[r]) { ulp[r] = a.uni_lp[tok[r]]; unx[r] = a.uni_next[tok[r]]; }
+  }
+  const long long steps = (long long)a.order * a.max_probe;
+  for (long long it = 0; it < steps; ++it) {
+    int4 e[N][LM_AHEAD];
+    float bw[N];
+    int bk[N];
+    bool any = false;
+#pragma unroll
+    for (int r = 0; r < N; ++r) {
+      if (open[r] && s[r] != 0) {
+        const unsigned h = ngram_hash((unsigned)s[r], (unsigned)tok[r]) + (unsigned)p[r];
+#pragma unroll
+        for (int q = 0; q < LM_AHEAD; ++q) e[r][q] = a.table[(h + (unsigned)q) & (unsigned)a.cap_mask];
+        bw[r] = a.bow[s[r]];
+        bk[r] = a.backoff[s[r]];
+        any = true;
+      }
+    }
+    if (!any) break;
+#pragma unroll
+    for (int r = 0; r < N; ++r) {
+      if (open[r] && s[r] != 0) {
+        int verdict = 0;                                // 1: hit, 2: the round is over
+        int4 hit = make_int4(0, 0, 0, 0);
+#pragma unroll
+        for (int q = 0; q < LM_AHEAD; ++q) {
+          if (verdict == 0) {
+            if (p[r] + q >= a.max_probe || e[r][q].x == -1) verdict = 2;
+            else if (e[r][q].x == s[r] && e[r][q].y == tok[r]) { verdict = 1; hit = e[r][q]; }
+          }
+        }
+        if (verdict == 1) {
+          lp[r] = acc[r] + __int_as_float(hit.z);
+          next[r] = clamp_state(hit.w, a.S);
+          open[r] = false;
+        } else if (verdict == 2 || p[r] + LM_AHEAD >= a.max_probe) {
+          acc[r] += bw[r];
+          s[r] = (rd[r] + 1 >= a.order) ? 0 : clamp_state(bk[r], a.S);
+          rd[r] += 1;
+          p[r] = 0;
+        } else {
+          p[r] += LM_AHEAD;
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < N; ++r) {
+    if (open[r]) {
+      lp[r] = acc[r] + ulp[r];
+      next[r] = clamp_state(unx[r], a.S);
+    }
+  }
+}
+
+template <typename T, bool LM>
+__global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(std::conditional_t<LM, BeamLmArgs, BeamArgs> a) {
   constexpr int M = BEAM_MAX;
+  constexpr int ML = LM ? M : 1, MC = LM ? M * M : 1;   // (the plain instantiation never names the arrays below: they take no LDS there)
+  __shared__ float s_lmw[2][ML], s_lms[2][ML];          // per slot: the weighted LM term of its prefix, the unweighted sum of ln P
+  __shared__ int s_lst[2][ML];                          // its LM state
+  __shared__ float s_candlp[MC];                        // this frame's look-ups, entry W + i Kc + k at i Kc + k: ln P(cid[k] | state of slot i)
+  __shared__ int s_candnx[MC];                          // and the state behind it
+  __shared__ float s_fkey[ML], s_flm[ML];               // the final keys and LM sums (with the end of sentence)
+  __shared__ int s_perm[ML];                            // the final order: place -> slot
+  static_assert(!LM || (3 * 2 * M + 2 * M * M + 3 * M) * 4 <= 12 * 1024, "ctc_beam_kernel<LM>: LDS budget of the LM state");
   __shared__ int s_node[2][M], s_par[2][M], s_last[2][M], s_len[2][M];
   __shared__ float s_pb[2][M], s_pnb[2][M], s_tot[2][M];
   __shared__ int s_first[2][M];                         // the node's first child, as nodes[node].z
@@ -732,6 +856,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(BeamArgs a) {
     s_node[0][tid] = 0; s_par[0][tid] = -1; s_last[0][tid] = -1; s_len[0][tid] = 0;
     s_pb[0][tid] = 0.0f; s_pnb[0][tid] = -INFINITY; s_tot[0][tid] = 0.0f; s_first[0][tid] = -1; s_kids[0][tid] = 0ull;
     s_cid[0][tid] = s_cid[1][tid] = -1;                 // the frames write [0, Kc)
+    if constexpr (LM) { s_lmw[0][tid] = 0.0f; s_lms[0][tid] = 0.0f; s_lst[0][tid] = clamp_state(a.start_state, a.S); }
   }
   if (tid == 0) nodes[0] = make_int4(-1, -1, -1, -1);
   int cur = 0, nb = 1;
@@ -756,6 +881,23 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(BeamArgs a) {
     if (small_row && tid < a.C) s_row[f][tid] = pf_x;
     __syncthreads();                                    // the record; the beam the last frame left
     if (t + 1 < Tb) fetch(t + 1);
+
+    // LM: ln P(candidate k | state of slot i) for every fresh entry of the table, kept for the keys and laid out for the build step
+    float cand_lp[BEAM_EPT];
+    if constexpr (LM) {
+      int st[BEAM_EPT], tk[BEAM_EPT], nx_[BEAM_EPT];
+      bool want[BEAM_EPT];
+#pragma unroll
+      for (int r = 0; r < BEAM_EPT; ++r) {
+        want[r] = ei[r] >= 0 && ei[r] < nb;
+        st[r] = want[r] ? s_lst[cur][ei[r]] : 0;
+        tk[r] = want[r] ? s_cid[f][ek[r]] : 0;
+      }
+      lm_lookup<BEAM_EPT>(a, st, tk, want, cand_lp, nx_);
+#pragma unroll
+      for (int r = 0; r < BEAM_EPT; ++r)
+        if (want[r]) { s_candlp[ei[r] * Kc + ek[r]] = cand_lp[r]; s_candnx[ei[r] * Kc + ek[r]] = nx_[r]; }
+    }
 
     // resident prefixes: blank, the repeat of the last label, and what the parent prefix sends through that label
     if (tid < nb) {
@@ -794,9 +936,11 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(BeamArgs a) {
       float v = -INFINITY;
       if (e < nb) {
         v = log_add(s_npb[e], s_npnb[e]);
+        if constexpr (LM) v = v > -INFINITY ? v + s_lmw[cur][e] : v;
       } else if (ei[r] >= 0 && ei[r] < nb) {
         const int i = ei[r], k = ek[r];
         if (!((s_merged[i] >> k) & 1u)) v = (s_cid[f][k] == s_last[cur][i] ? s_pb[cur][i] : s_tot[cur][i]) + s_clp[f][k];
+        if constexpr (LM) v = v > -INFINITY ? v + (s_lmw[cur][i] + lm_term(a.lm_weight, cand_lp[r], a.length_bonus)) : v;
       }
       key[r] = v > -INFINITY ? beam_key(v, e) : 0ull;   // (a NaN total is no entry either)
     }
@@ -887,7 +1031,20 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(BeamArgs a) {
     // the next beam, in the order of the selection
     const int nx = cur ^ 1;
     if (tid < nsel) {
-      const float tot = key_value(mysel);
+      float tot = key_value(mysel);
+      if constexpr (LM) {                               // the key is total + lmw there: the total again, the same expression as for the key
+        if (sel_e < W) {
+          tot = log_add(s_npb[sel_e], s_npnb[sel_e]);
+          s_lmw[nx][tid] = s_lmw[cur][sel_e]; s_lms[nx][tid] = s_lms[cur][sel_e]; s_lst[nx][tid] = s_lst[cur][sel_e];
+        } else {
+          const int i = s_selpar[tid], k = (sel_e - W) % Kc;
+          const float lp = s_candlp[sel_e - W];
+          tot = (s_cid[f][k] == s_last[cur][i] ? s_pb[cur][i] : s_tot[cur][i]) + s_clp[f][k];
+          s_lmw[nx][tid] = s_lmw[cur][i] + lm_term(a.lm_weight, lp, a.length_bonus);
+          s_lms[nx][tid] = s_lms[cur][i] + lp;
+          s_lst[nx][tid] = s_candnx[sel_e - W];
+        }
+      }
       if (sel_e < W) {
         s_node[nx][tid] = s_node[cur][sel_e]; s_par[nx][tid] = s_par[cur][sel_e]; s_last[nx][tid] = s_last[cur][sel_e];
         s_len[nx][tid] = s_len[cur][sel_e]; s_pb[nx][tid] = s_npb[sel_e]; s_pnb[nx][tid] = s_npnb[sel_e];
@@ -907,23 +1064,98 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(BeamArgs a) {
   __syncthreads();
 
   // the result: slot h is hypothesis h; its chain is walked backwards
+  // LM: the final key total + lmw, with use_eos + lm_weight ln P(</s> | state); the beam is put in the order of these keys once more,
+  // equal keys in the order of the last selection (s_perm: place -> slot, the identity wherever no rank lands)
+  if constexpr (LM) {
+    if (tid < M) {
+      float key = -INFINITY, lm = -INFINITY;
+      if (tid < nb) {
+        key = s_tot[cur][tid] + s_lmw[cur][tid];
+        lm = s_lms[cur][tid];
+        if (a.use_eos) {
+          const int st[1] = {s_lst[cur][tid]}, tk[1] = {a.C};
+          const bool want[1] = {true};
+          float lp[1];
+          int nx_[1];
+          lm_lookup<1>(a, st, tk, want, lp, nx_);
+          key += lm_term(a.lm_weight, lp[0], 0.0f);
+          lm += lp[0];
+        }
+      }
+      s_fkey[tid] = key;
+      s_flm[tid] = lm;
+      s_perm[tid] = tid;
+    }
+    __syncthreads();
+    if (tid < nb) {
+      const float mine = s_fkey[tid];
+      int rank = 0;
+#pragma unroll
+      for (int j = 0; j < M; ++j) rank += (j < nb && (s_fkey[j] > mine || (s_fkey[j] == mine && j < tid))) ? 1 : 0;   // < nb
+      s_perm[rank] = tid;
+    }
+    __syncthreads();
+  }
+  auto slot_of = [&](int h) {
+    if constexpr (LM) return s_perm[h];
+    else return h;
+  };
   for (int64_t i = tid; i < (int64_t)a.nbest * a.T; i += BEAM_THREADS) {
     const int h = (int)(i / a.T), t = (int)(i % a.T);
-    if (t >= (h < nb ? s_len[cur][h] : 0)) a.ids[(int64_t)b * a.ld_ids_b + (int64_t)h * a.ld_ids_h + t] = a.pad;
+    if (t >= (h < nb ? s_len[cur][slot_of(h)] : 0)) a.ids[(int64_t)b * a.ld_ids_b + (int64_t)h * a.ld_ids_h + t] = a.pad;
   }
   if (tid < a.nbest) {
     const bool have = tid < nb;
-    const int len = have ? s_len[cur][tid] : 0;
+    const int sl = slot_of(tid);
+    const int len = have ? s_len[cur][sl] : 0;
     a.lengths[(int64_t)b * a.nbest + tid] = len;
-    a.scores[(int64_t)b * a.nbest + tid] = have ? s_tot[cur][tid] : -INFINITY;
+    a.scores[(int64_t)b * a.nbest + tid] = have ? s_tot[cur][sl] : -INFINITY;
+    if constexpr (LM) {
+      a.lm_out[(int64_t)b * a.nbest + tid] = have ? s_flm[sl] : -INFINITY;
+      a.total_out[(int64_t)b * a.nbest + tid] = have ? s_fkey[sl] : -INFINITY;
+    }
     int64_t* o = a.ids + (int64_t)b * a.ld_ids_b + (int64_t)tid * a.ld_ids_h;
-    int n = have ? s_node[cur][tid] : 0;
+    int n = have ? s_node[cur][sl] : 0;
     for (int s = len - 1; s >= 0 && n > 0; --s) {
       const int4 nd = nodes[n];
       o[s] = nd.y;
       n = nd.x;
     }
   }
+}
+
+// The argument checks, the workspace and launch 1 of fk_ctc_beam_search and fk_ctc_beam_search_lm; fills everything
+// of `a` the plain search reads.
+static int beam_front(const char* fn, const void* logits, int64_t ldb, int64_t ldt, const int64_t* input_lengths, int64_t B, int64_t T, int64_t C,
+                      int64_t blank, int64_t W, int64_t K, int64_t nbest, int64_t pad, int64_t* ids, int64_t ld_ids_b, int64_t ld_ids_h,
+                      int64_t* lengths, float* scores, int dtype, void* workspace, size_t workspace_bytes, void* stream, BeamArgs& a) {
+  FK_CHECK_ARG(dtype == FK_F32 || dtype == FK_BF16, "%s: bad dtype %d", fn, dtype);
+  FK_CHECK_ARG(logits && ids && lengths && scores, "%s: null pointer", fn);
+  FK_CHECK_ARG(B > 0 && T > 0 && B * T < (1LL << 31), "%s: B = %lld, T = %lld", fn, (long long)B, (long long)T);
+  FK_CHECK_ARG(C >= 2 && C < (1LL << 31), "%s: C = %lld, must be >= 2 (a class beside the blank)", fn, (long long)C);
+  FK_CHECK_ARG(blank >= 0 && blank < C, "%s: blank = %lld outside [0, C = %lld)", fn, (long long)blank, (long long)C);
+  FK_CHECK_ARG(W >= 1 && W <= BEAM_MAX && K >= 1 && K <= BEAM_MAX, "%s: W = %lld, K = %lld outside the envelope (1 .. %d each)", fn, (long long)W,
+               (long long)K, BEAM_MAX);
+  FK_CHECK_ARG(T * W < (1LL << 31) - 1, "%s: T W = %lld nodes per sample", fn, (long long)(T * W));
+  FK_CHECK_ARG(nbest >= 1 && nbest <= W, "%s: nbest = %lld outside 1 .. W = %lld", fn, (long long)nbest, (long long)W);
+  FK_CHECK_ARG(ldt >= C && ldb >= ldt, "%s: row stride %lld below C = %lld (batch stride %lld)", fn, (long long)ldt, (long long)C, (long long)ldb);
+  FK_CHECK_ARG(ld_ids_h >= T && ld_ids_b >= (nbest - 1) * ld_ids_h + T, "%s: ids strides %lld / %lld below [nbest = %lld, T = %lld]", fn,
+               (long long)ld_ids_b, (long long)ld_ids_h, (long long)nbest, (long long)T);
+  const size_t need = beam_ws_carve(a.w, workspace, B, T, W, K);
+  FK_CHECK_ARG(workspace && workspace_bytes >= need, "%s: workspace too small (%zu bytes, fk_ctc_beam_workspace_bytes gives %zu)", fn, workspace_bytes, need);
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t rows = B * T;
+  const int Kc = (int)(K < C - 1 ? K : C - 1);
+  if (C > 1024)
+    FK_BY_DTYPE(dtype, TT, hipLaunchKernelGGL((ctc_beam_prune_kernel<TT, true>), dim3((unsigned)(rows < 8192 ? rows : 8192)), dim3(256), 0, s, (const TT*)logits, ldb, ldt, input_lengths, a.w, rows, (int)T, (int)C, (int)blank, (int)K, Kc));
+  else
+    FK_BY_DTYPE(dtype, TT, hipLaunchKernelGGL((ctc_beam_prune_kernel<TT, false>), dim3((unsigned)(fk_cdiv(rows, 4) < 8192 ? fk_cdiv(rows, 4) : 8192)), dim3(256), 0, s, (const TT*)logits, ldb, ldt, input_lengths, a.w, rows, (int)T, (int)C, (int)blank, (int)K, Kc));
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fk_set_error(FK_ELAUNCH, "%s(prune): %s", fn, hipGetErrorString(e));
+  a.logits = logits; a.ldb = ldb; a.ldt = ldt; a.input_lengths = input_lengths;
+  a.ids = ids; a.ld_ids_b = ld_ids_b; a.ld_ids_h = ld_ids_h; a.lengths = lengths; a.scores = scores; a.pad = pad;
+  a.T = (int)T; a.C = (int)C; a.blank = (int)blank; a.W = (int)W; a.K = (int)K; a.Kc = Kc; a.nbest = (int)nbest;
+  return FK_OK;
 }
 
 }  // namespace
@@ -1030,36 +1262,43 @@ size_t fk_ctc_beam_workspace_bytes(int64_t B, int64_t T, int64_t W, int64_t K) {
 int fk_ctc_beam_search(const void* logits, int64_t ldb, int64_t ldt, const int64_t* input_lengths, int64_t B, int64_t T, int64_t C, int64_t blank,
                        int64_t W, int64_t K, int64_t nbest, int64_t pad, int64_t* ids, int64_t ld_ids_b, int64_t ld_ids_h, int64_t* lengths,
                        float* scores, int dtype, void* workspace, size_t workspace_bytes, void* stream) {
-  FK_DT_CHECK("fk_ctc_beam_search");
-  FK_CHECK_ARG(logits && ids && lengths && scores, "fk_ctc_beam_search: null pointer");
-  FK_CHECK_ARG(B > 0 && T > 0 && B * T < (1LL << 31), "fk_ctc_beam_search: B = %lld, T = %lld", (long long)B, (long long)T);
-  FK_CHECK_ARG(C >= 2 && C < (1LL << 31), "fk_ctc_beam_search: C = %lld, must be >= 2 (a class beside the blank)", (long long)C);
-  FK_CHECK_ARG(blank >= 0 && blank < C, "fk_ctc_beam_search: blank = %lld outside [0, C = %lld)", (long long)blank, (long long)C);
-  FK_CHECK_ARG(W >= 1 && W <= BEAM_MAX && K >= 1 && K <= BEAM_MAX, "fk_ctc_beam_search: W = %lld, K = %lld outside the envelope (1 .. %d each)",
-               (long long)W, (long long)K, BEAM_MAX);
-  FK_CHECK_ARG(T * W < (1LL << 31) - 1, "fk_ctc_beam_search: T W = %lld nodes per sample", (long long)(T * W));
-  FK_CHECK_ARG(nbest >= 1 && nbest <= W, "fk_ctc_beam_search: nbest = %lld outside 1 .. W = %lld", (long long)nbest, (long long)W);
-  FK_CHECK_ARG(ldt >= C && ldb >= ldt, "fk_ctc_beam_search: row stride %lld below C = %lld (batch stride %lld)", (long long)ldt, (long long)C,
-               (long long)ldb);
-  FK_CHECK_ARG(ld_ids_h >= T && ld_ids_b >= (nbest - 1) * ld_ids_h + T, "fk_ctc_beam_search: ids strides %lld / %lld below [nbest = %lld, T = %lld]",
-               (long long)ld_ids_b, (long long)ld_ids_h, (long long)nbest, (long long)T);
   BeamArgs a;
-  const size_t need = beam_ws_carve(a.w, workspace, B, T, W, K);
-  FK_CHECK_ARG(workspace && workspace_bytes >= need, "fk_ctc_beam_search: workspace too small (%zu bytes, fk_ctc_beam_workspace_bytes gives %zu)", workspace_bytes,
-               need);
-  hipStream_t s = (hipStream_t)stream;
-  const int64_t rows = B * T;
-  const int Kc = (int)(K < C - 1 ? K : C - 1);
-  if (C > 1024)
-    FK_BY_DTYPE(dtype, TT, hipLaunchKernelGGL((ctc_beam_prune_kernel<TT, true>), dim3((unsigned)(rows < 8192 ? rows : 8192)), dim3(256), 0, s, (const TT*)logits, ldb, ldt, input_lengths, a.w, rows, (int)T, (int)C, (int)blank, (int)K, Kc));
-  else
-    FK_BY_DTYPE(dtype, TT, hipLaunchKernelGGL((ctc_beam_prune_kernel<TT, false>), dim3((unsigned)(fk_cdiv(rows, 4) < 8192 ? fk_cdiv(rows, 4) : 8192)), dim3(256), 0, s, (const TT*)logits, ldb, ldt, input_lengths, a.w, rows, (int)T, (int)C, (int)blank, (int)K, Kc));
-  FK_CHECK_LAUNCH("fk_ctc_beam_search(prune)");
-  a.logits = logits; a.ldb = ldb; a.ldt = ldt; a.input_lengths = input_lengths;
-  a.ids = ids; a.ld_ids_b = ld_ids_b; a.ld_ids_h = ld_ids_h; a.lengths = lengths; a.scores = scores; a.pad = pad;
-  a.T = (int)T; a.C = (int)C; a.blank = (int)blank; a.W = (int)W; a.K = (int)K; a.Kc = Kc; a.nbest = (int)nbest;
-  FK_BY_DTYPE(dtype, TT, hipLaunchKernelGGL((ctc_beam_kernel<TT>), dim3((unsigned)B), dim3(BEAM_THREADS), 0, s, a));
+  const int rc = beam_front("fk_ctc_beam_search", logits, ldb, ldt, input_lengths, B, T, C, blank, W, K, nbest, pad, ids, ld_ids_b, ld_ids_h, lengths, scores,
+                            dtype, workspace, workspace_bytes, stream, a);
+  if (rc != FK_OK) return rc;
+  FK_BY_DTYPE(dtype, TT, hipLaunchKernelGGL((ctc_beam_kernel<TT, false>), dim3((unsigned)B), dim3(BEAM_THREADS), 0, (hipStream_t)stream, a));
   FK_CHECK_LAUNCH("fk_ctc_beam_search(recursion)");
+  return FK_OK;
+}
+
+uint32_t fk_ngram_hash(uint32_t state, uint32_t token) { return ngram_hash(state, token); }
+
+int fk_ctc_beam_search_lm(const void* logits, int64_t ldb, int64_t ldt, const int64_t* input_lengths, int64_t B, int64_t T, int64_t C, int64_t blank,
+                          int64_t W, int64_t K, int64_t nbest, int64_t pad, const int32_t* lm_table, int64_t lm_cap, int64_t lm_max_probe,
+                          const float* lm_bow, const int32_t* lm_backoff, int64_t lm_states, const float* lm_uni_lp, const int32_t* lm_uni_next,
+                          int64_t lm_start_state, int64_t lm_order, float lm_weight, float length_bonus, int use_eos, int64_t* ids,
+                          int64_t ld_ids_b, int64_t ld_ids_h, int64_t* lengths, float* am, float* lm, float* total, int dtype, void* workspace,
+                          size_t workspace_bytes, void* stream) {
+  FK_CHECK_ARG(lm_table && lm_bow && lm_backoff && lm_uni_lp && lm_uni_next && lm && total, "fk_ctc_beam_search_lm: null pointer (LM tables / lm / total)");
+  FK_CHECK_ARG(((uintptr_t)lm_table & 15) == 0, "fk_ctc_beam_search_lm: the hash table must be 16-byte aligned");
+  FK_CHECK_ARG(lm_order >= 1 && lm_order <= 8, "fk_ctc_beam_search_lm: order = %lld outside 1 .. 8", (long long)lm_order);
+  FK_CHECK_ARG(lm_cap >= 1 && lm_cap < (1LL << 31) && (lm_cap & (lm_cap - 1)) == 0, "fk_ctc_beam_search_lm: cap = %lld is no power of two below 2^31", (long long)lm_cap);
+  FK_CHECK_ARG(lm_max_probe >= 1 && lm_max_probe <= lm_cap, "fk_ctc_beam_search_lm: max_probe = %lld outside 1 .. cap = %lld", (long long)lm_max_probe, (long long)lm_cap);
+  FK_CHECK_ARG(lm_states >= 1 && lm_states < (1LL << 31) && lm_start_state >= 0 && lm_start_state < lm_states,
+               "fk_ctc_beam_search_lm: states = %lld, start_state = %lld", (long long)lm_states, (long long)lm_start_state);
+  FK_CHECK_ARG(C < (1LL << 31) - 1, "fk_ctc_beam_search_lm: C = %lld leaves no id for the end of sentence", (long long)C);
+  FK_CHECK_ARG(std::isfinite(lm_weight) && std::isfinite(length_bonus), "fk_ctc_beam_search_lm: lm_weight = %g, length_bonus = %g must be finite",
+               (double)lm_weight, (double)length_bonus);
+  BeamLmArgs a;
+  const int rc = beam_front("fk_ctc_beam_search_lm", logits, ldb, ldt, input_lengths, B, T, C, blank, W, K, nbest, pad, ids, ld_ids_b, ld_ids_h, lengths, am,
+                            dtype, workspace, workspace_bytes, stream, a);
+  if (rc != FK_OK) return rc;
+  a.table = (const int4*)lm_table; a.bow = lm_bow; a.backoff = lm_backoff; a.uni_lp = lm_uni_lp; a.uni_next = lm_uni_next;
+  a.lm_out = lm; a.total_out = total; a.lm_weight = lm_weight; a.length_bonus = length_bonus;
+  a.S = (int)lm_states; a.cap_mask = (int)(lm_cap - 1); a.max_probe = (int)lm_max_probe; a.order = (int)lm_order;
+  a.start_state = (int)lm_start_state; a.use_eos = use_eos != 0;
+  FK_BY_DTYPE(dtype, TT, hipLaunchKernelGGL((ctc_beam_kernel<TT, true>), dim3((unsigned)B), dim3(BEAM_THREADS), 0, (hipStream_t)stream, a));
+  FK_CHECK_LAUNCH("fk_ctc_beam_search_lm(recursion)");
   return FK_OK;
 }
 

@@ -850,6 +850,20 @@ def ctc_beam_decode(logits: Tensor, input_lengths: Optional[Tensor] = None, blan
     return K.ctc_beam_search(logits, input_lengths, blank, beam_width, topk, nbest, pad)
 
 
+@torch.no_grad()
+def ctc_beam_decode_lm(logits: Tensor, lm, input_lengths: Optional[Tensor] = None, blank: int = 0, beam_width: int = 8, topk: Optional[int] = None,
+                       nbest: int = 1, lm_weight: float = 1.0, length_bonus: float = 0.0, use_eos: bool = True, pad: int = -100):
+    """Prefix beam search with n-gram shallow fusion: the backoff model `lm` (utils.ngram.NGramLM over the head's classes) takes part in
+    every selection, so a labelling the acoustic model alone would have dropped can stay in the beam, which no rescoring of the final
+    list can do.  The beam is ranked by CTC total + lm_weight * ln P_lm(labelling) + length_bonus * length, at the end (use_eos) + lm_weight
+    * ln P_lm(</s> | labelling) -> (ids int64 [B, nbest, T] padded with `pad`, lengths int64 [B, nbest], am fp32 [B, nbest] the pure CTC
+    score, lm fp32 [B, nbest] the unweighted ln P_lm, total fp32 [B, nbest] the ranking key), best first.  Two launches, nothing waits for
+    the host; the model's tables are copied to the device once."""
+    if logits.stride(-1) != 1:
+        logits = logits.contiguous()
+    return K.ctc_beam_search_lm(logits, lm, input_lengths, blank, beam_width, topk, nbest, lm_weight, length_bonus, use_eos, pad)
+
+
 class HeadCrossEntropy(torch.autograd.Function):
     """loss = mean CE(Linear([LN](x)), targets) over the rows whose target != ignore_index, WITHOUT a [rows, V] tensor in either
     direction: lm_head + F.cross_entropy of models/gpt2_model.py:205-210 and the `to_words` head of the notebook CE BrainFormer, used when

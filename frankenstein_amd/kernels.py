@@ -1220,6 +1220,36 @@ def ctc_beam_search(logits: Tensor, input_lengths: Optional[Tensor] = None, blan
     return ids, lengths, scores
 
 
+def ctc_beam_search_lm(logits: Tensor, lm, input_lengths: Optional[Tensor] = None, blank: int = 0, beam_width: int = 8, topk: Optional[int] = None,
+                       nbest: int = 1, lm_weight: float = 1.0, length_bonus: float = 0.0, use_eos: bool = True,
+                       pad: int = -100) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """ctc_beam_search with the backoff n-gram model `lm` (utils.ngram.NGramLM, or its compile()d tables) inside the selection:
+    key = CTC total + lm_weight * ln P_lm + length_bonus * length (semantics: include/franken_hip.h) -> (ids int64 [B, nbest, T], lengths
+    int64 [B, nbest], am fp32 [B, nbest] the pure CTC mass, lm fp32 [B, nbest] the unweighted ln P_lm, total fp32 [B, nbest] the final
+    key), best first.  The model's n_classes must be C."""
+    assert logits.dim() == 3 and logits.stride(2) == 1 and logits.dtype in (torch.float32, torch.bfloat16)
+    B, T, Cn = logits.shape
+    tables = lm.compile() if hasattr(lm, "compile") else lm
+    if tables.n_classes != Cn:
+        raise ValueError(f"the language model has {tables.n_classes} classes, the logits {Cn}")
+    K = min(32, Cn - 1) if topk is None else int(topk)
+    dev = logits.device
+    d = tables.to(dev)
+    il = _ctc_lengths(input_lengths, B, dev)
+    ids = torch.empty((B, nbest, T), dtype=torch.int64, device=dev)
+    lengths = torch.empty((B, nbest), dtype=torch.int64, device=dev)
+    am, lms, total = (torch.empty((B, nbest), dtype=torch.float32, device=dev) for _ in range(3))
+    nbytes = lib().fk_ctc_beam_workspace_bytes(B, T, beam_width, K)
+    ws, _ = _ws(nbytes, dev)
+    with _timed("ctc_beam_search_lm"):
+        call("fk_ctc_beam_search_lm", logits.data_ptr(), logits.stride(0), logits.stride(1), _ptr(il), B, T, Cn, blank, beam_width, K, nbest, pad,
+             d["table"].data_ptr(), tables.cap, tables.max_probe, d["bow"].data_ptr(), d["backoff"].data_ptr(), tables.n_states,
+             d["uni_lp"].data_ptr(), d["uni_next"].data_ptr(), tables.start_state, tables.order, float(lm_weight), float(length_bonus),
+             int(bool(use_eos)), ids.data_ptr(), ids.stride(0), ids.stride(1), lengths.data_ptr(), am.data_ptr(), lms.data_ptr(),
+             total.data_ptr(), fk_dtype(logits), _ptr(ws), nbytes, _stream())
+    return ids, lengths, am, lms, total
+
+
 class CeChunkState:
     """per-row running statistics of the chunked cross entropy (fk_ce_chunk_*)"""
 

@@ -62,6 +62,11 @@ class BrainFormerCTC(_FileBrainFormer):
     (W hypotheses) is rescored by the GPT `lm` on the device (GPT.rescore_nbest: total = CTC score + lm_weight * log p_lm + length_bonus *
     length; lm_prefix = the brain features a Franky conditions on) and the first k of the new order come back in the same forms, the
     scores being the totals.  A hypothesis that holds the blank id or another token outside the LM's vocabulary is not scored and ranks last.
+    decode(x, beam_width=W, nbest=k, ngram=m, ngram_weight=1.0, ngram_bonus=0.0, ngram_eos=True): the backoff n-gram model `m`
+    (utils.ngram.NGramLM over the output_dim classes) takes part in every selection of the search (engine.ctc_beam_decode_lm), the way a
+    phoneme head gets a language model at all; same forms, the scores being the fused totals.  With ngram= AND lm= the fused search fills
+    the whole beam, the GPT rescores it with the PURE CTC score as its acoustic score (the n-gram only decides which hypotheses reach the
+    list; its own score is not added a second time), and the first k of the GPT's order come back.
     utils.metrics.token_error_rate(targets, ids) of that result is the phoneme / token error rate."""
     config = Config
     head_name = 'to_words'
@@ -80,17 +85,24 @@ class BrainFormerCTC(_FileBrainFormer):
 
     @torch.no_grad()
     def decode(self, x, beam_width=None, topk=None, nbest=1, lm=None, lm_prefix=None, lm_weight=1.0, length_bonus=0.0, eos_token_id=None,
-               am_weight=1.0, bos_token_id=50256, max_nodes=None):
+               am_weight=1.0, bos_token_id=50256, max_nodes=None, ngram=None, ngram_weight=1.0, ngram_bonus=0.0, ngram_eos=True):
         logits = self.features(x)
         if beam_width is None:
-            if lm is not None:
-                raise ValueError("decode(lm=...) rescores a beam: give a beam_width")
+            if lm is not None or ngram is not None:
+                raise ValueError("decode(lm=...) rescores a beam and decode(ngram=...) steers one: give a beam_width")
             return E.ctc_greedy_decode(logits, blank=self.blank, pad=-100)
+        fused = dict(blank=self.blank, beam_width=beam_width, topk=topk, lm_weight=ngram_weight, length_bonus=ngram_bonus, use_eos=ngram_eos, pad=-100)
+        if lm is None and ngram is not None:
+            ids, lengths, _, _, total = E.ctc_beam_decode_lm(logits, ngram, nbest=nbest, **fused)
+            return (ids[:, 0], lengths[:, 0]) if nbest == 1 else (ids, lengths, total)
         if lm is None:
             ids, lengths, scores = E.ctc_beam_decode(logits, blank=self.blank, beam_width=beam_width, topk=topk, nbest=nbest, pad=-100)
             return (ids[:, 0], lengths[:, 0]) if nbest == 1 else (ids, lengths, scores)
         # the WHOLE final beam is rescored (GPT.rescore_nbest) and the first nbest places of the new order come back; scores = total
-        ids, lengths, scores = E.ctc_beam_decode(logits, blank=self.blank, beam_width=beam_width, topk=topk, nbest=beam_width, pad=-100)
+        if ngram is not None:                             # the n-gram decides which hypotheses reach the list; the GPT scores them on am
+            ids, lengths, scores, _, _ = E.ctc_beam_decode_lm(logits, ngram, nbest=beam_width, **fused)
+        else:
+            ids, lengths, scores = E.ctc_beam_decode(logits, blank=self.blank, beam_width=beam_width, topk=topk, nbest=beam_width, pad=-100)
         ids, lengths, _, _, total, _, _ = lm.rescore_nbest(ids, lengths, scores, prefix=lm_prefix, lm_weight=lm_weight, am_weight=am_weight,
                                                            length_bonus=length_bonus, bos_token_id=bos_token_id, eos_token_id=eos_token_id,
                                                            max_nodes=max_nodes)

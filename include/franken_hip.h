@@ -572,6 +572,45 @@ int fk_ctc_beam_search(const void* logits, int64_t ldb, int64_t ldt, const int64
                        int64_t W, int64_t K, int64_t nbest, int64_t pad, int64_t* ids, int64_t ld_ids_b, int64_t ld_ids_h, int64_t* lengths,
                        float* scores, int dtype, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- CTC prefix beam search with n-gram shallow fusion (csrc/ctc.hip): fk_ctc_beam_search with a backoff n-gram language model inside
+ *      the selection.  Semantics of this build (tests/ctc_lm_ref.py restates them in float64); all arithmetic is fp32.
+ *   The LM factor of a prefix depends on the prefix alone, so the acoustic recursion (pb, pnb, total, the flow between resident prefixes,
+ *   the candidate rule) is EXACTLY fk_ctc_beam_search's.  Only the selection key changes:
+ *     key(p) = total(p) + lmw(p);   lmw(()) = 0;   lmw(p + (c,)) = lmw(p) + (lm_weight * ln P_lm(c | p) + length_bonus)
+ *   (the product, then the bonus, then the sum, each rounded).  A slot also carries lm(p) = the unweighted sum of ln P_lm and the LM state
+ *   of p.  A new prefix gets its term by one look-up (state of its parent slot, its label); a resident prefix keeps its own; a prefix that
+ *   returns to the beam gets the same bits (the same sum from the same parent value).  The W entries with the largest key survive, an
+ *   entry whose total is -inf never; exact ties as in fk_ctc_beam_search.  The blank is never looked up.  use_eos != 0: the final beam is
+ *   put in order once more by key + lm_weight * ln P_lm(</s> | state), equal keys in the order of the last selection, and lm includes
+ *   that term.  Result, best first, the first nbest: ids and lengths as fk_ctc_beam_search, am fp32 [B, nbest] = total (the pure CTC mass:
+ *   fk_ctc_beam_search's scores), lm fp32 [B, nbest] (unweighted), total fp32 [B, nbest] = the final key.  A slot without hypothesis:
+ *   length 0, am = lm = total = -inf, a row of pad.  With lm_weight = 0, length_bonus = 0 and use_eos = 0 ids, lengths and am are
+ *   fk_ctc_beam_search's bits.
+ *   The model (frankenstein_amd/utils/ngram.py compiles and validates it): an LM token id is a class id, the end of sentence is id C.  A
+ *   state is a context that occurs in the model, state 0 the empty context, lm_start_state the state of (<s>,).
+ *     lm_table    int32 [lm_cap][4], 16-byte aligned: open addressing, {state, token, bits of the fp32 ln p, next state}, state -1 =
+ *                 empty; lm_cap a power of two (>= 2 x entries); the home of (state, token) is fk_ngram_hash(state, token) & (lm_cap - 1)
+ *                 with h = state * 0x9E3779B1 ^ token * 0x85EBCA6B; h ^= h >> 15; h *= 0x2C1B3C6D; h ^= h >> 12 (uint32), linear probing;
+ *                 lm_max_probe = the largest number of entries a successful look-up reads
+ *     lm_bow      fp32 [lm_states] ln of the backoff weight; lm_backoff int32 [lm_states] the state of the context without its first
+ *                 symbol (strictly shorter)
+ *     lm_uni_lp   fp32 [C + 1], lm_uni_next int32 [C + 1]: state 0, dense
+ *   Look-up of (s, c), acc = 0, at most lm_order rounds: s == 0 -> (acc + uni_lp[c], uni_next[c]); else read at most lm_max_probe entries
+ *   from the home of (s, c): a hit -> (acc + ln p, next); an empty entry or the last probe -> acc += bow[s], s = backoff[s]; behind the
+ *   last round the unigram.  The device cannot check the tables: every loop is bounded by lm_order * lm_max_probe, every state read from a
+ *   table is clamped into [0, lm_states), a token into [0, C], a table index by lm_cap - 1.  A malformed table gives wrong scores, never
+ *   an unbounded loop or an access outside the tables.
+ *   Envelope and workspace of fk_ctc_beam_search (fk_ctc_beam_workspace_bytes; the LM state lives in LDS), and 1 <= lm_order <= 8, lm_cap a
+ *   power of two, 1 <= lm_max_probe <= lm_cap, 0 <= lm_start_state < lm_states, finite weights, no null table: FK_EINVAL beyond, no launch.
+ *   Two launches (the first is fk_ctc_beam_search's), no atomics, the same bits every run, nothing waits for the host.                  */
+uint32_t fk_ngram_hash(uint32_t state, uint32_t token);
+int fk_ctc_beam_search_lm(const void* logits, int64_t ldb, int64_t ldt, const int64_t* input_lengths, int64_t B, int64_t T, int64_t C, int64_t blank,
+                          int64_t W, int64_t K, int64_t nbest, int64_t pad, const int32_t* lm_table, int64_t lm_cap, int64_t lm_max_probe,
+                          const float* lm_bow, const int32_t* lm_backoff, int64_t lm_states, const float* lm_uni_lp, const int32_t* lm_uni_next,
+                          int64_t lm_start_state, int64_t lm_order, float lm_weight, float length_bonus, int use_eos, int64_t* ids,
+                          int64_t ld_ids_b, int64_t ld_ids_h, int64_t* lengths, float* am, float* lm, float* total, int dtype, void* workspace,
+                          size_t workspace_bytes, void* stream);
+
 /* ---- n-best rescoring with a language model (csrc/rescore.hip): the hypotheses of one sentence (fk_ctc_beam_search's n-best list) share
  *      token prefixes, so every DISTINCT prefix is scored once: the list becomes a trie, the trie one packed GPT forward under an ancestor
  *      mask, the head goes through fk_head_ce_fwd (no [rows, V] logits), and the sums, the combination with the acoustic score and the

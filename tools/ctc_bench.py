@@ -6,7 +6,11 @@ No parent commit has this path: torch's number is the only yardstick.
 python tools/ctc_bench.py --beam W [rounds] [reps]: the prefix beam search (engine.ctc_beam_decode, beam width W, both launches) beside the
 greedy decode on the same GPU and the same logits, and beside the float64 host restatement (tests/ctc_beam_ref.py) on the host, at the
 project's vocabulary (32 frames, 50258 classes, 20 candidates) and at a phoneme head (768 frames, 41 classes, min(32, C - 1) candidates),
-B = 32 each.  torch has no CTC beam search: the host restatement is the only alternative a user has."""
+B = 32 each.  torch has no CTC beam search: the host restatement is the only alternative a user has.
+
+python tools/ctc_bench.py --beam W --ngram ORDER [rounds] [reps]: also the search with n-gram shallow fusion (engine.ctc_beam_decode_lm) on
+the same logits, in the same interleaved rounds: an interpolated Witten-Bell model of that order from 2000 seeded Zipf-distributed
+sequences over the head's classes (utils.ngram), with its table size and max_probe, and what the fusion adds per frame."""
 import sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -20,6 +24,9 @@ argv = sys.argv[1:]
 beam = int(argv.pop(argv.index("--beam") + 1)) if "--beam" in argv else None
 if beam is not None:
     argv.remove("--beam")
+ngram = int(argv.pop(argv.index("--ngram") + 1)) if "--ngram" in argv else None
+if ngram is not None:
+    argv.remove("--ngram")
 rounds = int(argv[0]) if len(argv) > 0 else 7
 reps = int(argv[1]) if len(argv) > 1 else 10
 dev = torch.device("cuda")
@@ -42,6 +49,11 @@ for B, T, C, Kc in (BEAM_SHAPES if beam is not None else []):
     logits = 2.0 * torch.randn(B, T, C, device=dev, generator=g)
     logits[:, :, blank] += 3.0
     cases = {"beam": lambda: E.ctc_beam_decode(logits, None, blank, beam, Kc, beam), "greedy": lambda: E.ctc_greedy_decode(logits, None, blank)}
+    if ngram is not None:
+        from frankenstein_amd.utils.ngram import NGramLM, zipf_sequences
+        lm = NGramLM.from_corpus(zipf_sequences(2000, C, blank, (5, 20) if C > 1024 else (10, 40), 0, n_types=min(C - 1, 5000)), ngram, C)
+        tab = lm.compile()
+        cases["fused"] = lambda: E.ctc_beam_decode_lm(logits, lm, None, blank, beam, Kc, beam, 0.8, 0.5)
     for f in cases.values():
         f()
     torch.cuda.synchronize()
@@ -62,6 +74,13 @@ for B, T, C, Kc in (BEAM_SHAPES if beam is not None else []):
     print(f"(B, T, C) = ({B}, {T}, {C})  W {beam} K {Kc} nbest {beam}:  " + "  ".join(f"{k} {t:9.1f} us" for k, t in med.items())
           + f"  host float64 restatement {host * 1e3:9.1f} ms ({n_host} samples timed, scaled to {B})  best hypothesis differs from greedy in {differ} of {B}"
           + f"  best ids equal the restatement's: {same}", flush=True)
+    if ngram is not None:
+        spread = {k: (min(v), max(v)) for k, v in times.items()}
+        moved = int((cases["fused"]()[0][:, 0] != ids[:, 0]).any(1).sum())
+        print(f"    order {ngram}: {tab.n_entries} n-grams in {tab.cap} entries ({tab.cap * 16 / 1024:.0f} KiB), {tab.n_states} states, max_probe {tab.max_probe};  "
+              f"fused - beam {med['fused'] - med['beam']:+9.1f} us = {(med['fused'] - med['beam']) / T:+.3f} us per frame, fused / beam {med['fused'] / med['beam']:.2f};  "
+              f"rounds min .. max: beam {spread['beam'][0]:.1f} .. {spread['beam'][1]:.1f} us, fused {spread['fused'][0]:.1f} .. {spread['fused'][1]:.1f} us;  "
+              f"the best hypothesis moves in {moved} of {B}", flush=True)
 
 for B, T, C, L in (SHAPES if beam is None else []):
     blank = C - 1
