@@ -25,9 +25,10 @@
 //                    tests/ctc_lm_ref.py): launch 1 as above, launch 2 the LM instantiation of ctc_beam_kernel, whose slots also carry the
 //                    LM term, the LM sum and the LM state of their prefix (in LDS); the model is a state machine over one hash table
 //
+// row_lse, the backward and the prune kernel share one row frame (RowFrame) and one launch (CTC_LAUNCH_ROWS: the route and the grid).
 // Device-side clamps (every access stays inside the buffers whatever the integers say): input_length into [0, T], target_length into
-// [0, Lmax], a label into [0, C) and off the blank (a label equal to the blank becomes blank - 1, or 1 when the blank is 0).  With a
-// clamped label the loss is meaningless but defined.
+// [0, Lmax] (clamp_len), a label into [0, C) and off the blank (a label equal to the blank becomes blank - 1, or 1 when the blank is
+// 0).  With a clamped label the loss is meaningless but defined.
 #include <math.h>
 
 #include "fk_common.h"
@@ -65,83 +66,99 @@ static inline size_t ctc_ws_carve(CtcWs& w, void* base, int64_t B, int64_t T, in
 }
 
 // ---- group reductions: the group is one wave (shuffles only) or the whole workgroup (through sh, >= 8 floats; barriers) ---------------
+template <typename V, typename Op> FK_DEV V across_waves(V v, V* sh, V init, Op op) {   // the waves' values folded in wave order from `init`
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  v = init;
+  for (int i = 0; i < (int)(blockDim.x >> 6); ++i) v = op(v, sh[i]);
+  return v;
+}
 template <bool BLOCK> FK_DEV float group_max(float v, float* sh) {
   v = wave_max(v);
-  if constexpr (BLOCK) {
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    v = -INFINITY;
-    for (int i = 0; i < (int)(blockDim.x >> 6); ++i) v = fmaxf(v, sh[i]);
-  }
+  if constexpr (BLOCK) v = across_waves(v, sh, -INFINITY, [](float a, float b) { return fmaxf(a, b); });
   return v;
 }
 template <bool BLOCK> FK_DEV float group_sum(float v, float* sh) {
   v = wave_sum(v);
-  if constexpr (BLOCK) {
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    v = 0.0f;
-    for (int i = 0; i < (int)(blockDim.x >> 6); ++i) v += sh[i];
-  }
+  if constexpr (BLOCK) v = across_waves(v, sh, 0.0f, [](float a, float b) { return a + b; });
   return v;
 }
 FK_DEV int block_min_int(int v, int* sh) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  for (int i = 0; i < (int)(blockDim.x >> 6); ++i) v = min(v, sh[i]);
-  return v;
+  return across_waves(v, sh, v, [](int a, int b) { return min(a, b); });
 }
 
-// Row sweep on the shared vector I/O: scalar elements up to the row's first 16-byte boundary, whole vectors, a scalar tail.  Any row
-// stride and any C take the vector body (C = 50258 in fp32 leaves every other row 8 bytes off the boundary).
-template <typename T> FK_DEV int row_head(const T* p, int C) {
-  constexpr int N = VecIO<T>::N;
-  const int h = (int)((N - (int)(((uintptr_t)p / sizeof(T)) % N)) % N);
-  return h < C ? h : C;
+// input_lengths[b] into [0, T], target_lengths[b] into [0, Lmax]; no array: the full length
+FK_DEV int clamp_len(const int64_t* lengths, int b, int hi) {
+  if (!lengths) return hi;
+  const int64_t v = lengths[b];
+  return v < 0 ? 0 : (v > hi ? hi : (int)v);
 }
+
+// running (max, sum of exponentials) per lane, rescaled once per vector; exp(-inf - -inf) is never formed; returns the vector's own maximum
+template <int N> FK_DEV float lse_push(float& m, float& s, const float (&v)[N]) {
+  float best = v[0];
+#pragma unroll
+  for (int e = 1; e < N; ++e) best = fmaxf(best, v[e]);
+  const float vm = fmaxf(m, best);
+  if (vm > -INFINITY) {
+    float acc = s * __expf(m - vm);
+#pragma unroll
+    for (int e = 0; e < N; ++e) acc += __expf(v[e] - vm);
+    s = acc;
+    m = vm;
+  }
+  return best;
+}
+FK_DEV void lse_push(float& m, float& s, float x) { const float v[1] = {x}; lse_push(m, s, v); }
+
+// The frame of a row-parallel kernel (row_lse, backward, beam prune).  A group of G threads owns a row: the whole workgroup (BLOCK: one
+// row a pass), or one wave of the four (four rows a pass, wave `sub` the row base + sub, base from f.first in steps of f.step: a
+// block-uniform trip count); thread gl takes every G-th element or vector of the row.  A row is swept on the shared vector I/O: scalar
+// elements up to its first 16-byte boundary (head), nvec whole vectors, a scalar tail.  Any row stride and any C take the vector body (C =
+// 50258 in fp32 leaves every other row 8 bytes off the boundary).  The sweeps stay with the kernels: prune loads ahead, the backward stores.
+template <typename T, bool BLOCK> struct RowFrame {
+  static constexpr int N = VecIO<T>::N, G = BLOCK ? 256 : 64, RPB = BLOCK ? 1 : 4;
+  const int gl = BLOCK ? threadIdx.x : (threadIdx.x & 63), sub = BLOCK ? 0 : (threadIdx.x >> 6);
+  const int64_t first = (int64_t)blockIdx.x * RPB, step = (int64_t)gridDim.x * RPB;
+  FK_DEV static int row_head(const T* p, int C) {       // elements in front of the first 16-byte boundary of the row at p, at most C
+    const int h = (int)((N - (int)(((uintptr_t)p / sizeof(T)) % N)) % N);
+    return h < C ? h : C;
+  }
+  struct Split { int head, nvec, tail; };               // [0, head) scalar, nvec vectors from head, [tail, C) scalar
+  FK_DEV static Split split(int head, int C) { return {head, (C - head) / N, head + (C - head) / N * N}; }
+  // the row's logsumexp from the lanes' (m, s); every thread of the workgroup calls it (sh: 8 floats; under BLOCK it holds barriers)
+  FK_DEV static float finish(float m, float s, float* sh) {
+    const float M = group_max<BLOCK>(m, sh);
+    const float tot = group_sum<BLOCK>(m > -INFINITY ? s * __expf(m - M) : 0.0f, sh);
+    return M + logf(tot);
+  }
+};
 
 // ---- launch 1: row_lse -------------------------------------------------------------------------------------------------------
-// running (max, sum of exponentials) per lane, rescaled once per vector; exp(-inf - -inf) is never formed
-FK_DEV void lse_push(float& m, float& s, float x) {
-  const float mn = fmaxf(m, x);
-  if (mn > -INFINITY) { s = s * __expf(m - mn) + __expf(x - mn); m = mn; }
-}
 template <typename T, bool BLOCK>
 __global__ __launch_bounds__(256) void ctc_row_lse_kernel(const T* logits, int64_t ldb, int64_t ldt, float* row_lse, int64_t rows, int T_, int C) {
-  constexpr int N = VecIO<T>::N, G = BLOCK ? 256 : 64, RPB = BLOCK ? 1 : 4;
+  const RowFrame<T, BLOCK> f{};
+  constexpr int N = f.N, G = f.G;
   __shared__ float sh[8];
-  const int gl = BLOCK ? threadIdx.x : (threadIdx.x & 63), sub = BLOCK ? 0 : (threadIdx.x >> 6);
-  for (int64_t base = (int64_t)blockIdx.x * RPB; base < rows; base += (int64_t)gridDim.x * RPB) {   // block-uniform trip count
-    const int64_t row = base + sub;
+  for (int64_t base = f.first; base < rows; base += f.step) {
+    const int64_t row = base + f.sub;
     float m = -INFINITY, s = 0.0f;
     if (row < rows) {
       const T* lr = logits + (row / T_) * ldb + (row % T_) * ldt;
-      const int head = row_head<T>(lr, C), nvec = (C - head) / N;
-      for (int c = gl; c < head; c += G) lse_push(m, s, to_f32<T>(lr[c]));
-      for (int i = gl; i < nvec; i += G) {
+      const auto sp = f.split(f.row_head(lr, C), C);
+      for (int c = f.gl; c < sp.head; c += G) lse_push(m, s, to_f32<T>(lr[c]));
+      for (int i = f.gl; i < sp.nvec; i += G) {
         float v[N];
-        VecIO<T>::load(lr + head + i * N, v);
-        float vm = m;
-#pragma unroll
-        for (int e = 0; e < N; ++e) vm = fmaxf(vm, v[e]);
-        if (vm > -INFINITY) {
-          float acc = s * __expf(m - vm);
-#pragma unroll
-          for (int e = 0; e < N; ++e) acc += __expf(v[e] - vm);
-          s = acc;
-          m = vm;
-        }
+        VecIO<T>::load(lr + sp.head + i * N, v);
+        lse_push(m, s, v);
       }
-      for (int c = head + nvec * N + gl; c < C; c += G) lse_push(m, s, to_f32<T>(lr[c]));
+      for (int c = sp.tail + f.gl; c < C; c += G) lse_push(m, s, to_f32<T>(lr[c]));
     }
-    const float M = group_max<BLOCK>(m, sh);
-    const float tot = group_sum<BLOCK>(m > -INFINITY ? s * __expf(m - M) : 0.0f, sh);
-    if (row < rows && gl == 0) row_lse[row] = M + logf(tot);
+    const float lse = f.finish(m, s, sh);
+    if (row < rows && f.gl == 0) row_lse[row] = lse;
   }
 }
 
@@ -177,16 +194,11 @@ __global__ __launch_bounds__(WAVE ? 64 : CTC_MAX_THREADS) void ctc_lattice_kerne
   const int b = blockIdx.x, dir = blockIdx.y, s = threadIdx.x;
 
   // lengths, clamped; without target_lengths: the leading entries that differ from pad_value
-  int Tb = a.T;
-  if (a.input_lengths) {
-    const int64_t v = a.input_lengths[b];
-    Tb = v < 0 ? 0 : (v > a.T ? a.T : (int)v);
-  }
+  const int Tb = clamp_len(a.input_lengths, b, a.T);
   const int64_t* tg = a.targets + (int64_t)b * a.ldtgt;
   int Lb;
   if (a.target_lengths) {
-    const int64_t v = a.target_lengths[b];
-    Lb = v < 0 ? 0 : (v > a.Lmax ? a.Lmax : (int)v);
+    Lb = clamp_len(a.target_lengths, b, a.Lmax);
   } else {
     int f = a.Lmax;
     for (int i = s; i < a.Lmax; i += blockDim.x)
@@ -337,12 +349,13 @@ struct CtcBwdArgs {
 
 template <typename T, bool BLOCK>
 __global__ __launch_bounds__(256) void ctc_bwd_kernel(CtcBwdArgs a) {
-  constexpr int N = VecIO<T>::N, G = BLOCK ? 256 : 64, RPB = BLOCK ? 1 : 4;
+  const RowFrame<T, BLOCK> f{};
+  constexpr int N = f.N, G = f.G;
   __shared__ float sh[8];
-  const int gl = BLOCK ? threadIdx.x : (threadIdx.x & 63), sub = BLOCK ? 0 : (threadIdx.x >> 6);
+  const int gl = f.gl;
   const int64_t rows = (int64_t)a.B * a.T;
-  for (int64_t base = (int64_t)blockIdx.x * RPB; base < rows; base += (int64_t)gridDim.x * RPB) {   // block-uniform trip count
-    const int64_t row = base + sub;
+  for (int64_t base = f.first; base < rows; base += f.step) {
+    const int64_t row = base + f.sub;
     int b = 0, t = 0, Lb = 0;
     float g = 0.0f, raw = 0.0f, lse = 0.0f;
     const T* lr = nullptr;
@@ -363,17 +376,17 @@ __global__ __launch_bounds__(256) void ctc_bwd_kernel(CtcBwdArgs a) {
       full = t < Tb && !infeasible;
       // a frame past the sample's end is exactly zero; an infeasible sample is zero under zero_infinity and NaN without, as torch's
       const float fill = (t < Tb && infeasible && !a.zero_inf) ? NAN : 0.0f;
-      const int hl = row_head<T>(lr, a.C), hd = row_head<T>(dr, a.C);
-      const int head = hl == hd ? hl : a.C, nvec = (a.C - head) / N;      // rows that disagree about the boundary go element by element
-      for (int c = gl; c < head; c += G) dr[c] = from_f32<T>(full ? g * __expf(to_f32<T>(lr[c]) - lse) : fill);
-      for (int i = gl; i < nvec; i += G) {
+      const int hl = f.row_head(lr, a.C), hd = f.row_head(dr, a.C);
+      const auto sp = f.split(hl == hd ? hl : a.C, a.C);             // rows that disagree about the boundary go element by element
+      for (int c = gl; c < sp.head; c += G) dr[c] = from_f32<T>(full ? g * __expf(to_f32<T>(lr[c]) - lse) : fill);
+      for (int i = gl; i < sp.nvec; i += G) {
         float v[N], o[N];
-        if (full) VecIO<T>::load(lr + head + i * N, v);
+        if (full) VecIO<T>::load(lr + sp.head + i * N, v);
 #pragma unroll
         for (int e = 0; e < N; ++e) o[e] = full ? g * __expf(v[e] - lse) : fill;
-        VecIO<T>::store(dr + head + i * N, o);
+        VecIO<T>::store(dr + sp.head + i * N, o);
       }
-      for (int c = head + nvec * N + gl; c < a.C; c += G) dr[c] = from_f32<T>(full ? g * __expf(to_f32<T>(lr[c]) - lse) : fill);
+      for (int c = sp.tail + gl; c < a.C; c += G) dr[c] = from_f32<T>(full ? g * __expf(to_f32<T>(lr[c]) - lse) : fill);
     }
     __syncthreads();                                    // the classes of the target are rewritten below, behind the sweep's stores
     if (BLOCK ? full : true) {                          // (block-uniform under BLOCK: the reductions inside hold barriers)
@@ -427,11 +440,7 @@ __global__ __launch_bounds__(256) void ctc_collapse_kernel(const int64_t* am, in
   const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t* a = am + (int64_t)b * lda;
   int64_t* o = ids + (int64_t)b * ldi;
-  int Tb = T;
-  if (input_lengths) {
-    const int64_t v = input_lengths[b];
-    Tb = v < 0 ? 0 : (v > T ? T : (int)v);
-  }
+  const int Tb = clamp_len(input_lengths, b, T);
   int run = 0;
   for (int t0 = 0; t0 < Tb; t0 += 256) {                // block-uniform trip count
     const int t = t0 + threadIdx.x;
@@ -502,14 +511,6 @@ FK_DEV float f32_unordered(unsigned k) { return __uint_as_float((k & 0x80000000u
 FK_DEV unsigned long long beam_key(float x, int idx) { return ((unsigned long long)f32_ordered(x) << 32) | (unsigned)(0x7fffffff - idx); }
 FK_DEV int key_index(unsigned long long k) { return 0x7fffffff - (int)(unsigned)(k & 0xffffffffull); }
 FK_DEV float key_value(unsigned long long k) { return f32_unordered((unsigned)(k >> 32)); }
-FK_DEV unsigned long long wave_max_u64(unsigned long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned long long w = __shfl_xor(v, o, 64);
-    v = w > v ? w : v;
-  }
-  return v;
-}
 // LDS that the lanes of ONE wave hand to each other: the accesses stay in program order for the compiler and the LDS serves a wave's
 // instructions in order
 FK_DEV void wave_lds_sync() {
@@ -574,37 +575,34 @@ FK_DEV void prune_push(PruneState& p, float x, int c, bool valid) {   // called 
 template <typename T, bool BLOCK>
 __global__ __launch_bounds__(256) void ctc_beam_prune_kernel(const T* logits, int64_t ldb, int64_t ldt, const int64_t* input_lengths, BeamWs w,
                                                               int64_t rows, int T_, int C, int blank, int K, int Kc) {
-  constexpr int N = VecIO<T>::N, G = BLOCK ? 256 : 64, RPB = BLOCK ? 1 : 4;
+  const RowFrame<T, BLOCK> f{};
+  constexpr int N = f.N, G = f.G;
   __shared__ float sh[8];
   __shared__ unsigned long long sh_buf[4][PRUNE_CAP];
-  const int gl = BLOCK ? threadIdx.x : (threadIdx.x & 63), sub = BLOCK ? 0 : (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int64_t base = (int64_t)blockIdx.x * RPB; base < rows; base += (int64_t)gridDim.x * RPB) {   // block-uniform trip count
-    const int64_t row = base + sub;
-    bool live = row < rows;                             // wave-uniform; block-uniform under BLOCK
-    if (live && input_lengths) {
-      const int64_t v = input_lengths[row / T_];
-      live = (row % T_) < (v < 0 ? 0 : (v > T_ ? T_ : v));
-    }
+  const int gl = f.gl, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int64_t base = f.first; base < rows; base += f.step) {
+    const int64_t row = base + f.sub;
+    const bool live = row < rows && (row % T_) < clamp_len(input_lengths, (int)(row / T_), T_);   // wave-uniform; block-uniform under BLOCK
     float m = -INFINITY, s = 0.0f;
     PruneState p{sh_buf[wave], 0ull, -INFINITY, 0, Kc, lane};
     const T* lr = logits;
     if (live) {
       lr = logits + (row / T_) * ldb + (row % T_) * ldt;
-      const int head = row_head<T>(lr, C), nvec = (C - head) / N, tail = head + nvec * N;
-      if (head > 0) {                                   // fewer than N elements: one step of the group
-        const bool ok = gl < head;
-        const float x = ok ? to_f32<T>(lr[gl]) : -INFINITY;
+      const auto sp = f.split(f.row_head(lr, C), C);
+      auto scalars = [&](int c, int end) {              // fewer than N elements: one step of the group
+        const bool ok = c < end;
+        const float x = ok ? to_f32<T>(lr[c]) : -INFINITY;
         if (ok) lse_push(m, s, x);
-        prune_push(p, x, gl, ok && gl != blank);
-      }
-      for (int i0 = 0; i0 < nvec; i0 += PRUNE_U * G) {  // wave-uniform trip count: prune_push holds ballots
+        prune_push(p, x, c, ok && c != blank);
+      };
+      if (sp.head > 0) scalars(gl, sp.head);
+      for (int i0 = 0; i0 < sp.nvec; i0 += PRUNE_U * G) {  // wave-uniform trip count: prune_push holds ballots
         float v[PRUNE_U][N];
 #pragma unroll
         for (int u = 0; u < PRUNE_U; ++u) {             // PRUNE_U vectors a lane in flight before the first is looked at
           const int i = i0 + u * G + gl;
-          if (i < nvec) {
-            VecIO<T>::load(lr + head + i * N, v[u]);
+          if (i < sp.nvec) {
+            VecIO<T>::load(lr + sp.head + i * N, v[u]);
           } else {
 #pragma unroll
             for (int e = 0; e < N; ++e) v[u][e] = -INFINITY;
@@ -612,39 +610,21 @@ __global__ __launch_bounds__(256) void ctc_beam_prune_kernel(const T* logits, in
         }
 #pragma unroll
         for (int u = 0; u < PRUNE_U; ++u) {
-          const int i = i0 + u * G + gl, c0 = head + i * N;
-          const bool ok = i < nvec;
-          float best = v[u][0];
-#pragma unroll
-          for (int e = 1; e < N; ++e) best = fmaxf(best, v[u][e]);
-          const float vm = fmaxf(m, best);
-          if (ok && vm > -INFINITY) {
-            float acc = s * __expf(m - vm);
-#pragma unroll
-            for (int e = 0; e < N; ++e) acc += __expf(v[u][e] - vm);
-            s = acc;
-            m = vm;
-          }
+          const int i = i0 + u * G + gl, c0 = sp.head + i * N;
+          const bool ok = i < sp.nvec;
+          const float best = lse_push(m, s, v[u]);     // (a vector behind the row is all -inf: it leaves m and s as they are)
           if (__ballot(ok && best >= p.bar_x) != 0ull) {
 #pragma unroll
             for (int e = 0; e < N; ++e) prune_push(p, v[u][e], c0 + e, ok && c0 + e != blank);
           }
         }
       }
-      if (tail < C) {
-        const int c = tail + gl;
-        const bool ok = c < C;
-        const float x = ok ? to_f32<T>(lr[c]) : -INFINITY;
-        if (ok) lse_push(m, s, x);
-        prune_push(p, x, c, ok && c != blank);
-      }
+      if (sp.tail < C) scalars(sp.tail + gl, C);
       p.cnt = prune_compact(p.buf, p.cnt, Kc, lane);    // the wave's best, descending
       if (lane >= p.cnt && lane < BEAM_MAX) p.buf[lane] = 0ull;
     }
-    const float M = group_max<BLOCK>(m, sh);
-    const float tot = group_sum<BLOCK>(m > -INFINITY ? s * __expf(m - M) : 0.0f, sh);   // its barriers order sh_buf for the merge
+    const float lse = f.finish(m, s, sh);          // its barriers order sh_buf for the merge
     if (live) {
-      const float lse = M + logf(tot);
       if (gl == 0) { w.lse[row] = lse; w.lpb[row] = to_f32<T>(lr[blank]) - lse; }
       // the lists of the group's waves merged by rank; a slot behind the Kc-th holds (-inf, -1)
       constexpr int NW = BLOCK ? 4 : 1;
@@ -807,6 +787,15 @@ FK_DEV void lm_lookup(const BeamLmArgs& a, const int (&state)[N], const int (&to
   }
 }
 
+// The three sums that are formed for a key and again when the chosen entry becomes a slot: the total of a resident prefix from this
+// frame's pb' and pnb'; what slot i (of a beam's last / pb / tot arrays) sends to its extension by class c at log-probability lp (a repeat
+// of the last label continues only what ended in a blank); the weighted LM term of a prefix with a token of ln P = lp behind it
+FK_DEV float resident_total(float npb, float npnb) { return log_add(npb, npnb); }
+FK_DEV float extended_total(int c, const int* last, const float* pb, const float* tot, int i, float lp) {
+  return (c == last[i] ? pb[i] : tot[i]) + lp;
+}
+FK_DEV float extended_lmw(float lmw, float weight, float lp, float bonus) { return lmw + lm_term(weight, lp, bonus); }
+
 template <typename T, bool LM>
 __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(std::conditional_t<LM, BeamLmArgs, BeamArgs> a) {
   constexpr int M = BEAM_MAX;
@@ -832,11 +821,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(std::conditional
   __shared__ int s_selpar[M], s_sellab[M], s_selnode[M], s_selfirst[M];   // the chosen new prefixes: parent slot, label, node, its first child
   static_assert((10 * 2 * M + 2 * M + 3 * M + 4 * M + 4 + 4 * M + 2 * BEAM_ROW) * 4 + (BEAM_THREADS + M * BEAM_EPT + 16 + M) * 8 <= 16 * 1024, "ctc_beam_kernel: LDS budget");
   const int tid = threadIdx.x, b = blockIdx.x, W = a.W, Kc = a.Kc;
-  int Tb = a.T;
-  if (a.input_lengths) {
-    const int64_t v = a.input_lengths[b];
-    Tb = v < 0 ? 0 : (v > a.T ? a.T : (int)v);
-  }
+  const int Tb = clamp_len(a.input_lengths, b, a.T);
   int4* nodes = a.w.nodes + (size_t)b * ((size_t)a.T * W + 1);
   const T* lg = (const T*)a.logits + (int64_t)b * a.ldb;
   const int64_t row0 = (int64_t)b * a.T;
@@ -872,82 +857,10 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(std::conditional
     else if (tid == M) pf_f = a.w.lpb[row];
     else if (tid == M + 1) pf_f = a.w.lse[row];
   };
-  if (Tb > 0) fetch(0);
-
-  for (int t = 0; t < Tb; ++t) {
-    const int f = t & 1;
-    if (tid < Kc) { s_clp[f][tid] = pf_f; s_cid[f][tid] = pf_i; }
-    else if (tid == M || tid == M + 1) s_fr[f][tid - M] = pf_f;
-    if (small_row && tid < a.C) s_row[f][tid] = pf_x;
-    __syncthreads();                                    // the record; the beam the last frame left
-    if (t + 1 < Tb) fetch(t + 1);
-
-    // LM: ln P(candidate k | state of slot i) for every fresh entry of the table, kept for the keys and laid out for the build step
-    float cand_lp[BEAM_EPT];
-    if constexpr (LM) {
-      int st[BEAM_EPT], tk[BEAM_EPT], nx_[BEAM_EPT];
-      bool want[BEAM_EPT];
-#pragma unroll
-      for (int r = 0; r < BEAM_EPT; ++r) {
-        want[r] = ei[r] >= 0 && ei[r] < nb;
-        st[r] = want[r] ? s_lst[cur][ei[r]] : 0;
-        tk[r] = want[r] ? s_cid[f][ek[r]] : 0;
-      }
-      lm_lookup<BEAM_EPT>(a, st, tk, want, cand_lp, nx_);
-#pragma unroll
-      for (int r = 0; r < BEAM_EPT; ++r)
-        if (want[r]) { s_candlp[ei[r] * Kc + ek[r]] = cand_lp[r]; s_candnx[ei[r] * Kc + ek[r]] = nx_[r]; }
-    }
-
-    // resident prefixes: blank, the repeat of the last label, and what the parent prefix sends through that label
-    if (tid < nb) {
-      const int j = tid, e = s_last[cur][j];
-      int ck = -1, ps = -1;
-      float lp_e = -INFINITY, npnb = -INFINITY;
-      if (e >= 0) {
-#pragma unroll
-        for (int k = 0; k < M; ++k) ck = s_cid[f][k] == e ? k : ck;                       // (entries behind Kc hold -1)
-        lp_e = ck >= 0 ? s_clp[f][ck] : (small_row ? s_row[f][e] : to_f32<T>(lg[(int64_t)t * a.ldt + e])) - s_fr[f][1];
-        npnb = s_pnb[cur][j] + lp_e;
-        const int par = s_par[cur][j];
-#pragma unroll
-        for (int i = 0; i < M; ++i) ps = (i < nb && s_node[cur][i] == par) ? i : ps;
-        if (ps >= 0) npnb = log_add(npnb, (e == s_last[cur][ps] ? s_pb[cur][ps] : s_tot[cur][ps]) + lp_e);
-      }
-      s_npb[j] = s_tot[cur][j] + s_fr[f][0];
-      s_npnb[j] = npnb;
-      s_pslot[j] = ps;
-      s_ck[j] = ck;
-    }
-    __syncthreads();
-    if (tid < nb) {
-      unsigned mk = 0u;
-#pragma unroll
-      for (int j = 0; j < M; ++j) mk |= (j < nb && s_pslot[j] == tid && s_ck[j] >= 0) ? (1u << s_ck[j]) : 0u;
-      s_merged[tid] = mk;
-    }
-    __syncthreads();
-
-    // the table's keys, in registers
-    unsigned long long key[BEAM_EPT];
-#pragma unroll
-    for (int r = 0; r < BEAM_EPT; ++r) {
-      const int e = tid + BEAM_THREADS * r;
-      float v = -INFINITY;
-      if (e < nb) {
-        v = log_add(s_npb[e], s_npnb[e]);
-        if constexpr (LM) v = v > -INFINITY ? v + s_lmw[cur][e] : v;
-      } else if (ei[r] >= 0 && ei[r] < nb) {
-        const int i = ei[r], k = ek[r];
-        if (!((s_merged[i] >> k) & 1u)) v = (s_cid[f][k] == s_last[cur][i] ? s_pb[cur][i] : s_tot[cur][i]) + s_clp[f][k];
-        if constexpr (LM) v = v > -INFINITY ? v + (s_lmw[cur][i] + lm_term(a.lm_weight, cand_lp[r], a.length_bonus)) : v;
-      }
-      key[r] = v > -INFINITY ? beam_key(v, e) : 0ull;   // (a NaN total is no entry either)
-    }
-
-    // The W largest keys.  Only the W threads with the largest own maximum can hold one of them: every thread ranks its maximum among
-    // the BEAM_THREADS maxima, those W threads lay all their keys out, and the at most W BEAM_EPT keys laid out are ranked among
-    // themselves.  Three barriers whatever W is; keys are distinct, so ranks are.  Thread r picks up the key of rank r.
+  // The W largest of the table's keys -> their number; leaves the key of rank r in s_selkey[r] and in thread r's mysel.  Only the W
+  // threads with the largest own maximum can hold one of them: every thread ranks its maximum among the BEAM_THREADS maxima, those W
+  // threads lay all their keys out, and the at most W BEAM_EPT keys laid out are ranked among themselves.  Three barriers whatever W is; keys are distinct, so ranks are.
+  auto select = [&](const unsigned long long (&key)[BEAM_EPT], unsigned long long& mysel) {
     unsigned long long mx = key[0];
 #pragma unroll
     for (int q = 1; q < BEAM_EPT; ++q) mx = key[q] > mx ? key[q] : mx;
@@ -979,11 +892,12 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(std::conditional
       }
     }
     __syncthreads();
-    const unsigned long long mysel = tid < M ? s_selkey[tid] : 0ull;
-    const int nsel = __popcll(__ballot((tid & 63) < W && s_selkey[tid & 63] != 0ull));   // the same in every wave
-
-    // nodes of the new prefixes: thread i looks its slot's chosen children up among the children of node[i], makes what is missing
-    const int sel_e = tid < nsel ? key_index(mysel) : 0;
+    mysel = tid < M ? s_selkey[tid] : 0ull;
+    return __popcll(__ballot((tid & 63) < W && s_selkey[tid & 63] != 0ull));   // the same in every wave
+  };
+  // Nodes of the new prefixes (thread r < nsel: chosen entry sel_e): thread i looks its slot's chosen children up among the children of
+  // node[i] and makes what is missing; leaves s_selpar / lab / node / first and the slots' first child and filter up to date.
+  auto make_nodes = [&](int t, int f, int cur, int nb, int nsel, int sel_e) {
     if (tid < nsel) {
       const bool fresh = sel_e >= W;
       s_selpar[tid] = fresh ? (sel_e - W) / Kc : -1;
@@ -1027,20 +941,162 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(std::conditional
       }
     }
     __syncthreads();
+  };
+  // LM, behind the last frame: the final key total + lmw, with use_eos + lm_weight ln P(</s> | state); the beam is put in the order of these keys once more,
+  // equal keys in the order of the last selection (s_perm: place -> slot, the identity wherever no rank lands)
+  auto lm_rerank = [&](int cur, int nb) {
+    if constexpr (LM) {
+      if (tid < M) {
+        float key = -INFINITY, lm = -INFINITY;
+        if (tid < nb) {
+          key = s_tot[cur][tid] + s_lmw[cur][tid];
+          lm = s_lms[cur][tid];
+          if (a.use_eos) {
+            const int st[1] = {s_lst[cur][tid]}, tk[1] = {a.C};
+            const bool want[1] = {true};
+            float lp[1];
+            int nx_[1];
+            lm_lookup<1>(a, st, tk, want, lp, nx_);
+            key += lm_term(a.lm_weight, lp[0], 0.0f);
+            lm += lp[0];
+          }
+        }
+        s_fkey[tid] = key;
+        s_flm[tid] = lm;
+        s_perm[tid] = tid;
+      }
+      __syncthreads();
+      if (tid < nb) {
+        const float mine = s_fkey[tid];
+        int rank = 0;
+#pragma unroll
+        for (int j = 0; j < M; ++j) rank += (j < nb && (s_fkey[j] > mine || (s_fkey[j] == mine && j < tid))) ? 1 : 0;   // < nb
+        s_perm[rank] = tid;
+      }
+      __syncthreads();
+    }
+  };
+  // The result: slot h is hypothesis h (LM: slot s_perm[h]); its chain is walked backwards into ids.
+  auto write_out = [&](int cur, int nb) {
+    auto slot_of = [&](int h) {
+      if constexpr (LM) return s_perm[h];
+      else return h;
+    };
+    for (int64_t i = tid; i < (int64_t)a.nbest * a.T; i += BEAM_THREADS) {
+      const int h = (int)(i / a.T), pos = (int)(i % a.T);
+      if (pos >= (h < nb ? s_len[cur][slot_of(h)] : 0)) a.ids[(int64_t)b * a.ld_ids_b + (int64_t)h * a.ld_ids_h + pos] = a.pad;
+    }
+    if (tid < a.nbest) {
+      const bool have = tid < nb;
+      const int sl = slot_of(tid);
+      const int len = have ? s_len[cur][sl] : 0;
+      a.lengths[(int64_t)b * a.nbest + tid] = len;
+      a.scores[(int64_t)b * a.nbest + tid] = have ? s_tot[cur][sl] : -INFINITY;
+      if constexpr (LM) {
+        a.lm_out[(int64_t)b * a.nbest + tid] = have ? s_flm[sl] : -INFINITY;
+        a.total_out[(int64_t)b * a.nbest + tid] = have ? s_fkey[sl] : -INFINITY;
+      }
+      int64_t* o = a.ids + (int64_t)b * a.ld_ids_b + (int64_t)tid * a.ld_ids_h;
+      int n = have ? s_node[cur][sl] : 0;
+      for (int s = len - 1; s >= 0 && n > 0; --s) {
+        const int4 nd = nodes[n];
+        o[s] = nd.y;
+        n = nd.x;
+      }
+    }
+  };
+  // the frames, as tests/ctc_beam_ref.py walks them: record, (LM look-ups,) resident step, keys, select, nodes, next beam
+  if (Tb > 0) fetch(0);
+
+  for (int t = 0; t < Tb; ++t) {
+    const int f = t & 1;
+    if (tid < Kc) { s_clp[f][tid] = pf_f; s_cid[f][tid] = pf_i; }
+    else if (tid == M || tid == M + 1) s_fr[f][tid - M] = pf_f;
+    if (small_row && tid < a.C) s_row[f][tid] = pf_x;
+    __syncthreads();                                    // the record; the beam the last frame left
+    if (t + 1 < Tb) fetch(t + 1);
+
+    // LM: ln P(candidate k | state of slot i) for every fresh entry of the table, kept for the keys and laid out for the build step
+    float cand_lp[BEAM_EPT];
+    if constexpr (LM) {
+      int st[BEAM_EPT], tk[BEAM_EPT], nx_[BEAM_EPT];
+      bool want[BEAM_EPT];
+#pragma unroll
+      for (int r = 0; r < BEAM_EPT; ++r) {
+        want[r] = ei[r] >= 0 && ei[r] < nb;
+        st[r] = want[r] ? s_lst[cur][ei[r]] : 0;
+        tk[r] = want[r] ? s_cid[f][ek[r]] : 0;
+      }
+      lm_lookup<BEAM_EPT>(a, st, tk, want, cand_lp, nx_);
+#pragma unroll
+      for (int r = 0; r < BEAM_EPT; ++r)
+        if (want[r]) { s_candlp[ei[r] * Kc + ek[r]] = cand_lp[r]; s_candnx[ei[r] * Kc + ek[r]] = nx_[r]; }
+    }
+
+    // resident prefixes: blank, the repeat of the last label, and what the parent prefix sends through that label
+    if (tid < nb) {
+      const int j = tid, e = s_last[cur][j];
+      int ck = -1, ps = -1;
+      float lp_e = -INFINITY, npnb = -INFINITY;
+      if (e >= 0) {
+#pragma unroll
+        for (int k = 0; k < M; ++k) ck = s_cid[f][k] == e ? k : ck;                       // (entries behind Kc hold -1)
+        lp_e = ck >= 0 ? s_clp[f][ck] : (small_row ? s_row[f][e] : to_f32<T>(lg[(int64_t)t * a.ldt + e])) - s_fr[f][1];
+        npnb = s_pnb[cur][j] + lp_e;
+        const int par = s_par[cur][j];
+#pragma unroll
+        for (int i = 0; i < M; ++i) ps = (i < nb && s_node[cur][i] == par) ? i : ps;
+        if (ps >= 0) npnb = log_add(npnb, extended_total(e, s_last[cur], s_pb[cur], s_tot[cur], ps, lp_e));
+      }
+      s_npb[j] = s_tot[cur][j] + s_fr[f][0];
+      s_npnb[j] = npnb;
+      s_pslot[j] = ps;
+      s_ck[j] = ck;
+    }
+    __syncthreads();
+    if (tid < nb) {
+      unsigned mk = 0u;
+#pragma unroll
+      for (int j = 0; j < M; ++j) mk |= (j < nb && s_pslot[j] == tid && s_ck[j] >= 0) ? (1u << s_ck[j]) : 0u;
+      s_merged[tid] = mk;
+    }
+    __syncthreads();
+
+    // the table's keys, in registers
+    unsigned long long key[BEAM_EPT];
+#pragma unroll
+    for (int r = 0; r < BEAM_EPT; ++r) {
+      const int e = tid + BEAM_THREADS * r;
+      float v = -INFINITY;
+      if (e < nb) {
+        v = resident_total(s_npb[e], s_npnb[e]);
+        if constexpr (LM) v = v > -INFINITY ? v + s_lmw[cur][e] : v;
+      } else if (ei[r] >= 0 && ei[r] < nb) {
+        const int i = ei[r], k = ek[r];
+        if (!((s_merged[i] >> k) & 1u)) v = extended_total(s_cid[f][k], s_last[cur], s_pb[cur], s_tot[cur], i, s_clp[f][k]);
+        if constexpr (LM) v = v > -INFINITY ? v + extended_lmw(s_lmw[cur][i], a.lm_weight, cand_lp[r], a.length_bonus) : v;
+      }
+      key[r] = v > -INFINITY ? beam_key(v, e) : 0ull;   // (a NaN total is no entry either)
+    }
+
+    unsigned long long mysel;
+    const int nsel = select(key, mysel);
+    const int sel_e = tid < nsel ? key_index(mysel) : 0;
+    make_nodes(t, f, cur, nb, nsel, sel_e);
 
     // the next beam, in the order of the selection
     const int nx = cur ^ 1;
     if (tid < nsel) {
       float tot = key_value(mysel);
-      if constexpr (LM) {                               // the key is total + lmw there: the total again, the same expression as for the key
+      if constexpr (LM) {                               // the key is total + lmw there: the total is formed again
         if (sel_e < W) {
-          tot = log_add(s_npb[sel_e], s_npnb[sel_e]);
+          tot = resident_total(s_npb[sel_e], s_npnb[sel_e]);
           s_lmw[nx][tid] = s_lmw[cur][sel_e]; s_lms[nx][tid] = s_lms[cur][sel_e]; s_lst[nx][tid] = s_lst[cur][sel_e];
         } else {
           const int i = s_selpar[tid], k = (sel_e - W) % Kc;
           const float lp = s_candlp[sel_e - W];
-          tot = (s_cid[f][k] == s_last[cur][i] ? s_pb[cur][i] : s_tot[cur][i]) + s_clp[f][k];
-          s_lmw[nx][tid] = s_lmw[cur][i] + lm_term(a.lm_weight, lp, a.length_bonus);
+          tot = extended_total(s_cid[f][k], s_last[cur], s_pb[cur], s_tot[cur], i, s_clp[f][k]);
+          s_lmw[nx][tid] = extended_lmw(s_lmw[cur][i], a.lm_weight, lp, a.length_bonus);
           s_lms[nx][tid] = s_lms[cur][i] + lp;
           s_lst[nx][tid] = s_candnx[sel_e - W];
         }
@@ -1062,66 +1118,30 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(std::conditional
     nb = nsel;
   }
   __syncthreads();
+  lm_rerank(cur, nb);
+  write_out(cur, nb);
+}
 
-  // the result: slot h is hypothesis h; its chain is walked backwards
-  // LM: the final key total + lmw, with use_eos + lm_weight ln P(</s> | state); the beam is put in the order of these keys once more,
-  // equal keys in the order of the last selection (s_perm: place -> slot, the identity wherever no rank lands)
-  if constexpr (LM) {
-    if (tid < M) {
-      float key = -INFINITY, lm = -INFINITY;
-      if (tid < nb) {
-        key = s_tot[cur][tid] + s_lmw[cur][tid];
-        lm = s_lms[cur][tid];
-        if (a.use_eos) {
-          const int st[1] = {s_lst[cur][tid]}, tk[1] = {a.C};
-          const bool want[1] = {true};
-          float lp[1];
-          int nx_[1];
-          lm_lookup<1>(a, st, tk, want, lp, nx_);
-          key += lm_term(a.lm_weight, lp[0], 0.0f);
-          lm += lp[0];
-        }
-      }
-      s_fkey[tid] = key;
-      s_flm[tid] = lm;
-      s_perm[tid] = tid;
-    }
-    __syncthreads();
-    if (tid < nb) {
-      const float mine = s_fkey[tid];
-      int rank = 0;
-#pragma unroll
-      for (int j = 0; j < M; ++j) rank += (j < nb && (s_fkey[j] > mine || (s_fkey[j] == mine && j < tid))) ? 1 : 0;   // < nb
-      s_perm[rank] = tid;
-    }
-    __syncthreads();
-  }
-  auto slot_of = [&](int h) {
-    if constexpr (LM) return s_perm[h];
-    else return h;
-  };
-  for (int64_t i = tid; i < (int64_t)a.nbest * a.T; i += BEAM_THREADS) {
-    const int h = (int)(i / a.T), t = (int)(i % a.T);
-    if (t >= (h < nb ? s_len[cur][slot_of(h)] : 0)) a.ids[(int64_t)b * a.ld_ids_b + (int64_t)h * a.ld_ids_h + t] = a.pad;
-  }
-  if (tid < a.nbest) {
-    const bool have = tid < nb;
-    const int sl = slot_of(tid);
-    const int len = have ? s_len[cur][sl] : 0;
-    a.lengths[(int64_t)b * a.nbest + tid] = len;
-    a.scores[(int64_t)b * a.nbest + tid] = have ? s_tot[cur][sl] : -INFINITY;
-    if constexpr (LM) {
-      a.lm_out[(int64_t)b * a.nbest + tid] = have ? s_flm[sl] : -INFINITY;
-      a.total_out[(int64_t)b * a.nbest + tid] = have ? s_fkey[sl] : -INFINITY;
-    }
-    int64_t* o = a.ids + (int64_t)b * a.ld_ids_b + (int64_t)tid * a.ld_ids_h;
-    int n = have ? s_node[cur][sl] : 0;
-    for (int s = len - 1; s >= 0 && n > 0; --s) {
-      const int4 nd = nodes[n];
-      o[s] = nd.y;
-      n = nd.x;
-    }
-  }
+// The route of a row-parallel kernel (a template over <T, BLOCK>; TT names the dtype in its arguments): a row of more than 1024 classes
+// takes a workgroup, a shorter one a wave, four rows a workgroup; at most 8192 workgroups walk the rows.
+#define CTC_LAUNCH_ROWS(kernel, dtype, rows, C, stream, ...)                                                                           \
+  do {                                                                                                                                  \
+    const bool block__ = (C) > 1024;                                                                                                    \
+    const int64_t wgs__ = block__ ? (rows) : fk_cdiv((rows), 4);                                                                        \
+    const dim3 grid__((unsigned)(wgs__ < 8192 ? wgs__ : 8192));                                                                         \
+    if (block__) FK_BY_DTYPE(dtype, TT, hipLaunchKernelGGL((kernel<TT, true>), grid__, dim3(256), 0, stream, __VA_ARGS__));             \
+    else FK_BY_DTYPE(dtype, TT, hipLaunchKernelGGL((kernel<TT, false>), grid__, dim3(256), 0, stream, __VA_ARGS__));                    \
+  } while (0)
+
+// The checks every entry point over logits [B, T, C] makes first, under the caller's name (`pointers`: its own are all there).  The
+// stride checks stay with the callers: each message names the caller's other strides, behind the caller's envelope checks.
+static int check_common(const char* fn, int dtype, bool pointers, int64_t B, int64_t T, int64_t C, int64_t blank) {
+  FK_CHECK_ARG(dtype == FK_F32 || dtype == FK_BF16, "%s: bad dtype %d", fn, dtype);
+  FK_CHECK_ARG(pointers, "%s: null pointer", fn);
+  FK_CHECK_ARG(B > 0 && T > 0 && B * T < (1LL << 31), "%s: B = %lld, T = %lld", fn, (long long)B, (long long)T);
+  FK_CHECK_ARG(C >= 2 && C < (1LL << 31), "%s: C = %lld, must be >= 2 (a class beside the blank)", fn, (long long)C);
+  FK_CHECK_ARG(blank >= 0 && blank < C, "%s: blank = %lld outside [0, C = %lld)", fn, (long long)blank, (long long)C);
+  return FK_OK;
 }
 
 // The argument checks, the workspace and launch 1 of fk_ctc_beam_search and fk_ctc_beam_search_lm; fills everything
@@ -1129,11 +1149,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(std::conditional
 static int beam_front(const char* fn, const void* logits, int64_t ldb, int64_t ldt, const int64_t* input_lengths, int64_t B, int64_t T, int64_t C,
                       int64_t blank, int64_t W, int64_t K, int64_t nbest, int64_t pad, int64_t* ids, int64_t ld_ids_b, int64_t ld_ids_h,
                       int64_t* lengths, float* scores, int dtype, void* workspace, size_t workspace_bytes, void* stream, BeamArgs& a) {
-  FK_CHECK_ARG(dtype == FK_F32 || dtype == FK_BF16, "%s: bad dtype %d", fn, dtype);
-  FK_CHECK_ARG(logits && ids && lengths && scores, "%s: null pointer", fn);
-  FK_CHECK_ARG(B > 0 && T > 0 && B * T < (1LL << 31), "%s: B = %lld, T = %lld", fn, (long long)B, (long long)T);
-  FK_CHECK_ARG(C >= 2 && C < (1LL << 31), "%s: C = %lld, must be >= 2 (a class beside the blank)", fn, (long long)C);
-  FK_CHECK_ARG(blank >= 0 && blank < C, "%s: blank = %lld outside [0, C = %lld)", fn, (long long)blank, (long long)C);
+  if (const int rc = check_common(fn, dtype, logits && ids && lengths && scores, B, T, C, blank)) return rc;
   FK_CHECK_ARG(W >= 1 && W <= BEAM_MAX && K >= 1 && K <= BEAM_MAX, "%s: W = %lld, K = %lld outside the envelope (1 .. %d each)", fn, (long long)W,
                (long long)K, BEAM_MAX);
   FK_CHECK_ARG(T * W < (1LL << 31) - 1, "%s: T W = %lld nodes per sample", fn, (long long)(T * W));
@@ -1146,10 +1162,7 @@ static int beam_front(const char* fn, const void* logits, int64_t ldb, int64_t l
   hipStream_t s = (hipStream_t)stream;
   const int64_t rows = B * T;
   const int Kc = (int)(K < C - 1 ? K : C - 1);
-  if (C > 1024)
-    FK_BY_DTYPE(dtype, TT, hipLaunchKernelGGL((ctc_beam_prune_kernel<TT, true>), dim3((unsigned)(rows < 8192 ? rows : 8192)), dim3(256), 0, s, (const TT*)logits, ldb, ldt, input_lengths, a.w, rows, (int)T, (int)C, (int)blank, (int)K, Kc));
-  else
-    FK_BY_DTYPE(dtype, TT, hipLaunchKernelGGL((ctc_beam_prune_kernel<TT, false>), dim3((unsigned)(fk_cdiv(rows, 4) < 8192 ? fk_cdiv(rows, 4) : 8192)), dim3(256), 0, s, (const TT*)logits, ldb, ldt, input_lengths, a.w, rows, (int)T, (int)C, (int)blank, (int)K, Kc));
+  CTC_LAUNCH_ROWS(ctc_beam_prune_kernel, dtype, rows, C, s, (const TT*)logits, ldb, ldt, input_lengths, a.w, rows, (int)T, (int)C, (int)blank, (int)K, Kc);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fk_set_error(FK_ELAUNCH, "%s(prune): %s", fn, hipGetErrorString(e));
   a.logits = logits; a.ldb = ldb; a.ldt = ldt; a.input_lengths = input_lengths;
@@ -1178,11 +1191,7 @@ int fk_ctc_loss_fwd(const void* logits, int64_t ldb, int64_t ldt, const int64_t*
                     const int64_t* target_lengths, int64_t pad_value, float* nll, float* loss2, float* row_lse, int64_t B, int64_t T,
                     int64_t C, int64_t Lmax, int64_t blank, int reduction, int zero_infinity, int want_lattice, int dtype, void* workspace,
                     size_t workspace_bytes, void* stream) {
-  FK_DT_CHECK("fk_ctc_loss_fwd");
-  FK_CHECK_ARG(logits && nll && loss2 && row_lse && workspace && (targets || Lmax == 0), "fk_ctc_loss_fwd: null pointer");
-  FK_CHECK_ARG(B > 0 && T > 0 && B * T < (1LL << 31), "fk_ctc_loss_fwd: B = %lld, T = %lld", (long long)B, (long long)T);
-  FK_CHECK_ARG(C >= 2 && C < (1LL << 31), "fk_ctc_loss_fwd: C = %lld, must be >= 2 (a class beside the blank)", (long long)C);
-  FK_CHECK_ARG(blank >= 0 && blank < C, "fk_ctc_loss_fwd: blank = %lld outside [0, C = %lld)", (long long)blank, (long long)C);
+  if (const int rc = check_common("fk_ctc_loss_fwd", dtype, logits && nll && loss2 && row_lse && workspace && (targets || Lmax == 0), B, T, C, blank)) return rc;
   FK_CHECK_ARG(Lmax >= 0 && 2 * Lmax + 1 <= CTC_MAX_S, "fk_ctc_loss_fwd: Lmax = %lld outside the envelope (2 * Lmax + 1 <= %d extended states)",
                (long long)Lmax, CTC_MAX_S);
   FK_CHECK_ARG(ldt >= C && ldb >= ldt && ldtgt >= Lmax, "fk_ctc_loss_fwd: row stride %lld below C = %lld (batch stride %lld, target stride %lld)",
@@ -1194,10 +1203,7 @@ int fk_ctc_loss_fwd(const void* logits, int64_t ldb, int64_t ldt, const int64_t*
   FK_CHECK_ARG(workspace_bytes >= need, "fk_ctc_loss_fwd: workspace too small (%zu bytes, fk_ctc_workspace_bytes gives %zu)", workspace_bytes, need);
   hipStream_t s = (hipStream_t)stream;
   const int64_t rows = B * T;
-  if (C > 1024)
-    FK_BY_DTYPE(dtype, TT, hipLaunchKernelGGL((ctc_row_lse_kernel<TT, true>), dim3((unsigned)(rows < 8192 ? rows : 8192)), dim3(256), 0, s, (const TT*)logits, ldb, ldt, row_lse, rows, (int)T, (int)C));
-  else
-    FK_BY_DTYPE(dtype, TT, hipLaunchKernelGGL((ctc_row_lse_kernel<TT, false>), dim3((unsigned)(fk_cdiv(rows, 4) < 8192 ? fk_cdiv(rows, 4) : 8192)), dim3(256), 0, s, (const TT*)logits, ldb, ldt, row_lse, rows, (int)T, (int)C));
+  CTC_LAUNCH_ROWS(ctc_row_lse_kernel, dtype, rows, C, s, (const TT*)logits, ldb, ldt, row_lse, rows, (int)T, (int)C);
   FK_CHECK_LAUNCH("fk_ctc_loss_fwd(row_lse)");
   a.logits = logits; a.ldb = ldb; a.ldt = ldt; a.targets = targets; a.ldtgt = ldtgt;
   a.input_lengths = input_lengths; a.target_lengths = target_lengths; a.pad_value = pad_value;
@@ -1217,11 +1223,7 @@ int fk_ctc_loss_fwd(const void* logits, int64_t ldb, int64_t ldt, const int64_t*
 int fk_ctc_loss_bwd(const void* logits, int64_t ldb, int64_t ldt, const float* row_lse, const float* grad_out, void* dlogits, int64_t lddb,
                     int64_t lddt, int64_t B, int64_t T, int64_t C, int64_t Lmax, int64_t blank, int reduction, int zero_infinity, int dtype,
                     const void* workspace, size_t workspace_bytes, void* stream) {
-  FK_DT_CHECK("fk_ctc_loss_bwd");
-  FK_CHECK_ARG(logits && row_lse && grad_out && dlogits && workspace, "fk_ctc_loss_bwd: null pointer");
-  FK_CHECK_ARG(B > 0 && T > 0 && B * T < (1LL << 31), "fk_ctc_loss_bwd: B = %lld, T = %lld", (long long)B, (long long)T);
-  FK_CHECK_ARG(C >= 2 && C < (1LL << 31), "fk_ctc_loss_bwd: C = %lld, must be >= 2 (a class beside the blank)", (long long)C);
-  FK_CHECK_ARG(blank >= 0 && blank < C, "fk_ctc_loss_bwd: blank = %lld outside [0, C = %lld)", (long long)blank, (long long)C);
+  if (const int rc = check_common("fk_ctc_loss_bwd", dtype, logits && row_lse && grad_out && dlogits && workspace, B, T, C, blank)) return rc;
   FK_CHECK_ARG(Lmax >= 0 && 2 * Lmax + 1 <= CTC_MAX_S, "fk_ctc_loss_bwd: Lmax = %lld outside the envelope (2 * Lmax + 1 <= %d extended states)",
                (long long)Lmax, CTC_MAX_S);
   FK_CHECK_ARG(ldt >= C && ldb >= ldt && lddt >= C && lddb >= lddt, "fk_ctc_loss_bwd: row stride %lld / %lld below C = %lld", (long long)ldt,
@@ -1235,10 +1237,7 @@ int fk_ctc_loss_bwd(const void* logits, int64_t ldb, int64_t ldt, const float* r
   a.B = (int)B; a.T = (int)T; a.C = (int)C; a.blank = (int)blank; a.reduction = reduction; a.zero_inf = zero_infinity != 0;
   hipStream_t s = (hipStream_t)stream;
   const int64_t rows = B * T;
-  if (C > 1024)
-    FK_BY_DTYPE(dtype, TT, hipLaunchKernelGGL((ctc_bwd_kernel<TT, true>), dim3((unsigned)(rows < 8192 ? rows : 8192)), dim3(256), 0, s, a));
-  else
-    FK_BY_DTYPE(dtype, TT, hipLaunchKernelGGL((ctc_bwd_kernel<TT, false>), dim3((unsigned)(fk_cdiv(rows, 4) < 8192 ? fk_cdiv(rows, 4) : 8192)), dim3(256), 0, s, a));
+  CTC_LAUNCH_ROWS(ctc_bwd_kernel, dtype, rows, C, s, a);
   FK_CHECK_LAUNCH("fk_ctc_loss_bwd");
   return FK_OK;
 }

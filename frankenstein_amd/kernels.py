@@ -1198,12 +1198,8 @@ def ctc_collapse(argmax: Tensor, input_lengths: Optional[Tensor] = None, blank: 
     return ids, lengths
 
 
-def ctc_beam_search(logits: Tensor, input_lengths: Optional[Tensor] = None, blank: int = 0, beam_width: int = 8, topk: Optional[int] = None,
-                    nbest: int = 1, pad: int = -100) -> Tuple[Tensor, Tensor, Tensor]:
-    """Prefix beam search over logits [B, T, C] (fp32 / bf16, unit column stride, any row and batch stride; NOT log-softmaxed) ->
-    (ids int64 [B, nbest, T] padded with `pad`, lengths int64 [B, nbest], scores fp32 [B, nbest]): the nbest most probable labellings
-    the beam found, best first, with their log-probability mass (semantics: include/franken_hip.h).  beam_width and topk (new prefixes
-    proposed per resident prefix and frame; None: min(32, C - 1)) up to 32.  A slot without hypothesis: length 0, score -inf."""
+def _ctc_beam_prologue(logits: Tensor, input_lengths: Optional[Tensor], beam_width: int, topk: Optional[int], nbest: int):
+    """What both beam searches set up before their call -> (B, T, C, K, il, ids, lengths, ws, nbytes); topk None: min(32, C - 1)."""
     assert logits.dim() == 3 and logits.stride(2) == 1 and logits.dtype in (torch.float32, torch.bfloat16)
     B, T, Cn = logits.shape
     K = min(32, Cn - 1) if topk is None else int(topk)
@@ -1211,9 +1207,19 @@ def ctc_beam_search(logits: Tensor, input_lengths: Optional[Tensor] = None, blan
     il = _ctc_lengths(input_lengths, B, dev)
     ids = torch.empty((B, nbest, T), dtype=torch.int64, device=dev)
     lengths = torch.empty((B, nbest), dtype=torch.int64, device=dev)
-    scores = torch.empty((B, nbest), dtype=torch.float32, device=dev)
     nbytes = lib().fk_ctc_beam_workspace_bytes(B, T, beam_width, K)
     ws, _ = _ws(nbytes, dev)
+    return B, T, Cn, K, il, ids, lengths, ws, nbytes
+
+
+def ctc_beam_search(logits: Tensor, input_lengths: Optional[Tensor] = None, blank: int = 0, beam_width: int = 8, topk: Optional[int] = None,
+                    nbest: int = 1, pad: int = -100) -> Tuple[Tensor, Tensor, Tensor]:
+    """Prefix beam search over logits [B, T, C] (fp32 / bf16, unit column stride, any row and batch stride; NOT log-softmaxed) ->
+    (ids int64 [B, nbest, T] padded with `pad`, lengths int64 [B, nbest], scores fp32 [B, nbest]): the nbest most probable labellings
+    the beam found, best first, with their log-probability mass (semantics: include/franken_hip.h).  beam_width and topk (new prefixes
+    proposed per resident prefix and frame; None: min(32, C - 1)) up to 32.  A slot without hypothesis: length 0, score -inf."""
+    B, T, Cn, K, il, ids, lengths, ws, nbytes = _ctc_beam_prologue(logits, input_lengths, beam_width, topk, nbest)
+    scores = torch.empty((B, nbest), dtype=torch.float32, device=logits.device)
     with _timed("ctc_beam_search"):
         call("fk_ctc_beam_search", logits.data_ptr(), logits.stride(0), logits.stride(1), _ptr(il), B, T, Cn, blank, beam_width, K, nbest, pad,
              ids.data_ptr(), ids.stride(0), ids.stride(1), lengths.data_ptr(), scores.data_ptr(), fk_dtype(logits), _ptr(ws), nbytes, _stream())
@@ -1227,20 +1233,12 @@ def ctc_beam_search_lm(logits: Tensor, lm, input_lengths: Optional[Tensor] = Non
     key = CTC total + lm_weight * ln P_lm + length_bonus * length (semantics: include/franken_hip.h) -> (ids int64 [B, nbest, T], lengths
     int64 [B, nbest], am fp32 [B, nbest] the pure CTC mass, lm fp32 [B, nbest] the unweighted ln P_lm, total fp32 [B, nbest] the final
     key), best first.  The model's n_classes must be C."""
-    assert logits.dim() == 3 and logits.stride(2) == 1 and logits.dtype in (torch.float32, torch.bfloat16)
-    B, T, Cn = logits.shape
     tables = lm.compile() if hasattr(lm, "compile") else lm
-    if tables.n_classes != Cn:
-        raise ValueError(f"the language model has {tables.n_classes} classes, the logits {Cn}")
-    K = min(32, Cn - 1) if topk is None else int(topk)
-    dev = logits.device
-    d = tables.to(dev)
-    il = _ctc_lengths(input_lengths, B, dev)
-    ids = torch.empty((B, nbest, T), dtype=torch.int64, device=dev)
-    lengths = torch.empty((B, nbest), dtype=torch.int64, device=dev)
-    am, lms, total = (torch.empty((B, nbest), dtype=torch.float32, device=dev) for _ in range(3))
-    nbytes = lib().fk_ctc_beam_workspace_bytes(B, T, beam_width, K)
-    ws, _ = _ws(nbytes, dev)
+    if tables.n_classes != logits.shape[-1]:
+        raise ValueError(f"the language model has {tables.n_classes} classes, the logits {logits.shape[-1]}")
+    B, T, Cn, K, il, ids, lengths, ws, nbytes = _ctc_beam_prologue(logits, input_lengths, beam_width, topk, nbest)
+    d = tables.to(logits.device)
+    am, lms, total = (torch.empty((B, nbest), dtype=torch.float32, device=logits.device) for _ in range(3))
     with _timed("ctc_beam_search_lm"):
         call("fk_ctc_beam_search_lm", logits.data_ptr(), logits.stride(0), logits.stride(1), _ptr(il), B, T, Cn, blank, beam_width, K, nbest, pad,
              d["table"].data_ptr(), tables.cap, tables.max_probe, d["bow"].data_ptr(), d["backoff"].data_ptr(), tables.n_states,

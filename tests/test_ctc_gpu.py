@@ -27,7 +27,10 @@ def refs(key):
     """-> (case, logits fp32 as the kernel sees them (bf16-rounded for the bf16 case), float64 reference with zero_infinity, tol_nll,
     tol_unit, torch's fp32 errors): computed once, shared, read-only"""
     name, bf16 = (key[:-5], True) if key.endswith("_bf16") else (key, False)
-    case = CC.make(name)
+    return refs_of(CC.make(name), bf16)
+
+
+def refs_of(case, bf16):
     x = case["logits"].to(torch.bfloat16).float() if bf16 else case["logits"]
     ref = R.ctc(x.numpy(), case["targets"].numpy(), case["input_lengths"].numpy(), case["target_lengths"].numpy(), blank=case["blank"],
                 zero_infinity=True, want_lattice=True)
@@ -102,6 +105,46 @@ def test_parity_with_float64(key):
                 assert nll[b] == 0.0 and not got[b].any()
         if case["ld"] > C:
             assert bool(torch.isnan(store[:, :, C:]).all())
+
+
+@functools.lru_cache(maxsize=None)
+def misaligned_case():
+    """B = 2, T = 5, C = 13, Lmax = 3: contiguous logits (row stride 13), one adjacent repeat, a sample that ends early"""
+    g = torch.Generator().manual_seed(1313)
+    return dict(name="misaligned", logits=3.0 * torch.randn((2, 5, 13), generator=g), targets=torch.tensor([[4, 4, 9], [12, 1, CC.PAD]]),
+                input_lengths=torch.tensor([5, 3]), target_lengths=torch.tensor([3, 2]), blank=0, infeasible=0, ld=13)
+
+
+@pytest.mark.parametrize("reduction", ["mean", "none"])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
+def test_backward_rows_that_disagree_about_the_vector_boundary(dtype, reduction):
+    """logits rows at stride 13 from an aligned base, dlogits rows at stride 16 from one element into its storage: on most rows the two
+    pointers reach their first 16-byte boundary after a different number of elements and ctc_bwd_kernel goes element by element"""
+    case = misaligned_case()
+    _, x, ref, _, tol_unit, _ = refs_of(case, dtype == torch.bfloat16)
+    B, T, C = x.shape
+    lg = x.to(dtype).cuda()
+    assert lg.is_contiguous() and lg.stride(1) == C
+    store = torch.full((1 + B * T * 16 + 7,), float("nan"), dtype=dtype, device="cuda")
+    dl = store[1:1 + B * T * 16].view(B, T, 16)[:, :, :C]
+    per_vec = 16 // lg.element_size()
+    heads = [[(-(p.data_ptr() // p.element_size())) % per_vec for p in (lg[b, t], dl[b, t])] for b in range(B) for t in range(T)]
+    assert sum(hl != hd for hl, hd in heads) > B * T // 2
+    st = K.ctc_loss_fwd(lg, case["targets"].cuda(), case["input_lengths"].cuda(), case["target_lengths"].cuda(), 0, reduction, True)
+    gout = gout_for(reduction, B)
+    K.ctc_loss_bwd(lg, st, gout.cuda(), dl)
+    got = dl.float().cpu().numpy().astype(np.float64)
+    want = R.dlogits(ref, reduction, gout.numpy())
+    f = factor(ref, reduction, gout)
+    bound = tol_unit * f[:, None, None] + (2.0 ** -8 * np.abs(want) if dtype == torch.bfloat16 else 0.0)
+    k_unit = float((np.abs(got - want) / f[:, None, None]).max())
+    print(f"ctc misaligned backward {dtype} {reduction}: dlogits/g |kernel - f64| {k_unit:.3e} (tol {tol_unit:.3e})")
+    assert np.all(np.abs(got - want) <= bound), (k_unit, tol_unit)
+    inside = torch.zeros(store.numel(), dtype=torch.bool, device="cuda")
+    inside[1:1 + B * T * 16].view(B, T, 16)[:, :, :C] = True
+    assert bool(torch.isnan(store[~inside]).all()) and not bool(torch.isnan(store[inside]).any())
+    for b in range(B):
+        assert not got[b, int(ref["Tb"][b]):].any()
 
 
 @pytest.mark.parametrize("key", ["a", "b31", "b32", "c", "d"])
