@@ -19,6 +19,8 @@ NORM_LAYER, NORM_RMS = 0, 1
 ATTN_Q_PRESCALED = 1
 GEMV_GELU = 1
 NT_RING2, NT_RING192, NT_RING128, NT_BIG, NT_GLDS4, NT_GLDS, NT_STAGED = range(7)     # fk_gemm_nt_route
+NT_LANE = 7                                                                           # fk_gemm_nt_rope_route / fk_gemm_nt_swiglu_route
+MLP_BWD_HIPCC, MLP_BWD_ASM = 0, 1                                                     # fk_mlp_bwd_fused_route
 NT_ROUTE_F32 = -2
 ATTN_FWD_GENERIC, ATTN_FWD_FEWQ, ATTN_FWD_PS, ATTN_FWD_ASM = range(4)                 # fk_attn_route
 ATTN_DQ_GENERIC, ATTN_DQ_FEWQ, ATTN_DQ_PS, ATTN_DQ_ASM = range(4)
@@ -37,6 +39,9 @@ SIGNATURES = {
     "fk_gemm_nt_dswiglu": (_int, [_p, _i64, _p, _i64, _p, _i64, _p, _i64, _i64, _i64, _i64, _int, _p]),
     "fk_mlp_bwd_fused": (_int, [_p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _i64, _i64, _i64, _int, _p]),
     "fk_gemm_nt_route": (_int, [_i64, _i64, _i64, _int, _int, _int, _int]),
+    "fk_gemm_nt_rope_route": (_int, [_i64] * 6 + [_int] + [_i64] * 5 + [_int, _int]),
+    "fk_gemm_nt_swiglu_route": (_int, [_i64] * 7 + [_int, _int]),
+    "fk_mlp_bwd_fused_route": (_int, [_i64, _i64]),
     "fk_gemm_tn_route": (_int, [_i64, _i64, _i64, _int, _p, _p]),
     "fk_gemm_tn_workspace_bytes": (_sz, [_i64, _i64, _i64, _int]),
     "fk_gemm_tn": (_int, [_p, _i64, _p, _i64, _p, _i64, _i64, _i64, _i64, _int, _int, _p, _sz, _p]),

@@ -1597,7 +1597,7 @@ int colsum_blocks(int64_t rows) {
 
 }  // namespace
 
-bool fk_qkv_rope_fused_ok(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, const void* bias, int64_t T, int64_t D, int64_t rot_cols, int64_t q_cols, int dtype);
+bool fk_qkv_rope_fused_ok(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, bool has_bias, int64_t T, int64_t D, int64_t rot_cols, int64_t q_cols, int dtype);
 int fk_qkv_rope_fused_launch(const void* A, int64_t lda, const void* W, int64_t ldb, void* C, int64_t ldc, int64_t M, int64_t N, const float* table, int64_t table_bs, int64_t T, int64_t pos_off, int64_t rot_cols, int64_t q_cols, int64_t q_off, void* stream);
 bool fk_mlp_up_fused_ok(int64_t M, int64_t H, int64_t K, int64_t lda, int64_t ldb, int64_t ldh, int64_t ldg, int dtype);      // mlp_fused.hip
 int fk_mlp_up_fused_launch(const void* A, int64_t lda, const void* W13, int64_t ldb, void* H13, int64_t ldh, void* G, int64_t ldg, int64_t M, int64_t H, void* stream);
@@ -1666,6 +1666,21 @@ static int launch_nt(const char* name, const void* A, int64_t lda, const void* B
   return FK_OK;
 }
 
+// Whether fk_gemm_nt_rope / fk_gemm_nt_swiglu hand a call to the token-on-the-lane kernels (mlp_fused.hip: wide bf16 projections at
+// d = 384, head_dim 64 for the rotation; same bits as the tiled kernels) — the WHOLE decision, so that the entry points and the route
+// queries (fk_gemm_nt_rope_route / fk_gemm_nt_swiglu_route) cannot disagree.  align_ok: every pointer of the call (the rotation table
+// included) is non-null and 16-byte aligned.
+static bool aligned16(const void* a, const void* b, const void* c, const void* d) {
+  return a && b && c && d && (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d) & 15) == 0;
+}
+static bool rope_takes_lane(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, bool has_bias, int64_t T, int64_t pos_off,
+                            int64_t D, int64_t rot_cols, int64_t q_cols, bool align_ok, int dtype) {
+  return align_ok && M > 0 && pos_off >= 0 && fk_qkv_rope_fused_ok(M, N, K, lda, ldb, ldc, has_bias, T, D, rot_cols, q_cols, dtype);
+}
+static bool swiglu_takes_lane(int64_t M, int64_t H, int64_t K, int64_t lda, int64_t ldb, int64_t ldh, int64_t ldg, bool align_ok, int dtype) {
+  return align_ok && M > 0 && fk_mlp_up_fused_ok(M, H, K, lda, ldb, ldh, ldg, dtype);
+}
+
 int fk_gemm_nt(const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc, int64_t M, int64_t N,
                int64_t K, const void* bias, const void* residual, int64_t ldr, int64_t res_rows, int dtype,
                int out_dtype, void* stream) {
@@ -1677,8 +1692,7 @@ int fk_gemm_nt_rope(const void* A, int64_t lda, const void* B, int64_t ldb, void
                     int64_t rot_cols, int64_t q_cols, int64_t q_table_off, int dtype, void* stream) {
   FK_CHECK_ARG(table && T > 0 && D > 0 && rot_cols >= 0, "fk_gemm_nt_rope: bad rope arguments");
   FK_CHECK_ARG(q_cols >= 0 && q_cols <= rot_cols && q_cols % 8 == 0 && q_table_off % 4 == 0, "fk_gemm_nt_rope: bad pre-scaled query table (q_cols %lld, offset %lld)", (long long)q_cols, (long long)q_table_off);
-  if (A && B && C && (((uintptr_t)A | (uintptr_t)B | (uintptr_t)C | (uintptr_t)table) & 15) == 0 && M > 0 && pos_off >= 0 &&
-      fk_qkv_rope_fused_ok(M, N, K, lda, ldb, ldc, bias, T, D, rot_cols, q_cols, dtype))      // wide bf16 projections at d = 384, head_dim 64: the token-on-the-lane kernel (mlp_fused.hip), same bits
+  if (rope_takes_lane(M, N, K, lda, ldb, ldc, bias != nullptr, T, pos_off, D, rot_cols, q_cols, aligned16(A, B, C, table), dtype))
     return fk_qkv_rope_fused_launch(A, lda, B, ldb, C, ldc, M, N, table, table_bs, T, pos_off, rot_cols, q_cols, q_table_off, stream);
   return launch_nt("fk_gemm_nt_rope", A, lda, B, ldb, C, ldc, M, N, K, bias, nullptr, 0, 0, dtype, dtype, 0, nullptr, 0, stream,
                    RopeSpec{table, table_bs, (int)T, (int)pos_off, (int)D, (int)rot_cols, (int)q_cols, q_table_off});
@@ -1687,8 +1701,7 @@ int fk_gemm_nt_rope(const void* A, int64_t lda, const void* B, int64_t ldb, void
 int fk_gemm_nt_swiglu(const void* A, int64_t lda, const void* W13, int64_t ldb, void* H13, int64_t ldh, void* G,
                       int64_t ldg, int64_t M, int64_t H, int64_t K, int dtype, void* stream) {
   FK_CHECK_ARG(H > 0 && H % 4 == 0, "fk_gemm_nt_swiglu: hidden size must be a multiple of 4");
-  if (A && W13 && H13 && G && (((uintptr_t)A | (uintptr_t)W13 | (uintptr_t)H13 | (uintptr_t)G) & 15) == 0 && M > 0 &&
-      fk_mlp_up_fused_ok(M, H, K, lda, ldb, ldh, ldg, dtype))          // wide bf16 MLPs at d = 384: the token-on-the-lane kernel (mlp_fused.hip), same bits
+  if (swiglu_takes_lane(M, H, K, lda, ldb, ldh, ldg, aligned16(A, W13, H13, G), dtype))
     return fk_mlp_up_fused_launch(A, lda, W13, ldb, H13, ldh, G, ldg, M, H, stream);
   return launch_nt("fk_gemm_nt_swiglu", A, lda, W13, ldb, H13, ldh, M, 2 * H, K, nullptr, nullptr, 0, 0, dtype, dtype, 1, G, ldg, stream);
 }
@@ -1707,6 +1720,25 @@ int fk_gemm_nt_route(int64_t M, int64_t N, int64_t K, int dtype, int vec_epi, in
   FK_CHECK_ARG(M > 0 && N > 0 && K > 0 && mode >= 0 && mode <= 2, "fk_gemm_nt_route: bad problem M=%lld N=%lld K=%lld mode=%d", (long long)M, (long long)N, (long long)K, mode);
   if (dtype == FK_F32) return FK_NT_ROUTE_F32;
   return (int)nt_route(M, N, K, dtype, vec_epi != 0, mode, has_rope != 0);
+}
+
+// FK_NT_LANE where the entry point takes the token-on-the-lane kernel, else what launch_nt would run: nt_route with the vector epilogue as
+// launch_nt decides it from what a query knows (N and the output's leading dimension % 8 == 0, an aligned output)
+int fk_gemm_nt_rope_route(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, int has_bias, int64_t T, int64_t pos_off,
+                          int64_t D, int64_t rot_cols, int64_t q_cols, int align_ok, int dtype) {
+  FK_CHECK_ARG(dtype == FK_F32 || dtype == FK_BF16, "fk_gemm_nt_rope_route: bad dtype %d", dtype);
+  FK_CHECK_ARG(M > 0 && N > 0 && K > 0, "fk_gemm_nt_rope_route: bad problem M=%lld N=%lld K=%lld", (long long)M, (long long)N, (long long)K);
+  if (rope_takes_lane(M, N, K, lda, ldb, ldc, has_bias != 0, T, pos_off, D, rot_cols, q_cols, align_ok != 0, dtype)) return FK_NT_LANE;
+  if (dtype == FK_F32) return FK_NT_ROUTE_F32;
+  return (int)nt_route(M, N, K, dtype, N % 8 == 0 && ldc % 8 == 0 && align_ok != 0, 0, true);
+}
+
+int fk_gemm_nt_swiglu_route(int64_t M, int64_t H, int64_t K, int64_t lda, int64_t ldb, int64_t ldh, int64_t ldg, int align_ok, int dtype) {
+  FK_CHECK_ARG(dtype == FK_F32 || dtype == FK_BF16, "fk_gemm_nt_swiglu_route: bad dtype %d", dtype);
+  FK_CHECK_ARG(M > 0 && H > 0 && K > 0, "fk_gemm_nt_swiglu_route: bad problem M=%lld H=%lld K=%lld", (long long)M, (long long)H, (long long)K);
+  if (swiglu_takes_lane(M, H, K, lda, ldb, ldh, ldg, align_ok != 0, dtype)) return FK_NT_LANE;
+  if (dtype == FK_F32) return FK_NT_ROUTE_F32;
+  return (int)nt_route(M, 2 * H, K, dtype, (2 * H) % 8 == 0 && ldh % 8 == 0 && align_ok != 0, 1, false);
 }
 
 // what fk_gemm_tn does with a shape: the kernel (tile columns of the large-tile kernel, 0 = the small one), the number of split slabs and

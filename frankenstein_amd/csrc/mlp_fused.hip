@@ -836,10 +836,10 @@ static bool mu_grid_fills(int64_t M) {
   const int64_t wg = fk_cdiv(M, MU_TOK), rounds = fk_cdiv(wg, 256);
   return wg * 10 >= rounds * 256 * 7;
 }
-bool fk_qkv_rope_fused_ok(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, const void* bias, int64_t T, int64_t D, int64_t rot_cols,
+bool fk_qkv_rope_fused_ok(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, bool has_bias, int64_t T, int64_t D, int64_t rot_cols,
                           int64_t q_cols, int dtype) {
   // anything launch_nt would refuse (an empty problem, a leading dimension shorter than its row) is left to it: this kernel has no checks of its own
-  return dtype == FK_BF16 && K == MF_D && D == 64 && N > 0 && N < (1LL << 31) && N % 64 == 0 && rot_cols % 64 == 0 && q_cols % 64 == 0 && rot_cols <= N && !bias &&
+  return dtype == FK_BF16 && K == MF_D && D == 64 && N > 0 && N < (1LL << 31) && N % 64 == 0 && rot_cols % 64 == 0 && q_cols % 64 == 0 && rot_cols <= N && !has_bias &&
          mu_grid_fills(M) && M < (1LL << 31) && T > 0 && M % T == 0 && lda % 8 == 0 && ldb % 8 == 0 && ldc % 8 == 0 && lda >= K && ldb >= K && ldc >= N &&
          64 * ldb * 2 < (1LL << 32);
 }
@@ -874,6 +874,13 @@ extern "C" int fk_debug_mf_stamps(unsigned long long* out, int reset) {
 }
 #endif
 
+// whole 128-token tiles, and the dh13 rows addressable with 32-bit byte offsets from a per-chunk scalar base: the generated-stream kernel;
+// everything else the kernel hipcc schedules (host only; fk_mlp_bwd_fused asks the same function)
+extern "C" int fk_mlp_bwd_fused_route(int64_t M, int64_t lddh) {
+  FK_CHECK_ARG(M > 0 && lddh > 0, "fk_mlp_bwd_fused_route: bad problem M=%lld lddh=%lld", (long long)M, (long long)lddh);
+  return M % MF_TOK == 0 && M * lddh * 2 < (1LL << 32) ? FK_MLP_BWD_ASM : FK_MLP_BWD_HIPCC;
+}
+
 extern "C" int fk_mlp_bwd_fused(const void* dY, int64_t lddy, const void* W2T, int64_t ldw2t, const void* H13, int64_t ldh, const void* W13T,
                                 int64_t ldw13t, void* dH13, int64_t lddh, void* dX, int64_t lddx, int64_t M, int64_t H, int64_t D, int dtype,
                                 void* stream) {
@@ -890,8 +897,7 @@ extern "C" int fk_mlp_bwd_fused(const void* dY, int64_t lddy, const void* W2T, i
                "fk_mlp_bwd_fused: pointers must be 16-byte aligned");
   MlpBwdArgs a{(const bf16_t*)dY, (const bf16_t*)W2T, (const bf16_t*)H13, (const bf16_t*)W13T, (bf16_t*)dH13, (bf16_t*)dX,
                lddy, ldw2t, ldh, ldw13t, lddh, lddx, (int)M, (int)H};
-  // whole 128-token tiles, and the dh13 rows addressable with 32-bit byte offsets from a per-chunk scalar base: the generated-stream kernel
-  if (M % MF_TOK == 0 && M * lddh * 2 < (1LL << 32))
+  if (fk_mlp_bwd_fused_route(M, lddh) == FK_MLP_BWD_ASM)
     fk_launch_lds<mlp_bwd_fused_asm_kernel>(dim3((unsigned)(M / MF_TOK)), dim3(MF_NW * 64), MF_LDS, (hipStream_t)stream, a);
   else
     fk_launch_lds<mlp_bwd_fused_kernel>(dim3((unsigned)fk_cdiv(M, MF_TOK)), dim3(MF_NW * 64), MF_LDS, (hipStream_t)stream, a);

@@ -198,8 +198,11 @@ def mlp_bwd_fused(dy: Tensor, w2t: Tensor, h13: Tensor, w13t: Tensor) -> Tuple[T
 # the kernels fk_gemm_nt and its fused forms choose between (fk_gemm_nt_route); NT_ROUTE_F32: fp32 operands, the staged fp32 kernel
 NT_RING2, NT_RING192, NT_RING128, NT_BIG, NT_GLDS4, NT_GLDS, NT_STAGED = _lib.NT_RING2, _lib.NT_RING192, _lib.NT_RING128, _lib.NT_BIG, _lib.NT_GLDS4, _lib.NT_GLDS, _lib.NT_STAGED
 NT_ROUTE_F32 = _lib.NT_ROUTE_F32
+NT_LANE = _lib.NT_LANE                                     # the token-on-the-lane kernels (gemm_nt_rope_route / gemm_nt_swiglu_route only)
 NT_ROUTE_NAMES = {NT_RING2: "NT_RING2", NT_RING192: "NT_RING192", NT_RING128: "NT_RING128", NT_BIG: "NT_BIG", NT_GLDS4: "NT_GLDS4",
-                  NT_GLDS: "NT_GLDS", NT_STAGED: "NT_STAGED", NT_ROUTE_F32: "NT_STAGED_F32"}
+                  NT_GLDS: "NT_GLDS", NT_STAGED: "NT_STAGED", NT_LANE: "NT_LANE", NT_ROUTE_F32: "NT_STAGED_F32"}
+MLP_BWD_HIPCC, MLP_BWD_ASM = _lib.MLP_BWD_HIPCC, _lib.MLP_BWD_ASM      # fk_mlp_bwd_fused_route
+MLP_BWD_ROUTE_NAMES = {MLP_BWD_HIPCC: "MLP_BWD_HIPCC", MLP_BWD_ASM: "MLP_BWD_ASM"}
 TN_SMALL, TN_BIG128, TN_BIG192 = 0, 128, 192               # fk_gemm_tn_route
 
 
@@ -210,6 +213,36 @@ def gemm_nt_route(M: int, N: int, K: int, dtype=torch.bfloat16, vec_epi: bool = 
     r = lib().fk_gemm_nt_route(M, N, K, fk_dtype(dtype), int(vec_epi), mode, int(has_rope))
     if r == -1:
         _lib.check(r, "fk_gemm_nt_route")
+    return r
+
+
+def gemm_nt_swiglu_route(M: int, H: int, K: int, lda: Optional[int] = None, ldb: Optional[int] = None, ldh: Optional[int] = None,
+                         ldg: Optional[int] = None, align_ok: bool = True, dtype=torch.bfloat16) -> int:
+    """The kernel gemm_nt_swiglu (fk_gemm_nt_swiglu) runs for this call: NT_LANE (the token-on-the-lane kernel) or the tiled kernel
+    gemm_nt_route names for mode 1.  Leading dimensions default to the row widths; align_ok: every pointer is 16-byte aligned."""
+    r = lib().fk_gemm_nt_swiglu_route(M, H, K, K if lda is None else lda, K if ldb is None else ldb, 2 * H if ldh is None else ldh,
+                                      H if ldg is None else ldg, int(align_ok), fk_dtype(dtype))
+    if r == -1:
+        _lib.check(r, "fk_gemm_nt_swiglu_route")
+    return r
+
+
+def gemm_nt_rope_route(M: int, N: int, K: int, T: int, D: int, rot_cols: int, q_cols: int = 0, pos_off: int = 0, has_bias: bool = False,
+                       lda: Optional[int] = None, ldb: Optional[int] = None, ldc: Optional[int] = None, align_ok: bool = True,
+                       dtype=torch.bfloat16) -> int:
+    """The kernel gemm_nt_rope (fk_gemm_nt_rope) runs for this call: NT_LANE or the tiled kernel gemm_nt_route names with has_rope."""
+    r = lib().fk_gemm_nt_rope_route(M, N, K, K if lda is None else lda, K if ldb is None else ldb, N if ldc is None else ldc, int(has_bias),
+                                    T, pos_off, D, rot_cols, q_cols, int(align_ok), fk_dtype(dtype))
+    if r == -1:
+        _lib.check(r, "fk_gemm_nt_rope_route")
+    return r
+
+
+def mlp_bwd_fused_route(M: int, lddh: int) -> int:
+    """MLP_BWD_ASM (the generated-stream kernel) or MLP_BWD_HIPCC: the kernel mlp_bwd_fused runs for M rows of a dh13 with leading dimension lddh."""
+    r = lib().fk_mlp_bwd_fused_route(M, lddh)
+    if r == -1:
+        _lib.check(r, "fk_mlp_bwd_fused_route")
     return r
 
 

@@ -98,11 +98,26 @@ int fk_mlp_bwd_fused(const void* dY, int64_t lddy, const void* W2T, int64_t ldw2
  *   FK_NT_* values below for bf16 operands, FK_NT_ROUTE_F32 for fp32 operands (always the register-staged kernel).  vec_epi: N, ldc
  *   (and ldr) are multiples of 8 and C (and the residual) 16-byte aligned; mode: 0 plain / bias / residual / RoPE, 1 fk_gemm_nt_swiglu
  *   (N = 2H), 2 fk_gemm_nt_dswiglu (N = H); has_rope: fk_gemm_nt_rope.  The token-on-the-lane kernels that fk_gemm_nt_rope and
- *   fk_gemm_nt_swiglu put in front at K = 384 from 45 825 rows on are not part of the answer.  Follows the FK_NT_* environment knobs
+ *   fk_gemm_nt_swiglu put in front at K = 384 from 45 825 rows on are not part of the answer (fk_gemm_nt_rope_route /
+ *   fk_gemm_nt_swiglu_route below answer for a whole call of those two).  Follows the FK_NT_* environment knobs
  *   exactly as the launch does.                                                                                                    */
-enum { FK_NT_RING2 = 0, FK_NT_RING192 = 1, FK_NT_RING128 = 2, FK_NT_BIG = 3, FK_NT_GLDS4 = 4, FK_NT_GLDS = 5, FK_NT_STAGED = 6 };
+enum { FK_NT_RING2 = 0, FK_NT_RING192 = 1, FK_NT_RING128 = 2, FK_NT_BIG = 3, FK_NT_GLDS4 = 4, FK_NT_GLDS = 5, FK_NT_STAGED = 6, FK_NT_LANE = 7 };
 #define FK_NT_ROUTE_F32 (-2)
 int fk_gemm_nt_route(int64_t M, int64_t N, int64_t K, int dtype, int vec_epi, int mode, int has_rope);
+/* fk_gemm_nt_rope_route / fk_gemm_nt_swiglu_route: the whole answer for a call of fk_gemm_nt_rope / fk_gemm_nt_swiglu (host only, nothing
+ *   is launched): FK_NT_LANE where the entry point hands the call to a token-on-the-lane kernel (bf16, K = 384, 256-token workgroups that
+ *   fill at least 70 % of their rounds of 256, i.e. 45 825 .. 65 536 rows, 91 649 .. 131 072, ...; H % 32 == 0, or N % 64 == 0 with D = 64,
+ *   rot_cols % 64 == 0, q_cols % 64 == 0 and no bias; leading dimensions multiples of 8 that cover their rows; pos_off >= 0), else what
+ *   fk_gemm_nt_route answers for the tiled form of the call.  align_ok: every pointer of the call (A, the weight, the outputs, the
+ *   rotation table) is non-null and 16-byte aligned.  The entry points decide with the same functions.                              */
+int fk_gemm_nt_rope_route(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, int has_bias, int64_t T, int64_t pos_off,
+                          int64_t D, int64_t rot_cols, int64_t q_cols, int align_ok, int dtype);
+int fk_gemm_nt_swiglu_route(int64_t M, int64_t H, int64_t K, int64_t lda, int64_t ldb, int64_t ldh, int64_t ldg, int align_ok, int dtype);
+/* fk_mlp_bwd_fused_route: which of its two kernels fk_mlp_bwd_fused runs (host only): FK_MLP_BWD_ASM, the generated-stream kernel, for
+ *   whole 128-token tiles whose dH13 rows are addressable with 32-bit byte offsets (M % 128 == 0 and M * lddh * 2 < 2^32), else
+ *   FK_MLP_BWD_HIPCC, the kernel hipcc schedules.                                                                                   */
+enum { FK_MLP_BWD_HIPCC = 0, FK_MLP_BWD_ASM = 1 };
+int fk_mlp_bwd_fused_route(int64_t M, int64_t lddh);
 /* fk_gemm_tn: C[N1,N2] (fp32) (+)= sum_m A[m,N1] * B[m,N2]  — the weight gradient dW = dY^T X of a Linear
  *   (autograd of the call sites above).  Split over m with deterministic slab reduction.                     */
 size_t fk_gemm_tn_workspace_bytes(int64_t M, int64_t N1, int64_t N2, int dtype);

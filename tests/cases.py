@@ -319,3 +319,58 @@ ATTN_SPIKE_CASES = [
     _attn("bf16", 1, 2, 200, 200, 64, ("block", 8), _PS, ps=True, spike=-2048.0),
     _attn("bf16", 1, 2, 256, 256, 64, ("none",), ("FWD_ASM", "DQ_ASM", "DKDVW_ASM"), ps=True, spike=-2048.0),
 ]
+
+
+# ------------------------------------------------------------------------------------------------ token-on-the-lane kernels
+# The shapes of tests/test_lane_kernels_gpu.py (csrc/mlp_fused.hip: mlp_up_fused_kernel, qkv_rope_fused_kernel, mlp_bwd_fused_kernel and
+# mlp_bwd_fused_asm_kernel), shared with tests/test_lane_routes_cpu.py, which pins the kernel each of them reaches
+# (kernels.gemm_nt_swiglu_route / gemm_nt_rope_route / mlp_bwd_fused_route) and checks the inputs of tests/lane_ref.py against mutations
+# of the float64 reference.  d = 384 everywhere.  The forward kernels take a call only when its 256-token workgroups fill at least 70 %
+# of their rounds of 256 (mu_grid_fills): 45 825 .. 65 536 rows in one round, 91 649 .. 131 072 in two.
+LANE_D = 384
+LANE_M_ACCEPTED = ((45825, 65536), (91649, 131072))        # per number of rounds: first and last row count taken
+LANE_M_REJECTED = ((1, 45824), (65537, 91648), (131073, 137472))
+
+# up-projection + SwiGLU: (route, M, H).  H = 32 / 64 / 96 / 160: 1, 2, 3 and 5 chunks of 32 hidden units; M = 45 825 (one row in the
+# last workgroup), 46 080 (whole workgroups), 49 007 (cuts an 8-row h13 store group and a 16-row g group); one two-round case
+LANE_UP_CASES = [("NT_LANE", M, H) for H in (32, 64, 96, 160) for M in (45825, 46080, 49000 + 7)] + [("NT_LANE", 91649, 32)]
+
+# q|k|v projection + RoPE, D = 64: (route, B, T, N, rot_cols, q_cols, pos_off, per_sample_table); the table has exactly pos_off + T rows
+LANE_QKV_CASES = [
+    ("NT_LANE", 45825, 1, 64, 0, 0, 0, False),
+    ("NT_LANE", 47, 975, 64, 64, 0, 5, True),
+    ("NT_LANE", 15275, 3, 64, 64, 64, 0, True),
+    ("NT_LANE", 1, 45825, 64, 64, 64, 5, False),
+    ("NT_LANE", 15275, 3, 192, 0, 0, 5, False),
+    ("NT_LANE", 45825, 1, 192, 192, 0, 5, True),
+    ("NT_LANE", 47, 975, 192, 192, 192, 0, False),
+    ("NT_LANE", 1, 45825, 192, 128, 64, 0, True),
+    ("NT_LANE", 47, 975, 384, 0, 0, 0, True),
+    ("NT_LANE", 15275, 3, 384, 384, 0, 5, False),
+    ("NT_LANE", 45825, 1, 384, 384, 384, 0, False),
+    ("NT_LANE", 47, 975, 384, 256, 128, 5, True),
+    ("NT_LANE", 15275, 3, 384, 256, 128, 0, True),
+    ("NT_LANE", 1, 45825, 384, 256, 128, 5, False),
+]
+
+# the backward chain (fk_mlp_bwd_fused): (kernel, M, H); operands depend on H alone (the first M rows of 1024), so cases of one H are
+# the same problem cut at different rows: (256, 64) on the generated stream and (255, 64) on the hipcc kernel are compared row for row
+LANE_BWD_CASES = [
+    ("MLP_BWD_HIPCC", 1, 32), ("MLP_BWD_HIPCC", 384 + 9, 32), ("MLP_BWD_ASM", 128, 32),
+    ("MLP_BWD_HIPCC", 7, 64), ("MLP_BWD_HIPCC", 255, 64), ("MLP_BWD_ASM", 256, 64),
+    ("MLP_BWD_HIPCC", 33, 96), ("MLP_BWD_HIPCC", 1000, 96), ("MLP_BWD_ASM", 128, 96),
+    ("MLP_BWD_HIPCC", 127, 128), ("MLP_BWD_HIPCC", 384 + 9, 128), ("MLP_BWD_ASM", 256, 128),
+    ("MLP_BWD_HIPCC", 129, 160), ("MLP_BWD_HIPCC", 7, 160), ("MLP_BWD_ASM", 256, 160),
+]
+LANE_BWD_ROWS = 1024                                        # rows the backward operands are drawn for
+LANE_BWD_PAIR = (("MLP_BWD_ASM", 256, 64), ("MLP_BWD_HIPCC", 255, 64))
+
+# saturated gates: pre-activations of exactly +-these values (both sides of __expf's overflow at 88.72)
+LANE_SATURATED = (8, 16, 32, 64, 88, 96, 128)
+
+# padded leading dimensions (test_padded_leading_dimensions): every operand and output of a call in a wider sentinel-filled buffer, pads
+# of 8 .. 72 elements so that no two leading dimensions of a call are equal.  up: (M, H, pads of a, w13, h13, g); qkv: (B, T, N, rot, q,
+# pos_off, per_sample, pads of a, w, out); backward: (M, H, pads of dy, w2t, h13, w13t, dh13, dx), a whole-tile and a ragged M
+LANE_PAD_UP = (45825, 32, (8, 16, 24, 40))
+LANE_PAD_QKV = (47, 975, 192, 128, 64, 5, True, (8, 16, 24))
+LANE_PAD_BWD = [(128, 96, (8, 16, 24, 40, 56, 72)), (129, 96, (72, 56, 40, 24, 16, 8))]

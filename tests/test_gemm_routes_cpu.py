@@ -44,7 +44,7 @@ def test_route_constants_match_the_header(K):
     vals = {k.strip()[3:]: int(v) for k, v in (e.split("=") for e in enum.split(","))}
     assert vals == {n: v for v, n in K.NT_ROUTE_NAMES.items() if v >= 0}
     assert int(re.search(r"#define FK_NT_ROUTE_F32 \((-?\d+)\)", hdr).group(1)) == K.NT_ROUTE_F32 < 0
-    assert sorted(vals.values()) == list(range(7))
+    assert sorted(vals.values()) == list(range(8)) and vals["NT_LANE"] == 7      # NT_LANE: fk_gemm_nt_rope_route / fk_gemm_nt_swiglu_route only
 
 
 @pytest.mark.parametrize("case", cases.NT_PLAIN_CASES, ids=lambda c: "-".join(map(str, c)))

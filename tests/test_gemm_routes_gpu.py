@@ -29,7 +29,8 @@ What reaches what (ids start with the route; "F32" = fp32 operands on the staged
   test_rope                        the same routes; D 8 / 16 / 64 / 128, T 5 / 57 / 300, bias, pos_off, pre-scaled query columns, shared and
                                    per-sample tables (the wrap at a sample boundary in the prefetched and the in-sweep form)
   test_gemm_tn_exact               one split, empty trailing splits, a 3-row last split, the scalar slab reduction, the large-tile kernel
-(the per-sample table of the token-on-the-lane kernel: tests/test_kernels_gpu.py, test_qkv_projection_with_rope_token_on_the_lane_...)"""
+(the token-on-the-lane kernels that take over from 45 825 rows on at K = 384: tests/test_lane_kernels_gpu.py, on these operands and this
+bound; their per-sample table also in tests/test_kernels_gpu.py, test_qkv_projection_with_rope_token_on_the_lane_...)"""
 import numpy as np
 import pytest
 import torch

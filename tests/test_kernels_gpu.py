@@ -751,9 +751,14 @@ def test_qkv_projection_with_rope_token_on_the_lane_equals_the_tiled_kernel_bit_
     tab, qtab = both[0], both[1]
     sl = (lambda t, b0, b1: t[b0:b1]) if per_sample else (lambda t, b0, b1: t)
     kw = (lambda b0, b1: dict(q_cols=H * D, q_table=sl(qtab, b0, b1))) if prescaled else (lambda b0, b1: {})
+    # the whole call takes the token-on-the-lane kernel, each reference piece a tiled one (host-side query, these pointers and strides)
+    route = lambda rows: K.NT_ROUTE_NAMES[K.gemm_nt_rope_route(rows, N, d, T, D, 2 * H * D, H * D if prescaled else 0, 5, False, x.stride(0), w.stride(0), N,
+                                                               all(t_.data_ptr() % 16 == 0 for t_ in (x, w, tab)), x.dtype)]
+    assert route(M) == "NT_LANE"
     out = K.gemm_nt_rope(x, w, None, tab, T, 5, D, 2 * H * D, **kw(0, B))
     cut = (B // 2) * T
     assert M >= 45825 and cut < 45825 and M - cut < 45825
+    assert route(cut) != "NT_LANE" != route(M - cut)
     ref = torch.cat([K.gemm_nt_rope(x[b0 * T:b1 * T], w, None, sl(tab, b0, b1), T, 5, D, 2 * H * D, **kw(b0, b1)) for b0, b1 in ((0, B // 2), (B // 2, B))])
     assert torch.equal(out, ref), float((out.float() - ref.float()).abs().max())
     y = (x.float().cpu() @ w.float().cpu().t()).view(B, T, 3 * H, D // 2, 2)
@@ -789,9 +794,12 @@ def test_swiglu_up_projection_token_on_the_lane_equals_the_tiled_kernel_bit_for_
     g = torch.Generator().manual_seed(M + 3 * H)
     x = (torch.randn(M, d, generator=g) * 0.7).bfloat16().cuda()
     w13 = (torch.randn(2 * H, d, generator=g) / math.sqrt(d)).bfloat16().cuda()
+    route = lambda rows: K.NT_ROUTE_NAMES[K.gemm_nt_swiglu_route(rows, H, d, x.stride(0), w13.stride(0), 2 * H, H, x.data_ptr() % 16 == 0 and w13.data_ptr() % 16 == 0, x.dtype)]
+    assert route(M) == "NT_LANE"                          # the whole call: the token-on-the-lane kernel; each reference piece: a tiled one
     h13, gg = K.gemm_nt_swiglu(x, w13)
     cut = M // 2
     assert M >= 45825 and M - cut < 45825
+    assert route(cut) != "NT_LANE" != route(M - cut)
     ref = [K.gemm_nt_swiglu(x[a:b], w13) for a, b in ((0, cut), (cut, M))]
     h13_ref, g_ref = torch.cat([r[0] for r in ref]), torch.cat([r[1] for r in ref])
     assert torch.equal(h13, h13_ref), float((h13.float() - h13_ref.float()).abs().max())
@@ -819,6 +827,8 @@ def test_mlp_backward_fused_equals_the_two_gemm_kernels_bit_for_bit(K, case):
     w13t = (torch.randn(d, 2 * H, generator=g) / math.sqrt(H)).bfloat16().cuda()
     dh_ref = K.gemm_nt_dswiglu(dy, w2t, h13)
     dx_ref = K.gemm_nt(dh_ref, w13t)
+    # whole 128-token tiles: the generated-stream kernel; 1000 and 4133 rows: the hipcc kernel
+    assert K.MLP_BWD_ROUTE_NAMES[K.mlp_bwd_fused_route(M, 2 * H)] == ("MLP_BWD_ASM" if M in (128, 256, 384, 1024, 4096, 33 * 1024) else "MLP_BWD_HIPCC")
     dh, dx = K.mlp_bwd_fused(dy, w2t, h13, w13t)
     assert torch.equal(dh, dh_ref), float((dh.float() - dh_ref.float()).abs().max())
     assert torch.equal(dx, dx_ref), float((dx.float() - dx_ref.float()).abs().max())
