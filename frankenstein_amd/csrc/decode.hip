@@ -14,15 +14,28 @@
 //                       it keeps the token history of every row on the device (two buffers swapped by step parity under a beam search)
 // The select, the beam attention and the sampling are one kernel template each, and so are their host sides (beam_select,
 // check_ / launch_attn_decode_beam and sample_topk behind the kernels): the entry points of a family share their checks and their launch.
+// What the kernels share is written once, in front of its first user:
+//   clamp_index                       every slot / parent / table / token index that a corrupt input must not take outside its buffer
+//   softmax_merge                     the online softmax of both attention kernels: the merge of the lanes' (m, l, o[]) across the wave
+//                                     (wave_max / wave_sum of fk_common.h) and the four waves, and the store
+//   row_key / for_row_keys            logit i of a row as the sampler and the beam top-k see it (scaled, with its sortable image), and the
+//                                     strided or contiguous loop over a row
+//   radix_select + bin_walk           the four 8-bit passes of radix_select_kth (a count per key) and mass_select_tau (a mass per key)
+//   block_reduce / block_scan_inclusive   over the SAMPLE_THREADS of a sampling or top-k block
+//   step_tail                         the end of a decode step: live rows, ticket, the last block advances the counters
+//   rank_desc                         rank among (value descending, index ascending) by counting
+// and on the host FK_BY_HEAD_DIM (nests with FK_BY_DTYPE), check_logit_rows and make_eos_args.
 #include "fk_common.h"
 
 namespace {
 
+// x as an index into n entries: a corrupt or out-of-range value reads or writes a wrong entry, never outside the buffer
+template <typename I> FK_DEV I clamp_index(I x, I n) { return x < 0 ? 0 : (x >= n ? n - 1 : x); }
+
 template <typename T>
 __global__ void gpt_embed_step_kernel(const int64_t* idx, const float* wte, const float* wpe, const int32_t* pos, T* out, int dim, int64_t vocab) {
   const int b = blockIdx.x;
-  int64_t tok = idx[b];
-  tok = tok < 0 ? 0 : (tok >= vocab ? vocab - 1 : tok);
+  const int64_t tok = clamp_index(idx[b], vocab);
   const float* e = wte + tok * dim;
   const float* pe = wpe + (int64_t)pos[0] * dim;
   for (int c = threadIdx.x; c < dim; c += blockDim.x) out[(int64_t)b * dim + c] = from_f32<T>(e[c] + pe[c]);
@@ -36,13 +49,47 @@ __global__ void kv_append_kernel(const T* qkv, T* kv, const int32_t* pos, int d,
   for (int c = threadIdx.x; c < 2 * d; c += blockDim.x) dst[c] = src[c];
 }
 
+// ---- online softmax of one query, shared by the two attention kernels.  A lane keeps (m, l, o[N]) over the keys it has seen: the running
+// maximum of the scores, the sum of exp(s - m) and N elements of the values weighted so.  The update by one key stays written out in the two
+// key loops: as a shared call it compiled, under -ffp-contract=fast, to the other fusion of o * a + pj * v in the fp32 beam kernels
+// (profiles/decode_shared_asm_diff.txt), and the outputs are held to the bits of the loops as they stand.
+// The merge of the partials of a block of 256 lanes, and the store of the D outputs to out[0 .. D).  The lanes of a wave whose numbers agree
+// modulo STOP hold the same slice `sub` (N elements) of the D outputs: they are merged by shuffles (offsets 32 .. STOP), lanes 0 .. STOP - 1 of
+// each wave put their slice into red[wave] (behind it the wave's maximum and sum), and thread t < D merges the four waves for output t.
+// The order of the floating-point operations is part of the result: the weight w goes on before the shuffles, the division comes last.
+template <typename T, int D, int N, int STOP> FK_DEV void softmax_merge(float m, float l, float (&o)[N], int sub, float (*red)[D + 2], T* out) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const float wm = wave_max<STOP>(m);
+  const float w = (m == -INFINITY) ? 0.0f : __expf(m - wm);
+  l = wave_sum<STOP>(l * w);
+#pragma unroll
+  for (int i = 0; i < N; ++i) o[i] = wave_sum<STOP>(o[i] * w);
+  if (lane < STOP) {
+    if (sub == 0) { red[wave][D] = wm; red[wave][D + 1] = l; }
+#pragma unroll
+    for (int i = 0; i < N; ++i) red[wave][sub * N + i] = o[i];
+  }
+  __syncthreads();
+  if (tid < D) {
+    const float M4 = fmaxf(fmaxf(red[0][D], red[1][D]), fmaxf(red[2][D], red[3][D]));
+    float L = 0.0f, acc = 0.0f;
+#pragma unroll
+    for (int wv = 0; wv < 4; ++wv) {
+      const float ww = (red[wv][D] == -INFINITY) ? 0.0f : __expf(red[wv][D] - M4);
+      L += red[wv][D + 1] * ww;
+      acc += red[wv][tid] * ww;
+    }
+    out[tid] = from_f32<T>(acc / L);
+  }
+}
+
 // block = (b, h), 256 threads; thread t owns keys t, t + 256, ...; partial (max, sum, o[D]) merged wave- then block-wide
 template <typename T, int D>
 __global__ __launch_bounds__(256) void attn_decode_kernel(const T* q, int64_t q_bs, const T* kv, int64_t kv_bs, int64_t kv_rs, T* out,
                                                           int64_t o_bs, const int32_t* pos, int H, float scale) {
   __shared__ float sq[D];
   __shared__ float red[4][D + 2];
-  const int h = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int h = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
   const int nk = pos[0] + 1;
   const int d_model = H * D;
   if (tid < D) sq[tid] = to_f32<T>(q[(int64_t)b * q_bs + h * D + tid]) * scale;
@@ -62,41 +109,8 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const T* q, int64_t q_
     for (int i = 0; i < D; ++i) o[i] = o[i] * a + pj * to_f32<T>(vr[i]);
     m = mn;
   }
-  // wave merge
-  float wm = m;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) wm = fmaxf(wm, __shfl_xor(wm, off, 64));
-  const float w = (m == -INFINITY) ? 0.0f : __expf(m - wm);
-  l *= w;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) l += __shfl_xor(l, off, 64);
-#pragma unroll
-  for (int i = 0; i < D; ++i) {
-    float v = o[i] * w;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    o[i] = v;
-  }
-  if (lane == 0) {
-    red[wave][D] = wm;
-    red[wave][D + 1] = l;
-#pragma unroll
-    for (int i = 0; i < D; ++i) red[wave][i] = o[i];
-  }
-  __syncthreads();
-  if (tid < D) {
-    const float M4 = fmaxf(fmaxf(red[0][D], red[1][D]), fmaxf(red[2][D], red[3][D]));
-    float L = 0.0f, acc = 0.0f;
-#pragma unroll
-    for (int wv = 0; wv < 4; ++wv) {
-      const float ww = (red[wv][D] == -INFINITY) ? 0.0f : __expf(red[wv][D] - M4);
-      L += red[wv][D + 1] * ww;
-      acc += red[wv][tid] * ww;
-    }
-    out[(int64_t)b * o_bs + h * D + tid] = from_f32<T>(acc / L);
-  }
+  softmax_merge<T, D, D, 1>(m, l, o, 0, red, out + (int64_t)b * o_bs + h * D);      // every lane holds all of D
 }
-
 
 // ---- sampling tail of GPT.generate on the device (models/gpt2_model.py:340-351): logits / temperature -> top-k crop (everything below
 // the k-th largest value becomes -inf; ties with it stay, like `logits < v[:, [-1]]`) -> softmax -> one multinomial draw.  One block per
@@ -118,66 +132,115 @@ FK_DEV void philox4x32_10(unsigned k0, unsigned k1, unsigned (&c)[4]) {
     k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
   }
 }
-template <typename F> FK_DEV float block_reduce(float v, float* red, F op, float ident) {
+// maximum (MAX) or sum of v over the SAMPLE_THREADS of the block; red: one word per wave
+template <bool MAX> FK_DEV float block_reduce(float v, float* red) {
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = op(v, __shfl_xor(v, o, 64));
+  v = MAX ? wave_max(v) : wave_sum(v);
   __syncthreads();
   if (lane == 0) red[wv] = v;
   __syncthreads();
-  float r = ident;
-  for (int i = 0; i < SAMPLE_THREADS / 64; ++i) r = op(r, red[i]);
+  float r = MAX ? -INFINITY : 0.0f;
+  for (int i = 0; i < SAMPLE_THREADS / 64; ++i) r = MAX ? fmaxf(r, red[i]) : r + red[i];
   return r;
 }
 
-// k-th largest of the V values row[i] * inv_temp (1 <= k <= V) as its sortable key, by a 4-pass radix select, 8 bits per pass from the
-// top; every thread of the block calls it and gets the same key.  hist: 256 words of LDS, sel_prefix / sel_remaining: one word each.
-// Behind it *sel_remaining says how many of the values EQUAL to the k-th belong to the k largest (k minus the count of strictly larger
-// ones) and hist[key & 255] how many such values the row holds.
-FK_DEV unsigned radix_select_kth(const float* row, int V, float inv_temp, int k, unsigned* hist, unsigned* sel_prefix, unsigned* sel_remaining) {
+// Inclusive scan (Hillis-Steele) over the SAMPLE_THREADS words of LDS into which every thread has just stored its own
+template <typename T> FK_DEV void block_scan_inclusive(T* scan) {
   const int tid = threadIdx.x;
-  if (tid == 0) { *sel_prefix = 0u; *sel_remaining = (unsigned)k; }
+  __syncthreads();
+  for (int o = 1; o < SAMPLE_THREADS; o <<= 1) {
+    const T add = tid >= o ? scan[tid - o] : T(0);
+    __syncthreads();
+    scan[tid] += add;
+    __syncthreads();
+  }
+}
+
+// Logit i of a row as the sampler and the beam top-k see it: x = row[i] * inv_temp and the sortable image of x
+struct RowKey { float x; unsigned key; };
+FK_DEV RowKey row_key(const float* row, int i, float inv_temp) {
+  const float x = row[i] * inv_temp;
+  return {x, f32_sortable(x)};
+}
+// f(i, x, key) for i = i0, i0 + stride, .. below i1: the block's strided pass over a row is (tid, V, SAMPLE_THREADS), a thread's contiguous chunk
+// (i0, i1, 1).  The draw and the tie order depend on the chunk form; the loops that leave early or run backwards call row_key themselves.
+template <typename F> FK_DEV void for_row_keys(const float* row, float inv_temp, int i0, int i1, int stride, F f) {
+  for (int i = i0; i < i1; i += stride) {
+    const RowKey e = row_key(row, i, inv_temp);
+    f(i, e.x, e.key);
+  }
+}
+
+// The first wave's walk over the 256 bins of a radix pass, from the top, until the running sum reaches the target rem0 = target(sum of all
+// bins): lane l owns the bins 255 - 4l .. 252 - 4l, a scan finds the lane, and the lane walks its 4 bins and publishes the prefix with the
+// bin's 8 bits in it and what of the target is left inside that bin.  CAN_MISS says what happens when the target lies beyond the total:
+// without it bin 0 takes whatever is left, as a walk that stops at bin 1 would; with it no lane answers and *sel_rem stays as it is.
+template <typename Acc, bool CAN_MISS, typename Target>
+FK_DEV void bin_walk(const Acc* hist, unsigned prefix, int shift, unsigned* sel_prefix, Acc* sel_rem, Target target) {
+  const int tid = threadIdx.x;                            // < 64
+  Acc h[4], mine = 0;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) { h[q] = hist[255 - 4 * tid - q]; mine += h[q]; }
+  Acc incl = mine;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const Acc up = __shfl_up(incl, o, 64);
+    if (tid >= o) incl += up;
+  }
+  const Acc rem0 = target(__shfl(incl, 63, 64));
+  const Acc before = incl - mine;                         // what the bins above this lane's hold
+  if (before < rem0 && (rem0 <= incl || (!CAN_MISS && tid == 63))) {      // one lane: the bins above hold less than the target, with its own they reach it
+    Acc rem = rem0 - before;
+    int q = 0;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      if (q == c && h[c] < rem) { rem -= h[c]; q = c + 1; }
+    }
+    *sel_prefix = prefix | ((unsigned)(255 - 4 * tid - q) << shift);
+    *sel_rem = rem;                                       // >= 1, and the chosen bin holds at least as much: the next pass reaches it too
+  }
+}
+
+// A 4-pass radix select over the sortable keys of the V values row[i] * inv_temp, 8 bits per pass from the top: every pass adds weigh(x, key)
+// (0: the key does not take part) of the keys that match the prefix found so far to a 256-bin histogram in LDS and walks the bins
+// (bin_walk) for the one that holds the target; target(pass, total) names it, *sel_rem starts as rem_init.  Every thread of the block calls
+// it and gets the same key; with CAN_MISS (rem_init is then 0) that is 0 when the first pass does not reach its target.  hist: 256 words of
+// LDS, sel_prefix / sel_rem: one word each.
+template <typename Acc, bool CAN_MISS, typename Weigh, typename Target>
+FK_DEV unsigned radix_select(const float* row, int V, float inv_temp, Acc rem_init, Acc* hist, unsigned* sel_prefix, Acc* sel_rem, Weigh weigh, Target target) {
+  const int tid = threadIdx.x;
+  if (tid == 0) { *sel_prefix = 0u; *sel_rem = rem_init; }
+#pragma unroll                                            // shift and mask are constants of each pass, and the first pass tests no prefix
   for (int pass = 0; pass < 4; ++pass) {
     const int shift = 24 - 8 * pass;
-    if (tid < 256) hist[tid] = 0u;
+    if (tid < 256) hist[tid] = 0;
     __syncthreads();
     const unsigned prefix = *sel_prefix, mask_hi = pass == 0 ? 0u : (0xFFFFFFFFu << (shift + 8));
-    for (int i = tid; i < V; i += SAMPLE_THREADS) {
-      const unsigned key = f32_sortable(row[i] * inv_temp);
-      if ((key & mask_hi) == prefix) atomicAdd(&hist[(key >> shift) & 255u], 1u);
-    }
-    __syncthreads();
-    if (tid < 64) {                                     // walk the 256 bins from the top until the k-th largest falls into one: lane l
-      const unsigned rem0 = *sel_remaining;             // of the first wave owns the bins 255 - 4l .. 252 - 4l, a scan finds the lane
-      unsigned h[4], mine = 0u;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) { h[q] = hist[255 - 4 * tid - q]; mine += h[q]; }
-      unsigned incl = mine;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const unsigned up = __shfl_up(incl, o, 64);
-        if (tid >= o) incl += up;
+    for_row_keys(row, inv_temp, tid, V, SAMPLE_THREADS, [&](int, float x, unsigned key) {
+      if ((key & mask_hi) == prefix) {
+        const Acc w = weigh(x, key);
+        if (w) atomicAdd(&hist[(key >> shift) & 255u], w);
       }
-      const unsigned before = incl - mine;              // keys in the bins above this lane's
-      if (before < rem0 && (rem0 <= incl || tid == 63)) {   // one lane; bin 0 takes whatever is left, as a walk that stops at bin 1 would
-        unsigned rem = rem0 - before;
-        int q = 0;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-          if (q == c && h[c] < rem) { rem -= h[c]; q = c + 1; }
-        }
-        *sel_prefix = prefix | ((unsigned)(255 - 4 * tid - q) << shift);
-        *sel_remaining = rem;
-      }
-    }
+    });
     __syncthreads();
+    if (tid < 64) bin_walk<Acc, CAN_MISS>(hist, prefix, shift, sel_prefix, sel_rem, [&](Acc total) { return target(pass, total); });
+    __syncthreads();
+    if (CAN_MISS && pass == 0 && *sel_rem == 0) return 0u;      // block-uniform
   }
   return *sel_prefix;
 }
 
+// k-th largest of the V values row[i] * inv_temp (1 <= k <= V) as its sortable key: radix_select with a count of 1 per key and the target
+// k, which the V >= k keys always reach (bin 0 takes whatever is left).  hist: 256 words of LDS, sel_prefix / sel_remaining: one word each.
+// Behind it *sel_remaining says how many of the values EQUAL to the k-th belong to the k largest (k minus the count of strictly larger
+// ones) and hist[key & 255] how many such values the row holds.
+FK_DEV unsigned radix_select_kth(const float* row, int V, float inv_temp, int k, unsigned* hist, unsigned* sel_prefix, unsigned* sel_remaining) {
+  return radix_select<unsigned, false>(row, V, inv_temp, (unsigned)k, hist, sel_prefix, sel_remaining, [](float, unsigned) { return 1u; },
+                                       [&](int, unsigned) { return *sel_remaining; });
+}
+
 // Nucleus (top-p) threshold of fk_sample_topp: the smallest key v among the kept keys (>= kth) whose strictly larger kept keys hold less than
-// top_p of the kept mass, mass(i) = exp(row[i] * inv_temp - mx).  radix_select_kth with a histogram of MASS per bin instead of a count: four
-// passes of 8 bits from the top over the keys that match the prefix, the first wave walks the 256 bins from the top as a scan and stops in the
+// top_p of the kept mass, mass(i) = exp(row[i] * inv_temp - mx).  radix_select with a histogram of MASS per bin instead of a count: the walk stops in the
 // bin in which the running mass reaches the target.  The masses are summed as integers, floor(e * 2^32) <= 2^32 in 64-bit LDS words (V < 2^31
 // of them cannot overflow), so neither the histogram nor any comparison depends on the order in which the atomics land.  The target is
 // floor(top_p * total) + 1 units: key v stays iff mass_gt(v) <= floor(top_p * total), the rule `mass_gt < top_p * total` up to one unit of
@@ -185,55 +248,19 @@ FK_DEV unsigned radix_select_kth(const float* row, int V, float inv_temp, int k,
 // Every thread of the block calls it and gets the same key.  mhist: 256 64-bit words of LDS, sel_prefix / sel_rem: one word each.
 FK_DEV unsigned mass_select_tau(const float* row, int V, float inv_temp, unsigned kth, float mx, float top_p, unsigned long long* mhist, unsigned* sel_prefix,
                                 unsigned long long* sel_rem) {
-  const int tid = threadIdx.x;
-  if (tid == 0) { *sel_prefix = 0u; *sel_rem = 0ull; }
-  for (int pass = 0; pass < 4; ++pass) {
-    const int shift = 24 - 8 * pass;
-    if (tid < 256) mhist[tid] = 0ull;
-    __syncthreads();
-    const unsigned prefix = *sel_prefix, mask_hi = pass == 0 ? 0u : (0xFFFFFFFFu << (shift + 8));
-    for (int i = tid; i < V; i += SAMPLE_THREADS) {
-      const float x = row[i] * inv_temp;
-      const unsigned key = f32_sortable(x);
-      if (key >= kth && (key & mask_hi) == prefix) {
-        const float e = __expf(x - mx);                   // <= 1: mx is the maximum of the kept values; NaN and 0 add nothing
-        const unsigned long long m = e > 0.0f ? (unsigned long long)(e * 4294967296.0f) : 0ull;
-        if (m) atomicAdd(&mhist[(key >> shift) & 255u], m);
-      }
-    }
-    __syncthreads();
-    if (tid < 64) {                                       // lane l owns the bins 255 - 4l .. 252 - 4l, as in radix_select_kth
-      unsigned long long h[4], mine = 0ull;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) { h[q] = mhist[255 - 4 * tid - q]; mine += h[q]; }
-      unsigned long long incl = mine;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const unsigned long long up = __shfl_up(incl, o, 64);
-        if (tid >= o) incl += up;
-      }
-      unsigned long long rem0 = *sel_rem;
-      if (pass == 0) {                                    // the first histogram holds every kept key: its sum is the total
-        const unsigned long long total = __shfl(incl, 63, 64);
-        rem0 = top_p >= 1.0f ? ~0ull : (unsigned long long)((double)top_p * (double)total) + 1ull;
-        if (rem0 > total) rem0 = 0ull;                    // not reached: no lane answers and *sel_rem stays 0
-      }
-      const unsigned long long before = incl - mine;      // mass in the bins above this lane's
-      if (before < rem0 && rem0 <= incl) {                // one lane: the bins above hold less than the target, with its own they reach it
-        unsigned long long rem = rem0 - before;
-        int q = 0;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-          if (q == c && h[c] < rem) { rem -= h[c]; q = c + 1; }
-        }
-        *sel_prefix = prefix | ((unsigned)(255 - 4 * tid - q) << shift);
-        *sel_rem = rem;                                   // >= 1, and the chosen bin holds at least as much: the next pass reaches it too
-      }
-    }
-    __syncthreads();
-    if (pass == 0 && *sel_rem == 0ull) return 0u;         // block-uniform
-  }
-  return *sel_prefix;
+  return radix_select<unsigned long long, true>(
+      row, V, inv_temp, 0ull, mhist, sel_prefix, sel_rem,
+      [&](float x, unsigned key) {
+        if (key < kth) return 0ull;
+        const float e = __expf(x - mx);                     // <= 1: mx is the maximum of the kept values; NaN and 0 add nothing
+        return e > 0.0f ? (unsigned long long)(e * 4294967296.0f) : 0ull;
+      },
+      [&](int pass, unsigned long long total) {
+        if (pass != 0) return *sel_rem;
+        // the first histogram holds every kept key: its sum is the total
+        const unsigned long long rem0 = top_p >= 1.0f ? ~0ull : (unsigned long long)((double)top_p * (double)total) + 1ull;
+        return rem0 > total ? 0ull : rem0;                  // not reached: no lane answers, *sel_rem stays 0 and 0 comes back
+      });
 }
 
 // End-of-text state of the EOS variants below (all device pointers; unused and empty in the plain instantiations): fin[r] 0/1 (a finished
@@ -250,18 +277,25 @@ struct EosArgs {
   int32_t* live;
 };
 
-// The end of a launch of gridDim.x blocks that share one step counter: every block adds its unfinished rows to live_acc and takes a
-// ticket; the last one fetches and clears the sum and advances the counters.  Only atomics carry a value between the blocks.
-FK_DEV void eos_ticket_tail(const EosArgs& ea, unsigned n_live, unsigned* ticket, int64_t* step, int64_t my_step, int32_t* pos_inc) {
-  atomicAdd(ea.live_acc, n_live);
-  __threadfence();
-  if (atomicAdd(ticket, 1u) == gridDim.x - 1) {
+// The end of a decode step, called by one thread of every block whose launch shares one step counter (and one position).  TICKET: the
+// launch has gridDim.x blocks, every block takes a ticket behind its own writes and the last one, by when every block has read step[0]
+// (and pos[0]) and has written its rows, clears the ticket and advances the counters; without it the launch is one block, which advances
+// them itself.  EOS: every block first adds its unfinished rows to live_acc, and the last one fetches and clears the sum.  Only atomics
+// carry a value between the blocks.
+template <bool EOS, bool TICKET>
+FK_DEV void step_tail(const EosArgs& ea, unsigned n_live, unsigned* ticket, int64_t* step, int64_t my_step, int32_t* pos_inc) {
+  if constexpr (EOS) atomicAdd(ea.live_acc, n_live);
+  if constexpr (TICKET) {
     __threadfence();
-    ea.live[0] = (int32_t)atomicExch(ea.live_acc, 0u);
+    if (atomicAdd(ticket, 1u) != gridDim.x - 1) return;
+    if constexpr (EOS) {
+      __threadfence();
+      ea.live[0] = (int32_t)atomicExch(ea.live_acc, 0u);
+    }
     ticket[0] = 0u;
-    step[0] = my_step + 1;
-    if (pos_inc) pos_inc[0] += 1;
   }
+  step[0] = my_step + 1;
+  if (pos_inc) pos_inc[0] += 1;
 }
 
 // EOS: a row with fin[b] != 0 draws nothing and emits ea.eos; a row that draws ea.eos becomes done; len[b] counts the tokens of a row up to
@@ -286,7 +320,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_topk_kernel(const float
       if (tid == 0) {
         cur[b] = ea.eos;
         if (out && my_step >= 0 && my_step < out_cols) out[(int64_t)b * out_ld + my_step] = ea.eos;
-        eos_ticket_tail(ea, 0u, ticket, step, my_step, pos_inc);
+        step_tail<true, true>(ea, 0u, ticket, step, my_step, pos_inc);
       }
       return;
     }
@@ -297,11 +331,10 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_topk_kernel(const float
   if (top_k > 0 && top_k < V) kth = radix_select_kth(row, V, inv_temp, top_k, hist, &sel_prefix, &sel_remaining);
   // ---- softmax over the kept logits: maximum, then the sum of exp; per-thread partial sums of CONTIGUOUS index chunks for the draw
   float mx = -INFINITY;
-  for (int i = tid; i < V; i += SAMPLE_THREADS) {
-    const float x = row[i] * inv_temp;
-    if (f32_sortable(x) >= kth) mx = fmaxf(mx, x);
-  }
-  mx = block_reduce(mx, red, [](float a, float c) { return fmaxf(a, c); }, -INFINITY);
+  for_row_keys(row, inv_temp, tid, V, SAMPLE_THREADS, [&](int, float x, unsigned key) {
+    if (key >= kth) mx = fmaxf(mx, x);
+  });
+  mx = block_reduce<true>(mx, red);
   if constexpr (NUCLEUS) {                                // the most likely token always stays, so mx is the nucleus's maximum as well
     __shared__ unsigned long long mhist[256];
     __shared__ unsigned long long sel_rem;
@@ -310,18 +343,11 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_topk_kernel(const float
   }
   const int chunk = (V + SAMPLE_THREADS - 1) / SAMPLE_THREADS, i0 = tid * chunk, i1 = min(V, i0 + chunk);
   float part = 0.0f;
-  for (int i = i0; i < i1; ++i) {
-    const float x = row[i] * inv_temp;
-    if (f32_sortable(x) >= kth) part += __expf(x - mx);
-  }
+  for_row_keys(row, inv_temp, i0, i1, 1, [&](int, float x, unsigned key) {
+    if (key >= kth) part += __expf(x - mx);
+  });
   scan[tid] = part;
-  __syncthreads();
-  for (int o = 1; o < SAMPLE_THREADS; o <<= 1) {          // inclusive scan of the chunk sums (Hillis-Steele)
-    const float add = tid >= o ? scan[tid - o] : 0.0f;
-    __syncthreads();
-    scan[tid] += add;
-    __syncthreads();
-  }
+  block_scan_inclusive(scan);                             // of the chunk sums
   const float total = scan[SAMPLE_THREADS - 1];
   // ---- one uniform in [0, 1) and the first index whose cumulative mass exceeds u * total
   unsigned c[4] = {(unsigned)my_step, (unsigned)((unsigned long long)my_step >> 32), (unsigned)b, 0x5A3Cu};
@@ -334,9 +360,9 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_topk_kernel(const float
     float acc = before;
     int pick = -1;
     for (int i = i0; i < i1; ++i) {
-      const float x = row[i] * inv_temp;
-      if (f32_sortable(x) >= kth) {
-        const float e = __expf(x - mx);
+      const RowKey rk = row_key(row, i, inv_temp);
+      if (rk.key >= kth) {
+        const float e = __expf(rk.x - mx);
         acc += e;
         if (e > 0.0f) pick = i;                           // last kept index WITH MASS seen: the fallback when rounding leaves acc <= target
         if (acc > target) break;
@@ -349,30 +375,26 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_topk_kernel(const float
     int w = winner;
     if (w < 0) {                                          // target >= total by rounding: the last kept index with mass (a -inf entry is kept by the
       for (int i = V - 1; i >= 0; --i) {                  // crop whenever top_k is off, and is never a token to emit)
-        const float x = row[i] * inv_temp;
-        if (f32_sortable(x) >= kth && __expf(x - mx) > 0.0f) { w = i; break; }
+        const RowKey rk = row_key(row, i, inv_temp);
+        if (rk.key >= kth && __expf(rk.x - mx) > 0.0f) { w = i; break; }
       }
     }
     if (w < 0) {                                          // a row without any mass (all -inf, NaN): the last kept index, as ever
       for (int i = V - 1; i >= 0; --i)
-        if (f32_sortable(row[i] * inv_temp) >= kth) { w = i; break; }
+        if (row_key(row, i, inv_temp).key >= kth) { w = i; break; }
     }
     cur[b] = w;
+    unsigned n_live = 0u;
     if constexpr (EOS) {
       if (out && my_step >= 0 && my_step < out_cols) out[(int64_t)b * out_ld + my_step] = w;
       const bool ended = ea.eos >= 0 && w == ea.eos;
       ea.len[b] = (int32_t)((unsigned)ea.len[b] + 1u);
       if (ended) ea.fin[b] = 1;
-      eos_ticket_tail(ea, ended ? 0u : 1u, ticket, step, my_step, pos_inc);
+      n_live = ended ? 0u : 1u;
     } else {
       if (out && my_step < out_cols) out[(int64_t)b * out_ld + my_step] = w;       // a step counter past the buffer is not a write past it
-      __threadfence();
-      if (atomicAdd(ticket, 1u) == gridDim.x - 1) {         // every block has read step[0] and written its token
-        ticket[0] = 0u;
-        step[0] = my_step + 1;
-        if (pos_inc) pos_inc[0] += 1;
-      }
     }
+    step_tail<EOS, true>(ea, n_live, ticket, step, my_step, pos_inc);
   }
 }
 
@@ -412,8 +434,7 @@ __global__ __launch_bounds__(RULES_THREADS) void logit_rules_kernel(float* logit
     } else if (!append) {
       src = dst = nw + (int64_t)r * hist_ld;
     } else {
-      int pr = parent_log[(s - 1) * (int64_t)gridDim.x + r];
-      pr = pr < 0 ? 0 : (pr >= W ? W - 1 : pr);           // a corrupt log reads a wrong row of its own sentence, never outside the buffer
+      const int pr = clamp_index(parent_log[(s - 1) * (int64_t)gridDim.x + r], W);      // a corrupt log reads a wrong row of its own sentence
       src = od + (int64_t)((r / W) * W + pr) * hist_ld;
       dst = nw + (int64_t)r * hist_ld;
     }
@@ -481,7 +502,7 @@ __global__ __launch_bounds__(256) void attn_decode_beam_kernel(const T* q, int64
   constexpr int VN = VecIO<T>::N, LPK = D / VN, GROUPS = 256 / LPK;
   typedef T vec_t __attribute__((ext_vector_type(VN)));
   __shared__ float red[4][D + 2];
-  const int h = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, wave = tid >> 6;
+  const int h = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
   const int sub = tid % LPK, grp = tid / LPK;
   int p = pos[0];
   int base = 0;                                           // first slot of this row's sentence
@@ -503,8 +524,7 @@ __global__ __launch_bounds__(256) void attn_decode_beam_kernel(const T* q, int64
   for (int j = grp; j < nk; j += GROUPS) {
     int slot = b - base;                                  // the newest row is the beam's own (fk_kv_append has just written it, or this launch does)
     if (j < p) {
-      slot = arow[j];
-      slot = slot < 0 ? 0 : (slot >= W ? W - 1 : slot);   // a corrupt table reads a wrong row, never outside the cache
+      slot = clamp_index(arow[j], W);                     // a corrupt table reads a wrong row, never outside the cache
     }
     T* kr = kv + (int64_t)(base + slot) * kv_bs + (int64_t)j * kv_rs + h * D + sub * VN;
     vec_t kvec, vvec;
@@ -529,38 +549,17 @@ __global__ __launch_bounds__(256) void attn_decode_beam_kernel(const T* q, int64
     for (int i = 0; i < VN; ++i) o[i] = o[i] * a + pj * to_f32<T>(vvec[i]);
     m = mn;
   }
-  // wave merge over the key groups (lanes that hold the same slice of D)
-  float wm = m;
-#pragma unroll
-  for (int off = 32; off >= LPK; off >>= 1) wm = fmaxf(wm, __shfl_xor(wm, off, 64));
-  const float w = (m == -INFINITY) ? 0.0f : __expf(m - wm);
-  l *= w;
-#pragma unroll
-  for (int off = 32; off >= LPK; off >>= 1) l += __shfl_xor(l, off, 64);
-#pragma unroll
-  for (int i = 0; i < VN; ++i) {
-    float v = o[i] * w;
-#pragma unroll
-    for (int off = 32; off >= LPK; off >>= 1) v += __shfl_xor(v, off, 64);
-    o[i] = v;
-  }
-  if ((tid & 63) < LPK) {
-    if (sub == 0) { red[wave][D] = wm; red[wave][D + 1] = l; }
-#pragma unroll
-    for (int i = 0; i < VN; ++i) red[wave][sub * VN + i] = o[i];
-  }
-  __syncthreads();
-  if (tid < D) {
-    const float M4 = fmaxf(fmaxf(red[0][D], red[1][D]), fmaxf(red[2][D], red[3][D]));
-    float L = 0.0f, acc = 0.0f;
-#pragma unroll
-    for (int wv = 0; wv < 4; ++wv) {
-      const float ww = (red[wv][D] == -INFINITY) ? 0.0f : __expf(red[wv][D] - M4);
-      L += red[wv][D + 1] * ww;
-      acc += red[wv][tid] * ww;
-    }
-    out[(int64_t)b * o_bs + h * D + tid] = from_f32<T>(acc / L);
-  }
+  // the key groups of a wave are the lanes that hold the same slice of D
+  softmax_merge<T, D, VN, LPK>(m, l, o, sub, red, out + (int64_t)b * o_bs + h * D);
+}
+
+// Rank of the entry (v, id) among the n entries (val[c], ids ? ids[c] : c) ordered by value descending, then id ascending: the count of
+// the entries with valid(c) that come before it.  Ranks of distinct entries are distinct, whatever order the entries were stored in.
+struct AllValid { FK_DEV bool operator()(int) const { return true; } };
+template <typename T, typename Valid = AllValid> FK_DEV int rank_desc(const T* val, const int* ids, int n, T v, int id, Valid valid = Valid()) {
+  int rank = 0;
+  for (int c = 0; c < n; ++c) rank += (valid(c) && (val[c] > v || (val[c] == v && (ids ? ids[c] : c) < id))) ? 1 : 0;
+  return rank;
 }
 
 // One block per row: lp = x - logsumexp(x), x = logits * (1 / temperature); the k largest lp, descending, equal values by ascending id.
@@ -586,35 +585,27 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void beam_topk_kernel(const float* 
   if (tid == 0) n_above = 0u;
   // ---- log-sum-exp over the whole row
   float mx = -INFINITY;
-  for (int i = tid; i < V; i += SAMPLE_THREADS) mx = fmaxf(mx, row[i] * inv_temp);
-  mx = block_reduce(mx, red, [](float a, float c) { return fmaxf(a, c); }, -INFINITY);
+  for_row_keys(row, inv_temp, tid, V, SAMPLE_THREADS, [&](int, float x, unsigned) { mx = fmaxf(mx, x); });
+  mx = block_reduce<true>(mx, red);
   float part = 0.0f;
   const bool take_all_eq = n_eq == n_eq_take;              // no tie straddles rank k: everything >= the k-th value is in
-  for (int i = tid; i < V; i += SAMPLE_THREADS) {
-    const float x = row[i] * inv_temp;
+  for_row_keys(row, inv_temp, tid, V, SAMPLE_THREADS, [&](int i, float x, unsigned key) {
     part += expf(x - mx);
-    const unsigned key = f32_sortable(x);
     if (key > kth || (take_all_eq && key == kth)) {
       const unsigned at = atomicAdd(&n_above, 1u);
       if (at < (unsigned)BEAM_MAX_K) { ckey[at] = key; cid[at] = i; }
     }
-  }
-  const float lse = mx + logf(block_reduce(part, red, [](float a, float c) { return a + c; }, 0.0f));
+  });
+  const float lse = mx + logf(block_reduce<false>(part, red));
   if (!take_all_eq) {                                      // block-uniform.  The first n_eq_take ids among the ties: contiguous chunks + a scan of their counts
     const int chunk = (V + SAMPLE_THREADS - 1) / SAMPLE_THREADS, i0 = (int)min((int64_t)V, (int64_t)tid * chunk), i1 = (int)min((int64_t)V, (int64_t)i0 + chunk);
     unsigned mine = 0u;
-    for (int i = i0; i < i1; ++i) mine += f32_sortable(row[i] * inv_temp) == kth ? 1u : 0u;
+    for_row_keys(row, inv_temp, i0, i1, 1, [&](int, float, unsigned key) { mine += key == kth ? 1u : 0u; });
     scan[tid] = mine;
-    __syncthreads();
-    for (int o = 1; o < SAMPLE_THREADS; o <<= 1) {
-      const unsigned add = tid >= o ? scan[tid - o] : 0u;
-      __syncthreads();
-      scan[tid] += add;
-      __syncthreads();
-    }
+    block_scan_inclusive(scan);
     unsigned rank = scan[tid] - mine;                      // ties in front of this chunk
     for (int i = i0; i < i1 && rank < n_eq_take; ++i) {
-      if (f32_sortable(row[i] * inv_temp) == kth) {
+      if (row_key(row, i, inv_temp).key == kth) {
         const unsigned at = (unsigned)n_gt + rank;
         if (at < (unsigned)BEAM_MAX_K) { ckey[at] = kth; cid[at] = i; }
         ++rank;
@@ -623,11 +614,9 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void beam_topk_kernel(const float* 
   }
   __syncthreads();
   if (tid < k) {
-    const unsigned mk = ckey[tid];
     const int mi = cid[tid];
-    int rank = 0;
-    for (int c = 0; c < k; ++c) rank += (ckey[c] > mk || (ckey[c] == mk && cid[c] < mi)) ? 1 : 0;
-    top_lp[(int64_t)r * k + rank] = row[mi] * inv_temp - lse;
+    const int rank = rank_desc(ckey, cid, k, ckey[tid], mi);
+    top_lp[(int64_t)r * k + rank] = row_key(row, mi, inv_temp).x - lse;
     top_id[(int64_t)r * k + rank] = mi;
   }
 }
@@ -690,9 +679,7 @@ __global__ __launch_bounds__(BEAM_SELECT_THREADS) void beam_select_kernel(const 
   __syncthreads();
   for (int e = tid; e < W * k; e += BEAM_SELECT_THREADS) {            // draw rank of entry j inside beam i (ties: the lower j first)
     const int i = e / k, j = e - i * k;
-    const float g = gum[e];
-    int rank = 0;
-    for (int c = 0; c < k; ++c) rank += (gum[i * k + c] > g || (gum[i * k + c] == g && c < j)) ? 1 : 0;
+    const int rank = rank_desc(gum + i * k, nullptr, k, gum[e], j);
     if (rank < W) pick[i * W + rank] = j;
   }
   __syncthreads();
@@ -704,27 +691,20 @@ __global__ __launch_bounds__(BEAM_SELECT_THREADS) void beam_select_kernel(const 
       const bool done = sfin[i] != 0;
       const float raw = done ? sc[i] : sc[i] + top_lp[i * row_stride + pick[tid]];
       const int L = done ? slen[i] : (int)((unsigned)slen[i] + 1u);
-      const int at = L < 0 ? 0 : (L > ea.n_lenpow - 1 ? ea.n_lenpow - 1 : L);      // a length past the table ranks with its last entry
       cand[tid] = raw;
-      cnorm[tid] = raw * ea.inv_lenpow[at];
+      cnorm[tid] = raw * ea.inv_lenpow[clamp_index(L, ea.n_lenpow)];              // a length past the table ranks with its last entry
     }
     __syncthreads();
-    if (tid < nc && !(sfin[tid / W] != 0 && tid % W > 0)) {  // a finished beam has its candidate 0 only; at least W candidates are valid
-      const float s = cnorm[tid];
-      int rank = 0;
-      for (int c = 0; c < nc; ++c) {
-        const bool valid = !(sfin[c / W] != 0 && c % W > 0);
-        rank += (valid && (cnorm[c] > s || (cnorm[c] == s && c < tid))) ? 1 : 0;
-      }
+    const auto valid = [&](int c) { return !(sfin[c / W] != 0 && c % W > 0); };   // a finished beam has its candidate 0 only; at least W candidates are valid
+    if (tid < nc && valid(tid)) {
+      const int rank = rank_desc(cnorm, nullptr, nc, cnorm[tid], tid, valid);
       if (rank < W) surv[rank] = tid;
     }
   } else {
     if (tid < nc) cand[tid] = sc[tid / W] + top_lp[(tid / W) * row_stride + pick[tid]];
     __syncthreads();
     if (tid < nc) {
-      const float s = cand[tid];
-      int rank = 0;
-      for (int c = 0; c < nc; ++c) rank += (cand[c] > s || (cand[c] == s && c < tid)) ? 1 : 0;
+      const int rank = rank_desc(cand, nullptr, nc, cand[tid], tid);
       if (rank < W) surv[rank] = tid;
     }
   }
@@ -762,25 +742,13 @@ __global__ __launch_bounds__(BEAM_SELECT_THREADS) void beam_select_kernel(const 
       anc[b * anc_ld + j] = v;
     }
   }
-  if constexpr (GROUPED) {
-    __syncthreads();                                       // the whole block has written its rows of the table
-    if (tid == 0) {
-      if constexpr (EOS) {
-        unsigned n_live = 0u;
-        for (int b = 0; b < W; ++b) n_live += (unsigned)alive[b];
-        eos_ticket_tail(ea, n_live, ticket, step, my_step, pos_inc);
-      } else {
-        __threadfence();
-        if (atomicAdd(ticket, 1u) == gridDim.x - 1) {        // every block has read step[0] and pos[0] and has written its sentence
-          ticket[0] = 0u;
-          step[0] = my_step + 1;
-          if (pos_inc) pos_inc[0] += 1;
-        }
-      }
+  if constexpr (GROUPED) __syncthreads();                  // the whole block has written its rows of the table
+  if (tid == 0) {                                          // every read of the counters is behind a barrier above
+    unsigned n_live = 0u;
+    if constexpr (EOS) {
+      for (int b = 0; b < W; ++b) n_live += (unsigned)alive[b];
     }
-  } else if (tid == 0) {                                   // every read of the counters is behind a barrier above
-    step[0] = my_step + 1;
-    if (pos_inc) pos_inc[0] += 1;
+    step_tail<EOS, GROUPED>(ea, n_live, ticket, step, my_step, pos_inc);      // one block and no ticket unless GROUPED
   }
 }
 
@@ -804,20 +772,17 @@ __global__ __launch_bounds__(BACKTRACK_THREADS) void beam_backtrack_kernel(const
   if (b < W) {
     raw = scores[g * W + b];
     L = len[g * W + b];
-    const int at = L < 0 ? 0 : (L > n_lenpow - 1 ? n_lenpow - 1 : L);
-    norm[b] = raw * inv_lenpow[at];
+    norm[b] = raw * inv_lenpow[clamp_index(L, n_lenpow)];
   }
   __syncthreads();
   if (b >= W) return;
-  int rank = 0;
-  for (int c = 0; c < W; ++c) rank += (norm[c] > norm[b] || (norm[c] == norm[b] && c < b)) ? 1 : 0;
+  const int rank = rank_desc(norm, nullptr, W, norm[b], b);
   int64_t* row = out_ids + ((int64_t)g * W + rank) * out_ld;
   int x = b;
   for (int64_t t = n - 1; t >= 0; --t) {
     const int64_t at = t * log_ld + (int64_t)g * W + x;
     if (t0 + t < out_cols) row[t0 + t] = tok_log[at];
-    const int pr = parent_log[at];
-    x = pr < 0 ? 0 : (pr >= W ? W - 1 : pr);
+    x = clamp_index(parent_log[at], W);
   }
   for (int64_t c = t0 + n; c < out_cols; ++c) row[c] = pad;
   out_scores[g * W + rank] = raw;
@@ -828,6 +793,32 @@ __global__ __launch_bounds__(BACKTRACK_THREADS) void beam_backtrack_kernel(const
 
 // What the entry points of a family share, written once: the argument checks, the launch and its check.  `fn` is the entry point's name, `ptrs`
 // whether all the pointers it needs are there; each returns FK_OK or the fk_set_error code.
+
+// Host head_dim dispatch: the statement(s) are compiled once per supported head_dim with `DD` a constant and the arm of `D` (checked by the
+// caller: 16, 32, 64 or 128) runs.  Nests with FK_BY_DTYPE.
+#define FK_BY_HEAD_DIM(D, DD, ...)                                \
+  do {                                                            \
+    if ((D) == 16) { constexpr int DD = 16; __VA_ARGS__; }        \
+    else if ((D) == 32) { constexpr int DD = 32; __VA_ARGS__; }   \
+    else if ((D) == 64) { constexpr int DD = 64; __VA_ARGS__; }   \
+    else { constexpr int DD = 128; __VA_ARGS__; }                 \
+  } while (0)
+
+// `rows` rows of V logits, ld apart: one block per row (grid x), 32-bit indices inside a row
+static int check_logit_rows(const char* fn, int64_t rows, int64_t V, int64_t ld) {
+  FK_CHECK_ARG(rows > 0 && rows < 65536 && V > 0 && V < (1LL << 31) && ld >= V, "%s: bad arguments (rows=%lld V=%lld ld=%lld)", fn, (long long)rows, (long long)V,
+               (long long)ld);
+  return FK_OK;
+}
+
+// The end-of-text state of a launch from the entry point's arguments: an id of 2^31 or more is refused, a negative one means "none" (-1)
+static int make_eos_args(const char* fn, int64_t eos, int32_t* fin, int32_t* len, const float* inv_lenpow, int64_t n_lenpow, uint32_t* live_acc, int32_t* live,
+                         EosArgs* ea) {
+  FK_CHECK_ARG(eos < (1LL << 31), "%s: need eos < 2^31 (eos=%lld)", fn, (long long)eos);
+  *ea = EosArgs{eos < 0 ? -1 : (int)eos, fin, len, inv_lenpow, (int)n_lenpow, live_acc, live};
+  return FK_OK;
+}
+
 template <bool EOS, bool NUCLEUS>
 static int sample_topk(const char* fn, bool ptrs, const float* logits, int64_t ld, int64_t B, int64_t V, float temperature, int64_t top_k, float top_p,
                        const uint64_t* seed, int64_t* step, int32_t* pos_inc, int64_t* cur, int64_t* out, int64_t out_ld, int64_t out_cols, uint32_t* ticket,
@@ -835,8 +826,8 @@ static int sample_topk(const char* fn, bool ptrs, const float* logits, int64_t l
   FK_CHECK_ARG(out == nullptr || (out_cols > 0 && out_cols <= out_ld), "%s: out given without its width (out_cols=%lld, out_ld=%lld)", fn, (long long)out_cols,
                (long long)out_ld);
   FK_CHECK_ARG(ptrs, "%s: null pointer", fn);
-  FK_CHECK_ARG(B > 0 && B < 65536 && V > 0 && V < (1LL << 31) && ld >= V && temperature > 0.0f, "%s: bad arguments (B=%lld V=%lld temperature=%g)", fn,
-               (long long)B, (long long)V, (double)temperature);
+  if (const int rc = check_logit_rows(fn, B, V, ld); rc != FK_OK) return rc;
+  FK_CHECK_ARG(temperature > 0.0f, "%s: need temperature > 0 (temperature=%g)", fn, (double)temperature);      // refuses NaN as well
   FK_CHECK_ARG(!NUCLEUS || (top_p > 0.0f && top_p <= 1.0f), "%s: need 0 < top_p <= 1 (top_p=%g)", fn, (double)top_p);      // refuses NaN as well
   hipLaunchKernelGGL((sample_topk_kernel<EOS, NUCLEUS>), dim3((unsigned)B), dim3(SAMPLE_THREADS), 0, (hipStream_t)stream, logits, ld, (int)V, 1.0f / temperature,
                      (int)(top_k > 0 && top_k < V ? top_k : 0), top_p, (const unsigned long long*)seed, step, pos_inc, cur, out, out_ld, out_cols, ticket, ea);
@@ -860,10 +851,8 @@ static int launch_attn_decode_beam(const char* fn, const void* q, int64_t q_bs, 
                                    void* stream) {
   hipStream_t s = (hipStream_t)stream;
   dim3 grid((unsigned)H, (unsigned)rows), block(256);
-#define FK_ADB(TT, DD) hipLaunchKernelGGL((attn_decode_beam_kernel<TT, DD, GROUPED>), grid, block, 0, s, (const TT*)q, q_bs, (TT*)kv, kv_bs, kv_rs, (int)tmax, anc, anc_ld, (TT*)out, o_bs, pos, (int)W, (int)H, scale, append)
-  if (dtype == FK_BF16) { if (D == 16) FK_ADB(bf16_t, 16); else if (D == 32) FK_ADB(bf16_t, 32); else if (D == 64) FK_ADB(bf16_t, 64); else FK_ADB(bf16_t, 128); }
-  else { if (D == 16) FK_ADB(float, 16); else if (D == 32) FK_ADB(float, 32); else if (D == 64) FK_ADB(float, 64); else FK_ADB(float, 128); }
-#undef FK_ADB
+  FK_BY_DTYPE(dtype, T, FK_BY_HEAD_DIM(D, DD, hipLaunchKernelGGL((attn_decode_beam_kernel<T, DD, GROUPED>), grid, block, 0, s, (const T*)q, q_bs, (T*)kv, kv_bs, kv_rs,
+                                                          (int)tmax, anc, anc_ld, (T*)out, o_bs, pos, (int)W, (int)H, scale, append)));
   FK_CHECK_LAUNCH(fn);
   return FK_OK;
 }
@@ -912,10 +901,8 @@ int fk_attn_decode(const void* q, int64_t q_bs, const void* kv, int64_t kv_bs, i
   FK_CHECK_ARG(D == 16 || D == 32 || D == 64 || D == 128, "fk_attn_decode: head_dim %lld not in {16, 32, 64, 128}", (long long)D);
   hipStream_t s = (hipStream_t)stream;
   dim3 grid((unsigned)H, (unsigned)B), block(256);
-#define FK_AD(TT, DD) hipLaunchKernelGGL((attn_decode_kernel<TT, DD>), grid, block, 0, s, (const TT*)q, q_bs, (const TT*)kv, kv_bs, kv_rs, (TT*)out, o_bs, pos, (int)H, scale)
-  if (dtype == FK_BF16) { if (D == 16) FK_AD(bf16_t, 16); else if (D == 32) FK_AD(bf16_t, 32); else if (D == 64) FK_AD(bf16_t, 64); else FK_AD(bf16_t, 128); }
-  else { if (D == 16) FK_AD(float, 16); else if (D == 32) FK_AD(float, 32); else if (D == 64) FK_AD(float, 64); else FK_AD(float, 128); }
-#undef FK_AD
+  FK_BY_DTYPE(dtype, T, FK_BY_HEAD_DIM(D, DD, hipLaunchKernelGGL((attn_decode_kernel<T, DD>), grid, block, 0, s, (const T*)q, q_bs, (const T*)kv, kv_bs, kv_rs, (T*)out,
+                                                          o_bs, pos, (int)H, scale)));
   FK_CHECK_LAUNCH("fk_attn_decode");
   return FK_OK;
 }
@@ -935,8 +922,8 @@ int fk_attn_decode_beam(const void* q, int64_t q_bs, const void* kv, int64_t kv_
 
 int fk_beam_topk(const float* logits, int64_t ld, int64_t R, int64_t V, float temperature, int64_t k, float* top_lp, int64_t* top_id, void* stream) {
   FK_CHECK_ARG(logits && top_lp && top_id, "fk_beam_topk: null pointer");
-  FK_CHECK_ARG(R > 0 && R < 65536 && V > 0 && V < (1LL << 31) && ld >= V && temperature > 0.0f,
-               "fk_beam_topk: bad arguments (R=%lld V=%lld ld=%lld temperature=%g)", (long long)R, (long long)V, (long long)ld, (double)temperature);
+  if (const int rc = check_logit_rows("fk_beam_topk", R, V, ld); rc != FK_OK) return rc;
+  FK_CHECK_ARG(temperature > 0.0f, "fk_beam_topk: need temperature > 0 (temperature=%g)", (double)temperature);      // refuses NaN as well
   FK_CHECK_ARG(k >= 1 && k <= BEAM_MAX_K && k <= V, "fk_beam_topk: k=%lld outside 1 .. min(%d, V=%lld)", (long long)k, BEAM_MAX_K, (long long)V);
   hipLaunchKernelGGL(beam_topk_kernel, dim3((unsigned)R), dim3(SAMPLE_THREADS), 0, (hipStream_t)stream, logits, ld, (int)V, 1.0f / temperature, (int)k,
                      top_lp, top_id);
@@ -975,9 +962,9 @@ int fk_beam_select_eos(const float* top_lp, const int64_t* top_id, int64_t row_s
                        float* scores, const uint64_t* seed, int64_t* step, const int32_t* pos, int32_t* pos_inc, int64_t* cur, int32_t* parent_log,
                        int64_t* tok_log, int64_t log_rows, int32_t* anc, int64_t anc_ld, uint32_t* ticket, int64_t eos, int32_t* fin, int32_t* len,
                        const float* inv_lenpow, int64_t n_lenpow, uint32_t* live_acc, int32_t* live, void* stream) {
-  FK_CHECK_ARG(n_lenpow >= 1 && n_lenpow < (1LL << 31) && eos < (1LL << 31), "fk_beam_select_eos: need 1 <= n_lenpow < 2^31 and eos < 2^31 (n_lenpow=%lld eos=%lld)",
-               (long long)n_lenpow, (long long)eos);
-  const EosArgs ea{eos < 0 ? -1 : (int)eos, fin, len, inv_lenpow, (int)n_lenpow, live_acc, live};
+  FK_CHECK_ARG(n_lenpow >= 1 && n_lenpow < (1LL << 31), "fk_beam_select_eos: need 1 <= n_lenpow < 2^31 (n_lenpow=%lld)", (long long)n_lenpow);
+  EosArgs ea;
+  if (const int rc = make_eos_args("fk_beam_select_eos", eos, fin, len, inv_lenpow, n_lenpow, live_acc, live, &ea); rc != FK_OK) return rc;
   return beam_select<true, true>("fk_beam_select_eos", top_lp && top_id && scores && seed && step && pos && cur && anc && ticket && fin && len && inv_lenpow && live_acc && live,
                                  top_lp, top_id, row_stride, group_stride, S, W, k, scores, seed, step, pos, pos_inc, cur, parent_log, tok_log, log_rows, anc, anc_ld,
                                  ticket, ea, stream);
@@ -1003,8 +990,8 @@ int fk_beam_backtrack(const int32_t* parent_log, const int64_t* tok_log, int64_t
 int fk_sample_topk_eos(const float* logits, int64_t ld, int64_t B, int64_t V, float temperature, int64_t top_k, const uint64_t* seed, int64_t* step,
                        int32_t* pos_inc, int64_t* cur, int64_t* out, int64_t out_ld, int64_t out_cols, uint32_t* ticket, int64_t eos, int32_t* done,
                        int32_t* len, uint32_t* live_acc, int32_t* live, void* stream) {
-  FK_CHECK_ARG(eos < (1LL << 31), "fk_sample_topk_eos: need eos < 2^31 (eos=%lld)", (long long)eos);
-  const EosArgs ea{eos < 0 ? -1 : (int)eos, done, len, nullptr, 0, live_acc, live};
+  EosArgs ea;
+  if (const int rc = make_eos_args("fk_sample_topk_eos", eos, done, len, nullptr, 0, live_acc, live, &ea); rc != FK_OK) return rc;
   return sample_topk<true, false>("fk_sample_topk_eos", logits && seed && step && cur && ticket && done && len && live_acc && live, logits, ld, B, V, temperature, top_k,
                                   1.0f, seed, step, pos_inc, cur, out, out_ld, out_cols, ticket, ea, stream);
 }
@@ -1019,8 +1006,8 @@ int fk_sample_topp(const float* logits, int64_t ld, int64_t B, int64_t V, float 
                                     EosArgs{}, stream);
   }
   FK_CHECK_ARG(len && live_acc && live, "fk_sample_topp: done given without len / live_acc / live (all four or none)");
-  FK_CHECK_ARG(eos < (1LL << 31), "fk_sample_topp: need eos < 2^31 (eos=%lld)", (long long)eos);
-  const EosArgs ea{eos < 0 ? -1 : (int)eos, done, len, nullptr, 0, live_acc, live};
+  EosArgs ea;
+  if (const int rc = make_eos_args("fk_sample_topp", eos, done, len, nullptr, 0, live_acc, live, &ea); rc != FK_OK) return rc;
   return sample_topk<true, true>("fk_sample_topp", ptrs, logits, ld, B, V, temperature, top_k, top_p, seed, step, pos_inc, cur, out, out_ld, out_cols, ticket, ea, stream);
 }
 
@@ -1029,8 +1016,7 @@ int fk_logit_rules(float* logits, int64_t ld, int64_t R, int64_t V, float penalt
                    int64_t log_rows, int64_t W, int broadcast, void* stream) {
   FK_CHECK_ARG(logits && step && cur && hist, "fk_logit_rules: null pointer");
   FK_CHECK_ARG((hist2 == nullptr) == (parent_log == nullptr), "fk_logit_rules: hist2 and parent_log select the beam mode together (both or none)");
-  FK_CHECK_ARG(R > 0 && R < 65536 && V > 0 && V < (1LL << 31) && ld >= V, "fk_logit_rules: bad arguments (R=%lld V=%lld ld=%lld)", (long long)R, (long long)V,
-               (long long)ld);
+  if (const int rc = check_logit_rows("fk_logit_rules", R, V, ld); rc != FK_OK) return rc;
   FK_CHECK_ARG(penalty > 0.0f && penalty <= 3.402823466e38f, "fk_logit_rules: need a finite penalty > 0 (penalty=%g)", (double)penalty);      // refuses NaN as well
   FK_CHECK_ARG(ngram >= 0 && ngram < (1LL << 31) && min_new >= 0 && min_new < (1LL << 31) && eos < (1LL << 31),
                "fk_logit_rules: need 0 <= ngram, min_new < 2^31 and eos < 2^31 (ngram=%lld min_new=%lld eos=%lld)", (long long)ngram, (long long)min_new, (long long)eos);

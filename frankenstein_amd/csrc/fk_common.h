@@ -25,7 +25,6 @@ typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));   // v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32 operands
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
@@ -157,14 +156,15 @@ FK_DEV float fk_gelu(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118
 // ------------------------------------------------------------------------------------------------
 // wave helpers
 // ------------------------------------------------------------------------------------------------
-FK_DEV float wave_sum(float v) {
+// over the whole wave, or with STOP (a power of two) over the 64 / STOP lanes whose numbers agree modulo STOP: butterfly offsets 32 .. STOP
+template <int STOP = 1> FK_DEV float wave_sum(float v) {
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  for (int o = 32; o >= STOP; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
-FK_DEV float wave_max(float v) {
+template <int STOP = 1> FK_DEV float wave_max(float v) {
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  for (int o = 32; o >= STOP; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
 }
 

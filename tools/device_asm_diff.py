@@ -16,7 +16,7 @@ from pathlib import Path
 
 from kernel_resources import ROOT, compile_isa, parse_remarks
 
-FIGURES = ("VGPRs", "TotalSGPRs", "ScratchSize", "VGPRs Spill", "SGPRs Spill", "Occupancy")
+FIGURES = ("VGPRs", "TotalSGPRs", "ScratchSize", "LDS Size", "VGPRs Spill", "SGPRs Spill", "Occupancy")
 
 
 def functions(asm: str) -> dict:
