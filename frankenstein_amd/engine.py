@@ -73,13 +73,35 @@ def _arena_grad(p: Tensor):
     return g if (g is not None and getattr(p, "_fk_arena", False) and g.is_contiguous()) else None
 
 
+def wgrad_path(in_arena: Sequence[bool], swiglu_interleaved: bool = False, slab_ok: bool = False, adjacent: bool = False) -> str:
+    """Where wgrad puts the gradients of one row-concatenated weight group (host-side, no GPU).  in_arena: per parameter, whether its
+    .grad is a contiguous view of the gradient arena; slab_ok: K.gemm_tn_swiglu_ok of the product; adjacent: the arena views follow
+    each other in memory in the order of the group.
+      "tensors"     one parameter is outside the arena: gemm_tn into a temporary, split (or de-interleaved) and handed to autograd
+      "swiglu_slab" gemm_tn_swiglu_: the slab reduction adds the de-interleaved rows to both arena views
+      "swiglu_add"  gemm_tn into a temporary, two add2d_ into the arena views
+      "adjacent"    gemm_tn accumulates into the arena views as one [sum N, K] matrix
+      "split_add"   gemm_tn into a temporary, one add2d_ per parameter"""
+    if not all(in_arena):
+        return "tensors"
+    if swiglu_interleaved:
+        return "swiglu_slab" if slab_ok else "swiglu_add"
+    return "adjacent" if adjacent else "split_add"
+
+
+def norm_bwd_path(gamma_in_arena: bool, has_beta: bool, beta_in_arena: bool) -> str:
+    """"arena": norm_bwd accumulates dgamma (and dbeta) straight into the arena views; "tensors": it returns them (host-side, no GPU)."""
+    return "arena" if gamma_in_arena and (not has_beta or beta_in_arena) else "tensors"
+
+
 def wgrad(a: Tensor, b: Tensor, params: Sequence[Tensor], swiglu_interleaved: bool = False):
     """Gradients of the row-concatenated weights `params` = a^T b ([sum N, K], fp32).  Returns a list aligned with params:
     tensors (caller hands them to autograd) or Nones when the result was accumulated directly into the arena (on the
     weight-gradient stream when one is enabled, else on the current stream)."""
     side = _WGRAD_STREAM
     grads = [_arena_grad(p) for p in params]
-    if any(g is None for g in grads):
+    in_arena = [g is not None for g in grads]
+    if wgrad_path(in_arena, swiglu_interleaved) == "tensors":
         dw = K.gemm_tn(a, b)
         if swiglu_interleaved:
             return list(_deinterleave_rows(dw, params[0].shape[0]))
@@ -91,15 +113,16 @@ def wgrad(a: Tensor, b: Tensor, params: Sequence[Tensor], swiglu_interleaved: bo
     with torch.cuda.stream(side if side is not None else torch.cuda.current_stream()):
         Kd = b.shape[1]
         adjacent = all(grads[i + 1].data_ptr() == grads[i].data_ptr() + grads[i].numel() * 4 for i in range(len(grads) - 1))
-        if swiglu_interleaved and K.gemm_tn_swiglu_ok(a, b, grads[0], grads[1]):
+        path = wgrad_path(in_arena, swiglu_interleaved, swiglu_interleaved and K.gemm_tn_swiglu_ok(a, b, grads[0], grads[1]), adjacent)
+        if path == "swiglu_slab":
             K.gemm_tn_swiglu_(a, b, grads[0], grads[1])            # the slab reduction adds the de-interleaved rows to both gradients
-        elif swiglu_interleaved:
+        elif path == "swiglu_add":
             dw = K.gemm_tn(a, b)                                   # [2H, K] interleaved rows
             H = params[0].shape[0]
             v = dw.view(H // 4, 8 * Kd)
             K.add2d_(grads[0].view(H // 4, 4 * Kd), v[:, :4 * Kd])
             K.add2d_(grads[1].view(H // 4, 4 * Kd), v[:, 4 * Kd:])
-        elif adjacent:
+        elif path == "adjacent":
             n = sum(p.shape[0] for p in params)
             out = torch.as_strided(grads[0], (n, Kd), (Kd, 1))
             K.gemm_tn(a, b, out=out, accumulate=True)
@@ -118,7 +141,7 @@ def norm_bwd(dh: Tensor, x2: Tensor, ln_w: Tensor, ln_b: Optional[Tensor], mean:
     (returns Nones for them: no temporary, no autograd add); plain tensors otherwise."""
     gw = _arena_grad(ln_w)
     gb = _arena_grad(ln_b) if ln_b is not None else None
-    if gw is not None and (ln_b is None or gb is not None):
+    if norm_bwd_path(gw is not None, ln_b is not None, gb is not None) == "arena":
         dx, _, _ = K.norm_bwd(dh, x2, ln_w.detach(), mean, rstd, dres=dres, kind=kind, want_beta=ln_b is not None,
                               dgamma=gw.view(-1), dbeta=None if gb is None else gb.view(-1), accumulate=True)
         return dx, None, None
@@ -357,6 +380,30 @@ def _attn_prescale(D: int) -> bool:
     return _COMPUTE_DTYPE == torch.bfloat16 and D == 64
 
 
+def attn_proj_path(B: int, N: int, H: int, D: int, has_rope: bool, mask_kind: int, has_dropout: bool) -> str:
+    """The QKV projection AttnBranch.forward runs for B x N tokens, H heads of width D, in the current compute dtype (host-side, no GPU):
+      "rope_ps"    gemm_nt_rope, queries rotated with the pre-scaled table (lean attention kernels)
+      "rope"       gemm_nt_rope, one table (fp32 mode, head_dim != 64, dense masks, dropout)
+      "ident_ps"   no RoPE: gemm_nt_rope with the identity pair, queries pre-scaled
+      "plain"      no RoPE: gemm_nt
+      "plain_rope" gemm_nt, then rope_ in place (head widths the fused epilogue does not take)"""
+    HD = H * D
+    ps = _attn_prescale(D) and mask_kind != K.MASK_DENSE and not has_dropout     # dense masks / dropout: the generic kernels
+    if has_rope and D % 8 == 0 and (3 * HD) % 8 == 0:     # RoPE fused into the projection epilogue
+        return "rope_ps" if ps else "rope"
+    if (not has_rope and N >= 64 and (B * N) % 8 == 0 and (3 * HD) % 8 == 0 and ps
+            and os.environ.get("FK_ATTN_NO_IDENT_PRESCALE") is None):
+        return "ident_ps"
+    return "plain_rope" if has_rope else "plain"
+
+
+def attn_bwd_rope_path(has_rope: bool, D: int) -> Optional[str]:
+    """How AttnBranch.backward un-rotates dQ / dK: "fused" into attn_bwd's stores, "kernel" = rope_(conj) afterwards, None without RoPE."""
+    if not has_rope:
+        return None
+    return "fused" if D % 4 == 0 else "kernel"
+
+
 # --------------------------------------------------------------------------------------------- dropout
 # nn.Dropout / SDPA dropout_p of the GPT-2 decoder in training mode (models/gpt2_model.py:40,64,75,85,91,129).  No mask tensor exists:
 # every application is (p, seed words, site) and the kernels regenerate keep / drop from the element index (include/franken_hip.h,
@@ -448,27 +495,22 @@ class AttnBranch(torch.autograd.Function):
             h, mean, rstd = x2, None, None
         HD = H * D
         bq = None if qkv_b is None else shadow([qkv_b])
-        prescale = False
-        if rope is not None and D % 8 == 0 and (3 * HD) % 8 == 0:     # RoPE fused into the projection epilogue
-            prescale = _attn_prescale(D) and mask.kind != K.MASK_DENSE and drop is None     # dense masks / dropout: the generic kernels
-            if prescale:
-                tab, qtab = rope.pair((1.0 / math.sqrt(D)) * 1.4426950408889634)
-                qkv = K.gemm_nt_rope(h, shadow(qkv_w), bq, tab, N, rope.pos_off(N), D, 2 * HD, q_cols=HD, q_table=qtab)
-            else:
-                qkv = K.gemm_nt_rope(h, shadow(qkv_w), bq, rope.table, N, rope.pos_off(N), D, 2 * HD)
-            qkv3 = qkv.view(B, N, 3 * HD)
-        elif (rope is None and N >= 64 and M % 8 == 0 and (3 * HD) % 8 == 0 and _attn_prescale(D) and mask.kind != K.MASK_DENSE and drop is None
-              and os.environ.get("FK_ATTN_NO_IDENT_PRESCALE") is None):
+        path = attn_proj_path(B, N, H, D, rope is not None, mask.kind, drop is not None)
+        prescale = path in ("rope_ps", "ident_ps")
+        if path == "rope_ps":                         # RoPE fused into the projection epilogue, queries pre-scaled
+            tab, qtab = rope.pair((1.0 / math.sqrt(D)) * 1.4426950408889634)
+            qkv = K.gemm_nt_rope(h, shadow(qkv_w), bq, tab, N, rope.pos_off(N), D, 2 * HD, q_cols=HD, q_table=qtab)
+        elif path == "rope":
+            qkv = K.gemm_nt_rope(h, shadow(qkv_w), bq, rope.table, N, rope.pos_off(N), D, 2 * HD)
+        elif path == "ident_ps":
             # no RoPE, but the lean kernels want pre-scaled queries: the same epilogue with an identity "rotation" (identity_pair)
             tab, qtab = identity_pair(D, (1.0 / math.sqrt(D)) * 1.4426950408889634, x.device)
             qkv = K.gemm_nt_rope(h, shadow(qkv_w), bq, tab, 8, 0, D, 2 * HD, q_cols=HD, q_table=qtab)
-            qkv3 = qkv.view(B, N, 3 * HD)
-            prescale = True
         else:
             qkv = K.gemm_nt(h, shadow(qkv_w), bias=bq)
-            qkv3 = qkv.view(B, N, 3 * HD)
-            if rope is not None:
-                K.rope_(qkv3, 2 * H, D, rope.table, rope.pos_off(N))
+        qkv3 = qkv.view(B, N, 3 * HD)
+        if path == "plain_rope":
+            K.rope_(qkv3, 2 * H, D, rope.table, rope.pos_off(N))
         q, k, v = (qkv3[..., i * HD:(i + 1) * HD].unflatten(-1, (H, D)) for i in range(3))
         o, lse = K.attn_fwd(q, k, v, mask, q_prescaled=prescale, dropout=None if drop is None else drop[:3])
         if drop is None:
@@ -506,12 +548,13 @@ class AttnBranch(torch.autograd.Function):
         qkv3, dqkv3 = qkv.view(B, N, 3 * HD), dqkv.view(B, N, 3 * HD)
         q, k, v = (qkv3[..., i * HD:(i + 1) * HD].unflatten(-1, (H, D)) for i in range(3))
         dq, dk, dv = (dqkv3[..., i * HD:(i + 1) * HD].unflatten(-1, (H, D)) for i in range(3))
-        if rope is not None and D % 4 == 0:       # inverse RoPE fused into the dQ / dK stores
+        rpath = attn_bwd_rope_path(rope is not None, D)
+        if rpath == "fused":                      # inverse RoPE fused into the dQ / dK stores
             K.attn_bwd(q, k, v, o, do.view(B, N, H, D), lse, dq, dk, dv, mask, rope_table=rope.table, rope_off=rope.pos_off(N),
                        q_prescaled=ctx.prescale, dropout=None if drop is None else drop[:3])
         else:
             K.attn_bwd(q, k, v, o, do.view(B, N, H, D), lse, dq, dk, dv, mask, q_prescaled=ctx.prescale, dropout=None if drop is None else drop[:3])
-            if rope is not None:
+            if rpath == "kernel":
                 K.rope_(dqkv3, 2 * H, D, rope.table, rope.pos_off(N), conj=True)
         dh = K.gemm_nt(dqkv, shadow(qkv_w, transpose=True))
         dws = wgrad(dqkv, h, list(qkv_w))
@@ -571,6 +614,26 @@ class CrossAttnBranch(torch.autograd.Function):
 _MLP_BWD_FUSED = os.environ.get("FK_MLP_BWD_FUSED", "1") != "0"
 
 
+def mlp_path(hidden: int, has_gate: bool, has_up_bias: bool) -> str:
+    """MlpBranch.forward's up-projection (host-side, no GPU): "swiglu_fused" = gemm_nt_swiglu on the interleaved shadow, "swiglu" =
+    gemm_nt + swiglu_fwd, "gelu" = gemm_nt + gelu_fwd."""
+    if not has_gate:
+        return "gelu"
+    return "swiglu_fused" if not has_up_bias and hidden % 8 == 0 else "swiglu"
+
+
+def mlp_bwd_path(fused: bool, dtype, d: int, hidden: int, rows: int) -> str:
+    """MlpBranch.backward's data-gradient chain (host-side, no GPU): "one_launch" = mlp_bwd_fused, "dswiglu" = gemm_nt_dswiglu + gemm_nt,
+    "plain" = gemm_nt, swiglu_bwd / gelu_bwd, gemm_nt."""
+    if not fused:
+        return "plain"
+    # 128 tokens per workgroup: below ~256 workgroups the two tiled GEMMs fill the chip better
+    if (_MLP_BWD_FUSED and dtype == torch.bfloat16 and d == 384 and hidden % 32 == 0 and rows >= 32768
+            and rows * (2 * hidden) * 2 < 2 ** 32):
+        return "one_launch"
+    return "dswiglu"
+
+
 class MlpBranch(torch.autograd.Function):
     """y = [x +] W2 act(W1 [LN](x)):  SwiGLU (w1,w3 -> silu*gate -> w2, models/brainformer.py:115-124,244) when
     ``gate_w`` is given, GELU-erf MLP with biases (models/gpt2_model.py:87-92,105) otherwise."""
@@ -587,7 +650,7 @@ class MlpBranch(torch.autograd.Function):
             h, mean, rstd = K.norm_fwd(x2, ln_w.detach(), None if ln_b is None else ln_b.detach(), eps, nkind)
         else:
             h, mean, rstd = x2, None, None
-        fused = gate_w is not None and up_b is None and up_w.shape[0] % 8 == 0
+        fused = mlp_path(up_w.shape[0], gate_w is not None, up_b is not None) == "swiglu_fused"
         if fused:     # up-projection + SwiGLU in one kernel (interleaved hidden layout)
             a, g = K.gemm_nt_swiglu(h, shadow_swiglu(up_w, gate_w))
         else:
@@ -622,13 +685,13 @@ class MlpBranch(torch.autograd.Function):
         dyd = dy2 if drop is None else K.dropout(dy2, drop[0], drop[1], drop[2])         # the gradient behind the dropout
         (ddown,) = wgrad(dyd, g, [down_w])
         ddb = K.colsum(dyd) if has_db else None
-        if (ctx.fused and _MLP_BWD_FUSED and dyd.dtype == torch.bfloat16 and d == 384 and g.shape[1] % 32 == 0 and dyd.shape[0] >= 32768          # 128 tokens per workgroup: below ~256 workgroups the two tiled GEMMs fill the chip better
-                and dyd.shape[0] * a.shape[1] * 2 < 2 ** 32):
+        bpath = mlp_bwd_path(ctx.fused, dyd.dtype, d, g.shape[1], dyd.shape[0])
+        if bpath == "one_launch":
             # both products of the data-gradient chain in ONE attention-shaped launch, dh13 handed over in registers: the same bits as the
             # two launches below, -0.3 ... -0.4 ms per cfg2 step; FK_MLP_BWD_FUSED=0 keeps the two launches
             da, dh = K.mlp_bwd_fused(dyd, shadow([down_w], transpose=True), a, shadow_swiglu(up_w, gate_w, transpose=True))
             dups = wgrad(da, h, [up_w, gate_w], swiglu_interleaved=True)
-        elif ctx.fused:   # down-projection dgrad + SwiGLU backward in one kernel; dg is never materialised
+        elif bpath == "dswiglu":   # down-projection dgrad + SwiGLU backward in one kernel; dg is never materialised
             da = K.gemm_nt_dswiglu(dyd, shadow([down_w], transpose=True), a)
             dh = K.gemm_nt(da, shadow_swiglu(up_w, gate_w, transpose=True))
             dups = wgrad(da, h, [up_w, gate_w], swiglu_interleaved=True)
