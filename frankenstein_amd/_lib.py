@@ -110,6 +110,8 @@ SIGNATURES = {
     "fk_ctc_loss_fwd": (_int, [_p, _i64, _i64, _p, _i64, _p, _p, _i64, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _int, _int, _int, _int, _p, _sz, _p]),
     "fk_ctc_loss_bwd": (_int, [_p, _i64, _i64, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _int, _int, _int, _p, _sz, _p]),
     "fk_ctc_collapse": (_int, [_p, _i64, _p, _p, _i64, _p, _i64, _i64, _i64, _i64, _p]),
+    "fk_ctc_align_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "fk_ctc_align": (_int, [_p, _i64, _i64, _p, _i64, _p, _p, _i64] + [_i64] * 6 + [_p, _p, _i64, _p, _i64, _p, _p, _p, _i64, _int, _p, _sz, _p]),
     "fk_ctc_beam_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),
     "fk_ctc_beam_search": (_int, [_p, _i64, _i64, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _p, _i64, _i64, _p, _p, _int, _p, _sz, _p]),
     "fk_ngram_hash": (_u32, [_u32, _u32]),

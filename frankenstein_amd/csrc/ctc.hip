@@ -15,6 +15,11 @@
 //                      dlogits[b,t,c] = g_b (exp(logit - lse) - exp(logsumexp_{s: l'_s = c}(alpha_t(s) + beta_t(s)) + nll_b - (logit - lse)))
 //                    the softmax term is a vector sweep of the row; the states of one class are summed in a fixed order (blank states: a
 //                    tree; a label: its first occurrence walks the chain of later occurrences that the forward recorded) — no atomics.
+//   fk_ctc_align     forced alignment (semantics: include/franken_hip.h; float64 restatement tests/ctc_align_ref.py)
+//                    launch 1  ctc_row_lse_kernel  as above
+//                    launch 2  ctc_align_kernel    one workgroup per sample on the lattice kernel's two routes: the alpha sweep with max for
+//                              logsumexp and a 2-bit back-pointer per (t, s), sixteen frames a dword; then the same workgroup walks back in
+//                              chunks of 256 frames whose back-pointers sit in LDS, and writes path, index, spans and per-label sums
 //   fk_ctc_collapse  greedy decoding behind fk_argmax_rows: merge repeated frames, drop blanks, ordered compaction by ballot + prefix count
 //   fk_ctc_beam_search  prefix beam search, n-best with scores (semantics: include/franken_hip.h; float64 restatement tests/ctc_beam_ref.py)
 //                    launch 1  ctc_beam_prune_kernel  row-parallel like row_lse: one sweep of the row gives row_lse, lp[blank] and the K best
@@ -95,6 +100,31 @@ FK_DEV int clamp_len(const int64_t* lengths, int b, int hi) {
   if (!lengths) return hi;
   const int64_t v = lengths[b];
   return v < 0 ? 0 : (v > hi ? hi : (int)v);
+}
+
+// The frame of a one-workgroup-per-sample kernel over the extended states (the lattice, the alignment): thread s owns state s of
+// l' = (blank, l_1, blank, ..., l_L, blank).
+// L_b: target_lengths[b] clamped, or without the array the leading entries of the row tg that differ from pad_value (every thread of the
+// workgroup calls it; sh: 8 ints; it holds barriers)
+FK_DEV int target_len(const int64_t* target_lengths, const int64_t* tg, int64_t pad_value, int b, int Lmax, int* sh) {
+  if (target_lengths) return clamp_len(target_lengths, b, Lmax);
+  int f = Lmax;
+  for (int i = threadIdx.x; i < Lmax; i += blockDim.x)
+    if (tg[i] == pad_value) { f = i; break; }
+  return block_min_int(f, sh);
+}
+// the class of extended state s: a label clamped into [0, C) and off the blank, the blank for an even state or one behind the target
+FK_DEV int state_label(const int64_t* tg, int s, int Lb, int C, int blank) {
+  if (!(s & 1) || (s >> 1) >= Lb) return blank;
+  int64_t l = tg[s >> 1];
+  l = l < 0 ? 0 : (l >= C ? C - 1 : l);
+  if (l == blank) l = blank == 0 ? 1 : blank - 1;
+  return (int)l;
+}
+// state s exchanges mass with state `far` = s -+ 2 across the blank between them: both carry labels, and different ones (sh_lab: the
+// classes of all CTC_MAX_THREADS states)
+FK_DEV bool may_skip(const int* sh_lab, int s, int far, int S, int lab) {
+  return s < S && (s & 1) && far >= 1 && far < S && sh_lab[far >= 0 && far < CTC_MAX_THREADS ? far : s] != lab;
 }
 
 // running (max, sum of exponentials) per lane, rescaled once per vector; exp(-inf - -inf) is never formed; returns the vector's own maximum
@@ -196,25 +226,11 @@ __global__ __launch_bounds__(WAVE ? 64 : CTC_MAX_THREADS) void ctc_lattice_kerne
   // lengths, clamped; without target_lengths: the leading entries that differ from pad_value
   const int Tb = clamp_len(a.input_lengths, b, a.T);
   const int64_t* tg = a.targets + (int64_t)b * a.ldtgt;
-  int Lb;
-  if (a.target_lengths) {
-    Lb = clamp_len(a.target_lengths, b, a.Lmax);
-  } else {
-    int f = a.Lmax;
-    for (int i = s; i < a.Lmax; i += blockDim.x)
-      if (tg[i] == a.pad_value) { f = i; break; }
-    Lb = block_min_int(f, sh_red);
-  }
+  const int Lb = target_len(a.target_lengths, tg, a.pad_value, b, a.Lmax, sh_red);
   const int S = 2 * Lb + 1;
 
   // the class of this thread's state
-  int lab = a.blank;
-  if ((s & 1) && (s >> 1) < Lb) {
-    int64_t l = tg[s >> 1];
-    l = l < 0 ? 0 : (l >= a.C ? a.C - 1 : l);
-    if (l == a.blank) l = a.blank == 0 ? 1 : a.blank - 1;
-    lab = (int)l;
-  }
+  const int lab = state_label(tg, s, Lb, a.C, a.blank);
   sh_lab[s] = lab;
   __syncthreads();
   const bool live = s < S, odd = (s & 1) != 0;
@@ -250,7 +266,7 @@ __global__ __launch_bounds__(WAVE ? 64 : CTC_MAX_THREADS) void ctc_lattice_kerne
   // alpha (dir 0) looks at s - 1 and s - 2 and walks t = 0 .. T_b - 1; beta (dir 1) looks at s + 1 and s + 2 and walks down from T_b - 1
   const int d = dir ? 1 : -1;
   const int far = s + 2 * d;
-  const bool skip = live && odd && far >= 1 && far < S && sh_lab[far >= 0 && far < CTC_MAX_THREADS ? far : s] != lab;
+  const bool skip = may_skip(sh_lab, s, far, S, lab);
   const bool init = live && (dir ? (s >= S - 2) : (s <= 1));
   const T* lg = (const T*)a.logits + (int64_t)b * a.ldb + lab;
   const float* lse = a.row_lse + (int64_t)b * a.T;
@@ -319,6 +335,237 @@ __global__ __launch_bounds__(WAVE ? 64 : CTC_MAX_THREADS) void ctc_lattice_kerne
       const float raw = -lse3(sh_fin[0], sh_fin[1], -INFINITY);
       a.w.nll_raw[b] = raw;
       a.nll[b] = (a.zero_inf && raw == INFINITY) ? 0.0f : raw;
+    }
+  }
+}
+
+// ---- forced alignment: the lattice in the max-plus semiring with a back-pointer per (t, s), then the walk back ---------------------------
+// forward  v_t(s) = max(v_{t-1}(s), v_{t-1}(s-1), v_{t-1}(s-2) if may_skip) + lp_t(l'_s); the move 0 / 1 / 2 that won (exact ties: the smaller
+//          move) is two bits; a thread gathers the codes of CTC_ALIGN_PACK frames in a register and stores one dword: bp[b][t / PACK][s]
+// backward CTC_ALIGN_CHUNK frames at a time from the last to the first: thread s copies column s of the chunk's packed rows (what it wrote
+//          itself) into LDS, thread 0 walks the chunk there (a dependent LDS read a frame, no global access) and leaves the state per
+//          frame in LDS, then all threads turn states into path / index and mark the span boundaries of the labels (in LDS)
+// last     thread i stores start / end of label i and sums lp_t(l_i) over its frames in ascending order.  No atomics.
+constexpr int CTC_ALIGN_PACK = 16;                      // frames per back-pointer dword
+constexpr int CTC_ALIGN_CHUNK = 256;                    // frames per backtrack chunk
+constexpr int ALIGN_ROWS = CTC_ALIGN_CHUNK / CTC_ALIGN_PACK;
+static_assert(CTC_ALIGN_PACK * 2 == 32 && CTC_ALIGN_CHUNK % CTC_ALIGN_PACK == 0 && CTC_PF <= CTC_ALIGN_PACK && CTC_ALIGN_PACK % CTC_PF == 0,
+              "a dword of 2-bit codes; whole dwords a chunk");
+static_assert(ALIGN_ROWS * CTC_MAX_THREADS * 4 + (CTC_ALIGN_CHUNK + 2) * 4 + CTC_MAX_THREADS * 4 + 2 * 256 * 4 + 64 <= 40 * 1024,
+              "ctc_align_kernel: LDS budget (four workgroups of 512 threads a CU: all 32 waves)");
+
+struct CtcAlignWs {
+  float* row_lse;   // [B T]
+  unsigned* bp;     // [B][ceil(T / PACK)][S_pad] sixteen 2-bit moves a dword, frame t in bits 2 (t % PACK)
+};
+static inline size_t align_ws_carve(CtcAlignWs& w, void* base, int64_t B, int64_t T, int S_pad) {
+  char* p = (char*)base;
+  size_t o = 0;
+  w.row_lse = (float*)(p + o); o += a256((size_t)B * T * sizeof(float));
+  w.bp = (unsigned*)(p + o);   o += a256((size_t)B * fk_cdiv(T, CTC_ALIGN_PACK) * S_pad * sizeof(unsigned));
+  return o;
+}
+
+struct CtcAlignArgs {
+  const void* logits;
+  int64_t ldb, ldt;
+  const int64_t* targets;
+  int64_t ldtgt;
+  const int64_t* input_lengths;
+  const int64_t* target_lengths;
+  int64_t pad_value, pad;
+  CtcAlignWs w;
+  float* score;
+  int64_t* path;
+  int64_t ld_path;
+  int64_t* index;
+  int64_t ld_index;
+  int64_t* start;
+  int64_t* end;
+  float* label_lp;
+  int64_t ld_lab;
+  int T, C, Lmax, S_pad, blank;
+};
+
+// what a sample holds where there is nothing to say: frames [t0, T) of path / index, labels [l0, Lmax) of start / end / label_lp
+FK_DEV void align_fill(const CtcAlignArgs& a, int b, int t0, int l0) {
+  for (int t = t0 + threadIdx.x; t < a.T; t += blockDim.x) {
+    a.path[(int64_t)b * a.ld_path + t] = a.pad;
+    if (a.index) a.index[(int64_t)b * a.ld_index + t] = -1;
+  }
+  for (int i = l0 + threadIdx.x; i < a.Lmax; i += blockDim.x) {
+    if (a.start) a.start[(int64_t)b * a.ld_lab + i] = -1;
+    if (a.end) a.end[(int64_t)b * a.ld_lab + i] = -1;
+    if (a.label_lp) a.label_lp[(int64_t)b * a.ld_lab + i] = 0.0f;
+  }
+}
+
+template <typename T, bool WAVE>
+__global__ __launch_bounds__(WAVE ? 64 : CTC_MAX_THREADS) void ctc_align_kernel(CtcAlignArgs a) {
+  constexpr int W = CTC_MAX_THREADS + 4;                // LDS route: state s at index s + 2, two -inf entries either side
+  constexpr int SW = WAVE ? 64 : CTC_MAX_THREADS;       // row stride of the chunk's back-pointers in LDS
+  __shared__ int sh_lab[CTC_MAX_THREADS];
+  __shared__ int sh_red[8];
+  __shared__ float sh_fin[2];
+  __shared__ unsigned sh_bp[ALIGN_ROWS * SW];
+  float* sh_st = reinterpret_cast<float*>(sh_bp);       // the forward's double-buffered state vector: over before the first chunk is copied in
+  static_assert(WAVE || 2 * W <= ALIGN_ROWS * SW, "the state vector fits into the chunk buffer");
+  __shared__ int sh_state[CTC_ALIGN_CHUNK + 2];       // [1 + i]: the state at frame c0 + i; [0] and [n + 1]: the frames either side, -1: none
+  __shared__ int sh_start[256], sh_end[256];            // per label (Lmax <= 255)
+  const int b = blockIdx.x, s = threadIdx.x;
+
+  const int Tb = clamp_len(a.input_lengths, b, a.T);
+  const int64_t* tg = a.targets + (int64_t)b * a.ldtgt;
+  const int Lb = target_len(a.target_lengths, tg, a.pad_value, b, a.Lmax, sh_red);
+  const int S = 2 * Lb + 1;
+  const int lab = state_label(tg, s, Lb, a.C, a.blank);
+  sh_lab[s] = lab;
+  if (s < 256) sh_start[s] = sh_end[s] = -1;
+  __syncthreads();
+  const bool live = s < S;
+
+  if (Tb == 0) {                                        // no frame: only the empty target has an alignment, the empty one
+    if (s == 0) a.score[b] = Lb == 0 ? 0.0f : -INFINITY;
+    align_fill(a, b, 0, 0);
+    return;
+  }
+
+  // ---- forward: the lattice kernel's alpha sweep with max for lse3 ----
+  const bool skip = may_skip(sh_lab, s, s - 2, S, lab);
+  const bool init = live && s <= 1;
+  const T* lg = (const T*)a.logits + (int64_t)b * a.ldb + lab;
+  const float* lse = a.w.row_lse + (int64_t)b * a.T;
+  const int NP = (a.T + CTC_ALIGN_PACK - 1) / CTC_ALIGN_PACK;
+  unsigned* bp = a.w.bp + (size_t)b * NP * a.S_pad + s;  // this thread's column: blockDim.x == S_pad on both routes
+
+  T ql[CTC_PF], nl[CTC_PF];
+  float qe[CTC_PF], ne[CTC_PF];
+#pragma unroll
+  for (int i = 0; i < CTC_PF; ++i) {
+    const int t = i < Tb ? i : Tb - 1;
+    ql[i] = lg[(int64_t)t * a.ldt];
+    qe[i] = lse[t];
+  }
+  if constexpr (!WAVE) {
+    if (s < 2) {
+      sh_st[s] = sh_st[W + s] = -INFINITY;
+      sh_st[a.S_pad + 2 + s] = sh_st[W + a.S_pad + 2 + s] = -INFINITY;
+    }
+  }
+  float v = -INFINITY;
+  unsigned codes = 0u;
+  for (int k0 = 0; k0 < Tb; k0 += CTC_PF) {
+#pragma unroll
+    for (int i = 0; i < CTC_PF; ++i) {
+      const int kk = k0 + CTC_PF + i, t = kk < Tb ? kk : Tb - 1;
+      nl[i] = lg[(int64_t)t * a.ldt];
+      ne[i] = lse[t];
+    }
+#pragma unroll
+    for (int i = 0; i < CTC_PF; ++i) {
+      const int k = k0 + i;
+      if (k < Tb) {                                     // workgroup-uniform
+        const float lp = to_f32<T>(ql[i]) - qe[i];
+        if (k == 0) {
+          v = init ? lp : -INFINITY;
+        } else {
+          float n1, n2;
+          if constexpr (WAVE) {
+            n1 = __shfl(v, (s - 1) & 63, 64);
+            n2 = __shfl(v, (s - 2) & 63, 64);
+            n1 = s >= 1 ? n1 : -INFINITY;
+          } else {
+            const float* cur = sh_st + ((k - 1) & 1) * W + s + 2;
+            n1 = cur[-1];
+            n2 = cur[-2];
+          }
+          n2 = skip ? n2 : -INFINITY;
+          float best = v;                               // exact ties: stay before s - 1 before s - 2
+          unsigned code = 0u;
+          if (n1 > best) { best = n1; code = 1u; }
+          if (n2 > best) { best = n2; code = 2u; }
+          v = live ? best + lp : -INFINITY;
+          codes |= code << (2 * (k & (CTC_ALIGN_PACK - 1)));
+        }
+        if constexpr (!WAVE) {
+          sh_st[(k & 1) * W + s + 2] = v;
+          __syncthreads();
+        }
+        if ((k & (CTC_ALIGN_PACK - 1)) == CTC_ALIGN_PACK - 1 || k == Tb - 1) {
+          bp[(size_t)(k / CTC_ALIGN_PACK) * a.S_pad] = codes;
+          codes = 0u;
+        }
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < CTC_PF; ++i) { ql[i] = nl[i]; qe[i] = ne[i]; }
+  }
+
+  // ---- the end state: the better of S - 1 and S - 2, S - 1 on an exact tie ----
+  if (s == S - 1) { sh_fin[0] = v; if (S < 2) sh_fin[1] = -INFINITY; }
+  if (s == S - 2) sh_fin[1] = v;
+  __syncthreads();
+  const float e0 = sh_fin[0], e1 = sh_fin[1];
+  const float sc = e1 > e0 ? e1 : e0;
+  if (s == 0) a.score[b] = sc;
+  if (sc == -INFINITY) {                                // no alignment (workgroup-uniform)
+    align_fill(a, b, 0, 0);
+    return;
+  }
+  align_fill(a, b, Tb, Lb);
+
+  // ---- backward: chunk by chunk, the walk in LDS ----
+  int cur = e1 > e0 ? S - 2 : S - 1;                    // thread 0's: the state at the frame the walk stands at
+  int after = -1;                                       //             the state at the first frame behind the chunk
+  int64_t* path = a.path + (int64_t)b * a.ld_path;
+  int64_t* index = a.index ? a.index + (int64_t)b * a.ld_index : nullptr;
+  for (int c0 = (Tb - 1) / CTC_ALIGN_CHUNK * CTC_ALIGN_CHUNK; c0 >= 0; c0 -= CTC_ALIGN_CHUNK) {
+    const int n = Tb - c0 < CTC_ALIGN_CHUNK ? Tb - c0 : CTC_ALIGN_CHUNK;
+    const int rows = (n + CTC_ALIGN_PACK - 1) / CTC_ALIGN_PACK;
+    unsigned col[ALIGN_ROWS];
+#pragma unroll
+    for (int r = 0; r < ALIGN_ROWS; ++r) col[r] = r < rows ? bp[(size_t)(c0 / CTC_ALIGN_PACK + r) * a.S_pad] : 0u;
+#pragma unroll
+    for (int r = 0; r < ALIGN_ROWS; ++r) sh_bp[r * SW + s] = col[r];
+    __syncthreads();
+    if (s == 0) {
+      sh_state[n + 1] = after;
+      for (int i = n - 1; i >= 0; --i) {
+        sh_state[i + 1] = cur;
+        after = cur;
+        const unsigned code = (sh_bp[(i / CTC_ALIGN_PACK) * SW + cur] >> (2 * (i & (CTC_ALIGN_PACK - 1)))) & 3u;
+        if (c0 + i > 0) {
+          cur -= (int)code;
+          cur = cur < 0 ? 0 : (cur >= S ? S - 1 : cur);
+        }
+      }
+      sh_state[0] = c0 > 0 ? cur : -1;
+    }
+    __syncthreads();
+    for (int i = s; i < n; i += blockDim.x) {
+      const int st = sh_state[i + 1], t = c0 + i;
+      path[t] = sh_lab[st];
+      if (index) index[t] = (st & 1) ? (st >> 1) : -1;
+      if (st & 1) {
+        if (sh_state[i] != st) sh_start[st >> 1] = t;
+        if (sh_state[i + 2] != st) sh_end[st >> 1] = t + 1;
+      }
+    }
+    __syncthreads();
+  }
+
+  // ---- per label: its span and the sum of its log-probabilities along it, one add a frame in ascending order ----
+  if (s < Lb) {
+    int t0 = sh_start[s], t1 = sh_end[s];
+    if (a.start) a.start[(int64_t)b * a.ld_lab + s] = t0;
+    if (a.end) a.end[(int64_t)b * a.ld_lab + s] = t1;
+    if (a.label_lp) {
+      t0 = t0 < 0 ? 0 : t0;
+      t1 = t1 > Tb ? Tb : t1;
+      const T* lr = (const T*)a.logits + (int64_t)b * a.ldb + sh_lab[2 * s + 1];
+      float sum = 0.0f;
+      for (int t = t0; t < t1; ++t) sum += to_f32<T>(lr[(int64_t)t * a.ldt]) - lse[t];
+      a.label_lp[(int64_t)b * a.ld_lab + s] = sum;
     }
   }
 }
@@ -1249,6 +1496,47 @@ int fk_ctc_collapse(const int64_t* argmax, int64_t lda, const int64_t* input_len
                (long long)B, (long long)T, (long long)lda, (long long)ldi);
   hipLaunchKernelGGL(ctc_collapse_kernel, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, argmax, lda, input_lengths, ids, ldi, lengths, (int)T, blank, pad);
   FK_CHECK_LAUNCH("fk_ctc_collapse");
+  return FK_OK;
+}
+
+size_t fk_ctc_align_workspace_bytes(int64_t B, int64_t T, int64_t Lmax) {
+  if (B <= 0 || T <= 0 || B * T >= (1LL << 31) || Lmax < 0 || 2 * Lmax + 1 > CTC_MAX_S) return 0;
+  CtcAlignWs w;
+  return align_ws_carve(w, nullptr, B, T, ctc_spad(Lmax));
+}
+
+int fk_ctc_align(const void* logits, int64_t ldb, int64_t ldt, const int64_t* targets, int64_t ldtgt, const int64_t* input_lengths,
+                 const int64_t* target_lengths, int64_t pad_value, int64_t B, int64_t T, int64_t C, int64_t Lmax, int64_t blank, int64_t pad,
+                 float* score, int64_t* path, int64_t ld_path, int64_t* index, int64_t ld_index, int64_t* start, int64_t* end, float* label_lp,
+                 int64_t ld_lab, int dtype, void* workspace, size_t workspace_bytes, void* stream) {
+  if (const int rc = check_common("fk_ctc_align", dtype, logits && score && path && (targets || Lmax == 0), B, T, C, blank)) return rc;
+  FK_CHECK_ARG(Lmax >= 0 && 2 * Lmax + 1 <= CTC_MAX_S, "fk_ctc_align: Lmax = %lld outside the envelope (2 * Lmax + 1 <= %d extended states)",
+               (long long)Lmax, CTC_MAX_S);
+  FK_CHECK_ARG(ldt >= C && ldb >= ldt && ldtgt >= Lmax, "fk_ctc_align: row stride %lld below C = %lld (batch stride %lld, target stride %lld)",
+               (long long)ldt, (long long)C, (long long)ldb, (long long)ldtgt);
+  FK_CHECK_ARG(T < (1LL << 31) - CTC_ALIGN_CHUNK, "fk_ctc_align: T = %lld frames leave no room for the frame index", (long long)T);
+  FK_CHECK_ARG(ld_path >= T && (!index || ld_index >= T), "fk_ctc_align: path / index stride %lld / %lld below T = %lld", (long long)ld_path,
+               (long long)ld_index, (long long)T);
+  FK_CHECK_ARG(!(start || end || label_lp) || ld_lab >= Lmax, "fk_ctc_align: label stride %lld below Lmax = %lld", (long long)ld_lab, (long long)Lmax);
+  CtcAlignArgs a;
+  a.S_pad = ctc_spad(Lmax);
+  const size_t need = align_ws_carve(a.w, workspace, B, T, a.S_pad);
+  FK_CHECK_ARG(workspace && workspace_bytes >= need, "fk_ctc_align: workspace too small (%zu bytes, fk_ctc_align_workspace_bytes gives %zu)",
+               workspace_bytes, need);
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t rows = B * T;
+  CTC_LAUNCH_ROWS(ctc_row_lse_kernel, dtype, rows, C, s, (const TT*)logits, ldb, ldt, a.w.row_lse, rows, (int)T, (int)C);
+  FK_CHECK_LAUNCH("fk_ctc_align(row_lse)");
+  a.logits = logits; a.ldb = ldb; a.ldt = ldt; a.targets = targets; a.ldtgt = ldtgt;
+  a.input_lengths = input_lengths; a.target_lengths = target_lengths; a.pad_value = pad_value; a.pad = pad;
+  a.score = score; a.path = path; a.ld_path = ld_path; a.index = index; a.ld_index = ld_index;
+  a.start = start; a.end = end; a.label_lp = label_lp; a.ld_lab = ld_lab;
+  a.T = (int)T; a.C = (int)C; a.Lmax = (int)Lmax; a.blank = (int)blank;
+  if (a.S_pad <= 64)
+    FK_BY_DTYPE(dtype, TT, hipLaunchKernelGGL((ctc_align_kernel<TT, true>), dim3((unsigned)B), dim3(64), 0, s, a));
+  else
+    FK_BY_DTYPE(dtype, TT, hipLaunchKernelGGL((ctc_align_kernel<TT, false>), dim3((unsigned)B), dim3(a.S_pad), 0, s, a));
+  FK_CHECK_LAUNCH("fk_ctc_align(align)");
   return FK_OK;
 }
 

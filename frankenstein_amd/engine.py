@@ -11,7 +11,7 @@ Design (MI355X-first, not a translation of the reference's op graph):
 """
 from __future__ import annotations
 
-from typing import List, Optional, Sequence, Tuple
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import math
 import os
@@ -925,6 +925,41 @@ def ctc_beam_decode_lm(logits: Tensor, lm, input_lengths: Optional[Tensor] = Non
     if logits.stride(-1) != 1:
         logits = logits.contiguous()
     return K.ctc_beam_search_lm(logits, lm, input_lengths, blank, beam_width, topk, nbest, lm_weight, length_bonus, use_eos, pad)
+
+
+class CtcAlignment(NamedTuple):
+    """engine.ctc_forced_align's result.  score fp32 [B]: the log-probability of the best alignment (-inf: the sample has none); path int64
+    [B, T]: the class per frame (`pad` behind the sample's end); index int64 [B, T]: the label of the target a frame emits (-1: blank or
+    behind the end); start / end int64 [B, Lmax]: label i holds the frames [start, end) (-1 / -1 behind the target's end); label_lp fp32
+    [B, Lmax]: the sum of the label's frame log-probabilities."""
+    score: Tensor
+    path: Tensor
+    index: Tensor
+    start: Tensor
+    end: Tensor
+    label_lp: Tensor
+
+    @property
+    def confidence(self) -> Tensor:
+        """fp32 [B, Lmax]: exp(label_lp / (end - start)), the geometric mean of the posteriors of the label's class over its frames; 0 where
+        there is no label"""
+        n = (self.end - self.start).clamp(min=1).to(torch.float32)
+        return torch.where(self.end > self.start, torch.exp(self.label_lp / n), torch.zeros_like(self.label_lp))
+
+
+@torch.no_grad()
+def ctc_forced_align(logits: Tensor, targets: Tensor, input_lengths: Optional[Tensor] = None, target_lengths: Optional[Tensor] = None,
+                     blank: int = 0, pad_value: int = -100, pad: int = -100) -> CtcAlignment:
+    """Forced alignment: the most probable alignment of logits [B, T, C] (fp32 / bf16, batch first, NOT log-softmaxed) to targets int64
+    [B, Lmax] (Viterbi over the CTC lattice; exact ties and corner cases: include/franken_hip.h, fk_ctc_align).  Lengths as ctc_loss:
+    target_lengths None: a target ends at its first `pad_value`; input_lengths None: T frames each; up to 255 labels.  The result is
+    indices and detached floats: no autograd graph.  Two launches, nothing waits for the host."""
+    if logits.stride(-1) != 1:
+        logits = logits.contiguous()
+    if targets.dim() == 2 and targets.shape[1] > 0 and targets.stride(1) != 1:
+        targets = targets.contiguous()
+    r = K.ctc_align(logits.detach(), targets, input_lengths, target_lengths, blank, pad_value, pad)
+    return CtcAlignment(r["score"], r["path"], r["index"], r["start"], r["end"], r["label_lp"])
 
 
 class HeadCrossEntropy(torch.autograd.Function):

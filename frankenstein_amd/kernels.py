@@ -1231,6 +1231,50 @@ def ctc_collapse(argmax: Tensor, input_lengths: Optional[Tensor] = None, blank: 
     return ids, lengths
 
 
+CTC_ALIGN_PACK, CTC_ALIGN_CHUNK = 16, 256       # csrc/ctc.hip: frames per back-pointer dword, frames per backtrack chunk in LDS
+
+
+def ctc_align(logits: Tensor, targets: Tensor, input_lengths: Optional[Tensor] = None, target_lengths: Optional[Tensor] = None, blank: int = 0,
+              pad_value: int = -100, pad: int = -100, want_index: bool = True, want_spans: bool = True, out: Optional[dict] = None) -> dict:
+    """Forced alignment (fk_ctc_align; semantics: include/franken_hip.h): logits [B, T, C] (fp32 / bf16, unit column stride, any row and
+    batch stride, NOT log-softmaxed), targets int64 [B, Lmax] (unit column stride), lengths as ctc_loss_fwd -> dict(score fp32 [B], path
+    int64 [B, T], index int64 [B, T], start / end int64 [B, Lmax], label_lp fp32 [B, Lmax]).  want_index / want_spans False: those
+    outputs are not computed (None).  out: tensors to write into, by the same names (unit column stride; tests: padded row strides)."""
+    assert logits.dim() == 3 and logits.stride(2) == 1 and targets.dim() == 2 and targets.dtype == torch.int64
+    B, T, Cn = logits.shape
+    Lmax = targets.shape[1]
+    assert targets.shape[0] == B and (Lmax == 0 or targets.stride(1) == 1)
+    dev = logits.device
+    out = dict(out or {})
+    new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)
+    r = {"score": out.get("score", None), "path": out.get("path", None), "index": None, "start": None, "end": None, "label_lp": None}
+    if r["score"] is None:
+        r["score"] = new((B,), torch.float32)
+    if r["path"] is None:
+        r["path"] = new((B, T), torch.int64)
+    if want_index:
+        r["index"] = out["index"] if "index" in out else new((B, T), torch.int64)
+    if want_spans:
+        for k, dt in (("start", torch.int64), ("end", torch.int64), ("label_lp", torch.float32)):
+            r[k] = out[k] if k in out else new((B, Lmax), dt)
+    assert r["score"].dtype == torch.float32 and r["score"].shape == (B,) and r["score"].is_contiguous()
+    for k, n, dt in (("path", T, torch.int64), ("index", T, torch.int64), ("start", Lmax, torch.int64), ("end", Lmax, torch.int64),
+                     ("label_lp", Lmax, torch.float32)):
+        t = r[k]
+        assert t is None or (t.dtype == dt and t.shape == (B, n) and (n == 0 or t.stride(1) == 1)), k
+    ld_lab = {r[k].stride(0) for k in ("start", "end", "label_lp") if r[k] is not None}
+    assert len(ld_lab) <= 1, "start, end and label_lp share one row stride"
+    nbytes = lib().fk_ctc_align_workspace_bytes(B, T, Lmax)
+    ws, _ = _ws(nbytes, dev)
+    il, tl = _ctc_lengths(input_lengths, B, dev), _ctc_lengths(target_lengths, B, dev)
+    with _timed("ctc_align"):
+        call("fk_ctc_align", logits.data_ptr(), logits.stride(0), logits.stride(1), targets.data_ptr() if Lmax else None,
+             targets.stride(0) if Lmax else 0, _ptr(il), _ptr(tl), pad_value, B, T, Cn, Lmax, blank, pad, r["score"].data_ptr(),
+             r["path"].data_ptr(), r["path"].stride(0), _ptr(r["index"]), r["index"].stride(0) if want_index else 0, _ptr(r["start"]),
+             _ptr(r["end"]), _ptr(r["label_lp"]), ld_lab.pop() if ld_lab else 0, fk_dtype(logits), _ptr(ws), nbytes, _stream())
+    return r
+
+
 def _ctc_beam_prologue(logits: Tensor, input_lengths: Optional[Tensor], beam_width: int, topk: Optional[int], nbest: int):
     """What both beam searches set up before their call -> (B, T, C, K, il, ids, lengths, ws, nbytes); topk None: min(32, C - 1)."""
     assert logits.dim() == 3 and logits.stride(2) == 1 and logits.dtype in (torch.float32, torch.bfloat16)

@@ -67,7 +67,9 @@ class BrainFormerCTC(_FileBrainFormer):
     phoneme head gets a language model at all; same forms, the scores being the fused totals.  With ngram= AND lm= the fused search fills
     the whole beam, the GPT rescores it with the PURE CTC score as its acoustic score (the n-gram only decides which hypotheses reach the
     list; its own score is not added a second time), and the first k of the GPT's order come back.
-    utils.metrics.token_error_rate(targets, ids) of that result is the phoneme / token error rate."""
+    utils.metrics.token_error_rate(targets, ids) of that result is the phoneme / token error rate.
+    align(x, targets): forced alignment (engine.ctc_forced_align), where in the read-out every label of a transcript or hypothesis sits and
+    how confident the head is of it."""
     config = Config
     head_name = 'to_words'
 
@@ -82,6 +84,14 @@ class BrainFormerCTC(_FileBrainFormer):
         if targets is None:
             return None, logits
         return E.ctc_loss(logits, targets, blank=self.blank, reduction='mean', zero_infinity=True, pad_value=-100), logits
+
+    @torch.no_grad()
+    def align(self, x, targets, input_lengths=None, target_lengths=None):
+        """Forced alignment of the read-out to `targets` (int64 [B, Lmax] padded with -100, or with target_lengths): the most probable
+        alignment as an engine.CtcAlignment (score, path, index, start, end, label_lp, .confidence), frames being read-out tokens.  To
+        align a hypothesis of the beam search (ids, lengths, scores = decode(x, beam_width=W, nbest=k)): align(x, ids[:, 0, :Lmax],
+        target_lengths=lengths[:, 0]) with Lmax <= 255 at least the longest hypothesis; its confidence flags the shaky tokens."""
+        return E.ctc_forced_align(self.features(x), targets, input_lengths, target_lengths, blank=self.blank, pad_value=-100, pad=-100)
 
     @torch.no_grad()
     def decode(self, x, beam_width=None, topk=None, nbest=1, lm=None, lm_prefix=None, lm_weight=1.0, length_bonus=0.0, eos_token_id=None,

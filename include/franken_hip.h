@@ -564,6 +564,35 @@ int fk_ctc_loss_bwd(const void* logits, int64_t ldb, int64_t ldt, const float* r
 int fk_ctc_collapse(const int64_t* argmax, int64_t lda, const int64_t* input_lengths, int64_t* ids, int64_t ldi, int64_t* lengths, int64_t B,
                     int64_t T, int64_t blank, int64_t pad, void* stream);
 
+/* ---- CTC forced alignment (csrc/ctc.hip): the most probable ALIGNMENT of logits [B, T, C] to a given transcript, with label spans and
+ *      per-label log-probabilities.  Semantics of this build (tests/ctc_align_ref.py restates them in float64); all arithmetic is fp32.
+ *   logits, targets, input_lengths, target_lengths, pad_value, blank: as fk_ctc_loss_fwd, lengths and labels clamped on the device in the
+ *   same way.  Per sample: lp_t = log_softmax(logits[b, t, :]) (row_lse as in the loss), l' = (blank, l_1, blank, ..., l_L, blank),
+ *   S = 2 L_b + 1.  v_0(0) = lp_0(blank), v_0(1) = lp_0(l_1), every other state -inf; for t >= 1
+ *     v_t(s) = max(v_{t-1}(s), v_{t-1}(s-1), v_{t-1}(s-2) if s is odd and l'_s != l'_{s-2}) + lp_t(l'_s)
+ *   with a back-pointer to the move that won; on an exact tie the smaller move wins (stay before s-1 before s-2).  The end state is the
+ *   better of v_{T_b-1}(S-1) and v_{T_b-1}(S-2), S-1 on an exact tie; score[b] is that value, the log-probability of the single best
+ *   alignment (score <= -nll of fk_ctc_loss_fwd), and the path is the back-pointer walk from the end state.
+ *   Results (nothing else is written; the padding of a row stride keeps what it held):
+ *     score fp32 [B];
+ *     path int64 [B, T] (row stride ld_path >= T): the class emitted at frame t; `pad` for t >= T_b;
+ *     index int64 [B, T] (ld_index >= T): which label of the target frame t emits, 0 .. L_b - 1; -1 on a blank frame and for t >= T_b;
+ *     start, end int64 [B, Lmax] (ld_lab >= Lmax): label i holds the frames [start, end), end > start; -1 / -1 for i >= L_b;
+ *     label_lp fp32 [B, Lmax] (ld_lab): the sum of lp_t(l_i) over the label's frames in ascending frame order, one fp32 add a frame; 0 for
+ *       i >= L_b.  exp(label_lp / (end - start)) is the label's confidence (geometric mean of its frame posteriors).
+ *   index, start, end, label_lp may each be NULL (not written); score and path may not.
+ *   A sample without alignment (T_b < L_b + adjacent repeats, T_b = 0 < L_b, or every alignment at -inf): score -inf, path all `pad`, index
+ *   all -1, every start = end = -1, label_lp = 0; never NaN.  T_b = 0 = L_b: score 0 and the same empty rows.  L_b = 0: an all-blank path.
+ *   Envelope: fk_ctc_loss_fwd's (Lmax <= 255, C >= 2, blank in [0, C), ldt >= C, fp32 / bf16), T < 2^31 - 256; FK_EINVAL beyond, no launch.
+ *   workspace: fk_ctc_align_workspace_bytes(B, T, Lmax) (0 outside the envelope): row_lse [B T] and the back-pointers, two bits per
+ *   (t, s), uint32 [B, ceil(T / 16), S_pad].  Two launches (the first is fk_ctc_loss_fwd's row_lse), no atomics, the same bits every
+ *   run, nothing waits for the host.                                                                                                  */
+size_t fk_ctc_align_workspace_bytes(int64_t B, int64_t T, int64_t Lmax);
+int fk_ctc_align(const void* logits, int64_t ldb, int64_t ldt, const int64_t* targets, int64_t ldtgt, const int64_t* input_lengths,
+                 const int64_t* target_lengths, int64_t pad_value, int64_t B, int64_t T, int64_t C, int64_t Lmax, int64_t blank, int64_t pad,
+                 float* score, int64_t* path, int64_t ld_path, int64_t* index, int64_t ld_index, int64_t* start, int64_t* end,
+                 float* label_lp, int64_t ld_lab, int dtype, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- CTC prefix beam search (csrc/ctc.hip): the most probable LABELLINGS of logits [B, T, C] (fp32 / bf16, strides as above), n-best
  *      with scores.  Semantics of this build (tests/ctc_beam_ref.py restates them in float64); all arithmetic is fp32.
  *   A beam is at most W distinct prefixes (tuples of non-blank labels), each with pb / pnb, the log-mass of the alignments of the frames

@@ -10,7 +10,12 @@ B = 32 each.  torch has no CTC beam search: the host restatement is the only alt
 
 python tools/ctc_bench.py --beam W --ngram ORDER [rounds] [reps]: also the search with n-gram shallow fusion (engine.ctc_beam_decode_lm) on
 the same logits, in the same interleaved rounds: an interpolated Witten-Bell model of that order from 2000 seeded Zipf-distributed
-sequences over the head's classes (utils.ngram), with its table size and max_probe, and what the fusion adds per frame."""
+sequences over the head's classes (utils.ngram), with its table size and max_probe, and what the fusion adds per frame.
+
+python tools/ctc_bench.py --align [rounds] [reps]: the forced alignment (engine.ctc_forced_align, both launches) beside the CTC loss forward
+without lattice (K.ctc_loss_fwd(want_grad=False): the same row_lse launch and the same sweep with logsumexp for max) at the same shape in
+the same interleaved rounds, and beside the float64 host restatement (tests/ctc_align_ref.py), at B = 32, 32 x 50258 with 25 labels and
+768 x 41 with 120 labels."""
 import sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -27,6 +32,9 @@ if beam is not None:
 ngram = int(argv.pop(argv.index("--ngram") + 1)) if "--ngram" in argv else None
 if ngram is not None:
     argv.remove("--ngram")
+align = "--align" in argv
+if align:
+    argv.remove("--align")
 rounds = int(argv[0]) if len(argv) > 0 else 7
 reps = int(argv[1]) if len(argv) > 1 else 10
 dev = torch.device("cuda")
@@ -82,7 +90,37 @@ for B, T, C, Kc in (BEAM_SHAPES if beam is not None else []):
               f"rounds min .. max: beam {spread['beam'][0]:.1f} .. {spread['beam'][1]:.1f} us, fused {spread['fused'][0]:.1f} .. {spread['fused'][1]:.1f} us;  "
               f"the best hypothesis moves in {moved} of {B}", flush=True)
 
-for B, T, C, L in (SHAPES if beam is None else []):
+for B, T, C, L in ([SHAPES[0], SHAPES[2]] if align else []):
+    from tests import ctc_align_ref as AR
+    blank = C - 1
+    logits = 3.0 * torch.randn(B, T, C, device=dev, generator=g)
+    targets = torch.randint(0, C - 1, (B, L), device=dev, generator=g)
+    il = torch.full((B,), T, dtype=torch.int64, device=dev)
+    tl = torch.full((B,), L, dtype=torch.int64, device=dev)
+    cases = {"align": lambda: E.ctc_forced_align(logits, targets, il, tl, blank),
+             "loss fwd": lambda: K.ctc_loss_fwd(logits, targets, il, tl, blank, "mean", True, want_grad=False)}
+    for f in cases.values():
+        f()
+    torch.cuda.synchronize()
+    times = {k: [] for k in cases}
+    for _ in range(rounds):
+        for k, f in cases.items():
+            times[k].append(timed(f))
+    med = {k: sorted(v)[len(v) // 2] for k, v in times.items()}
+    spread = {k: (min(v), max(v)) for k, v in times.items()}
+    r = cases["align"]()
+    n_host = min(B, 2)                                         # the host walks sample after sample: two are timed, B are charged
+    t0 = time.perf_counter()
+    ref = AR.viterbi(logits[:n_host].cpu().numpy(), targets[:n_host].cpu().numpy(), None, None, blank)
+    host = (time.perf_counter() - t0) / n_host * B
+    same = bool((r.path[:n_host].cpu().numpy() == ref["path"]).all())
+    feasible = int(torch.isfinite(r.score).sum())
+    print(f"(B, T, C, L) = ({B}, {T}, {C}, {L})  route {K.CTC_ROUTE_NAMES[K.ctc_route(L)]:8s} " + "  ".join(f"{k} {t:8.1f} us" for k, t in med.items())
+          + f"  align / loss fwd {med['align'] / med['loss fwd']:.2f}  rounds min .. max: align {spread['align'][0]:.1f} .. {spread['align'][1]:.1f} us, "
+          + f"loss fwd {spread['loss fwd'][0]:.1f} .. {spread['loss fwd'][1]:.1f} us  host float64 restatement {host * 1e3:9.1f} ms ({n_host} samples timed, "
+          + f"scaled to {B})  samples with an alignment {feasible} of {B}  paths equal the restatement's: {same}", flush=True)
+
+for B, T, C, L in (SHAPES if beam is None and not align else []):
     blank = C - 1
     logits = 3.0 * torch.randn(B, T, C, device=dev, generator=g)
     targets = torch.randint(0, C - 1, (B, L), device=dev, generator=g)
