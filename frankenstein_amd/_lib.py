@@ -121,6 +121,12 @@ SIGNATURES = {
     "fk_nbest_trie_mask": (_int, [_p, _p, _p, _i64, _i64, _i64, _p]),
     "fk_gpt_embed_pos": (_int, [_p] * 6 + [_i64] * 6 + [_int, _p]),
     "fk_nbest_rescore": (_int, [_p] * 8 + [_i64, _i64, _p, _p] + [_i64] * 4 + [_int, _f32, _f32, _f32, _i64] + [_p] * 9),
+    "fk_edit_distance_route": (_int, [_i64, _i64]),
+    "fk_edit_distance": (_int, [_p, _i64, _i64, _p, _i64, _i64, _p, _i64, _i64, _p, _i64, _i64, _i64, _i64, _p, _p, _p]),
+    "fk_nbest_pairwise_distance": (_int, [_p, _i64, _i64, _p, _p, _i64, _i64, _i64, _p, _p]),
+    "fk_mbr_rank": (_int, [_p, _p, _f32, _p, _i64, _i64, _p, _i64, _i64, _i64, _i64] + [_p] * 8),
+    "fk_mwer_combine": (_int, [_p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p]),
+    "fk_mwer_reduce_rows": (_int, [_p, _p, _p, _i64, _i64, _i64, _int, _int, _p]),
     "fk_ce_workspace_bytes": (_sz, [_i64]),
     "fk_ce_loss_fwd": (_int, [_p, _i64, _p, _p, _p, _i64, _i64, _i64, _int, _p, _sz, _p]),
     "fk_ce_loss_bwd": (_int, [_p, _i64, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _int, _p]),
@@ -141,6 +147,7 @@ VQ_EMA, VQ_KMEANS = 0, 1                                                        
 CTC_WAVE, CTC_LDS = 0, 1                                                             # fk_ctc_route
 CTC_NONE, CTC_SUM, CTC_MEAN = 0, 1, 2                                                 # fk_ctc_loss_* reductions
 NBEST_MAX_HYPS, NBEST_MAX_T, NBEST_MAX_NODES, NBEST_MAX_ROWS = 32, 1024, 32769, 4096         # the envelope of fk_nbest_* (csrc/rescore.hip)
+EDIT_LANE, EDIT_ROWS4, EDIT_ROWS16 = 0, 1, 2                                          # fk_edit_distance_route
 VQ_ROWS = 32                                                                          # data rows per workgroup of fk_vq_assign
 
 

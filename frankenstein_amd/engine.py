@@ -962,6 +962,180 @@ def ctc_forced_align(logits: Tensor, targets: Tensor, input_lengths: Optional[Te
     return CtcAlignment(r["score"], r["path"], r["index"], r["start"], r["end"], r["label_lp"])
 
 
+# ---- edit distance on the device (csrc/editdist.hip): error rates, the oracle error of a list, MBR re-ranking and the MWER loss ----
+
+def _seq3(t: Tensor, lens: Optional[Tensor], pad_value: int):
+    """[B, L] or [B, n, L] ids (+ lengths [B] / [B, n]) -> int64 [B, n, L] with unit token stride and L >= 1, lengths int64 [B, n] or None"""
+    assert t.dtype == torch.int64 and t.dim() in (2, 3), "ids: int64 [B, L] or [B, n, L]"
+    if t.dim() == 2:
+        t = t.unsqueeze(1)
+    if lens is not None:
+        lens = lens.to(torch.int64).reshape(t.shape[0], t.shape[1]).contiguous()
+    if t.shape[2] == 0:                                   # a column-less array holds empty sequences
+        t = t.new_full((t.shape[0], t.shape[1], 1), pad_value)
+    elif t.stride(2) != 1:
+        t = t.contiguous()
+    return t, lens
+
+
+@torch.no_grad()
+def edit_distance(a: Tensor, b: Tensor, a_lengths: Optional[Tensor] = None, b_lengths: Optional[Tensor] = None, pad_value: int = -100) -> Tensor:
+    """Unit-cost Levenshtein distances on int64 ids, on the device (the host yardstick is utils.metrics.edit_distance).  a [P, La] against
+    b [P, Lb] -> int32 [P] (pair by pair); a [B, La] against b [B, n, Lb] -> int32 [B, n] (a sentence's reference against its n
+    hypotheses); a [B, n, La] against b [B, n, Lb] -> int32 [B, n].  Lengths int64 of the leading shape, or None: a sequence ends at its
+    first `pad_value` (the -100 label padding).  At most 1024 tokens per row and 32 sequences per group.  One launch, nothing waits for the
+    host."""
+    flat = b.dim() == 2
+    a3, al = _seq3(a, a_lengths, pad_value)
+    b3, bl = _seq3(b, b_lengths, pad_value)
+    d = K.edit_distance(a3, al, b3, bl, pad_value)
+    return d[:, 0] if flat else d
+
+
+@torch.no_grad()
+def error_rate(references: Tensor, hypotheses: Tensor, reference_lengths: Optional[Tensor] = None, hypothesis_lengths: Optional[Tensor] = None,
+               pad_value: int = -100):
+    """The corpus error rate of utils.metrics.token_error_rate without leaving the device: references int64 [B, Lr], hypotheses int64
+    [B, Lh] (lengths int64 [B], or None: -100 padded) -> (rate, errors, ref_lengths): rate the fp32 device scalar sum(errors) /
+    sum(reference lengths) (nan for an empty corpus of references), errors int32 [B], ref_lengths int32 [B].  No synchronisation: read
+    rate with .item() when the number is wanted."""
+    assert references.dim() == 2 and hypotheses.dim() == 2
+    a3, al = _seq3(references, reference_lengths, pad_value)
+    b3, bl = _seq3(hypotheses, hypothesis_lengths, pad_value)
+    d, alen = K.edit_distance(a3, al, b3, bl, pad_value, want_lengths=True)
+    errors, ref_lengths = d[:, 0], alen[:, 0]
+    return errors.sum().to(torch.float32) / ref_lengths.sum().to(torch.float32), errors, ref_lengths
+
+
+@torch.no_grad()
+def nbest_oracle(ids: Tensor, lengths: Tensor, scores: Optional[Tensor], targets: Tensor, target_lengths: Optional[Tensor] = None,
+                 pad_value: int = -100):
+    """The oracle error of an n-best list (is the beam wide enough?): ids int64 [B, n, T], lengths int64 [B, n], scores fp32 [B, n] or
+    None, targets int64 [B, L] -> (errors int32 [B], index int64 [B]): the smallest distance to the reference over the valid hypotheses
+    (finite score) and the first hypothesis that has it; a sentence without a valid hypothesis: 2^31 - 1 and index 0."""
+    a3, al = _seq3(targets, target_lengths, pad_value)
+    b3, bl = _seq3(ids, lengths, pad_value)
+    d = K.edit_distance(a3, al, b3, bl, pad_value)
+    if scores is not None:
+        d = torch.where(torch.isfinite(scores), d, torch.full_like(d, 2 ** 31 - 1))
+    best, index = d.min(dim=1)
+    first = (d == best[:, None]).to(torch.int64).argmax(dim=1)          # min's index among equals is unspecified; the first one is wanted
+    return best, first
+
+
+class MbrResult(NamedTuple):
+    """engine.mbr_rerank's result, best (smallest expected distance) first: ids int64 [B, n, T] padded with `pad`, lengths int64 [B, n],
+    scores fp32 [B, n] (the input scores in the new order), risk fp32 [B, n] (+inf for an invalid hypothesis), order int64 [B, n] (the
+    input index of each place), n_valid int64 [B], dist int32 [B, n, n] in INPUT order (-1 in an invalid hypothesis' row and column)."""
+    ids: Tensor
+    lengths: Tensor
+    scores: Tensor
+    risk: Tensor
+    order: Tensor
+    n_valid: Tensor
+    dist: Tensor
+
+
+@torch.no_grad()
+def mbr_rerank(ids: Tensor, lengths: Tensor, scores: Tensor, scale: float = 1.0, pad: int = -100) -> MbrResult:
+    """Minimum-Bayes-risk selection from n-best lists (ids int64 [B, n, T], lengths int64 [B, n], scores fp32 [B, n]: what
+    ctc_beam_decode, ctc_beam_decode_lm or GPT.rescore_nbest return): under the posterior softmax(scale * scores) over a sentence's valid
+    hypotheses (finite score) every hypothesis gets its EXPECTED edit distance to the others, and the list comes back by ascending risk;
+    exact ties go to the better-scored (earlier) hypothesis, invalid ones last.  scale = 0 is the uniform posterior (the list's medoid), a
+    large scale returns the best-scored hypothesis.  Two launches, nothing waits for the host."""
+    if ids.stride(-1) != 1:
+        ids = ids.contiguous()
+    lengths, scores = lengths.contiguous(), scores.to(torch.float32).contiguous()
+    dist = K.nbest_pairwise_distance(ids, lengths, scores)
+    _, (o_ids, o_len, o_sc, o_risk, order, n_valid) = K.mbr_rank(dist, ids, lengths, scores, scale, pad)
+    return MbrResult(o_ids, o_len, o_sc, o_risk, order, n_valid, dist)
+
+
+class CtcMwerLoss(torch.autograd.Function):
+    """mwer_weight * MWER + ce_weight * CTC as ONE node over the logits: the forward is the CTC lattice of every hypothesis on the logits
+    expanded n times (reduction none), fk_mwer_combine and, with ce_weight, the CTC loss of the targets; the backward is kernel launches and
+    pointwise scaling only (the CTC backward of the expanded rows scaled by grad_out * coef / count, fk_mwer_reduce_rows back to [B, T, C]
+    on top of the CTC term's gradient), so one gradient reaches the logits and no reduction or accumulation is left to the autograd
+    engine inside a captured step.  A row the combine ruled out is never read: its CTC backward is NaN whatever it is scaled by."""
+
+    @staticmethod
+    def forward(ctx, logits, targets, input_lengths, target_lengths, hyp_targets, hyp_frames, hyp_lengths, errors, scores, lengths, blank,
+                mwer_weight, ce_weight, zero_infinity, pad_value):
+        B, T, Cn = logits.shape
+        n = errors.shape[1]
+        want = ctx.needs_input_grad[0]
+        lx = logits.detach().unsqueeze(1).expand(B, n, T, Cn).reshape(B * n, T, Cn)
+        st = K.ctc_loss_fwd(lx, hyp_targets, hyp_frames, hyp_lengths, blank, "none", False, pad_value, want_grad=want)
+        loss_b, coef, count, valid = K.mwer_combine(st.nll.view(B, n), errors, scores, lengths, 255)
+        count = count.clamp(min=1.0)
+        loss = loss_b.sum() / count[0]
+        if mwer_weight != 1.0:
+            loss = mwer_weight * loss
+        st_ce = None
+        if ce_weight:
+            st_ce = K.ctc_loss_fwd(logits.detach(), targets, input_lengths, target_lengths, blank, "mean", zero_infinity, pad_value,
+                                    want_grad=want)
+            loss = loss + ce_weight * st_ce.loss2[0]
+        ctx.st, ctx.st_ce, ctx.weights = st, st_ce, (mwer_weight, ce_weight)
+        ctx.save_for_backward(logits, lx, coef, count, valid)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gout):
+        logits, lx, coef, count, valid = ctx.saved_tensors
+        mwer_weight, ce_weight = ctx.weights
+        g = gout.reshape(()).float()
+        dlogits = None
+        if ctx.st_ce is not None:
+            dlogits = K.ctc_loss_bwd(logits, ctx.st_ce, (g * ce_weight).reshape(1).contiguous())
+            if not dlogits.is_contiguous():
+                dlogits = dlogits.contiguous()
+        rows = K.ctc_loss_bwd(lx, ctx.st, ((g * mwer_weight) * coef / count[0]).reshape(-1).contiguous())
+        dlogits = K.mwer_reduce_rows(rows, valid, dlogits, accumulate=dlogits is not None)
+        return (dlogits,) + (None,) * 14
+
+
+def ctc_mwer_loss(logits: Tensor, targets: Tensor, beam_width: int = 8, nbest: int = 4, topk: Optional[int] = None, blank: int = 0,
+                  ce_weight: float = 0.0, hyps=None, input_lengths: Optional[Tensor] = None, target_lengths: Optional[Tensor] = None,
+                  pad_value: int = -100, mwer_weight: float = 1.0, zero_infinity: bool = False) -> Tensor:
+    """Minimum-word-error-rate loss of a CTC head: over the n-best list of each sentence, sum_i p_i (errors_i - mean errors) with p =
+    softmax(-nll) renormalised over the list, averaged over the sentences; the result is mwer_weight * that + ce_weight * ctc_loss(logits,
+    targets) (reduction 'mean', with this zero_infinity).  It trains the head on the metric itself.  logits [B, T, C] (fp32 / bf16, NOT log-softmaxed), targets int64
+    [B, Lmax] as ctc_loss takes them.
+
+    The list is ctc_beam_decode(beam_width, topk, nbest) on the detached logits, or the caller's hyps = (ids int64 [B, n, Th], lengths
+    int64 [B, n], scores fp32 [B, n]).  nll[b, i] is the exact full-sum CTC loss of hypothesis i (the CTC lattice kernels, reduction 'none',
+    NOT the pruned beam score), errors[b, i] its edit distance to the target (engine.edit_distance), and the gradient flows through nll
+    only.  A hypothesis is left out when its beam score or its nll is not finite (an empty beam slot, an infeasible labelling) or when it
+    has more than 255 labels (the CTC envelope); a sentence without a hypothesis contributes 0.  With nbest = 1 the loss and its gradient
+    are 0.
+
+    Cost: the logits are expanded to [B * n, T, C], so the step holds n copies of the logits and of their gradient: nothing for a 41-class
+    phoneme head, about 1.6 GB of fp32 gradient at B = 32, n = 8, 32 x 50258.  Nothing waits for the host (graph-capturable); the whole
+    loss is one autograd node (CtcMwerLoss), so one gradient reaches the logits."""
+    assert logits.dim() == 3 and targets.dim() == 2 and targets.dtype == torch.int64
+    B, T, Cn = logits.shape
+    if logits.stride(-1) != 1 or not logits.is_contiguous():
+        logits = logits.contiguous()
+    if targets.shape[1] > 0 and targets.stride(1) != 1:
+        targets = targets.contiguous()
+    with torch.no_grad():
+        if hyps is None:
+            ids, lengths, scores = ctc_beam_decode(logits.detach(), input_lengths, blank, beam_width, topk, nbest, pad_value)
+        else:
+            ids, lengths, scores = hyps
+        n, Th = ids.shape[1], ids.shape[2]
+        errors = edit_distance(targets, ids, target_lengths, lengths, pad_value)
+        W = min(Th, 255)                                  # the host decides by the column count; a longer hypothesis is left out by its length
+        hyp_targets = ids[:, :, :W].reshape(B * n, W)
+        hyp_lengths = lengths.clamp(0, W).reshape(B * n)
+        hyp_frames = None if input_lengths is None else input_lengths.repeat_interleave(n, output_size=B * n)
+        scores = scores.to(torch.float32).contiguous()
+        lengths = lengths.contiguous() if Th > 255 else None
+    return CtcMwerLoss.apply(logits, targets, input_lengths, target_lengths, hyp_targets, hyp_frames, hyp_lengths, errors, scores, lengths, blank,
+                             float(mwer_weight), float(ce_weight), bool(zero_infinity), pad_value)
+
+
 class HeadCrossEntropy(torch.autograd.Function):
     """loss = mean CE(Linear([LN](x)), targets) over the rows whose target != ignore_index, WITHOUT a [rows, V] tensor in either
     direction: lm_head + F.cross_entropy of models/gpt2_model.py:205-210 and the `to_words` head of the notebook CE BrainFormer, used when

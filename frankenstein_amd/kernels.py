@@ -1592,3 +1592,105 @@ def nbest_rescore(stats, trie: NbestTrie, ids: Tensor, lengths: Tensor, am: Opti
              int(has_eos), am_weight, lm_weight, length_bonus, pad, lm.data_ptr(), ids_out.data_ptr(), len_out.data_ptr(), am_out.data_ptr(),
              lm_out.data_ptr(), total.data_ptr(), order.data_ptr(), n_scored.data_ptr(), _stream())
     return lm, (ids_out, len_out, am_out, lm_out, total, order, n_scored)
+
+
+# ---- edit distance, MBR ranking and the MWER terms (csrc/editdist.hip; semantics: include/franken_hip.h) ----
+
+def edit_distance_route(La: int, Lb: int) -> int:
+    """The kernel a pair of row widths takes (fk_edit_distance_route; host-side query, no launch): EDIT_LANE with min(La, Lb) <= 64,
+    EDIT_ROWS4 up to 256, EDIT_ROWS16 up to 1024; raises outside 1 .. NBEST_MAX_T."""
+    rc = lib().fk_edit_distance_route(La, Lb)
+    _lib.check(0 if rc >= 0 else rc, "fk_edit_distance_route")
+    return rc
+
+
+def _edit_seqs(t: Tensor, lens: Optional[Tensor], what: str):
+    assert t.dim() == 3 and t.dtype == torch.int64 and t.stride(2) == 1, f"{what}: int64 [B, n, L] with unit token stride"
+    if lens is not None:
+        assert lens.dtype == torch.int64 and lens.shape == t.shape[:2] and lens.is_contiguous() and lens.device == t.device, \
+            f"{what} lengths: contiguous int64 [B, n]"
+    return t.shape
+
+
+def _edit_ld(t: Tensor) -> Tuple[int, int]:
+    """(batch stride, sequence stride) of int64 [B, n, L]; a dimension of one element may carry any stride, so it gets the dense one"""
+    B, n, L = t.shape
+    ldh = t.stride(1) if n > 1 else max(t.stride(1), L)
+    return (t.stride(0) if B > 1 else max(t.stride(0), (n - 1) * ldh + L)), ldh
+
+
+def edit_distance(a: Tensor, a_lengths: Optional[Tensor], b: Tensor, b_lengths: Optional[Tensor], pad_value: int = -100,
+                  want_lengths: bool = False):
+    """a int64 [B, n_a, La] (n_a = n or 1: the group's reference), b int64 [B, n, Lb], any batch and sequence stride; lengths int64 or None
+    (a sequence ends at its first `pad_value`) -> dist int32 [B, n], and with want_lengths the measured lengths of a, int32 [B, n_a]
+    (fk_edit_distance)."""
+    B, n_a, La = _edit_seqs(a, a_lengths, "a")
+    Bb, n, Lb = _edit_seqs(b, b_lengths, "b")
+    assert B == Bb and a.device == b.device
+    dist = torch.empty((B, n), dtype=torch.int32, device=b.device)
+    alen_out = torch.empty((B, n_a), dtype=torch.int32, device=b.device) if want_lengths else None
+    with _timed("edit_distance"):
+        call("fk_edit_distance", a.data_ptr(), *_edit_ld(a), _ptr(a_lengths), n_a, La, b.data_ptr(), *_edit_ld(b), _ptr(b_lengths), Lb, B, n,
+             pad_value, dist.data_ptr(), _ptr(alen_out), _stream())
+    return (dist, alen_out) if want_lengths else dist
+
+
+def nbest_pairwise_distance(ids: Tensor, lengths: Tensor, scores: Optional[Tensor]) -> Tensor:
+    """All pairwise distances inside every sentence's list -> int32 [B, n, n], -1 in the row and column of a hypothesis whose score is not
+    finite (fk_nbest_pairwise_distance)."""
+    B, n, T = _nbest_ids(ids, lengths, scores)
+    dist = torch.empty((B, n, n), dtype=torch.int32, device=ids.device)
+    with _timed("nbest_pairwise_distance"):
+        call("fk_nbest_pairwise_distance", ids.data_ptr(), *_edit_ld(ids), lengths.data_ptr(), _ptr(scores), B, n, T, dist.data_ptr(), _stream())
+    return dist
+
+
+def mbr_rank(dist: Tensor, ids: Tensor, lengths: Tensor, scores: Tensor, scale: float = 1.0, pad: int = -100):
+    """dist int32 [B, n, n] of nbest_pairwise_distance -> (risk fp32 [B, n] in input order, ranked) with ranked = (ids [B, n, T] padded with
+    `pad`, lengths, scores, risk, order int64 [B, n], n_valid int64 [B]) in the order of ascending expected distance (fk_mbr_rank)."""
+    B, n, T = _nbest_ids(ids, lengths, scores)
+    assert scores is not None and dist.dtype == torch.int32 and dist.shape == (B, n, n) and dist.is_contiguous()
+    dev = ids.device
+    risk, sc_out, risk_out = (torch.empty((B, n), dtype=torch.float32, device=dev) for _ in range(3))
+    ids_out = torch.empty((B, n, T), dtype=torch.int64, device=dev)
+    len_out, order = (torch.empty((B, n), dtype=torch.int64, device=dev) for _ in range(2))
+    n_valid = torch.empty(B, dtype=torch.int64, device=dev)
+    with _timed("mbr_rank"):
+        call("fk_mbr_rank", dist.data_ptr(), scores.data_ptr(), float(scale), ids.data_ptr(), *_edit_ld(ids), lengths.data_ptr(), B, n, T,
+             pad, risk.data_ptr(), ids_out.data_ptr(), len_out.data_ptr(), sc_out.data_ptr(), risk_out.data_ptr(), order.data_ptr(),
+             n_valid.data_ptr(), _stream())
+    return risk, (ids_out, len_out, sc_out, risk_out, order, n_valid)
+
+
+def mwer_combine(nll: Tensor, errors: Tensor, scores: Optional[Tensor] = None, lengths: Optional[Tensor] = None, max_len: int = 255):
+    """nll fp32 [B, n], errors int32 [B, n], scores fp32 [B, n] / lengths int64 [B, n] or None -> (loss fp32 [B], coef fp32 [B, n] = d loss /
+    d nll, count fp32 [1] = the sentences with a valid hypothesis, valid uint8 [B, n]) (fk_mwer_combine)."""
+    assert nll.dim() == 2 and nll.dtype == torch.float32 and nll.is_contiguous()
+    B, n = nll.shape
+    assert errors.dtype == torch.int32 and errors.shape == (B, n) and errors.is_contiguous()
+    assert scores is None or (scores.dtype == torch.float32 and scores.shape == (B, n) and scores.is_contiguous())
+    assert lengths is None or (lengths.dtype == torch.int64 and lengths.shape == (B, n) and lengths.is_contiguous())
+    dev = nll.device
+    loss = torch.empty(B, dtype=torch.float32, device=dev)
+    coef = torch.empty((B, n), dtype=torch.float32, device=dev)
+    count = torch.empty(1, dtype=torch.float32, device=dev)
+    valid = torch.empty((B, n), dtype=torch.uint8, device=dev)
+    with _timed("mwer_combine"):
+        call("fk_mwer_combine", nll.data_ptr(), errors.data_ptr(), _ptr(scores), _ptr(lengths), max_len, B, n, loss.data_ptr(), coef.data_ptr(),
+             count.data_ptr(), valid.data_ptr(), _stream())
+    return loss, coef, count, valid
+
+
+def mwer_reduce_rows(rows: Tensor, valid: Tensor, out: Optional[Tensor] = None, accumulate: bool = False) -> Tensor:
+    """rows [B * n, ...] (fp32 / bf16, contiguous: the gradient of logits expanded n times), valid uint8 [B, n] -> out [B, ...]: the valid
+    rows of every sentence added in a fixed order, on top of `out` with accumulate (fk_mwer_reduce_rows).  An invalid row is never read."""
+    B, n = valid.shape
+    assert valid.dtype == torch.uint8 and valid.is_contiguous() and rows.is_contiguous() and rows.shape[0] == B * n
+    if out is None:
+        assert not accumulate
+        out = torch.empty((B, *rows.shape[1:]), dtype=rows.dtype, device=rows.device)
+    assert out.is_contiguous() and out.dtype == rows.dtype and out.numel() * n == rows.numel()
+    with _timed("mwer_reduce_rows"):
+        call("fk_mwer_reduce_rows", rows.data_ptr(), valid.data_ptr(), out.data_ptr(), B, n, rows.numel() // (B * n), int(accumulate), fk_dtype(rows),
+             _stream())
+    return out

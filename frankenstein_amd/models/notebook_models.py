@@ -67,14 +67,23 @@ class BrainFormerCTC(_FileBrainFormer):
     phoneme head gets a language model at all; same forms, the scores being the fused totals.  With ngram= AND lm= the fused search fills
     the whole beam, the GPT rescores it with the PURE CTC score as its acoustic score (the n-gram only decides which hypotheses reach the
     list; its own score is not added a second time), and the first k of the GPT's order come back.
-    utils.metrics.token_error_rate(targets, ids) of that result is the phoneme / token error rate.
+    decode(..., beam_width=W, nbest=k, mbr=True, mbr_scale=1.0): minimum-Bayes-risk selection as the last step.  The WHOLE final list (W
+    hypotheses) of whichever path was asked for, with that path's ranking score (the CTC score, the fused total, the GPT's total), goes
+    through engine.mbr_rerank: the hypothesis with the smallest expected edit distance under softmax(mbr_scale * score) comes first.  The
+    first k of that order come back in the same forms, the scores being -risk.
+    utils.metrics.token_error_rate(targets, ids) of that result is the phoneme / token error rate; error_rate(x, targets, **decode
+    arguments) computes the same number on the device (engine.error_rate).
+    mwer_weight (constructor argument or attribute, default None = off): forward's loss becomes ctc + mwer_weight * mwer, one
+    engine.ctc_mwer_loss over the n-best list of a prefix beam search (mwer_beam = 8 wide, mwer_nbest = 4 hypotheses); the logits are expanded
+    mwer_nbest times for it (engine.ctc_mwer_loss says what that costs).
     align(x, targets): forced alignment (engine.ctc_forced_align), where in the read-out every label of a transcript or hypothesis sits and
     how confident the head is of it."""
     config = Config
     head_name = 'to_words'
 
-    def __init__(self, config: Config, blank=None):
+    def __init__(self, config: Config, blank=None, mwer_weight=None, mwer_beam=8, mwer_nbest=4):
         super().__init__(config)
+        self.mwer_weight, self.mwer_beam, self.mwer_nbest = mwer_weight, mwer_beam, mwer_nbest
         self.blank = config.output_dim - 1 if blank is None else int(blank)
         if not 0 <= self.blank < config.output_dim:
             raise ValueError(f"blank = {self.blank} outside [0, output_dim = {config.output_dim})")
@@ -83,7 +92,18 @@ class BrainFormerCTC(_FileBrainFormer):
         logits = self.features(x)
         if targets is None:
             return None, logits
-        return E.ctc_loss(logits, targets, blank=self.blank, reduction='mean', zero_infinity=True, pad_value=-100), logits
+        if self.mwer_weight is None:
+            return E.ctc_loss(logits, targets, blank=self.blank, reduction='mean', zero_infinity=True, pad_value=-100), logits
+        return E.ctc_mwer_loss(logits, targets, beam_width=self.mwer_beam, nbest=self.mwer_nbest, blank=self.blank, ce_weight=1.0, pad_value=-100,
+                               mwer_weight=self.mwer_weight, zero_infinity=True), logits
+
+    @torch.no_grad()
+    def error_rate(self, x, targets, **decode_kwargs):
+        """decode(x, **decode_kwargs), its best hypothesis against targets (int64 [B, Lmax] padded with -100) -> engine.error_rate's (rate,
+        errors, ref_lengths): the corpus error rate as a device scalar, no synchronisation"""
+        out = self.decode(x, **decode_kwargs)
+        ids, lengths = (out[0][:, 0], out[1][:, 0]) if out[0].dim() == 3 else (out[0], out[1])
+        return E.error_rate(targets, ids, hypothesis_lengths=lengths, pad_value=-100)
 
     @torch.no_grad()
     def align(self, x, targets, input_lengths=None, target_lengths=None):
@@ -95,8 +115,14 @@ class BrainFormerCTC(_FileBrainFormer):
 
     @torch.no_grad()
     def decode(self, x, beam_width=None, topk=None, nbest=1, lm=None, lm_prefix=None, lm_weight=1.0, length_bonus=0.0, eos_token_id=None,
-               am_weight=1.0, bos_token_id=50256, max_nodes=None, ngram=None, ngram_weight=1.0, ngram_bonus=0.0, ngram_eos=True):
+               am_weight=1.0, bos_token_id=50256, max_nodes=None, ngram=None, ngram_weight=1.0, ngram_bonus=0.0, ngram_eos=True, mbr=False,
+               mbr_scale=1.0):
         logits = self.features(x)
+        if mbr:
+            if beam_width is None:
+                raise ValueError("decode(mbr=True) re-ranks a beam: give a beam_width")
+            return self._decode_mbr(logits, beam_width, topk, nbest, lm, lm_prefix, lm_weight, length_bonus, eos_token_id, am_weight, bos_token_id,
+                                    max_nodes, ngram, ngram_weight, ngram_bonus, ngram_eos, mbr_scale)
         if beam_width is None:
             if lm is not None or ngram is not None:
                 raise ValueError("decode(lm=...) rescores a beam and decode(ngram=...) steers one: give a beam_width")
@@ -117,6 +143,22 @@ class BrainFormerCTC(_FileBrainFormer):
                                                            length_bonus=length_bonus, bos_token_id=bos_token_id, eos_token_id=eos_token_id,
                                                            max_nodes=max_nodes)
         return (ids[:, 0], lengths[:, 0]) if nbest == 1 else (ids[:, :nbest], lengths[:, :nbest], total[:, :nbest])
+
+    def _decode_mbr(self, logits, beam_width, topk, nbest, lm, lm_prefix, lm_weight, length_bonus, eos_token_id, am_weight, bos_token_id, max_nodes,
+                    ngram, ngram_weight, ngram_bonus, ngram_eos, mbr_scale):
+        """the whole final list of the path asked for, with that path's ranking score, through engine.mbr_rerank"""
+        if ngram is not None:
+            ids, lengths, am, _, score = E.ctc_beam_decode_lm(logits, ngram, blank=self.blank, beam_width=beam_width, topk=topk, nbest=beam_width,
+                                                              lm_weight=ngram_weight, length_bonus=ngram_bonus, use_eos=ngram_eos, pad=-100)
+        else:
+            ids, lengths, score = E.ctc_beam_decode(logits, blank=self.blank, beam_width=beam_width, topk=topk, nbest=beam_width, pad=-100)
+            am = score
+        if lm is not None:
+            ids, lengths, _, _, score, _, _ = lm.rescore_nbest(ids, lengths, am, prefix=lm_prefix, lm_weight=lm_weight, am_weight=am_weight,
+                                                               length_bonus=length_bonus, bos_token_id=bos_token_id, eos_token_id=eos_token_id,
+                                                               max_nodes=max_nodes)
+        r = E.mbr_rerank(ids, lengths, score, scale=mbr_scale, pad=-100)
+        return (r.ids[:, 0], r.lengths[:, 0]) if nbest == 1 else (r.ids[:, :nbest], r.lengths[:, :nbest], -r.risk[:, :nbest])
 
 
 class Franky(nn.Module):

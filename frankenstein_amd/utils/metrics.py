@@ -3,7 +3,10 @@
 The reference's only WER is HuggingFace ``evaluate.load("wer")`` in the Whisper notebook (notebooks/whisper_hugging_face.ipynb, the
 ``compute_metrics`` cell): 100 x (substitutions + deletions + insertions over all samples) / (reference words over all samples), words
 split on whitespace.  ``wer`` below is that definition (as a fraction); ``token_error_rate`` is the same on token-id sequences, which is
-what the parity tests use to compare decoded sequences of this build with the CPU reference ("WER 0" = identical decodes)."""
+what the parity tests use to compare decoded sequences of this build with the CPU reference ("WER 0" = identical decodes).
+
+These host functions are the yardstick.  The device versions (no copy back, no Python loop) are engine.edit_distance, engine.error_rate
+(the same corpus definition as ``_rate``), engine.nbest_oracle and engine.mbr_rerank (csrc/editdist.hip)."""
 from __future__ import annotations
 
 from typing import Iterable, Sequence

@@ -705,6 +705,55 @@ int fk_nbest_rescore(const float* row_m, const float* row_s, const float* row_t,
                      int64_t* ids_out, int64_t* lengths_out, float* am_out, float* lm_out, float* total_out, int64_t* order, int64_t* n_scored,
                      void* stream);
 
+/* ---- edit distance (csrc/editdist.hip): unit-cost Levenshtein distance on int64 ids compared by exact equality (no vocabulary; two
+ *      different int64 ids stay different), and what an error rate, a minimum-Bayes-risk (MBR) selection from an n-best list and a
+ *      minimum-word-error-rate (MWER) loss need over it.  Distances are int32, everything else fp32; no atomics, no workspace, the same bits
+ *      every run, nothing waits for the host.  tests/edit_ref.py restates all of it in Python ints / float64.
+ *   fk_edit_distance: B groups x n pairs.  a int64 [B, n_a, La] (strides ld_a_b, ld_a_h >= La) with n_a == n (pair h is a[g, h] against
+ *     b[g, h]) or n_a == 1 (the group's one sequence, the reference, meets all n); alen int64 [B, n_a] or NULL; b int64 [B, n, Lb] with its
+ *     own strides, blen int64 [B, n] or NULL.  A length is clamped into [0, L] on the device; with a NULL length a sequence ends at its first
+ *     `pad_value` or at L (the -100 convention of fk_ctc_loss_fwd).  Entries at or behind the length are never used (behind a NULL length's
+ *     first pad_value: never beyond the row).  dist int32 [B, n]; alen_out int32 [B, n_a] or NULL: the lengths of a as measured, so a rate
+ *     needs no second pass.
+ *   fk_edit_distance_route(La, Lb): the kernel a pair of row widths takes (host-side query, no launch).  One wave per pair sweeps
+ *     anti-diagonals; the sequence of the narrower array sits on the lanes: FK_EDIT_LANE one row per lane (min(La, Lb) <= 64),
+ *     FK_EDIT_ROWS4 four rows per lane (<= 256), FK_EDIT_ROWS16 sixteen (<= 1024); FK_EINVAL outside 1 .. FK_NBEST_MAX_T.
+ *   fk_nbest_pairwise_distance: ids int64 [B, n, T], lengths int64 [B, n] (clamped), scores fp32 [B, n] or NULL (all valid) -> dist int32
+ *     [B, n, n]: pairs i < j are computed once and mirrored, the diagonal is 0, and the row and the column (diagonal included) of a
+ *     hypothesis whose score is not finite (the beam search's empty slot: length 0, score -inf) hold -1.
+ *   fk_mbr_rank: over the valid j (finite score) of a sentence m = max_j scale s_j, w_j = exp(scale s_j - m), Z = sum_j w_j added in
+ *     ascending j, p_j = w_j / Z, risk_i = sum_j p_j dist[i][j] (each product rounded, added in ascending j over the valid j).  The valid
+ *     hypotheses are ranked by risk ascending, exact ties by the smaller input index (the better-scored hypothesis); the invalid ones follow
+ *     in input order with risk +inf.  risk fp32 [B, n] in INPUT order; in the new order ids_out int64 [B, n, T] (padded with `pad` behind
+ *     the length), lengths_out int64 (clamped), scores_out, risk_out fp32 [B, n], order int64 [B, n] (the input index of each place), n_valid
+ *     int64 [B].  A NaN risk leaves the order among the valid ones unspecified.  One wave per sentence.
+ *   fk_mwer_combine: nll fp32 [B, n], errors int32 [B, n]; hypothesis i of a sentence is valid when nll is finite, its score (scores fp32
+ *     [B, n] or NULL) is finite and its length (lengths int64 [B, n] or NULL) is at most max_len.  Over the valid i: p = softmax(-nll), e_mean
+ *     = the plain mean of the errors, loss[b] = sum_i p_i (e_i - e_mean), coef[b, i] = d loss[b] / d nll[b, i] = -p_i (e_i - sum_k p_k e_k);
+ *     coef = 0 for an invalid i, loss = 0 for a sentence without a valid hypothesis.  loss fp32 [B], coef fp32 [B, n], count fp32 [1] = the
+ *     sentences that have a valid hypothesis, valid uint8 [B, n] or NULL.  One launch.
+ *   fk_mwer_reduce_rows: rows [B n, row_elems] in `dtype` (the gradient of logits expanded n times), valid uint8 [B, n] -> out [B, row_elems]
+ *     in `dtype`: out[b] = (accumulate != 0 ? out[b] : 0) + the sum of rows[b n + i] over the valid i, added in ascending i in fp32.  A row
+ *     that is not valid is never read (the CTC backward of an infeasible labelling is NaN).
+ *   Envelope (FK_EINVAL beyond, no launch): 1 <= n <= FK_NBEST_MAX_HYPS, 1 <= La, Lb, T <= FK_NBEST_MAX_T, strides at least the row, a
+ *   finite scale, no NULL required pointer.                                                                                              */
+#define FK_EDIT_LANE 0
+#define FK_EDIT_ROWS4 1
+#define FK_EDIT_ROWS16 2
+int fk_edit_distance_route(int64_t La, int64_t Lb);
+int fk_edit_distance(const int64_t* a, int64_t ld_a_b, int64_t ld_a_h, const int64_t* alen, int64_t n_a, int64_t La, const int64_t* b, int64_t ld_b_b,
+                     int64_t ld_b_h, const int64_t* blen, int64_t Lb, int64_t B, int64_t n, int64_t pad_value, int32_t* dist, int32_t* alen_out,
+                     void* stream);
+int fk_nbest_pairwise_distance(const int64_t* ids, int64_t ld_ids_b, int64_t ld_ids_h, const int64_t* lengths, const float* scores, int64_t B, int64_t n,
+                               int64_t T, int32_t* dist, void* stream);
+int fk_mbr_rank(const int32_t* dist, const float* scores, float scale, const int64_t* ids, int64_t ld_ids_b, int64_t ld_ids_h, const int64_t* lengths,
+                int64_t B, int64_t n, int64_t T, int64_t pad, float* risk, int64_t* ids_out, int64_t* lengths_out, float* scores_out, float* risk_out,
+                int64_t* order, int64_t* n_valid, void* stream);
+int fk_mwer_combine(const float* nll, const int32_t* errors, const float* scores, const int64_t* lengths, int64_t max_len, int64_t B, int64_t n,
+                    float* loss, float* coef, float* count, uint8_t* valid, void* stream);
+int fk_mwer_reduce_rows(const void* rows, const uint8_t* valid, void* out, int64_t B, int64_t n, int64_t row_elems, int accumulate, int dtype,
+                        void* stream);
+
 /* ---- optimizer: torch.optim.AdamW step fused with clip_grad_value_ (utils/train_utils.py:117-119,142-143) over a
  *      flat fp32 arena: g' = clamp(g * grad_scale, -clip, clip) (clip <= 0: no clamp); p *= 1 - lr*wd;
  *      m = b1 m + (1-b1) g'; v = b2 v + (1-b2) g'^2; p -= lr/(1-b1^step) * m / (sqrt(v)/sqrt(1-b2^step) + eps).
