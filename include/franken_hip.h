@@ -280,7 +280,15 @@ int fk_attn_decode(const void* q, int64_t q_bs, const void* kv, int64_t kv_bs, i
  * Philox4x32-10 uniform keyed by (*seed; *step, b).  Writes the token to cur[b] and, if out != NULL and *step < out_cols, to out[b*out_ld + *step] (out is [B, out_cols] with row
  * stride out_ld: a reused state or one graph replay too many cannot write past it; out != NULL needs 0 < out_cols <= out_ld); the last
  * block to finish sets *step += 1 and, if pos_inc != NULL, *pos_inc += 1 (so a captured decode graph advances by itself).  logits fp32,
- * `ticket` a zero-initialised uint32 scratch word owned by the caller.  top_k = 1 is the deterministic argmax (first maximum).        */
+ * `ticket` a zero-initialised uint32 scratch word owned by the caller.  top_k = 1 is the deterministic argmax (first maximum).
+ * The draw is a pure function of (logits, temperature, top_k, *seed, *step, b), and tests/sample_ref.py restates it:
+ *   x_i = logits_i * (1.0f / temperature), both operations in fp32; the crop keeps x_i >= the k-th largest x, ties kept (top_k >= V: none);
+ *   e_i = exp(x_i - max kept x); the CDF runs in INDEX order and the token is the first index whose cumulative mass exceeds u * total;
+ *   u = (c0 >> 8) / 2^24 in [0, 1), c0 = word 0 of Philox4x32-10 with the key (seed lo, seed hi) and the counter
+ *   (step lo, step hi, b, 0x5A3C), lo / hi the 32-bit halves of *seed and *step;
+ *   an entry without mass (-inf, or a logit that underflows) is never emitted, not even where rounding leaves u * total >= the sum.
+ * The sums are fp32 (per-thread chunks of ceil(V / 1024) consecutive indices, then a scan), so a u * total within 2^-17 of the total
+ * mass of a boundary between two tokens may fall on either side of it.                                                              */
 int fk_sample_topk(const float* logits, int64_t ld, int64_t B, int64_t V, float temperature, int64_t top_k, const uint64_t* seed,
                    int64_t* step, int32_t* pos_inc, int64_t* cur, int64_t* out, int64_t out_ld, int64_t out_cols, uint32_t* ticket,
                    void* stream);

@@ -13,6 +13,7 @@ import torch
 
 import frankenstein_amd as fa
 from tests import cases as C
+from tests.sample_ref import philox4x32_10
 from tests.test_decode_gpt2_gpu import inputs as inputs_124m
 from tests.test_decode_gpt2_gpu import model, z  # noqa: F401  (module-scoped fixtures: GPT-2 124M and its golden file)
 from tests.test_kernels_gpu import close, dev, q, rnd
@@ -147,17 +148,6 @@ def test_beam_topk_ties_keep_the_lowest_ids_in_ascending_order(K):
 
 
 # =============================================================================================== 3. fk_beam_select
-def philox4x32_10(key, ctr):
-    """Philox4x32-10 (Salmon et al., SC'11) on python ints: key (k0, k1), counter (c0, c1, c2, c3) -> 4 words"""
-    k0, k1 = key
-    c = list(ctr)
-    for _ in range(10):
-        p0, p1 = 0xD2511F53 * c[0], 0xCD9E8D57 * c[2]
-        c = [((p1 >> 32) ^ c[1] ^ k0) & 0xFFFFFFFF, p1 & 0xFFFFFFFF, ((p0 >> 32) ^ c[3] ^ k1) & 0xFFFFFFFF, p0 & 0xFFFFFFFF]
-        k0, k1 = (k0 + 0x9E3779B9) & 0xFFFFFFFF, (k1 + 0xBB67AE85) & 0xFFFFFFFF
-    return c
-
-
 def test_philox_restatement_known_answers():
     """the known-answer vectors of the Random123 distribution (kat_vectors: philox4x32 10 rounds)"""
     assert philox4x32_10((0, 0), (0, 0, 0, 0)) == [0x6627E8D5, 0xE169C58D, 0xBC57AC4C, 0x9B00DBD8]

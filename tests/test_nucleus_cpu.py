@@ -2,8 +2,9 @@
 (FK_EINVAL before any launch; the pointers are small fake addresses, so every call has exactly one thing wrong with it), the host-tensor
 form of GPT._sample draws from exactly the set the rule keeps, and GPT.generate / Franky.generate refuse a top_p outside (0, 1].
 
-`nucleus_ref` is the float64 numpy restatement of the rule in include/franken_hip.h (fk_sample_topp); tests/test_nucleus_gpu.py holds the
-kernel to the same function.  It also returns the MARGIN of a case, min_i |mass_gt(i) / total - top_p| over the tokens the top-k crop keeps:
+`nucleus_ref` (tests/sample_ref.py) is the float64 numpy restatement of the rule in include/franken_hip.h (fk_sample_topp);
+tests/test_nucleus_gpu.py holds the kernel to the same function.  It also returns the MARGIN of a case,
+min_i |mass_gt(i) / total - top_p| over the tokens the top-k crop keeps:
 the header lets a token closer than 1e-4 to the boundary fall on either side, so every case first asserts a margin >= 0.02 (a condition on
 its inputs; the crafted rows below give 0.03 .. 0.08)."""
 import ctypes
@@ -13,9 +14,10 @@ import numpy as np
 import pytest
 import torch
 
+from tests.sample_ref import MIN_MARGIN, nucleus_ref  # noqa: F401  (moved there; tests/test_nucleus_gpu.py imports both from here)
+
 EINVAL = -1
 P = 4096          # a fake, 16-byte aligned "device pointer": never dereferenced by a refused call
-MIN_MARGIN = 0.02
 
 # The crafted row: six head tokens with these probabilities, the remaining .11 spread over all other tokens as one identical float.
 # mass_gt / total of the heads and the tail: 0, .30, .50, .65, .75, .83, .89
@@ -28,22 +30,6 @@ def crafted_row(V, positions, temperature, shift=0.0):
     p = np.full(V, (1.0 - sum(HEADS)) / (V - len(HEADS)), np.float64)
     p[list(positions)] = HEADS
     return (temperature * (np.log(p) + shift)).astype(np.float32)
-
-
-def nucleus_ref(logits, temperature, top_k, top_p):
-    """logits fp32 [V], one row -> (kept bool [V], margin, probs float64 [V]: the distribution renormalised over the kept tokens)"""
-    x = logits.astype(np.float64) / float(temperature)
-    V = x.size
-    in_k = np.ones(V, bool) if not top_k or top_k >= V else x >= np.sort(x)[V - top_k]                 # ties with the k-th largest stay
-    e = np.where(in_k, np.exp(x - x[in_k].max()), 0.0)
-    total = e.sum()
-    vals = np.unique(x[in_k])[::-1]                                                                   # distinct kept values, descending
-    mass = np.array([e[in_k & (x == v)].sum() for v in vals])
-    gt_of = dict(zip(vals.tolist(), (np.cumsum(mass) - mass).tolist()))                               # value -> mass of the strictly larger ones
-    mass_gt = np.array([gt_of[v] if k else np.inf for v, k in zip(x.tolist(), in_k.tolist())])
-    kept = in_k & (mass_gt < top_p * total)
-    margin = float(np.abs(mass_gt[in_k] / total - top_p).min())
-    return kept, margin, np.where(kept, e, 0.0) / e[kept].sum()
 
 
 # (top_p, top_k) -> how many of the heads stay, and whether the tail does
