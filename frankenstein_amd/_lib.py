@@ -117,6 +117,8 @@ SIGNATURES = {
     "fk_ngram_hash": (_u32, [_u32, _u32]),
     "fk_ctc_beam_search_lm": (_int, [_p, _i64, _i64, _p] + [_i64] * 8 + [_p, _i64, _i64, _p, _p, _i64, _p, _p, _i64, _i64, _f32, _f32, _int, _p, _i64, _i64,
                                      _p, _p, _p, _p, _int, _p, _sz, _p]),
+    "fk_ctc_prefix_init": (_int, [_p, _i64, _i64, _p] + [_i64] * 5 + [_p, _i64, _i64, _p, _p, _p, _p, _int, _p]),
+    "fk_ctc_prefix_score": (_int, [_p, _i64, _i64, _p, _p] + [_i64] * 6 + [_p, _p, _int, _f32, _i64, _p, _p, _p, _p, _i64, _p, _p, _p, _p, _int, _p]),
     "fk_nbest_trie": (_int, [_p, _i64, _i64, _p, _p] + [_i64] * 8 + [_p] * 8),
     "fk_nbest_trie_mask": (_int, [_p, _p, _p, _i64, _i64, _i64, _p]),
     "fk_gpt_embed_pos": (_int, [_p] * 6 + [_i64] * 6 + [_int, _p]),
@@ -146,6 +148,7 @@ VQ_CHAIN, VQ_FUSED = 0, 1                                                       
 VQ_EMA, VQ_KMEANS = 0, 1                                                              # fk_vq_codebook_update modes
 CTC_WAVE, CTC_LDS = 0, 1                                                             # fk_ctc_route
 CTC_NONE, CTC_SUM, CTC_MEAN = 0, 1, 2                                                 # fk_ctc_loss_* reductions
+CTC_PREFIX_MAX_T, CTC_PREFIX_MAX_PROMPT, CTC_PREFIX_FLOOR = 1024, 64, -1e10               # the envelope of fk_ctc_prefix_* and its finite floor
 NBEST_MAX_HYPS, NBEST_MAX_T, NBEST_MAX_NODES, NBEST_MAX_ROWS = 32, 1024, 32769, 4096         # the envelope of fk_nbest_* (csrc/rescore.hip)
 EDIT_LANE, EDIT_ROWS4, EDIT_ROWS16 = 0, 1, 2                                          # fk_edit_distance_route
 VQ_ROWS = 32                                                                          # data rows per workgroup of fk_vq_assign

@@ -30,6 +30,10 @@
 //                    tests/ctc_lm_ref.py): launch 1 as above, launch 2 the LM instantiation of ctc_beam_kernel, whose slots also carry the
 //                    LM term, the LM sum and the LM state of their prefix (in LDS); the model is a state machine over one hash table
 //
+//   fk_ctc_prefix_init / fk_ctc_prefix_score  CTC prefix scores for the candidates of the GPT beam search (joint CTC / attention decoding;
+//                    semantics: include/franken_hip.h; float64 restatement tests/ctc_prefix_ref.py): launch 1 of init as above, then one
+//                    wave per sentence / per beam row: the hypothesis' state r_n / r_b [T] in LDS, the k candidates on the lanes
+//
 // row_lse, the backward and the prune kernel share one row frame (RowFrame) and one launch (CTC_LAUNCH_ROWS: the route and the grid).
 // Device-side clamps (every access stays inside the buffers whatever the integers say): input_length into [0, T], target_length into
 // [0, Lmax] (clamp_len), a label into [0, C) and off the blank (a label equal to the blank becomes blank - 1, or 1 when the blank is
@@ -1391,6 +1395,213 @@ static int check_common(const char* fn, int dtype, bool pointers, int64_t B, int
   return FK_OK;
 }
 
+// ---- prefix scores for joint CTC / attention decoding (the rule: include/franken_hip.h; float64 restatement tests/ctc_prefix_ref.py) ----
+// One wave per row of the GPT beam search.  A hypothesis' state r_n / r_b [T] sits in LDS; the kernels recompute instead of storing every
+// candidate's state: the score of a candidate needs no recursion (psi' = logsumexp_t(phi[t] + y[t][c]), phi from the hypothesis alone), so
+// the k candidates sit on the lanes and sweep the frames with CTC_PF gathers in flight, and only the one extension the select chose
+// (pfx_extend) walks the frames in order, on one lane, from operands the wave has staged in LDS.
+constexpr int PFX_MAX_T = 1024, PFX_MAX_K = 64, PFX_MAX_W = 16, PFX_MAX_PROMPT = 64;
+constexpr int PFX_NONE = -1, PFX_BAD = -2;             // `last` of the empty hypothesis / of one that took a label outside the classes
+
+struct PfxLds { float n[PFX_MAX_T], b[PFX_MAX_T], phi[PFX_MAX_T], y[PFX_MAX_T], yb[PFX_MAX_T], lse[PFX_MAX_T]; };
+static_assert(sizeof(PfxLds) <= 32 * 1024, "ctc_prefix kernels: LDS budget");
+
+// log(e^a + e^b); two -inf give -inf, never inf - inf
+FK_DEV float lae(float a, float b) {
+  const float m = fmaxf(a, b);
+  return m == -INFINITY ? -INFINITY : m + __logf(1.0f + __expf(fminf(a, b) - m));
+}
+
+// The hypothesis in L.n / L.b (psi, last) takes label c; L.lse and L.yb hold the sentence's row_lse and y[.][blank].  Every lane calls it
+// (barriers inside).  A label outside [0, C) or equal to the blank leaves the impossible hypothesis: everything -inf, last = PFX_BAD.
+template <typename T>
+FK_DEV void pfx_extend(PfxLds& L, const T* lg, int64_t ldt, int Tg, int C, int blank, int64_t c, float& psi, int& last) {
+  const int lane = threadIdx.x;
+  const bool ok = c >= 0 && c < C && c != blank;
+  const bool same = ok && (int)c == last, empty = last == PFX_NONE;
+  const T* col = lg + (ok ? c : 0);
+  float m = -INFINITY, s = 0.0f;
+  for (int t = lane; t < Tg; t += 64) {                 // phi[0] = 0 or -inf stands for n[0] = y[0][c] or -inf
+    const float y = ok ? to_f32<T>(col[(int64_t)t * ldt]) - L.lse[t] : -INFINITY;
+    const float phi = t == 0 ? (empty ? 0.0f : -INFINITY) : (same ? L.b[t - 1] : lae(L.n[t - 1], L.b[t - 1]));
+    L.phi[t] = phi;
+    L.y[t] = y;
+    lse_push(m, s, phi + y);
+  }
+  const float M = wave_max(m);
+  const float tot = wave_sum(m > -INFINITY ? s * __expf(m - M) : 0.0f);
+  psi = M > -INFINITY ? M + logf(tot) : -INFINITY;
+  __syncthreads();
+  if (lane == 0) {
+    float n = -INFINITY, b = -INFINITY;
+#pragma unroll 4
+    for (int t = 0; t < Tg; ++t) {
+      const float nn = lae(n, L.phi[t]) + L.y[t];
+      const float bb = t ? lae(n, b) + L.yb[t] : -INFINITY;
+      L.n[t] = nn;
+      L.b[t] = bb;
+      n = nn;
+      b = bb;
+    }
+  }
+  __syncthreads();
+  last = ok ? (int)c : PFX_BAD;
+}
+
+// the state in LDS to row `row` of a state buffer [rows, 2, T]; frames behind the sentence's length get -inf, so every element is written
+FK_DEV void pfx_store(const PfxLds& L, float* st, int64_t row, int T, int Tg) {
+  float* d = st + row * 2 * T;
+  for (int t = threadIdx.x; t < T; t += 64) {
+    d[t] = t < Tg ? L.n[t] : -INFINITY;
+    d[T + t] = t < Tg ? L.b[t] : -INFINITY;
+  }
+}
+
+struct PfxInitArgs {
+  const void* logits;
+  int64_t ldb, ldt;
+  const int64_t* input_lengths;
+  const float* row_lse;
+  const int64_t* prompt;
+  int64_t prompt_ld;
+  float* st0;
+  float* psi;
+  int32_t* last;
+  int T, C, blank, W, P;
+};
+
+template <typename T>
+__global__ __launch_bounds__(64) void ctc_prefix_init_kernel(PfxInitArgs a) {
+  __shared__ PfxLds L;
+  const int lane = threadIdx.x, g = blockIdx.x;
+  const int Tg = clamp_len(a.input_lengths, g, a.T);
+  const T* lg = (const T*)a.logits + (int64_t)g * a.ldb;
+  const float* lse = a.row_lse + (int64_t)g * a.T;
+  for (int t = lane; t < Tg; t += 64) {
+    L.lse[t] = lse[t];
+    L.yb[t] = to_f32<T>(lg[(int64_t)t * a.ldt + a.blank]) - lse[t];
+    L.n[t] = -INFINITY;
+  }
+  __syncthreads();
+  if (lane == 0) {                                      // the empty hypothesis: r_b[t] = the blanks of frames 0 .. t, summed in frame order
+    float acc = 0.0f;
+    for (int t = 0; t < Tg; ++t) { acc += L.yb[t]; L.b[t] = acc; }
+  }
+  __syncthreads();
+  float psi = 0.0f;
+  int last = PFX_NONE;
+  for (int i = 0; i < a.P; ++i) pfx_extend<T>(L, lg, a.ldt, Tg, a.C, a.blank, a.prompt[(int64_t)g * a.prompt_ld + i], psi, last);
+  for (int b = 0; b < a.W; ++b) {
+    const int64_t r = (int64_t)g * a.W + b;
+    pfx_store(L, a.st0, r, a.T, Tg);
+    if (lane == 0) { a.psi[r] = psi; a.last[r] = last; }
+  }
+}
+
+struct PfxArgs {
+  const void* logits;
+  int64_t ldb, ldt;
+  const int64_t* input_lengths;
+  const float* row_lse;
+  float* top_lp;
+  const int64_t* top_id;
+  const int32_t* fin;
+  const int64_t* step;
+  const int32_t* parent_log;
+  const int64_t* tok_log;
+  float* st[2];
+  float* psi;         // [2][S W], like `last`: the halves swap with the state buffers
+  int32_t* last;
+  int64_t eos, log_rows;
+  float weight;
+  int S, T, C, blank, W, k, broadcast;
+};
+
+template <typename T>
+__global__ __launch_bounds__(64) void ctc_prefix_score_kernel(PfxArgs a) {
+  __shared__ PfxLds L;
+  const int lane = threadIdx.x, R = a.S * a.W;
+  const int g = a.broadcast ? blockIdx.x : blockIdx.x / a.W;
+  const int r = a.broadcast ? g * a.W : blockIdx.x;
+  const int64_t step = *a.step;
+  if (step < 0 || step > a.log_rows) return;
+  if (a.fin && a.fin[r]) return;                        // a finished beam: its row of top_lp stays, it carries no state
+  const int par = (int)(step & 1);
+  const bool advance = !a.broadcast && step > 0;
+  const int Tg = clamp_len(a.input_lengths, g, a.T);
+  const T* lg = (const T*)a.logits + (int64_t)g * a.ldb;
+  const float* lse = a.row_lse + (int64_t)g * a.T;
+
+  // the hypothesis this row continues: its own (first step), or the one the last select made its parent, in the other buffer
+  int src_buf = par, src_row = r;
+  int64_t tok = 0;
+  if (advance) {
+    const int64_t o = (step - 1) * R + r;
+    const int p = a.parent_log[o];
+    src_row = g * a.W + (p < 0 ? 0 : (p >= a.W ? a.W - 1 : p));
+    src_buf = par ^ 1;
+    tok = a.tok_log[o];
+  }
+  const float* sn = a.st[src_buf] + (int64_t)src_row * 2 * a.T;
+  for (int t = lane; t < Tg; t += 64) {
+    L.n[t] = sn[t];
+    L.b[t] = sn[a.T + t];
+    L.lse[t] = lse[t];
+    if (advance) L.yb[t] = to_f32<T>(lg[(int64_t)t * a.ldt + a.blank]) - lse[t];
+  }
+  float psi = a.psi[src_buf * R + src_row];
+  int last = a.last[src_buf * R + src_row];
+  __syncthreads();
+  if (advance) {
+    pfx_extend<T>(L, lg, a.ldt, Tg, a.C, a.blank, tok, psi, last);
+    pfx_store(L, a.st[par], r, a.T, Tg);
+    if (lane == 0) { a.psi[par * R + r] = psi; a.last[par * R + r] = last; }
+  }
+
+  // phi of a label other than `last` (a label equal to it reads r_b[t - 1] directly)
+  for (int t = lane; t < Tg; t += 64) L.phi[t] = t ? lae(L.n[t - 1], L.b[t - 1]) : (last == PFX_NONE ? 0.0f : -INFINITY);
+  __syncthreads();
+  if (lane >= a.k) return;
+  const int64_t o = (int64_t)blockIdx.x * a.k + lane;
+  const int64_t c = a.top_id[o];
+  float delta = FK_CTC_PREFIX_FLOOR;
+  if (Tg > 0 && psi > -INFINITY) {
+    float psi2 = -INFINITY;
+    if (a.eos >= 0 && c == a.eos) {                     // the hypothesis ends here: the probability of the whole labelling
+      psi2 = lae(L.n[Tg - 1], L.b[Tg - 1]);
+    } else if (c >= 0 && c < a.C && c != a.blank) {
+      const bool same = (int)c == last;
+      const T* col = lg + c;
+      float m = -INFINITY, s = 0.0f;
+      for (int t0 = 0; t0 < Tg; t0 += CTC_PF) {
+        T raw[CTC_PF];
+#pragma unroll
+        for (int i = 0; i < CTC_PF; ++i) raw[i] = col[(int64_t)(t0 + i < Tg ? t0 + i : Tg - 1) * a.ldt];
+        float v[CTC_PF];
+#pragma unroll
+        for (int i = 0; i < CTC_PF; ++i) {
+          const int t = t0 + i < Tg ? t0 + i : Tg - 1;
+          const float phi = same ? (t ? L.b[t - 1] : -INFINITY) : L.phi[t];
+          v[i] = t0 + i < Tg ? phi + (to_f32<T>(raw[i]) - L.lse[t]) : -INFINITY;
+        }
+        lse_push(m, s, v);
+      }
+      psi2 = m > -INFINITY ? m + logf(s) : -INFINITY;
+    }
+    if (psi2 > -INFINITY) delta = psi2 - psi;
+  }
+  a.top_lp[o] = __fadd_rn(__fmul_rn(__fsub_rn(1.0f, a.weight), a.top_lp[o]), __fmul_rn(a.weight, delta));
+}
+
+// the checks fk_ctc_prefix_init and fk_ctc_prefix_score share
+static int prefix_check(const char* fn, int dtype, bool pointers, int64_t ldb, int64_t ldt, int64_t S, int64_t T, int64_t C, int64_t blank, int64_t W) {
+  if (const int rc = check_common(fn, dtype, pointers, S, T, C, blank)) return rc;
+  FK_CHECK_ARG(T <= PFX_MAX_T && W >= 1 && W <= PFX_MAX_W && S * W < (1LL << 24), "%s: T = %lld, W = %lld, S = %lld outside the envelope (T <= %d, 1 <= W <= %d)",
+               fn, (long long)T, (long long)W, (long long)S, PFX_MAX_T, PFX_MAX_W);
+  FK_CHECK_ARG(ldt >= C && ldb >= ldt, "%s: row stride %lld below C = %lld (batch stride %lld)", fn, (long long)ldt, (long long)C, (long long)ldb);
+  return FK_OK;
+}
+
 // The argument checks, the workspace and launch 1 of fk_ctc_beam_search and fk_ctc_beam_search_lm; fills everything
 // of `a` the plain search reads.
 static int beam_front(const char* fn, const void* logits, int64_t ldb, int64_t ldt, const int64_t* input_lengths, int64_t B, int64_t T, int64_t C,
@@ -1586,6 +1797,48 @@ int fk_ctc_beam_search_lm(const void* logits, int64_t ldb, int64_t ldt, const in
   a.start_state = (int)lm_start_state; a.use_eos = use_eos != 0;
   FK_BY_DTYPE(dtype, TT, hipLaunchKernelGGL((ctc_beam_kernel<TT, true>), dim3((unsigned)B), dim3(BEAM_THREADS), 0, (hipStream_t)stream, a));
   FK_CHECK_LAUNCH("fk_ctc_beam_search_lm(recursion)");
+  return FK_OK;
+}
+
+int fk_ctc_prefix_init(const void* logits, int64_t ldb, int64_t ldt, const int64_t* input_lengths, int64_t S, int64_t T, int64_t C, int64_t blank,
+                       int64_t W, const int64_t* prompt, int64_t prompt_ld, int64_t P, float* row_lse, float* state0, float* psi, int32_t* last,
+                       int dtype, void* stream) {
+  if (const int rc = prefix_check("fk_ctc_prefix_init", dtype, logits && row_lse && state0 && psi && last, ldb, ldt, S, T, C, blank, W)) return rc;
+  FK_CHECK_ARG(P >= 0 && P <= PFX_MAX_PROMPT && (P == 0 || (prompt && prompt_ld >= P)), "fk_ctc_prefix_init: %lld prompt labels (at most %d; stride %lld)",
+               (long long)P, PFX_MAX_PROMPT, (long long)prompt_ld);
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t rows = S * T;
+  CTC_LAUNCH_ROWS(ctc_row_lse_kernel, dtype, rows, C, s, (const TT*)logits, ldb, ldt, row_lse, rows, (int)T, (int)C);
+  FK_CHECK_LAUNCH("fk_ctc_prefix_init(row_lse)");
+  PfxInitArgs a;
+  a.logits = logits; a.ldb = ldb; a.ldt = ldt; a.input_lengths = input_lengths; a.row_lse = row_lse; a.prompt = prompt; a.prompt_ld = prompt_ld;
+  a.st0 = state0; a.psi = psi; a.last = last;
+  a.T = (int)T; a.C = (int)C; a.blank = (int)blank; a.W = (int)W; a.P = (int)P;
+  FK_BY_DTYPE(dtype, TT, hipLaunchKernelGGL((ctc_prefix_init_kernel<TT>), dim3((unsigned)S), dim3(64), 0, s, a));
+  FK_CHECK_LAUNCH("fk_ctc_prefix_init(state)");
+  return FK_OK;
+}
+
+int fk_ctc_prefix_score(const void* logits, int64_t ldb, int64_t ldt, const int64_t* input_lengths, const float* row_lse, int64_t S, int64_t T,
+                        int64_t C, int64_t blank, int64_t W, int64_t k, float* top_lp, const int64_t* top_id, int broadcast, float weight,
+                        int64_t eos, const int32_t* fin, const int64_t* step, const int32_t* parent_log, const int64_t* tok_log, int64_t log_rows,
+                        float* state0, float* state1, float* psi, int32_t* last, int dtype, void* stream) {
+  if (const int rc = prefix_check("fk_ctc_prefix_score", dtype,
+                                  logits && row_lse && top_lp && top_id && step && parent_log && tok_log && state0 && state1 && psi && last, ldb, ldt, S,
+                                  T, C, blank, W))
+    return rc;
+  FK_CHECK_ARG(k >= 1 && k <= PFX_MAX_K, "fk_ctc_prefix_score: k = %lld outside the envelope (1 .. %d candidates, one wave)", (long long)k, PFX_MAX_K);
+  FK_CHECK_ARG(weight >= 0.0f && weight <= 1.0f, "fk_ctc_prefix_score: weight = %g outside [0, 1]", (double)weight);
+  FK_CHECK_ARG(log_rows >= 1 && state0 != state1, "fk_ctc_prefix_score: log_rows = %lld, or one buffer for both states", (long long)log_rows);
+  FK_CHECK_ARG(eos < 0 || fin, "fk_ctc_prefix_score: an end-of-text id needs the finished flags");
+  PfxArgs a;
+  a.logits = logits; a.ldb = ldb; a.ldt = ldt; a.input_lengths = input_lengths; a.row_lse = row_lse; a.top_lp = top_lp; a.top_id = top_id;
+  a.fin = fin; a.step = step; a.parent_log = parent_log; a.tok_log = tok_log; a.st[0] = state0; a.st[1] = state1; a.psi = psi; a.last = last;
+  a.eos = eos; a.log_rows = log_rows; a.weight = weight;
+  a.S = (int)S; a.T = (int)T; a.C = (int)C; a.blank = (int)blank; a.W = (int)W; a.k = (int)k; a.broadcast = broadcast != 0;
+  const dim3 grid((unsigned)(broadcast ? S : S * W));
+  FK_BY_DTYPE(dtype, TT, hipLaunchKernelGGL((ctc_prefix_score_kernel<TT>), grid, dim3(64), 0, (hipStream_t)stream, a));
+  FK_CHECK_LAUNCH("fk_ctc_prefix_score");
   return FK_OK;
 }
 

@@ -1325,6 +1325,65 @@ def ctc_beam_search_lm(logits: Tensor, lm, input_lengths: Optional[Tensor] = Non
     return ids, lengths, am, lms, total
 
 
+# ------------------------------------------------------------------------------------------- joint CTC / attention decoding
+CTC_PREFIX_MAX_T, CTC_PREFIX_MAX_PROMPT, CTC_PREFIX_FLOOR = _lib.CTC_PREFIX_MAX_T, _lib.CTC_PREFIX_MAX_PROMPT, _lib.CTC_PREFIX_FLOOR
+
+
+class CtcPrefixState:
+    """Device-side state of the CTC prefix scorer inside a beam search of S sentences x `width` beams (fk_ctc_prefix_* in
+    include/franken_hip.h has the rule): the logits [S, T, C] of the frame-synchronous head (kept, not copied), row_lse [S, T], the two
+    state buffers st[0] / st[1] fp32 [S * width, 2, T] (r_n, then r_b) that swap by the parity of the step, psi fp32 and last int32
+    [2, S * width] whose halves swap with them, the clamped-on-device lengths, the blank and the weight of the CTC term."""
+    __slots__ = ("logits", "row_lse", "st", "psi", "last", "lengths", "blank", "weight", "width")
+
+
+def ctc_prefix_init(logits: Tensor, width: int, weight: float, blank: Optional[int] = None, input_lengths: Optional[Tensor] = None,
+                    prompt: Optional[Tensor] = None) -> CtcPrefixState:
+    """row_lse and the state of every row of a beam search before its first step: the empty hypothesis, advanced by the labels in
+    `prompt` (int64 [S, P], None: none).  logits [S, T, C] fp32 / bf16, unit column stride, any row and batch stride; blank None: C - 1.
+    The state buffers come from torch.empty: the kernels write every element before they read it."""
+    assert logits.dim() == 3 and logits.stride(2) == 1 and logits.dtype in (torch.float32, torch.bfloat16)
+    S, T, Cn = logits.shape
+    dev = logits.device
+    st = CtcPrefixState()
+    st.logits, st.width, st.weight, st.blank = logits, int(width), float(weight), Cn - 1 if blank is None else int(blank)
+    st.lengths = _ctc_lengths(input_lengths, S, dev)
+    R = S * st.width
+    st.row_lse = torch.empty((S, T), dtype=torch.float32, device=dev)
+    st.st = (torch.empty((R, 2, T), dtype=torch.float32, device=dev), torch.empty((R, 2, T), dtype=torch.float32, device=dev))
+    st.psi = torch.empty((2, R), dtype=torch.float32, device=dev)
+    st.last = torch.empty((2, R), dtype=torch.int32, device=dev)
+    P = 0
+    if prompt is not None:
+        assert prompt.dtype == torch.int64 and prompt.dim() == 2 and prompt.shape[0] == S and prompt.device == dev
+        prompt = prompt.contiguous()
+        P = prompt.shape[1]
+    call("fk_ctc_prefix_init", logits.data_ptr(), logits.stride(0), logits.stride(1), _ptr(st.lengths), S, T, Cn, st.blank, st.width,
+         _ptr(prompt) if P else None, P, P, st.row_lse.data_ptr(), st.st[0].data_ptr(), st.psi.data_ptr(), st.last.data_ptr(), fk_dtype(logits),
+         _stream())
+    return st
+
+
+def ctc_prefix_score_(top_lp: Tensor, top_id: Tensor, state: CtcPrefixState, beam_state: BeamState, broadcast: bool = False) -> Tensor:
+    """top_lp <- (1 - weight) * top_lp + weight * (psi(h c) - psi(h)) for the k candidates of every row, in place, one launch between
+    beam_topk and beam_select* (fk_ctc_prefix_score).  At beam_state.step > 0 every row's state first follows the parent and the token the
+    last select logged; rows of finished beams (beam_state.fin) stay as they are.  top_lp / top_id [S * W, k], or [S, k] with
+    broadcast=True (the first step: nothing advances)."""
+    S, T, Cn = state.logits.shape
+    W, k = state.width, top_lp.shape[1]
+    assert beam_state.width == W and beam_state.groups == S
+    assert top_lp.dtype == torch.float32 and top_id.dtype == torch.int64 and top_lp.is_contiguous() and top_id.is_contiguous()
+    assert top_lp.shape == top_id.shape and top_lp.shape[0] == (S if broadcast else S * W)
+    fin = getattr(beam_state, "fin", None)
+    eos = getattr(beam_state, "eos", None)
+    call("fk_ctc_prefix_score", state.logits.data_ptr(), state.logits.stride(0), state.logits.stride(1), _ptr(state.lengths),
+         state.row_lse.data_ptr(), S, T, Cn, state.blank, W, k, top_lp.data_ptr(), top_id.data_ptr(), int(bool(broadcast)), state.weight,
+         -1 if eos is None else int(eos), _ptr(fin), beam_state.step.data_ptr(), beam_state.parent_log.data_ptr(), beam_state.tok_log.data_ptr(),
+         beam_state.parent_log.shape[0], state.st[0].data_ptr(), state.st[1].data_ptr(), state.psi.data_ptr(), state.last.data_ptr(),
+         fk_dtype(state.logits), _stream())
+    return top_lp
+
+
 class CeChunkState:
     """per-row running statistics of the chunked cross entropy (fk_ce_chunk_*)"""
 

@@ -184,6 +184,74 @@ def _beam_step_host(top_lp, top_ix, picks, scores, lens, fin, eos, inv_lenpow):
     return parent, new_tok, raw.reshape(-1)[order], L.reshape(-1)[order].to(lens.dtype), new_fin
 
 
+class _CtcPrefixHost:
+    """The CTC prefix scorer of joint decoding for the W beams of ONE sentence as torch ops: the rule of fk_ctc_prefix_init /
+    fk_ctc_prefix_score (include/franken_hip.h) in fp32 on the logits' device, for the re-forward paths of generate_beam_search.
+    State: r_n / r_b [W, Tg], psi [W], last [W] (-1: the empty hypothesis, -2: one that took a label outside the classes)."""
+    FLOOR = K.CTC_PREFIX_FLOOR
+
+    def __init__(self, logits, Tg, blank, weight, eos, W, prompt_labels=()):
+        T, self.C = logits.shape
+        self.Tg = max(0, min(int(Tg), T))
+        self.blank, self.eos = int(blank), -1 if eos is None else int(eos)
+        self.w = torch.tensor(float(weight), dtype=torch.float32, device=logits.device)
+        self.y = torch.log_softmax(logits[:self.Tg].float(), dim=-1)
+        dev = logits.device
+        self.r_n = torch.full((W, self.Tg), -math.inf, device=dev)
+        self.r_b = torch.cumsum(self.y[:, self.blank], 0)[None, :].repeat(W, 1)
+        self.psi = torch.zeros(W, device=dev)
+        self.last = torch.full((W,), -1, dtype=torch.int64, device=dev)
+        for c in prompt_labels:
+            self.advance(torch.arange(W, device=dev), torch.full((W,), int(c), dtype=torch.int64, device=dev))
+
+    def _valid(self, c):
+        return (c >= 0) & (c < self.C) & (c != self.blank)
+
+    def _phi(self, same):
+        """phi [n, Tg] of n (hypothesis, label) pairs laid out like `same` [W, m]: column 0 stands for n[0] (0: the empty hypothesis)"""
+        diff = torch.logaddexp(self.r_n, self.r_b)
+        first = torch.where(self.last == -1, 0.0, -math.inf)[:, None, None].expand(-1, same.shape[1], 1)
+        rest = torch.where(same[:, :, None], self.r_b[:, None, :-1], diff[:, None, :-1])
+        return torch.cat((first, rest), dim=2)                                   # [W, m, Tg]
+
+    def score(self, top_lp, top_id, fin=None):
+        """(1 - weight) * top_lp + weight * delta for top_lp / top_id [W, k]; rows of finished beams come back as they are"""
+        if self.Tg == 0:
+            delta = torch.full_like(top_lp, self.FLOOR)
+        else:
+            ok = self._valid(top_id)
+            ycol = self.y[:, torch.where(ok, top_id, 0)].permute(1, 2, 0)        # [W, k, Tg]
+            ycol = torch.where(ok[:, :, None], ycol, -math.inf)
+            psi2 = torch.logsumexp(self._phi(top_id == self.last[:, None]) + ycol, dim=2)
+            if self.eos >= 0:
+                psi2 = torch.where(top_id == self.eos, torch.logaddexp(self.r_n[:, -1], self.r_b[:, -1])[:, None], psi2)
+            good = torch.isfinite(psi2) & torch.isfinite(self.psi)[:, None]
+            delta = torch.where(good, psi2 - torch.where(good, self.psi[:, None], 0.0), self.FLOOR)
+        out = (1.0 - self.w) * top_lp.float() + self.w * delta
+        return out if fin is None else torch.where(fin.bool()[:, None], top_lp.float(), out)
+
+    def advance(self, parent, tok):
+        """row b becomes extend(state of row parent[b], tok[b])"""
+        r_n, r_b, last = self.r_n[parent], self.r_b[parent], self.last[parent]
+        ok = self._valid(tok)
+        self.r_n, self.r_b, self.last = r_n, r_b, last                           # _phi reads the parents' states
+        phi = self._phi((tok == last)[:, None])[:, 0]                            # [W, Tg]
+        y = torch.where(ok[:, None], self.y[:, torch.where(ok, tok, 0)].t(), -math.inf)
+        n, b = torch.full_like(r_n, -math.inf), torch.full_like(r_b, -math.inf)
+        if self.Tg > 0:
+            self.psi = torch.logsumexp(phi + y, dim=1)
+            n_prev, b_prev = phi[:, 0] + y[:, 0], b[:, 0]
+            n[:, 0] = n_prev
+            for t in range(1, self.Tg):
+                n_new = torch.logaddexp(n_prev, phi[:, t]) + y[:, t]
+                b_prev = torch.logaddexp(n_prev, b_prev) + self.y[t, self.blank]
+                n_prev = n_new
+                n[:, t], b[:, t] = n_prev, b_prev
+        else:
+            self.psi = torch.full_like(self.psi, -math.inf)
+        self.r_n, self.r_b, self.last = n, b, torch.where(ok, tok, -2)
+
+
 @dataclass
 class GPTConfig:
     block_size: int = 1024
@@ -471,6 +539,65 @@ class GPT(nn.Module):
         return dict(repetition_penalty=p, no_repeat_ngram_size=n, min_new_tokens=m, eos_token_id=None if eos_token_id is None else int(eos_token_id))
 
     @staticmethod
+    def _check_ctc(ctc_logits, ctc_weight, ctc_blank, ctc_input_lengths, ctc_from_prompt, idx):
+        """The arguments of joint CTC / attention decoding, checked before any GPU work.  Off (no logits, or weight 0): None comes back and the
+        calls are those without them; otherwise dict(logits [S, T, C] with unit column stride, weight, blank, lengths int64 [S] or None,
+        from_prompt).  0 <= ctc_weight <= 1, the logits [S, T, C] ([T, C] with one sentence) in fp32 or bf16 with C >= 2, 0 <= blank < C,
+        ctc_input_lengths one integer per sentence, 0 <= ctc_from_prompt <= the prompt's length."""
+        try:
+            w = float(ctc_weight)
+        except (TypeError, ValueError):
+            raise ValueError(f"ctc_weight must be a number in [0, 1], got {ctc_weight!r}") from None
+        if not 0.0 <= w <= 1.0:                                          # NaN fails both comparisons
+            raise ValueError(f"ctc_weight must lie in [0, 1], got {ctc_weight!r}")
+        if ctc_logits is None:
+            if w != 0.0:
+                raise ValueError("ctc_weight > 0 needs ctc_logits")
+            return None
+        S, t0 = idx.shape
+        lg = ctc_logits[None] if ctc_logits.dim() == 2 else ctc_logits
+        if lg.dim() != 3 or lg.shape[0] != S or lg.shape[1] < 1 or lg.shape[2] < 2:
+            raise ValueError(f"ctc_logits must be [S = {S}, T >= 1, C >= 2] (or [T, C] for one sentence), got {tuple(ctc_logits.shape)}")
+        if lg.dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError(f"ctc_logits must be fp32 or bf16, got {lg.dtype}")
+        Cn = lg.shape[2]
+        blank = Cn - 1 if ctc_blank is None else ctc_blank
+        if isinstance(blank, bool) or not isinstance(blank, numbers.Integral) or not 0 <= blank < Cn:
+            raise ValueError(f"ctc_blank must be a class in [0, {Cn}), got {ctc_blank!r}")
+        if isinstance(ctc_from_prompt, bool) or not isinstance(ctc_from_prompt, numbers.Integral) or not 0 <= ctc_from_prompt <= t0:
+            raise ValueError(f"ctc_from_prompt must be an integer in [0, {t0}] (the prompt's length), got {ctc_from_prompt!r}")
+        lengths = ctc_input_lengths
+        if lengths is not None:
+            lengths = torch.as_tensor(lengths)
+            if lengths.dim() != 1 or lengths.numel() != S or lengths.dtype.is_floating_point or lengths.dtype == torch.bool:
+                raise ValueError(f"ctc_input_lengths must hold one integer per sentence ({S}), got {tuple(lengths.shape)} {lengths.dtype}")
+            lengths = lengths.to(device=lg.device, dtype=torch.int64)
+        if w == 0.0:
+            return None
+        return dict(logits=lg if lg.stride(2) == 1 else lg.contiguous(), weight=w, blank=int(blank), lengths=lengths, from_prompt=int(ctc_from_prompt))
+
+    @staticmethod
+    def _ctc_kwargs_of(ctc, g):
+        """the ctc_* arguments of generate_beam_search for sentence g alone"""
+        return dict(ctc_logits=ctc["logits"][g:g + 1], ctc_weight=ctc["weight"], ctc_blank=ctc["blank"], ctc_from_prompt=ctc["from_prompt"],
+                    ctc_input_lengths=None if ctc["lengths"] is None else ctc["lengths"][g:g + 1])
+
+    @staticmethod
+    def _ctc_host(ctc, g, idx, W, eos):
+        """the torch form of the prefix scorer (_CtcPrefixHost) for the W beams of sentence g, advanced by the prompt's labels"""
+        lg = ctc["logits"][g]
+        P = ctc["from_prompt"]
+        return _CtcPrefixHost(lg, lg.shape[0] if ctc["lengths"] is None else int(ctc["lengths"][g]), ctc["blank"], ctc["weight"], eos, W,
+                              idx[g, idx.shape[1] - P:].tolist() if P else ())
+
+    @staticmethod
+    def _gumbel_picks(top_lp, W):
+        """W entries per row without replacement with probability ~ exp(top_lp), by Gumbel keys like fk_beam_select (torch.multinomial refuses
+        rows with fewer than W entries of non-zero probability, which the finite floor of the CTC term can produce) -> int64 [rows, W]"""
+        u = torch.rand(top_lp.shape, device=top_lp.device).clamp_(1e-7, 1.0 - 1e-7)
+        return (top_lp.float() - torch.log(-torch.log(u))).topk(W, dim=1).indices
+
+    @staticmethod
     def _device_rules(rules, prompt, steps, width=None):
         """the device-side state (K.LogitRules) of the checked rules `rules` (_check_logit_rules), or None"""
         if rules is None:
@@ -710,7 +837,8 @@ class GPT(nn.Module):
 
     @torch.no_grad()
     def generate_beam_search(self, idx, max_new_tokens, prefix, temperature=1.0, topk=20, beam_width=5, use_cache=False, use_graph=None, seeds=None,
-                             eos_token_id=None, length_penalty=0.0, check_every=8, repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0):
+                             eos_token_id=None, length_penalty=0.0, check_every=8, repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0,
+                             ctc_logits=None, ctc_weight=0.0, ctc_blank=None, ctc_input_lengths=None, ctc_from_prompt=0):
         """Stochastic beam search of the reference (models/gpt2_model.py:355-416): every step each of the `beam_width` beams draws
         `beam_width` continuations WITHOUT replacement from its `topk` most likely tokens, the `beam_width` best-scoring
         (cumulative log-probability) of the beam_width^2 candidates survive; returns the best beam's ids.
@@ -730,15 +858,27 @@ class GPT(nn.Module):
         repetition_penalty / no_repeat_ngram_size / min_new_tokens: the rules of generate (_apply_logit_rules) on every beam's own history,
         applied to its logits before the temperature and the log-softmax; the end-of-text id is exempt from the first two (a deliberate
         departure from the usual implementations).  On the caches it is one more launch in front of K.beam_topk, which also carries the
-        histories along with the beams (K.logit_rules_).  All three at their defaults: off, the calls are those without them."""
+        histories along with the beams (K.logit_rules_).  All three at their defaults: off, the calls are those without them.
+        ctc_logits / ctc_weight: one-pass joint CTC / attention decoding.  ctc_logits [S, T, C] (or [T, C] for one sentence; fp32 / bf16, NOT
+        log-softmaxed) are the frames of a frame-synchronous CTC head over the same token ids; every candidate c of every beam h is then
+        ranked by (1 - ctc_weight) * log p(c | h) + ctc_weight * (psi(h c) - psi(h)), psi = the CTC prefix log-probability (the rule:
+        fk_ctc_prefix_score in include/franken_hip.h), and the draw, the selection and the scores run on these joint values.  ctc_blank
+        (default C - 1), ctc_input_lengths int64 [S] (default T each), ctc_from_prompt = P: the last P prompt tokens are labels of the CTC
+        transcript too (a target that begins with the start token).  On the caches it is one launch between K.beam_topk and the select
+        (K.ctc_prefix_score_; T <= 1024, P <= 64); the re-forward paths apply the same rule as torch ops (_CtcPrefixHost) and draw by
+        Gumbel keys.  ctc_logits None or ctc_weight 0: off, the calls and launches are those without them."""
         if topk is None:
             topk = 2 * beam_width
+        ctc = self._check_ctc(ctc_logits, ctc_weight, ctc_blank, ctc_input_lengths, ctc_from_prompt, idx)
         rules = self._check_logit_rules(repetition_penalty, no_repeat_ngram_size, min_new_tokens, eos_token_id, self.config.vocab_size,
                                         idx.shape[1] + max_new_tokens, topk)
         self.eval()
         total = (0 if prefix is None else prefix.shape[1]) + idx.shape[1] + max_new_tokens
         in_envelope = (use_cache and idx.is_cuda and max_new_tokens > 0 and total <= self.config.block_size
                        and 1 <= beam_width <= K.BEAM_MAX_WIDTH and beam_width <= topk <= min(K.BEAM_MAX_TOPK, self.config.vocab_size))
+        if ctc is not None:
+            in_envelope = (in_envelope and ctc["logits"].is_cuda and ctc["logits"].shape[1] <= K.CTC_PREFIX_MAX_T
+                           and ctc["from_prompt"] <= K.CTC_PREFIX_MAX_PROMPT)
         eos_mode = eos_token_id is not None or length_penalty != 0.0
         eos = None if eos_token_id is None else int(eos_token_id)
         if eos_mode:
@@ -747,17 +887,20 @@ class GPT(nn.Module):
             check_every = int(check_every)
         if in_envelope:
             return self._beam_search_cached(idx, max_new_tokens, prefix, temperature, topk, beam_width, use_graph, seeds, eos,
-                                            float(length_penalty), check_every, eos_mode, rules)
+                                            float(length_penalty), check_every, eos_mode, rules, ctc)
         if eos_mode:
-            return self._beam_search_host_eos(idx, max_new_tokens, prefix, temperature, topk, beam_width, eos, float(length_penalty), check_every, rules)
+            return self._beam_search_host_eos(idx, max_new_tokens, prefix, temperature, topk, beam_width, eos, float(length_penalty), check_every, rules,
+                                              ctc)
         S = idx.shape[0]
         if S > 1:
             kw = {} if rules is None else {k: v for k, v in rules.items() if k != "eos_token_id"}
             return torch.stack([self.generate_beam_search(idx[g:g + 1], max_new_tokens, None if prefix is None else prefix[g:g + 1], temperature,
-                                                          topk, beam_width, **kw) for g in range(S)])
+                                                          topk, beam_width, **kw, **({} if ctc is None else self._ctc_kwargs_of(ctc, g)))
+                                for g in range(S)])
         beams = idx.repeat(beam_width, 1)
         scores = torch.zeros(beam_width, device=idx.device)
         prefix = prefix.expand(beam_width, -1, -1)
+        joint = None if ctc is None else self._ctc_host(ctc, 0, idx, beam_width, None)
         for it in range(max_new_tokens):
             _, logits = self(beams, prefix=prefix.contiguous())
             last = logits[:, -1, :].float()
@@ -765,18 +908,26 @@ class GPT(nn.Module):
                 last = self._apply_logit_rules(last, beams, it, **rules)
             logp = torch.log_softmax(last / temperature, dim=-1)
             top_lp, top_ix = logp.topk(topk, dim=-1)
-            picks = torch.multinomial(top_lp.exp(), beam_width, replacement=False)           # [beam, beam_width] indices into top-k
+            if joint is None:
+                picks = torch.multinomial(top_lp.exp(), beam_width, replacement=False)       # [beam, beam_width] indices into top-k
+            else:
+                top_lp = joint.score(top_lp, top_ix)
+                picks = self._gumbel_picks(top_lp, beam_width)
             cand_score = (scores[:, None] + top_lp.gather(1, picks)).reshape(-1)
             cand_tok = top_ix.gather(1, picks).reshape(-1)
             cand_beam = torch.arange(beam_width, device=idx.device).repeat_interleave(beam_width)
             order = torch.sort(cand_score, descending=True, stable=True).indices[:beam_width]
             beams = torch.cat((beams[cand_beam[order]], cand_tok[order, None]), dim=1)
             scores = cand_score[order]
+            if joint is not None:
+                joint.advance(cand_beam[order], cand_tok[order])
+        if joint is not None:
+            self.last_beams, self.last_beam_scores = beams.tolist(), scores.tolist()
         return beams[scores.argmax()]
 
     @torch.no_grad()
     def _beam_search_cached(self, idx, max_new_tokens, prefix, temperature, topk, W, use_graph, seeds, eos=None, alpha=0.0, check_every=None,
-                            eos_mode=False, rules=None):
+                            eos_mode=False, rules=None, ctc=None):
         """generate_beam_search for S >= 1 sentences on per-layer caches [S * W, total, 2d] that are never reordered: row g * W + b is beam b
         of sentence g, slot b of a sentence holds the rows its beam position b wrote, the int32 ancestry table names the slot (counted
         inside the sentence, so the sentences cannot read each other's rows) of every row of every beam, and the select kernel rewrites
@@ -792,10 +943,16 @@ class GPT(nn.Module):
         included), the live count is read every `check_every` steps, and K.beam_backtrack replaces the host's walk: the ids come back
         ranked, [S, W, t0 + max_new_tokens], padded behind the steps that ran; last_beam_lengths and last_steps are set as well.
         rules (_check_logit_rules): K.logit_rules_ runs in front of both K.beam_topk calls; it follows the parents in the log of the last
-        select, so every row's history is that of the beam it now continues."""
+        select, so every row's history is that of the beam it now continues.
+        ctc (_check_ctc): K.ctc_prefix_score_ runs between both K.beam_topk calls and their select: it follows the same log, so every row's
+        CTC state is that of the beam it now continues, and rewrites top_lp with the joint values the select then draws and ranks on."""
         dev, d = idx.device, self.config.n_embd
         S, t0 = idx.shape
         lr = self._device_rules(rules, idx, max_new_tokens, width=W)
+        cs = None
+        if ctc is not None:
+            P = ctc["from_prompt"]
+            cs = K.ctc_prefix_init(ctc["logits"], W, ctc["weight"], ctc["blank"], ctc["lengths"], idx[:, t0 - P:].to(torch.int64) if P else None)
         p0 = (0 if prefix is None else prefix.shape[1]) + t0
         total = p0 + max_new_tokens
         if use_graph is None:
@@ -816,6 +973,8 @@ class GPT(nn.Module):
         if lr is not None:
             K.logit_rules_(lg0, lr, state.step, cur, state.parent_log, broadcast=True)
         K.beam_topk(lg0, temperature, topk, top_lp[:S], top_id[:S])
+        if cs is not None:
+            K.ctc_prefix_score_(top_lp[:S], top_id[:S], cs, state, broadcast=True)
         select(top_lp[:S], top_id[:S], state, cur, torch.tensor([-1], dtype=torch.int32, device=dev), broadcast=True)
         pos = torch.tensor([p0], dtype=torch.int32, device=dev)
 
@@ -824,6 +983,8 @@ class GPT(nn.Module):
             if lr is not None:
                 K.logit_rules_(lg, lr, state.step, cur, state.parent_log)
             K.beam_topk(lg, temperature, topk, top_lp, top_id)
+            if cs is not None:
+                K.ctc_prefix_score_(top_lp, top_id, cs, state)
             select(top_lp, top_id, state, cur, pos, pos_inc=pos)
 
         steps = self._run_steps(step, max_new_tokens, use_graph, state.live if eos_mode else None, check_every)
@@ -853,7 +1014,7 @@ class GPT(nn.Module):
         return torch.tensor(best[0] if S == 1 else best, dtype=idx.dtype, device=dev)
 
     @torch.no_grad()
-    def _beam_search_host_eos(self, idx, max_new_tokens, prefix, temperature, topk, W, eos, alpha, check_every, rules=None):
+    def _beam_search_host_eos(self, idx, max_new_tokens, prefix, temperature, topk, W, eos, alpha, check_every, rules=None, ctc=None):
         """The re-forward loop of generate_beam_search with the end-of-text rules (_beam_step_host), sentence by sentence; draws by
         torch.multinomial.  Sets last_beams, last_beam_scores, last_beam_lengths (best first) and last_steps like the cached search."""
         S, t0 = idx.shape
@@ -867,6 +1028,7 @@ class GPT(nn.Module):
             lens = torch.zeros(W, dtype=torch.int64, device=dev)
             fin = torch.zeros(W, dtype=torch.bool, device=dev)
             pf = None if prefix is None else prefix[g:g + 1].expand(W, -1, -1).contiguous()
+            joint = None if ctc is None else self._ctc_host(ctc, g, idx, W, eos)
             n = 0
             while n < max_new_tokens:
                 if n > 0 and n % check_every == 0 and bool(fin.all()):
@@ -878,8 +1040,14 @@ class GPT(nn.Module):
                     last = self._apply_logit_rules(last, beams, n, **rules)
                 logp = torch.log_softmax(last / temperature, dim=-1)
                 top_lp, top_ix = logp.topk(topk, dim=-1)
-                picks = torch.multinomial(top_lp.exp(), W, replacement=False)
+                if joint is None:
+                    picks = torch.multinomial(top_lp.exp(), W, replacement=False)
+                else:
+                    top_lp = joint.score(top_lp, top_ix, fin)
+                    picks = self._gumbel_picks(top_lp, W)
                 parent, tok, scores, lens, fin = _beam_step_host(top_lp, top_ix, picks, scores, lens, fin, -1 if eos is None else eos, table)
+                if joint is not None:
+                    joint.advance(parent, tok)
                 beams = torch.cat((beams[parent], tok[:, None]), dim=1)
                 n += 1
             steps = max(steps, n)

@@ -230,7 +230,7 @@ class Franky(nn.Module):
 
     @torch.no_grad()
     def generate_beam(self, x, max_new_tokens=25, temperature=1.0, topk=20, beam_width=5, eot=50256, batch_sentences=None, stop=False,
-                      length_penalty=0.0, repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0):
+                      length_penalty=0.0, repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, ctc=None, ctc_weight=0.0):
         """x: numpy [T, C].  Brain features -> prefix -> the stochastic beam search of the decoder on its key/value caches
         (GPT.generate_beam_search, use_cache=True).  Returns the best beam's ids, `eot` first.
         x: numpy [S, T, C] decodes S trials and returns ids [S, 1 + max_new_tokens]: the encoder and the search run in chunks of
@@ -240,16 +240,30 @@ class Franky(nn.Module):
         [T, C] returns the best beam trimmed behind its first generated `eot`, [S, T, C] the padded [S, 1 + max_new_tokens] and sets
         last_lengths [S].
         repetition_penalty / no_repeat_ngram_size / min_new_tokens: GPT.generate_beam_search's rules on every beam's own tokens; `eot` is
-        exempt from the penalty and the n-gram ban (see generate), min_new_tokens needs stop=True."""
+        exempt from the penalty and the n-gram ban (see generate), min_new_tokens needs stop=True.
+        ctc (a BrainFormerCTC over the same token ids) with ctc_weight > 0: one-pass joint CTC / attention decoding
+        (GPT.generate_beam_search's ctc_* arguments): ctc.features of the same chunk of trials are the frames, ctc.blank the blank, and the
+        prompt `eot` counts as the first label of the transcript, because the targets the head was trained on begin with it.  ctc None or
+        ctc_weight 0: off, the head does not run and the result is the one without the arguments."""
         rules = self._rules(repetition_penalty, no_repeat_ngram_size, min_new_tokens, eot if stop else None, max_new_tokens,
                             2 * beam_width if topk is None else topk)
+        if not 0.0 <= float(ctc_weight) <= 1.0:                              # before the encoder runs
+            raise ValueError(f"ctc_weight must lie in [0, 1], got {ctc_weight!r}")
+        if float(ctc_weight) > 0.0 and ctc is None:
+            raise ValueError("ctc_weight > 0 needs the CTC model `ctc`")
+
+        def ctc_kw(xin):                                                     # the head runs on the chunk of trials the encoder just saw
+            if ctc is None or float(ctc_weight) == 0.0:
+                return {}
+            return dict(ctc_logits=ctc.features(xin), ctc_weight=float(ctc_weight), ctc_blank=ctc.blank, ctc_from_prompt=1)
+
         eos_kw = dict(eos_token_id=eot if stop else None, length_penalty=length_penalty) if (stop or length_penalty != 0.0) else {}
         if x.ndim == 2:
             xin = torch.from_numpy(x[None]).to(self.device).float()
             prefix = self.brain_model(xin)
             ids = torch.full((1, 1), eot, dtype=torch.long, device=self.device)
             out = self.llm_model.generate_beam_search(ids, max_new_tokens, prefix, temperature=temperature, topk=topk, beam_width=beam_width,
-                                                      use_cache=True, **eos_kw, **rules)
+                                                      use_cache=True, **eos_kw, **rules, **ctc_kw(xin))
             if eos_kw:
                 self.last_lengths = torch.tensor([self.llm_model.last_beam_lengths[0]])
             return out[:1 + int(self.last_lengths[0])] if stop else out
@@ -261,7 +275,7 @@ class Franky(nn.Module):
             prefix = self.brain_model(xin)
             ids = torch.full((xin.shape[0], 1), eot, dtype=torch.long, device=self.device)
             out = self.llm_model.generate_beam_search(ids, max_new_tokens, prefix, temperature=temperature, topk=topk, beam_width=beam_width,
-                                                      use_cache=True, **eos_kw, **rules)
+                                                      use_cache=True, **eos_kw, **rules, **ctc_kw(xin))
             outs.append(out.view(xin.shape[0], -1))
             if eos_kw:
                 lens = self.llm_model.last_beam_lengths

@@ -663,6 +663,44 @@ int fk_ctc_beam_search_lm(const void* logits, int64_t ldb, int64_t ldt, const in
                           int64_t ld_ids_b, int64_t ld_ids_h, int64_t* lengths, float* am, float* lm, float* total, int dtype, void* workspace,
                           size_t workspace_bytes, void* stream);
 
+/* ---- CTC prefix scores inside the GPT beam search (csrc/ctc.hip): one-pass joint CTC / attention decoding.  Every candidate c of every
+ *      beam h of fk_beam_topk is rescored in front of fk_beam_select*:
+ *          top_lp[r][j] <- (1 - weight) * top_lp[r][j] + weight * delta(h_r, c),   delta = psi(h c) - psi(h),
+ *      psi = the CTC PREFIX log-probability (all labellings that start with the hypothesis) under logits [S, T, C] of the frame-synchronous
+ *      head, sentence g = r / W.  Float64 restatement: tests/ctc_prefix_ref.py.
+ *   y[t][c] = logits[g][t][c] - row_lse[g][t] for t < T_g = clamp(input_lengths[g], 0, T) (NULL: T).  lae = log(e^a + e^b), -inf for two -inf.
+ *   A hypothesis (the generated tokens, behind the P prompt labels fk_ctc_prefix_init was given) carries r_n[t] / r_b[t] (the alignments of
+ *   frames 0..t to it that end in a label / in the blank), psi and its last label.  Empty: r_n = -inf, r_b[t] = y[0][blank] + .. + y[t][blank]
+ *   summed in frame order, psi = 0, last = -1.
+ *   Extension by c (0 <= c < C, c != blank):  n[0] = y[0][c] if the hypothesis is empty, else -inf;  b[0] = -inf;  psi' = n[0];  for t >= 1:
+ *       phi = (c == last) ? r_b[t-1] : lae(r_n[t-1], r_b[t-1]);   n[t] = lae(n[t-1], phi) + y[t][c];   b[t] = lae(n[t-1], b[t-1]) + y[t][blank];
+ *       psi' = lae(psi', phi + y[t][c])                    (the kernels sum the T terms of psi' as one logsumexp)
+ *   and the new hypothesis has r_n = n, r_b = b, psi = psi', last = c.  A label outside [0, C) or equal to the blank gives the impossible
+ *   hypothesis (everything -inf, last = -2).
+ *   delta = psi' - psi;  for c == eos (eos >= 0; tested first, eos need not be a class): delta = lae(r_n[T_g-1], r_b[T_g-1]) - psi, the
+ *   probability of the whole labelling.  delta = FK_CTC_PREFIX_FLOOR when psi' or psi is -inf, c is the blank or outside [0, C), or T_g = 0:
+ *   finite, so nothing behind it meets an inf or a NaN.  The joint value is two fp32 multiplies and one add, (1 - weight) one fp32 subtract.
+ *   State: two buffers fp32 [S*W, 2, T] (r_n, then r_b; frames >= T_g hold -inf), psi fp32 [2][S*W], last int32 [2][S*W], the halves and the
+ *   buffers swapped by the parity of *step exactly like hist / hist2 of fk_logit_rules: at *step > 0 (and broadcast == 0) row r first becomes
+ *   extend(old[g*W + clamp(parent_log[(*step-1)*S*W + r], 0, W-1)], tok_log[(*step-1)*S*W + r]) in the buffer of *step's parity, then its k
+ *   candidates are scored; no block reads what another block of the launch writes.  broadcast != 0 is the first step: top_lp / top_id are
+ *   [S, k], row g uses the state of row g*W and nothing advances.  A row with fin[r] != 0 (fin may be NULL) is left untouched, state and
+ *   top_lp; *step < 0 or > log_rows: the launch writes nothing.  Every element of a state row is written before it is read, so the buffers
+ *   need no initialisation.
+ * fk_ctc_prefix_init: row_lse [S, T] (fk_ctc_loss_fwd's launch), then per sentence the empty hypothesis extended by prompt[g][0 .. P) (int64,
+ *   row stride prompt_ld; P = 0: none) into rows g*W .. g*W+W-1 of state0 and of the first halves of psi / last.  Two launches.
+ * fk_ctc_prefix_score: one launch, one wave per row, the k candidates on the lanes; no atomics, the same bits every run, no host read.
+ * Envelope: fp32 / bf16 logits, ldt >= C, ldb >= ldt, 1 <= T <= 1024, 1 <= k <= 64, 1 <= W <= 16, C >= 2, 0 <= blank < C, 0 <= P <= 64,
+ *   0 <= weight <= 1, eos >= 0 only with fin: FK_EINVAL beyond, no launch.                                                            */
+#define FK_CTC_PREFIX_FLOOR (-1e10f)
+int fk_ctc_prefix_init(const void* logits, int64_t ldb, int64_t ldt, const int64_t* input_lengths, int64_t S, int64_t T, int64_t C, int64_t blank,
+                       int64_t W, const int64_t* prompt, int64_t prompt_ld, int64_t P, float* row_lse, float* state0, float* psi, int32_t* last,
+                       int dtype, void* stream);
+int fk_ctc_prefix_score(const void* logits, int64_t ldb, int64_t ldt, const int64_t* input_lengths, const float* row_lse, int64_t S, int64_t T,
+                        int64_t C, int64_t blank, int64_t W, int64_t k, float* top_lp, const int64_t* top_id, int broadcast, float weight,
+                        int64_t eos, const int32_t* fin, const int64_t* step, const int32_t* parent_log, const int64_t* tok_log, int64_t log_rows,
+                        float* state0, float* state1, float* psi, int32_t* last, int dtype, void* stream);
+
 /* ---- n-best rescoring with a language model (csrc/rescore.hip): the hypotheses of one sentence (fk_ctc_beam_search's n-best list) share
  *      token prefixes, so every DISTINCT prefix is scored once: the list becomes a trie, the trie one packed GPT forward under an ancestor
  *      mask, the head goes through fk_head_ce_fwd (no [rows, V] logits), and the sums, the combination with the acoustic score and the

@@ -8,6 +8,7 @@
     python tools/decode_bench.py --model gpt2 --batch 1 --top-p 0.9                  # nucleus sampling: the step with and without top_p
     python tools/decode_bench.py --model gpt2 --batch 1 --repetition-penalty 1.3 --no-repeat-ngram 3 --min-new-tokens 10    # the history rules
     python tools/decode_bench.py --model gpt2 --beam 5 --repetition-penalty 1.3 --no-repeat-ngram 3 --min-new-tokens 10     # ... in the beam search
+    python tools/decode_bench.py --model gpt2 --beam 5 --ctc-weight 0.3 --sentences 1,3 --new-tokens 25    # joint CTC / attention decoding: the prefix scorer on and off
 
 Random weights, a 32-token brain prefix, one start token, top_k = 1.  A generate() call also pays the prefill and, in graph mode, the
 capture, so the per-token figure is the MARGINAL cost: (time of N new tokens - time of N/4 new tokens) / (3N/4), medians over the
@@ -305,6 +306,60 @@ def rules_bench(g, a, prefix, start):
               f"{max(times[name][n]) * 1e3:.2f}]", flush=True)
 
 
+def ctc_bench(g, a, d_model):
+    """--beam W --ctc-weight L [--sentences S[,S..]]: what the CTC prefix scorer (one more launch per step, fk_ctc_prefix_score) costs the
+    cached search.  CTC frames [S, --ctc-frames, 50258] of random fp32 logits, the blank last; the same call with the scorer off and on, as
+    a hipGraph, in one process with the repeats interleaved; us/step is marginal like every other figure of this file.  Below them the
+    launch on its own: device events around a run of back-to-back launches on a state one step into a search (it advances and scores)."""
+    from frankenstein_amd import kernels as K
+    W, n, n4 = a.beam, a.new_tokens, max(1, a.new_tokens // 4)
+    for S in (a.sentences or [1]):
+        prefix = torch.randn(S, 32, d_model, device="cuda")
+        start = torch.full((S, 1), 50256, dtype=torch.long, device="cuda")
+        frames = torch.randn(S, a.ctc_frames, 50258, device="cuda")
+        kw = dict(topk=a.topk, beam_width=W, use_cache=True, use_graph=True)
+        modes = {"scorer off": {}, f"ctc_weight = {a.ctc_weight}": dict(ctc_logits=frames, ctc_weight=a.ctc_weight, ctc_from_prompt=1)}
+        times = {name: {n4: [], n: []} for name in modes}
+        for extra in modes.values():                        # warm up both lengths of every mode
+            for k in (n4, n):
+                g.generate_beam_search(start, k, prefix, **kw, **extra)
+        for _ in range(a.repeats):
+            for k in (n4, n):
+                for name, extra in modes.items():
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    g.generate_beam_search(start, k, prefix, **kw, **extra)
+                    torch.cuda.synchronize()
+                    times[name][k].append(time.perf_counter() - t0)
+        for name in modes:
+            t4, t = statistics.median(times[name][n4]), statistics.median(times[name][n])
+            step = (t - t4) / (n - n4) if n > n4 else t / n
+            print(f"S = {S:2d}  {name:20s}: {step * 1e6:9.1f} us/step (marginal)   | whole call {t * 1e3:8.2f} ms [{min(times[name][n]) * 1e3:.2f} .. "
+                  f"{max(times[name][n]) * 1e3:.2f}], {n4} tokens {t4 * 1e3:8.2f} ms", flush=True)
+        # the launch on its own: row r continues beam r % W with a token of the vocabulary, then scores topk candidates
+        cs = K.ctc_prefix_init(frames, W, a.ctc_weight, None, None, start)
+        st = K.BeamState("cuda", W, 2, 64, seed=list(range(S)), groups=S)
+        st.parent_log[0] = (torch.arange(S * W, device="cuda") % W).to(torch.int32)
+        st.tok_log[0] = torch.randint(0, 50256, (S * W,), device="cuda")
+        st.step.fill_(1)
+        top_id = torch.stack([torch.randperm(50257, device="cuda")[:a.topk] for _ in range(S * W)])
+        top_lp = torch.full((S * W, a.topk), -3.0, device="cuda")
+        reps = 200
+        for _ in range(20):
+            K.ctc_prefix_score_(top_lp, top_id, cs, st)
+        ts = []
+        for _ in range(a.repeats):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(reps):
+                K.ctc_prefix_score_(top_lp, top_id, cs, st)
+            e1.record()
+            torch.cuda.synchronize()
+            ts.append(e0.elapsed_time(e1) * 1e3 / reps)
+        print(f"S = {S:2d}  fk_ctc_prefix_score alone ({S * W} rows x {a.topk} candidates x {a.ctc_frames} frames): {statistics.median(ts):7.2f} us per launch, "
+              f"back to back [{min(ts):.2f} .. {max(ts):.2f}]", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", choices=sorted(MODELS), default="nano")
@@ -323,6 +378,8 @@ def main():
     ap.add_argument("--repetition-penalty", type=float, default=1.0, help="history rules: time generate (or, with --beam, the cached search) with and without them, interleaved")
     ap.add_argument("--no-repeat-ngram", type=int, default=0, help="history rules: no_repeat_ngram_size")
     ap.add_argument("--min-new-tokens", type=int, default=0, help="history rules: min_new_tokens (the calls then carry an end-of-text id)")
+    ap.add_argument("--ctc-weight", type=float, default=None, help="with --beam: joint CTC / attention decoding, the search with and without the prefix scorer")
+    ap.add_argument("--ctc-frames", type=int, default=32, help="with --ctc-weight: frames of the CTC head")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "decode_bench needs the GPU"
 
@@ -343,6 +400,11 @@ def main():
         print(f"history rules: repetition_penalty {a.repetition_penalty}, no_repeat_ngram_size {a.no_repeat_ngram}, min_new_tokens {a.min_new_tokens}"
               + (f"; beam width {a.beam}, topk {a.topk}" if a.beam else ""))
         return rules_bench(g, a, prefix, start)
+    if a.ctc_weight is not None:
+        if not a.beam or B != 1:
+            ap.error("--ctc-weight needs --beam (and --sentences for more than one sentence)")
+        print(f"beam width {a.beam}, topk {a.topk}, CTC prefix scorer with weight {a.ctc_weight} on {a.ctc_frames} frames")
+        return ctc_bench(g, a, m["n_embd"])
     if a.beam and a.sentences:
         print(f"beam width {a.beam}, topk {a.topk}, sentences {a.sentences}")
         return sentences_bench(g, a, m["n_embd"])
