@@ -142,7 +142,11 @@ SIGNATURES = {
     "fk_vq_assign": (_int, [_p, _i64, _p, _p, _p, _p, _i64, _p, _i64, _p, _p, _f32, _p, _i64, _i64, _i64, _int, _p]),
     "fk_vq_bwd": (_int, [_p, _p, _p, _p, _f32, _p, _i64, _int, _p]),
     "fk_vq_codebook_update": (_int, [_p, _p, _p, _p, _i64, _p, _i64, _p, _p, _i64, _i64, _f32, _f32, _f32, _int, _p]),
+    "fk_day_adapter_fwd": (_int, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _int, _p]),
+    "fk_day_adapter_bwd_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64]),
+    "fk_day_adapter_bwd": (_int, [_p, _p, _p, _i64, _p, _p, _p, _sz, _i64, _i64, _i64, _i64, _i64, _p]),
 }
+DAY_MAX_C = 512                                                                       # the envelope of fk_day_adapter_*
 ADAMW_MAX_SLOTS, GRAD_SUMSQ_MAX_BLOCKS = 16, 1024
 VQ_CHAIN, VQ_FUSED = 0, 1                                                             # fk_vq_route
 VQ_EMA, VQ_KMEANS = 0, 1                                                              # fk_vq_codebook_update modes

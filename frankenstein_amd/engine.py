@@ -800,6 +800,93 @@ class PatchEmbed(torch.autograd.Function):
         return None, dw, db, dspace, None
 
 
+def day_ids(date_info, B: int, device) -> Optional[Tensor]:
+    """date_info as the kernels take it: None, or int64 [B] on `device`.  Accepts None, a Python int (broadcast over the batch) and an
+    int64 / int32 tensor [B] on any device; the values are never read on the host."""
+    if date_info is None:
+        return None
+    if isinstance(date_info, int):
+        return torch.full((B,), date_info, dtype=torch.int64, device=device)
+    if not isinstance(date_info, Tensor):
+        date_info = torch.as_tensor(date_info)
+    if date_info.dtype not in (torch.int64, torch.int32):
+        raise TypeError(f"date_info must be int64 or int32, got {date_info.dtype}")
+    d = date_info.reshape(-1)
+    if d.numel() != B:
+        raise ValueError(f"date_info has {d.numel()} entries for a batch of {B}")
+    return d.to(device=device, dtype=torch.int64).contiguous()
+
+
+class DayPatchify(torch.autograd.Function):
+    """tok [B, (T / P) * C, ldp] = to_patches(x + x @ delta[day] + bias[day]) in the compute dtype, columns P..ldp-1 zero
+    (fk_day_adapter_fwd: the adapted signal never exists in memory).  x is data; day: int64 [B] on the device or None.  The backward
+    takes d_tok in the same layout and returns (d_delta, d_bias) from fk_day_adapter_bwd; only x and day are saved.
+    carrier=True returns (tok, carrier): autograd casts a gradient to the dtype of the tensor it belongs to, so an fp32 d_tok handed back
+    for a bf16 tok would be rounded to bf16 on the way.  `carrier` is an fp32 tensor of tok's shape without memory (one element,
+    expanded) whose only purpose is to own the fp32 gradient: PatchEmbedTok / MaskedPatchEmbedTok take it beside tok and return d_tok for
+    it, unrounded.  out_fp32=True: tok itself in fp32 (the stand-alone P = 1 mode)."""
+
+    @staticmethod
+    def forward(ctx, x, day, delta, bias, P, ldp, out_fp32=False, carrier=False):
+        B, T, Cn = x.shape
+        xin = x if x.dtype == torch.float32 else K.cast(x.contiguous(), torch.float32)
+        xin = xin.contiguous()
+        tok = K.day_adapter_fwd(xin, day, delta.detach(), bias.detach(), P, ldp, torch.float32 if out_fp32 else _COMPUTE_DTYPE)
+        ctx.P, ctx.dshape = P, tuple(delta.shape)
+        ctx.save_for_backward(xin, day)
+        ctx.set_materialize_grads(False)
+        tok = tok.view(B, (T // P) * Cn, ldp)
+        if not carrier:
+            return tok
+        return tok, torch.empty((1,), dtype=torch.float32, device=tok.device).expand(tok.shape)
+
+    @staticmethod
+    def backward(ctx, d_tok, d_carrier=None):
+        x, day = ctx.saved_tensors
+        g = d_carrier if d_carrier is not None else d_tok
+        if g is None:
+            return (None,) * 8
+        d2 = g.contiguous().view(-1, g.shape[-1])
+        if d2.dtype != torch.float32:
+            d2 = K.cast(d2, torch.float32)
+        d_delta, d_bias = K.day_adapter_bwd(x, day, d2, ctx.P, ctx.dshape)
+        return None, None, d_delta, d_bias, None, None, None, None
+
+
+def _d_tok(dh2: Tensor, emb_w: Tensor, kp: int) -> Tensor:
+    """d_tok [rows, kp] fp32 = dh @ emb_w (columns P..kp-1 zero): the small-N NT GEMM on the transposed, K-padded weight shadow"""
+    return K.gemm_nt(dh2, shadow([emb_w], transpose=True, pad_k=kp), out_dtype=torch.float32)
+
+
+class PatchEmbedTok(torch.autograd.Function):
+    """PatchEmbed on tokens that are a differentiable input (DayPatchify's): tok [B, nT * C, kp] compute dtype, kp = P rounded up to 32.
+    The backward also returns d_tok = dh @ emb_w (fp32, same layout): for `carrier` (DayPatchify's, which keeps it fp32) when one is
+    given, else for tok itself (autograd then casts it to tok's dtype)."""
+
+    @staticmethod
+    def forward(ctx, tok, emb_w, emb_b, space, P, carrier=None):
+        B, N, kp = tok.shape
+        Cn, d = space.shape[1], space.shape[2]
+        tok2 = tok.view(B * N, kp)
+        sp = shadow([space.view(Cn, d)])
+        h = K.gemm_nt(tok2, shadow([emb_w], pad_k=kp), bias=shadow([emb_b]), residual=sp, res_rows=Cn)
+        ctx.dims = (B, N // Cn, Cn, d, P, kp)
+        ctx.save_for_backward(tok2, emb_w)
+        return h.view(B, N, d)
+
+    @staticmethod
+    def backward(ctx, dh):
+        tok2, emb_w = ctx.saved_tensors
+        B, nT, Cn, d, P, kp = ctx.dims
+        dh2 = dh.contiguous().view(-1, d)
+        dw = K.gemm_tn(dh2, tok2)[:, :P].contiguous()
+        db = K.colsum(dh2)
+        dspace = K.colsum(dh2.view(B * nT, Cn * d)).view(1, Cn, d)
+        to_carrier = ctx.needs_input_grad[5]
+        d_tok = _d_tok(dh2, emb_w, kp).view(B, nT * Cn, kp) if (to_carrier or ctx.needs_input_grad[0]) else None
+        return (None if to_carrier else d_tok), dw, db, dspace, None, (d_tok if to_carrier else None)
+
+
 class ExpandQueries(torch.autograd.Function):
     """learnable_queries [1,M,d] (fp32 master) -> [B,M,d] compute dtype (models/brainformer.py:545)."""
 
@@ -1395,6 +1482,38 @@ class MaskedPatchEmbed(torch.autograd.Function):
         dspace = torch.zeros((Cn, d), dtype=torch.float32, device=dh.device)
         K.scatter_add_rows_(dspace, unmasked, dh2, idx_mod=Cn)
         return None, dw, db, dspace.view(1, Cn, d), None, None
+
+
+class MaskedPatchEmbedTok(torch.autograd.Function):
+    """MaskedPatchEmbed on tokens that are a differentiable input (DayPatchify's): the backward also returns d_tok_all, dh @ emb_w of the
+    kept tokens scattered into a zeroed [B, n_tokens, kp] (fp32), for `carrier` when one is given (see PatchEmbedTok)."""
+
+    @staticmethod
+    def forward(ctx, tok_all, emb_w, emb_b, space, unmasked, P, carrier=None):
+        B, N, kp = tok_all.shape
+        Cn, d = space.shape[1], space.shape[2]
+        tok_u = K.gather_rows(tok_all, unmasked)
+        sp = K.gather_rows(shadow([space.view(Cn, d)]), unmasked, idx_mod=Cn)
+        n = unmasked.shape[1]
+        h = K.gemm_nt(tok_u.view(B * n, kp), shadow([emb_w], pad_k=kp), bias=shadow([emb_b]), residual=sp.view(B * n, d))
+        ctx.dims = (B, n, N, Cn, d, P, kp)
+        ctx.save_for_backward(tok_u, unmasked, emb_w)
+        return h.view(B, n, d)
+
+    @staticmethod
+    def backward(ctx, dh):
+        tok_u, unmasked, emb_w = ctx.saved_tensors
+        B, n, N, Cn, d, P, kp = ctx.dims
+        dh2 = dh.contiguous().view(B * n, d)
+        dw = K.gemm_tn(dh2, tok_u.view(B * n, -1))[:, :P].contiguous()
+        db = K.colsum(dh2)
+        dspace = torch.zeros((Cn, d), dtype=torch.float32, device=dh.device)
+        K.scatter_add_rows_(dspace, unmasked, dh2, idx_mod=Cn)
+        d_tok, to_carrier = None, ctx.needs_input_grad[6]
+        if to_carrier or ctx.needs_input_grad[0]:
+            d_tok = torch.zeros((B, N, kp), dtype=torch.float32, device=dh.device)
+            K.scatter_rows_(d_tok, unmasked, _d_tok(dh2, emb_w, kp).view(B, n, kp))
+        return (None if to_carrier else d_tok), dw, db, dspace.view(1, Cn, d), None, None, (d_tok if to_carrier else None)
 
 
 class AssembleDecoder(torch.autograd.Function):

@@ -10,7 +10,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib
-from ._lib import FK_BF16, FK_F32, MASK_BLOCK_CAUSAL, MASK_CAUSAL, MASK_DENSE, MASK_KEYPAD, MASK_NONE, MASK_PREFIX, NORM_LAYER, NORM_RMS, ATTN_Q_PRESCALED, call, lib
+from ._lib import FK_BF16, FK_F32, MASK_BLOCK_CAUSAL, MASK_CAUSAL, MASK_DENSE, MASK_KEYPAD, MASK_NONE, MASK_PREFIX, NORM_LAYER, NORM_RMS, ATTN_Q_PRESCALED, DAY_MAX_C, call, lib
 
 Tensor = torch.Tensor
 
@@ -528,6 +528,49 @@ def patchify(x: Tensor, P: int, ldp: int, dtype: torch.dtype) -> Tensor:
     tok = torch.empty((B * (T // P) * Cc, ldp), dtype=dtype, device=x.device)
     call("fk_patchify", x.data_ptr(), tok.data_ptr(), B, T, Cc, P, ldp, fk_dtype(dtype), _stream())
     return tok
+
+
+def _day_check(x: Tensor, day: Optional[Tensor], delta: Tensor, bias: Tensor):
+    assert x.dtype == torch.float32 and x.dim() == 3 and x.is_contiguous()
+    B, T, Cc = x.shape
+    n_days = delta.shape[0]
+    assert delta.dtype == torch.float32 and delta.shape == (n_days, Cc, Cc) and delta.is_contiguous() and delta.device == x.device
+    assert bias.dtype == torch.float32 and bias.shape == (n_days, Cc) and bias.is_contiguous() and bias.device == x.device
+    assert day is None or (day.dtype == torch.int64 and day.shape == (B,) and day.is_contiguous() and day.device == x.device)
+    return B, T, Cc, n_days
+
+
+def day_adapter_fwd(x: Tensor, day: Optional[Tensor], delta: Tensor, bias: Tensor, P: int, ldp: int, dtype: torch.dtype) -> Tensor:
+    """fk_day_adapter_fwd: tok [B * (T / P) * C, ldp] = patchify(x + x @ delta[day] + bias[day]); day int64 [B] on the device (None, or
+    an entry outside [0, n_days): pass-through).  P = 1, ldp = 1, float32 is the adapted [B, T, C] signal itself."""
+    B, T, Cc, n_days = _day_check(x, day, delta, bias)
+    tok = torch.empty((B * (T // P) * Cc, ldp), dtype=dtype, device=x.device)
+    with _timed("day_adapter_fwd"):
+        call("fk_day_adapter_fwd", x.data_ptr(), _ptr(day), delta.data_ptr(), bias.data_ptr(), tok.data_ptr(), B, T, Cc, P, ldp, n_days,
+             fk_dtype(dtype), _stream())
+    return tok
+
+
+def day_adapter_bwd(x: Tensor, day: Optional[Tensor], d_tok: Tensor, P: int, delta_shape, out: Optional[Tuple[Tensor, Tensor]] = None):
+    """fk_day_adapter_bwd: (d_delta [n_days, C, C], d_bias [n_days, C]) from d_tok fp32 [B * (T / P) * C, ldp]; every slice is
+    overwritten (a day absent from the batch: zeros)."""
+    assert x.dtype == torch.float32 and x.dim() == 3 and x.is_contiguous()
+    B, T, Cc = x.shape
+    n_days = delta_shape[0]
+    assert tuple(delta_shape) == (n_days, Cc, Cc)
+    assert day is None or (day.dtype == torch.int64 and day.shape == (B,) and day.is_contiguous() and day.device == x.device)
+    assert d_tok.dtype == torch.float32 and d_tok.dim() == 2 and d_tok.is_contiguous() and d_tok.shape[0] == B * (T // P) * Cc
+    ldp = d_tok.shape[1]
+    if out is None:
+        out = (torch.empty((n_days, Cc, Cc), dtype=torch.float32, device=x.device), torch.empty((n_days, Cc), dtype=torch.float32, device=x.device))
+    d_delta, d_bias = out
+    assert d_delta.shape == (n_days, Cc, Cc) and d_bias.shape == (n_days, Cc) and d_delta.is_contiguous() and d_bias.is_contiguous()
+    assert d_delta.dtype == torch.float32 and d_bias.dtype == torch.float32
+    ws, nb = _ws(lib().fk_day_adapter_bwd_workspace_bytes(B, T, Cc, P, n_days) if day is not None else 0, x.device)
+    with _timed("day_adapter_bwd"):
+        call("fk_day_adapter_bwd", x.data_ptr(), _ptr(day), d_tok.data_ptr(), ldp, d_delta.data_ptr(), d_bias.data_ptr(), _ptr(ws), nb,
+             B, T, Cc, P, n_days, _stream())
+    return d_delta, d_bias
 
 
 def swiglu_fwd(h13: Tensor) -> Tensor:

@@ -49,6 +49,8 @@ class MAEConfig(Serializable):
     # decoder
     n_dec_layers: Optional[int] = 4
     decoder_dim: Optional[int] = 256
+    # per-session input adapter (DayAdapter): number of recording sessions date_info indexes; 0 = no adapter, no extra parameter
+    n_days: int = 0
 
 
 @dataclass
@@ -305,6 +307,43 @@ class CrossBlock(nn.Module):
 
 
 # ------------------------------------------------------------------------------------------- models
+class DayAdapter(nn.Module):
+    """Per-session input adapter (no counterpart in the reference, which accepts date_info and never reads it): with d = date_info[b],
+        y[b, t, :] = x[b, t, :] + x[b, t, :] @ delta[d] + bias[d]
+    delta [n_days, C, C] and bias [n_days, C] start at zero, so a fresh adapter is the identity and weight decay pulls towards it; there
+    is no nonlinearity; x is data and gets no gradient.  A d outside [0, n_days) (-1 = unknown session) and date_info=None pass the
+    sample through unchanged and give it no gradient.  Sums are fp32 in both compute modes (csrc/dayadapt.hip).
+    forward(x, date_info) -> the adapted [B, T, C] signal in fp32; an Encoder that owns an adapter does not call this: it fuses the
+    transform into its patch tokeniser (engine.DayPatchify).  date_info: int64 / int32 tensor [B] on any device, a Python int, or None."""
+
+    def __init__(self, n_days: int, n_channels: int):
+        super().__init__()
+        if n_days < 1 or not 1 <= n_channels <= K.DAY_MAX_C:
+            raise ValueError(f"DayAdapter needs n_days >= 1 and 1 <= n_channels <= {K.DAY_MAX_C}, got {n_days}, {n_channels}")
+        self.n_days, self.n_channels = n_days, n_channels
+        self.delta = nn.Parameter(torch.zeros(n_days, n_channels, n_channels))
+        self.bias = nn.Parameter(torch.zeros(n_days, n_channels))
+
+    def tokens(self, x, date_info, P: int, ldp: int):
+        """(tok, carrier): to_patches of the adapted signal, [B, (T / P) * C, ldp] in the compute dtype (columns P..ldp-1 zero),
+        differentiable in delta and bias, and the fp32 gradient carrier of engine.DayPatchify"""
+        return E.DayPatchify.apply(x, E.day_ids(date_info, x.shape[0], self.delta.device), self.delta, self.bias, P, ldp, False, True)
+
+    def forward(self, x, date_info=None):
+        B, T, C = x.shape
+        day = E.day_ids(date_info, B, self.delta.device)
+        return E.DayPatchify.apply(x, day, self.delta, self.bias, 1, 1, True).view(B, T, C)
+
+    @torch.no_grad()
+    def copy_day(self, src: int, dst: int) -> None:
+        """seed session dst from session src (a new recording day starts from its neighbour's fit)"""
+        if not (0 <= src < self.n_days and 0 <= dst < self.n_days):
+            raise IndexError(f"copy_day({src}, {dst}) outside [0, {self.n_days})")
+        self.delta[dst].copy_(self.delta[src])
+        self.bias[dst].copy_(self.bias[src])
+        E.bump_weight_epoch()
+
+
 class Encoder(nn.Module):
     def __init__(self, config):
         super().__init__()
@@ -319,6 +358,8 @@ class Encoder(nn.Module):
             ln_f=LayerNorm(config.dim),
         ))
         self.space_embedding = nn.Parameter(torch.randn(1, config.n_electrodes, config.dim), requires_grad=True)
+        if getattr(config, "n_days", 0) > 0:                 # state-dict keys encoder.day_adapter.{delta,bias}; none with n_days == 0
+            self.day_adapter = DayAdapter(config.n_days, config.n_electrodes)
         self.precompute_rope_cash = build_complex_rope_cache(dim=config.head_dim, seq_len=self.block_size,
                                                              theta=config.rope_theta)
         # The reference registers the [N, N] boolean mask as a buffer (models/brainformer.py:298): 37.7 MB at N = 6144 that no kernel
@@ -371,11 +412,24 @@ class Encoder(nn.Module):
     def get_num_params(self):
         return sum(p.numel() for p in self.parameters())
 
-    def forward(self, x, kv_cache=None):
-        """x: [B, T, C] feature frames -> [B, (T/patch)*C, dim] tokens."""
+    def day_active(self, date_info) -> bool:
+        """does this forward go through the adapter?  Not without one (n_days == 0), and not with date_info=None unless its
+        parameters are being trained (they then get their exact-zero gradients); otherwise today's path, launch for launch."""
+        ad = getattr(self, "day_adapter", None)
+        if ad is None:
+            return False
+        return date_info is not None or (torch.is_grad_enabled() and (ad.delta.requires_grad or ad.bias.requires_grad))
+
+    def forward(self, x, kv_cache=None, date_info=None):
+        """x: [B, T, C] feature frames -> [B, (T/patch)*C, dim] tokens.  date_info: the sessions of the samples (DayAdapter)."""
         assert x.shape[2] == self.n_electrodes and x.shape[1] % self.patch_size == 0
-        h = E.PatchEmbed.apply(x, self.transformer.emb.weight, self.transformer.emb.bias, self.space_embedding,
-                               self.patch_size)
+        if self.day_active(date_info):
+            P = self.patch_size
+            tok, carrier = self.day_adapter.tokens(x, date_info, P, (P + 31) // 32 * 32)
+            h = E.PatchEmbedTok.apply(tok, self.transformer.emb.weight, self.transformer.emb.bias, self.space_embedding, P, carrier)
+        else:
+            h = E.PatchEmbed.apply(x, self.transformer.emb.weight, self.transformer.emb.bias, self.space_embedding,
+                                   self.patch_size)
         T = h.shape[1]
         mask = Mask(MASK_BLOCK_CAUSAL, self.n_electrodes).sliced(self.block_size, self.block_size, T, T)   # attn_mask[-T:, -T:]
         rope = self.rope_cache
@@ -426,7 +480,11 @@ class MAE(nn.Module):
         P = cfg.patch_size
         kp = (P + 31) // 32 * 32
         xin = x if x.dtype == torch.float32 else x.float()
-        tok_all = K.patchify(xin.contiguous(), P, kp, E.compute_dtype()).view(B, (T // P) * Cn, kp)
+        adapt = enc.day_active(date_info)
+        if adapt:                                            # the adapter acts on the encoder's input; the target stays the raw patches
+            tok_all, carrier = enc.day_adapter.tokens(xin, date_info, P, kp)
+        else:
+            tok_all = K.patchify(xin.contiguous(), P, kp, E.compute_dtype()).view(B, (T // P) * Cn, kp)
         n_tokens = tok_all.shape[1]
         if indices is None:
             masked, unmasked = self.get_masking_indices(masking_ratio, tok_all)
@@ -437,8 +495,9 @@ class MAE(nn.Module):
         table = torch.view_as_real(enc.rope_cache).reshape(enc.block_size, -1)
         rope = K.gather_rows(table.contiguous(), unmasked).view(B, unmasked.shape[1], -1, 2)
         mask = Mask.from_token_ids(unmasked, unmasked, enc.n_electrodes)
-        tokens = E.MaskedPatchEmbed.apply(tok_all, enc.transformer.emb.weight, enc.transformer.emb.bias,
-                                          enc.space_embedding, unmasked, P)
+        tokens = (E.MaskedPatchEmbedTok.apply(tok_all, enc.transformer.emb.weight, enc.transformer.emb.bias, enc.space_embedding, unmasked, P, carrier)
+                  if adapt else
+                  E.MaskedPatchEmbed.apply(tok_all, enc.transformer.emb.weight, enc.transformer.emb.bias, enc.space_embedding, unmasked, P))
         for block in enc.transformer.h:
             tokens = block(tokens, attn_mask=mask, rope=rope)
         tokens = enc.transformer.ln_f(tokens)
@@ -446,7 +505,7 @@ class MAE(nn.Module):
         for block in self.decoder.h:
             dec = block(dec)
         pred = self.to_signals(E.GatherRows.apply(dec, masked))                    # [B, n_masked, P]
-        tok_p = tok_all if kp == P else K.patchify(xin.contiguous(), P, P, E.compute_dtype()).view(B, n_tokens, P)
+        tok_p = tok_all if (kp == P and not adapt) else K.patchify(xin.contiguous(), P, P, E.compute_dtype()).view(B, n_tokens, P)
         target = K.gather_rows(tok_p, masked)                                      # [B, n_masked, P] (data, no gradient)
         loss = E.mse_loss(pred, target)
         if return_preds:
@@ -507,24 +566,24 @@ class BrainFormer(nn.Module):
             self.precompute_rope_cash = self.precompute_rope_cash.to(device=self.device)
         return self.precompute_rope_cash
 
-    def queries_out(self, x):
+    def queries_out(self, x, date_info=None):
         """encoder -> learnable queries -> perceiver CrossBlocks (before ln_f and the head)."""
         b = x.shape[0]
-        ctx = self.encoder(x)
+        ctx = self.encoder(x, date_info=date_info)
         q = E.ExpandQueries.apply(self.learnable_queries, b)
         for cross_block in self.perceiver.h:
             q = cross_block(q, ctx, self.self_attn_mask, self.cross_attn_mask, sa_rope=self.rope_cache)
         return q
 
-    def features(self, x):
+    def features(self, x, date_info=None):
         """encoder -> learnable queries -> perceiver CrossBlocks -> ln_f -> head."""
-        q = self.queries_out(x)
+        q = self.queries_out(x, date_info)
         head = self.perceiver[self.head_name]
         ln = self.perceiver.ln_f
         return E.NormLinear.apply(q, ln.weight, ln.bias, head.weight, head.bias, ln.eps, False)
 
     def forward(self, x, targets=None, date_info=None):
-        pred = self.features(x)
+        pred = self.features(x, date_info)
         if targets is None:
             return None, pred
         return E.l1_loss(pred, targets), pred
@@ -532,7 +591,7 @@ class BrainFormer(nn.Module):
     @torch.no_grad()
     def inference(self, myo, date_info):
         x = torch.from_numpy(myo)[None].to(self.device).float()
-        pred = self.forward(x, targets=None)[1]
+        pred = self.forward(x, targets=None, date_info=date_info)[1]
         return pred[0].float().cpu().numpy().T
 
 

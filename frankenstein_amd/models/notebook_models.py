@@ -27,7 +27,7 @@ class BrainEncoder(_FileBrainFormer):
     head_name = 'to_words'
 
     def forward(self, x, targets=None, date_info=None):
-        return self.features(x)
+        return self.features(x, date_info)
 
 
 class BrainFormerCE(_FileBrainFormer):
@@ -38,10 +38,10 @@ class BrainFormerCE(_FileBrainFormer):
     def forward(self, x, targets=None, date_info=None):
         if targets is not None and getattr(self, "fuse_head_loss", False):
             # loss only (train_utils.enable_fused_head_loss): perceiver.ln_f -> to_words -> CE without the [B, tokens, V] logits
-            q = self.queries_out(x)
+            q = self.queries_out(x, date_info)
             head, ln = self.perceiver[self.head_name], self.perceiver.ln_f
             return E.head_cross_entropy(q, ln.weight, ln.bias, head.weight, head.bias, targets, ln.eps, -100, getattr(self, "head_chunk", 8192)), None
-        logits = self.features(x)
+        logits = self.features(x, date_info)
         if targets is None:
             return None, logits
         return E.cross_entropy(logits, targets, -100), logits
@@ -89,7 +89,7 @@ class BrainFormerCTC(_FileBrainFormer):
             raise ValueError(f"blank = {self.blank} outside [0, output_dim = {config.output_dim})")
 
     def forward(self, x, targets=None, date_info=None):
-        logits = self.features(x)
+        logits = self.features(x, date_info)
         if targets is None:
             return None, logits
         if self.mwer_weight is None:
@@ -98,26 +98,26 @@ class BrainFormerCTC(_FileBrainFormer):
                                mwer_weight=self.mwer_weight, zero_infinity=True), logits
 
     @torch.no_grad()
-    def error_rate(self, x, targets, **decode_kwargs):
+    def error_rate(self, x, targets, date_info=None, **decode_kwargs):
         """decode(x, **decode_kwargs), its best hypothesis against targets (int64 [B, Lmax] padded with -100) -> engine.error_rate's (rate,
         errors, ref_lengths): the corpus error rate as a device scalar, no synchronisation"""
-        out = self.decode(x, **decode_kwargs)
+        out = self.decode(x, date_info=date_info, **decode_kwargs)
         ids, lengths = (out[0][:, 0], out[1][:, 0]) if out[0].dim() == 3 else (out[0], out[1])
         return E.error_rate(targets, ids, hypothesis_lengths=lengths, pad_value=-100)
 
     @torch.no_grad()
-    def align(self, x, targets, input_lengths=None, target_lengths=None):
+    def align(self, x, targets, input_lengths=None, target_lengths=None, date_info=None):
         """Forced alignment of the read-out to `targets` (int64 [B, Lmax] padded with -100, or with target_lengths): the most probable
         alignment as an engine.CtcAlignment (score, path, index, start, end, label_lp, .confidence), frames being read-out tokens.  To
         align a hypothesis of the beam search (ids, lengths, scores = decode(x, beam_width=W, nbest=k)): align(x, ids[:, 0, :Lmax],
         target_lengths=lengths[:, 0]) with Lmax <= 255 at least the longest hypothesis; its confidence flags the shaky tokens."""
-        return E.ctc_forced_align(self.features(x), targets, input_lengths, target_lengths, blank=self.blank, pad_value=-100, pad=-100)
+        return E.ctc_forced_align(self.features(x, date_info), targets, input_lengths, target_lengths, blank=self.blank, pad_value=-100, pad=-100)
 
     @torch.no_grad()
     def decode(self, x, beam_width=None, topk=None, nbest=1, lm=None, lm_prefix=None, lm_weight=1.0, length_bonus=0.0, eos_token_id=None,
                am_weight=1.0, bos_token_id=50256, max_nodes=None, ngram=None, ngram_weight=1.0, ngram_bonus=0.0, ngram_eos=True, mbr=False,
-               mbr_scale=1.0):
-        logits = self.features(x)
+               mbr_scale=1.0, date_info=None):
+        logits = self.features(x, date_info)
         if mbr:
             if beam_width is None:
                 raise ValueError("decode(mbr=True) re-ranks a beam: give a beam_width")
@@ -182,22 +182,26 @@ class Franky(nn.Module):
     def device(self) -> torch.device:
         return next(self.parameters()).device
 
+    def _brain(self, x, date_info):
+        """brain_model(x), with the sessions of the samples when there are any (a brain model without the argument keeps working)"""
+        return self.brain_model(x) if date_info is None else self.brain_model(x, date_info=date_info)
+
     def forward(self, x, targets=None, date_info=None):
-        features = self.brain_model(x)
+        features = self._brain(x, date_info)
         new_idx = targets.clone()
         new_idx[new_idx == -100] = 50256
         return self.llm_model.forward(idx=new_idx, prefix=features, targets=targets)
 
     @torch.no_grad()
-    def rescore(self, x, ids, lengths, scores, **weights):
+    def rescore(self, x, ids, lengths, scores, date_info=None, **weights):
         """Re-rank the n-best lists (ids [S, n, T], lengths, scores [S, n]: BrainFormerCTC.decode(..., nbest=n) of the same trials) under the
         decoder conditioned on the brain features of x (tensor [S, T, C]): brain_model(x) is the prefix of llm_model.rescore_nbest, whose
         keyword arguments (lm_weight, am_weight, length_bonus, eos_token_id, max_nodes, ...) and ranked outputs these are."""
-        return self.llm_model.rescore_nbest(ids, lengths, scores, prefix=self.brain_model(x), **weights)
+        return self.llm_model.rescore_nbest(ids, lengths, scores, prefix=self._brain(x, date_info), **weights)
 
     @torch.no_grad()
     def generate(self, x, max_new_tokens=25, temperature=1.0, top_k=10, eot=50256, stop=False, top_p=None, repetition_penalty=1.0,
-                 no_repeat_ngram_size=0, min_new_tokens=0):
+                 no_repeat_ngram_size=0, min_new_tokens=0, date_info=None):
         """x: numpy [T, C].  Returns generated token ids (the notebook's version is unfinished; this one runs).
         stop=True ends a sentence at its first generated `eot` (what the notebook's cell tried with its undefined stop_tokens): the ids come
         back trimmed behind that token; x: numpy [S, T, C] then decodes S trials, returns [S, 1 + max_new_tokens] padded with `eot` and sets
@@ -210,7 +214,7 @@ class Franky(nn.Module):
         rules = self._rules(repetition_penalty, no_repeat_ngram_size, min_new_tokens, eot if stop else None, max_new_tokens, top_k or 1)
         if stop:
             xin = torch.from_numpy(x if x.ndim == 3 else x[None]).to(self.device).float()
-            prefix = self.brain_model(xin)
+            prefix = self._brain(xin, date_info)
             ids = torch.full((xin.shape[0], 1), eot, dtype=torch.long, device=self.device)
             self.llm_model.generate(ids, max_new_tokens, prefix=prefix, temperature=temperature, top_k=top_k, eos_token_id=eot, top_p=top_p, **rules)
             self.last_lengths = self.llm_model.last_lengths.cpu()           # int64 on the host, as generate_beam leaves it
@@ -218,7 +222,7 @@ class Franky(nn.Module):
                 return self.llm_model.last_tokens
             return self.llm_model.last_tokens[0, :1 + int(self.last_lengths[0])]
         xin = torch.from_numpy(x[None]).to(self.device).float()
-        prefix = self.brain_model(xin)
+        prefix = self._brain(xin, date_info)
         ids = torch.full((1, 1), eot, dtype=torch.long, device=self.device)
         return self.llm_model.generate(ids, max_new_tokens, prefix=prefix, temperature=temperature, top_k=top_k, top_p=top_p, **rules)
 
@@ -230,7 +234,8 @@ class Franky(nn.Module):
 
     @torch.no_grad()
     def generate_beam(self, x, max_new_tokens=25, temperature=1.0, topk=20, beam_width=5, eot=50256, batch_sentences=None, stop=False,
-                      length_penalty=0.0, repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, ctc=None, ctc_weight=0.0):
+                      length_penalty=0.0, repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, ctc=None, ctc_weight=0.0,
+                      date_info=None):
         """x: numpy [T, C].  Brain features -> prefix -> the stochastic beam search of the decoder on its key/value caches
         (GPT.generate_beam_search, use_cache=True).  Returns the best beam's ids, `eot` first.
         x: numpy [S, T, C] decodes S trials and returns ids [S, 1 + max_new_tokens]: the encoder and the search run in chunks of
@@ -252,18 +257,21 @@ class Franky(nn.Module):
         if float(ctc_weight) > 0.0 and ctc is None:
             raise ValueError("ctc_weight > 0 needs the CTC model `ctc`")
 
-        def ctc_kw(xin):                                                     # the head runs on the chunk of trials the encoder just saw
+        def days(s0, n):                                                     # the sessions of trials s0 .. s0 + n - 1
+            return date_info[s0:s0 + n] if isinstance(date_info, torch.Tensor) and date_info.dim() > 0 else date_info
+
+        def ctc_kw(xin, di):                                                 # the head runs on the chunk of trials the encoder just saw
             if ctc is None or float(ctc_weight) == 0.0:
                 return {}
-            return dict(ctc_logits=ctc.features(xin), ctc_weight=float(ctc_weight), ctc_blank=ctc.blank, ctc_from_prompt=1)
+            return dict(ctc_logits=ctc.features(xin, di), ctc_weight=float(ctc_weight), ctc_blank=ctc.blank, ctc_from_prompt=1)
 
         eos_kw = dict(eos_token_id=eot if stop else None, length_penalty=length_penalty) if (stop or length_penalty != 0.0) else {}
         if x.ndim == 2:
             xin = torch.from_numpy(x[None]).to(self.device).float()
-            prefix = self.brain_model(xin)
+            prefix = self._brain(xin, date_info)
             ids = torch.full((1, 1), eot, dtype=torch.long, device=self.device)
             out = self.llm_model.generate_beam_search(ids, max_new_tokens, prefix, temperature=temperature, topk=topk, beam_width=beam_width,
-                                                      use_cache=True, **eos_kw, **rules, **ctc_kw(xin))
+                                                      use_cache=True, **eos_kw, **rules, **ctc_kw(xin, date_info))
             if eos_kw:
                 self.last_lengths = torch.tensor([self.llm_model.last_beam_lengths[0]])
             return out[:1 + int(self.last_lengths[0])] if stop else out
@@ -272,10 +280,11 @@ class Franky(nn.Module):
         outs, lengths = [], []
         for s0 in range(0, x.shape[0], batch_sentences):
             xin = torch.from_numpy(x[s0:s0 + batch_sentences]).to(self.device).float()
-            prefix = self.brain_model(xin)
+            di = days(s0, xin.shape[0])
+            prefix = self._brain(xin, di)
             ids = torch.full((xin.shape[0], 1), eot, dtype=torch.long, device=self.device)
             out = self.llm_model.generate_beam_search(ids, max_new_tokens, prefix, temperature=temperature, topk=topk, beam_width=beam_width,
-                                                      use_cache=True, **eos_kw, **rules, **ctc_kw(xin))
+                                                      use_cache=True, **eos_kw, **rules, **ctc_kw(xin, di))
             outs.append(out.view(xin.shape[0], -1))
             if eos_kw:
                 lens = self.llm_model.last_beam_lengths

@@ -585,6 +585,10 @@ class GraphedTrainStep:
         self.model, self.optimizer, self.cfg = model, optimizer, cfg
         self.get_lr = scheduler or init_lr_scheduler(cfg)
         self.static = tuple(t.clone() if torch.is_tensor(t) else t for t in batch)
+        if len(self.static) == 3 and self.static[2] is not None:
+            # date_info is part of the static batch: int64 [B] on the device whatever form it came in (tensor on any device, Python int),
+            # so that the captured kernels read a buffer which every call copies into
+            self.static = (*self.static[:2], self._days(batch[2]).clone())
         optimizer.sync.enabled = False
         cur = torch.cuda.current_stream()
         side = torch.cuda.Stream()
@@ -609,7 +613,14 @@ class GraphedTrainStep:
             torch.cuda.current_stream().wait_stream(side)
         return loss.detach()
 
+    def _days(self, date_info):
+        return E.day_ids(date_info, self.static[0].shape[0], self.static[0].device)
+
     def __call__(self, batch, step: int):
+        if len(self.static) == 3 and torch.is_tensor(self.static[2]) and len(batch) == 3:
+            if batch[2] is None:
+                raise RuntimeError("GraphedTrainStep was captured with date_info, got None (use -1 for an unknown session)")
+            batch = (*batch[:2], self._days(batch[2]))
         for dst, src in zip(self.static, batch):
             if torch.is_tensor(dst):
                 if dst.shape != src.shape:

@@ -862,6 +862,32 @@ int fk_vq_codebook_update(float* embed, float* embed_avg, float* cluster_size, c
                           const float* sums, int64_t ld_sums, const float* seed, float* n_ws, int64_t K, int64_t D, float decay, float eps,
                           float dead, int mode, void* stream);
 
+/* ---- per-session input adapter (build-defined: the reference hands date_info to every forward and never reads it; float64
+ *      restatement in tests/day_adapter_ref.py).  With C = n_electrodes and d = day[b], the session ("day") of sample b:
+ *          y[b, t, :] = x[b, t, :] + x[b, t, :] @ delta[d] + bias[d]          0 <= d < n_days
+ *          y[b, t, :] = x[b, t, :]                                            any other d (-1 = unknown session), or day == NULL
+ *      delta [n_days, C, C] and bias [n_days, C] are fp32 masters (zeros = the identity; weight decay pulls towards it); no
+ *      nonlinearity; x fp32 [B, T, C] is data and gets no gradient.  Products and sums are fp32 in both compute modes (exact
+ *      fp32-input MFMA; x + bias is added to the finished sum); the only rounding to `dtype` is the store.  day: int64 [B] ON THE DEVICE,
+ *      never read by the host; an out-of-range value selects the pass-through, it is never used as an index.
+ * fk_day_adapter_fwd writes y straight in fk_patchify's layout and contract: tok[b, (t / P) * C + c, p] in `dtype`, row stride
+ *   ldp >= P, columns P..ldp-1 zero; with delta == 0 and bias == 0 the values are those of fk_patchify.  The adapted [B, T, C]
+ *   signal never exists in memory.  P = 1, ldp = 1, dtype = FK_F32 is the natural [B, T, C] layout.
+ * fk_day_adapter_bwd: d_tok fp32 in the same layout (row stride ldp), dy[b, tp * P + p, c'] = d_tok[b, tp * C + c', p]:
+ *          d_delta[d, c, c'] = sum_{b: day[b] = d} sum_t x[b, t, c] * dy[b, t, c']
+ *          d_bias[d, c']     = sum_{b: day[b] = d} sum_t dy[b, t, c']
+ *   ALL n_days slices are overwritten; a day absent from the batch (and every day when day == NULL) gets exact zeros.  No atomics,
+ *   no host read of day; the summation order is fixed by (B, T, C, P) and the contents of day: the same bits on every run.
+ *   Scratch is the caller's workspace (fk_day_adapter_bwd_workspace_bytes; not needed when day == NULL); graph-capturable.
+ * Envelope (anything else is refused with FK_EINVAL, on the host, before any launch): 1 <= C <= 512 (any C: tails are padded in
+ *   LDS), T % P == 0, ldp >= P, n_days >= 1 (<= 65535 for the backward), sizes within int32, pointers aligned to their element. */
+int fk_day_adapter_fwd(const float* x, const int64_t* day, const float* delta, const float* bias, void* tok, int64_t B, int64_t T,
+                       int64_t C, int64_t P, int64_t ldp, int64_t n_days, int dtype, void* stream);
+size_t fk_day_adapter_bwd_workspace_bytes(int64_t B, int64_t T, int64_t C, int64_t P, int64_t n_days);
+int fk_day_adapter_bwd(const float* x, const int64_t* day, const float* d_tok, int64_t ldp, float* d_delta, float* d_bias,
+                       void* workspace, size_t workspace_bytes, int64_t B, int64_t T, int64_t C, int64_t P, int64_t n_days,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif
