@@ -145,7 +145,9 @@ SIGNATURES = {
     "fk_day_adapter_fwd": (_int, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _int, _p]),
     "fk_day_adapter_bwd_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64]),
     "fk_day_adapter_bwd": (_int, [_p, _p, _p, _i64, _p, _p, _p, _sz, _i64, _i64, _i64, _i64, _i64, _p]),
+    "fk_augment_patchify": (_int, [_p, _p, _i64, _i64, _i64, _i64, _i64, _p, _p, _int, _p]),
 }
+AUG_MAX_SPANS = 8                                                                     # the most time spans fk_augment_patchify draws
 DAY_MAX_C = 512                                                                       # the envelope of fk_day_adapter_*
 ADAMW_MAX_SLOTS, GRAD_SUMSQ_MAX_BLOCKS = 16, 1024
 VQ_CHAIN, VQ_FUSED = 0, 1                                                             # fk_vq_route
@@ -161,6 +163,13 @@ VQ_ROWS = 32                                                                    
 class AdamwGroup(C.Structure):
     """fk_adamw_group: one slot's hyper-parameters as the host hands them to fk_adamw_step_groups"""
     _fields_ = [("lr", _f64), ("beta1", _f64), ("beta2", _f64), ("eps", _f64), ("weight_decay", _f64), ("step", _i64)]
+
+
+class AugmentCfg(C.Structure):
+    """fk_augment_cfg: the knobs of fk_augment_patchify, read on the host"""
+    _fields_ = [("white_sd", _f32), ("offset_sd", _f32), ("chan_drop_p", _f32), ("time_shift", C.c_int32), ("n_time_masks", C.c_int32),
+                ("time_mask_len", C.c_int32), ("keep_padding", C.c_int32), ("reserved", C.c_int32)]
+
 
 _lib = None
 

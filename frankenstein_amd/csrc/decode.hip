@@ -123,15 +123,6 @@ FK_DEV unsigned f32_sortable(float x) {          // monotone: a < b  <=>  key(a)
   const unsigned u = __float_as_uint(x);
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
-FK_DEV void philox4x32_10(unsigned k0, unsigned k1, unsigned (&c)[4]) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned long long p0 = 0xD2511F53ull * c[0], p1 = 0xCD9E8D57ull * c[2];
-    const unsigned n0 = (unsigned)(p1 >> 32) ^ c[1] ^ k0, n1 = (unsigned)p1, n2 = (unsigned)(p0 >> 32) ^ c[3] ^ k1, n3 = (unsigned)p0;
-    c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-}
 // maximum (MAX) or sum of v over the SAMPLE_THREADS of the block; red: one word per wave
 template <bool MAX> FK_DEV float block_reduce(float v, float* red) {
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;

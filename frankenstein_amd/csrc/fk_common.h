@@ -188,6 +188,18 @@ FK_DEV DropKey drop_key(const unsigned* seed_ptr, unsigned site, unsigned thresh
 FK_DEV unsigned drop_row(const DropKey& k, unsigned hi) { return fk_mix32(fk_mix32(hi ^ k.seed) + k.salt); }
 FK_DEV bool drop_keep(const DropKey& k, unsigned row, unsigned lo) { return fk_mix32(row ^ (lo * 0x9E3779B9u)) >= k.thresh; }
 
+// Philox4x32-10 (Salmon et al., SC'11): key (k0, k1), counter c -> four random words in place.  The generator of the sampler
+// (decode.hip) and of the signal augmentation (augment.hip); restated in tests/sample_ref.py.
+FK_DEV void philox4x32_10(unsigned k0, unsigned k1, unsigned (&c)[4]) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const unsigned long long p0 = 0xD2511F53ull * c[0], p1 = 0xCD9E8D57ull * c[2];
+    const unsigned n0 = (unsigned)(p1 >> 32) ^ c[1] ^ k0, n1 = (unsigned)p1, n2 = (unsigned)(p0 >> 32) ^ c[3] ^ k1, n3 = (unsigned)p0;
+    c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+}
+
 // Streaming output stores.  A line written once and not read again by the same launch can be stored non-temporal (global_store ... nt:
 // the L2 treats it as a streaming request), so that it does not push the operand panels the launch keeps re-reading out of the XCD's
 // 4-MiB L2 (with plain stores the up-projection fetched its 151-MB activation operand 6 times).

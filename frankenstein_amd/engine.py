@@ -13,6 +13,7 @@ from __future__ import annotations
 
 from typing import List, NamedTuple, Optional, Sequence, Tuple
 
+import dataclasses
 import math
 import os
 import weakref
@@ -474,6 +475,89 @@ class Dropout(torch.autograd.Function):
         return K.dropout(dy.contiguous(), d[0], d[1], d[2]), None
 
 
+# --------------------------------------------------------------------------------------------- signal augmentation
+# Training-time perturbation of the neural features, drawn inside the patch tokeniser (fk_augment_patchify; the rule is in
+# include/franken_hip.h and restated in tests/augment_ref.py).  Like dropout it owns a [seed, step] word pair on the device, a stream of
+# its own (advancing dropout does not move the augmentation and vice versa): augment_begin() adds 1 to the step word on the device, so a
+# captured training step draws fresh noise on every replay.  The tokens are saved for the backward, so nothing is ever regenerated and
+# no snapshot of the words is needed.
+_AUG_WORDS: dict = {}
+
+
+@dataclasses.dataclass(frozen=True)
+class AugmentConfig:
+    """The knobs of the signal augmentation; all zero = off.  white_sd / offset_sd: standard deviations of the per-frame white noise and
+    of the per-trial channel offset (in units of the z-scored signal); chan_drop_p: probability that an electrode is zeroed for a trial;
+    time_shift S: a shift of -S .. S frames per trial; n_time_masks spans of 0 .. time_mask_len frames are zeroed; keep_padding: all-zero
+    frames (padding) receive no noise."""
+    white_sd: float = 0.0
+    offset_sd: float = 0.0
+    chan_drop_p: float = 0.0
+    time_shift: int = 0
+    n_time_masks: int = 0
+    time_mask_len: int = 0
+    keep_padding: bool = True
+
+    @property
+    def active(self) -> bool:
+        return bool(self.white_sd > 0 or self.offset_sd > 0 or self.chan_drop_p > 0 or self.time_shift > 0
+                    or (self.n_time_masks > 0 and self.time_mask_len > 0))
+
+    @classmethod
+    def from_model_config(cls, config) -> "AugmentConfig":
+        """from the aug_* fields of MAEConfig / SimpleEncoderConfig (a config without them: everything off)"""
+        g = lambda name: getattr(config, name, 0) or 0
+        return cls(float(g("aug_white_sd")), float(g("aug_offset_sd")), float(g("aug_chan_drop")), int(g("aug_time_shift")),
+                   int(g("aug_time_masks")), int(g("aug_time_mask_len")))
+
+
+def augment_seed(initial_seed: int, rank: int = 0) -> int:
+    """The seed word: data-parallel ranks hold different samples and must not draw the same noise.  31 bits (an int32 tensor holds it)."""
+    return (int(initial_seed) + 0x9E3779B9 * int(rank)) & 0x7FFFFFFF
+
+
+def _dist_rank() -> int:
+    import torch.distributed as dist
+    return dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+
+
+def augment_words(device) -> Tensor:
+    """The [seed, step] words of `device` (int32, device memory; the same tensor for the life of the process).  A new torch.manual_seed
+    restarts the stream in place, never while capturing (a captured graph holds the tensor's address)."""
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    seed = augment_seed(torch.initial_seed(), _dist_rank())
+    ent = _AUG_WORDS.get(device)
+    if ent is None:
+        ent = _AUG_WORDS[device] = [seed, torch.tensor([seed, 0], dtype=torch.int32, device=device)]
+    elif ent[0] != seed and not torch.cuda.is_current_stream_capturing():
+        ent[0] = seed
+        ent[1].copy_(torch.tensor([seed, 0], dtype=torch.int32))
+    return ent[1]
+
+
+def augment_begin(device) -> Tensor:
+    """Start of a training forward with an active augmentation: step word + 1 on the device (inside a captured graph too).  Returns the words."""
+    words = augment_words(device)
+    words[1:].add_(1)
+    return words
+
+
+def augment_tokens(x: Tensor, P: int, ldp: int, dtype: torch.dtype, cfg: AugmentConfig, words: Optional[Tensor] = None) -> Tensor:
+    """to_patches(augment(x)) [B * (T / P) * C, ldp] drawn at the CURRENT step word (the caller has called augment_begin)"""
+    xin = x if x.dtype == torch.float32 else K.cast(x.contiguous(), torch.float32)
+    xin = xin.contiguous()
+    return K.augment_patchify(xin, P, ldp, dtype, cfg, augment_words(xin.device) if words is None else words)
+
+
+def augment_signal(x: Tensor, cfg: AugmentConfig, words: Optional[Tensor] = None) -> Tensor:
+    """The augmented [B, T, C] signal itself in fp32 (the kernel's P = 1 mode), drawn at the current step word: bit for bit what the
+    fused tokeniser patchifies at the same words."""
+    B, T, Cn = x.shape
+    return augment_tokens(x, 1, 1, torch.float32, cfg, words).view(B, T, Cn)
+
+
 # --------------------------------------------------------------------------------------------- functions
 class AttnBranch(torch.autograd.Function):
     """y = [x +] proj(SDPA(rope(q), rope(k), v)) with q,k,v = Linear([LN](x));  one pre-norm attention branch.
@@ -773,16 +857,17 @@ class LayerNormFn(torch.autograd.Function):
 
 class PatchEmbed(torch.autograd.Function):
     """tokens = Linear(patch -> dim)(to_patches(x)) + space_embedding[c]  (models/brainformer.py:338-343).
-    x is data (no gradient); K (= patch size) is zero-padded to a 16-byte multiple for the GEMM."""
+    x is data (no gradient); K (= patch size) is zero-padded to a 16-byte multiple for the GEMM.  aug: an active AugmentConfig in a
+    training forward (the caller has called augment_begin): the tokeniser launch draws the augmentation, one launch either way."""
 
     @staticmethod
-    def forward(ctx, x, emb_w, emb_b, space, P):
+    def forward(ctx, x, emb_w, emb_b, space, P, aug=None):
         B, T, Cn = x.shape
         d = emb_w.shape[0]
         dt = _COMPUTE_DTYPE
         kp = (P + 31) // 32 * 32
         xin = x if x.dtype == torch.float32 else K.cast(x.contiguous(), torch.float32)
-        tok = K.patchify(xin.contiguous(), P, kp, dt)
+        tok = K.patchify(xin.contiguous(), P, kp, dt) if aug is None else augment_tokens(xin, P, kp, dt, aug)
         sp = shadow([space.view(Cn, d)])
         h = K.gemm_nt(tok, shadow([emb_w], pad_k=kp), bias=shadow([emb_b]), residual=sp, res_rows=Cn)
         ctx.dims = (B, T // P, Cn, d, P)
@@ -797,7 +882,7 @@ class PatchEmbed(torch.autograd.Function):
         dw = K.gemm_tn(dh2, tok)[:, :P].contiguous()
         db = K.colsum(dh2)
         dspace = K.colsum(dh2.view(B * nT, Cn * d)).view(1, Cn, d)
-        return None, dw, db, dspace, None
+        return None, dw, db, dspace, None, None
 
 
 def day_ids(date_info, B: int, device) -> Optional[Tensor]:

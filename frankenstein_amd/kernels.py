@@ -4,6 +4,7 @@ fallback: every function ends in a libfranken_hip.so call.
 """
 from __future__ import annotations
 
+import ctypes
 import math
 from typing import Optional, Tuple
 
@@ -571,6 +572,25 @@ def day_adapter_bwd(x: Tensor, day: Optional[Tensor], d_tok: Tensor, P: int, del
         call("fk_day_adapter_bwd", x.data_ptr(), _ptr(day), d_tok.data_ptr(), ldp, d_delta.data_ptr(), d_bias.data_ptr(), _ptr(ws), nb,
              B, T, Cc, P, n_days, _stream())
     return d_delta, d_bias
+
+
+def augment_cfg_struct(cfg) -> _lib.AugmentCfg:
+    """fk_augment_cfg from an object with the knobs as attributes (engine.AugmentConfig)"""
+    return _lib.AugmentCfg(float(cfg.white_sd), float(cfg.offset_sd), float(cfg.chan_drop_p), int(cfg.time_shift), int(cfg.n_time_masks),
+                      int(cfg.time_mask_len), int(bool(cfg.keep_padding)), 0)
+
+
+def augment_patchify(x: Tensor, P: int, ldp: int, dtype: torch.dtype, cfg, words: Tensor) -> Tensor:
+    """fk_augment_patchify: tok [B * (T / P) * C, ldp] = patchify(augment(x)), drawn with the device words int32 [seed, step] (the rule:
+    include/franken_hip.h).  With every knob zero: fk_patchify's bits.  P = 1, ldp = 1, float32 is the augmented [B, T, C] signal itself."""
+    assert x.dtype == torch.float32 and x.dim() == 3 and x.is_contiguous()
+    assert words.dtype == torch.int32 and words.shape == (2,) and words.is_contiguous() and words.device == x.device
+    B, T, Cc = x.shape
+    c = augment_cfg_struct(cfg)
+    tok = torch.empty((B * (T // P) * Cc, ldp), dtype=dtype, device=x.device)
+    with _timed("augment_patchify"):
+        call("fk_augment_patchify", x.data_ptr(), tok.data_ptr(), B, T, Cc, P, ldp, ctypes.byref(c), words.data_ptr(), fk_dtype(dtype), _stream())
+    return tok
 
 
 def swiglu_fwd(h13: Tensor) -> Tensor:

@@ -49,6 +49,13 @@ class MAEConfig(Serializable):
     # decoder
     n_dec_layers: Optional[int] = 4
     decoder_dim: Optional[int] = 256
+    # training-time signal augmentation drawn inside the patch tokeniser (engine.AugmentConfig); all zero = off, no parameters
+    aug_white_sd: float = 0.0
+    aug_offset_sd: float = 0.0
+    aug_chan_drop: float = 0.0
+    aug_time_shift: int = 0
+    aug_time_masks: int = 0
+    aug_time_mask_len: int = 0
     # per-session input adapter (DayAdapter): number of recording sessions date_info indexes; 0 = no adapter, no extra parameter
     n_days: int = 0
 
@@ -344,10 +351,27 @@ class DayAdapter(nn.Module):
         E.bump_weight_epoch()
 
 
+class SignalAugment(nn.Module):
+    """Training-time signal augmentation as a parameter-free module, for callers that augment outside the encoder: in train() every
+    call advances the augmentation step word and returns engine.augment_signal(x, cfg), fp32 [B, T, C]; the identity in eval() and with
+    an all-zero config.  An Encoder whose config has aug_* fields does not need this: it draws inside its tokeniser."""
+
+    def __init__(self, cfg: "E.AugmentConfig"):
+        super().__init__()
+        self.cfg = cfg
+
+    def forward(self, x):
+        if not (self.training and self.cfg.active):
+            return x
+        E.augment_begin(x.device)
+        return E.augment_signal(x, self.cfg)
+
+
 class Encoder(nn.Module):
     def __init__(self, config):
         super().__init__()
         self.config = config
+        self.augment = E.AugmentConfig.from_model_config(config)      # a plain attribute: no parameter, no state-dict key
         self.patch_size = config.patch_size
         self.n_electrodes = config.n_electrodes
         self.n_patches_per_channel = config.window_size // config.patch_size
@@ -420,16 +444,28 @@ class Encoder(nn.Module):
             return False
         return date_info is not None or (torch.is_grad_enabled() and (ad.delta.requires_grad or ad.bias.requires_grad))
 
+    def augment_active(self) -> bool:
+        """does this forward draw the signal augmentation?  Only in train() with a knob on; otherwise nothing is launched or advanced."""
+        return self.training and self.augment.active
+
     def forward(self, x, kv_cache=None, date_info=None):
-        """x: [B, T, C] feature frames -> [B, (T/patch)*C, dim] tokens.  date_info: the sessions of the samples (DayAdapter)."""
+        """x: [B, T, C] feature frames -> [B, (T/patch)*C, dim] tokens.  date_info: the sessions of the samples (DayAdapter).
+        In train() with an active augmentation the tokeniser launch draws it (no extra pass); with a DayAdapter in play the augmented
+        signal is written once (engine.augment_signal, one extra pass) and the adapter's fused tokeniser and backward take it as x."""
         assert x.shape[2] == self.n_electrodes and x.shape[1] % self.patch_size == 0
+        aug = None
+        if self.augment_active():
+            E.augment_begin(x.device)
+            aug = self.augment
         if self.day_active(date_info):
             P = self.patch_size
+            if aug is not None:
+                x = E.augment_signal(x, aug)
             tok, carrier = self.day_adapter.tokens(x, date_info, P, (P + 31) // 32 * 32)
             h = E.PatchEmbedTok.apply(tok, self.transformer.emb.weight, self.transformer.emb.bias, self.space_embedding, P, carrier)
         else:
             h = E.PatchEmbed.apply(x, self.transformer.emb.weight, self.transformer.emb.bias, self.space_embedding,
-                                   self.patch_size)
+                                   self.patch_size, aug)
         T = h.shape[1]
         mask = Mask(MASK_BLOCK_CAUSAL, self.n_electrodes).sliced(self.block_size, self.block_size, T, T)   # attn_mask[-T:, -T:]
         rope = self.rope_cache
@@ -449,6 +485,8 @@ class MAE(nn.Module):
         self.config = config
         self.decoder_dim = config.decoder_dim
         self.encoder = Encoder(config)
+        if self.encoder.augment.time_shift != 0:             # the target is patchified from the clean, unshifted x
+            raise ValueError("MAE: aug_time_shift != 0 would reconstruct an unshifted target from a shifted input, a different task")
         self.decoder = nn.ModuleDict(dict(
             emb=nn.Identity(),
             h=nn.ModuleList([Block(config) for _ in range(config.n_dec_layers)]),
@@ -481,8 +519,13 @@ class MAE(nn.Module):
         kp = (P + 31) // 32 * 32
         xin = x if x.dtype == torch.float32 else x.float()
         adapt = enc.day_active(date_info)
+        aug = enc.augment if enc.augment_active() else None  # the encoder's input is augmented, the target stays clean: denoising
+        if aug is not None:
+            E.augment_begin(xin.device)
         if adapt:                                            # the adapter acts on the encoder's input; the target stays the raw patches
-            tok_all, carrier = enc.day_adapter.tokens(xin, date_info, P, kp)
+            tok_all, carrier = enc.day_adapter.tokens(xin if aug is None else E.augment_signal(xin, aug), date_info, P, kp)
+        elif aug is not None:
+            tok_all = E.augment_tokens(xin, P, kp, E.compute_dtype(), aug).view(B, (T // P) * Cn, kp)
         else:
             tok_all = K.patchify(xin.contiguous(), P, kp, E.compute_dtype()).view(B, (T // P) * Cn, kp)
         n_tokens = tok_all.shape[1]
@@ -505,7 +548,7 @@ class MAE(nn.Module):
         for block in self.decoder.h:
             dec = block(dec)
         pred = self.to_signals(E.GatherRows.apply(dec, masked))                    # [B, n_masked, P]
-        tok_p = tok_all if (kp == P and not adapt) else K.patchify(xin.contiguous(), P, P, E.compute_dtype()).view(B, n_tokens, P)
+        tok_p = tok_all if (kp == P and not adapt and aug is None) else K.patchify(xin.contiguous(), P, P, E.compute_dtype()).view(B, n_tokens, P)
         target = K.gather_rows(tok_p, masked)                                      # [B, n_masked, P] (data, no gradient)
         loss = E.mse_loss(pred, target)
         if return_preds:

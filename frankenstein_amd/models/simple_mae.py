@@ -32,6 +32,13 @@ class SimpleEncoderConfig(Serializable):
     n_heads: int = 4
     n_kv_heads: int = 4
     rope_theta: int = 10000
+    # training-time signal augmentation of the input frames (engine.AugmentConfig); all zero = off, no parameters
+    aug_white_sd: float = 0.0
+    aug_offset_sd: float = 0.0
+    aug_chan_drop: float = 0.0
+    aug_time_shift: int = 0
+    aug_time_masks: int = 0
+    aug_time_mask_len: int = 0
 
 
 @dataclass
@@ -71,6 +78,7 @@ class SimpleEncoder(nn.Module):
     def __init__(self, config):
         super().__init__()
         self.config = config
+        self.augment = E.AugmentConfig.from_model_config(config)      # a plain attribute: no parameter, no state-dict key
         self.transformer = nn.ModuleDict(dict(
             emb=Linear(config.patch_size, config.dim),
             h=nn.ModuleList([Block(config) for _ in range(config.n_layers)]),
@@ -98,11 +106,19 @@ class SimpleEncoder(nn.Module):
     def get_num_params(self):
         return sum(p.numel() for p in self.parameters())
 
-    def forward(self, x, attn_mask=None, rope_cache=None):
-        """x [B, T, C] frames (C = patch_size).  The reference slices the 2-D cache as rope[:T] (models/simple_mae:40)."""
+    def augment_active(self) -> bool:
+        return self.training and self.augment.active
+
+    def forward(self, x, attn_mask=None, rope_cache=None, augment=True):
+        """x [B, T, C] frames (C = patch_size).  The reference slices the 2-D cache as rope[:T] (models/simple_mae:40).
+        In train() with an active augmentation the frames are augmented first (engine.augment_signal; all-zero padding frames stay
+        zero); augment=False: the caller has done so already (SimpleMAE augments before it gathers the kept frames)."""
         attn_mask = self.attn_mask if attn_mask is None else attn_mask
         if rope_cache is None:
             rope_cache = self.rope_cache[: x.shape[1]]
+        if augment and self.augment_active():
+            E.augment_begin(x.device)
+            x = E.augment_signal(x, self.augment)
         h = self.transformer.emb(x)
         for block in self.transformer.h:
             h = block(h, attn_mask=attn_mask, rope=rope_cache)
@@ -114,6 +130,8 @@ class SimpleMAE(nn.Module):
         super().__init__()
         self.encoder_config = encoder_config
         self.encoder = SimpleEncoder(encoder_config)
+        if self.encoder.augment.time_shift != 0:             # the target frames are the clean, unshifted x
+            raise ValueError("SimpleMAE: aug_time_shift != 0 would reconstruct an unshifted target from a shifted input, a different task")
         self.dim = mae_config.dim
         self.decoder = nn.ModuleDict(dict(
             emb=Linear(encoder_config.dim, mae_config.dim),
@@ -146,7 +164,11 @@ class SimpleMAE(nn.Module):
         table = torch.view_as_real(self.encoder.rope_cache).reshape(self.encoder_config.block_size, -1)
         rope_u = K.gather_rows(table.contiguous(), unmasked).view(B, unmasked.shape[1], -1, 2)
         xc = E.to_compute(xin)                                                   # frames in the compute dtype
-        tokens = self.encoder(K.gather_rows(xc, unmasked), attn_mask=mask_u, rope_cache=rope_u)
+        xe = xc                                                                  # the encoder's input: augmented in train(); the target,
+        if self.encoder.augment_active():                                        # the padding mask and the loss weights stay the clean x's
+            E.augment_begin(xin.device)
+            xe = E.to_compute(E.augment_signal(xin, self.encoder.augment))
+        tokens = self.encoder(K.gather_rows(xe, unmasked), attn_mask=mask_u, rope_cache=rope_u, augment=False)
         dec = E.AssembleDecoder.apply(self.decoder.emb(tokens), self.mask_token, self.decoder_pos_emb.weight, unmasked, masked)
         for block in self.decoder.h:
             dec = block(dec, mask_all)

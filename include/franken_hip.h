@@ -888,6 +888,38 @@ int fk_day_adapter_bwd(const float* x, const int64_t* day, const float* d_tok, i
                        void* workspace, size_t workspace_bytes, int64_t B, int64_t T, int64_t C, int64_t P, int64_t n_days,
                        void* stream);
 
+/* ---- training-time signal augmentation inside the patch tokeniser (build-defined: the reference has none; float64 restatement in
+ *      tests/augment_ref.py).  One launch with fk_patchify's reads and writes; no noise or mask tensor exists.
+ * Random numbers: Philox4x32-10 with key (words[0], words[1]), `words` = int32 [2] ON THE DEVICE holding [seed, step] (the caller
+ *   advances the step word on the device, inside a captured graph too), counter (i0, i1, b, 0xA0610000 | kind) -> words w0..w3.
+ *   A pair of standard normals from a word pair (wa, wb):  u1 = ((wa >> 9) + 0.5) / 2^23  (24 bits: exact in fp32, never 0 or 1;
+ *   ((wa >> 8) + 0.5) / 2^24 would need 25 and round to 1.0 at the top),  u2 = (wb >> 8) / 2^24,  r = sqrt(-2 ln u1),
+ *   (r cos 2 pi u2, r sin 2 pi u2)  (logf, sqrtf, sincospif(2 u2)).  (w0, w1) gives normals 0 and 1 of a block, (w2, w3) normals 2, 3.
+ *     kind 1 white      (i0, i1) = (t, c >> 2)   normal c & 3 is n_w(b, t, c); t is the OUTPUT frame
+ *     kind 2 offset     (c >> 2, 0)              normal c & 3 is n_o(b, c), constant over time
+ *     kind 3 electrode  (c >> 2, 0)              channel c of sample b is dropped iff w[c & 3] < thresh,
+ *                                                thresh = min(floor(chan_drop_p * 2^32), 2^32 - 1) (host, double)
+ *     kind 4 span m     (m, 0), m < n_time_masks len = ((w0 >> 8) * (time_mask_len + 1)) >> 24, start = ((w1 >> 8) * (T - len + 1)) >> 24
+ *                                                (64-bit products); output frames start <= t < start + len are masked; spans may overlap
+ *     kind 5 shift      (0, 0)                   s_b = (((w0 >> 8) * (2 time_shift + 1)) >> 24) - time_shift, in [-time_shift, time_shift]
+ * Output element (b, t, c):
+ *   1. ts = t - s_b; outside [0, T): +0.  Otherwise src = x[b, ts, c].
+ *   2. keep_padding and noise on (white_sd > 0 or offset_sd > 0), and every channel of frame x[b, ts, :] exactly zero: +0 (the
+ *      pipeline pads with zeros and SimpleMAE recognises padding as all-zero frames: noise must not turn padding into data).
+ *   3. v = src + white_sd * n_w(b, t, c) + offset_sd * n_o(b, c) in fp32; a term whose sd is 0 is skipped, not multiplied by zero.
+ *   4. channel dropped, or t inside a span: +0.  Masks come last: a masked element is exactly zero, the z-scored mean.
+ *   5. one rounding to `dtype`; tok[b, (t / P) * C + c, p] for p < P, zeros for P <= p < ldp (fk_patchify's layout).
+ *   With every knob zero the result has fk_patchify's bits.  P = 1, ldp = 1, FK_F32 is the augmented [B, T, C] signal itself.
+ * Refused with FK_EINVAL on the host, before any launch: a null pointer, T % P != 0, ldp < P, a P * (C + 1) fp32 slab above 64 KiB,
+ *   a negative or non-finite sd, chan_drop_p outside [0, 1), n_time_masks outside [0, 8], time_mask_len outside [0, T], time_shift
+ *   outside [0, T), a dtype other than FK_F32 / FK_BF16, sizes beyond int32, misaligned pointers.  cfg is read on the host. */
+typedef struct fk_augment_cfg {
+  float white_sd, offset_sd, chan_drop_p;
+  int32_t time_shift, n_time_masks, time_mask_len, keep_padding, reserved;
+} fk_augment_cfg;
+int fk_augment_patchify(const float* x, void* tok, int64_t B, int64_t T, int64_t C, int64_t P, int64_t ldp, const fk_augment_cfg* cfg,
+                        const uint32_t* words, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
