@@ -146,7 +146,14 @@ SIGNATURES = {
     "fk_day_adapter_bwd_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64]),
     "fk_day_adapter_bwd": (_int, [_p, _p, _p, _i64, _p, _p, _p, _sz, _i64, _i64, _i64, _i64, _i64, _p]),
     "fk_augment_patchify": (_int, [_p, _p, _i64, _i64, _i64, _i64, _i64, _p, _p, _int, _p]),
+    "fk_lora_route": (_int, [_i64, _i64, _i64, _i64, _int]),
+    "fk_lora_fwd": (_int, [_p, _i64, _p, _p, _i64, _i64, _i64, _i64, _f32, _i64, _f32, _p, _i64, _p, _p, _i64, _int, _p]),
+    "fk_lora_wgrad_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),
+    "fk_lora_wgrad": (_int, [_p, _p, _p, _p, _i64, _i64, _i64, _i64, _f32, _p, _p, _int, _int, _p, _sz, _p]),
+    "fk_lora_merge": (_int, [_p, _p, _p, _i64, _i64, _i64, _f32, _p, _i64, _int, _p]),
 }
+LORA_R32, LORA_R64 = 0, 1                                                             # fk_lora_route
+LORA_FWD_ROWS, LORA_WGRAD_ROWS = 32, 64                                               # rows per workgroup / per slice of fk_lora_fwd / fk_lora_wgrad
 AUG_MAX_SPANS = 8                                                                     # the most time spans fk_augment_patchify draws
 DAY_MAX_C = 512                                                                       # the envelope of fk_day_adapter_*
 ADAMW_MAX_SLOTS, GRAD_SUMSQ_MAX_BLOCKS = 16, 1024

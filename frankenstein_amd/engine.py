@@ -74,15 +74,19 @@ def _arena_grad(p: Tensor):
     return g if (g is not None and getattr(p, "_fk_arena", False) and g.is_contiguous()) else None
 
 
-def wgrad_path(in_arena: Sequence[bool], swiglu_interleaved: bool = False, slab_ok: bool = False, adjacent: bool = False) -> str:
+def wgrad_path(in_arena: Sequence[bool], swiglu_interleaved: bool = False, slab_ok: bool = False, adjacent: bool = False,
+               requires_grad: Optional[Sequence[bool]] = None) -> str:
     """Where wgrad puts the gradients of one row-concatenated weight group (host-side, no GPU).  in_arena: per parameter, whether its
     .grad is a contiguous view of the gradient arena; slab_ok: K.gemm_tn_swiglu_ok of the product; adjacent: the arena views follow
-    each other in memory in the order of the group.
+    each other in memory in the order of the group; requires_grad: per parameter (None: all of them do).
+      "skip"        no parameter of the group requires grad (a frozen base): no launch, Nones
       "tensors"     one parameter is outside the arena: gemm_tn into a temporary, split (or de-interleaved) and handed to autograd
       "swiglu_slab" gemm_tn_swiglu_: the slab reduction adds the de-interleaved rows to both arena views
       "swiglu_add"  gemm_tn into a temporary, two add2d_ into the arena views
       "adjacent"    gemm_tn accumulates into the arena views as one [sum N, K] matrix
       "split_add"   gemm_tn into a temporary, one add2d_ per parameter"""
+    if requires_grad is not None and not any(requires_grad):
+        return "skip"
     if not all(in_arena):
         return "tensors"
     if swiglu_interleaved:
@@ -102,7 +106,10 @@ def wgrad(a: Tensor, b: Tensor, params: Sequence[Tensor], swiglu_interleaved: bo
     side = _WGRAD_STREAM
     grads = [_arena_grad(p) for p in params]
     in_arena = [g is not None for g in grads]
-    if wgrad_path(in_arena, swiglu_interleaved) == "tensors":
+    first = wgrad_path(in_arena, swiglu_interleaved, requires_grad=[p.requires_grad for p in params])
+    if first == "skip":
+        return [None] * len(params)
+    if first == "tensors":
         dw = K.gemm_tn(a, b)
         if swiglu_interleaved:
             return list(_deinterleave_rows(dw, params[0].shape[0]))
@@ -153,11 +160,15 @@ def norm_bwd(dh: Tensor, x2: Tensor, ln_w: Tensor, ln_b: Optional[Tensor], mean:
 class _Shadow:
     """One compute-dtype weight copy.  `jobs` are the fk_cast_pack_rows calls that fill `tensor` from the masters
     (src, dst view, transpose, rblk, rstride, roff); `params` are weak references (a shadow dies with its model)."""
-    __slots__ = ("stamp", "tensor", "jobs", "params", "dtype", "ptrs", "repack")
+    __slots__ = ("stamp", "tensor", "jobs", "params", "dtype", "ptrs", "repack", "trained")
 
     def __init__(self):
         self.stamp, self.tensor, self.jobs, self.params, self.dtype, self.ptrs = None, None, [], (), None, ()
         self.repack = None       # shadows whose layout is not a cast_pack job (convolution weights): callable that refills `tensor` in place
+        self.trained = None      # the masters an optimizer must own for refresh_shadows to re-pack this shadow (None: all of `params`)
+
+    def owned_by(self, ids) -> bool:
+        return all(id(r()) in ids for r in (self.params if self.trained is None else self.trained))
 
     def alive(self) -> bool:
         """masters still exist and still live where the pack jobs read them (ParamArena moves parameter storage)"""
@@ -265,6 +276,32 @@ def shadow_swiglu(w1: Tensor, w3: Tensor, transpose: bool = False) -> Tensor:
     return ent.tensor
 
 
+def shadow_lora(w: Tensor, A: Tensor, B: Tensor, scale: float, pad_n: int = 0) -> Tensor:
+    """Compute-dtype shadow of the MERGED weight w + scale * (B A) ([N, K], rows zero-padded to pad_n), straight from the three fp32
+    masters (fk_lora_merge: the bits of casting the merged fp32 master).  Stamped on the epoch and on the versions of all three
+    tensors; refilled IN PLACE, also by refresh_shadows when the optimizer owns A and B (w is frozen and in no optimizer), so a
+    captured decode graph sees every step.  Every inference path reads it in place of shadow([w]): no extra launch per step."""
+    dt = _COMPUTE_DTYPE
+    key = (("lora", w.data_ptr(), A.data_ptr(), B.data_ptr(), tuple(w.shape), tuple(A.shape), float(scale)), pad_n, dt)
+    ent = _shadow_entry(key, (w, A, B))
+    stamp = ent.current_stamp()
+    if ent.stamp == stamp:
+        return ent.tensor
+    refs = ent.params
+
+    def pack():
+        wd, ad, bd = (r().detach() for r in refs)
+        n = wd.shape[0]
+        if ent.tensor is None:
+            ent.tensor = (torch.zeros if pad_n > n else torch.empty)((max(n, pad_n), wd.shape[1]), dtype=dt, device=wd.device)
+        K.lora_merge(wd, ad, bd, scale, out=ent.tensor[:n])      # in place: the storage a captured GEMM reads stays the same
+
+    ent.repack, ent.trained = pack, refs[1:]
+    pack()
+    ent.stamp = stamp
+    return ent.tensor
+
+
 def refresh_shadows(params: Sequence[Tensor]) -> None:
     """Re-pack, in ONE launch (fk_cast_pack_multi), every shadow built so far whose masters all belong to `params` — called by
     the optimizer right after it updated the masters (one launch per step instead of one or two per weight)."""
@@ -274,7 +311,7 @@ def refresh_shadows(params: Sequence[Tensor]) -> None:
     # shadows with their own in-place re-pack (convolution weights): refreshed here too, so that a captured graph, which keeps
     # reading the shadow's storage, sees every optimizer step (they used to be rebuilt lazily into NEW storage by the eager forward only)
     for e in _SHADOWS.values():
-        if e.repack is not None and e.tensor is not None and e.dtype == _COMPUTE_DTYPE and all(id(r()) in ids for r in e.params):
+        if e.repack is not None and e.tensor is not None and e.dtype == _COMPUTE_DTYPE and e.owned_by(ids):
             e.repack()
             e.stamp = e.current_stamp()
     ents = [e for e in _SHADOWS.values()
@@ -559,6 +596,23 @@ def augment_signal(x: Tensor, cfg: AugmentConfig, words: Optional[Tensor] = None
 
 
 # --------------------------------------------------------------------------------------------- functions
+def _lora_add(x2: Tensor, A: Tensor, B: Tensor, scale: float, y: Tensor, q_cols: int = 0, q_scale: float = 1.0) -> Tensor:
+    """y += scale * colscale * ((x2 A^T) B^T) in ONE launch (fk_lora_fwd, in place on y); returns u = x2 A^T for the backward"""
+    _, u = K.lora_fwd(x2, shadow([A]), shadow([B]), scale, res=y, out=y, q_cols=q_cols, q_scale=q_scale)
+    return u
+
+
+def _lora_backward(dy2: Tensor, x2: Tensor, u: Tensor, A: Tensor, B: Tensor, scale: float, dx: Tensor):
+    """The adapter's share of a Linear's backward: dx += scale * (dy2 B) A in one launch (fk_lora_fwd on the transposed shadows), then
+    dA, dB in one fk_lora_wgrad — accumulated straight into the gradient arena when both live there (Nones), tensors otherwise."""
+    _, du = K.lora_fwd(dy2, shadow([B], transpose=True), shadow([A], transpose=True), scale, res=dx, out=dx)
+    gA, gB = _arena_grad(A), _arena_grad(B)
+    if gA is not None and gB is not None:
+        K.lora_wgrad(dy2, u, du, x2, scale, dA=gA, dB=gB, accumulate=True)
+        return None, None
+    return K.lora_wgrad(dy2, u, du, x2, scale)
+
+
 class AttnBranch(torch.autograd.Function):
     """y = [x +] proj(SDPA(rope(q), rope(k), v)) with q,k,v = Linear([LN](x));  one pre-norm attention branch.
 
@@ -567,6 +621,16 @@ class AttnBranch(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, ln_w, ln_b, pw, pb, qkv_b, spec, *qkv_w):
+        return AttnBranch.run_forward(ctx, x, ln_w, ln_b, pw, pb, qkv_b, spec, qkv_w, None)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return AttnBranch.run_backward(ctx, dy)[0]
+
+    @staticmethod
+    def run_forward(ctx, x, ln_w, ln_b, pw, pb, qkv_b, spec, qkv_w, lora):
+        """the body of forward; lora = (scale, A_qkv, B_qkv, A_proj, B_proj), either pair None, for the adapted form (AttnBranchLora):
+        the correction joins c_attn's output with the query scale applied, and c_proj's output before the residual dropout"""
         H, D, mask, rope, residual, eps, nkind = spec[:7]
         drop = spec[7] if len(spec) > 7 else None       # (p, seed words, site of the attention dropout, site of the residual dropout)
         B, N, d = x.shape
@@ -592,6 +656,10 @@ class AttnBranch(torch.autograd.Function):
             qkv = K.gemm_nt_rope(h, shadow(qkv_w), bq, tab, 8, 0, D, 2 * HD, q_cols=HD, q_table=qtab)
         else:
             qkv = K.gemm_nt(h, shadow(qkv_w), bias=bq)
+        u_q = u_p = None
+        if lora is not None and lora[1] is not None:
+            assert rope is None, "adapters on a rotated projection are not supported (GPT-2 branches have no RoPE)"
+            u_q = _lora_add(h, lora[1], lora[2], lora[0], qkv, HD if prescale else 0, (1.0 / math.sqrt(D)) * 1.4426950408889634)
         qkv3 = qkv.view(B, N, 3 * HD)
         if path == "plain_rope":
             K.rope_(qkv3, 2 * H, D, rope.table, rope.pos_off(N))
@@ -600,24 +668,34 @@ class AttnBranch(torch.autograd.Function):
         if drop is None:
             y = K.gemm_nt(o.view(M, HD), shadow([pw]), bias=None if pb is None else shadow([pb]),
                           residual=x2 if residual else None)
+            if lora is not None and lora[3] is not None:     # x + c_proj(o) + delta: added to the finished row, one launch
+                u_p = _lora_add(o.view(M, HD), lora[3], lora[4], lora[0], y)
         else:                                           # x + resid_dropout(c_proj(y))  (models/gpt2_model.py:75,104)
             y = K.gemm_nt(o.view(M, HD), shadow([pw]), bias=None if pb is None else shadow([pb]))
+            if lora is not None and lora[3] is not None:     # x + drop(c_proj(o) + delta)
+                u_p = _lora_add(o.view(M, HD), lora[3], lora[4], lora[0], y)
             K.dropout(y, drop[0], drop[1], drop[3], residual=x2 if residual else None, out=y)
         ctx.spec, ctx.has_ln, ctx.nw, ctx.prescale = spec, has_ln, len(qkv_w), prescale
         ctx.flags = (ln_b is not None, pb is not None, qkv_b is not None)
         ctx.ln_b = ln_b
-        ctx.save_for_backward(x, ln_w, pw, *qkv_w, h if has_ln else None, mean, rstd, qkv, o, lse)
+        ctx.lora_scale = None if lora is None else lora[0]
+        extra = () if lora is None else (lora[1], lora[2], lora[3], lora[4], u_q, u_p)
+        ctx.save_for_backward(x, ln_w, pw, *qkv_w, h if has_ln else None, mean, rstd, qkv, o, lse, *extra)
         return y.view(B, N, -1)
 
     @staticmethod
-    def backward(ctx, dy):
+    def run_backward(ctx, dy):
+        """the body of backward -> (the gradients of forward's inputs, (dA_qkv, dB_qkv, dA_proj, dB_proj) of the adapted form or None)"""
         H, D, mask, rope, residual, eps, nkind = ctx.spec[:7]
         drop = ctx.spec[7] if len(ctx.spec) > 7 else None
         sv = ctx.saved_tensors
         x, ln_w, pw = sv[0], sv[1], sv[2]
         qkv_w = sv[3:3 + ctx.nw]
-        h, mean, rstd, qkv, o, lse = sv[3 + ctx.nw:]
+        h, mean, rstd, qkv, o, lse = sv[3 + ctx.nw:9 + ctx.nw]
+        lora = sv[9 + ctx.nw:] if ctx.lora_scale is not None else None
+        dlora = [None] * 4
         has_lnb, has_pb, has_qb = ctx.flags
+        has_pb, has_qb = has_pb and ctx.needs_input_grad[4], has_qb and ctx.needs_input_grad[5]     # a frozen bias: no column sum
         B, N, d = x.shape
         M, HD = B * N, H * D
         x2 = x.view(M, d)
@@ -626,6 +704,8 @@ class AttnBranch(torch.autograd.Function):
         dy2 = dy.contiguous().view(M, -1)
         dyp = dy2 if drop is None else K.dropout(dy2, drop[0], drop[1], drop[3])        # the gradient behind the residual dropout
         do = K.gemm_nt(dyp, shadow([pw], transpose=True))
+        if lora is not None and lora[2] is not None:
+            dlora[2], dlora[3] = _lora_backward(dyp, o.view(M, HD), lora[5], lora[2], lora[3], ctx.lora_scale, do)
         (dpw,) = wgrad(dyp, o.view(M, HD), [pw])
         dpb = K.colsum(dyp) if has_pb else None
         dqkv = torch.empty_like(qkv)
@@ -641,13 +721,30 @@ class AttnBranch(torch.autograd.Function):
             if rpath == "kernel":
                 K.rope_(dqkv3, 2 * H, D, rope.table, rope.pos_off(N), conj=True)
         dh = K.gemm_nt(dqkv, shadow(qkv_w, transpose=True))
+        if lora is not None and lora[0] is not None:     # dqkv is the gradient w.r.t. the UNSCALED q | k | v: no column scale here
+            dlora[0], dlora[1] = _lora_backward(dqkv, h, lora[4], lora[0], lora[1], ctx.lora_scale, dh)
         dws = wgrad(dqkv, h, list(qkv_w))
         dqb = K.colsum(dqkv) if has_qb else None
         if ctx.has_ln:
             dx, dg, db = norm_bwd(dh, x2, ln_w, ctx.ln_b, mean, rstd, dres=dy2 if residual else None, kind=nkind)
         else:
             dx, dg, db = (K.add(dh, dy2) if residual else dh), None, None
-        return (dx.view(B, N, d), dg, db, dpw, dpb, dqb, None, *dws)
+        return (dx.view(B, N, d), dg, db, dpw, dpb, dqb, None, *dws), (None if lora is None else dlora)
+
+
+class AttnBranchLora(torch.autograd.Function):
+    """AttnBranch with low-rank adapters on c_attn and / or the attention c_proj (csrc/lora.hip); the base GEMMs, their routes and the
+    frozen-parameter rules are AttnBranch's.  lora = (A_qkv [r, d], B_qkv [3 H D, r], A_proj [r, H D], B_proj [d, r]), a pair may be
+    None; scale = alpha / r.  The adapters are inputs, so autograd sees them."""
+
+    @staticmethod
+    def forward(ctx, x, ln_w, ln_b, pw, pb, qkv_b, spec, scale, a_qkv, b_qkv, a_proj, b_proj, *qkv_w):
+        return AttnBranch.run_forward(ctx, x, ln_w, ln_b, pw, pb, qkv_b, spec, qkv_w, (scale, a_qkv, b_qkv, a_proj, b_proj))
+
+    @staticmethod
+    def backward(ctx, dy):
+        g, dl = AttnBranch.run_backward(ctx, dy)
+        return (*g[:7], None, *dl, *g[7:])
 
 
 class CrossAttnBranch(torch.autograd.Function):
@@ -724,6 +821,16 @@ class MlpBranch(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, ln_w, ln_b, up_w, up_b, gate_w, down_w, down_b, spec):
+        return MlpBranch.run_forward(ctx, x, ln_w, ln_b, up_w, up_b, gate_w, down_w, down_b, spec, None)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return MlpBranch.run_backward(ctx, dy)[0]
+
+    @staticmethod
+    def run_forward(ctx, x, ln_w, ln_b, up_w, up_b, gate_w, down_w, down_b, spec, lora):
+        """the body of forward; lora = (scale, A_up, B_up, A_down, B_down), either pair None, for the adapted form (MlpBranchLora, the
+        GELU MLP only): the correction joins c_fc's pre-activation before the GELU and c_proj's output before the dropout"""
         residual, eps, nkind = spec[:3]
         drop = spec[3] if len(spec) > 3 else None       # (p, seed words, site): dropout on the down-projection's output
         shp = x.shape
@@ -735,30 +842,45 @@ class MlpBranch(torch.autograd.Function):
         else:
             h, mean, rstd = x2, None, None
         fused = mlp_path(up_w.shape[0], gate_w is not None, up_b is not None) == "swiglu_fused"
-        if fused:     # up-projection + SwiGLU in one kernel (interleaved hidden layout)
+        u_up = u_down = None
+        if fused:    # up-projection + SwiGLU in one kernel (interleaved hidden layout)
             a, g = K.gemm_nt_swiglu(h, shadow_swiglu(up_w, gate_w))
         else:
             ups = [up_w] if gate_w is None else [up_w, gate_w]
             a = K.gemm_nt(h, shadow(ups), bias=None if up_b is None else shadow([up_b]))
+            if lora is not None and lora[1] is not None:
+                assert gate_w is None, "adapters are built for the GELU MLP"
+                u_up = _lora_add(h, lora[1], lora[2], lora[0], a)
             g = K.gelu_fwd(a) if gate_w is None else K.swiglu_fwd(a)
+        assert lora is None or not fused, "adapters are built for the GELU MLP"
         if drop is None:
             y = K.gemm_nt(g, shadow([down_w]), bias=None if down_b is None else shadow([down_b]),
                           residual=x2 if residual else None)
+            if lora is not None and lora[3] is not None:     # x + c_proj(g) + delta: added to the finished row, one launch
+                u_down = _lora_add(g, lora[3], lora[4], lora[0], y)
         else:                                           # x + dropout(c_proj(gelu(c_fc(x))))  (models/gpt2_model.py:87-92,105)
             y = K.gemm_nt(g, shadow([down_w]), bias=None if down_b is None else shadow([down_b]))
+            if lora is not None and lora[3] is not None:     # x + drop(c_proj(g) + delta)
+                u_down = _lora_add(g, lora[3], lora[4], lora[0], y)
             K.dropout(y, drop[0], drop[1], drop[2], residual=x2 if residual else None, out=y)
         ctx.spec, ctx.has_ln, ctx.fused = spec, has_ln, fused
         ctx.flags = (ln_b is not None, up_b is not None, gate_w is not None, down_b is not None)
         ctx.ln_b = ln_b
-        ctx.save_for_backward(x, ln_w, up_w, gate_w, down_w, h if has_ln else None, mean, rstd, a, g)
+        ctx.lora_scale = None if lora is None else lora[0]
+        extra = () if lora is None else (lora[1], lora[2], lora[3], lora[4], u_up, u_down)
+        ctx.save_for_backward(x, ln_w, up_w, gate_w, down_w, h if has_ln else None, mean, rstd, a, g, *extra)
         return y.view(*shp[:-1], y.shape[-1])
 
     @staticmethod
-    def backward(ctx, dy):
+    def run_backward(ctx, dy):
+        """the body of backward -> (the gradients of forward's inputs, (dA_up, dB_up, dA_down, dB_down) of the adapted form or None)"""
         residual, eps, nkind = ctx.spec[:3]
         drop = ctx.spec[3] if len(ctx.spec) > 3 else None
-        x, ln_w, up_w, gate_w, down_w, h, mean, rstd, a, g = ctx.saved_tensors
+        x, ln_w, up_w, gate_w, down_w, h, mean, rstd, a, g = ctx.saved_tensors[:10]
+        lora = ctx.saved_tensors[10:] if ctx.lora_scale is not None else None
+        dlora = [None] * 4
         has_lnb, has_ub, gated, has_db = ctx.flags
+        has_ub, has_db = has_ub and ctx.needs_input_grad[4], has_db and ctx.needs_input_grad[7]     # a frozen bias: no column sum
         shp = x.shape
         d = shp[-1]
         x2 = x.reshape(-1, d)
@@ -781,15 +903,33 @@ class MlpBranch(torch.autograd.Function):
             dups = wgrad(da, h, [up_w, gate_w], swiglu_interleaved=True)
         else:
             dg_ = K.gemm_nt(dyd, shadow([down_w], transpose=True))
+            if lora is not None and lora[2] is not None:
+                dlora[2], dlora[3] = _lora_backward(dyd, g, lora[5], lora[2], lora[3], ctx.lora_scale, dg_)
             da = K.swiglu_bwd(a, dg_) if gated else K.gelu_bwd(a, dg_)
             dh = K.gemm_nt(da, shadow(ups, transpose=True))
+            if lora is not None and lora[0] is not None:
+                dlora[0], dlora[1] = _lora_backward(da, h, lora[4], lora[0], lora[1], ctx.lora_scale, dh)
             dups = wgrad(da, h, ups)
         dub = K.colsum(da) if has_ub else None
         if ctx.has_ln:
             dx, dgam, dbet = norm_bwd(dh, x2, ln_w, ctx.ln_b, mean, rstd, dres=dy2 if residual else None, kind=nkind)
         else:
             dx, dgam, dbet = (K.add(dh, dy2) if residual else dh), None, None
-        return (dx.view(shp), dgam, dbet, dups[0], dub, dups[1] if gated else None, ddown, ddb, None)
+        return (dx.view(shp), dgam, dbet, dups[0], dub, dups[1] if gated else None, ddown, ddb, None), (None if lora is None else dlora)
+
+
+class MlpBranchLora(torch.autograd.Function):
+    """MlpBranch (the GELU MLP) with low-rank adapters on c_fc and / or c_proj (csrc/lora.hip); the base GEMMs, their routes and the
+    frozen-parameter rules are MlpBranch's.  (A_up [r, d], B_up [hidden, r], A_down [r, hidden], B_down [d, r]), a pair may be None."""
+
+    @staticmethod
+    def forward(ctx, x, ln_w, ln_b, up_w, up_b, gate_w, down_w, down_b, spec, scale, a_up, b_up, a_down, b_down):
+        return MlpBranch.run_forward(ctx, x, ln_w, ln_b, up_w, up_b, gate_w, down_w, down_b, spec, (scale, a_up, b_up, a_down, b_down))
+
+    @staticmethod
+    def backward(ctx, dy):
+        g, dl = MlpBranch.run_backward(ctx, dy)
+        return (*g, None, *dl)
 
 
 class NormLinear(torch.autograd.Function):
@@ -831,8 +971,8 @@ class NormLinear(torch.autograd.Function):
         else:
             dyp = dy2
         dh = K.gemm_nt(dyp, shadow([w], transpose=True, pad_n=npad))
-        dw = K.gemm_tn(dyp, h)[:nout]
-        db = K.colsum(dy2) if has_b else None
+        dw = K.gemm_tn(dyp, h)[:nout] if ctx.needs_input_grad[3] else None      # a frozen weight: no product
+        db = K.colsum(dy2) if has_b and ctx.needs_input_grad[4] else None
         if ctx.has_ln:
             dx, dg, dbe = norm_bwd(dh, x2, ln_w, ctx.ln_b, mean, rstd)
         else:
@@ -1355,9 +1495,11 @@ class HeadCrossEntropy(torch.autograd.Function):
         dlT, db = K.head_ce_bwd(h, wsh, bsh, tg, lse, loss2, g, V, npad, rows_pad, has_b, ignore_index)
         dh32 = K.gemm_tn(dlT, wsh)                                          # [rows_pad, d] = sum_v dlT[v, m] W[v, :]
         dh = dh32[:rows] if h.dtype == torch.float32 else K.cast(dh32[:rows], h.dtype)
-        hT = torch.zeros((d, rows_pad), dtype=h.dtype, device=h.device)
-        K.transpose2d(h, out=hT)
-        dw = K.gemm_nt(dlT, hT, out_dtype=torch.float32)[:V]                # [V, d] = sum_m dlT[v, m] H[m, :]
+        dw = None
+        if ctx.needs_input_grad[3]:                                         # a frozen head: neither the transpose nor the [V, d] product
+            hT = torch.zeros((d, rows_pad), dtype=h.dtype, device=h.device)
+            K.transpose2d(h, out=hT)
+            dw = K.gemm_nt(dlT, hT, out_dtype=torch.float32)[:V]            # [V, d] = sum_m dlT[v, m] H[m, :]
         if has_ln:
             dx, dg, dbe = norm_bwd(dh, x2, ln_w, ctx.ln_b, mean, rstd)
         else:

@@ -593,6 +593,72 @@ def augment_patchify(x: Tensor, P: int, ldp: int, dtype: torch.dtype, cfg, words
     return tok
 
 
+# ------------------------------------------------------------------------------------------- low-rank adapters (csrc/lora.hip)
+def lora_route(M: int, N: int, K: int, r: int, dtype) -> int:
+    """fk_lora_route: the forward's kernel variant (_lib.LORA_R32 / LORA_R64), or -1 outside the envelope"""
+    return lib().fk_lora_route(M, N, K, r, dtype if isinstance(dtype, int) else fk_dtype(dtype))
+
+
+def lora_fwd(x: Tensor, a: Tensor, b: Tensor, scale: float, res: Optional[Tensor] = None, out: Optional[Tensor] = None,
+             q_cols: int = 0, q_scale: float = 1.0, want_u: bool = True) -> Tuple[Tensor, Optional[Tensor]]:
+    """fk_lora_fwd: (out, u) with u [M, r] = round(x a^T) and out [M, N] = (res or 0) + scale * colscale * (u b^T); a [r, K], b [N, r] in
+    x's dtype.  res may be `out` itself (in place).  The data gradient is lora_fwd(dy, b_t, a_t, scale, res=dh, out=dh)."""
+    assert x.dim() == 2 and x.stride(1) == 1 and a.dim() == 2 and b.dim() == 2 and a.is_contiguous() and b.is_contiguous()
+    assert a.dtype == x.dtype and b.dtype == x.dtype
+    M, K = x.shape
+    r, N = a.shape[0], b.shape[0]
+    assert a.shape == (r, K) and b.shape == (N, r), (x.shape, a.shape, b.shape)
+    if out is None:
+        out = torch.empty((M, N), dtype=x.dtype, device=x.device)
+    assert out.shape == (M, N) and out.stride(1) == 1 and out.dtype == x.dtype
+    ldr = 0
+    if res is not None:
+        assert res.shape == (M, N) and res.stride(1) == 1 and res.dtype == x.dtype
+        ldr = res.stride(0)
+    u = torch.empty((M, r), dtype=x.dtype, device=x.device) if want_u else None
+    with _timed(f"lora_fwd:{M}x{N}x{K}x{r}"):
+        call("fk_lora_fwd", x.data_ptr(), x.stride(0), a.data_ptr(), b.data_ptr(), M, N, K, r, scale, q_cols, q_scale, _ptr(res), ldr,
+             _ptr(u), out.data_ptr(), out.stride(0), fk_dtype(x), _stream())
+    return out, u
+
+
+def lora_wgrad(dy: Tensor, u: Tensor, du: Tensor, x: Tensor, scale: float, dA: Optional[Tensor] = None, dB: Optional[Tensor] = None,
+               accumulate: bool = False) -> Tuple[Tensor, Tensor]:
+    """fk_lora_wgrad: dB [N, r] (+)= scale * dy^T u and dA [r, K] (+)= scale * du^T x in fp32, du the unscaled dy b of the transposed
+    lora_fwd call; the row slices are added in a fixed order (same bits on every run)."""
+    assert dy.dim() == 2 and x.dim() == 2 and dy.is_contiguous() and x.is_contiguous() and u.is_contiguous() and du.is_contiguous()
+    M, N = dy.shape
+    K, r = x.shape[1], u.shape[1]
+    assert x.shape[0] == M and u.shape == (M, r) and du.shape == (M, r) and dy.dtype == x.dtype == u.dtype == du.dtype
+    if dA is None or dB is None:
+        assert not accumulate and dA is None and dB is None
+        dA = torch.empty((r, K), dtype=torch.float32, device=x.device)
+        dB = torch.empty((N, r), dtype=torch.float32, device=x.device)
+    assert dA.shape == (r, K) and dB.shape == (N, r) and dA.dtype == dB.dtype == torch.float32 and dA.is_contiguous() and dB.is_contiguous()
+    ws, nb = _ws(lib().fk_lora_wgrad_workspace_bytes(M, N, K, r), x.device)
+    with _timed(f"lora_wgrad:{M}x{N}x{K}x{r}"):
+        call("fk_lora_wgrad", dy.data_ptr(), u.data_ptr(), du.data_ptr(), x.data_ptr(), M, N, K, r, scale, dA.data_ptr(), dB.data_ptr(),
+             int(accumulate), fk_dtype(x), _ptr(ws), nb, _stream())
+    return dA, dB
+
+
+def lora_merge(w: Tensor, a: Tensor, b: Tensor, scale: float, out_dtype: Optional[torch.dtype] = None, out: Optional[Tensor] = None) -> Tensor:
+    """fk_lora_merge: out [N, K] = w + scale * (b a) from the fp32 masters, an fp32 fma chain over r; out_dtype float32 (may be w itself)
+    or bfloat16 (the rounding of that same fp32 value)."""
+    assert w.dim() == 2 and w.is_contiguous() and a.is_contiguous() and b.is_contiguous()
+    assert w.dtype == a.dtype == b.dtype == torch.float32
+    N, K = w.shape
+    r = a.shape[0]
+    assert a.shape == (r, K) and b.shape == (N, r)
+    odt = out_dtype or (out.dtype if out is not None else torch.float32)
+    if out is None:
+        out = torch.empty((N, K), dtype=odt, device=w.device)
+    assert out.shape == (N, K) and out.stride(1) == 1 and out.dtype == odt
+    with _timed("lora_merge"):
+        call("fk_lora_merge", w.data_ptr(), a.data_ptr(), b.data_ptr(), N, K, r, scale, out.data_ptr(), out.stride(0), fk_dtype(odt), _stream())
+    return out
+
+
 def swiglu_fwd(h13: Tensor) -> Tensor:
     assert h13.dim() == 2 and h13.is_contiguous()
     rows, H2 = h13.shape

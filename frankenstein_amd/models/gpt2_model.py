@@ -37,6 +37,15 @@ class LayerNorm(nn.Module):
         return E.LayerNormFn.apply(_prep(input), self.weight, self.bias, self.eps, K.NORM_LAYER)
 
 
+LORA_TARGETS = ("c_attn", "attn.c_proj", "c_fc", "mlp.c_proj")      # the adaptable Linears of a block (GPT.add_lora)
+
+
+def _lora_of(lin):
+    """(lora_A, lora_B, scale) of an adapted Linear (GPT.add_lora), else None"""
+    a = getattr(lin, "lora_A", None)
+    return None if a is None else (a, lin.lora_B, lin.lora_scale)
+
+
 class CausalSelfAttention(nn.Module):
     def __init__(self, config):
         super().__init__()
@@ -52,6 +61,11 @@ class CausalSelfAttention(nn.Module):
         spec = (self.n_head, self.n_embd // self.n_head, CAUSAL if mask is None else mask, None, residual, 0.0 if ln is None else ln.eps, K.NORM_LAYER)
         if self.dropout and self.training:          # SDPA dropout_p + resid_dropout (models/gpt2_model.py:64,75): two sites
             spec = spec + (E.drop_spec(self.dropout, x.device, 2),)
+        la, lp = _lora_of(self.c_attn), _lora_of(self.c_proj)
+        if la is not None or lp is not None:
+            return E.AttnBranchLora.apply(x, None if ln is None else ln.weight, None if ln is None else ln.bias,
+                                          self.c_proj.weight, self.c_proj.bias, self.c_attn.bias, spec, (la or lp)[2],
+                                          *(la or (None, None))[:2], *(lp or (None, None))[:2], self.c_attn.weight)
         return E.AttnBranch.apply(x, None if ln is None else ln.weight, None if ln is None else ln.bias,
                                   self.c_proj.weight, self.c_proj.bias, self.c_attn.bias, spec, self.c_attn.weight)
 
@@ -71,6 +85,11 @@ class MLP(nn.Module):
         spec = (residual, 0.0 if ln is None else ln.eps, K.NORM_LAYER)
         if self.dropout.p and self.training:        # models/gpt2_model.py:91
             spec = spec + (E.drop_spec(self.dropout.p, x.device, 1),)
+        lf, lp = _lora_of(self.c_fc), _lora_of(self.c_proj)
+        if lf is not None or lp is not None:
+            return E.MlpBranchLora.apply(x, None if ln is None else ln.weight, None if ln is None else ln.bias,
+                                         self.c_fc.weight, self.c_fc.bias, None, self.c_proj.weight, self.c_proj.bias, spec, (lf or lp)[2],
+                                         *(lf or (None, None))[:2], *(lp or (None, None))[:2])
         return E.MlpBranch.apply(x, None if ln is None else ln.weight, None if ln is None else ln.bias,
                                  self.c_fc.weight, self.c_fc.bias, None, self.c_proj.weight, self.c_proj.bias, spec)
 
@@ -128,7 +147,11 @@ def _step_linear(x, lin, ln=None, gelu=False, residual=None, step_rows=None, hea
     _cached_logits) and the device-position step (forward_decode, _decode_logits_dev) both come through here, so they take
     the same route.  head_vocab = V: the vocabulary head, fp32 logits [rows, V] from the 16-byte-padded shadow of the weight."""
     rows = x.shape[0] if step_rows is None else step_rows
-    if head_vocab is None:
+    lo = _lora_of(lin)
+    if lo is not None:              # an adapted Linear: the shadow of the merged weight, refreshed in place with the adapters
+        assert head_vocab is None
+        w, n, odt = E.shadow_lora(lin.weight, *lo), None, None
+    elif head_vocab is None:
         w, n, odt = E.shadow([lin.weight]), None, None
     else:
         w, n, odt = E.shadow([lin.weight], pad_n=(head_vocab + 7) // 8 * 8), head_vocab, torch.float32   # 16-byte rows for the vector GEMM epilogue
@@ -284,10 +307,13 @@ class _GptEmbed(torch.autograd.Function):
         if t_ctx:
             dprefix = torch.empty((B, t_ctx, d), dtype=dx.dtype, device=dx.device)
             K.copy2d(dx.view(B, t_full * d)[:, :t_ctx * d], dprefix.view(B, t_ctx * d))
-        dwte = torch.zeros(ctx.shapes[0], dtype=torch.float32, device=dx.device)
-        K.gpt_embed_bwd_wte(idx.contiguous(), dx, dwte, t_ctx)
-        dwpe = torch.zeros(ctx.shapes[1], dtype=torch.float32, device=dx.device)
-        K.colsum(dx.view(B, t_full * d), out=dwpe.view(-1)[: t_full * d])
+        dwte = dwpe = None
+        if ctx.needs_input_grad[2]:                   # frozen embeddings: no [V, d] buffer, no scatter
+            dwte = torch.zeros(ctx.shapes[0], dtype=torch.float32, device=dx.device)
+            K.gpt_embed_bwd_wte(idx.contiguous(), dx, dwte, t_ctx)
+        if ctx.needs_input_grad[3]:
+            dwpe = torch.zeros(ctx.shapes[1], dtype=torch.float32, device=dx.device)
+            K.colsum(dx.view(B, t_full * d), out=dwpe.view(-1)[: t_full * d])
         return None, dprefix, dwte, dwpe
 
 
@@ -474,6 +500,78 @@ class GPT(nn.Module):
         if device_type == 'cuda' and all(p.is_cuda for g in groups for p in g['params']):
             return tu.FusedAdamW(self, lr=learning_rate, betas=betas, param_groups=groups)
         return torch.optim.AdamW(groups, lr=learning_rate, betas=betas)
+
+    # ------------------------------------------------------------------------------------------- low-rank adapters (LoRA)
+    def _lora_linears(self, targets=LORA_TARGETS):
+        """[(name relative to the model, Linear)] of the chosen targets, block by block"""
+        bad = [t for t in targets if t not in LORA_TARGETS]
+        if bad:
+            raise ValueError(f"unknown LoRA targets {bad}: choose from {LORA_TARGETS}")
+        pick = {"c_attn": lambda b: b.attn.c_attn, "attn.c_proj": lambda b: b.attn.c_proj, "c_fc": lambda b: b.mlp.c_fc,
+                "mlp.c_proj": lambda b: b.mlp.c_proj}
+        full = {"c_attn": "attn.c_attn", "attn.c_proj": "attn.c_proj", "c_fc": "mlp.c_fc", "mlp.c_proj": "mlp.c_proj"}
+        return [(f"transformer.h.{i}.{full[t]}", pick[t](b)) for i, b in enumerate(self.transformer.h) for t in LORA_TARGETS if t in targets]
+
+    def lora_config(self):
+        """dict(rank, alpha, targets) of the live adapters, or None"""
+        return getattr(self, "_lora_cfg", None)
+
+    def add_lora(self, rank=8, alpha=16.0, targets=LORA_TARGETS):
+        """Freeze the GPT and put a trainable low-rank correction on the chosen Linears of every block:
+            y = x W^T + b + (alpha / rank) * (x A^T) B^T,   lora_A [rank, in] (Kaiming-uniform, as nn.Linear), lora_B [out, rank] = 0
+        so a fresh adapter changes nothing.  Every other parameter of the GPT gets requires_grad = False (re-enable some before building
+        the optimizer if wanted); the base state-dict keys are untouched, so load the pre-trained checkpoint first and call this after.
+        The kernels take 4 <= rank <= 64 with rank % 4 == 0 (fk_lora_route)."""
+        if self.lora_config() is not None:
+            raise RuntimeError("the model already has adapters: merge_lora() first")
+        if not (4 <= rank <= 64 and rank % 4 == 0):
+            raise ValueError(f"LoRA rank {rank} outside the kernels' envelope: 4 <= rank <= 64, rank % 4 == 0")
+        for p in self.parameters():
+            p.requires_grad_(False)
+        for _, lin in self._lora_linears(targets):
+            w = lin.weight
+            a = torch.empty((rank, w.shape[1]), dtype=torch.float32, device=w.device)
+            nn.init.kaiming_uniform_(a, a=math.sqrt(5))
+            lin.lora_A = nn.Parameter(a)
+            lin.lora_B = nn.Parameter(torch.zeros((w.shape[0], rank), dtype=torch.float32, device=w.device))
+            lin.lora_scale = float(alpha) / rank
+        self._lora_cfg = dict(rank=int(rank), alpha=float(alpha), targets=tuple(t for t in LORA_TARGETS if t in targets))
+        return self
+
+    @torch.no_grad()
+    def merge_lora(self):
+        """Fold the adapters into the fp32 masters (fk_lora_merge, in place), remove them and bump the weight epoch: the state dict has
+        exactly the reference's keys again.  Parameters stay frozen as they are."""
+        cfg = self.lora_config()
+        if cfg is None:
+            return self
+        for _, lin in self._lora_linears(cfg["targets"]):
+            K.lora_merge(lin.weight.data, lin.lora_A.data.contiguous(), lin.lora_B.data.contiguous(), lin.lora_scale, out=lin.weight.data)
+            del lin.lora_A, lin.lora_B, lin.lora_scale
+        self._lora_cfg = None
+        E.bump_weight_epoch()
+        return self
+
+    def lora_state_dict(self):
+        """{'<linear>.lora_A' / '<linear>.lora_B': tensor} of the adapters alone"""
+        cfg = self.lora_config()
+        out = {}
+        for name, lin in (self._lora_linears(cfg["targets"]) if cfg else ()):
+            out[name + ".lora_A"] = lin.lora_A.detach()
+            out[name + ".lora_B"] = lin.lora_B.detach()
+        return out
+
+    @torch.no_grad()
+    def load_lora_state_dict(self, sd):
+        """copy adapters saved by lora_state_dict into this model's (add_lora with the same rank and targets first)"""
+        own = self.lora_state_dict()
+        if set(own) != set(sd):
+            raise KeyError(f"adapter keys differ: missing {sorted(set(own) - set(sd))}, unexpected {sorted(set(sd) - set(own))}")
+        for k, v in own.items():
+            if tuple(v.shape) != tuple(sd[k].shape):
+                raise ValueError(f"{k}: shape {tuple(sd[k].shape)} does not fit {tuple(v.shape)}")
+            v.copy_(sd[k].to(v.device, v.dtype))
+        E.bump_weight_epoch()
 
     def estimate_mfu(self, fwdbwd_per_iter, dt, peak_flops=2.5e15):
         """model flops utilisation vs the MI355X dense bf16 MFMA peak (the reference hard-codes A100 312 TF)."""

@@ -259,10 +259,14 @@ class GradSync:
 
 def decay_groups(model: torch.nn.Module, weight_decay: float) -> List[dict]:
     """The two parameter groups of the reference's GPT.configure_optimizers (models/gpt2_model.py:286-298): trainable tensors with
-    dim() >= 2 (matmul weights, embeddings) decayed, the rest (biases, norm weights) not; a tied tensor appears once."""
+    dim() >= 2 (matmul weights, embeddings) decayed, the rest (biases, norm weights) not; a tied tensor appears once.  Frozen parameters
+    are in neither group.  Low-rank adapters (`lora_A` / `lora_B`, GPT.add_lora) are not decayed: decay would pull the correction B A
+    to zero, i.e. back to the pre-trained weight, at a rate unrelated to the decay of the weight they correct."""
     ps = _unique_trainable(model)
-    return [{'params': [p for p in ps if p.dim() >= 2], 'weight_decay': weight_decay},
-            {'params': [p for p in ps if p.dim() < 2], 'weight_decay': 0.0}]
+    lora = {id(p) for n, p in model.named_parameters() if n.endswith(('.lora_A', '.lora_B'))}
+    decayed = [p for p in ps if p.dim() >= 2 and id(p) not in lora]
+    return [{'params': decayed, 'weight_decay': weight_decay},
+            {'params': [p for p in ps if p.dim() < 2 or id(p) in lora], 'weight_decay': 0.0}]
 
 
 def adamw_tables(offsets, sizes, group_of, touched, lag, t: int, max_slots: int = K.ADAMW_MAX_SLOTS):
@@ -804,6 +808,43 @@ def save_model(model, path) -> None:
     import safetensors.torch
     sd = {k: v.detach().clone().contiguous() for k, v in model.state_dict().items() if v is not None}
     safetensors.torch.save_file(sd, str(path))
+
+
+def _adapted(model):
+    """the module that carries the adapters: the GPT itself, or the `llm_model` of a Franky"""
+    for m in model.modules():
+        if callable(getattr(m, "lora_state_dict", None)) and callable(getattr(m, "add_lora", None)):
+            return m
+    raise TypeError("the model has no GPT with add_lora / lora_state_dict")
+
+
+def save_lora(model, path) -> None:
+    """The adapters alone (GPT.lora_state_dict) as safetensors; rank, alpha and targets travel in the file's metadata."""
+    import safetensors.torch
+    gpt = _adapted(model)
+    cfg = gpt.lora_config()
+    if cfg is None:
+        raise RuntimeError("the model has no adapters (add_lora first)")
+    sd = {k: v.detach().clone().contiguous() for k, v in gpt.lora_state_dict().items()}
+    meta = {"lora_rank": str(cfg["rank"]), "lora_alpha": repr(cfg["alpha"]), "lora_targets": ",".join(cfg["targets"])}
+    safetensors.torch.save_file(sd, str(path), metadata=meta)
+
+
+def load_lora(model, path) -> dict:
+    """Read a save_lora file into the model: adds the adapters with the file's rank, alpha and targets when the model has none (a model
+    that has some must have the same), then copies the tensors.  Returns dict(rank, alpha, targets)."""
+    import safetensors
+    import safetensors.torch
+    gpt = _adapted(model)
+    with safetensors.safe_open(str(path), framework="pt") as f:
+        meta = f.metadata() or {}
+    cfg = dict(rank=int(meta["lora_rank"]), alpha=float(meta["lora_alpha"]), targets=tuple(meta["lora_targets"].split(",")))
+    if gpt.lora_config() is None:
+        gpt.add_lora(rank=cfg["rank"], alpha=cfg["alpha"], targets=cfg["targets"])
+    elif gpt.lora_config() != cfg:
+        raise ValueError(f"the file's adapters {cfg} differ from the model's {gpt.lora_config()}")
+    gpt.load_lora_state_dict(safetensors.torch.load_file(str(path)))
+    return cfg
 
 
 def run_train_model(model, datasets, config, project_name='transformer', save_folder=Path('logs'), logger=None):

@@ -920,6 +920,41 @@ typedef struct fk_augment_cfg {
 int fk_augment_patchify(const float* x, void* tok, int64_t B, int64_t T, int64_t C, int64_t P, int64_t ldp, const fk_augment_cfg* cfg,
                         const uint32_t* words, int dtype, void* stream);
 
+/* ---- low-rank adapters (LoRA) on a frozen Linear (build-defined: the reference fine-tunes every parameter; float64 restatement in
+ *      tests/lora_ref.py).  For W [N, K] (frozen), A [r, K], B [N, r] and s = alpha / r:
+ *          y = x W^T + b + s (x A^T) B^T
+ *      The base product stays with fk_gemm_nt; these entry points are the products with one extent equal to r.
+ * fk_lora_fwd: one launch.  x [M, K] (row stride ldx), A [r, K] and B [N, r] contiguous, all in `dtype` (the compute-dtype shadows):
+ *          u[m, j]   = round_to_dtype( sum_k x[m, k] A[j, k] )                       fp32 accumulation, ONE rounding
+ *          out[m, n] = round_to_dtype( (res ? res[m, n] : 0) + scale * colscale(n) * sum_j u[m, j] B[n, j] )     fp32 accumulation
+ *          colscale(n) = q_scale for n < q_cols, 1 elsewhere  (the query columns a projection epilogue pre-scales)
+ *   u_out [M, r] (contiguous; may be NULL) receives u: it is the MFMA operand of the second product and the tensor the backward
+ *   reads.  res (row stride ldr) may be NULL, a separate tensor, or `out` itself (every element is read by the lane that writes it).
+ *   The data gradient is the same call on the transposed shadows B^T [r, N] and A^T [K, r]:
+ *          fk_lora_fwd(dy, ldy, Bt, At, M, K, N, r, s, 0, 1, dh, ldh, du, dh, ldh, ...)   ->   du = dy B (unscaled),  dh += s du A.
+ * fk_lora_wgrad: dy [M, N], u [M, r], du [M, r], x [M, K] contiguous in `dtype`; dA [r, K], dB [N, r] fp32:
+ *          dB[n, j] (+)= scale * sum_m dy[m, n] u[m, j]        dA[j, k] (+)= scale * sum_m du[m, j] x[m, k]
+ *   with du the UNSCALED dy B of the call above (scale * du^T x = (scale du)^T x).  accumulate != 0 adds to dA / dB, 0 overwrites.
+ *   Rows are split in slices of 64 whose partials (workspace: fk_lora_wgrad_workspace_bytes, 0 for M <= 64) are added in slice
+ *   order inside this entry point: no atomics, the same bits on every run.
+ * fk_lora_merge: W, A, B fp32 masters (contiguous), out [N, K] (row stride ldo) in out_dtype:
+ *          out[n, k] = fma(scale, c_r, W[n, k]),   c_0 = 0,  c_{j+1} = fma(B[n, j], A[j, k], c_j)      all fp32
+ *   stored as fp32, or as bf16 rounded from that same fp32 value: a merged bf16 shadow has the bits of casting the merged master.
+ * fk_lora_route (host): the forward's kernel variant, or -1 outside the envelope: FK_F32 / FK_BF16, 4 <= r <= 64 with r % 4 == 0,
+ *   N and K multiples of 8 (4 for fp32), M >= 1, every extent and leading dimension below 2^31.  Outside it, a leading dimension
+ *   shorter than its row, ldx not a multiple of 16 bytes, a null or misaligned pointer or a short workspace: FK_EINVAL on the host,
+ *   before any launch.  No scratch memory, no host synchronisation, graph-capturable. */
+enum { FK_LORA_R32 = 0, FK_LORA_R64 = 1 };
+int fk_lora_route(int64_t M, int64_t N, int64_t K, int64_t r, int dtype);
+int fk_lora_fwd(const void* x, int64_t ldx, const void* A, const void* B, int64_t M, int64_t N, int64_t K, int64_t r, float scale,
+                int64_t q_cols, float q_scale, const void* res, int64_t ldr, void* u_out, void* out, int64_t ldo, int dtype,
+                void* stream);
+size_t fk_lora_wgrad_workspace_bytes(int64_t M, int64_t N, int64_t K, int64_t r);
+int fk_lora_wgrad(const void* dy, const void* u, const void* du, const void* x, int64_t M, int64_t N, int64_t K, int64_t r, float scale,
+                  float* dA, float* dB, int accumulate, int dtype, void* workspace, size_t workspace_bytes, void* stream);
+int fk_lora_merge(const float* W, const float* A, const float* B, int64_t N, int64_t K, int64_t r, float scale, void* out, int64_t ldo,
+                  int out_dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
