@@ -117,6 +117,9 @@ SIGNATURES = {
     "fk_ngram_hash": (_u32, [_u32, _u32]),
     "fk_ctc_beam_search_lm": (_int, [_p, _i64, _i64, _p] + [_i64] * 8 + [_p, _i64, _i64, _p, _p, _i64, _p, _p, _i64, _i64, _f32, _f32, _int, _p, _i64, _i64,
                                      _p, _p, _p, _p, _int, _p, _sz, _p]),
+    "fk_ctc_beam_lex_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),
+    "fk_ctc_beam_search_lex": (_int, [_p, _i64, _i64, _p] + [_i64] * 9 + [_p, _i64, _i64, _p, _i64, _p, _i64, _i64, _p, _i64, _i64, _p, _p, _i64, _p, _p,
+                                      _i64, _i64, _f32, _f32, _int, _p, _i64, _i64, _p, _p, _i64, _i64, _p, _p, _p, _p, _p, _int, _p, _sz, _p]),
     "fk_ctc_prefix_init": (_int, [_p, _i64, _i64, _p] + [_i64] * 5 + [_p, _i64, _i64, _p, _p, _p, _p, _int, _p]),
     "fk_ctc_prefix_score": (_int, [_p, _i64, _i64, _p, _p] + [_i64] * 6 + [_p, _p, _int, _f32, _i64, _p, _p, _p, _p, _i64, _p, _p, _p, _p, _int, _p]),
     "fk_nbest_trie": (_int, [_p, _i64, _i64, _p, _p] + [_i64] * 8 + [_p] * 8),

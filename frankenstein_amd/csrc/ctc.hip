@@ -29,6 +29,9 @@
 //   fk_ctc_beam_search_lm  the same search with a backoff n-gram model inside the selection (shallow fusion; float64 restatement
 //                    tests/ctc_lm_ref.py): launch 1 as above, launch 2 the LM instantiation of ctc_beam_kernel, whose slots also carry the
 //                    LM term, the LM sum and the LM state of their prefix (in LDS); the model is a state machine over one hash table
+//   fk_ctc_beam_search_lex  the same search constrained to the words of a pronunciation lexicon, a word-level n-gram model at word ends
+//                    (float64 restatement tests/ctc_lex_ref.py): launch 1 as above, launch 2 the lexicon instantiation of ctc_beam_kernel,
+//                    whose slots also carry the trie node of their unfinished word and their word count; the trie is a hash table of edges
 //
 //   fk_ctc_prefix_init / fk_ctc_prefix_score  CTC prefix scores for the candidates of the GPT beam search (joint CTC / attention decoding;
 //                    semantics: include/franken_hip.h; float64 restatement tests/ctc_prefix_ref.py): launch 1 of init as above, then one
@@ -1038,6 +1041,62 @@ FK_DEV void lm_lookup(const BeamLmArgs& a, const int (&state)[N], const int (&to
   }
 }
 
+// Lexicon (fk_ctc_beam_search_lex): the search over labellings that spell dictionary words.  The acoustic recursion is the one above and
+// the LM fields are the LM instantiation's, over WORD ids (the tables of BeamLmArgs hold the word model, its end of sentence is id V); a
+// slot also carries the node of the pronunciation trie its unfinished word has reached (0: a word start) and its word count.  A fresh
+// candidate c != sep gets a key only if the trie has the child (node of slot i, c): one probe sequence per entry of the table, made where
+// the LM instantiation makes its look-ups.  The sep candidate of a slot is admissible at a terminal node; its word is chosen there among
+// the node's up to LEX_HOMOPHONES words by one word-LM look-up each, thread 8 i + h homophone h of slot i.  The chosen word of a sep
+// node is kept beside the node (nword), so the walk back fills ids and words in one pass.
+constexpr int LEX_HOMOPHONES = 8;
+constexpr int LEX_AHEAD = 4;                           // entries of a trie probe sequence in flight (768 x 41, W 32, 2000 words: 21.0 ms with 2, 20.8 ms with 4)
+static_assert(BEAM_MAX * LEX_HOMOPHONES <= BEAM_THREADS, "one homophone look-up per thread");
+struct BeamLexArgs : BeamLmArgs {
+  const int4* trie;       // [tcap] {node, class, child, 0}, node -1: empty
+  const int2* node_words; // [n_nodes] {first, count} into word_list
+  const int* word_list;   // [n_list]
+  int* nword;             // [B][T W + 1] beside BeamWs::nodes: the word a sep node closed, -1 for every other node
+  int64_t* words;         // [B, nbest, Lw]
+  int64_t ld_words_b, ld_words_h;
+  int64_t* word_lengths;  // [B, nbest]
+  unsigned char* complete;// [B, nbest]
+  int sep, V, n_nodes, n_list, tcap_mask, tmax_probe, Lw;
+};
+FK_DEV int clamp_index(int i, int n) { return i < 0 ? 0 : (i >= n ? n - 1 : i); }
+
+// N trie look-ups side by side: child (node, class) or -1.  One probe sequence each, LEX_AHEAD entries a step in flight, none behind
+// tmax_probe; the loop is bounded by tmax_probe, a table index by the mask and a child read from the table is clamped into [0, n_nodes).
+template <int N>
+FK_DEV void trie_lookup(const BeamLexArgs& a, const int (&node)[N], const int (&cls)[N], const bool (&want)[N], int (&child)[N]) {
+  bool open[N];
+#pragma unroll
+  for (int r = 0; r < N; ++r) { open[r] = want[r]; child[r] = -1; }
+  for (int p = 0; p < a.tmax_probe; p += LEX_AHEAD) {
+    int4 e[N][LEX_AHEAD];
+    bool any = false;
+#pragma unroll
+    for (int r = 0; r < N; ++r) {
+      if (open[r]) {
+        const unsigned h = ngram_hash((unsigned)node[r], (unsigned)cls[r]) + (unsigned)p;
+#pragma unroll
+        for (int q = 0; q < LEX_AHEAD; ++q) e[r][q] = a.trie[(h + (unsigned)q) & (unsigned)a.tcap_mask];
+        any = true;
+      }
+    }
+    if (!any) break;
+#pragma unroll
+    for (int r = 0; r < N; ++r) {
+#pragma unroll
+      for (int q = 0; q < LEX_AHEAD; ++q) {
+        if (open[r]) {
+          if (p + q >= a.tmax_probe || e[r][q].x == -1) open[r] = false;
+          else if (e[r][q].x == node[r] && e[r][q].y == cls[r]) { child[r] = clamp_index(e[r][q].z, a.n_nodes); open[r] = false; }
+        }
+      }
+    }
+  }
+}
+
 // The three sums that are formed for a key and again when the chosen entry becomes a slot: the total of a resident prefix from this
 // frame's pb' and pnb'; what slot i (of a beam's last / pb / tot arrays) sends to its extension by class c at log-probability lp (a repeat
 // of the last label continues only what ended in a blank); the weighted LM term of a prefix with a token of ln P = lp behind it
@@ -1047,10 +1106,16 @@ FK_DEV float extended_total(int c, const int* last, const float* pb, const float
 }
 FK_DEV float extended_lmw(float lmw, float weight, float lp, float bonus) { return lmw + lm_term(weight, lp, bonus); }
 
-template <typename T, bool LM>
-__global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(std::conditional_t<LM, BeamLmArgs, BeamArgs> a) {
+template <typename T, bool LM, bool LEX = false>
+__global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(std::conditional_t<LEX, BeamLexArgs, std::conditional_t<LM, BeamLmArgs, BeamArgs>> a) {
+  static_assert(LM || !LEX, "the lexicon search carries the LM fields");
   constexpr int M = BEAM_MAX;
   constexpr int ML = LM ? M : 1, MC = LM ? M * M : 1;   // (the plain instantiation never names the arrays below: they take no LDS there)
+  constexpr int MX = LEX ? M : 1;                       // (nor does any but the lexicon instantiation name these)
+  __shared__ int s_lex[2][MX], s_wc[2][MX];             // per slot: the trie node of its unfinished word, its word count
+  __shared__ float s_seplp[MX];                         // this frame's sep extension of slot i: ln P(w* | word state),
+  __shared__ int s_sepnx[MX], s_sepw[MX];               // the state behind w*, and w* (-1: the node is not terminal, no sep)
+  __shared__ int s_fwc[MX], s_fword[MX], s_fdone[MX];   // behind the last frame: word count with the closing word, that word or -1, complete
   __shared__ float s_lmw[2][ML], s_lms[2][ML];          // per slot: the weighted LM term of its prefix, the unweighted sum of ln P
   __shared__ int s_lst[2][ML];                          // its LM state
   __shared__ float s_candlp[MC];                        // this frame's look-ups, entry W + i Kc + k at i Kc + k: ln P(cid[k] | state of slot i)
@@ -1093,8 +1158,17 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(std::conditional
     s_pb[0][tid] = 0.0f; s_pnb[0][tid] = -INFINITY; s_tot[0][tid] = 0.0f; s_first[0][tid] = -1; s_kids[0][tid] = 0ull;
     s_cid[0][tid] = s_cid[1][tid] = -1;                 // the frames write [0, Kc)
     if constexpr (LM) { s_lmw[0][tid] = 0.0f; s_lms[0][tid] = 0.0f; s_lst[0][tid] = clamp_state(a.start_state, a.S); }
+    if constexpr (LEX) { s_lex[0][tid] = 0; s_wc[0][tid] = 0; }
   }
   if (tid == 0) nodes[0] = make_int4(-1, -1, -1, -1);
+  [[maybe_unused]] int* nword = nullptr;
+  [[maybe_unused]] std::conditional_t<LEX, BeamLmArgs, int> wlm{};                   // lexicon: the word model's view of the arguments (tokens are clamped into [0, V])
+  if constexpr (LEX) {
+    nword = a.nword + (size_t)b * ((size_t)a.T * W + 1);
+    if (tid == 0) nword[0] = -1;
+    wlm = a;
+    wlm.C = a.V;
+  }
   int cur = 0, nb = 1;
 
   // the frame's record is loaded one frame ahead: threads [0, Kc) a candidate each, thread M lp[blank], thread M + 1 row_lse
@@ -1193,10 +1267,98 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(std::conditional
     }
     __syncthreads();
   };
+  // Lexicon: the word a sep behind slot i closes, w* = argmax over the words of the slot's node of ln P(w | word state), exact ties to
+  // the first of the node's list.  Thread 8 i + h looks homophone h up (`gate`: the same in all threads); the 8 lanes of a slot sit in
+  // one wave.  Leaves s_seplp / s_sepnx / s_sepw[i] (-1: no word ends at the node).  A list index is clamped into [0, n_list), a word
+  // into [0, V), a count into [0, 8]; the root never ends a word.
+  auto choose_words = [&](int cur, int nb, bool gate) {
+    if constexpr (LEX) {
+      const int i = tid / LEX_HOMOPHONES, h = tid % LEX_HOMOPHONES;
+      const bool live = gate && i < nb;
+      const int n = live ? clamp_index(s_lex[cur][i], a.n_nodes) : 0;
+      int2 nw = make_int2(0, 0);
+      if (n > 0) nw = a.node_words[n];
+      const int cnt = nw.y < 0 ? 0 : (nw.y > LEX_HOMOPHONES ? LEX_HOMOPHONES : nw.y);
+      const bool want[1] = {h < cnt};
+      const int wd = want[0] ? clamp_index(a.word_list[clamp_index(nw.x + h, a.n_list)], a.V) : 0;
+      const int st[1] = {live ? s_lst[cur][i] : 0}, tk[1] = {wd};
+      float lp[1];
+      int nx_[1];
+      lm_lookup<1>(wlm, st, tk, want, lp, nx_);
+      float best = want[0] ? lp[0] : -INFINITY;
+      int bh = h;
+#pragma unroll
+      for (int d = 1; d < LEX_HOMOPHONES; d <<= 1) {    // (every lane of the wave is here: no lane left above)
+        const float ol = __shfl_xor(best, d);
+        const int oh = __shfl_xor(bh, d);
+        if (ol > best || (ol == best && oh < bh)) { best = ol; bh = oh; }
+      }
+      const int src = (tid & 63 & ~(LEX_HOMOPHONES - 1)) + bh;
+      const int bnx = __shfl(nx_[0], src), bw = __shfl(wd, src);
+      if (h == 0) { s_seplp[i] = best; s_sepnx[i] = bnx; s_sepw[i] = cnt > 0 ? bw : -1; }
+    }
+  };
+  // Lexicon, behind the last frame: a hypothesis at the root is complete; one at a terminal node is closed as if by a sep without an
+  // acoustic term (its word, LM term, bonus and state) and is complete; any other is incomplete and keeps its key.  Complete ones add
+  // the end of sentence under use_eos.  The order: complete first, then the final key, equal keys in the order of the last selection.
+  auto lex_rerank = [&](int cur, int nb) {
+    if constexpr (LEX) {
+      choose_words(cur, nb, true);
+      __syncthreads();
+      if (tid < M) {
+        float key = -INFINITY, lm = -INFINITY;
+        int done = 0, wc = 0, word = -1;
+        if (tid < nb) {
+          float lmw = s_lmw[cur][tid];
+          int st1 = s_lst[cur][tid];
+          lm = s_lms[cur][tid];
+          wc = s_wc[cur][tid];
+          done = s_lex[cur][tid] == 0;
+          if (!done && s_sepw[tid] >= 0) {
+            lmw = extended_lmw(lmw, a.lm_weight, s_seplp[tid], a.length_bonus);
+            lm += s_seplp[tid];
+            st1 = s_sepnx[tid];
+            word = s_sepw[tid];
+            wc += 1;
+            done = 1;
+          }
+          key = s_tot[cur][tid] + lmw;
+          if (a.use_eos && done) {
+            const int st[1] = {st1}, tk[1] = {a.V};
+            const bool want[1] = {true};
+            float lp[1];
+            int nx_[1];
+            lm_lookup<1>(wlm, st, tk, want, lp, nx_);
+            key += lm_term(a.lm_weight, lp[0], 0.0f);
+            lm += lp[0];
+          }
+        }
+        s_fkey[tid] = key;
+        s_flm[tid] = lm;
+        s_fdone[tid] = done;
+        s_fwc[tid] = wc;
+        s_fword[tid] = word;
+        s_perm[tid] = tid;
+      }
+      __syncthreads();
+      if (tid < nb) {
+        const float mine = s_fkey[tid];
+        const int md = s_fdone[tid];
+        int rank = 0;
+#pragma unroll
+        for (int j = 0; j < M; ++j) {
+          const bool ahead = s_fdone[j] != md ? s_fdone[j] > md : (s_fkey[j] > mine || (s_fkey[j] == mine && j < tid));
+          rank += (j < nb && ahead) ? 1 : 0;
+        }
+        s_perm[rank] = tid;
+      }
+      __syncthreads();
+    }
+  };
   // LM, behind the last frame: the final key total + lmw, with use_eos + lm_weight ln P(</s> | state); the beam is put in the order of these keys once more,
   // equal keys in the order of the last selection (s_perm: place -> slot, the identity wherever no rank lands)
   auto lm_rerank = [&](int cur, int nb) {
-    if constexpr (LM) {
+    if constexpr (LM && !LEX) {
       if (tid < M) {
         float key = -INFINITY, lm = -INFINITY;
         if (tid < nb) {
@@ -1249,10 +1411,29 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(std::conditional
       }
       int64_t* o = a.ids + (int64_t)b * a.ld_ids_b + (int64_t)tid * a.ld_ids_h;
       int n = have ? s_node[cur][sl] : 0;
-      for (int s = len - 1; s >= 0 && n > 0; --s) {
-        const int4 nd = nodes[n];
-        o[s] = nd.y;
-        n = nd.x;
+      if constexpr (LEX) {                              // the same walk fills the words: a sep node holds the word it closed
+        int64_t* ow = a.words + (int64_t)b * a.ld_words_b + (int64_t)tid * a.ld_words_h;
+        int wn = have ? s_fwc[sl] : 0;
+        wn = wn > a.Lw ? a.Lw : wn;
+        a.word_lengths[(int64_t)b * a.nbest + tid] = wn;
+        a.complete[(int64_t)b * a.nbest + tid] = have ? (unsigned char)s_fdone[sl] : 0;
+        for (int j = wn; j < a.Lw; ++j) ow[j] = a.pad;
+        int wp = wn;
+        if (have && s_fword[sl] >= 0 && wp > 0) ow[--wp] = s_fword[sl];
+        for (int s = len - 1; s >= 0 && n > 0; --s) {
+          const int4 nd = nodes[n];
+          const int wd = nword[n];
+          o[s] = nd.y;
+          if (wd >= 0 && wp > 0) ow[--wp] = wd;
+          n = nd.x;
+        }
+        for (int j = 0; j < wp; ++j) ow[j] = a.pad;     // (only a malformed table leaves a gap)
+      } else {
+        for (int s = len - 1; s >= 0 && n > 0; --s) {
+          const int4 nd = nodes[n];
+          o[s] = nd.y;
+          n = nd.x;
+        }
       }
     }
   };
@@ -1269,7 +1450,27 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(std::conditional
 
     // LM: ln P(candidate k | state of slot i) for every fresh entry of the table, kept for the keys and laid out for the build step
     float cand_lp[BEAM_EPT];
-    if constexpr (LM) {
+    [[maybe_unused]] int cand_child[BEAM_EPT];          // lexicon: the trie node behind a fresh entry that is no sep, -1: the lexicon has none
+    if constexpr (LEX) {
+      int nd[BEAM_EPT], cl[BEAM_EPT];
+      bool want[BEAM_EPT];
+#pragma unroll
+      for (int r = 0; r < BEAM_EPT; ++r) {
+        const bool fresh = ei[r] >= 0 && ei[r] < nb;
+        cl[r] = fresh ? s_cid[f][ek[r]] : 0;
+        nd[r] = fresh ? s_lex[cur][ei[r]] : 0;
+        want[r] = fresh && cl[r] != a.sep;
+        cand_lp[r] = 0.0f;
+      }
+      trie_lookup<BEAM_EPT>(a, nd, cl, want, cand_child);
+#pragma unroll
+      for (int r = 0; r < BEAM_EPT; ++r)
+        if (want[r]) s_candnx[ei[r] * Kc + ek[r]] = cand_child[r];
+      bool sep_cand = false;
+#pragma unroll
+      for (int k = 0; k < M; ++k) sep_cand |= s_cid[f][k] == a.sep;                         // (entries behind Kc hold -1)
+      choose_words(cur, nb, sep_cand);
+    } else if constexpr (LM) {
       int st[BEAM_EPT], tk[BEAM_EPT], nx_[BEAM_EPT];
       bool want[BEAM_EPT];
 #pragma unroll
@@ -1325,7 +1526,12 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(std::conditional
       } else if (ei[r] >= 0 && ei[r] < nb) {
         const int i = ei[r], k = ek[r];
         if (!((s_merged[i] >> k) & 1u)) v = extended_total(s_cid[f][k], s_last[cur], s_pb[cur], s_tot[cur], i, s_clp[f][k]);
-        if constexpr (LM) v = v > -INFINITY ? v + extended_lmw(s_lmw[cur][i], a.lm_weight, cand_lp[r], a.length_bonus) : v;
+        if constexpr (LEX) {                            // a candidate the lexicon rejects has no key; only a sep moves the LM term
+          const bool is_sep = s_cid[f][k] == a.sep;
+          const bool ok = is_sep ? s_sepw[i] >= 0 : cand_child[r] >= 0;
+          const float lmw = is_sep ? extended_lmw(s_lmw[cur][i], a.lm_weight, s_seplp[i], a.length_bonus) : s_lmw[cur][i];
+          v = (ok && v > -INFINITY) ? v + lmw : -INFINITY;
+        } else if constexpr (LM) v = v > -INFINITY ? v + extended_lmw(s_lmw[cur][i], a.lm_weight, cand_lp[r], a.length_bonus) : v;
       }
       key[r] = v > -INFINITY ? beam_key(v, e) : 0ull;   // (a NaN total is no entry either)
     }
@@ -1343,13 +1549,26 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(std::conditional
         if (sel_e < W) {
           tot = resident_total(s_npb[sel_e], s_npnb[sel_e]);
           s_lmw[nx][tid] = s_lmw[cur][sel_e]; s_lms[nx][tid] = s_lms[cur][sel_e]; s_lst[nx][tid] = s_lst[cur][sel_e];
+          if constexpr (LEX) { s_lex[nx][tid] = s_lex[cur][sel_e]; s_wc[nx][tid] = s_wc[cur][sel_e]; }
         } else {
           const int i = s_selpar[tid], k = (sel_e - W) % Kc;
-          const float lp = s_candlp[sel_e - W];
-          tot = extended_total(s_cid[f][k], s_last[cur], s_pb[cur], s_tot[cur], i, s_clp[f][k]);
-          s_lmw[nx][tid] = extended_lmw(s_lmw[cur][i], a.lm_weight, lp, a.length_bonus);
-          s_lms[nx][tid] = s_lms[cur][i] + lp;
-          s_lst[nx][tid] = s_candnx[sel_e - W];
+          if constexpr (LEX) {
+            tot = extended_total(s_cid[f][k], s_last[cur], s_pb[cur], s_tot[cur], i, s_clp[f][k]);
+            const bool is_sep = s_cid[f][k] == a.sep;
+            s_lmw[nx][tid] = is_sep ? extended_lmw(s_lmw[cur][i], a.lm_weight, s_seplp[i], a.length_bonus) : s_lmw[cur][i];
+            s_lms[nx][tid] = is_sep ? s_lms[cur][i] + s_seplp[i] : s_lms[cur][i];
+            s_lst[nx][tid] = is_sep ? s_sepnx[i] : s_lst[cur][i];
+            s_lex[nx][tid] = is_sep ? 0 : s_candnx[sel_e - W];
+            s_wc[nx][tid] = s_wc[cur][i] + (is_sep ? 1 : 0);
+            const int nd = s_selnode[tid], id = nd < -1 ? -2 - nd : nd;   // <= T W: inside the sample's table
+            if (id >= 0) nword[id] = is_sep ? s_sepw[i] : -1;             // (a node that came back holds the same word already)
+          } else {
+            const float lp = s_candlp[sel_e - W];
+            tot = extended_total(s_cid[f][k], s_last[cur], s_pb[cur], s_tot[cur], i, s_clp[f][k]);
+            s_lmw[nx][tid] = extended_lmw(s_lmw[cur][i], a.lm_weight, lp, a.length_bonus);
+            s_lms[nx][tid] = s_lms[cur][i] + lp;
+            s_lst[nx][tid] = s_candnx[sel_e - W];
+          }
         }
       }
       if (sel_e < W) {
@@ -1370,6 +1589,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(std::conditional
   }
   __syncthreads();
   lm_rerank(cur, nb);
+  lex_rerank(cur, nb);
   write_out(cur, nb);
 }
 
@@ -1797,6 +2017,66 @@ int fk_ctc_beam_search_lm(const void* logits, int64_t ldb, int64_t ldt, const in
   a.start_state = (int)lm_start_state; a.use_eos = use_eos != 0;
   FK_BY_DTYPE(dtype, TT, hipLaunchKernelGGL((ctc_beam_kernel<TT, true>), dim3((unsigned)B), dim3(BEAM_THREADS), 0, (hipStream_t)stream, a));
   FK_CHECK_LAUNCH("fk_ctc_beam_search_lm(recursion)");
+  return FK_OK;
+}
+
+size_t fk_ctc_beam_lex_workspace_bytes(int64_t B, int64_t T, int64_t W, int64_t K) {
+  const size_t base = fk_ctc_beam_workspace_bytes(B, T, W, K);
+  return base ? base + a256((size_t)B * (T * W + 1) * sizeof(int)) : 0;
+}
+
+int fk_ctc_beam_search_lex(const void* logits, int64_t ldb, int64_t ldt, const int64_t* input_lengths, int64_t B, int64_t T, int64_t C, int64_t blank,
+                           int64_t sep, int64_t W, int64_t K, int64_t nbest, int64_t pad, const int32_t* trie_table, int64_t trie_cap,
+                           int64_t trie_max_probe, const int32_t* node_words, int64_t n_nodes, const int32_t* word_list, int64_t n_list, int64_t V,
+                           const int32_t* lm_table, int64_t lm_cap, int64_t lm_max_probe, const float* lm_bow, const int32_t* lm_backoff,
+                           int64_t lm_states, const float* lm_uni_lp, const int32_t* lm_uni_next, int64_t lm_start_state, int64_t lm_order,
+                           float lm_weight, float word_bonus, int use_eos, int64_t* words, int64_t ld_words_b, int64_t ld_words_h,
+                           int64_t* word_lengths, int64_t* ids, int64_t ld_ids_b, int64_t ld_ids_h, int64_t* lengths, float* am, float* lm,
+                           float* total, uint8_t* complete, int dtype, void* workspace, size_t workspace_bytes, void* stream) {
+  const char* fn = "fk_ctc_beam_search_lex";
+  FK_CHECK_ARG(trie_table && node_words && word_list, "%s: null pointer (lexicon tables)", fn);
+  FK_CHECK_ARG(lm_table && lm_bow && lm_backoff && lm_uni_lp && lm_uni_next, "%s: null pointer (word LM tables)", fn);
+  FK_CHECK_ARG(words && word_lengths && lm && total && complete, "%s: null pointer (words / word_lengths / lm / total / complete)", fn);
+  FK_CHECK_ARG(((uintptr_t)trie_table & 15) == 0 && ((uintptr_t)lm_table & 15) == 0, "%s: the hash tables must be 16-byte aligned", fn);
+  FK_CHECK_ARG(((uintptr_t)node_words & 7) == 0, "%s: node_words must be 8-byte aligned", fn);
+  if (const int rc = check_common(fn, dtype, logits && ids && lengths && am, B, T, C, blank)) return rc;
+  FK_CHECK_ARG(sep >= 0 && sep < C && sep != blank, "%s: sep = %lld outside [0, C = %lld) or equal to blank = %lld", fn, (long long)sep, (long long)C,
+               (long long)blank);
+  FK_CHECK_ARG(trie_cap >= 1 && trie_cap < (1LL << 31) && (trie_cap & (trie_cap - 1)) == 0, "%s: trie cap = %lld is no power of two below 2^31", fn,
+               (long long)trie_cap);
+  FK_CHECK_ARG(trie_max_probe >= 1 && trie_max_probe <= trie_cap, "%s: trie max_probe = %lld outside 1 .. cap = %lld", fn, (long long)trie_max_probe,
+               (long long)trie_cap);
+  FK_CHECK_ARG(n_nodes >= 1 && n_nodes < (1LL << 31), "%s: nodes = %lld (the root is node 0)", fn, (long long)n_nodes);
+  FK_CHECK_ARG(n_list >= 1 && n_list < (1LL << 31) && V >= 1 && V < (1LL << 31) - 1, "%s: word list of %lld entries, V = %lld words", fn, (long long)n_list,
+               (long long)V);
+  FK_CHECK_ARG(lm_order >= 1 && lm_order <= 8, "%s: order = %lld outside 1 .. 8", fn, (long long)lm_order);
+  FK_CHECK_ARG(lm_cap >= 1 && lm_cap < (1LL << 31) && (lm_cap & (lm_cap - 1)) == 0, "%s: LM cap = %lld is no power of two below 2^31", fn, (long long)lm_cap);
+  FK_CHECK_ARG(lm_max_probe >= 1 && lm_max_probe <= lm_cap, "%s: LM max_probe = %lld outside 1 .. cap = %lld", fn, (long long)lm_max_probe, (long long)lm_cap);
+  FK_CHECK_ARG(lm_states >= 1 && lm_states < (1LL << 31) && lm_start_state >= 0 && lm_start_state < lm_states, "%s: states = %lld, start_state = %lld", fn,
+               (long long)lm_states, (long long)lm_start_state);
+  FK_CHECK_ARG(std::isfinite(lm_weight) && std::isfinite(word_bonus), "%s: lm_weight = %g, word_bonus = %g must be finite", fn, (double)lm_weight,
+               (double)word_bonus);
+  const int64_t Lw = T > 0 ? (T + 1) / 2 : 0;
+  FK_CHECK_ARG(T <= 0 || (ld_words_h >= Lw && ld_words_b >= (nbest - 1) * ld_words_h + Lw), "%s: words strides %lld / %lld below [nbest = %lld, (T + 1) / 2 = %lld]",
+               fn, (long long)ld_words_b, (long long)ld_words_h, (long long)nbest, (long long)Lw);
+  const size_t need = fk_ctc_beam_lex_workspace_bytes(B, T, W, K);
+  FK_CHECK_ARG(need == 0 || (workspace && workspace_bytes >= need), "%s: workspace too small (%zu bytes, fk_ctc_beam_lex_workspace_bytes gives %zu)", fn,
+               workspace_bytes, need);
+  BeamLexArgs a;
+  const int rc = beam_front(fn, logits, ldb, ldt, input_lengths, B, T, C, blank, W, K, nbest, pad, ids, ld_ids_b, ld_ids_h, lengths, am, dtype, workspace,
+                            workspace_bytes, stream, a);
+  if (rc != FK_OK) return rc;
+  a.table = (const int4*)lm_table; a.bow = lm_bow; a.backoff = lm_backoff; a.uni_lp = lm_uni_lp; a.uni_next = lm_uni_next;
+  a.lm_out = lm; a.total_out = total; a.lm_weight = lm_weight; a.length_bonus = word_bonus;
+  a.S = (int)lm_states; a.cap_mask = (int)(lm_cap - 1); a.max_probe = (int)lm_max_probe; a.order = (int)lm_order;
+  a.start_state = (int)lm_start_state; a.use_eos = use_eos != 0;
+  a.trie = (const int4*)trie_table; a.node_words = (const int2*)node_words; a.word_list = word_list;
+  a.nword = (int*)((char*)workspace + fk_ctc_beam_workspace_bytes(B, T, W, K));
+  a.words = words; a.ld_words_b = ld_words_b; a.ld_words_h = ld_words_h; a.word_lengths = word_lengths; a.complete = complete;
+  a.sep = (int)sep; a.V = (int)V; a.n_nodes = (int)n_nodes; a.n_list = (int)n_list; a.tcap_mask = (int)(trie_cap - 1);
+  a.tmax_probe = (int)trie_max_probe; a.Lw = (int)Lw;
+  FK_BY_DTYPE(dtype, TT, hipLaunchKernelGGL((ctc_beam_kernel<TT, true, true>), dim3((unsigned)B), dim3(BEAM_THREADS), 0, (hipStream_t)stream, a));
+  FK_CHECK_LAUNCH("fk_ctc_beam_search_lex(recursion)");
   return FK_OK;
 }
 

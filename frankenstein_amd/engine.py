@@ -1239,6 +1239,36 @@ def ctc_beam_decode_lm(logits: Tensor, lm, input_lengths: Optional[Tensor] = Non
     return K.ctc_beam_search_lm(logits, lm, input_lengths, blank, beam_width, topk, nbest, lm_weight, length_bonus, use_eos, pad)
 
 
+class CtcLexiconResult(NamedTuple):
+    """engine.ctc_beam_decode_lexicon's result, best first.  words int64 [B, nbest, (T + 1) // 2] padded with `pad`, word_lengths int64
+    [B, nbest]; ids int64 [B, nbest, T] / lengths: the labelling (separators included); am (the CTC mass), lm (the unweighted ln P of the
+    word model), total (the ranking key) fp32 [B, nbest]; complete uint8 [B, nbest]: the labelling ends at a word boundary."""
+    words: Tensor
+    word_lengths: Tensor
+    ids: Tensor
+    lengths: Tensor
+    am: Tensor
+    lm: Tensor
+    total: Tensor
+    complete: Tensor
+
+
+@torch.no_grad()
+def ctc_beam_decode_lexicon(logits: Tensor, lexicon, lm=None, sep: int = 1, input_lengths: Optional[Tensor] = None, blank: int = 0,
+                            beam_width: int = 8, topk: Optional[int] = None, nbest: int = 1, lm_weight: float = 1.0, word_bonus: float = 0.0,
+                            use_eos: bool = True, pad: int = -100) -> CtcLexiconResult:
+    """Prefix beam search over a phoneme / letter head that returns WORDS: the search is constrained to labellings that spell words of
+    `lexicon` (utils.lexicon.Lexicon) separated by the class `sep`; at every word end the word-level backoff model `lm` (utils.ngram.NGramLM
+    over the lexicon's word ids, None: none) picks among homophones and adds lm_weight * ln P_lm(word | words so far) + word_bonus to the
+    ranking key, at the end (use_eos) lm_weight * ln P_lm(</s>).  A hypothesis whose last word is finished (with or without a final sep) is
+    complete and ranks before every incomplete one.  Two launches, nothing waits for the host; the tables are copied to the device once.
+    Not built: LM look-ahead into the trie, an unknown-word path, forking on homophones (one word per labelling, chosen greedily)."""
+    if logits.stride(-1) != 1:
+        logits = logits.contiguous()
+    return CtcLexiconResult(*K.ctc_beam_search_lex(logits, lexicon, lm, sep, input_lengths, blank, beam_width, topk, nbest, lm_weight, word_bonus,
+                                                   use_eos, pad))
+
+
 class CtcAlignment(NamedTuple):
     """engine.ctc_forced_align's result.  score fp32 [B]: the log-probability of the best alignment (-inf: the sample has none); path int64
     [B, T]: the class per frame (`pad` behind the sample's end); index int64 [B, T]: the label of the target a frame emits (-1: blank or

@@ -1404,8 +1404,9 @@ def ctc_align(logits: Tensor, targets: Tensor, input_lengths: Optional[Tensor] =
     return r
 
 
-def _ctc_beam_prologue(logits: Tensor, input_lengths: Optional[Tensor], beam_width: int, topk: Optional[int], nbest: int):
-    """What both beam searches set up before their call -> (B, T, C, K, il, ids, lengths, ws, nbytes); topk None: min(32, C - 1)."""
+def _ctc_beam_prologue(logits: Tensor, input_lengths: Optional[Tensor], beam_width: int, topk: Optional[int], nbest: int,
+                       ws_bytes: str = "fk_ctc_beam_workspace_bytes"):
+    """What the beam searches set up before their call -> (B, T, C, K, il, ids, lengths, ws, nbytes); topk None: min(32, C - 1)."""
     assert logits.dim() == 3 and logits.stride(2) == 1 and logits.dtype in (torch.float32, torch.bfloat16)
     B, T, Cn = logits.shape
     K = min(32, Cn - 1) if topk is None else int(topk)
@@ -1413,7 +1414,7 @@ def _ctc_beam_prologue(logits: Tensor, input_lengths: Optional[Tensor], beam_wid
     il = _ctc_lengths(input_lengths, B, dev)
     ids = torch.empty((B, nbest, T), dtype=torch.int64, device=dev)
     lengths = torch.empty((B, nbest), dtype=torch.int64, device=dev)
-    nbytes = lib().fk_ctc_beam_workspace_bytes(B, T, beam_width, K)
+    nbytes = getattr(lib(), ws_bytes)(B, T, beam_width, K)
     ws, _ = _ws(nbytes, dev)
     return B, T, Cn, K, il, ids, lengths, ws, nbytes
 
@@ -1452,6 +1453,39 @@ def ctc_beam_search_lm(logits: Tensor, lm, input_lengths: Optional[Tensor] = Non
              int(bool(use_eos)), ids.data_ptr(), ids.stride(0), ids.stride(1), lengths.data_ptr(), am.data_ptr(), lms.data_ptr(),
              total.data_ptr(), fk_dtype(logits), _ptr(ws), nbytes, _stream())
     return ids, lengths, am, lms, total
+
+
+def ctc_beam_search_lex(logits: Tensor, lexicon, lm=None, sep: int = 1, input_lengths: Optional[Tensor] = None, blank: int = 0, beam_width: int = 8,
+                        topk: Optional[int] = None, nbest: int = 1, lm_weight: float = 1.0, word_bonus: float = 0.0, use_eos: bool = True,
+                        pad: int = -100):
+    """ctc_beam_search constrained to labellings that spell words of `lexicon` (utils.lexicon.Lexicon, or its compile()d tables) separated
+    by the class `sep`, with the word-level backoff n-gram model `lm` (utils.ngram.NGramLM over the lexicon's word ids, its tables, or
+    None: only word_bonus acts) applied at word ends (semantics: include/franken_hip.h) -> (words int64 [B, nbest, (T + 1) // 2] padded
+    with `pad`, word_lengths int64 [B, nbest], ids int64 [B, nbest, T], lengths int64 [B, nbest], am / lm / total fp32 [B, nbest],
+    complete uint8 [B, nbest]), best first."""
+    lex = lexicon.compile() if hasattr(lexicon, "compile") else lexicon
+    tables = lex.null_lm() if lm is None else (lm.compile() if hasattr(lm, "compile") else lm)
+    if tables.n_classes != lex.n_words:
+        raise ValueError(f"the word model has {tables.n_classes} words, the lexicon {lex.n_words}")
+    if blank in lex.classes or sep in lex.classes or max(lex.classes) >= logits.shape[-1]:
+        raise ValueError(f"a pronunciation holds the blank {blank}, the separator {sep} or a class outside the head's {logits.shape[-1]}")
+    B, T, Cn, K, il, ids, lengths, ws, nbytes = _ctc_beam_prologue(logits, input_lengths, beam_width, topk, nbest, "fk_ctc_beam_lex_workspace_bytes")
+    dev = logits.device
+    d, t = tables.to(dev), lex.to(dev)
+    Lw = (T + 1) // 2
+    words = torch.empty((B, nbest, Lw), dtype=torch.int64, device=dev)
+    word_lengths = torch.empty((B, nbest), dtype=torch.int64, device=dev)
+    complete = torch.empty((B, nbest), dtype=torch.uint8, device=dev)
+    am, lms, total = (torch.empty((B, nbest), dtype=torch.float32, device=dev) for _ in range(3))
+    with _timed("ctc_beam_search_lex"):
+        call("fk_ctc_beam_search_lex", logits.data_ptr(), logits.stride(0), logits.stride(1), _ptr(il), B, T, Cn, blank, sep, beam_width, K, nbest, pad,
+             t["table"].data_ptr(), lex.cap, lex.max_probe, t["node_words"].data_ptr(), lex.n_nodes, t["word_list"].data_ptr(),
+             int(t["word_list"].numel()), lex.n_words, d["table"].data_ptr(), tables.cap, tables.max_probe, d["bow"].data_ptr(),
+             d["backoff"].data_ptr(), tables.n_states, d["uni_lp"].data_ptr(), d["uni_next"].data_ptr(), tables.start_state, tables.order,
+             float(lm_weight), float(word_bonus), int(bool(use_eos)), words.data_ptr(), words.stride(0), words.stride(1), word_lengths.data_ptr(),
+             ids.data_ptr(), ids.stride(0), ids.stride(1), lengths.data_ptr(), am.data_ptr(), lms.data_ptr(), total.data_ptr(),
+             complete.data_ptr(), fk_dtype(logits), _ptr(ws), nbytes, _stream())
+    return words, word_lengths, ids, lengths, am, lms, total, complete
 
 
 # ------------------------------------------------------------------------------------------- joint CTC / attention decoding

@@ -71,6 +71,10 @@ class BrainFormerCTC(_FileBrainFormer):
     hypotheses) of whichever path was asked for, with that path's ranking score (the CTC score, the fused total, the GPT's total), goes
     through engine.mbr_rerank: the hypothesis with the smallest expected edit distance under softmax(mbr_scale * score) comes first.  The
     first k of that order come back in the same forms, the scores being -risk.
+    decode_words(x, lexicon, sep, beam_width=W, nbest=1, ngram=word_lm, ...): WORDS out of a phoneme / letter head whose class `sep` separates
+    words: the search constrained to the pronunciations of a utils.lexicon.Lexicon with a word-level n-gram model at word ends
+    (engine.ctc_beam_decode_lexicon) -> (words, word_lengths[, scores]); word_error_rate(x, target_words, lexicon, sep, ...) is its
+    engine.error_rate.  decode itself is unchanged by it.
     utils.metrics.token_error_rate(targets, ids) of that result is the phoneme / token error rate; error_rate(x, targets, **decode
     arguments) computes the same number on the device (engine.error_rate).
     mwer_weight (constructor argument or attribute, default None = off): forward's loss becomes ctc + mwer_weight * mwer, one
@@ -143,6 +147,32 @@ class BrainFormerCTC(_FileBrainFormer):
                                                            length_bonus=length_bonus, bos_token_id=bos_token_id, eos_token_id=eos_token_id,
                                                            max_nodes=max_nodes)
         return (ids[:, 0], lengths[:, 0]) if nbest == 1 else (ids[:, :nbest], lengths[:, :nbest], total[:, :nbest])
+
+    @torch.no_grad()
+    def decode_words(self, x, lexicon, sep, beam_width=8, topk=None, nbest=1, ngram=None, ngram_weight=1.0, word_bonus=0.0, ngram_eos=True,
+                     mbr=False, mbr_scale=1.0, date_info=None):
+        """Words out of a phoneme / letter head (engine.ctc_beam_decode_lexicon): the beam search constrained to the pronunciations of
+        `lexicon` (utils.lexicon.Lexicon) with the class `sep` between words and the WORD-level n-gram model `ngram` (utils.ngram.NGramLM over
+        the lexicon's word ids, or None) at word ends -> (words int64 [B, L] padded with -100, word_lengths int64 [B]), L = (n_output_tokens +
+        1) // 2; nbest > 1 -> (words [B, nbest, L], word_lengths [B, nbest], scores [B, nbest]), best first, the scores being the totals.
+        mbr=True: the whole final list (beam_width hypotheses) goes through engine.mbr_rerank over its WORDS with the total as its score, and
+        the first nbest of that order come back, the scores being -risk.  lexicon.text(words, word_lengths) gives the strings."""
+        logits = self.features(x, date_info)
+        r = E.ctc_beam_decode_lexicon(logits, lexicon, ngram, sep=sep, blank=self.blank, beam_width=beam_width, topk=topk,
+                                      nbest=beam_width if mbr else nbest, lm_weight=ngram_weight, word_bonus=word_bonus, use_eos=ngram_eos, pad=-100)
+        words, word_lengths, scores = r.words, r.word_lengths, r.total
+        if mbr:
+            m = E.mbr_rerank(words, word_lengths, scores, scale=mbr_scale, pad=-100)
+            words, word_lengths, scores = m.ids[:, :nbest], m.lengths[:, :nbest], -m.risk[:, :nbest]
+        return (words[:, 0], word_lengths[:, 0]) if nbest == 1 else (words, word_lengths, scores)
+
+    @torch.no_grad()
+    def word_error_rate(self, x, target_words, lexicon, sep, date_info=None, **decode_kwargs):
+        """decode_words(x, lexicon, sep, **decode_kwargs), its best hypothesis against target_words (int64 [B, Lmax] word ids padded with
+        -100) -> engine.error_rate's (rate, errors, ref_lengths): the corpus word error rate as a device scalar, no synchronisation"""
+        out = self.decode_words(x, lexicon, sep, date_info=date_info, **decode_kwargs)
+        words, lengths = (out[0][:, 0], out[1][:, 0]) if out[0].dim() == 3 else (out[0], out[1])
+        return E.error_rate(target_words, words, hypothesis_lengths=lengths, pad_value=-100)
 
     def _decode_mbr(self, logits, beam_width, topk, nbest, lm, lm_prefix, lm_weight, length_bonus, eos_token_id, am_weight, bos_token_id, max_nodes,
                     ngram, ngram_weight, ngram_bonus, ngram_eos, mbr_scale):

@@ -663,6 +663,56 @@ int fk_ctc_beam_search_lm(const void* logits, int64_t ldb, int64_t ldt, const in
                           int64_t ld_ids_b, int64_t ld_ids_h, int64_t* lengths, float* am, float* lm, float* total, int dtype, void* workspace,
                           size_t workspace_bytes, void* stream);
 
+/* ---- Lexicon-constrained CTC prefix beam search (csrc/ctc.hip): words out of a phoneme / letter head.  Semantics of this build
+ *      (tests/ctc_lex_ref.py restates them in float64); all arithmetic is fp32.
+ *   The head has a word separator class sep != blank, both in [0, C).  A lexicon maps pronunciations (non-empty tuples of classes, none
+ *   blank or sep) to word ids in [0, V); several words may share a pronunciation (homophones, at most 8 a node), a word may have several.
+ *   It is compiled to a trie, node 0 the root = the state at a word start; a node where a pronunciation ends is terminal (the root never).
+ *   The acoustic recursion (pb, pnb, total, the candidate rule, the flow between resident prefixes) is EXACTLY fk_ctc_beam_search's, over
+ *   labellings of the head's classes, sep included.  A slot also carries its trie node, its word count, lmw, lm (as fk_ctc_beam_search_lm)
+ *   and the state of the word LM.  Only which NEW prefixes are proposed and the key change:
+ *     p (node n) + (c,), c != sep:  proposed only if the trie has the child (n, c); it takes that child; lmw, lm, word state carry over
+ *     p (node n) + (sep,):          proposed only if n is terminal.  w* = argmax over the words of n of ln P_lm(w | word state), exact ties
+ *                                   to the first word of the node's list (ascending word id);  lmw' = lmw + (lm_weight * ln P(w*) +
+ *                                   word_bonus) (the product, then the bonus, then the sum, each rounded);  lm' = lm + ln P(w*);  the word
+ *                                   state advances by w*, the node becomes the root, the word count goes up by one
+ *     key = total + lmw; an entry with total -inf is never kept; exact ties, and the bits of a prefix that returns, as in
+ *     fk_ctc_beam_search_lm.  A rejected candidate has no key and costs no beam slot.  Neither blank nor sep is ever looked up in the LM.
+ *   After the last frame a hypothesis at the root is complete; one at a terminal node is closed as if by a sep without acoustic term (its
+ *   word, LM term, bonus and state advance) and is complete; one at any other node is incomplete: no closing term, its unfinished word is
+ *   not emitted.  use_eos != 0: complete hypotheses add lm_weight * ln P_lm(</s> | state) (and lm that term).  Final order: complete
+ *   before incomplete, then the final key descending, then the order of the last selection.
+ *   Result, best first, the first nbest: words int64 [B, nbest, (T + 1) / 2] (strides ld_words_b, ld_words_h) padded with `pad`,
+ *   word_lengths int64 [B, nbest], ids / lengths the labelling as fk_ctc_beam_search, am (the CTC mass) / lm (unweighted) / total (the
+ *   final key) fp32 [B, nbest], complete uint8 [B, nbest].  A slot without hypothesis: lengths 0, scores -inf, rows of pad, complete 0.
+ *   T_b = 0 gives the empty, complete hypothesis.
+ *   Tables (frankenstein_amd/utils/lexicon.py compiles and validates them):
+ *     trie_table  int32 [trie_cap][4], 16-byte aligned: open addressing, {node, class, child, 0}, node -1 = empty; trie_cap a power of two
+ *                 (>= 2 x entries); the home of (node, class) is fk_ngram_hash(node, class) & (trie_cap - 1), linear probing;
+ *                 trie_max_probe = the largest number of entries a successful look-up reads.  One probe sequence a look-up, no backoff.
+ *     node_words  int32 [n_nodes][2], 8-byte aligned: {first, count} into word_list int32 [n_list]; count 0: not terminal
+ *     lm_*        the word model as in fk_ctc_beam_search_lm, over V word ids, the end of sentence is id V.  Without a model pass a
+ *                 unigram table of zeros (order 1, one state): every ln P is 0, w* the lowest id, only word_bonus acts.
+ *   The device cannot check the tables: the trie loop is bounded by trie_max_probe, the word-LM look-ups by lm_order * lm_max_probe; a
+ *   child read from the trie is clamped into [0, n_nodes), a count into [0, 8], a list index into [0, n_list), a word into [0, V), LM
+ *   states and tokens as in fk_ctc_beam_search_lm, and every table index is masked.  A malformed table gives wrong words, never an
+ *   unbounded loop or an access outside a table.
+ *   Envelope of fk_ctc_beam_search; workspace fk_ctc_beam_lex_workspace_bytes(B, T, W, K) (0 outside the envelope: fk_ctc_beam_search's and
+ *   one int32 per trie node, the word a sep node closed).  FK_EINVAL, no launch: sep outside [0, C) or equal to blank, a null table, a hash
+ *   table that is not 16-byte aligned, a capacity that is no power of two, max_probe outside 1 .. cap, n_nodes < 1, n_list < 1, V < 1,
+ *   weights that are not finite, a short workspace, words strides below (T + 1) / 2.
+ *   Two launches (the first is fk_ctc_beam_search's), no atomics, the same bits every run, nothing waits for the host.
+ *   Not built: LM look-ahead into the trie, an unknown-word path, forking on homophones (the choice is greedy per labelling).            */
+size_t fk_ctc_beam_lex_workspace_bytes(int64_t B, int64_t T, int64_t W, int64_t K);
+int fk_ctc_beam_search_lex(const void* logits, int64_t ldb, int64_t ldt, const int64_t* input_lengths, int64_t B, int64_t T, int64_t C, int64_t blank,
+                           int64_t sep, int64_t W, int64_t K, int64_t nbest, int64_t pad, const int32_t* trie_table, int64_t trie_cap,
+                           int64_t trie_max_probe, const int32_t* node_words, int64_t n_nodes, const int32_t* word_list, int64_t n_list, int64_t V,
+                           const int32_t* lm_table, int64_t lm_cap, int64_t lm_max_probe, const float* lm_bow, const int32_t* lm_backoff,
+                           int64_t lm_states, const float* lm_uni_lp, const int32_t* lm_uni_next, int64_t lm_start_state, int64_t lm_order,
+                           float lm_weight, float word_bonus, int use_eos, int64_t* words, int64_t ld_words_b, int64_t ld_words_h,
+                           int64_t* word_lengths, int64_t* ids, int64_t ld_ids_b, int64_t ld_ids_h, int64_t* lengths, float* am, float* lm,
+                           float* total, uint8_t* complete, int dtype, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- CTC prefix scores inside the GPT beam search (csrc/ctc.hip): one-pass joint CTC / attention decoding.  Every candidate c of every
  *      beam h of fk_beam_topk is rescored in front of fk_beam_select*:
  *          top_lp[r][j] <- (1 - weight) * top_lp[r][j] + weight * delta(h_r, c),   delta = psi(h c) - psi(h),

@@ -12,6 +12,12 @@ python tools/ctc_bench.py --beam W --ngram ORDER [rounds] [reps]: also the searc
 the same logits, in the same interleaved rounds: an interpolated Witten-Bell model of that order from 2000 seeded Zipf-distributed
 sequences over the head's classes (utils.ngram), with its table size and max_probe, and what the fusion adds per frame.
 
+python tools/ctc_bench.py --beam W --lexicon N_WORDS [--ngram ORDER] [rounds] [reps]: also the lexicon-constrained search
+(engine.ctc_beam_decode_lexicon) in the same interleaved rounds: a seeded synthetic lexicon of N_WORDS words (utils.lexicon.zipf_lexicon,
+pronunciations of 2 .. 6 classes, the separator is class C - 2 and gets + 1.5 on a copy of the logits so that words end) with a
+Witten-Bell word model of order ORDER (3 without --ngram) from 2000 seeded Zipf-distributed word sequences, and the same search without
+a word model: the difference between the two is what the word-LM look-ups cost, the rest over the plain search is the trie.
+
 python tools/ctc_bench.py --align [rounds] [reps]: the forced alignment (engine.ctc_forced_align, both launches) beside the CTC loss forward
 without lattice (K.ctc_loss_fwd(want_grad=False): the same row_lse launch and the same sweep with logsumexp for max) at the same shape in
 the same interleaved rounds, and beside the float64 host restatement (tests/ctc_align_ref.py), at B = 32, 32 x 50258 with 25 labels and
@@ -32,6 +38,9 @@ if beam is not None:
 ngram = int(argv.pop(argv.index("--ngram") + 1)) if "--ngram" in argv else None
 if ngram is not None:
     argv.remove("--ngram")
+lexicon = int(argv.pop(argv.index("--lexicon") + 1)) if "--lexicon" in argv else None
+if lexicon is not None:
+    argv.remove("--lexicon")
 align = "--align" in argv
 if align:
     argv.remove("--align")
@@ -62,6 +71,17 @@ for B, T, C, Kc in (BEAM_SHAPES if beam is not None else []):
         lm = NGramLM.from_corpus(zipf_sequences(2000, C, blank, (5, 20) if C > 1024 else (10, 40), 0, n_types=min(C - 1, 5000)), ngram, C)
         tab = lm.compile()
         cases["fused"] = lambda: E.ctc_beam_decode_lm(logits, lm, None, blank, beam, Kc, beam, 0.8, 0.5)
+    if lexicon is not None:
+        from frankenstein_amd.utils.lexicon import zipf_lexicon
+        from frankenstein_amd.utils.ngram import NGramLM, zipf_sequences
+        sep = C - 2
+        lex = zipf_lexicon(lexicon, C, blank, sep, (2, 6), 0, 0.1)
+        wlm = NGramLM.from_corpus(zipf_sequences(2000, lexicon + 1, lexicon, (5, 20), 0), ngram or 3, lexicon)
+        ltab, wtab = lex.compile(), wlm.compile()
+        lex_logits = logits.clone()
+        lex_logits[:, :, sep] += 1.5
+        cases["lex"] = lambda: E.ctc_beam_decode_lexicon(lex_logits, lex, wlm, sep, None, blank, beam, Kc, beam, 0.8, 0.5)
+        cases["lex no model"] = lambda: E.ctc_beam_decode_lexicon(lex_logits, lex, None, sep, None, blank, beam, Kc, beam, 0.8, 0.5)
     for f in cases.values():
         f()
     torch.cuda.synchronize()
@@ -89,6 +109,14 @@ for B, T, C, Kc in (BEAM_SHAPES if beam is not None else []):
               f"fused - beam {med['fused'] - med['beam']:+9.1f} us = {(med['fused'] - med['beam']) / T:+.3f} us per frame, fused / beam {med['fused'] / med['beam']:.2f};  "
               f"rounds min .. max: beam {spread['beam'][0]:.1f} .. {spread['beam'][1]:.1f} us, fused {spread['fused'][0]:.1f} .. {spread['fused'][1]:.1f} us;  "
               f"the best hypothesis moves in {moved} of {B}", flush=True)
+    if lexicon is not None:
+        spread = {k: (min(v), max(v)) for k, v in times.items()}
+        r = cases["lex"]()
+        print(f"    lexicon {lexicon} words: {ltab.n_nodes} trie nodes in {ltab.cap} entries ({ltab.cap * 16 / 1024:.0f} KiB), max_probe {ltab.max_probe}; word model order "
+              f"{wlm.order}: {wtab.n_entries} n-grams, max_probe {wtab.max_probe};  lex - beam {med['lex'] - med['beam']:+9.1f} us = {(med['lex'] - med['beam']) / T:+.3f} us per frame, "
+              f"lex / beam {med['lex'] / med['beam']:.2f};  of it the word-LM look-ups (lex - lex no model) {med['lex'] - med['lex no model']:+9.1f} us, the trie and the "
+              f"rest (lex no model - beam) {med['lex no model'] - med['beam']:+9.1f} us;  rounds min .. max: " + ", ".join(f"{k} {a:.1f} .. {b:.1f} us" for k, (a, b) in spread.items())
+              + f";  complete best hypotheses {int(r.complete[:, 0].sum())} of {B}, words in them {float(r.word_lengths[:, 0].float().mean()):.1f} on average", flush=True)
 
 for B, T, C, L in ([SHAPES[0], SHAPES[2]] if align else []):
     from tests import ctc_align_ref as AR
