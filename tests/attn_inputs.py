@@ -24,7 +24,11 @@ Bound, on every element:   |got - ref| <= [2^-8 |ref| + 2^-8 mag, bf16 only] + 2
 with mag the float64 sum of the absolute terms of the last product (o: sum_j P |v|, dv: sum_i P |dO|, dq: scale sum_j |dS| |k|,
 dk: scale sum_i |dS| |q|): 2^-8 |ref| is one bf16 ulp for the stored output, 2^-8 mag one bf16 rounding of P in front of its matrix
 product and one of dS in front of its products (2^-9 each), 2e-5 the project's fp32 tolerance (test_kernels_gpu.close), absolute and
-relative to mag.  lse: atol = rtol = 1e-4 for both dtypes (it is fp32 on the device and the scores are exact)."""
+relative to mag.  lse: atol = rtol = 1e-4 for both dtypes (it is fp32 on the device and the scores are exact).
+
+Fused inverse RoPE (attn_bwd with a rope_table; tests/test_attn_rope_cpu.py, tests/test_attn_rope_gpu.py): rope_table draws angles that
+keep |cos| and |sin| above 0.38, unrotate turns dq, dk and their mags by minus the angle, and the same bound holds with mag' (the
+rotation is linear with coefficients of at most 1; the kernels rotate fp32 accumulators and round once at the store)."""
 import math
 
 import torch
@@ -271,10 +275,12 @@ def bf16(t):
     return t.float().to(BF).double()
 
 
-def rounding_model(q, k, v, do, vis, scale, dtype):
+def rounding_model(q, k, v, do, vis, scale, dtype, store=True):
     """The kernels' documented roundings on the CPU: bf16 operands round the unnormalised P in front of P V, the output O, the
     normalised P in front of P^T dO and dS in front of its two products, every output once more as it is stored, and delta comes from
-    the rounded O; fp32 operands run the same products in fp32 arithmetic.  [B, H, N, D] layout.  -> o, lse, dq, dk, dv"""
+    the rounded O; fp32 operands run the same products in fp32 arithmetic.  [B, H, N, D] layout.  -> o, lse, dq, dk, dv
+    store=False: dq and dk as the accumulators hold them, before the rounding of the store (the fused inverse RoPE rotates them first)"""
+    st = bf16 if store else (lambda t: t)
     if dtype == F32:
         o, lse, _, P = forward(q, k, v, vis, scale)
         o32 = o.float()
@@ -293,5 +299,52 @@ def rounding_model(q, k, v, do, vis, scale, dtype):
     lse = (m + torch.log(l)).masked_fill(dead, float("inf")).squeeze(-1)
     P = e / l
     dS = bf16(P * (do @ v.transpose(-1, -2) - (do * o).sum(-1, keepdim=True)))
-    return {"o": o, "lse": lse.float().double(), "dq": bf16(scale * (dS @ k)), "dk": bf16(scale * (dS.transpose(-1, -2) @ q)),
+    return {"o": o, "lse": lse.float().double(), "dq": st(scale * (dS @ k)), "dk": st(scale * (dS.transpose(-1, -2) @ q)),
             "dv": bf16(bf16(P).transpose(-1, -2) @ do)}
+
+
+# ------------------------------------------------------------------------------------------------ fused inverse RoPE
+# attn_bwd(..., rope_table=, rope_off=) rotates dq and dk by minus the angle of their row as it stores them (tests/test_attn_rope_cpu.py,
+# tests/test_attn_rope_gpu.py; cases: tests/cases.py ATTN_ROPE_CASES).  The kernels take any table, so the angles here are not RoPE's:
+# at RoPE's own angles most pairs of a short sequence have sin ~ 0, and a wrong sign or a neighbour's angle would hide in the tolerance.
+ROPE_SLACK = 8                                                       # table rows drawn past the last one a case reads
+
+
+def rope_table(Bt, rows, D, seed):
+    """fp32 [Bt, rows, D / 2, 2] of (cos, sin) of theta = (pi / 2) m + pi / 8 + (pi / 4) u, m in {0, 1, 2, 3}, u in [0, 1), drawn
+    independently for every sample, position and pair: |cos|, |sin| >= sin(pi / 8) = 0.38 everywhere, and neighbouring rows,
+    neighbouring pairs and different samples have unrelated angles."""
+    g = torch.Generator().manual_seed(seed)
+    m = torch.randint(0, 4, (Bt, rows, D // 2), generator=g).double()
+    u = torch.rand(Bt, rows, D // 2, generator=g, dtype=torch.float64)
+    th = (math.pi / 2) * m + math.pi / 8 + (math.pi / 4) * u
+    return torch.stack([torch.cos(th), torch.sin(th)], -1).float()
+
+
+def case_table(case):
+    """-> (tall, Tc): the case's table with ROPE_SLACK rows more than the Tc = rope_off + N it hands over (tall[:, :Tc]); the "strided"
+    form hands that slice over as it stands, a view whose batch stride exceeds Tc * D"""
+    Tc = case["rope_off"] + case["Nq"]
+    Bt = 1 if case["table"] == "shared" else case["B"]
+    return rope_table(Bt, Tc + ROPE_SLACK, case["D"], case["seed"]), Tc
+
+
+def unrotate(x, mag, table, off):
+    """x, mag [B, H, N, D] float64, table [Bt, rows, D / 2, 2] (Bt in {1, B}), row r of x at table row off + r.  For the pairs (d, d + 1):
+    out0 = x0 c + x1 s, out1 = -x0 s + x1 c, and mag0' = |c| mag0 + |s| mag1, mag1' = |s| mag0 + |c| mag1.  The table's fp32 values are
+    widened to float64: the numbers the device holds."""
+    N = x.shape[2]
+    t = table.double()[:, None, off:off + N]                          # [Bt, 1, N, D / 2, 2]
+    c, s = t[..., 0], t[..., 1]
+    x0, x1, m0, m1 = x[..., 0::2], x[..., 1::2], mag[..., 0::2], mag[..., 1::2]
+    out = torch.stack([x0 * c + x1 * s, -x0 * s + x1 * c], -1).flatten(-2)
+    omag = torch.stack([c.abs() * m0 + s.abs() * m1, s.abs() * m0 + c.abs() * m1], -1).flatten(-2)
+    return out, omag
+
+
+def unrotate_grads(ref, table, off):
+    """the reference of attn_bwd with a rope_table: backward()'s dq and dk un-rotated (with their mags), dv as it is"""
+    out = dict(ref)
+    for n in ("dq", "dk"):
+        out[n], out["mag_" + n] = unrotate(ref[n], ref["mag_" + n], table, off)
+    return out

@@ -320,6 +320,44 @@ ATTN_SPIKE_CASES = [
     _attn("bf16", 1, 2, 256, 256, 64, ("none",), ("FWD_ASM", "DQ_ASM", "DKDVW_ASM"), ps=True, spike=-2048.0),
 ]
 
+# attn_bwd with a rope_table: the inverse rotation fused into the dQ / dK stores (tests/test_attn_rope_gpu.py; tests/test_attn_rope_cpu.py
+# pins the routes, what the list covers, and that a wrong rotation is a gross error on every case).  Self-attention (Nq = Nk = N), q | k | v
+# and dq | dk | dv views of one buffer each, as engine.AttnBranch.run_backward calls it.  routes: kernels.attn_route_names(..., rope=True).
+# table: "shared" [Tc, D/2, 2] | "sample" [B, Tc, D/2, 2] | "strided" (the [:, :Tc] slice of a taller per-sample buffer: batch stride
+# > Tc * D); Tc = rope_off + N (Rope.pos_off); seed: of the table's angles (attn_inputs.rope_table)
+def _rope(dtype, B, H, N, D, mask, routes, table, rope_off, ps=False, seed=0):
+    c = _attn(dtype, B, H, N, N, D, mask, routes, ps=ps)
+    c.update(id=f"{c['id']}-{table}-off{rope_off}", table=table, rope_off=rope_off, seed=1000 + seed)
+    return c
+
+
+_ASM = ("FWD_ASM", "DQ_ASM")
+ATTN_ROPE_CASES = [
+    # bf16 D = 64, pre-scaled queries: the generated streams (narrow and wide dK/dV, full and block-causal) ..
+    _rope("bf16", 2, 2, 128, 64, ("none",), _ASM + ("DKDV_ASM",), "shared", 0, ps=True),
+    _rope("bf16", 2, 2, 256, 64, ("none",), _ASM + ("DKDVW_ASM",), "strided", 0, ps=True),
+    _rope("bf16", 2, 2, 384, 64, ("block", 128), _ASM + ("DKDV_ASM",), "sample", 5, ps=True),
+    _rope("bf16", 2, 2, 512, 64, ("block", 256), _ASM + ("DKDVW_ASM",), "shared", 3, ps=True),
+    # .. and the tile loops: whole tiles, ragged, every analytic and table mask, position offsets in the mask and in the table at once
+    _rope("bf16", 2, 3, 192, 64, ("none",), _PS, "shared", 0, ps=True),
+    _rope("bf16", 2, 2, 200, 64, ("block", 8), _PS, "sample", 7, ps=True),
+    _rope("bf16", 2, 2, 333, 64, ("causal",), _PS, "strided", 0, ps=True),
+    _rope("bf16", 2, 2, 256, 64, ("sliced", "block", 128, 512, 512), _PS, "shared", 256, ps=True),
+    _rope("bf16", 2, 2, 260, 64, ("prefix", 16, 700), _PS, "sample", 1, ps=True),
+    _rope("bf16", 2, 2, 270, 64, ("keypad",), _PS, "shared", 9, ps=True),
+    # bf16 D = 64, queries not pre-scaled, dense mask: the generic kernels on the swizzled image (the engine's "rope" path)
+    _rope("bf16", 2, 2, 100, 64, ("dense", 2, 2), _GEN, "sample", 3),
+    # the generic kernels: fp32 D 8 / 16 / 32 / 64, bf16 D 8 (scalar bf16x4 store) / 16 / 32 / 128, ragged N, more than one workgroup
+    _rope("f32", 2, 3, 70, 8, ("causal",), _GEN, "sample", 3),
+    _rope("f32", 2, 2, 150, 16, ("keypad",), _GEN, "shared", 0),
+    _rope("f32", 2, 2, 90, 32, ("prefix", 16, 300), _GEN, "strided", 0),
+    _rope("f32", 1, 2, 133, 64, ("block", 16), _GEN, "shared", 5),
+    _rope("bf16", 2, 2, 130, 8, ("keypad",), _GEN, "sample", 1),
+    _rope("bf16", 2, 2, 140, 16, ("prefix", 16, 400), _GEN, "shared", 0),
+    _rope("bf16", 2, 3, 75, 32, ("causal",), _GEN, "strided", 0),
+    _rope("bf16", 2, 2, 200, 128, ("block", 8), _GEN, "shared", 7),
+]
+
 
 # ------------------------------------------------------------------------------------------------ token-on-the-lane kernels
 # The shapes of tests/test_lane_kernels_gpu.py (csrc/mlp_fused.hip: mlp_up_fused_kernel, qkv_rope_fused_kernel, mlp_bwd_fused_kernel and
