@@ -28,10 +28,21 @@ relative to mag.  lse: atol = rtol = 1e-4 for both dtypes (it is fp32 on the dev
 
 Fused inverse RoPE (attn_bwd with a rope_table; tests/test_attn_rope_cpu.py, tests/test_attn_rope_gpu.py): rope_table draws angles that
 keep |cos| and |sin| above 0.38, unrotate turns dq, dk and their mags by minus the angle, and the same bound holds with mag' (the
-rotation is linear with coefficients of at most 1; the kernels rotate fp32 accumulators and round once at the store)."""
+rotation is linear with coefficients of at most 1; the kernels rotate fp32 accumulators and round once at the store).
+
+Dropout on the probabilities (attn_fwd / attn_bwd with a dropout tuple; tests/test_attn_drop_cpu.py, tests/test_attn_drop_gpu.py):
+forward and backward take keep (bool, every decision predicted by tests/dropout_ref.py) and drop_scale s = fp32(1) / (fp32(1) - fp32(p))
+widened: Pd = P * keep * s, o = Pd v, dv = Pd^T dO, dP = keep * s * (dO v^T), delta = rowsum(dO * O), dS = P (dP - delta); lse is the
+softmax's own.  The mags go through Pd and |dS| and the bound formula is unchanged: the forward rounds the kept entries of the
+unnormalised P (2^-9 each, s / l is applied in fp32 behind the product: 2^-9 sum_kept P s |v| = 2^-9 mag_o), dK/dV rounds P s once in
+front of P^T dO (2^-9 mag_dv) and dS is rounded once as before.  The inputs aim every row at three or more keys of equal score, so one
+keep bit of a target is worth about s / 3 of |v| in o: a single wrong decision is a gross error, not only a wrong mask."""
 import math
 
+import numpy as np
 import torch
+
+from tests import dropout_ref as DR
 
 LOG2E = 1.4426950408889634
 BF, F32 = torch.bfloat16, torch.float32
@@ -232,8 +243,29 @@ def make_inputs(case):
 
 
 # ------------------------------------------------------------------------------------------------ reference
-def forward(q, k, v, vis, scale):
-    """q [.., Nq, D], k, v [.., Nk, D] float64, vis bool broadcastable to [.., Nq, Nk] -> o, lse, mag_o, P"""
+def drop_scale32(p):
+    """the 1 / (1 - p) the device holds (fp32 arithmetic on the fp32 p), widened to float64"""
+    return float(np.float32(1) / (np.float32(1) - np.float32(p)))
+
+
+def case_keep(case, hi=None, lo=None, **over):
+    """bool [B, H, Nq, Nk]: the keep decisions of a dropout case (tests/cases.py ATTN_DROP_CASES), predicted on the host
+    (tests/dropout_ref.py).  hi(b, h, q) and lo(key) replace the two index words (integer arrays [B, 1, 1, 1], [1, H, 1, 1], [1, 1, Nq, 1]
+    and [1, 1, 1, Nk] go in), seed = / step = / site = / p = replace the case's: the mutants of tests/test_attn_drop_cpu.py"""
+    B, H, Nq, Nk = case["B"], case["H"], case["Nq"], case["Nk"]
+    a = {n: over.get(n, case[n]) for n in ("seed", "step", "site", "p")}
+    b, h = np.arange(B, dtype=np.int64).reshape(B, 1, 1, 1), np.arange(H, dtype=np.int64).reshape(1, H, 1, 1)
+    q, key = np.arange(Nq, dtype=np.int64).reshape(1, 1, Nq, 1), np.arange(Nk, dtype=np.int64).reshape(1, 1, 1, Nk)
+    row = (b * H + h) * Nq + q if hi is None else hi(b, h, q)
+    col = key if lo is None else lo(key)
+    keep = DR.keep(a["seed"], a["step"], a["site"], (row & 0xFFFFFFFF).astype(np.uint64), (col & 0xFFFFFFFF).astype(np.uint64), a["p"])
+    return torch.from_numpy(np.broadcast_to(keep, (B, H, Nq, Nk)).copy())
+
+
+def forward(q, k, v, vis, scale, keep=None, drop_scale=1.0):
+    """q [.., Nq, D], k, v [.., Nk, D] float64, vis bool broadcastable to [.., Nq, Nk] -> o, lse, mag_o, P
+    keep (bool, broadcastable to [.., Nq, Nk]) and drop_scale: dropout on the probabilities, o = Pd v with Pd = P * keep * drop_scale;
+    lse and the returned P are the softmax's own (the statistics do not see the dropout)"""
     s = (q @ k.transpose(-1, -2)) * scale
     s = s.masked_fill(~vis, float("-inf"))
     m = s.max(-1, keepdim=True).values
@@ -242,17 +274,23 @@ def forward(q, k, v, vis, scale):
     l = e.sum(-1, keepdim=True)
     P = e / l.masked_fill(dead, 1.0)
     lse = (m + torch.log(l.masked_fill(dead, 1.0))).masked_fill(dead, float("inf")).squeeze(-1)
-    return P @ v, lse, P @ v.abs(), P
+    Pd = P if keep is None else P * keep * drop_scale
+    return Pd @ v, lse, Pd @ v.abs(), P
 
 
-def backward(q, k, v, do, P, o_used, scale):
-    """-> dq, dk, dv and their mags; delta = rowsum(do * o_used)"""
+def backward(q, k, v, do, P, o_used, scale, keep=None, drop_scale=1.0):
+    """-> dq, dk, dv and their mags; delta = rowsum(do * o_used)
+    keep, drop_scale: dv = Pd^T do and dP = keep * drop_scale * (do v^T) go through the dropout, dS = P (dP - delta) with the softmax's P"""
     dP = do @ v.transpose(-1, -2)
+    Pd = P
+    if keep is not None:
+        dP = dP * keep * drop_scale
+        Pd = P * keep * drop_scale
     delta = (do * o_used).sum(-1, keepdim=True)
     dS = P * (dP - delta)
     aS = dS.abs()
-    return {"dq": scale * (dS @ k), "dk": scale * (dS.transpose(-1, -2) @ q), "dv": P.transpose(-1, -2) @ do,
-            "mag_dq": scale * (aS @ k.abs()), "mag_dk": scale * (aS.transpose(-1, -2) @ q.abs()), "mag_dv": P.transpose(-1, -2) @ do.abs()}
+    return {"dq": scale * (dS @ k), "dk": scale * (dS.transpose(-1, -2) @ q), "dv": Pd.transpose(-1, -2) @ do,
+            "mag_dq": scale * (aS @ k.abs()), "mag_dk": scale * (aS.transpose(-1, -2) @ q.abs()), "mag_dv": Pd.transpose(-1, -2) @ do.abs()}
 
 
 def heads(t):
@@ -275,32 +313,48 @@ def bf16(t):
     return t.float().to(BF).double()
 
 
-def rounding_model(q, k, v, do, vis, scale, dtype, store=True):
+def rounding_model(q, k, v, do, vis, scale, dtype, store=True, keep=None, drop_scale=1.0):
     """The kernels' documented roundings on the CPU: bf16 operands round the unnormalised P in front of P V, the output O, the
     normalised P in front of P^T dO and dS in front of its two products, every output once more as it is stored, and delta comes from
     the rounded O; fp32 operands run the same products in fp32 arithmetic.  [B, H, N, D] layout.  -> o, lse, dq, dk, dv
-    store=False: dq and dk as the accumulators hold them, before the rounding of the store (the fused inverse RoPE rotates them first)"""
+    store=False: dq and dk as the accumulators hold them, before the rounding of the store (the fused inverse RoPE rotates them first)
+    keep, drop_scale: dropout, rounded where the kernels round: the forward zeroes the dropped entries of the unnormalised P, rounds
+    the kept ones and applies drop_scale / l in fp32 behind the product; dK/dV rounds P * drop_scale once in front of P^T dO; dS =
+    P (keep * drop_scale * dP - delta) is rounded once, as without dropout"""
     st = bf16 if store else (lambda t: t)
+    ks = None if keep is None else keep.double() * drop_scale
     if dtype == F32:
-        o, lse, _, P = forward(q, k, v, vis, scale)
+        o, lse, _, P = forward(q, k, v, vis, scale, keep, drop_scale)
         o32 = o.float()
         P32 = P.float()
         dP = do.float() @ v.float().transpose(-1, -2)
+        Pd32 = P32
+        if ks is not None:
+            dP = dP * ks.float()
+            Pd32 = P32 * ks.float()
         dS = P32 * (dP - (do.float() * o32).sum(-1, keepdim=True))
         return {"o": o32.double(), "lse": lse.float().double(), "dq": (scale * (dS @ k.float())).double(),
-                "dk": (scale * (dS.transpose(-1, -2) @ q.float())).double(), "dv": (P32.transpose(-1, -2) @ do.float()).double()}
+                "dk": (scale * (dS.transpose(-1, -2) @ q.float())).double(), "dv": (Pd32.transpose(-1, -2) @ do.float()).double()}
     s = (q @ k.transpose(-1, -2)) * scale
     s = s.masked_fill(~vis, float("-inf"))
     m = s.max(-1, keepdim=True).values
     dead = torch.isinf(m) & (m < 0)
     e = torch.exp(s - m.masked_fill(dead, 0.0))
     l = e.sum(-1, keepdim=True).masked_fill(dead, 1.0)
-    o = bf16((bf16(e) @ v) / l)
     lse = (m + torch.log(l)).masked_fill(dead, float("inf")).squeeze(-1)
     P = e / l
-    dS = bf16(P * (do @ v.transpose(-1, -2) - (do * o).sum(-1, keepdim=True)))
+    dP = do @ v.transpose(-1, -2)
+    if ks is None:
+        o = bf16((bf16(e) @ v) / l)
+        Pd = P
+    else:
+        inv = (torch.tensor(drop_scale, dtype=F32) / l.float()).double()      # drop_scale / l in fp32, behind the product
+        o = bf16(((bf16(e) * keep) @ v) * inv)
+        dP = dP * ks
+        Pd = P * ks
+    dS = bf16(P * (dP - (do * o).sum(-1, keepdim=True)))
     return {"o": o, "lse": lse.float().double(), "dq": st(scale * (dS @ k)), "dk": st(scale * (dS.transpose(-1, -2) @ q)),
-            "dv": bf16(bf16(P).transpose(-1, -2) @ do)}
+            "dv": bf16(bf16(Pd).transpose(-1, -2) @ do)}
 
 
 # ------------------------------------------------------------------------------------------------ fused inverse RoPE

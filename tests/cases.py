@@ -358,6 +358,49 @@ ATTN_ROPE_CASES = [
     _rope("bf16", 2, 2, 200, 128, ("block", 8), _GEN, "shared", 7),
 ]
 
+# attn_fwd / attn_bwd with a dropout tuple (tests/test_attn_drop_gpu.py; tests/test_attn_drop_cpu.py pins the routes, what the list covers,
+# and that a keep mask wrong in any way, down to one bit, is a gross error on every case).  Dropout runs on the generic kernels only
+# (kernels.attn_route_names(..., dropout=True)).  p: drop probability; seed, step: the two seed words on the device; site: the number of
+# the application within the forward (step and site nonzero; a RoPE case draws its table's angles from the same seed).  layout: "split" =
+# q in its own buffer, k | v side by side, as in the route tests; "qkv" = q | k | v and dq | dk | dv views of one [B, N, 3 H D] buffer each,
+# as engine.AttnBranch passes them (Nq = Nk).  table / rope_off as in _rope: attn_bwd gets the table together with the dropout tuple.
+def _drop(dtype, B, H, Nq, Nk, D, mask, p, layout="split", seed=424242, step=9, site=2, table=None, rope_off=0):
+    c = _attn(dtype, B, H, Nq, Nk, D, mask, _GEN)
+    c.update(id=f"{dtype}-{B}x{H}x{Nq}x{Nk}x{D}-{'_'.join(map(str, mask))}-p{p}-{layout}-{seed}.{step}.{site}"
+                + (f"-{table}-off{rope_off}" if table else ""), p=p, seed=seed, step=step, site=site, layout=layout)
+    if table:
+        c.update(table=table, rope_off=rope_off)
+    return c
+
+
+ATTN_DROP_ROWS = 1 << 16                 # the row-number case numbers its rows past this
+ATTN_DROP_CASES = [
+    # fp32 D 8 / 16 / 32 / 64, bf16 D 8 / 16 / 32 / 64 / 128; every mask kind, each at some p >= 0.25; ragged, Nq != Nk, p 0.1 .. 0.9
+    _drop("f32", 2, 3, 40, 130, 8, ("none",), 0.5),
+    _drop("f32", 2, 2, 150, 150, 16, ("causal",), 0.1, step=3, site=1),
+    _drop("f32", 1, 2, 150, 200, 32, ("sliced", "causal", 0, 300, 260), 0.25),
+    _drop("f32", 2, 2, 70, 100, 64, ("dense", 2, 2), 0.25, seed=77001, step=1, site=5),
+    _drop("f32", 2, 2, 139, 139, 32, ("keypad",), 0.9),
+    _drop("bf16", 2, 2, 130, 130, 8, ("keypad",), 0.25),
+    _drop("bf16", 2, 2, 140, 140, 16, ("prefix", 16, 400), 0.5),
+    _drop("bf16", 2, 3, 70, 100, 32, ("dense", 1, 3), 0.1),
+    _drop("bf16", 2, 2, 200, 200, 128, ("causal",), 0.9, seed=5, step=70000, site=3),
+    _drop("bf16", 2, 2, 130, 130, 64, ("block", 16), 0.5),
+    _drop("bf16", 1, 2, 150, 90, 64, ("dense", 1, 1), 0.5),
+    _drop("bf16", 2, 2, 150, 200, 32, ("sliced", "block", 8, 256, 256), 0.1),
+    _drop("bf16", 2, 2, 150, 330, 16, ("none",), 0.25, site=7),
+    # the engine's call: causal, D = 64, q | k | v and dq | dk | dv views of one buffer each, the product's p
+    _drop("bf16", 2, 3, 300, 300, 64, ("causal",), 0.1, "qkv"),
+    _drop("f32", 2, 2, 269, 269, 64, ("causal",), 0.1, "qkv"),
+    # dropout together with the fused inverse RoPE of attn_bwd
+    _drop("bf16", 2, 2, 200, 200, 64, ("block", 8), 0.25, "qkv", table="shared", rope_off=7),
+    _drop("f32", 2, 2, 133, 133, 16, ("prefix", 16, 300), 0.5, "qkv", table="sample", rope_off=0),
+    # row numbers (b H + h) Nq + q past 2^16: the only thing that tells the masks of two rows apart
+    _drop("f32", 2, 3, 11100, 70, 8, ("none",), 0.5),
+]
+# the captured forward + backward of the GPU file's replay test: ~200 keys, the step word advanced on the device between the replays
+ATTN_DROP_GRAPH_CASE = _drop("bf16", 2, 2, 200, 200, 64, ("causal",), 0.25, step=41, site=4)
+
 
 # ------------------------------------------------------------------------------------------------ token-on-the-lane kernels
 # The shapes of tests/test_lane_kernels_gpu.py (csrc/mlp_fused.hip: mlp_up_fused_kernel, qkv_rope_fused_kernel, mlp_bwd_fused_kernel and
